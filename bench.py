@@ -1,6 +1,6 @@
 """bench.py - the BASELINE.json workloads through HipExecutionEngine on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config q1|join|strkey] [--sf SF]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config q1|join|strkey] [--sf SF] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default = the metric's own configuration: TPC-H Q1 (the reference's benchmark query, README.md:141-158) on synthetic
@@ -10,6 +10,10 @@ split across the ranks.  Rank 0 prints ONE JSON line (DESIGN.md section 6 explai
 
 ``--config join`` / ``--config strkey`` run BASELINE configs 4 and 5 (sf=10 by default) with the same JSON shape, their
 own byte accounting and their own C oracle ports (oracle/q45_oracle.c).
+
+``--dump-outputs DIR`` writes the rows the last timed step returned as DIR/<column>.npy (float64, in the order
+``collect()`` returned them; see dump_outputs) so that two builds can be compared output for output: the inputs are
+seeded, equal arguments give equal tables.
 """
 
 from __future__ import annotations
@@ -29,7 +33,7 @@ time.tzset()
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
-HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s)
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (8.0 TB/s)
 CUTOFF = "1998-12-01"  # the reference's query (README.md:141-158): TPC-H's last ship date, every row passes
 SELECTIVE_CUTOFF = "1998-09-02"  # SURVEY 8d's second cutoff: ~97 % of the rows pass (other_configs.q1_cutoff)
 Q1_MOVED_BYTES_PER_ROW = 25  # the length bytes of the fixed-width l_returnflag are never read
@@ -171,6 +175,60 @@ def q1_full_check(rows, total_rows: int, cutoff: str) -> dict:
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 0  # the fixed sample of rows kept when the whole result would exceed DUMP_MAX_BYTES
+
+
+def _dump_column(values: list):
+    """One result column as float64: numbers as they are (None -> NaN), timestamps as microseconds since the epoch,
+    strings as a (rows, longest UTF-8 length) matrix of their bytes, zero padded (None -> a row of NaN)."""
+    import numpy as np
+
+    from oracle import blockfile as bfio
+
+    if any(isinstance(v, str) for v in values):
+        raw = [None if v is None else v.encode() for v in values]
+        out = np.zeros((len(raw), max((len(b) for b in raw if b is not None), default=0)), dtype=np.float64)
+        for i, b in enumerate(raw):
+            if b is None:
+                out[i] = np.nan
+            else:
+                out[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+        return out
+    return np.array([np.nan if v is None else float(bfio.to_us(v)) if isinstance(v, datetime) else float(v)
+                     for v in values], dtype=np.float64)
+
+
+def dump_outputs(rows, out_dir: Path) -> dict:
+    """--dump-outputs: the rows a caller of the timed path received from its last step, one out_dir/<column>.npy per
+    result column, rows in the order collect() returned them.  A result larger than DUMP_MAX_BYTES is cut to a fixed
+    seeded sample of its rows (in their original order; out_dir/row_index.npy then says which)."""
+    import re
+
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rows = list(rows or [])
+    names = list(rows[0]) if rows else []
+    cols = {name: _dump_column([r[name] for r in rows]) for name in names}
+    row_bytes = sum(a[:1].nbytes for a in cols.values())
+    budget = DUMP_MAX_BYTES - 128 * (len(cols) + 1)  # .npy headers
+    keep, index = len(rows), None
+    if row_bytes * len(rows) > budget:
+        keep = budget // (row_bytes + 8)  # + the row index
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(rows), size=keep, replace=False))
+        cols = {name: a[index] for name, a in cols.items()}
+    files = []
+    for name, a in cols.items():
+        file = re.sub(r"[^A-Za-z0-9_.-]", "_", name) + ".npy"
+        np.save(out_dir / file, a)
+        files.append(file)
+    if index is not None:
+        np.save(out_dir / "row_index.npy", index.astype(np.float64))
+        files.append("row_index.npy")
+    return {"dir": str(out_dir), "files": files, "rows": len(rows), "rows_dumped": keep}
+
+
 def timed_steps(wl, engine, steps: int, warmup: int, dist):
     """W untimed + exactly K timed steps of one workload, bracketed by synchronise (+ barrier) on both sides; the MAX
     over the ranks.  -> (seconds for the K steps, dominant kernel ms per step, exchange ms per step, last rows).
@@ -179,8 +237,11 @@ def timed_steps(wl, engine, steps: int, warmup: int, dist):
     import torch
 
     frames = getattr(wl, "frames", None) or [wl.frame]
-    engine.dev.time_scan_kernel(True)
-    if dist is not None:
+    # the timing events are switched on once per engine and kept: the engine's recorded runs replay the handles of the
+    # events they were made with, and a later timed region of the same engine replays those recordings
+    if engine.dev.scan_events is None:
+        engine.dev.time_scan_kernel(True)
+    if dist is not None and engine.dev.exchange_events is None:
         engine.dev.time_exchange(True)
 
     def fence():
@@ -362,8 +423,14 @@ def main() -> None:
     ap.add_argument("--no-other-configs", action="store_true",
                     help="q1 on one GPU: do not run BASELINE configs 4 / 5 (sf=10) after the timed region")
     ap.add_argument("--cutoff", default=CUTOFF, help="q1: WHERE l_shipdate <= CUTOFF")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path, default=None,
+                    help="write the result rows of the last timed step as DIR/<column>.npy (float64)")
     ap.add_argument("--cold-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.sf is None:
         args.sf = 100.0 if args.config == "q1" else 10.0
     if args.cold_child:
@@ -435,6 +502,8 @@ def main() -> None:
             "whole_step_GBps_per_gpu": wl.algorithmic_bytes_per_launch() / (elapsed / args.steps) / 1e9,
         }
         out["cold"] = dict(wl.cold)
+        if args.dump_outputs is not None:
+            out["dump_outputs"] = dump_outputs(rows, args.dump_outputs)
         if not args.no_full_check:
             out["full_check"] = wl.full_check(rows)
         if world == 1 and dist is None and not args.no_cpu_baseline:

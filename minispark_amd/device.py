@@ -262,6 +262,9 @@ class Device:
         self.exchange_events = None
         self.exchange_begins_at_scan_end = False  # the slab exchange's begin event is the timed scan launch's end event
         self.join_events = None
+        # bumped whenever the timing events above are replaced or dropped: a recording replays the raw event handles it
+        # captured, so it is only valid for the events it was made with (part of the engine's recording key)
+        self.timing_epoch = 0
 
     def native_engine(self) -> Any:
         """The library's engine handle for this GPU (hs_engine_create): owner of the reader's pinned staging pool."""
@@ -276,6 +279,8 @@ class Device:
     def start_recording(self) -> Recording:
         self.rec = Recording()
         self.rec._free = self._raw_lib.hs_capture_free
+        # the launches capture the timing events' raw handles: the events must outlive every replay of the recording
+        self.rec.keep.append((self.scan_events, self.exchange_events, self.join_events))
         self.lib = _RecordingLib(self._raw_lib, self.rec)
         hs.check(self._raw_lib.hs_capture_begin(), "hs_capture_begin")
         return self.rec
@@ -317,6 +322,7 @@ class Device:
     def time_scan_kernel(self, enable: bool = True) -> None:
         """Bracket the main scan kernel of every following aggregate_partial with HIP events (recorded
         by the library on the launch stream); read with scan_kernel_ms() after a synchronise."""
+        self.timing_epoch += 1
         if enable:
             self.scan_events = [torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)]
             for ev in self.scan_events:
@@ -327,6 +333,7 @@ class Device:
     def time_exchange(self, enable: bool = True) -> None:
         """Bracket the exchange collective of every following query with events on the launch stream (bench.py's
         time split); read with exchange_ms() after a synchronise."""
+        self.timing_epoch += 1
         if enable:
             # [0], [1]: around the query's first exchange (slabs / the join's build side); [2], [3]: around a second one
             # (the unit tables of the fused join)
@@ -347,6 +354,7 @@ class Device:
     def time_join(self, enable: bool = True) -> None:
         """Bracket the in-place join operator (table build + probe) of every following query with events on the
         launch stream - recorded as part of the run, so replayed runs are timed too; read with join_ms()."""
+        self.timing_epoch += 1
         if enable:
             self.join_events = [torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)]
             for ev in self.join_events:

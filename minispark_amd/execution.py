@@ -456,7 +456,8 @@ class HipExecutionEngine(ExecutionEngine):
     def _switches(self) -> tuple:
         """The run-time switches a recording was made under (tests flip them between runs of one query)."""
         return (self.replay_enabled, self.short_tail_enabled, self.shared_tier_enabled, self.dict_enabled,
-                self.fused_join_enabled, self.fused_probe_enabled, self.sharded_build_enabled, self.dev.zero_copy_results)
+                self.fused_join_enabled, self.fused_probe_enabled, self.sharded_build_enabled, self.dev.zero_copy_results,
+                self.dev.timing_epoch)
 
     @staticmethod
     def _stamp_of(path: str) -> tuple:
@@ -476,7 +477,8 @@ class HipExecutionEngine(ExecutionEngine):
         return out
 
     def _recording_key(self, plan: Any) -> Any:
-        """A recorded run is valid for the same plan object over the same device buffers and capacities."""
+        """A recorded run is valid for the same plan object over the same device buffers and capacities, with the same
+        timing events (their handles are part of the recorded launches)."""
         tables = []
         scans = getattr(plan, "_hs_scan_keys", None)
         if scans is None:
@@ -487,7 +489,7 @@ class HipExecutionEngine(ExecutionEngine):
             t = self._tables.get(key)
             tables.append((_uid(t), tuple(sorted((cid, c.data.data_ptr()) for cid, c in t.columns.items()))) if t else None)
         return (_uid(plan), tuple(tables), self.group_cap_hint, self.merge_cap_hint, len(self._global_partial),
-                len(self._global_merge))
+                len(self._global_merge), self.dev.timing_epoch)
 
     def _replay(self, rec: Any) -> list[JobResult] | None:
         self.dev.last_scan = getattr(rec, "scan_info", None)

@@ -2,6 +2,7 @@
 (PythonExecutionEngine) - build container only; /root/reference does not exist on the GPU box.
 
     TZ=UTC python tests/golden/make_golden.py
+    TZ=UTC python tests/golden/make_golden.py --lowering   (lowering_reference_objects.json only)
 
 Writes, per case: the input BlockFiles exactly as the reference's own writer produced them
 (tests/golden/<case>.<table>.bin, data fixtures) and tests/golden/<case>.json holding the expected
@@ -115,5 +116,44 @@ def main() -> None:
         print(f"{case.name}: {len(out.get('rows', []))} rows {out.get('error', '')}")
 
 
+LOWERING_CASES = ["q1_multiblock", "join_group", "concat_like", "edge_minmax", "e2e_join_group_having"]
+
+
+def lowering_fixture() -> None:
+    """tests/golden/lowering_reference_objects.json: plan each case with the REAL reference's DataFrame + planner and
+    lower its task objects with minispark_amd.lowering (class-name dispatch) - per stage the consumer classes, per
+    pre-shuffle aggregate the program bytes and the aggregate -> accumulator map (tests/test_plan_lowering.py)."""
+    import copy
+
+    sys.path.insert(0, str(ROOT))
+    from minispark_amd import hipspark as hs
+    from minispark_amd.constants import ColumnType as T
+    from minispark_amd.lowering import lower_aggregate
+    from tests.conftest import load_golden
+    from tests.queries import api_namespace, case_by_name
+
+    df, ex, io, sql, tasks = import_reference()
+    out = {}
+    for name in LOWERING_CASES:
+        golden = load_golden(name)
+        ref_api = api_namespace(lambda: df.DataFrame(engine=object.__new__(ex.PythonExecutionEngine)), sql.Col,
+                                sql.Functions, sql.Lit)
+        plan = ex.PythonExecutionEngine().generate_physical_plan(copy.deepcopy(case_by_name(name).build(ref_api, golden["paths"]).task))
+        entry = {"consumers": [[type(t).__name__ for t in s.consumers] for s in plan.stages], "aggregates": []}
+        for s in plan.stages:
+            for rt in s.consumers:
+                if type(rt).__name__ == "AggregateTask" and rt.before_shuffle:
+                    in_schema = [(n, T[str(t)]) for n, t in rt.parent_task.inferred_schema]
+                    kinds = [{T.INTEGER: hs.I32, T.FLOAT: hs.F32, T.STRING: hs.STR, T.TIMESTAMP: hs.I64}[t] for _, t in in_schema]
+                    a = lower_aggregate(in_schema, kinds, [], rt.group_by_column, rt.agg_columns)
+                    entry["aggregates"].append({"program": a.program.to_bytes().hex(), "agg_to_acc": list(a.agg_to_acc)})
+        out[name] = entry
+        print(f"{name}: {len(entry['aggregates'])} pre-shuffle aggregate(s)")
+    (HERE / "lowering_reference_objects.json").write_text(json.dumps(out, indent=1) + "\n")
+
+
 if __name__ == "__main__":
-    main()
+    if "--lowering" in sys.argv:
+        lowering_fixture()
+    else:
+        main()

@@ -155,6 +155,33 @@ def test_replay_of_recorded_query_is_identical(setup):
     assert sum(r["count_order"] for r in other) < sum(r["count_order"] for r in runs[0])
 
 
+def test_replays_record_the_current_timing_events(setup):
+    """A recording replays the raw handles of the timing events it was made with.  Replacing the events (bench.py turns
+    scan timing on before every timed region) must retire it: the next run takes the full path, the run after records
+    again, and the replays then record the NEW pair - never the destroyed one."""
+    import torch
+
+    engine, path, _ = setup
+    dev = engine.dev
+    frame = _frame(engine, path, "1995-06-17")
+    dev.time_scan_kernel(True)
+    try:
+        runs = [frame.collect() for _ in range(3)]
+        replays = engine.replays
+        assert replays >= 1
+        dev.time_scan_kernel(True)
+        assert frame.collect() == runs[0] and engine.replays == replays, "replayed a recording made with other events"
+        assert frame.collect() == runs[0] and frame.collect() == runs[0] and engine.replays == replays + 1
+        mark = torch.cuda.Event(enable_timing=True)
+        mark.record()
+        assert frame.collect() == runs[0] and engine.replays == replays + 2
+        torch.cuda.synchronize()
+        assert mark.elapsed_time(dev.scan_events[0]) >= 0, "the replay did not record the current scan events"
+        assert dev.scan_kernel_ms() > 0
+    finally:
+        dev.time_scan_kernel(False)
+
+
 def test_trace_file_holds_query_stage_replay_and_kernel_slices(tmp_path):
     """HipExecutionEngine(trace_file=...) writes a Chrome-trace JSON (opens in ui.perfetto.dev): host spans per
     query / stage / replay and the scan kernel's HIP-event duration on a GPU track."""

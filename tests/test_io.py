@@ -97,13 +97,13 @@ def test_row_api_against_independent_oracle_codec(tmp_path):
     assert blocks[0][2][0] == np.float32(0.1)  # FLOAT survives as f32
 
 
-def test_quantisation_errors_match_reference():
+def test_quantisation_errors_match_reference(tmp_path):
     with pytest.raises(OverflowError):
-        BlockFile(Path("/tmp/x"), [("i", ColumnType.INTEGER)])._write_python_columns(([2**31],), [("i", ColumnType.INTEGER)])
+        BlockFile(tmp_path / "x", [("i", ColumnType.INTEGER)])._write_python_columns(([2**31],), [("i", ColumnType.INTEGER)])
     with pytest.raises(OverflowError):
-        BlockFile(Path("/tmp/x"), [("f", ColumnType.FLOAT)])._write_python_columns(([1e39],), [("f", ColumnType.FLOAT)])
+        BlockFile(tmp_path / "x", [("f", ColumnType.FLOAT)])._write_python_columns(([1e39],), [("f", ColumnType.FLOAT)])
     with pytest.raises(AssertionError):
-        BlockFile(Path("/tmp/x"), [("f", ColumnType.FLOAT)])._write_python_columns(([1],), [("f", ColumnType.FLOAT)])
+        BlockFile(tmp_path / "x", [("f", ColumnType.FLOAT)])._write_python_columns(([1],), [("f", ColumnType.FLOAT)])
     with pytest.raises(ValueError):
         StrCol.from_strings(["x" * 256])
 

@@ -1,11 +1,11 @@
 """Planner + lowering (host logic): stage shapes equal the reference's own plans (recorded in the golden
 fixtures by running the reference's planner), schema validation raises the reference's errors, and the
-lowering of a task tree built by the REAL reference equals the lowering of this package's mirror."""
+lowering of a task tree built by the REAL reference (recorded in tests/golden/lowering_reference_objects.json) equals
+the lowering of this package's mirror."""
 
 from __future__ import annotations
 
-import sys
-from pathlib import Path
+import json
 
 import pytest
 
@@ -15,7 +15,7 @@ from minispark_amd.dataframe import DataFrame
 from minispark_amd.lowering import LoweringError, ProgramBuilder, lower_aggregate
 from minispark_amd.plan import PhysicalPlan
 from minispark_amd.sql import Col, Functions as F, Lit
-from tests.conftest import load_golden
+from tests.conftest import GOLDEN, load_golden
 from tests.queries import CASES, api_namespace
 
 API = api_namespace(lambda: DataFrame(engine=object()), Col, F, Lit)
@@ -113,37 +113,27 @@ def test_lowering_type_rules():
     assert b.string_parts(Col("s") + "-" + Col("s")).parts == [("col", 2), ("lit", b"-"), ("col", 2)]
 
 
-REFERENCE = Path("/root/reference/src")
+LOWERED_REFERENCE_OBJECTS = json.loads((GOLDEN / "lowering_reference_objects.json").read_text())
 
 
-@pytest.mark.skipif(not REFERENCE.exists(), reason="the reference is only present in the build container")
-@pytest.mark.parametrize("name", ["q1_multiblock", "join_group", "concat_like", "edge_minmax", "e2e_join_group_having"])
+@pytest.mark.parametrize("name", sorted(LOWERED_REFERENCE_OBJECTS))
 def test_reference_objects_lower_to_the_same_programs(name):
-    """Drop-in check: plan the query with the REAL reference's DataFrame + planner, lower its task objects
-    with minispark_amd.lowering (class-name dispatch) and compare with the mirror's programs byte for byte."""
-    sys.path.insert(0, str(Path(__file__).resolve().parent / "golden"))
-    import make_golden
-
-    df, ex, io, sql, tasks = make_golden.import_reference()
+    """Drop-in check: the query planned with the REAL reference's DataFrame + planner, its task objects lowered with
+    minispark_amd.lowering (class-name dispatch; recorded by tests/golden/make_golden.py --lowering), against the
+    mirror's plan and programs byte for byte."""
     from tests.queries import case_by_name
 
-    case = case_by_name(name)
+    ref = LOWERED_REFERENCE_OBJECTS[name]
     golden = load_golden(name)
-    ref_api = api_namespace(lambda: df.DataFrame(engine=object.__new__(ex.PythonExecutionEngine)), sql.Col, sql.Functions, sql.Lit)
-    import copy
-
-    ref_plan = ex.PythonExecutionEngine().generate_physical_plan(copy.deepcopy(case.build(ref_api, golden["paths"]).task))
-    own_plan = PhysicalPlan.generate_physical_plan(case.build(API, golden["paths"]).task)
-    assert len(ref_plan.stages) == len(own_plan.stages)
-    compared = 0
-    for rs, os_ in zip(ref_plan.stages, own_plan.stages):
-        for rt, ot in zip(rs.consumers, os_.consumers):
-            assert type(rt).__name__ == type(ot).__name__
-            if type(rt).__name__ == "AggregateTask" and rt.before_shuffle:
-                in_schema = [(n, T[str(t)]) for n, t in rt.parent_task.inferred_schema]
-                kinds = [{T.INTEGER: hs.I32, T.FLOAT: hs.F32, T.STRING: hs.STR, T.TIMESTAMP: hs.I64}[t] for _, t in in_schema]
-                a = lower_aggregate(in_schema, kinds, [], rt.group_by_column, rt.agg_columns)
+    own_plan = PhysicalPlan.generate_physical_plan(case_by_name(name).build(API, golden["paths"]).task)
+    assert [[type(t).__name__ for t in s.consumers] for s in own_plan.stages] == ref["consumers"]
+    own = []
+    for s in own_plan.stages:
+        for ot in s.consumers:
+            if type(ot).__name__ == "AggregateTask" and ot.before_shuffle:
+                kinds = [{T.INTEGER: hs.I32, T.FLOAT: hs.F32, T.STRING: hs.STR, T.TIMESTAMP: hs.I64}[t]
+                         for _, t in ot.parent_task.inferred_schema]
                 b = lower_aggregate(ot.parent_task.inferred_schema, kinds, [], ot.group_by_column, ot.agg_columns)
-                assert a.program.to_bytes() == b.program.to_bytes() and a.agg_to_acc == b.agg_to_acc
-                compared += 1
-    assert compared >= 1
+                own.append({"program": b.program.to_bytes().hex(), "agg_to_acc": list(b.agg_to_acc)})
+    assert own == ref["aggregates"]
+    assert len(own) >= 1

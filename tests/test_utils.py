@@ -76,3 +76,32 @@ def test_committed_pmc_traffic_belongs_to_the_current_scan_kernel_sources():
     if got["traffic"] is None:
         pytest.skip(got["traffic_source"])
     assert 0.9 * 26 * 600_037_902 < got["traffic"] < 1.1 * 26 * 600_037_902
+
+
+def test_bench_dump_outputs_writes_the_rows_as_float_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float64 .npy per result column, rows in the order given; strings as their bytes;
+    a result over the size cap becomes the same seeded sample of rows every time, with the row index beside it."""
+    from datetime import datetime
+
+    import numpy as np
+
+    import bench
+
+    rows = [{"flag": "A", "sum": 1.5, "n": 3, "day": datetime(1998, 12, 1)},
+            {"flag": "NO", "sum": None, "n": 4, "day": datetime(1970, 1, 1)}]
+    got = bench.dump_outputs(rows, tmp_path / "all")
+    assert got["files"] == ["flag.npy", "sum.npy", "n.npy", "day.npy"] and got["rows_dumped"] == 2
+    arrays = {f: np.load(tmp_path / "all" / f) for f in got["files"]}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert arrays["flag.npy"].tolist() == [[ord("A"), 0], [ord("N"), ord("O")]]
+    assert arrays["sum.npy"][0] == 1.5 and np.isnan(arrays["sum.npy"][1])
+    assert arrays["n.npy"].tolist() == [3, 4] and arrays["day.npy"].tolist() == [912470400e6, 0]
+
+    many = [{"k": f"x{i}", "v": float(i)} for i in range(1000)]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8192)
+    a, b = bench.dump_outputs(many, tmp_path / "a"), bench.dump_outputs(many, tmp_path / "b")
+    assert a["rows"] == 1000 and 0 < a["rows_dumped"] < 1000 and a["files"][-1] == "row_index.npy"
+    assert sum((tmp_path / "a" / f).stat().st_size for f in a["files"]) <= 8192
+    idx = np.load(tmp_path / "a" / "row_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "row_index.npy")) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "v.npy"), idx)
