@@ -144,7 +144,8 @@ typedef struct hs_agg_spec {
 const char* hs_last_error(void);
 int hs_version(void);
 /* sizeof() of ABI structure `which` as compiled: 0 hs_col, 1 hs_program, 2 hs_agg_spec, 3 hs_agg_geom, 4 hs_chunk,
- * 5 hs_slab_desc, 6 hs_finish_out, 7 hs_finish_spec, 8 hs_stage_plan, 9 hs_result_col, 10 hs_join8, 11 hs_join_stage_plan, 12 hs_select_stage_plan
+ * 5 hs_slab_desc, 6 hs_finish_out, 7 hs_finish_spec, 8 hs_stage_plan, 9 hs_result_col, 10 hs_join8, 11 hs_join_stage_plan, 12 hs_select_stage_plan,
+ * 14 hs_join_select_stage_plan (13 stays unassigned: it returns 0, the end of the round-4 list)
  * (0 for anything else) - lets a
  * binding verify its mirror. */
 size_t hs_sizeof(int32_t which);
@@ -449,6 +450,29 @@ int hs_join_hash_build(void* stream, const int32_t* build_keys, int64_t n_build,
                        uint32_t* list_count, void* ws, uint32_t* flags);
 int hs_join_hash_count(void* stream, const int32_t* probe_keys, int64_t n_probe, int64_t n_build, const void* table,
                        const uint32_t* rows, const uint32_t* list_count, int64_t* counts, void* aux);
+/* ---- the general inner join on STRING keys (round 5; csrc/hs_radix.hip) ----------------------------------------------------
+ * The hashed form above for STRING keys of any length (0 .. 255 bytes; the BlockFile's limit).  A key's hash is
+ * m = fmix64(h), h the 64-bit FNV-1a of its bytes (offset basis 0xcbf29ce484222325, prime 0x100000001b3 - the shuffle's
+ * string hash) and fmix64 MurmurHash3's finaliser (x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33;
+ * x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33): the HIGH 32 bits of m pick the window, ((m >> 32) * windows) >> 32 with windows =
+ * hs_join_hash_str_slots(n_build) / window size; the LOW 32 bits of m are the fingerprint stored in the slot, and
+ * fingerprint & (window size - 1) is the slot the key starts probing from.
+ * table = hs_join_hash_str_slots(n_build) 8-byte slots {fingerprint, word}, the word as in the dense form; windows of 512 slots
+ * (1024 past 19 M build rows) as in hs_join_hash_*.  A fingerprint never decides a match alone: the build compares the bytes
+ * of a key whose fingerprint it meets again with the slot's first key (two different keys of one fingerprint in one window take
+ * two slots), the probe compares the probe key with the first build row of the slot's list (length, then bytes) and probes on
+ * inside the window on a mismatch.  Build: hash pass, two stable partition passes of (window, row, fingerprint) tuples, one
+ * wave per window assembling it in LDS, coalesced stores - no global atomic; every list ascending in build row.  The second
+ * pass of the probe is hs_join_dense_fill(rows, aux, ...): counts / aux are left exactly as hs_join_dense_count leaves them.
+ * *status receives HS_FLAG_DICT_FULL only - a window met more distinct keys than slots and was left empty: the caller takes
+ * hs_join_build instead; any other inconsistency is OR-ed into *flags (device) and is an error.  n_build <= ~38 M rows
+ * (hs_join_hash_str_slots returns 0 beyond).  rows / list_count: n_build entries each; ws: hs_join_hash_str_ws_bytes(n_build). */
+size_t hs_join_hash_str_ws_bytes(int64_t n_build);
+int64_t hs_join_hash_str_slots(int64_t n_build); /* 0 = this size is not held */
+int hs_join_hash_str_build(void* stream, const hs_col* build_key, int64_t n_build, void* table, uint32_t* rows, uint32_t* list_count,
+                           void* ws, uint32_t* status, uint32_t* flags);
+int hs_join_hash_str_count(void* stream, const hs_col* build_key, const hs_col* probe_key, int64_t n_probe, int64_t n_build,
+                           const void* table, const uint32_t* rows, const uint32_t* list_count, int64_t* counts, void* aux);
 /* Merge order of a multi-rank final aggregate (the reference reads a partition's shuffle files in block order,
  * tasks.py:117-133): STABLE sort of positions 0 .. n-1 by order[i] in [-1, n_order) (global block id; -1 = padding,
  * sorted first) with the radix tier's partition passes, least significant byte first.  out_perm[j] = position of the
@@ -897,6 +921,47 @@ int hs_select_stage_prepare(hs_engine* engine, hs_table* table, const hs_select_
 int hs_select_stage_run(hs_select_stage* stage, void* stream, uint32_t* flags_out, int64_t* n_rows_out);
 int hs_select_result_write_blockfile(const hs_select_stage* stage, const char* path, int64_t rows_per_block);
 void hs_select_stage_destroy(hs_select_stage* stage);
+
+/* ---- the JOIN-to-rows stage behind the same boundary (round 5) ----------------------------------------------------------
+ * A JoinJob whose rows go to the result file (jobs.py:45-79; BroadcastHashJoinTask tasks.py:201-240, WriteToLocalFileTask
+ * tasks.py:391-410): both tables through the native reader (only the named columns), a WHERE per side (hs_eval + hs_compact;
+ * the lowering pushes every one-side conjunct to its side, which keeps the row order), the probe rows ordered by JoinJob -
+ * hs_partition_ids / hs_partition_perm by hash(key) % n_parts, the fixed FNV-1a for strings - then the join: INTEGER keys
+ * through hs_join_dense_* (key range <= 4 x build rows), else hs_join_hash_*, STRING keys through hs_join_hash_str_*, and
+ * hs_join_build / count / fill when a window overflows or the size is not held; pairs ordered by partition, probe row, build
+ * row - the engine's order.  Every output column (either side, strings included) is gathered through the pair lists and held
+ * on the host; hs_join_select_result_write_blockfile writes it as blocks of rows_per_block rows (no file for no rows).  The
+ * output size depends on the data, so runs are not replayed: a second run recomputes the same rows.  HS_E_LIMIT: key columns
+ * of other or different kinds. */
+typedef struct hs_join_select_stage hs_join_select_stage;
+#define HS_JOIN_SELECT_STAGE_PLAN_VERSION 1
+typedef struct hs_join_select_stage_plan {
+    int32_t version;                          /* HS_JOIN_SELECT_STAGE_PLAN_VERSION */
+    int32_t build_key_col, probe_key_col;     /* both INTEGER or both STRING */
+    int32_t n_parts;                          /* JoinJobs (the reference's SHUFFLE_PARTITIONS, 10) */
+    int32_t n_bcols;                          /* column slots of build_filter */
+    int32_t bcol_ids[HS_MAX_COLS];            /* slot -> build table column */
+    hs_program build_filter;                  /* one HS_OP_OUT 0 = the build row survives; n_ins 0 = no WHERE */
+    int32_t n_pcols;
+    int32_t pcol_ids[HS_MAX_COLS];            /* slot -> probe table column */
+    hs_program probe_filter;
+    int32_t n_out;
+    int32_t out_side[HS_FINISH_MAX_OUT];      /* 0 build table, 1 probe table */
+    int32_t out_col[HS_FINISH_MAX_OUT];       /* table column, passed through as stored */
+    int32_t out_types[HS_FINISH_MAX_OUT];     /* BlockFile type code of every result column */
+    char out_names[HS_FINISH_MAX_OUT][64];
+} hs_join_select_stage_plan;
+#define HS_JOIN_ROUTE_DENSE 1       /* hs_join_dense_* */
+#define HS_JOIN_ROUTE_HASH 2        /* hs_join_hash_* */
+#define HS_JOIN_ROUTE_HASH_STR 3    /* hs_join_hash_str_* */
+#define HS_JOIN_ROUTE_GLOBAL 4      /* hs_join_build / count / fill */
+int hs_join_select_stage_prepare(hs_engine* engine, hs_table* build, hs_table* probe, const hs_join_select_stage_plan* plan,
+                                 size_t plan_bytes, hs_join_select_stage** out);
+int hs_join_select_stage_run(hs_join_select_stage* stage, void* stream, uint32_t* flags_out, int64_t* n_rows_out);
+/* stats[5]: runs, rows of the last run, route of the last run (HS_JOIN_ROUTE_*), build rows and probe rows after the WHERE */
+int hs_join_select_stage_stats(const hs_join_select_stage* stage, int64_t* stats);
+int hs_join_select_result_write_blockfile(const hs_join_select_stage* stage, const char* path, int64_t rows_per_block);
+void hs_join_select_stage_destroy(hs_join_select_stage* stage);
 
 /* =================================================================================================
  * Launch capture: the native replay of a recorded query (reference: the Zig worker re-runs its compiled plan per job,

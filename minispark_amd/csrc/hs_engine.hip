@@ -1973,3 +1973,386 @@ extern "C" int hs_select_result_write_blockfile(const hs_select_stage* s, const 
     }
     return HS_OK;
 }
+
+// =====================================================================================================================
+// Round 5: the JOIN-to-rows stage behind the same boundary - a JoinJob whose rows go to the result file (jobs.py:45-79;
+// BroadcastHashJoinTask tasks.py:201-240, WriteToLocalFileTask tasks.py:391-410), the engine's _join end to end: native
+// reader for both tables -> WHERE per side (hs_eval + hs_compact) -> probe rows in JoinJob order (hs_partition_ids /
+// hs_partition_perm) -> join (dense / hashed INTEGER, hashed STRING windows, or the global table) -> pair lists -> gathers
+// of every output column through them -> host -> BlockFile blocks of rows_per_block rows.
+// =====================================================================================================================
+namespace {
+
+__global__ void __launch_bounds__(256) k_js_iota(int64_t* out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = i;
+}
+
+struct HostCol {  // one result column on the host: fixed-width values, or lens + payload (width -1)
+    std::vector<uint8_t> data, lens;
+    int width = 0;
+};
+
+int grid_of(int64_t n) {
+    const int64_t g = (n + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+bool read_i64(hipStream_t stream, const void* dev, int64_t& out) {
+    return hipMemcpyAsync(&out, dev, 8, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+}
+
+// the rows of one side the WHERE keeps, ascending (every row without a WHERE) -> rows (int64), n_kept
+int side_rows(hipStream_t stream, const hs_col* cols, int32_t n_cols, const hs_program& filter, int64_t n, DevBuf& rows,
+              int64_t& kept, uint32_t* flags) {
+    kept = n;
+    if (!rows.alloc((size_t)(n > 0 ? n : 1) * 8)) return HS_E_LAUNCH;
+    if (n == 0) return HS_OK;
+    if (filter.n_ins == 0) {
+        hipLaunchKernelGGL(k_js_iota, dim3(grid_of(n)), dim3(256), 0, stream, (int64_t*)rows.p, n);
+        return hipGetLastError() == hipSuccess ? HS_OK : HS_E_LAUNCH;
+    }
+    DevBuf mask, count, ws;
+    if (!mask.alloc((size_t)n) || !count.alloc(8) || !ws.alloc(hs_scan_ws_bytes(n))) return HS_E_LAUNCH;
+    void* outs[1] = {mask.p};
+    const int32_t kinds[1] = {HS_U8};
+    int rc = hs_eval(stream, cols, n_cols, &filter, nullptr, n, nullptr, outs, kinds, 1, flags);
+    if (!rc) rc = hs_compact(stream, (const uint8_t*)mask.p, n, (int64_t*)rows.p, (int64_t*)count.p, ws.p);
+    if (rc) return rc;
+    return read_i64(stream, count.p, kept) ? HS_OK : HS_E_LAUNCH;
+}
+
+// column c at rows idx[0 .. n) as a new device column (strings: lens, offsets, payload); out describes it
+int gather_col(hipStream_t stream, const hs_col& c, int64_t src_rows, const int64_t* idx, int64_t n, DevBuf& data, DevBuf& lens,
+               DevBuf& offs, hs_col& out, int64_t& payload, uint32_t* flags) {
+    payload = 0;
+    if (c.kind != HS_STR) {
+        const int w = elem_bytes(c.kind);
+        if (!data.alloc((size_t)(n > 0 ? n : 1) * (size_t)w)) return HS_E_LAUNCH;
+        out = hs_col{c.kind, -1, data.p, nullptr, nullptr};
+        return n > 0 ? hs_gather_fixed(stream, c.data, w, src_rows, idx, n, nullptr, data.p, flags) : HS_OK;
+    }
+    DevBuf mm, ws;
+    if (!lens.alloc((size_t)(n > 0 ? n : 1)) || !offs.alloc((size_t)(n + 1) * 8, true) || !mm.alloc(8)) return HS_E_LAUNCH;
+    if (n > 0) {
+        if (!ws.alloc(hs_scan_ws_bytes(n))) return HS_E_LAUNCH;
+        int rc = hs_gather_str_lens(stream, &c, src_rows, idx, n, (uint8_t*)lens.p, flags);
+        if (!rc) rc = hs_str_offsets(stream, (const uint8_t*)lens.p, n, (int64_t*)offs.p, (int32_t*)mm.p, ws.p);
+        if (rc) return rc;
+        if (!read_i64(stream, (const int64_t*)offs.p + n, payload)) return HS_E_LAUNCH;
+    }
+    if (!data.alloc((size_t)(payload > 0 ? payload : 1))) return HS_E_LAUNCH;
+    out = hs_col{HS_STR, -1, data.p, (const uint8_t*)lens.p, (const int64_t*)offs.p};
+    return n > 0 ? hs_gather_str_bytes(stream, &c, src_rows, idx, n, (const int64_t*)offs.p, (uint8_t*)data.p) : HS_OK;
+}
+
+}  // namespace
+
+struct hs_join_select_stage {
+    hs_engine* engine = nullptr;
+    hs_table *build = nullptr, *probe = nullptr;
+    hs_join_select_stage_plan plan{};
+    hs_col bcols[HS_MAX_COLS]{}, pcols[HS_MAX_COLS]{};
+    std::vector<HostCol> outs;
+    int64_t runs = 0, last_rows = 0, route = 0, n_build = 0, n_probe = 0;
+};
+
+extern "C" int hs_join_select_stage_prepare(hs_engine* e, hs_table* build, hs_table* probe, const hs_join_select_stage_plan* plan,
+                                            size_t plan_bytes, hs_join_select_stage** out) {
+    if (!e || !build || !probe || !plan || !out || plan_bytes != sizeof(hs_join_select_stage_plan) ||
+        plan->version != HS_JOIN_SELECT_STAGE_PLAN_VERSION || plan->n_bcols < 0 || plan->n_bcols > HS_MAX_COLS || plan->n_pcols < 0 ||
+        plan->n_pcols > HS_MAX_COLS || plan->n_out < 1 || plan->n_out > HS_FINISH_MAX_OUT || plan->n_parts < 1 || plan->n_parts > 255) {
+        hs_set_error("hs_join_select_stage_prepare: bad plan blob (size %zu, expected %zu)", plan_bytes, sizeof(hs_join_select_stage_plan));
+        return HS_E_ARG;
+    }
+    std::vector<int32_t> need[2];
+    need[0].assign(plan->bcol_ids, plan->bcol_ids + plan->n_bcols);
+    need[1].assign(plan->pcol_ids, plan->pcol_ids + plan->n_pcols);
+    need[0].push_back(plan->build_key_col);
+    need[1].push_back(plan->probe_key_col);
+    for (int o = 0; o < plan->n_out; ++o) {
+        if (plan->out_side[o] != 0 && plan->out_side[o] != 1) {
+            hs_set_error("hs_join_select_stage_prepare: output %d names no side", o);
+            return HS_E_ARG;
+        }
+        need[plan->out_side[o]].push_back(plan->out_col[o]);
+    }
+    hs_table* tables[2] = {build, probe};
+    for (int side = 0; side < 2; ++side)
+        for (int32_t c : need[side])
+            if (c < 0 || c >= (int)tables[side]->cols.size()) {
+                hs_set_error("hs_join_select_stage_prepare: no such column %d in the %s table", c, side ? "probe" : "build");
+                return HS_E_ARG;
+            }
+    const int32_t bt = build->cols[plan->build_key_col].type, pt = probe->cols[plan->probe_key_col].type;
+    if (bt != pt || (bt != 0 && bt != 1)) {
+        hs_set_error("hs_join_select_stage_prepare: join keys must be both INTEGER or both STRING (types %d, %d)", bt, pt);
+        return HS_E_LIMIT;
+    }
+    if (hipSetDevice(e->device) != hipSuccess) return HS_E_LAUNCH;
+    for (int side = 0; side < 2; ++side) {
+        const int rc = hs_table_load(e, tables[side], need[side].data(), (int32_t)need[side].size());
+        if (rc) return rc;
+    }
+    hs_join_select_stage* s = new hs_join_select_stage();
+    s->engine = e;
+    s->build = build;
+    s->probe = probe;
+    s->plan = *plan;
+    for (int i = 0; i < plan->n_bcols; ++i) s->bcols[i] = build->cols[plan->bcol_ids[i]].col;
+    for (int i = 0; i < plan->n_pcols; ++i) s->pcols[i] = probe->cols[plan->pcol_ids[i]].col;
+    *out = s;
+    return HS_OK;
+}
+
+extern "C" void hs_join_select_stage_destroy(hs_join_select_stage* s) { delete s; }
+
+namespace {
+
+// The join of the compacted key columns (build positions 0 .. nb, probe positions 0 .. np in JoinJob order) -> out_start
+// [np + 1], pair lists out_left / out_right (positions), n_out; route: HS_JOIN_ROUTE_*.
+struct JoinPairs {
+    DevBuf out_start, out_left, out_right;
+    int64_t n_out = 0;
+    int route = 0;
+};
+
+int join_pairs(hipStream_t stream, const hs_col& bk, int64_t nb, const hs_col& pk, int64_t np, uint32_t* flags, JoinPairs& J) {
+    DevBuf counts, aux, scan_ws, rows32, lcount, table, ws, status;
+    if (!counts.alloc((size_t)np * 8) || !J.out_start.alloc((size_t)(np + 1) * 8) || !scan_ws.alloc(hs_scan_ws_bytes(np)) ||
+        !aux.alloc(hs_join_dense_aux_bytes(np)) || !rows32.alloc((size_t)nb * 4) || !lcount.alloc((size_t)nb * 4) || !status.alloc(4, true))
+        return HS_E_LAUNCH;
+    int rc = HS_OK;
+    int route = 0;
+    if (bk.kind == HS_I32) {
+        DevBuf mm;
+        int32_t lohi[2] = {0, 0};
+        if (!mm.alloc(8)) return HS_E_LAUNCH;
+        rc = hs_minmax_i32(stream, (const int32_t*)bk.data, nb, (int32_t*)mm.p);
+        if (rc) return rc;
+        if (hipMemcpyAsync(lohi, mm.p, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+            return HS_E_LAUNCH;
+        // Device._join_indices_dense's rule: at most 32 slots per build row (+ 65 536) and 4 build rows per slot
+        const int64_t slots = (int64_t)lohi[1] - (int64_t)lohi[0] + 1;
+        const int64_t spread = 32 * nb + 65536;
+        const size_t dws = slots <= ((int64_t)1 << 29) && slots <= spread && slots * 4 >= nb ? hs_join_dense_ws_bytes(nb, slots) : 0;
+        if (dws) {
+            if (!table.alloc((size_t)slots * 4) || !ws.alloc(dws)) return HS_E_LAUNCH;
+            rc = hs_join_dense_build(stream, (const int32_t*)bk.data, nb, lohi[0], slots, (uint32_t*)table.p, (uint32_t*)rows32.p,
+                                     (uint32_t*)lcount.p, ws.p, flags);
+            if (!rc) rc = hs_join_dense_count(stream, (const int32_t*)pk.data, np, lohi[0], slots, (const uint32_t*)table.p,
+                                              (const uint32_t*)rows32.p, (const uint32_t*)lcount.p, (int64_t*)counts.p, aux.p);
+            if (rc) return rc;
+            route = HS_JOIN_ROUTE_DENSE;
+        } else if (hs_join_hash_slots(nb) > 0) {
+            if (!table.alloc((size_t)hs_join_hash_slots(nb) * 8) || !ws.alloc(hs_join_hash_ws_bytes(nb))) return HS_E_LAUNCH;
+            rc = hs_join_hash_build(stream, (const int32_t*)bk.data, nb, table.p, (uint32_t*)rows32.p, (uint32_t*)lcount.p, ws.p,
+                                    (uint32_t*)status.p);
+            if (!rc) rc = hs_join_hash_count(stream, (const int32_t*)pk.data, np, nb, table.p, (const uint32_t*)rows32.p,
+                                             (const uint32_t*)lcount.p, (int64_t*)counts.p, aux.p);
+            if (rc) return rc;
+            route = HS_JOIN_ROUTE_HASH;
+        }
+    } else if (hs_join_hash_str_slots(nb) > 0) {
+        if (!table.alloc((size_t)hs_join_hash_str_slots(nb) * 8) || !ws.alloc(hs_join_hash_str_ws_bytes(nb))) return HS_E_LAUNCH;
+        rc = hs_join_hash_str_build(stream, &bk, nb, table.p, (uint32_t*)rows32.p, (uint32_t*)lcount.p, ws.p, (uint32_t*)status.p, flags);
+        if (!rc) rc = hs_join_hash_str_count(stream, &bk, &pk, np, nb, table.p, (const uint32_t*)rows32.p, (const uint32_t*)lcount.p,
+                                             (int64_t*)counts.p, aux.p);
+        if (rc) return rc;
+        route = HS_JOIN_ROUTE_HASH_STR;
+    }
+    if (route) {
+        uint32_t st = 0;
+        if (hipMemcpyAsync(&st, status.p, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+            return HS_E_LAUNCH;
+        if (st & HS_FLAG_DICT_FULL) route = 0;  // a window overflowed: the global table takes this build side
+    }
+    if (route) {
+        rc = hs_exclusive_scan_i64(stream, (const int64_t*)counts.p, np, (int64_t*)J.out_start.p, scan_ws.p);
+        if (rc) return rc;
+        if (!read_i64(stream, (const int64_t*)J.out_start.p + np, J.n_out)) return HS_E_LAUNCH;
+        if (!J.out_left.alloc((size_t)(J.n_out > 0 ? J.n_out : 1) * 8) || !J.out_right.alloc((size_t)(J.n_out > 0 ? J.n_out : 1) * 8))
+            return HS_E_LAUNCH;
+        if (J.n_out > 0)
+            rc = hs_join_dense_fill(stream, np, (const uint32_t*)rows32.p, aux.p, (const int64_t*)J.out_start.p, (int64_t*)J.out_left.p,
+                                    (int64_t*)J.out_right.p);
+        J.route = route;
+        return rc;
+    }
+    // the global-memory table (tasks.py:201-240 as round 1 built it): any key kind and size
+    int64_t cap = 16;
+    while (cap < 2 * nb) cap *= 2;
+    DevBuf tkeys, treps, slot_start, rows64;
+    if (!tkeys.alloc((size_t)cap * 8) || !treps.alloc((size_t)cap * 8) || !slot_start.alloc((size_t)(cap + 1) * 8) ||
+        !rows64.alloc((size_t)nb * 8) || !ws.alloc(hs_join_build_ws_bytes(nb, cap)))
+        return HS_E_LAUNCH;
+    rc = hs_join_build(stream, &bk, nb, cap, (uint64_t*)tkeys.p, (int64_t*)treps.p, (int64_t*)slot_start.p, (int64_t*)rows64.p, ws.p, flags);
+    if (!rc) rc = hs_join_count(stream, &bk, &pk, np, cap, (const uint64_t*)tkeys.p, (const int64_t*)treps.p, (const int64_t*)slot_start.p,
+                                (int64_t*)counts.p);
+    if (!rc) rc = hs_exclusive_scan_i64(stream, (const int64_t*)counts.p, np, (int64_t*)J.out_start.p, scan_ws.p);
+    if (rc) return rc;
+    if (!read_i64(stream, (const int64_t*)J.out_start.p + np, J.n_out)) return HS_E_LAUNCH;
+    if (!J.out_left.alloc((size_t)(J.n_out > 0 ? J.n_out : 1) * 8) || !J.out_right.alloc((size_t)(J.n_out > 0 ? J.n_out : 1) * 8))
+        return HS_E_LAUNCH;
+    if (J.n_out > 0)
+        rc = hs_join_fill(stream, &bk, &pk, np, cap, (const uint64_t*)tkeys.p, (const int64_t*)treps.p, (const int64_t*)slot_start.p,
+                          (const int64_t*)rows64.p, (const int64_t*)J.out_start.p, (int64_t*)J.out_left.p, (int64_t*)J.out_right.p);
+    J.route = HS_JOIN_ROUTE_GLOBAL;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int hs_join_select_stage_run(hs_join_select_stage* s, void* stream_, uint32_t* flags_out, int64_t* n_rows_out) {
+    if (!s) {
+        hs_set_error("hs_join_select_stage_run: null stage");
+        return HS_E_ARG;
+    }
+    if (hipSetDevice(s->engine->device) != hipSuccess) return HS_E_LAUNCH;
+    hipStream_t stream = (hipStream_t)stream_;
+    const hs_join_select_stage_plan& P = s->plan;
+    uint32_t* flags = (uint32_t*)s->engine->flags.p;
+    if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
+    const int64_t nb_all = s->build->nrows, np_all = s->probe->nrows;
+    const hs_col& bkey = s->build->cols[P.build_key_col].col;
+    const hs_col& pkey = s->probe->cols[P.probe_key_col].col;
+    // 1. WHERE per side
+    DevBuf brows, prows;
+    int64_t nb = 0, np = 0;
+    int rc = side_rows(stream, s->bcols, P.n_bcols, P.build_filter, nb_all, brows, nb, flags);
+    if (!rc) rc = side_rows(stream, s->pcols, P.n_pcols, P.probe_filter, np_all, prows, np, flags);
+    if (rc) return rc;
+    // 2. probe rows in JoinJob order: partition ids of the surviving rows, a stable counting sort, the row ids through it
+    DevBuf part, perm, pstart, pws, porder;
+    if (!porder.alloc((size_t)(np > 0 ? np : 1) * 8)) return HS_E_LAUNCH;
+    if (np > 0) {
+        if (!part.alloc((size_t)np) || !perm.alloc((size_t)np * 8) || !pstart.alloc((size_t)(P.n_parts + 1) * 8) ||
+            !pws.alloc(hs_partition_ws_bytes(np, P.n_parts)))
+            return HS_E_LAUNCH;
+        rc = hs_partition_ids(stream, &pkey, (const int64_t*)prows.p, np, P.n_parts, (uint8_t*)part.p);
+        if (!rc) rc = hs_partition_perm(stream, (const uint8_t*)part.p, np, P.n_parts, (int64_t*)perm.p, (int64_t*)pstart.p, pws.p);
+        if (!rc) rc = hs_gather_fixed(stream, prows.p, 8, np, (const int64_t*)perm.p, np, nullptr, porder.p, flags);
+        if (rc) return rc;
+    }
+    // 3. the join over the key columns of the surviving rows
+    JoinPairs J;
+    if (nb > 0 && np > 0) {
+        DevBuf bk_data, bk_lens, bk_offs, pk_data, pk_lens, pk_offs;
+        hs_col bk{}, pk{};
+        int64_t payload = 0;
+        rc = gather_col(stream, bkey, nb_all, (const int64_t*)brows.p, nb, bk_data, bk_lens, bk_offs, bk, payload, flags);
+        if (!rc) rc = gather_col(stream, pkey, np_all, (const int64_t*)porder.p, np, pk_data, pk_lens, pk_offs, pk, payload, flags);
+        if (!rc) rc = join_pairs(stream, bk, nb, pk, np, flags, J);
+        if (rc) return rc;
+    }
+    // 4. table rows of every pair, then every output column through them -> host
+    const int64_t n_out = J.n_out;
+    DevBuf bidx, pidx;
+    if (n_out > 0) {
+        if (!bidx.alloc((size_t)n_out * 8) || !pidx.alloc((size_t)n_out * 8)) return HS_E_LAUNCH;
+        rc = hs_gather_fixed(stream, brows.p, 8, nb, (const int64_t*)J.out_left.p, n_out, nullptr, bidx.p, flags);
+        if (!rc) rc = hs_gather_fixed(stream, porder.p, 8, np, (const int64_t*)J.out_right.p, n_out, nullptr, pidx.p, flags);
+        if (rc) return rc;
+    }
+    s->outs.assign((size_t)P.n_out, HostCol());
+    for (int o = 0; o < P.n_out && n_out > 0; ++o) {
+        hs_table* t = P.out_side[o] ? s->probe : s->build;
+        const hs_col& c = t->cols[P.out_col[o]].col;
+        DevBuf data, lens, offs;
+        hs_col g{};
+        int64_t payload = 0;
+        rc = gather_col(stream, c, t->nrows, (const int64_t*)(P.out_side[o] ? pidx.p : bidx.p), n_out, data, lens, offs, g, payload, flags);
+        if (rc) return rc;
+        HostCol& out = s->outs[(size_t)o];
+        if (c.kind != HS_STR) {
+            out.width = elem_bytes(c.kind);
+            out.data.resize((size_t)n_out * (size_t)out.width);
+        } else {
+            out.width = -1;
+            out.lens.resize((size_t)n_out);
+            out.data.resize((size_t)payload);
+            if (hipMemcpyAsync(out.lens.data(), lens.p, (size_t)n_out, hipMemcpyDeviceToHost, stream) != hipSuccess) return HS_E_LAUNCH;
+        }
+        if ((!out.data.empty() && hipMemcpyAsync(out.data.data(), data.p, out.data.size(), hipMemcpyDeviceToHost, stream) != hipSuccess) ||
+            hipStreamSynchronize(stream) != hipSuccess)
+            return HS_E_LAUNCH;
+    }
+    uint32_t f = 0;
+    if (hipMemcpyAsync(&f, flags, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return HS_E_LAUNCH;
+    s->runs += 1;
+    s->last_rows = n_out;
+    s->route = J.route;
+    s->n_build = nb;
+    s->n_probe = np;
+    if (flags_out) *flags_out = f;
+    if (n_rows_out) *n_rows_out = n_out;
+    return HS_OK;
+}
+
+extern "C" int hs_join_select_stage_stats(const hs_join_select_stage* s, int64_t* stats) {
+    if (!s || !stats) {
+        hs_set_error("hs_join_select_stage_stats: bad arguments");
+        return HS_E_ARG;
+    }
+    stats[0] = s->runs;
+    stats[1] = s->last_rows;
+    stats[2] = s->route;
+    stats[3] = s->n_build;
+    stats[4] = s->n_probe;
+    return HS_OK;
+}
+
+// The rows of the last run as a BlockFile of rows_per_block-row blocks (as hs_select_result_write_blockfile)
+extern "C" int hs_join_select_result_write_blockfile(const hs_join_select_stage* s, const char* path, int64_t rows_per_block) {
+    if (!s || !path || rows_per_block < 1) {
+        hs_set_error("hs_join_select_result_write_blockfile: bad arguments");
+        return HS_E_ARG;
+    }
+    if (s->last_rows == 0) return HS_OK;
+    FILE* f = fopen(path, "wb");
+    if (!f) {
+        hs_set_error("hs_join_select_result_write_blockfile: cannot create %s", path);
+        return HS_E_ARG;
+    }
+    const hs_join_select_stage_plan& P = s->plan;
+    const uint8_t nc = (uint8_t)P.n_out;
+    fwrite(&nc, 1, 1, f);
+    for (int o = 0; o < P.n_out; ++o) {
+        const uint8_t type = (uint8_t)P.out_types[o];
+        const uint8_t len = (uint8_t)strnlen(P.out_names[o], sizeof(P.out_names[o]));
+        fwrite(&type, 1, 1, f);
+        fwrite(&len, 1, 1, f);
+        fwrite(P.out_names[o], 1, len, f);
+    }
+    std::vector<uint64_t> starts;
+    std::vector<int64_t> str_pos((size_t)P.n_out, 0);
+    for (int64_t lo = 0; lo < s->last_rows; lo += rows_per_block) {
+        const int64_t hi = lo + rows_per_block < s->last_rows ? lo + rows_per_block : s->last_rows;
+        const uint32_t rows = (uint32_t)(hi - lo);
+        starts.push_back((uint64_t)ftell(f));
+        fwrite(&rows, 4, 1, f);
+        for (int o = 0; o < P.n_out; ++o) {
+            const HostCol& out = s->outs[(size_t)o];
+            if (out.width > 0) {
+                const uint64_t bytes = (uint64_t)rows * (uint64_t)out.width;
+                fwrite(&bytes, 8, 1, f);
+                fwrite(out.data.data() + (size_t)lo * (size_t)out.width, 1, (size_t)bytes, f);
+            } else {
+                uint64_t payload = 0;
+                for (int64_t r = lo; r < hi; ++r) payload += out.lens[(size_t)r];
+                const uint64_t bytes = rows + payload;
+                fwrite(&bytes, 8, 1, f);
+                fwrite(out.lens.data() + lo, 1, rows, f);
+                fwrite(out.data.data() + str_pos[(size_t)o], 1, (size_t)payload, f);
+                str_pos[(size_t)o] += (int64_t)payload;
+            }
+        }
+    }
+    fwrite(starts.data(), 8, starts.size(), f);
+    const uint32_t nblocks = (uint32_t)starts.size();
+    fwrite(&nblocks, 4, 1, f);
+    if (fclose(f) != 0) {
+        hs_set_error("hs_join_select_result_write_blockfile: write to %s failed", path);
+        return HS_E_ARG;
+    }
+    return HS_OK;
+}

@@ -37,6 +37,7 @@ extern "C" size_t hs_sizeof(int32_t which) {
         case 10: return sizeof(hs_join8);
         case 11: return sizeof(hs_join_stage_plan);
         case 12: return sizeof(hs_select_stage_plan);
+        case 14: return sizeof(hs_join_select_stage_plan);
         default: return 0;
     }
 }

@@ -2558,3 +2558,406 @@ extern "C" int hs_join_hash_count(void* stream, const int32_t* probe_keys, int64
     RX_CHECK_LAUNCH("hs_join_hash_count");
     return HS_OK;
 }
+
+// =====================================================================================================
+// The general inner join on STRING keys (round 5; include/hipspark.h hs_join_hash_str_*)
+// =====================================================================================================
+// The hashed form above for keys of any byte length.  A key's 64-bit FNV-1a h (hs_fnv1a, the hash the shuffle already uses
+// for strings) goes through the 64-bit finaliser hs_mix64 - FNV-1a's high bits barely depend on the last bytes of a short
+// key (a multiply only carries upwards: keys that differ in their trailing digits crowded a few windows and overflowed
+// them) - and m = hs_mix64(h) is cut in two: the high 32 bits pick the WINDOW (multiply-shift, (m >> 32) * windows >> 32),
+// the low 32 bits are the FINGERPRINT stored in the slot, and fp & (2^L - 1) is the slot where the key starts probing.
+// Slots are {fingerprint, word}, the word as in the dense and hashed forms, so the probe is one scattered 8-byte read in the
+// usual case.  A fingerprint never decides a match on its own: the probe compares the key's bytes with the first build row
+// of the slot's list, the build compares bytes with the slot's representative row whenever a fingerprint is met again (a
+// duplicate key, or - rarely - another key of the same fingerprint in the same window, which then takes its own slot).
+// Build: one pass hashes every key (window number, fingerprint), two stable partition passes (RxPass.range = 1 on the
+// window number) bring the (window, row, fingerprint) tuples into window order, and one wave per window inserts, counts,
+// scans and places them in LDS exactly like k_jh_assemble.  Geometry (windows, L, workspace arrays) is jh_layout's.
+__device__ __forceinline__ uint32_t js_window(uint64_t m, uint32_t windows) { return (uint32_t)(((m >> 32) * (uint64_t)windows) >> 32); }
+
+// hs_mix64(hs_fnv1a(key)), from at most three aligned word loads when the key is <= 16 bytes long
+__device__ __forceinline__ uint64_t js_hash(const HsStr s) {
+    if (s.len > 16) return hs_mix64(hs_fnv1a(s.p, s.len));
+    uint64_t w0, w1;
+    hs_str_words16(s.p, s.len, w0, w1);
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (uint32_t i = 0; i < s.len; ++i) {
+        h ^= ((i < 8 ? w0 >> (8 * i) : w1 >> (8 * (i - 8))) & 0xffu);
+        h *= 0x100000001b3ull;
+    }
+    return hs_mix64(h);
+}
+
+__device__ __forceinline__ bool js_equal(const HsStr a, const HsStr b) {
+    if (a.len != b.len) return false;
+    if (a.len <= 16) {
+        uint64_t a0, a1, b0, b1;
+        hs_str_words16(a.p, a.len, a0, a1);
+        hs_str_words16(b.p, b.len, b0, b1);
+        return a0 == b0 && a1 == b1;
+    }
+    for (uint32_t i = 0; i < a.len; ++i)
+        if (a.p[i] != b.p[i]) return false;
+    return true;
+}
+
+__global__ void __launch_bounds__(256) k_js_hash(const hs_col key, int64_t n, uint32_t windows, uint32_t* win, uint32_t* fp) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t h = js_hash(hs_str_at(key, i));
+        win[i] = js_window(h, windows);
+        fp[i] = (uint32_t)h;
+    }
+}
+
+struct JsAssemble {
+    const int64_t* seg_start;  // [parts + 1] tuple ranges of the windows (parts >= windows; the rest are empty)
+    int64_t parts, windows;
+    const uint32_t* fp;        // tuples, window by window, in row order inside a window
+    const uint32_t* rows;
+    hs_col key;                // the build key column (byte compares)
+    uint2* table;              // [windows << L] {fingerprint, word}
+    uint32_t* out_rows;
+    uint32_t* list_count;
+    uint16_t* slot_of;
+    uint32_t* status;          // HS_FLAG_DICT_FULL only
+    uint32_t* flags;           // anything else
+};
+
+// slot of the key of build row `row` (fingerprint fp) in the wave's LDS window, claiming a free cell when it meets one first;
+// -1: the window is full
+template <int JH_L>
+__device__ __forceinline__ int js_slot(uint64_t* cell, const hs_col& key, uint32_t fp, uint32_t row) {
+    constexpr uint32_t wmask = (1u << JH_L) - 1u;
+    const uint64_t mine = (uint64_t)fp | ((uint64_t)row << 32);
+    const HsStr k = hs_str_at(key, row);
+    uint32_t s = fp & wmask;
+    for (int probe = 0; probe <= (int)wmask; ++probe) {
+        uint64_t cur = __hip_atomic_load(&cell[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (cur == JH_FREE) {
+            cur = atomicCAS((unsigned long long*)&cell[s], (unsigned long long)JH_FREE, (unsigned long long)mine);
+            if (cur == JH_FREE) return (int)s;
+        }
+        if ((uint32_t)cur == fp && js_equal(k, hs_str_at(key, (int64_t)(cur >> 32)))) return (int)s;
+        s = (s + 1) & wmask;
+    }
+    return -1;
+}
+
+template <int JH_L>
+__global__ void __launch_bounds__(256) k_js_assemble(const JsAssemble A) {
+    extern __shared__ __align__(16) uint64_t js_lds[];
+    constexpr int W = 1 << JH_L, per = W / HS_WAVE;
+    const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE, wpb = blockDim.x / HS_WAVE;
+    uint64_t* cell = js_lds + (size_t)w * (2 * W + W / 8);
+    uint32_t* cur = (uint32_t*)(cell + W);
+    uint32_t* head = cur + W;
+    uint8_t* tag = (uint8_t*)(head + W);
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t err = 0, full_any = 0;
+    for (int64_t p = (int64_t)blockIdx.x * wpb + w; p < A.parts; p += (int64_t)gridDim.x * wpb) {
+        const int64_t b = A.seg_start[p], e = A.seg_start[p + 1];
+        if (p >= A.windows) {
+            if (e > b) err |= HS_FLAG_BAD_PROGRAM;  // a tuple past the last window: the passes and the table disagree
+            continue;
+        }
+        uint32_t nfp = b + lane < e ? A.fp[b + lane] : 0u;
+        uint32_t nrow = b + lane < e ? A.rows[b + lane] : 0u;
+        for (int s = lane; s < W; s += HS_WAVE) {
+            cell[s] = JH_FREE;
+            cur[s] = 0;
+            head[s] = JD_EMPTY;
+        }
+        rx_wave_handover();
+        bool full = false;
+        for (int64_t base = b; base < e; base += HS_WAVE) {  // claim slots, count rows per slot
+            const uint32_t fp = nfp, row = nrow;
+            const bool valid = base + lane < e;
+            if (base + HS_WAVE + lane < e) {
+                nfp = A.fp[base + HS_WAVE + lane];
+                nrow = A.rows[base + HS_WAVE + lane];
+            }
+            if (valid) {
+                const int s = js_slot<JH_L>(cell, A.key, fp, row);
+                if (s < 0) full = true;
+                else atomicAdd(&cur[s], 1u);
+                A.slot_of[base + lane] = (uint16_t)s;
+            }
+        }
+        rx_wave_handover();
+        if (__ballot(full)) {  // (wave-uniform) leave the window empty and say so
+            full_any = HS_FLAG_DICT_FULL;
+            for (int s = lane; s < W; s += HS_WAVE) A.table[(p << JH_L) + s] = make_uint2(0u, JD_EMPTY);
+            continue;
+        }
+        uint32_t sum = 0;
+        for (int k = 0; k < per; ++k) sum += cur[lane * per + k];
+        uint32_t x = sum;
+        for (int d = 1; d < HS_WAVE; d <<= 1) {
+            const uint32_t up = __shfl_up(x, d, HS_WAVE);
+            if (lane >= d) x += up;
+        }
+        uint32_t run = x - sum;
+        for (int k = 0; k < per; ++k) {
+            const uint32_t c = cur[lane * per + k];
+            cur[lane * per + k] = run;
+            run += c;
+        }
+        rx_wave_handover();
+        uint32_t nslot = b + lane < e ? A.slot_of[b + lane] : 0u;
+        nrow = b + lane < e ? A.rows[b + lane] : 0u;
+        for (int64_t base = b; base < e; base += HS_WAVE) {  // ordered placement (see k_jd_assemble)
+            const bool valid = base + lane < e;
+            const uint32_t s = nslot, row = nrow;
+            if (base + HS_WAVE + lane < e) {
+                nslot = A.slot_of[base + HS_WAVE + lane];
+                nrow = A.rows[base + HS_WAVE + lane];
+            }
+            if (valid) tag[s] = (uint8_t)lane;
+            rx_wave_handover();
+            const bool shared_slot = valid && tag[s] != (uint8_t)lane;
+            const uint32_t at = valid ? cur[s] : 0u;
+            const uint32_t first = valid ? head[s] : 0u;
+            if (__ballot(shared_slot) == 0) {
+                if (valid) {
+                    A.out_rows[b + at] = row;
+                    cur[s] = at + 1u;
+                    if (first == JD_EMPTY) head[s] = row;
+                }
+                rx_wave_handover();
+                continue;
+            }
+            uint64_t peers = __ballot(valid);
+            for (int bit = 0; bit < JH_L; ++bit) {
+                const bool on = (s >> bit) & 1u;
+                const uint64_t bal = __ballot(valid && on);
+                peers &= on ? bal : ~bal;
+            }
+            const uint32_t rank = (uint32_t)__popcll(peers & below);
+            rx_wave_handover();
+            if (valid) {
+                A.out_rows[b + at + rank] = row;
+                if (rank == 0) {
+                    cur[s] = at + (uint32_t)__popcll(peers);
+                    if (first == JD_EMPTY) head[s] = row;
+                }
+            }
+            rx_wave_handover();
+        }
+        for (int s = lane; s < W; s += HS_WAVE) {
+            const uint32_t end = cur[s], start = s ? cur[s - 1] : 0u;
+            const uint32_t c = end - start;
+            uint32_t word = JD_EMPTY;
+            if (c == 1) word = head[s];
+            else if (c > 1) {
+                word = JD_MULTI | (uint32_t)(b + start);
+                A.list_count[b + start] = c;
+            }
+            A.table[(p << JH_L) + s] = make_uint2((uint32_t)cell[s], word);
+        }
+        rx_wave_handover();
+    }
+    if (full_any && lane == 0) atomicOr(A.status, full_any);
+    if (err && lane == 0) atomicOr(A.flags, err);
+}
+
+struct JsLayout {
+    JhLayout h;
+    size_t win, fp, fp_a, fp_b, total;
+};
+static bool js_layout(int64_t n, JsLayout& Y) {
+    if (!jh_layout(n, Y.h)) return false;
+    size_t off = Y.h.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += rx_align(bytes);
+        return at;
+    };
+    Y.win = take((size_t)n * 4 + 64);
+    Y.fp = take((size_t)n * 4 + 64);
+    Y.fp_a = take(Y.h.bits1 ? (size_t)n * 4 + 64 : 0);
+    Y.fp_b = take(Y.h.bits2 ? (size_t)n * 4 + 64 : 0);
+    Y.total = off;
+    return true;
+}
+
+extern "C" size_t hs_join_hash_str_ws_bytes(int64_t n_build) {
+    JsLayout Y;
+    return js_layout(n_build, Y) ? Y.total : 0;
+}
+extern "C" int64_t hs_join_hash_str_slots(int64_t n_build) {
+    JsLayout Y;
+    return js_layout(n_build, Y) ? Y.h.windows << Y.h.L : 0;
+}
+
+static bool js_str_col(const hs_col* c) { return c && c->kind == HS_STR && (c->fixed_len >= 0 || (c->lens && c->offs)); }
+
+extern "C" int hs_join_hash_str_build(void* stream_, const hs_col* build_key, int64_t n_build, void* table, uint32_t* rows,
+                                      uint32_t* list_count, void* ws_, uint32_t* status, uint32_t* flags) {
+    JsLayout Y;
+    if ((n_build > 0 && !js_str_col(build_key)) || !build_key || !table || !rows || !list_count || !ws_ || !status || !flags ||
+        ((uintptr_t)table & 7) || !js_layout(n_build, Y)) {
+        hs_set_error("hs_join_hash_str_build: bad arguments (a STRING key column, n_build <= 38 M rows, table 8-byte aligned)");
+        return HS_E_ARG;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    uint8_t* ws = (uint8_t*)ws_;
+    const JhLayout& G = Y.h;
+    const int64_t n = n_build;
+    uint32_t* win = (uint32_t*)(ws + Y.win);
+    uint32_t* fp = (uint32_t*)(ws + Y.fp);
+    uint32_t* iota = (uint32_t*)(ws + G.iota);
+    int64_t* seg0 = (int64_t*)(ws + G.seg0);
+    int64_t* seg1 = (int64_t*)(ws + G.seg1);
+    int64_t* seg2 = (int64_t*)(ws + G.seg2);
+    if (n > 0) {
+        int64_t g = (n + 255) / 256;
+        g = g > 4096 ? 4096 : g;
+        hipLaunchKernelGGL(k_js_hash, dim3((unsigned)g), dim3(256), 0, stream, *build_key, n, (uint32_t)G.windows, win, fp);
+        RX_CHECK_LAUNCH("hs_join_hash_str_build (hash)");
+    }
+    const int64_t n_iota = G.bits1 ? 0 : n;
+    int64_t grid = (n_iota + 255) / 256;
+    grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
+    hipLaunchKernelGGL(k_jd_setup, dim3((unsigned)grid), dim3(256), 0, stream, iota, n_iota, n, seg0);
+    RX_CHECK_LAUNCH("hs_join_hash_str_build (row ids)");
+    const uint32_t* t_fp = fp;
+    const uint32_t* t_rows = iota;
+    const int64_t* seg = seg0;
+    if (G.bits1 > 0 && n > 0) {
+        RxPass P;
+        std::memset(&P, 0, sizeof(P));
+        P.n_cols = 3;  // window number (the partition key), row id, fingerprint
+        P.esize[0] = P.esize[1] = P.esize[2] = 4;
+        P.range = 1;   // bins are bits of the window number itself
+        P.range_bias = 0;
+        P.key = hs_col{HS_I32, -1, win, nullptr, nullptr};
+        P.row0 = 0;
+        P.seg_start = seg0;  // pass 1: the top bits1 bits of the window number over the one segment [0, n)
+        P.tile_base = (int64_t*)(ws + G.tb0);
+        P.n_seg = 1;
+        P.shift = G.bits2;
+        P.bits = G.bits1;
+        P.first = 1;
+        P.src[1] = nullptr;  // the row id column is the position (k_rx_scatter4)
+        P.src[2] = fp;
+        P.dst[0] = ws + G.keys_a;
+        P.dst[1] = ws + G.rows_a;
+        P.dst[2] = ws + Y.fp_a;
+        int rc = rx_pass(stream, P, G.tiles1, (int64_t*)(ws + G.cnt), (int64_t*)(ws + G.scan), ws + G.scan_ws, n, G.bits2 ? seg1 : seg2);
+        if (rc != HS_OK) return rc;
+        t_fp = (const uint32_t*)(ws + Y.fp_a);
+        t_rows = (const uint32_t*)(ws + G.rows_a);
+        seg = seg2;
+        if (G.bits2) {  // pass 2: the low bits2 bits inside every segment of pass 1
+            P.seg_start = seg1;
+            P.tile_base = (int64_t*)(ws + G.tb1);
+            P.n_seg = G.nseg1;
+            P.shift = 0;
+            P.bits = G.bits2;
+            P.first = 0;
+            P.src[0] = ws + G.keys_a;
+            P.src[1] = ws + G.rows_a;
+            P.src[2] = ws + Y.fp_a;
+            P.dst[0] = ws + G.keys_b;
+            P.dst[1] = ws + G.rows_b;
+            P.dst[2] = ws + Y.fp_b;
+            rc = rx_pass(stream, P, G.tiles2, (int64_t*)(ws + G.cnt), (int64_t*)(ws + G.scan), ws + G.scan_ws, n, seg2);
+            if (rc != HS_OK) return rc;
+            t_fp = (const uint32_t*)(ws + Y.fp_b);
+            t_rows = (const uint32_t*)(ws + G.rows_b);
+        }
+    } else if (G.bits1 > 0) {  // no rows: every window is empty
+        hs_memset_async(seg2, 0, (size_t)(G.parts + 1) * 8, stream);
+        seg = seg2;
+    }
+    JsAssemble A;
+    A.seg_start = seg;
+    A.parts = G.bits1 > 0 ? G.parts : 1;
+    A.windows = G.windows;
+    A.fp = t_fp;
+    A.rows = t_rows;
+    A.key = *build_key;
+    A.table = (uint2*)table;
+    A.out_rows = rows;
+    A.list_count = list_count;
+    A.slot_of = (uint16_t*)(ws + G.slot_of);
+    A.status = status;
+    A.flags = flags;
+    const size_t per_wave = (size_t)17 << G.L;  // key cells (8 B) + cursors + first rows (4 B each) + tag bytes
+    constexpr int wpb = 4;
+    int64_t g = (A.parts + wpb - 1) / wpb;
+    if (g > 256 * 32) g = 256 * 32;
+    static unsigned long long attr_set = 0;
+    if (hs_first_on_device(attr_set))
+        (void)hipFuncSetAttribute((const void*)k_js_assemble<JH_L_LARGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (17 << JH_L_LARGE) * wpb);
+    if (G.L == JH_L_SMALL) hipLaunchKernelGGL(k_js_assemble<JH_L_SMALL>, dim3((unsigned)g), dim3(HS_WAVE * wpb), per_wave * wpb, stream, A);
+    else hipLaunchKernelGGL(k_js_assemble<JH_L_LARGE>, dim3((unsigned)g), dim3(HS_WAVE * wpb), per_wave * wpb, stream, A);
+    RX_CHECK_LAUNCH("hs_join_hash_str_build (assemble)");
+    return HS_OK;
+}
+
+struct JsProbe {
+    hs_col build, probe;
+    int64_t n;
+    uint32_t windows, pad;
+    const uint2* table;
+    const uint32_t* rows;
+    const uint32_t* list_count;
+    int64_t* counts;
+    uint32_t* aux;
+};
+
+// Probe, pass 1: one probe row per lane - hash, one 8-byte slot read, and on a fingerprint match one compare with the
+// list's first build row (length, then bytes); a mismatch keeps probing inside the window.  counts / aux as
+// hs_join_dense_count writes them.
+template <int JH_L>
+__global__ void __launch_bounds__(256) k_js_count(const JsProbe A) {
+    constexpr uint32_t wmask = (1u << JH_L) - 1u;
+    const int64_t second = (A.n + 3) & ~(int64_t)3;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * blockDim.x) {
+        const HsStr k = hs_str_at(A.probe, i);
+        const uint64_t h = js_hash(k);
+        const uint32_t fp = (uint32_t)h;
+        const uint2* win = A.table + ((int64_t)js_window(h, A.windows) << JH_L);
+        uint32_t at = fp & wmask;
+        uint32_t word = JD_EMPTY, first = JD_EMPTY, st = 0u;
+        uint2 slot = win[at];
+        for (int probe = 0; probe <= (int)wmask && slot.y != JD_EMPTY; ++probe) {
+            if (slot.x == fp) {
+                const bool multi = (slot.y & JD_MULTI) != 0u;
+                const uint32_t f = multi ? A.rows[slot.y & ~JD_MULTI] : slot.y;
+                if (js_equal(k, hs_str_at(A.build, f))) {
+                    word = slot.y;
+                    first = f;
+                    st = multi ? slot.y & ~JD_MULTI : 0u;
+                    break;
+                }
+            }
+            at = (at + 1) & wmask;
+            slot = win[at];
+        }
+        const uint32_t cnt = word == JD_EMPTY ? 0u : (word & JD_MULTI) ? A.list_count[st] : 1u;
+        A.counts[i] = (int64_t)cnt;
+        A.aux[i] = first;
+        A.aux[second + i] = st;
+    }
+}
+
+extern "C" int hs_join_hash_str_count(void* stream, const hs_col* build_key, const hs_col* probe_key, int64_t n_probe, int64_t n_build,
+                                      const void* table, const uint32_t* rows, const uint32_t* list_count, int64_t* counts, void* aux) {
+    JsLayout Y;
+    if (n_probe < 0 || !build_key || !probe_key || (n_probe > 0 && !js_str_col(probe_key)) || (n_build > 0 && !js_str_col(build_key)) ||
+        !table || !rows || !list_count || !counts || !aux || ((uintptr_t)counts & 15) || ((uintptr_t)aux & 15) || !js_layout(n_build, Y)) {
+        hs_set_error("hs_join_hash_str_count: bad arguments (STRING key columns, counts and aux 16-byte aligned; n_build as given to the build)");
+        return HS_E_ARG;
+    }
+    if (n_probe == 0) return HS_OK;
+    JsProbe A{*build_key, *probe_key, n_probe, (uint32_t)Y.h.windows, 0, (const uint2*)table, rows, list_count, counts, (uint32_t*)aux};
+    int64_t g = (n_probe + 255) / 256;
+    if (g > 256 * 64) g = 256 * 64;
+    if (Y.h.L == JH_L_SMALL) hipLaunchKernelGGL(k_js_count<JH_L_SMALL>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(k_js_count<JH_L_LARGE>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, A);
+    RX_CHECK_LAUNCH("hs_join_hash_str_count");
+    return HS_OK;
+}

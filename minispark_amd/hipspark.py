@@ -199,6 +199,8 @@ class hs_join_stage_plan(C.Structure):
 
 
 HS_SELECT_STAGE_PLAN_VERSION = 1
+HS_JOIN_SELECT_STAGE_PLAN_VERSION = 1
+JOIN_ROUTES = {1: "dense", 2: "hashed", 3: "hashed-string", 4: "global"}  # HS_JOIN_ROUTE_*
 
 
 class hs_select_stage_plan(C.Structure):
@@ -213,6 +215,26 @@ class hs_select_stage_plan(C.Structure):
         ("project_kinds", C.c_int32 * HS_MAX_OUTS),
         ("n_out", C.c_int32),
         ("out_src", C.c_int32 * HS_FINISH_MAX_OUT),
+        ("out_types", C.c_int32 * HS_FINISH_MAX_OUT),
+        ("out_names", (C.c_char * 64) * HS_FINISH_MAX_OUT),
+    ]
+
+
+class hs_join_select_stage_plan(C.Structure):
+    _fields_ = [
+        ("version", C.c_int32),
+        ("build_key_col", C.c_int32),
+        ("probe_key_col", C.c_int32),
+        ("n_parts", C.c_int32),
+        ("n_bcols", C.c_int32),
+        ("bcol_ids", C.c_int32 * HS_MAX_COLS),
+        ("build_filter", hs_program),
+        ("n_pcols", C.c_int32),
+        ("pcol_ids", C.c_int32 * HS_MAX_COLS),
+        ("probe_filter", hs_program),
+        ("n_out", C.c_int32),
+        ("out_side", C.c_int32 * HS_FINISH_MAX_OUT),
+        ("out_col", C.c_int32 * HS_FINISH_MAX_OUT),
         ("out_types", C.c_int32 * HS_FINISH_MAX_OUT),
         ("out_names", (C.c_char * 64) * HS_FINISH_MAX_OUT),
     ]
@@ -322,6 +344,10 @@ SIGNATURES: dict[str, tuple] = {
     "hs_join_hash_slots": (C.c_int64, [_I64]),
     "hs_join_hash_build": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P]),
     "hs_join_hash_count": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P]),
+    "hs_join_hash_str_ws_bytes": (C.c_size_t, [_I64]),
+    "hs_join_hash_str_slots": (C.c_int64, [_I64]),
+    "hs_join_hash_str_build": (C.c_int, [_P, _COLP, _I64, _P, _P, _P, _P, _P, _P]),
+    "hs_join_hash_str_count": (C.c_int, [_P, _COLP, _COLP, _I64, _I64, _P, _P, _P, _P, _P]),
     "hs_remap_u8": (C.c_int, [_P, _P, _I64, _P, _P]),
     "hs_dict_build": (C.c_int, [_P, _COLP, _I64, _I32, _P, _P, _P, _P]),
     "hs_dict_assign": (C.c_int, [_P, _COLP, _I64, _I32, _P, _P, _P, _P, _P]),
@@ -360,6 +386,11 @@ SIGNATURES: dict[str, tuple] = {
     "hs_select_stage_run": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(_I64)]),
     "hs_select_result_write_blockfile": (C.c_int, [_P, C.c_char_p, _I64]),
     "hs_select_stage_destroy": (None, [_P]),
+    "hs_join_select_stage_prepare": (C.c_int, [_P, _P, _P, C.POINTER(hs_join_select_stage_plan), C.c_size_t, C.POINTER(_P)]),
+    "hs_join_select_stage_run": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(_I64)]),
+    "hs_join_select_stage_stats": (C.c_int, [_P, C.POINTER(_I64)]),
+    "hs_join_select_result_write_blockfile": (C.c_int, [_P, C.c_char_p, _I64]),
+    "hs_join_select_stage_destroy": (None, [_P]),
     "hs_join_stage_prepare": (C.c_int, [_P, _P, _P, C.POINTER(hs_join_stage_plan), C.c_size_t, C.POINTER(_P)]),
     "hs_join_stage_run": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(_I64)]),
     "hs_join_stage_stats": (C.c_int, [_P, C.POINTER(_I64)]),

@@ -6,7 +6,8 @@ No torch, no :class:`minispark_amd.device.Device`: this is the whole host a cgo 
 behind the ABI.  The query shape it covers is the hot path's: ``table -> [filter]* -> group_by(col).agg(...)``, i.e. the
 reference's two stages [Load -> Filter* -> Aggregate(before) -> shuffle] + [shuffle -> Aggregate(after) -> (Project) ->
 result] (plan.py:182-204); round 3: a SELECT in front of the GROUP BY (its columns inlined, a computed INTEGER key
-materialised by the library), and any number of groups per block the on-chip tiers hold.
+materialised by the library), and any number of groups per block the on-chip tiers hold; round 5: a join whose rows go to
+the result file (lower_join_select_stage_plan / NativeJoinSelectStage).
 """
 
 from __future__ import annotations
@@ -369,6 +370,152 @@ def lower_select_stage_plan(full_task: Any, plan: Any = None) -> tuple[hs.hs_sel
     return blob, Path(stage.producer.file_path), out_schema
 
 
+def _walk_names(node: Any) -> list[str]:
+    """Column names an expression reads (plain columns, through aliases, LIKE and operators)."""
+    name = _cls(node)
+    if name in ("Col", "SchemaCol"):
+        return [node.name]
+    if name == "Lit":
+        return []
+    if name in ("AliasColumn", "LikeColumn"):
+        return _walk_names(node.original_col)
+    if name == "BinaryOperatorColumn":
+        return _walk_names(node.left_side) + _walk_names(node.right_side)
+    raise StageUnsupported(f"{name} in a join predicate")
+
+
+def _conjuncts(node: Any) -> list[Any]:
+    bare = _bare(node)
+    if _cls(bare) == "BinaryOperatorColumn" and bare.operator.__name__ == "and_":
+        return _conjuncts(bare.left_side) + _conjuncts(bare.right_side)
+    return [node]
+
+
+def lower_join_select_stage_plan(full_task: Any, plan: Any = None,
+                                 n_parts: int | None = None) -> tuple[hs.hs_join_select_stage_plan, Path, Path, Schema]:
+    """[scan, scan, join -> result file] (a JoinJob whose rows go to the result file, jobs.py:45-79) -> (plan blob of the
+    native JOIN-to-rows stage, build table path, probe table path, result schema).  Projections may only pass columns through
+    or rename them; every WHERE conjunct must read one side only and is pushed to that side's scan (the join keeps the order
+    of the rows that survive, so the result and its order do not change)."""
+    from . import constants  # noqa: PLC0415
+
+    if plan is None:
+        from .plan import PhysicalPlan  # noqa: PLC0415
+
+        plan = PhysicalPlan.generate_physical_plan(full_task)
+    stages = list(plan.stages)
+    join = next((st for st in stages if _cls(st.producer) == "BroadcastHashJoinTask"), None)
+    if join is None or len(stages) != 3 or len(join.dependencies) != 2 or _cls(join.writer) != "WriteToLocalFileTask":
+        raise StageUnsupported("not a [scan, scan, join -> result file] plan")
+    # every column name in scope -> (side, table column); side 0 = build (the join's left input), 1 = probe
+    tables, scope_per_side, filters = [], [], ([], [])
+    for dep in join.dependencies:
+        if _cls(dep.producer) != "LoadTableBlockTask":
+            raise StageUnsupported("a join input is not a table scan")
+        tables.append((dep.producer, list(dep.producer.inferred_schema)))
+    table_names = [[n for n, _ in schema] for _, schema in tables]
+    for side, dep in enumerate(join.dependencies):
+        scope = {n: (side, i) for i, n in enumerate(table_names[side])}
+        for task in dep.consumers:
+            scope = _pass_through(task, scope, filters, table_names)
+        scope_per_side.append(scope)
+    task = join.producer
+    lname, rname = task.left_key.name, task.right_key.name
+    if lname not in scope_per_side[0] or rname not in scope_per_side[1]:
+        raise StageUnsupported("join keys are not plain columns of the two inputs")
+    scope = dict(scope_per_side[1])
+    scope.update(scope_per_side[0])  # a name on both sides reads the build side's, as the engine's column lookup does
+    order = list(scope_per_side[0].values()) + list(scope_per_side[1].values())
+    for t in join.consumers:
+        if _cls(t) == "FilterTask":
+            _push_filter(t.condition, scope, filters, table_names)
+        elif _cls(t) == "ProjectTask":
+            new, refs = {}, []
+            for (n, _), c in zip(t.inferred_schema, t.columns):
+                bare = _bare(c)
+                if _cls(bare) not in ("Col", "SchemaCol") or bare.name == "*" or bare.name not in scope:
+                    raise StageUnsupported("a computed column after the join")
+                refs.append(scope[bare.name])
+                new.setdefault(n, scope[bare.name])  # a repeated name reads its first column, as the engine's lookup does
+            scope, order = new, refs
+        else:
+            raise StageUnsupported(f"{_cls(t)} after the join (a join feeding an aggregate is hs_join_stage)")
+    out_schema = list(join.writer.inferred_schema)
+    if len(order) != len(out_schema):
+        raise StageUnsupported("result schema does not match the joined columns")
+    if len(order) > hs.HS_FINISH_MAX_OUT:
+        raise StageUnsupported(f"more than {hs.HS_FINISH_MAX_OUT} result columns")
+    ltype = tables[0][1][scope_per_side[0][lname][1]][1]
+    rtype = tables[1][1][scope_per_side[1][rname][1]][1]
+    if ltype != rtype or ltype not in (ColumnType.INTEGER, ColumnType.STRING):
+        raise StageUnsupported(f"join keys of kinds {ltype} / {rtype}: both INTEGER or both STRING")
+    blob = hs.hs_join_select_stage_plan()
+    blob.version = hs.HS_JOIN_SELECT_STAGE_PLAN_VERSION
+    blob.build_key_col = scope_per_side[0][lname][1]
+    blob.probe_key_col = scope_per_side[1][rname][1]
+    blob.n_parts = n_parts if n_parts is not None else constants.SHUFFLE_PARTITIONS
+    for side, (n_field, ids_field, prog_field) in enumerate((("n_bcols", "bcol_ids", "build_filter"), ("n_pcols", "pcol_ids", "probe_filter"))):
+        if not filters[side]:
+            continue
+        schema = tables[side][1]
+        cond = filters[side][0]
+        for extra in filters[side][1:]:
+            cond = cond & extra
+        fb = ProgramBuilder(schema, [_FILE_KIND[t] for _, t in schema])
+        if fb.emit_out(0, cond) != "B":
+            fb = ProgramBuilder(schema, [_FILE_KIND[t] for _, t in schema])
+            fb.emit_out(0, cond != 0)
+        prog = fb.finish()
+        if len(prog.columns) > hs.HS_MAX_COLS:
+            raise StageUnsupported(f"a WHERE over more than {hs.HS_MAX_COLS} columns")
+        setattr(blob, n_field, len(prog.columns))
+        ids = getattr(blob, ids_field)
+        for slot, idx in enumerate(prog.columns):
+            ids[slot] = idx
+        setattr(blob, prog_field, prog.to_struct())
+    blob.n_out = len(order)
+    for o, ((name, ctype), (side, col)) in enumerate(zip(out_schema, order)):
+        if tables[side][1][col][1] != ctype:
+            raise StageUnsupported("a result column changes its type")
+        blob.out_side[o], blob.out_col[o] = side, col
+        blob.out_types[o] = _TYPE_CODE[ctype]
+        blob.out_names[o].value = name.encode()[:63]
+    return blob, Path(tables[0][0].file_path), Path(tables[1][0].file_path), out_schema
+
+
+def _push_filter(condition: Any, scope: dict, filters: tuple, table_names: list) -> None:
+    """Every conjunct of a WHERE -> over the table columns of the one side it reads -> that side's filters."""
+    for conj in _conjuncts(condition):
+        names = _walk_names(conj)
+        missing = [n for n in names if n not in scope]
+        if missing:
+            raise ValueError(f'Column "{missing[0]}" not found in schema {list(scope)}')
+        sides = {scope[n][0] for n in names}
+        if len(sides) > 1:
+            raise StageUnsupported("a WHERE conjunct over both sides of the join")
+        side = sides.pop() if sides else 1
+        defs = {n: Col(table_names[scope[n][0]][scope[n][1]]) for n in names}
+        filters[side].append(_substitute(conj, defs))
+
+
+def _pass_through(task: Any, scope: dict, filters: tuple, table_names: list) -> dict:
+    """A scan-stage task of a join input: a WHERE (pushed as it is) or a projection that selects / renames columns."""
+    if _cls(task) == "FilterTask":
+        _push_filter(task.condition, scope, filters, table_names)
+        return scope
+    if _cls(task) != "ProjectTask":
+        raise StageUnsupported(f"{_cls(task)} between a table and the join")
+    new = {}
+    for (n, _), c in zip(task.inferred_schema, task.columns):
+        bare = _bare(c)
+        if _cls(bare) not in ("Col", "SchemaCol") or bare.name == "*" or bare.name not in scope:
+            raise StageUnsupported("a computed column between a table and the join")
+        new.setdefault(n, scope[bare.name])
+    if len(new) != len(task.columns):
+        raise StageUnsupported("a projection that repeats a column name before the join")
+    return new
+
+
 class NativeSelectStage:
     """A prepared select / where query behind the C ABI: ``run(path)`` -> rows (through the result BlockFile the library writes)."""
 
@@ -395,6 +542,48 @@ class NativeSelectStage:
     def close(self) -> None:
         if self.handle:
             self.lib.hs_select_stage_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+class NativeJoinSelectStage:
+    """A prepared [scan, scan, join -> result file] query behind the C ABI: ``run(path)`` -> rows (through the result BlockFile
+    the library writes)."""
+
+    def __init__(self, engine: "NativeEngine", full_task: Any, plan: Any = None, n_parts: int | None = None) -> None:
+        self.engine, self.lib = engine, engine.lib
+        self.blob, self.build_path, self.probe_path, self.schema = lower_join_select_stage_plan(full_task, plan, n_parts)
+        self.handle = C.c_void_p()
+        hs.check(self.lib.hs_join_select_stage_prepare(engine.handle, engine.table(self.build_path), engine.table(self.probe_path),
+                                                       C.byref(self.blob), C.sizeof(self.blob), C.byref(self.handle)),
+                 "hs_join_select_stage_prepare")
+
+    def run(self, out_path: Path | str, rows_per_block: int | None = None, stream: int | None = None) -> list[Row]:
+        return read_result_file(out_path) if self.run_to_file(out_path, rows_per_block, stream) else []
+
+    def run_to_file(self, out_path: Path | str, rows_per_block: int | None = None, stream: int | None = None) -> int:
+        """One run; its rows go to the BlockFile at out_path (no file for no rows) -> the number of rows."""
+        from . import constants  # noqa: PLC0415
+
+        flags, nrows = C.c_uint32(0), C.c_int64(0)
+        hs.check(self.lib.hs_join_select_stage_run(self.handle, stream, C.byref(flags), C.byref(nrows)), "hs_join_select_stage_run")
+        raise_for_flags(flags.value)
+        if nrows.value == 0:
+            return 0
+        Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+        hs.check(self.lib.hs_join_select_result_write_blockfile(self.handle, str(out_path).encode(),
+                                                                rows_per_block or constants.ROWS_PER_BLOCK),
+                 "hs_join_select_result_write_blockfile")
+        return int(nrows.value)
+
+    def stats(self) -> dict:
+        s = (C.c_int64 * 5)()
+        hs.check(self.lib.hs_join_select_stage_stats(self.handle, s), "hs_join_select_stage_stats")
+        runs, rows, route, n_build, n_probe = (int(v) for v in s)
+        return {"runs": runs, "rows": rows, "route": hs.JOIN_ROUTES.get(route, route), "build_rows": n_build, "probe_rows": n_probe}
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.hs_join_select_stage_destroy(self.handle)
             self.handle = C.c_void_p()
 
 
