@@ -441,13 +441,14 @@ int hs_join_dense_fill(void* stream, int64_t n_probe, const uint32_t* rows, cons
  * with coalesced stores - no global atomic, no scattered store, lists ascending without a sort.  hs_join_hash_count: one
  * scattered 8-byte read per probe row in the usual case (~1.7 slots from the start at the table's load of 0.57, nearly always
  * the same 64-byte line); counts / aux exactly as hs_join_dense_count leaves them, so the second pass IS
- * hs_join_dense_fill(rows, aux, ...).  n_build <= ~38 M rows per call (hs_join_hash_slots returns 0 beyond); a window with
- * more distinct keys than slots (a degenerate hash) is left empty and raises HS_FLAG_DICT_FULL - the caller takes
- * hs_join_build instead.  rows / list_count: n_build entries each; ws: hs_join_hash_ws_bytes(n_build). */
+ * hs_join_dense_fill(rows, aux, ...).  n_build <= ~38 M rows per call (hs_join_hash_slots returns 0 beyond).  *status
+ * receives HS_FLAG_DICT_FULL only - a window met more distinct keys than slots (a degenerate hash) and was left empty: the
+ * caller takes hs_join_build instead; any other inconsistency is OR-ed into *flags (device) and is an error.
+ * rows / list_count: n_build entries each; ws: hs_join_hash_ws_bytes(n_build). */
 size_t hs_join_hash_ws_bytes(int64_t n_build);
 int64_t hs_join_hash_slots(int64_t n_build);
 int hs_join_hash_build(void* stream, const int32_t* build_keys, int64_t n_build, void* table, uint32_t* rows,
-                       uint32_t* list_count, void* ws, uint32_t* flags);
+                       uint32_t* list_count, void* ws, uint32_t* status, uint32_t* flags);
 int hs_join_hash_count(void* stream, const int32_t* probe_keys, int64_t n_probe, int64_t n_build, const void* table,
                        const uint32_t* rows, const uint32_t* list_count, int64_t* counts, void* aux);
 /* ---- the general inner join on STRING keys (round 5; csrc/hs_radix.hip) ----------------------------------------------------

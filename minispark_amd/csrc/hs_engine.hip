@@ -2146,7 +2146,7 @@ int join_pairs(hipStream_t stream, const hs_col& bk, int64_t nb, const hs_col& p
         } else if (hs_join_hash_slots(nb) > 0) {
             if (!table.alloc((size_t)hs_join_hash_slots(nb) * 8) || !ws.alloc(hs_join_hash_ws_bytes(nb))) return HS_E_LAUNCH;
             rc = hs_join_hash_build(stream, (const int32_t*)bk.data, nb, table.p, (uint32_t*)rows32.p, (uint32_t*)lcount.p, ws.p,
-                                    (uint32_t*)status.p);
+                                    (uint32_t*)status.p, flags);
             if (!rc) rc = hs_join_hash_count(stream, (const int32_t*)pk.data, np, nb, table.p, (const uint32_t*)rows32.p,
                                              (const uint32_t*)lcount.p, (int64_t*)counts.p, aux.p);
             if (rc) return rc;

@@ -1744,9 +1744,139 @@ extern "C" int hs_expand_by_bounds(void* stream, const int64_t* bounds, const in
 //      included) leaves with coalesced stores.
 // The probe is then one or two adjacent 4-byte reads per row (starts[s], starts[s + 1]) instead of a hash probe over
 // three arrays: count -> exclusive scan -> fill, pairs ordered by probe row, then build row (tasks.py:224-240).
+// The hashed INTEGER and STRING forms below share this build (jx_* : partition passes, per-window assembly, probe epilogue).
 constexpr int JD_MAX_L = 13;  // slots of one partition: 2^L cursors + 2^L first rows (uint32) + 2^L tag bytes in LDS per wave (72 KB at most)
 constexpr uint32_t JD_EMPTY = 0xffffffffu;  // slot word: no build row has this key
 constexpr uint32_t JD_MULTI = 0x80000000u;  // slot word: several - the low 31 bits are the start of the key's list in rows[]
+
+// ---- the assembly of one partition (dense) or window (hashed), one wave each --------------------------------------------
+// The wave walks its tuples [b, e) in row order with LDS tables of 2^L slots: cur[] (counts, then list cursors), head[] (the
+// first = lowest build row of every slot) and tag[] (placement: the lane that came by last in this step).  L is a
+// compile-time constant in the hashed kernels and a run-time value in the dense one; the helpers take it as an argument.
+
+// Clears the tables (and what clear(s) adds), then every tuple claims its slot - claim(tuple, i) -> slot, < 0: none, the
+// window is full - and counts a row there (LDS atomics: counting is order-free).  load(i) fetches tuple i; the first
+// step's tuples are asked for before the tables are cleared, every later step's before the current one is worked on (a
+// wave walks its partition in order: without this it paid one global round trip per step).  -> a tuple of this lane found
+// no slot.
+template <typename Load, typename Clear, typename Claim>
+__device__ __forceinline__ bool jx_count(uint32_t* cur, uint32_t* head, int L, int64_t b, int64_t e, int lane, Load load, Clear clear,
+                                         Claim claim) {
+    decltype(load(b)) next{};
+    if (b + lane < e) next = load(b + lane);
+    for (int s = lane; s < (1 << L); s += HS_WAVE) {
+        clear(s);
+        cur[s] = 0;
+        head[s] = JD_EMPTY;
+    }
+    rx_wave_handover();
+    bool full = false;
+    for (int64_t base = b; base < e; base += HS_WAVE) {
+        const auto t = next;
+        const bool valid = base + lane < e;
+        if (base + HS_WAVE + lane < e) next = load(base + HS_WAVE + lane);
+        if (valid) {
+            const int s = claim(t, base + lane);
+            if (s < 0) full = true;
+            else atomicAdd(&cur[s], 1u);
+        }
+    }
+    rx_wave_handover();
+    return full;
+}
+
+// exclusive scan of the 2^L counts: a lane's consecutive slots, then a scan over the lanes
+__device__ __forceinline__ void jx_scan(uint32_t* cur, int L, int lane) {
+    const int per = (1 << L) / HS_WAVE;  // (2^L >= 64)
+    uint32_t sum = 0;
+    for (int k = 0; k < per; ++k) sum += cur[lane * per + k];
+    uint32_t x = sum;
+    for (int d = 1; d < HS_WAVE; d <<= 1) {
+        const uint32_t up = __shfl_up(x, d, HS_WAVE);
+        if (lane >= d) x += up;
+    }
+    uint32_t run = x - sum;
+    for (int k = 0; k < per; ++k) {
+        const uint32_t c = cur[lane * per + k];
+        cur[lane * per + k] = run;
+        run += c;
+    }
+    rx_wave_handover();
+}
+
+// Ordered placement of the build rows rows[b, e) into out_rows[b, e): tuples arrive in row order; within a step, equal
+// slots take consecutive places in lane order.  Usually the 64 tuples of a step fall into 64 DIFFERENT slots (unique or
+// nearly unique build keys): every lane leaves its number in a tag byte of its slot and reads it back - all lanes find
+// their own: no ranking needed (the ten ballots per step were a third of this kernel).  Tuple i's slot is
+// slot(load(i)): the load is prefetched a step ahead, the slot worked out when the step comes.
+template <typename Load, typename Slot>
+__device__ __forceinline__ void jx_place(uint32_t* cur, uint32_t* head, uint8_t* tag, int L, int64_t b, int64_t e, int lane, Load load,
+                                         Slot slot, const uint32_t* rows, uint32_t* out_rows) {
+    const uint64_t below = (1ull << lane) - 1ull;
+    decltype(load(b)) nt{};
+    uint32_t nrow = 0u;
+    if (b + lane < e) {
+        nt = load(b + lane);
+        nrow = rows[b + lane];
+    }
+    for (int64_t base = b; base < e; base += HS_WAVE) {
+        const bool valid = base + lane < e;
+        const uint32_t s = slot(nt), row = nrow;
+        if (base + HS_WAVE + lane < e) {
+            nt = load(base + HS_WAVE + lane);
+            nrow = rows[base + HS_WAVE + lane];
+        }
+        if (valid) tag[s] = (uint8_t)lane;
+        rx_wave_handover();
+        const bool shared_slot = valid && tag[s] != (uint8_t)lane;
+        const uint32_t at = valid ? cur[s] : 0u;
+        const uint32_t first = valid ? head[s] : 0u;
+        if (__ballot(shared_slot) == 0) {  // (wave-uniform) 64 different slots: nothing to rank
+            if (valid) {
+                out_rows[b + at] = row;
+                cur[s] = at + 1u;
+                if (first == JD_EMPTY) head[s] = row;
+            }
+            rx_wave_handover();
+            continue;
+        }
+        uint64_t peers = __ballot(valid);
+        for (int bit = 0; bit < L; ++bit) {
+            const bool on = (s >> bit) & 1u;
+            const uint64_t bal = __ballot(valid && on);
+            peers &= on ? bal : ~bal;
+        }
+        const uint32_t rank = (uint32_t)__popcll(peers & below);
+        rx_wave_handover();  // every lane has read its slot's cursor before a leader moves it
+        if (valid) {
+            out_rows[b + at + rank] = row;
+            if (rank == 0) {
+                cur[s] = at + (uint32_t)__popcll(peers);
+                if (first == JD_EMPTY) head[s] = row;  // the step's lowest lane of the slot holds its lowest row
+            }
+        }
+        rx_wave_handover();
+    }
+}
+
+// the words of slots [0, live), store(s, word) (coalesced): JD_EMPTY, the one build row, or JD_MULTI + the list's start, whose
+// length goes to list_count there.  Lists lie in SLOT order, so list s starts where list s - 1 ends.
+template <typename Store>
+__device__ __forceinline__ void jx_emit(const uint32_t* cur, const uint32_t* head, int64_t b, int64_t live, int lane, uint32_t* list_count,
+                                        Store store) {
+    for (int s = lane; s < live; s += HS_WAVE) {
+        const uint32_t end = cur[s], start = s ? cur[s - 1] : 0u;
+        const uint32_t c = end - start;
+        uint32_t word = JD_EMPTY;
+        if (c == 1) word = head[s];
+        else if (c > 1) {
+            word = JD_MULTI | (uint32_t)(b + start);
+            list_count[b + start] = c;
+        }
+        store(s, word);
+    }
+    rx_wave_handover();
+}
 
 struct JdAssemble {
     const int64_t* seg_start;  // [parts + 1] tuple ranges of the partitions
@@ -1766,12 +1896,12 @@ __global__ void __launch_bounds__(256) k_jd_assemble(const JdAssemble A) {
     extern __shared__ __align__(16) uint32_t jd_lds[];
     const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE, wpb = blockDim.x / HS_WAVE;
     const int W = 1 << A.L;
-    uint32_t* cur = jd_lds + (size_t)w * (2 * W + W / 4);  // counts, then list cursors
-    uint32_t* head = cur + W;                    // the first (= lowest) build row of every slot
-    uint8_t* tag = (uint8_t*)(head + W);         // placement: the lane that came by last in this step
-    const uint64_t below = (1ull << lane) - 1ull;
-    const int per = W / HS_WAVE;  // consecutive slots of a lane in the scan (W >= 64)
+    uint32_t* cur = jd_lds + (size_t)w * (2 * W + W / 4);
+    uint32_t* head = cur + W;
+    uint8_t* tag = (uint8_t*)(head + W);
     const uint32_t wmask = (uint32_t)(W - 1), kmin = (uint32_t)A.key_min;
+    const auto key_at = [&](int64_t i) { return A.keys[i]; };
+    const auto slot = [=](int32_t key) { return ((uint32_t)key - kmin) & wmask; };
     uint32_t err = 0;
     for (int64_t p = (int64_t)blockIdx.x * wpb + w; p < A.parts; p += (int64_t)gridDim.x * wpb) {
         const int64_t b = A.seg_start[p], e = A.seg_start[p + 1];
@@ -1780,95 +1910,12 @@ __global__ void __launch_bounds__(256) k_jd_assemble(const JdAssemble A) {
             if (e > b) err |= HS_FLAG_BAD_PROGRAM;  // a key past the declared range
             continue;
         }
-        // the first step's tuples are asked for before the tables are cleared; every later step's before the current one
-        // is worked on (a wave walks its partition in order: without this it paid one global round trip per step)
-        int32_t nkey = b + lane < e ? A.keys[b + lane] : 0;
-        for (int s = lane; s < W; s += HS_WAVE) {
-            cur[s] = 0;
-            head[s] = JD_EMPTY;
-        }
-        rx_wave_handover();
-        for (int64_t base = b; base < e; base += HS_WAVE) {
-            const int32_t key = nkey;
-            const bool valid = base + lane < e;
-            if (base + HS_WAVE + lane < e) nkey = A.keys[base + HS_WAVE + lane];
-            if (valid) atomicAdd(&cur[((uint32_t)key - kmin) & wmask], 1u);  // LDS; counting is order-free
-        }
-        rx_wave_handover();
-        // exclusive scan of the W counts: a lane's consecutive slots, then a scan over the lanes
-        uint32_t sum = 0;
-        for (int k = 0; k < per; ++k) sum += cur[lane * per + k];
-        uint32_t x = sum;
-        for (int d = 1; d < HS_WAVE; d <<= 1) {
-            const uint32_t up = __shfl_up(x, d, HS_WAVE);
-            if (lane >= d) x += up;
-        }
-        uint32_t run = x - sum;
-        for (int k = 0; k < per; ++k) {
-            const uint32_t c = cur[lane * per + k];
-            cur[lane * per + k] = run;
-            run += c;
-        }
-        rx_wave_handover();
-        // ordered placement: tuples arrive in row order; within a step, equal slots take consecutive places in lane order.
-        // Usually the 64 tuples of a step fall into 64 DIFFERENT slots (unique or nearly unique build keys): every lane
-        // leaves its number in a tag byte of its slot and reads it back - all lanes find their own: no ranking needed (the
-        // ten ballots per step were a third of this kernel).
-        nkey = b + lane < e ? A.keys[b + lane] : 0;
-        uint32_t nrow = b + lane < e ? A.rows[b + lane] : 0u;
-        for (int64_t base = b; base < e; base += HS_WAVE) {
-            const bool valid = base + lane < e;
-            const uint32_t s = ((uint32_t)nkey - kmin) & wmask;
-            const uint32_t row = nrow;
-            if (base + HS_WAVE + lane < e) {
-                nkey = A.keys[base + HS_WAVE + lane];
-                nrow = A.rows[base + HS_WAVE + lane];
-            }
-            if (valid) tag[s] = (uint8_t)lane;
-            rx_wave_handover();
-            const bool shared_slot = valid && tag[s] != (uint8_t)lane;
-            const uint32_t at = valid ? cur[s] : 0u;
-            const uint32_t first = valid ? head[s] : 0u;
-            if (__ballot(shared_slot) == 0) {  // wave-uniform
-                if (valid) {
-                    A.out_rows[b + at] = row;
-                    cur[s] = at + 1u;
-                    if (first == JD_EMPTY) head[s] = row;
-                }
-                rx_wave_handover();
-                continue;
-            }
-            uint64_t peers = __ballot(valid);
-            for (int bit = 0; bit < A.L; ++bit) {
-                const bool on = (s >> bit) & 1u;
-                const uint64_t bal = __ballot(valid && on);
-                peers &= on ? bal : ~bal;
-            }
-            const uint32_t rank = (uint32_t)__popcll(peers & below);
-            rx_wave_handover();  // every lane has read its slot's cursor before a leader moves it
-            if (valid) {
-                A.out_rows[b + at + rank] = row;
-                if (rank == 0) {
-                    cur[s] = at + (uint32_t)__popcll(peers);
-                    if (first == JD_EMPTY) head[s] = row;  // the step's lowest lane of the slot holds its lowest row
-                }
-            }
-            rx_wave_handover();
-        }
-        // the partition's slice of the slot words (coalesced): lists are contiguous, so list s starts where list s - 1 ends
+        jx_count(cur, head, A.L, b, e, lane, key_at, [](int) {}, [&](int32_t key, int64_t) { return (int)slot(key); });
+        jx_scan(cur, A.L, lane);
+        jx_place(cur, head, tag, A.L, b, e, lane, key_at, slot, A.rows, A.out_rows);
+        // the partition's slice of the slot words
         const int64_t live = A.slots - slot0 < W ? A.slots - slot0 : W;
-        for (int s = lane; s < live; s += HS_WAVE) {
-            const uint32_t end = cur[s], start = s ? cur[s - 1] : 0u;
-            const uint32_t c = end - start;
-            uint32_t word = JD_EMPTY;
-            if (c == 1) word = head[s];
-            else if (c > 1) {
-                word = JD_MULTI | (uint32_t)(b + start);
-                A.list_count[b + start] = c;
-            }
-            A.words[slot0 + s] = word;
-        }
-        rx_wave_handover();
+        jx_emit(cur, head, b, live, lane, A.list_count, [&](int s, uint32_t word) { A.words[slot0 + s] = word; });
     }
     if (err) atomicOr(A.flags, err);
 }
@@ -1883,27 +1930,45 @@ __global__ void __launch_bounds__(256) k_jd_setup(uint32_t* iota, int64_t n_iota
     }
 }
 
-// the passes' geometry for a key range of `slots` slots: L = slots per partition (log2), bits1 + bits2 = partition bits
-static void jd_geometry(int64_t slots, int& L, int& bits1, int& bits2) {
-    int S = 0;
-    while (S < 31 && ((int64_t)1 << S) < slots) ++S;
-    L = 9;  // 512 slots: 4.5 KB of LDS per wave in the assembly (it runs on the number of waves a CU holds) ...
-    if (S - L > 2 * RX_MAX_BITS) L = S - 2 * RX_MAX_BITS;  // ... more when 65 536 partitions would not cover the range
-    const int bits = S > L ? S - L : 0;
-    bits1 = bits <= RX_MAX_BITS ? bits : (bits + 1) / 2;
-    bits2 = bits - bits1;
+// ---- the build's host side, shared by the three forms -----------------------------------------------------------------
+enum JxForm { JX_DENSE, JX_HASH, JX_HASH_STR };
+constexpr int JH_L_SMALL = 9, JH_L_LARGE = 10;  // window sizes of the hashed forms (log2), see their section below
+
+static int64_t jh_windows(int64_t n_build, int L) {   // ~1.75 slots per build row: distinct keys <= rows
+    const int64_t w = (n_build * 7 / 4 + ((int64_t)1 << L) - 1) >> L;
+    return w < 1 ? 1 : w;
 }
-struct JdLayout {
-    size_t keys_a, rows_a, keys_b, rows_b, iota, seg0, seg1, seg2, tb0, tb1, cnt, scan, scan_ws, total;
-    int64_t tiles1, tiles2, nseg1, parts, counters;
+
+struct JxLayout {
+    size_t keys_a, rows_a, keys_b, rows_b, iota, slot_of, win, fp, fp_a, fp_b, seg0, seg1, seg2, tb0, tb1, cnt, scan, scan_ws, total;
+    int64_t tiles1, tiles2, nseg1, parts, counters, windows;
     int L, bits1, bits2;
 };
-static bool jd_layout(int64_t n, int64_t slots, JdLayout& Y) {
-    if (n < 0 || n >= 0x7fffffffll || slots < 1 || slots > ((int64_t)1 << 29)) return false;  // a slot word holds a row in 31 bits
-    jd_geometry(slots, Y.L, Y.bits1, Y.bits2);
-    if (Y.L > JD_MAX_L) return false;  // (slots <= 2^29 with 16 partition bits)
+// Geometry and workspace of a build of n rows.  Dense: partitions of 2^L consecutive slots of the key range `slots`; hashed:
+// `windows` windows of 2^L slots.  The partition passes' arrays, then the hashed forms' slot scratch and the STRING form's
+// window numbers and fingerprints.
+static bool jx_layout(JxForm form, int64_t n, int64_t slots, JxLayout& Y) {
+    if (n < 0 || n >= 0x7fffffffll) return false;  // a slot word holds a row in 31 bits
+    int bits = 0;
+    if (form == JX_DENSE) {
+        if (slots < 1 || slots > ((int64_t)1 << 29)) return false;
+        int S = 0;
+        while (S < 31 && ((int64_t)1 << S) < slots) ++S;
+        Y.L = 9;  // 512 slots: 4.5 KB of LDS per wave in the assembly (it runs on the number of waves a CU holds) ...
+        if (S - Y.L > 2 * RX_MAX_BITS) Y.L = S - 2 * RX_MAX_BITS;  // ... more when 65 536 partitions would not cover the range
+        if (Y.L > JD_MAX_L) return false;  // (slots <= 2^29 with 16 partition bits)
+        bits = S > Y.L ? S - Y.L : 0;
+        Y.windows = 0;
+    } else {
+        Y.L = jh_windows(n, JH_L_SMALL) <= ((int64_t)1 << (2 * RX_MAX_BITS)) ? JH_L_SMALL : JH_L_LARGE;
+        Y.windows = jh_windows(n, Y.L);
+        while (((int64_t)1 << bits) < Y.windows) ++bits;
+        if (bits > 2 * RX_MAX_BITS) return false;  // 65 536 windows = 38 M build rows per call
+    }
+    Y.bits1 = bits <= RX_MAX_BITS ? bits : (bits + 1) / 2;
+    Y.bits2 = bits - Y.bits1;
     Y.nseg1 = (int64_t)1 << Y.bits1;
-    Y.parts = (int64_t)1 << (Y.bits1 + Y.bits2);
+    Y.parts = (int64_t)1 << bits;
     Y.tiles1 = n / RX_TILE + 2;
     Y.tiles2 = Y.bits2 ? n / RX_TILE + Y.nseg1 + 1 : 0;
     const int64_t c1 = Y.tiles1 << Y.bits1, c2 = Y.tiles2 << Y.bits2;
@@ -1914,11 +1979,18 @@ static bool jd_layout(int64_t n, int64_t slots, JdLayout& Y) {
         off += rx_align(bytes);
         return at;
     };
-    Y.keys_a = take((size_t)n * 4 + 64);
-    Y.rows_a = take((size_t)n * 4 + 64);
-    Y.keys_b = take(Y.bits2 ? (size_t)n * 4 + 64 : 0);
-    Y.rows_b = take(Y.bits2 ? (size_t)n * 4 + 64 : 0);
-    Y.iota = take(Y.bits1 ? 64 : (size_t)n * 4 + 64);  // row ids travel from the first pass on; needed as an array only without passes
+    const size_t col = (size_t)n * 4 + 64;  // one 4-byte column
+    const bool str = form == JX_HASH_STR;
+    Y.keys_a = take(col);
+    Y.rows_a = take(col);
+    Y.keys_b = take(Y.bits2 ? col : 0);
+    Y.rows_b = take(Y.bits2 ? col : 0);
+    Y.iota = take(Y.bits1 ? 64 : col);  // row ids travel from the first pass on; needed as an array only without passes
+    Y.slot_of = take(form == JX_DENSE ? 0 : (size_t)n * 2 + 64);
+    Y.win = take(str ? col : 0);
+    Y.fp = take(str ? col : 0);
+    Y.fp_a = take(str && Y.bits1 ? col : 0);
+    Y.fp_b = take(str && Y.bits2 ? col : 0);
     Y.seg0 = take(16);
     Y.seg1 = take((size_t)(Y.nseg1 + 1) * 8);
     Y.seg2 = take((size_t)(Y.parts + 1) * 8);
@@ -1931,21 +2003,19 @@ static bool jd_layout(int64_t n, int64_t slots, JdLayout& Y) {
     return true;
 }
 
-extern "C" size_t hs_join_dense_ws_bytes(int64_t n_build, int64_t slots) {
-    JdLayout Y;
-    return jd_layout(n_build, slots, Y) ? Y.total : 0;
-}
-
-extern "C" int hs_join_dense_build(void* stream_, const int32_t* build_keys, int64_t n_build, int32_t key_min, int64_t slots,
-                                   uint32_t* words, uint32_t* rows, uint32_t* list_count, void* ws_, uint32_t* flags) {
-    JdLayout Y;
-    if ((!build_keys && n_build > 0) || !words || !rows || !list_count || !ws_ || !flags || !jd_layout(n_build, slots, Y)) {
-        hs_set_error("hs_join_dense_build: bad arguments (n_build < 2^31, 1 <= slots <= 2^29)");
-        return HS_E_ARG;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
-    uint8_t* ws = (uint8_t*)ws_;
-    const int64_t n = n_build;
+// what one assembly launch reads: (partition key, row id[, third column]) tuples in partition order, and their ranges
+struct JxTuples {
+    const void* keys;
+    const uint32_t* rows;
+    const uint32_t* third;
+    const int64_t* seg;  // [parts + 1]
+    int64_t parts;
+};
+// Row ids, then one or two stable partition passes (RxPass.range = range, range_bias = bias) on the bits1 + bits2 bits of
+// the 4-byte partition key `key` above bit `low`; `third` (4 bytes per row, or null) travels along.  Without passes (one
+// partition) the tuples are the columns themselves and the row ids 0 .. n-1; without rows every partition is empty.
+static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const JxLayout& Y, int64_t n, const void* key, int range,
+                        int32_t bias, int low, const uint32_t* third, JxTuples& T) {
     uint32_t* iota = (uint32_t*)(ws + Y.iota);
     int64_t* seg0 = (int64_t*)(ws + Y.seg0);
     int64_t* seg1 = (int64_t*)(ws + Y.seg1);
@@ -1954,77 +2024,105 @@ extern "C" int hs_join_dense_build(void* stream_, const int32_t* build_keys, int
     int64_t grid = (n_iota + 255) / 256;
     grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
     hipLaunchKernelGGL(k_jd_setup, dim3((unsigned)grid), dim3(256), 0, stream, iota, n_iota, n, seg0);
-    RX_CHECK_LAUNCH("hs_join_dense_build (row ids)");
-    const int32_t* t_keys = build_keys;
-    const uint32_t* t_rows = iota;
-    const int64_t* seg = seg0;
-    if (Y.bits1 > 0 && n > 0) {
-        RxPass P;
-        std::memset(&P, 0, sizeof(P));
-        P.n_cols = 2;
-        P.esize[0] = P.esize[1] = 4;
-        P.range = 1;
-        P.range_bias = key_min;
-        P.key = hs_col{HS_I32, -1, build_keys, nullptr, nullptr};
-        P.row0 = 0;
-        // pass 1: the top bits1 bits of the slot over the one segment [0, n)
-        P.seg_start = seg0;
-        P.tile_base = (int64_t*)(ws + Y.tb0);
-        P.n_seg = 1;
-        P.shift = Y.L + Y.bits2;
-        P.bits = Y.bits1;
-        P.first = 1;
-        P.src[1] = nullptr;  // the row id column is the position (k_rx_scatter4)
-        P.dst[0] = ws + Y.keys_a;
-        P.dst[1] = ws + Y.rows_a;
-        int rc = rx_pass(stream, P, Y.tiles1, (int64_t*)(ws + Y.cnt), (int64_t*)(ws + Y.scan), ws + Y.scan_ws, n, Y.bits2 ? seg1 : seg2);
-        if (rc != HS_OK) return rc;
-        t_keys = (const int32_t*)(ws + Y.keys_a);
-        t_rows = (const uint32_t*)(ws + Y.rows_a);
-        seg = seg2;
-        if (Y.bits2) {  // pass 2: the next bits2 bits inside every segment of pass 1
-            P.seg_start = seg1;
-            P.tile_base = (int64_t*)(ws + Y.tb1);
-            P.n_seg = Y.nseg1;
-            P.shift = Y.L;
-            P.bits = Y.bits2;
-            P.first = 0;
-            P.src[0] = ws + Y.keys_a;
-            P.src[1] = ws + Y.rows_a;
-            P.dst[0] = ws + Y.keys_b;
-            P.dst[1] = ws + Y.rows_b;
-            rc = rx_pass(stream, P, Y.tiles2, (int64_t*)(ws + Y.cnt), (int64_t*)(ws + Y.scan), ws + Y.scan_ws, n, seg2);
-            if (rc != HS_OK) return rc;
-            t_keys = (const int32_t*)(ws + Y.keys_b);
-            t_rows = (const uint32_t*)(ws + Y.rows_b);
-        }
-    } else if (Y.bits1 > 0) {  // no rows: every partition is empty
-        hs_memset_async(seg2, 0, (size_t)(Y.parts + 1) * 8, stream);
-        seg = seg2;
+    if (hipGetLastError() != hipSuccess) {
+        hs_set_error("%s (row ids): kernel launch failed", who);
+        return HS_E_LAUNCH;
     }
-    JdAssemble A;
-    A.seg_start = seg;
-    A.parts = Y.bits1 > 0 ? Y.parts : 1;
-    A.keys = t_keys;
-    A.rows = t_rows;
-    A.slots = slots;
-    A.key_min = key_min;
-    A.L = Y.L;
-    A.words = words;
-    A.out_rows = rows;
-    A.list_count = list_count;
-    A.n = n;
-    A.flags = flags;
+    T = JxTuples{key, iota, third, seg0, 1};
+    if (Y.bits1 == 0) return HS_OK;
+    T.seg = seg2;
+    T.parts = Y.parts;
+    if (n == 0) {  // no rows: every partition is empty
+        hs_memset_async(seg2, 0, (size_t)(Y.parts + 1) * 8, stream);
+        return HS_OK;
+    }
+    RxPass P;
+    std::memset(&P, 0, sizeof(P));
+    P.n_cols = third ? 3 : 2;
+    P.esize[0] = P.esize[1] = 4;
+    if (third) P.esize[2] = 4;
+    P.range = range;
+    P.range_bias = bias;
+    P.key = hs_col{HS_I32, -1, key, nullptr, nullptr};
+    P.row0 = 0;
+    // pass 1: the top bits1 bits over the one segment [0, n)
+    P.seg_start = seg0;
+    P.tile_base = (int64_t*)(ws + Y.tb0);
+    P.n_seg = 1;
+    P.shift = low + Y.bits2;
+    P.bits = Y.bits1;
+    P.first = 1;
+    P.src[1] = nullptr;  // the row id column is the position (k_rx_scatter4)
+    P.src[2] = third;
+    P.dst[0] = ws + Y.keys_a;
+    P.dst[1] = ws + Y.rows_a;
+    P.dst[2] = third ? ws + Y.fp_a : nullptr;
+    int rc = rx_pass(stream, P, Y.tiles1, (int64_t*)(ws + Y.cnt), (int64_t*)(ws + Y.scan), ws + Y.scan_ws, n, Y.bits2 ? seg1 : seg2);
+    if (rc != HS_OK) return rc;
+    T.keys = ws + Y.keys_a;
+    T.rows = (const uint32_t*)(ws + Y.rows_a);
+    if (third) T.third = (const uint32_t*)(ws + Y.fp_a);
+    if (Y.bits2) {  // pass 2: the next bits2 bits inside every segment of pass 1
+        P.seg_start = seg1;
+        P.tile_base = (int64_t*)(ws + Y.tb1);
+        P.n_seg = Y.nseg1;
+        P.shift = low;
+        P.bits = Y.bits2;
+        P.first = 0;
+        P.src[0] = ws + Y.keys_a;
+        P.src[1] = ws + Y.rows_a;
+        P.src[2] = third ? ws + Y.fp_a : nullptr;
+        P.dst[0] = ws + Y.keys_b;
+        P.dst[1] = ws + Y.rows_b;
+        P.dst[2] = third ? ws + Y.fp_b : nullptr;
+        rc = rx_pass(stream, P, Y.tiles2, (int64_t*)(ws + Y.cnt), (int64_t*)(ws + Y.scan), ws + Y.scan_ws, n, seg2);
+        if (rc != HS_OK) return rc;
+        T.keys = ws + Y.keys_b;
+        T.rows = (const uint32_t*)(ws + Y.rows_b);
+        if (third) T.third = (const uint32_t*)(ws + Y.fp_b);
+    }
+    return HS_OK;
+}
+
+// one launch path for the assembly kernels: one wave per partition, per_wave bytes of LDS each, wpb waves per block.  Each
+// kernel whose blocks may take more than 64 KB of LDS (max_lds) asks for it once per device - every instantiation of this
+// template has its own flag.
+template <auto K, typename Args>
+static int jx_assemble(hipStream_t stream, const char* who, const Args& A, int64_t parts, size_t per_wave, int wpb, int max_lds) {
+    static unsigned long long attr_set = 0;
+    if (max_lds > 65536 && hs_first_on_device(attr_set))
+        (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    int64_t g = (parts + wpb - 1) / wpb;
+    if (g > 256 * 32) g = 256 * 32;
+    hipLaunchKernelGGL(K, dim3((unsigned)g), dim3(HS_WAVE * wpb), per_wave * wpb, stream, A);
+    if (hipGetLastError() != hipSuccess) {
+        hs_set_error("%s (assemble): kernel launch failed", who);
+        return HS_E_LAUNCH;
+    }
+    return HS_OK;
+}
+
+extern "C" size_t hs_join_dense_ws_bytes(int64_t n_build, int64_t slots) {
+    JxLayout Y;
+    return jx_layout(JX_DENSE, n_build, slots, Y) ? Y.total : 0;
+}
+
+extern "C" int hs_join_dense_build(void* stream_, const int32_t* build_keys, int64_t n_build, int32_t key_min, int64_t slots,
+                                   uint32_t* words, uint32_t* rows, uint32_t* list_count, void* ws_, uint32_t* flags) {
+    JxLayout Y;
+    if ((!build_keys && n_build > 0) || !words || !rows || !list_count || !ws_ || !flags || !jx_layout(JX_DENSE, n_build, slots, Y)) {
+        hs_set_error("hs_join_dense_build: bad arguments (n_build < 2^31, 1 <= slots <= 2^29)");
+        return HS_E_ARG;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    JxTuples T;
+    const int rc = jx_partition(stream, "hs_join_dense_build", (uint8_t*)ws_, Y, n_build, build_keys, 1, key_min, Y.L, nullptr, T);
+    if (rc != HS_OK) return rc;
+    const JdAssemble A{T.seg, T.parts, (const int32_t*)T.keys, T.rows, slots, key_min, Y.L, words, rows, list_count, n_build, flags};
     const size_t per_wave = (size_t)9 << Y.L;  // cursors + first rows (uint32) + tag bytes
     int wpb = (int)(65536 / per_wave);
     wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
-    int64_t g = (A.parts + wpb - 1) / wpb;
-    if (g > 256 * 32) g = 256 * 32;
-    static unsigned long long attr_set = 0;
-    if (hs_first_on_device(attr_set)) (void)hipFuncSetAttribute((const void*)k_jd_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, 9 << JD_MAX_L);
-    hipLaunchKernelGGL(k_jd_assemble, dim3((unsigned)g), dim3(HS_WAVE * wpb), per_wave * wpb, stream, A);
-    RX_CHECK_LAUNCH("hs_join_dense_build (assemble)");
-    return HS_OK;
+    return jx_assemble<k_jd_assemble>(stream, "hs_join_dense_build", A, T.parts, per_wave, wpb, 9 << JD_MAX_L);
 }
 
 struct JdProbe {
@@ -2044,6 +2142,43 @@ typedef int jd_i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned jd_u32x4 __attribute__((ext_vector_type(4)));
 typedef long long jd_i64x2 __attribute__((ext_vector_type(2)));
 
+// a slot word -> the probe row's match count, first build row and list start (a list's length and first row are read only
+// for a key with several partners)
+__device__ __forceinline__ void jx_resolve(uint32_t word, const uint32_t* rows, const uint32_t* list_count, uint32_t& cnt, uint32_t& first,
+                                           uint32_t& st) {
+    const bool multi = word != JD_EMPTY && (word & JD_MULTI);
+    st = multi ? word & ~JD_MULTI : 0u;
+    cnt = word == JD_EMPTY ? 0u : 1u;
+    first = word;
+    if (multi) {
+        cnt = list_count[st];
+        first = rows[st];
+    }
+}
+
+// the count pass's results for probe rows 4q .. 4q + 3 from their slot words: counts[], and in aux the first build rows,
+// then (from `second` on) the list starts - 16-byte nontemporal stores where all four rows exist
+__device__ __forceinline__ void jx_count_out(const uint32_t* word, int64_t q, int64_t n, const uint32_t* rows, const uint32_t* list_count,
+                                             int64_t* counts, uint32_t* aux) {
+    const int64_t second = (n + 3) & ~(int64_t)3;
+    uint32_t cnt[4], first[4], st[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) jx_resolve(word[j], rows, list_count, cnt[j], first[j], st[j]);
+    if (q * 4 + 3 < n) {
+        int64_t* c = counts + q * 4;
+        __builtin_nontemporal_store(jd_i64x2{(long long)cnt[0], (long long)cnt[1]}, reinterpret_cast<jd_i64x2*>(c));
+        __builtin_nontemporal_store(jd_i64x2{(long long)cnt[2], (long long)cnt[3]}, reinterpret_cast<jd_i64x2*>(c + 2));
+        __builtin_nontemporal_store(jd_u32x4{first[0], first[1], first[2], first[3]}, reinterpret_cast<jd_u32x4*>(aux) + q);
+        __builtin_nontemporal_store(jd_u32x4{st[0], st[1], st[2], st[3]}, reinterpret_cast<jd_u32x4*>(aux + second) + q);
+    } else {
+        for (int j = 0; j < 4 && q * 4 + j < n; ++j) {
+            counts[q * 4 + j] = (int64_t)cnt[j];
+            aux[q * 4 + j] = first[j];
+            aux[second + q * 4 + j] = st[j];
+        }
+    }
+}
+
 // Probe, pass 1: four keys per lane (one 16-byte load; buffers carry slack past n), ONE scattered 4-byte read per key - its
 // slot word says "no partner", names the one partner, or points at a list (then, and only then, two more reads: the
 // list's length and its first row); the four lookups of a lane are in flight together.  What the fill pass needs is written
@@ -2051,43 +2186,20 @@ typedef long long jd_i64x2 __attribute__((ext_vector_type(2)));
 // scattered arrays for a key with one partner - the usual case.
 __global__ void __launch_bounds__(256) k_jd_count(const JdProbe A) {
     const int64_t nq = (A.n + 3) / 4;
-    const int64_t second = (A.n + 3) & ~(int64_t)3;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
         const jd_i32x4 kv = __builtin_nontemporal_load(reinterpret_cast<const jd_i32x4*>(A.keys) + q);
         const int32_t k[4] = {kv.x, kv.y, kv.z, kv.w};
-        uint32_t word[4], cnt[4], first[4], st[4];
+        uint32_t word[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int64_t o = (int64_t)k[j] - (int64_t)A.key_min;
             const bool in = q * 4 + j < A.n && (uint64_t)o < (uint64_t)A.slots;
             word[j] = in ? A.words[o] : JD_EMPTY;
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool multi = word[j] != JD_EMPTY && (word[j] & JD_MULTI);
-            st[j] = multi ? word[j] & ~JD_MULTI : 0u;
-            cnt[j] = word[j] == JD_EMPTY ? 0u : 1u;
-            first[j] = word[j];
-            if (multi) {
-                cnt[j] = A.list_count[st[j]];
-                first[j] = A.rows[st[j]];
-            }
-        }
-        if (q * 4 + 3 < A.n) {
-            int64_t* c = A.counts + q * 4;
-            __builtin_nontemporal_store(jd_i64x2{(long long)cnt[0], (long long)cnt[1]}, reinterpret_cast<jd_i64x2*>(c));
-            __builtin_nontemporal_store(jd_i64x2{(long long)cnt[2], (long long)cnt[3]}, reinterpret_cast<jd_i64x2*>(c + 2));
-            __builtin_nontemporal_store(jd_u32x4{first[0], first[1], first[2], first[3]}, reinterpret_cast<jd_u32x4*>(A.aux) + q);
-            __builtin_nontemporal_store(jd_u32x4{st[0], st[1], st[2], st[3]}, reinterpret_cast<jd_u32x4*>(A.aux + second) + q);
-        } else {
-            for (int j = 0; j < 4 && q * 4 + j < A.n; ++j) {
-                A.counts[q * 4 + j] = (int64_t)cnt[j];
-                A.aux[q * 4 + j] = first[j];
-                A.aux[second + q * 4 + j] = st[j];
-            }
-        }
+        jx_count_out(word, q, A.n, A.rows, A.list_count, A.counts, A.aux);
     }
 }
+
 
 // Probe, pass 2: pairs ordered by probe row, then build row.  A stream: output offsets (their differences are the match
 // counts), the first build rows, the pairs; only a probe row with several partners reads the rest of its list.
@@ -2177,28 +2289,25 @@ extern "C" int hs_join_dense_fill(void* stream, int64_t n_probe, const uint32_t*
 //     present key sits 1.7 slots from its start on average - the same 64-byte line nearly always).
 // The slot word is the dense form's (JD_EMPTY / the one build row / JD_MULTI + list start), rows[] and list_count[] too, so
 // the probe's second pass IS hs_join_dense_fill.
-// slots per window, log2: 512 (8.5 KB of LDS per wave: key cells, cursors, first rows, tag bytes - 18 waves per CU) while
-// 65 536 windows hold the build side (19 M rows), else 1024 (17 KB: 9 waves per CU; 38 M rows).  The assembly is a chain of LDS
-// round trips per 64-tuple step, one wave per window: it runs on the number of waves a CU holds.
-constexpr int JH_L_SMALL = 9, JH_L_LARGE = 10;
+// slots per window, log2 (JH_L_SMALL / JH_L_LARGE): 512 (8.5 KB of LDS per wave: key cells, cursors, first rows, tag bytes
+// - 18 waves per CU) while 65 536 windows hold the build side (19 M rows), else 1024 (17 KB: 9 waves per CU; 38 M rows).
+// The assembly is a chain of LDS round trips per 64-tuple step, one wave per window: it runs on the number of waves a CU
+// holds.
 constexpr uint64_t JH_FREE = ~0ull;            // LDS key cell: nobody here yet (a key occupies the low 32 bits only)
-
-static int64_t jh_windows(int64_t n_build, int L) {   // ~1.75 slots per build row: distinct keys <= rows
-    const int64_t w = (n_build * 7 / 4 + ((int64_t)1 << L) - 1) >> L;
-    return w < 1 ? 1 : w;
-}
 
 struct JhAssemble {
     const int64_t* seg_start;  // [parts + 1] tuple ranges of the partitions = windows (parts >= windows; the rest are empty)
     int64_t parts, windows;
-    const int32_t* keys;       // tuples, window by window, in row order inside a window
+    const uint32_t* keys;      // tuples, window by window, in row order inside a window: the INTEGER keys | the STRING fingerprints
     const uint32_t* rows;
-    uint2* table;              // [windows << L] {key, word}
+    hs_col key;                // STRING: the build key column (byte compares)
+    uint2* table;              // [windows << L] {key | fingerprint, word}
     uint32_t* out_rows;        // [n]: build rows window by window, slot by slot, ascending within a slot
     uint32_t* list_count;      // [n]: at the start of a list of several rows, its length
     uint16_t* slot_of;         // [n] scratch: the slot every tuple found in the counting pass (the placement pass reads it back
                                // with coalesced loads instead of walking the LDS window again)
-    uint32_t* flags;
+    uint32_t* status;          // HS_FLAG_DICT_FULL only
+    uint32_t* flags;           // anything else
 };
 
 // slot of `key` in the wave's LDS window, claiming a free cell on the way when INSERT; -1: the window is full (more
@@ -2221,258 +2330,85 @@ __device__ __forceinline__ int jh_slot(uint64_t* cell, uint32_t key, uint32_t st
 }
 
 template <int JH_L>
+__device__ __forceinline__ int js_slot(uint64_t* cell, const hs_col& key, uint32_t fp, uint32_t row);  // (the STRING section)
+
+// One wave per window of 2^JH_L slots: its tuples claim LDS key cells, then counts, scan, ordered placement and the finished
+// window (jx_*).  The key form is the only difference: an INTEGER tuple claims its key's cell (jh_slot), a STRING tuple
+// (fingerprint, row) a cell of its fingerprint whose key bytes are its own (js_slot).  A window with more distinct keys than
+// slots is stored empty and raises HS_FLAG_DICT_FULL in *status.
+template <int JH_L, bool STR>
 __global__ void __launch_bounds__(256) k_jh_assemble(const JhAssemble A) {
     extern __shared__ __align__(16) uint64_t jh_lds[];
-    constexpr int W = 1 << JH_L, per = W / HS_WAVE;
+    constexpr int W = 1 << JH_L;
     const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE, wpb = blockDim.x / HS_WAVE;
     uint64_t* cell = jh_lds + (size_t)w * (2 * W + W / 8);   // key cells
-    uint32_t* cur = (uint32_t*)(cell + W);         // counts, then list cursors
-    uint32_t* head = cur + W;                      // the first (= lowest) build row of every slot
-    uint8_t* tag = (uint8_t*)(head + W);           // placement: the lane that came by last in this step
-    const uint64_t below = (1ull << lane) - 1ull;
-    uint32_t err = 0;
+    uint32_t* cur = (uint32_t*)(cell + W);
+    uint32_t* head = cur + W;
+    uint8_t* tag = (uint8_t*)(head + W);
+    const auto tuple_at = [&](int64_t i) { return make_uint2(A.keys[i], STR ? A.rows[i] : 0u); };
+    const auto claim = [&](uint2 t, int64_t i) {
+        const int s = STR ? js_slot<JH_L>(cell, A.key, t.x, t.y) : jh_slot<true, JH_L>(cell, t.x, rx_mix32(t.x));
+        A.slot_of[i] = (uint16_t)s;
+        return s;
+    };
+    uint32_t err = 0, full_any = 0;
     for (int64_t p = (int64_t)blockIdx.x * wpb + w; p < A.parts; p += (int64_t)gridDim.x * wpb) {
         const int64_t b = A.seg_start[p], e = A.seg_start[p + 1];
         if (p >= A.windows) {
             if (e > b) err |= HS_FLAG_BAD_PROGRAM;  // a tuple past the last window: the passes and the table disagree
             continue;
         }
-        int32_t nkey = b + lane < e ? A.keys[b + lane] : 0;
-        for (int s = lane; s < W; s += HS_WAVE) {
-            cell[s] = JH_FREE;
-            cur[s] = 0;
-            head[s] = JD_EMPTY;
-        }
-        rx_wave_handover();
-        bool full = false;
-        for (int64_t base = b; base < e; base += HS_WAVE) {  // claim slots, count rows per slot
-            const uint32_t key = (uint32_t)nkey;
-            const bool valid = base + lane < e;
-            if (base + HS_WAVE + lane < e) nkey = A.keys[base + HS_WAVE + lane];
-            if (valid) {
-                const int s = jh_slot<true, JH_L>(cell, key, rx_mix32(key));
-                if (s < 0) full = true;
-                else atomicAdd(&cur[s], 1u);
-                A.slot_of[base + lane] = (uint16_t)s;
-            }
-        }
-        rx_wave_handover();
+        const bool full = jx_count(cur, head, JH_L, b, e, lane, tuple_at, [&](int s) { cell[s] = JH_FREE; }, claim);
         if (__ballot(full)) {  // (wave-uniform) leave the window empty and say so
-            err |= HS_FLAG_DICT_FULL;
+            full_any = HS_FLAG_DICT_FULL;
             for (int s = lane; s < W; s += HS_WAVE) A.table[(p << JH_L) + s] = make_uint2(0u, JD_EMPTY);
             continue;
         }
-        uint32_t sum = 0;
-        for (int k = 0; k < per; ++k) sum += cur[lane * per + k];
-        uint32_t x = sum;
-        for (int d = 1; d < HS_WAVE; d <<= 1) {
-            const uint32_t up = __shfl_up(x, d, HS_WAVE);
-            if (lane >= d) x += up;
-        }
-        uint32_t run = x - sum;
-        for (int k = 0; k < per; ++k) {
-            const uint32_t c = cur[lane * per + k];
-            cur[lane * per + k] = run;
-            run += c;
-        }
-        rx_wave_handover();
-        uint32_t nslot = b + lane < e ? A.slot_of[b + lane] : 0u;
-        uint32_t nrow = b + lane < e ? A.rows[b + lane] : 0u;
-        for (int64_t base = b; base < e; base += HS_WAVE) {  // ordered placement (see k_jd_assemble)
-            const bool valid = base + lane < e;
-            const uint32_t s = nslot, row = nrow;
-            if (base + HS_WAVE + lane < e) {
-                nslot = A.slot_of[base + HS_WAVE + lane];
-                nrow = A.rows[base + HS_WAVE + lane];
-            }
-            if (valid) tag[s] = (uint8_t)lane;
-            rx_wave_handover();
-            const bool shared_slot = valid && tag[s] != (uint8_t)lane;
-            const uint32_t at = valid ? cur[s] : 0u;
-            const uint32_t first = valid ? head[s] : 0u;
-            if (__ballot(shared_slot) == 0) {  // (wave-uniform) 64 different slots: nothing to rank
-                if (valid) {
-                    A.out_rows[b + at] = row;
-                    cur[s] = at + 1u;
-                    if (first == JD_EMPTY) head[s] = row;
-                }
-                rx_wave_handover();
-                continue;
-            }
-            uint64_t peers = __ballot(valid);
-            for (int bit = 0; bit < JH_L; ++bit) {
-                const bool on = (s >> bit) & 1u;
-                const uint64_t bal = __ballot(valid && on);
-                peers &= on ? bal : ~bal;
-            }
-            const uint32_t rank = (uint32_t)__popcll(peers & below);
-            rx_wave_handover();
-            if (valid) {
-                A.out_rows[b + at + rank] = row;
-                if (rank == 0) {
-                    cur[s] = at + (uint32_t)__popcll(peers);
-                    if (first == JD_EMPTY) head[s] = row;
-                }
-            }
-            rx_wave_handover();
-        }
-        // the finished window (coalesced).  Lists lie in SLOT order, so list s starts where the previous slot's ends.
-        for (int s = lane; s < W; s += HS_WAVE) {
-            const uint32_t end = cur[s], start = s ? cur[s - 1] : 0u;
-            const uint32_t c = end - start;
-            uint32_t word = JD_EMPTY;
-            if (c == 1) word = head[s];
-            else if (c > 1) {
-                word = JD_MULTI | (uint32_t)(b + start);
-                A.list_count[b + start] = c;
-            }
-            A.table[(p << JH_L) + s] = make_uint2((uint32_t)cell[s], word);
-        }
-        rx_wave_handover();
+        jx_scan(cur, JH_L, lane);
+        jx_place(cur, head, tag, JH_L, b, e, lane, [&](int64_t i) { return (uint32_t)A.slot_of[i]; }, [](uint32_t s) { return s; }, A.rows,
+                 A.out_rows);
+        jx_emit(cur, head, b, W, lane, A.list_count,
+                [&](int s, uint32_t word) { A.table[(p << JH_L) + s] = make_uint2((uint32_t)cell[s], word); });
     }
-    if (err) atomicOr(A.flags, err);
+    if (full_any && lane == 0) atomicOr(A.status, full_any);
+    if (err && lane == 0) atomicOr(A.flags, err);
 }
 
-struct JhLayout {
-    size_t keys_a, rows_a, keys_b, rows_b, iota, slot_of, seg0, seg1, seg2, tb0, tb1, cnt, scan, scan_ws, total;
-    int64_t tiles1, tiles2, nseg1, parts, counters, windows;
-    int bits1, bits2, L;
-};
-static bool jh_layout(int64_t n, JhLayout& Y) {
-    if (n < 0 || n >= 0x7fffffffll) return false;  // a slot word holds a row in 31 bits
-    Y.L = jh_windows(n, JH_L_SMALL) <= ((int64_t)1 << (2 * RX_MAX_BITS)) ? JH_L_SMALL : JH_L_LARGE;
-    Y.windows = jh_windows(n, Y.L);
-    int bits = 0;
-    while (((int64_t)1 << bits) < Y.windows) ++bits;
-    if (bits > 2 * RX_MAX_BITS) return false;  // 65 536 windows = 38 M build rows per call
-    Y.bits1 = bits <= RX_MAX_BITS ? bits : (bits + 1) / 2;
-    Y.bits2 = bits - Y.bits1;
-    Y.nseg1 = (int64_t)1 << Y.bits1;
-    Y.parts = (int64_t)1 << bits;
-    Y.tiles1 = n / RX_TILE + 2;
-    Y.tiles2 = Y.bits2 ? n / RX_TILE + Y.nseg1 + 1 : 0;
-    const int64_t c1 = Y.tiles1 << Y.bits1, c2 = Y.tiles2 << Y.bits2;
-    Y.counters = c1 > c2 ? c1 : c2;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += rx_align(bytes);
-        return at;
-    };
-    Y.keys_a = take((size_t)n * 4 + 64);
-    Y.rows_a = take((size_t)n * 4 + 64);
-    Y.keys_b = take(Y.bits2 ? (size_t)n * 4 + 64 : 0);
-    Y.rows_b = take(Y.bits2 ? (size_t)n * 4 + 64 : 0);
-    Y.iota = take(Y.bits1 ? 64 : (size_t)n * 4 + 64);
-    Y.slot_of = take((size_t)n * 2 + 64);
-    Y.seg0 = take(16);
-    Y.seg1 = take((size_t)(Y.nseg1 + 1) * 8);
-    Y.seg2 = take((size_t)(Y.parts + 1) * 8);
-    Y.tb0 = take(16);
-    Y.tb1 = take((size_t)(Y.nseg1 + 1) * 8);
-    Y.cnt = take((size_t)Y.counters * 8);
-    Y.scan = take((size_t)(Y.counters + 1) * 8);
-    Y.scan_ws = take(hs_scan_ws_bytes(Y.counters > 1 ? Y.counters : 1));
-    Y.total = off;
-    return true;
+// the assembly of the hashed forms over the partitioned tuples T (the window number's passes)
+template <bool STR>
+static int jh_assemble(hipStream_t stream, const char* who, const JxLayout& Y, const JxTuples& T, const hs_col& key, uint8_t* ws, void* table,
+                       uint32_t* rows, uint32_t* list_count, uint32_t* status, uint32_t* flags) {
+    const JhAssemble A{T.seg, T.parts, Y.windows, STR ? T.third : (const uint32_t*)T.keys, T.rows, key, (uint2*)table, rows, list_count,
+                       (uint16_t*)(ws + Y.slot_of), status, flags};
+    const size_t per_wave = (size_t)17 << Y.L;  // key cells (8 B) + cursors + first rows (4 B each) + tag bytes
+    constexpr int wpb = 4;
+    if (Y.L == JH_L_SMALL) return jx_assemble<k_jh_assemble<JH_L_SMALL, STR>>(stream, who, A, T.parts, per_wave, wpb, (17 << JH_L_SMALL) * wpb);
+    return jx_assemble<k_jh_assemble<JH_L_LARGE, STR>>(stream, who, A, T.parts, per_wave, wpb, (17 << JH_L_LARGE) * wpb);
 }
 
 extern "C" size_t hs_join_hash_ws_bytes(int64_t n_build) {
-    JhLayout Y;
-    return jh_layout(n_build, Y) ? Y.total : 0;
+    JxLayout Y;
+    return jx_layout(JX_HASH, n_build, 0, Y) ? Y.total : 0;
 }
 extern "C" int64_t hs_join_hash_slots(int64_t n_build) {
-    JhLayout Y;
-    return jh_layout(n_build, Y) ? Y.windows << Y.L : 0;
+    JxLayout Y;
+    return jx_layout(JX_HASH, n_build, 0, Y) ? Y.windows << Y.L : 0;
 }
 
 extern "C" int hs_join_hash_build(void* stream_, const int32_t* build_keys, int64_t n_build, void* table, uint32_t* rows,
-                                  uint32_t* list_count, void* ws_, uint32_t* flags) {
-    JhLayout Y;
-    if ((!build_keys && n_build > 0) || !table || !rows || !list_count || !ws_ || !flags || ((uintptr_t)table & 7) || !jh_layout(n_build, Y)) {
+                                  uint32_t* list_count, void* ws_, uint32_t* status, uint32_t* flags) {
+    JxLayout Y;
+    if ((!build_keys && n_build > 0) || !table || !rows || !list_count || !ws_ || !status || !flags || ((uintptr_t)table & 7) ||
+        !jx_layout(JX_HASH, n_build, 0, Y)) {
         hs_set_error("hs_join_hash_build: bad arguments (n_build <= 38 M rows, table 8-byte aligned)");
         return HS_E_ARG;
     }
     hipStream_t stream = (hipStream_t)stream_;
     uint8_t* ws = (uint8_t*)ws_;
-    const int64_t n = n_build;
-    uint32_t* iota = (uint32_t*)(ws + Y.iota);
-    int64_t* seg0 = (int64_t*)(ws + Y.seg0);
-    int64_t* seg1 = (int64_t*)(ws + Y.seg1);
-    int64_t* seg2 = (int64_t*)(ws + Y.seg2);
-    const int64_t n_iota = Y.bits1 ? 0 : n;
-    int64_t grid = (n_iota + 255) / 256;
-    grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
-    hipLaunchKernelGGL(k_jd_setup, dim3((unsigned)grid), dim3(256), 0, stream, iota, n_iota, n, seg0);
-    RX_CHECK_LAUNCH("hs_join_hash_build (row ids)");
-    const int32_t* t_keys = build_keys;
-    const uint32_t* t_rows = iota;
-    const int64_t* seg = seg0;
-    if (Y.bits1 > 0 && n > 0) {
-        RxPass P;
-        std::memset(&P, 0, sizeof(P));
-        P.n_cols = 2;
-        P.esize[0] = P.esize[1] = 4;
-        P.range = 2;
-        P.range_bias = (int32_t)Y.windows;
-        P.key = hs_col{HS_I32, -1, build_keys, nullptr, nullptr};
-        P.row0 = 0;
-        P.seg_start = seg0;  // pass 1: the top bits1 bits of the window number over the one segment [0, n)
-        P.tile_base = (int64_t*)(ws + Y.tb0);
-        P.n_seg = 1;
-        P.shift = Y.bits2;
-        P.bits = Y.bits1;
-        P.first = 1;
-        P.src[1] = nullptr;  // the row id column is the position (k_rx_scatter4)
-        P.dst[0] = ws + Y.keys_a;
-        P.dst[1] = ws + Y.rows_a;
-        int rc = rx_pass(stream, P, Y.tiles1, (int64_t*)(ws + Y.cnt), (int64_t*)(ws + Y.scan), ws + Y.scan_ws, n, Y.bits2 ? seg1 : seg2);
-        if (rc != HS_OK) return rc;
-        t_keys = (const int32_t*)(ws + Y.keys_a);
-        t_rows = (const uint32_t*)(ws + Y.rows_a);
-        seg = seg2;
-        if (Y.bits2) {  // pass 2: the low bits2 bits inside every segment of pass 1
-            P.seg_start = seg1;
-            P.tile_base = (int64_t*)(ws + Y.tb1);
-            P.n_seg = Y.nseg1;
-            P.shift = 0;
-            P.bits = Y.bits2;
-            P.first = 0;
-            P.src[0] = ws + Y.keys_a;
-            P.src[1] = ws + Y.rows_a;
-            P.dst[0] = ws + Y.keys_b;
-            P.dst[1] = ws + Y.rows_b;
-            rc = rx_pass(stream, P, Y.tiles2, (int64_t*)(ws + Y.cnt), (int64_t*)(ws + Y.scan), ws + Y.scan_ws, n, seg2);
-            if (rc != HS_OK) return rc;
-            t_keys = (const int32_t*)(ws + Y.keys_b);
-            t_rows = (const uint32_t*)(ws + Y.rows_b);
-        }
-    } else if (Y.bits1 > 0) {  // no rows: every window is empty
-        hs_memset_async(seg2, 0, (size_t)(Y.parts + 1) * 8, stream);
-        seg = seg2;
-    }
-    JhAssemble A;
-    A.seg_start = seg;
-    A.parts = Y.bits1 > 0 ? Y.parts : 1;
-    A.windows = Y.windows;
-    A.keys = t_keys;
-    A.rows = t_rows;
-    A.table = (uint2*)table;
-    A.out_rows = rows;
-    A.list_count = list_count;
-    A.slot_of = (uint16_t*)(ws + Y.slot_of);
-    A.flags = flags;
-    const size_t per_wave = (size_t)17 << Y.L;  // key cells (8 B) + cursors + first rows (4 B each) + tag bytes
-    constexpr int wpb = 4;
-    int64_t g = (A.parts + wpb - 1) / wpb;
-    if (g > 256 * 32) g = 256 * 32;
-    static unsigned long long attr_set = 0;
-    if (hs_first_on_device(attr_set))
-        (void)hipFuncSetAttribute((const void*)k_jh_assemble<JH_L_LARGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (17 << JH_L_LARGE) * wpb);
-    if (Y.L == JH_L_SMALL) hipLaunchKernelGGL(k_jh_assemble<JH_L_SMALL>, dim3((unsigned)g), dim3(HS_WAVE * wpb), per_wave * wpb, stream, A);
-    else hipLaunchKernelGGL(k_jh_assemble<JH_L_LARGE>, dim3((unsigned)g), dim3(HS_WAVE * wpb), per_wave * wpb, stream, A);
-    RX_CHECK_LAUNCH("hs_join_hash_build (assemble)");
-    return HS_OK;
+    JxTuples T;
+    const int rc = jx_partition(stream, "hs_join_hash_build", ws, Y, n_build, build_keys, 2, (int32_t)Y.windows, 0, nullptr, T);
+    if (rc != HS_OK) return rc;
+    return jh_assemble<false>(stream, "hs_join_hash_build", Y, T, hs_col{}, ws, table, rows, list_count, status, flags);
 }
 
 struct JhProbe {
@@ -2492,11 +2428,10 @@ template <int JH_L>
 __global__ void __launch_bounds__(256) k_jh_count(const JhProbe A) {
     constexpr uint32_t wmask = (1u << JH_L) - 1u;
     const int64_t nq = (A.n + 3) / 4;
-    const int64_t second = (A.n + 3) & ~(int64_t)3;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
         const jd_i32x4 kv = __builtin_nontemporal_load(reinterpret_cast<const jd_i32x4*>(A.keys) + q);
         const uint32_t k[4] = {(uint32_t)kv.x, (uint32_t)kv.y, (uint32_t)kv.z, (uint32_t)kv.w};
-        uint32_t word[4], cnt[4], first[4], st[4], at[4];
+        uint32_t word[4], at[4];
         const uint2* win[4];
         uint2 slot[4];
 #pragma unroll
@@ -2514,38 +2449,15 @@ __global__ void __launch_bounds__(256) k_jh_count(const JhProbe A) {
             }
             word[j] = q * 4 + j < A.n && slot[j].x == k[j] ? slot[j].y : JD_EMPTY;
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool multi = word[j] != JD_EMPTY && (word[j] & JD_MULTI);
-            st[j] = multi ? word[j] & ~JD_MULTI : 0u;
-            cnt[j] = word[j] == JD_EMPTY ? 0u : 1u;
-            first[j] = word[j];
-            if (multi) {
-                cnt[j] = A.list_count[st[j]];
-                first[j] = A.rows[st[j]];
-            }
-        }
-        if (q * 4 + 3 < A.n) {
-            int64_t* c = A.counts + q * 4;
-            __builtin_nontemporal_store(jd_i64x2{(long long)cnt[0], (long long)cnt[1]}, reinterpret_cast<jd_i64x2*>(c));
-            __builtin_nontemporal_store(jd_i64x2{(long long)cnt[2], (long long)cnt[3]}, reinterpret_cast<jd_i64x2*>(c + 2));
-            __builtin_nontemporal_store(jd_u32x4{first[0], first[1], first[2], first[3]}, reinterpret_cast<jd_u32x4*>(A.aux) + q);
-            __builtin_nontemporal_store(jd_u32x4{st[0], st[1], st[2], st[3]}, reinterpret_cast<jd_u32x4*>(A.aux + second) + q);
-        } else {
-            for (int j = 0; j < 4 && q * 4 + j < A.n; ++j) {
-                A.counts[q * 4 + j] = (int64_t)cnt[j];
-                A.aux[q * 4 + j] = first[j];
-                A.aux[second + q * 4 + j] = st[j];
-            }
-        }
+        jx_count_out(word, q, A.n, A.rows, A.list_count, A.counts, A.aux);
     }
 }
 
 extern "C" int hs_join_hash_count(void* stream, const int32_t* probe_keys, int64_t n_probe, int64_t n_build, const void* table,
                                   const uint32_t* rows, const uint32_t* list_count, int64_t* counts, void* aux) {
-    JhLayout Y;
+    JxLayout Y;
     if ((!probe_keys && n_probe > 0) || n_probe < 0 || !table || !rows || !list_count || !counts || !aux || ((uintptr_t)probe_keys & 15) ||
-        ((uintptr_t)counts & 15) || ((uintptr_t)aux & 15) || !jh_layout(n_build, Y)) {
+        ((uintptr_t)counts & 15) || ((uintptr_t)aux & 15) || !jx_layout(JX_HASH, n_build, 0, Y)) {
         hs_set_error("hs_join_hash_count: bad arguments (probe keys, counts and aux 16-byte aligned; n_build as given to the build)");
         return HS_E_ARG;
     }
@@ -2573,7 +2485,7 @@ extern "C" int hs_join_hash_count(void* stream, const int32_t* probe_keys, int64
 // duplicate key, or - rarely - another key of the same fingerprint in the same window, which then takes its own slot).
 // Build: one pass hashes every key (window number, fingerprint), two stable partition passes (RxPass.range = 1 on the
 // window number) bring the (window, row, fingerprint) tuples into window order, and one wave per window inserts, counts,
-// scans and places them in LDS exactly like k_jh_assemble.  Geometry (windows, L, workspace arrays) is jh_layout's.
+// scans and places them in LDS: k_jh_assemble<L, true>.  Geometry (windows, L, workspace arrays) is jx_layout's.
 __device__ __forceinline__ uint32_t js_window(uint64_t m, uint32_t windows) { return (uint32_t)(((m >> 32) * (uint64_t)windows) >> 32); }
 
 // hs_mix64(hs_fnv1a(key)), from at most three aligned word loads when the key is <= 16 bytes long
@@ -2610,20 +2522,6 @@ __global__ void __launch_bounds__(256) k_js_hash(const hs_col key, int64_t n, ui
     }
 }
 
-struct JsAssemble {
-    const int64_t* seg_start;  // [parts + 1] tuple ranges of the windows (parts >= windows; the rest are empty)
-    int64_t parts, windows;
-    const uint32_t* fp;        // tuples, window by window, in row order inside a window
-    const uint32_t* rows;
-    hs_col key;                // the build key column (byte compares)
-    uint2* table;              // [windows << L] {fingerprint, word}
-    uint32_t* out_rows;
-    uint32_t* list_count;
-    uint16_t* slot_of;
-    uint32_t* status;          // HS_FLAG_DICT_FULL only
-    uint32_t* flags;           // anything else
-};
-
 // slot of the key of build row `row` (fingerprint fp) in the wave's LDS window, claiming a free cell when it meets one first;
 // -1: the window is full
 template <int JH_L>
@@ -2644,257 +2542,41 @@ __device__ __forceinline__ int js_slot(uint64_t* cell, const hs_col& key, uint32
     return -1;
 }
 
-template <int JH_L>
-__global__ void __launch_bounds__(256) k_js_assemble(const JsAssemble A) {
-    extern __shared__ __align__(16) uint64_t js_lds[];
-    constexpr int W = 1 << JH_L, per = W / HS_WAVE;
-    const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE, wpb = blockDim.x / HS_WAVE;
-    uint64_t* cell = js_lds + (size_t)w * (2 * W + W / 8);
-    uint32_t* cur = (uint32_t*)(cell + W);
-    uint32_t* head = cur + W;
-    uint8_t* tag = (uint8_t*)(head + W);
-    const uint64_t below = (1ull << lane) - 1ull;
-    uint32_t err = 0, full_any = 0;
-    for (int64_t p = (int64_t)blockIdx.x * wpb + w; p < A.parts; p += (int64_t)gridDim.x * wpb) {
-        const int64_t b = A.seg_start[p], e = A.seg_start[p + 1];
-        if (p >= A.windows) {
-            if (e > b) err |= HS_FLAG_BAD_PROGRAM;  // a tuple past the last window: the passes and the table disagree
-            continue;
-        }
-        uint32_t nfp = b + lane < e ? A.fp[b + lane] : 0u;
-        uint32_t nrow = b + lane < e ? A.rows[b + lane] : 0u;
-        for (int s = lane; s < W; s += HS_WAVE) {
-            cell[s] = JH_FREE;
-            cur[s] = 0;
-            head[s] = JD_EMPTY;
-        }
-        rx_wave_handover();
-        bool full = false;
-        for (int64_t base = b; base < e; base += HS_WAVE) {  // claim slots, count rows per slot
-            const uint32_t fp = nfp, row = nrow;
-            const bool valid = base + lane < e;
-            if (base + HS_WAVE + lane < e) {
-                nfp = A.fp[base + HS_WAVE + lane];
-                nrow = A.rows[base + HS_WAVE + lane];
-            }
-            if (valid) {
-                const int s = js_slot<JH_L>(cell, A.key, fp, row);
-                if (s < 0) full = true;
-                else atomicAdd(&cur[s], 1u);
-                A.slot_of[base + lane] = (uint16_t)s;
-            }
-        }
-        rx_wave_handover();
-        if (__ballot(full)) {  // (wave-uniform) leave the window empty and say so
-            full_any = HS_FLAG_DICT_FULL;
-            for (int s = lane; s < W; s += HS_WAVE) A.table[(p << JH_L) + s] = make_uint2(0u, JD_EMPTY);
-            continue;
-        }
-        uint32_t sum = 0;
-        for (int k = 0; k < per; ++k) sum += cur[lane * per + k];
-        uint32_t x = sum;
-        for (int d = 1; d < HS_WAVE; d <<= 1) {
-            const uint32_t up = __shfl_up(x, d, HS_WAVE);
-            if (lane >= d) x += up;
-        }
-        uint32_t run = x - sum;
-        for (int k = 0; k < per; ++k) {
-            const uint32_t c = cur[lane * per + k];
-            cur[lane * per + k] = run;
-            run += c;
-        }
-        rx_wave_handover();
-        uint32_t nslot = b + lane < e ? A.slot_of[b + lane] : 0u;
-        nrow = b + lane < e ? A.rows[b + lane] : 0u;
-        for (int64_t base = b; base < e; base += HS_WAVE) {  // ordered placement (see k_jd_assemble)
-            const bool valid = base + lane < e;
-            const uint32_t s = nslot, row = nrow;
-            if (base + HS_WAVE + lane < e) {
-                nslot = A.slot_of[base + HS_WAVE + lane];
-                nrow = A.rows[base + HS_WAVE + lane];
-            }
-            if (valid) tag[s] = (uint8_t)lane;
-            rx_wave_handover();
-            const bool shared_slot = valid && tag[s] != (uint8_t)lane;
-            const uint32_t at = valid ? cur[s] : 0u;
-            const uint32_t first = valid ? head[s] : 0u;
-            if (__ballot(shared_slot) == 0) {
-                if (valid) {
-                    A.out_rows[b + at] = row;
-                    cur[s] = at + 1u;
-                    if (first == JD_EMPTY) head[s] = row;
-                }
-                rx_wave_handover();
-                continue;
-            }
-            uint64_t peers = __ballot(valid);
-            for (int bit = 0; bit < JH_L; ++bit) {
-                const bool on = (s >> bit) & 1u;
-                const uint64_t bal = __ballot(valid && on);
-                peers &= on ? bal : ~bal;
-            }
-            const uint32_t rank = (uint32_t)__popcll(peers & below);
-            rx_wave_handover();
-            if (valid) {
-                A.out_rows[b + at + rank] = row;
-                if (rank == 0) {
-                    cur[s] = at + (uint32_t)__popcll(peers);
-                    if (first == JD_EMPTY) head[s] = row;
-                }
-            }
-            rx_wave_handover();
-        }
-        for (int s = lane; s < W; s += HS_WAVE) {
-            const uint32_t end = cur[s], start = s ? cur[s - 1] : 0u;
-            const uint32_t c = end - start;
-            uint32_t word = JD_EMPTY;
-            if (c == 1) word = head[s];
-            else if (c > 1) {
-                word = JD_MULTI | (uint32_t)(b + start);
-                A.list_count[b + start] = c;
-            }
-            A.table[(p << JH_L) + s] = make_uint2((uint32_t)cell[s], word);
-        }
-        rx_wave_handover();
-    }
-    if (full_any && lane == 0) atomicOr(A.status, full_any);
-    if (err && lane == 0) atomicOr(A.flags, err);
-}
-
-struct JsLayout {
-    JhLayout h;
-    size_t win, fp, fp_a, fp_b, total;
-};
-static bool js_layout(int64_t n, JsLayout& Y) {
-    if (!jh_layout(n, Y.h)) return false;
-    size_t off = Y.h.total;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += rx_align(bytes);
-        return at;
-    };
-    Y.win = take((size_t)n * 4 + 64);
-    Y.fp = take((size_t)n * 4 + 64);
-    Y.fp_a = take(Y.h.bits1 ? (size_t)n * 4 + 64 : 0);
-    Y.fp_b = take(Y.h.bits2 ? (size_t)n * 4 + 64 : 0);
-    Y.total = off;
-    return true;
-}
-
 extern "C" size_t hs_join_hash_str_ws_bytes(int64_t n_build) {
-    JsLayout Y;
-    return js_layout(n_build, Y) ? Y.total : 0;
+    JxLayout Y;
+    return jx_layout(JX_HASH_STR, n_build, 0, Y) ? Y.total : 0;
 }
 extern "C" int64_t hs_join_hash_str_slots(int64_t n_build) {
-    JsLayout Y;
-    return js_layout(n_build, Y) ? Y.h.windows << Y.h.L : 0;
+    JxLayout Y;
+    return jx_layout(JX_HASH_STR, n_build, 0, Y) ? Y.windows << Y.L : 0;
 }
 
 static bool js_str_col(const hs_col* c) { return c && c->kind == HS_STR && (c->fixed_len >= 0 || (c->lens && c->offs)); }
 
 extern "C" int hs_join_hash_str_build(void* stream_, const hs_col* build_key, int64_t n_build, void* table, uint32_t* rows,
                                       uint32_t* list_count, void* ws_, uint32_t* status, uint32_t* flags) {
-    JsLayout Y;
+    JxLayout Y;
     if ((n_build > 0 && !js_str_col(build_key)) || !build_key || !table || !rows || !list_count || !ws_ || !status || !flags ||
-        ((uintptr_t)table & 7) || !js_layout(n_build, Y)) {
+        ((uintptr_t)table & 7) || !jx_layout(JX_HASH_STR, n_build, 0, Y)) {
         hs_set_error("hs_join_hash_str_build: bad arguments (a STRING key column, n_build <= 38 M rows, table 8-byte aligned)");
         return HS_E_ARG;
     }
     hipStream_t stream = (hipStream_t)stream_;
     uint8_t* ws = (uint8_t*)ws_;
-    const JhLayout& G = Y.h;
     const int64_t n = n_build;
     uint32_t* win = (uint32_t*)(ws + Y.win);
     uint32_t* fp = (uint32_t*)(ws + Y.fp);
-    uint32_t* iota = (uint32_t*)(ws + G.iota);
-    int64_t* seg0 = (int64_t*)(ws + G.seg0);
-    int64_t* seg1 = (int64_t*)(ws + G.seg1);
-    int64_t* seg2 = (int64_t*)(ws + G.seg2);
     if (n > 0) {
         int64_t g = (n + 255) / 256;
         g = g > 4096 ? 4096 : g;
-        hipLaunchKernelGGL(k_js_hash, dim3((unsigned)g), dim3(256), 0, stream, *build_key, n, (uint32_t)G.windows, win, fp);
+        hipLaunchKernelGGL(k_js_hash, dim3((unsigned)g), dim3(256), 0, stream, *build_key, n, (uint32_t)Y.windows, win, fp);
         RX_CHECK_LAUNCH("hs_join_hash_str_build (hash)");
     }
-    const int64_t n_iota = G.bits1 ? 0 : n;
-    int64_t grid = (n_iota + 255) / 256;
-    grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
-    hipLaunchKernelGGL(k_jd_setup, dim3((unsigned)grid), dim3(256), 0, stream, iota, n_iota, n, seg0);
-    RX_CHECK_LAUNCH("hs_join_hash_str_build (row ids)");
-    const uint32_t* t_fp = fp;
-    const uint32_t* t_rows = iota;
-    const int64_t* seg = seg0;
-    if (G.bits1 > 0 && n > 0) {
-        RxPass P;
-        std::memset(&P, 0, sizeof(P));
-        P.n_cols = 3;  // window number (the partition key), row id, fingerprint
-        P.esize[0] = P.esize[1] = P.esize[2] = 4;
-        P.range = 1;   // bins are bits of the window number itself
-        P.range_bias = 0;
-        P.key = hs_col{HS_I32, -1, win, nullptr, nullptr};
-        P.row0 = 0;
-        P.seg_start = seg0;  // pass 1: the top bits1 bits of the window number over the one segment [0, n)
-        P.tile_base = (int64_t*)(ws + G.tb0);
-        P.n_seg = 1;
-        P.shift = G.bits2;
-        P.bits = G.bits1;
-        P.first = 1;
-        P.src[1] = nullptr;  // the row id column is the position (k_rx_scatter4)
-        P.src[2] = fp;
-        P.dst[0] = ws + G.keys_a;
-        P.dst[1] = ws + G.rows_a;
-        P.dst[2] = ws + Y.fp_a;
-        int rc = rx_pass(stream, P, G.tiles1, (int64_t*)(ws + G.cnt), (int64_t*)(ws + G.scan), ws + G.scan_ws, n, G.bits2 ? seg1 : seg2);
-        if (rc != HS_OK) return rc;
-        t_fp = (const uint32_t*)(ws + Y.fp_a);
-        t_rows = (const uint32_t*)(ws + G.rows_a);
-        seg = seg2;
-        if (G.bits2) {  // pass 2: the low bits2 bits inside every segment of pass 1
-            P.seg_start = seg1;
-            P.tile_base = (int64_t*)(ws + G.tb1);
-            P.n_seg = G.nseg1;
-            P.shift = 0;
-            P.bits = G.bits2;
-            P.first = 0;
-            P.src[0] = ws + G.keys_a;
-            P.src[1] = ws + G.rows_a;
-            P.src[2] = ws + Y.fp_a;
-            P.dst[0] = ws + G.keys_b;
-            P.dst[1] = ws + G.rows_b;
-            P.dst[2] = ws + Y.fp_b;
-            rc = rx_pass(stream, P, G.tiles2, (int64_t*)(ws + G.cnt), (int64_t*)(ws + G.scan), ws + G.scan_ws, n, seg2);
-            if (rc != HS_OK) return rc;
-            t_fp = (const uint32_t*)(ws + Y.fp_b);
-            t_rows = (const uint32_t*)(ws + G.rows_b);
-        }
-    } else if (G.bits1 > 0) {  // no rows: every window is empty
-        hs_memset_async(seg2, 0, (size_t)(G.parts + 1) * 8, stream);
-        seg = seg2;
-    }
-    JsAssemble A;
-    A.seg_start = seg;
-    A.parts = G.bits1 > 0 ? G.parts : 1;
-    A.windows = G.windows;
-    A.fp = t_fp;
-    A.rows = t_rows;
-    A.key = *build_key;
-    A.table = (uint2*)table;
-    A.out_rows = rows;
-    A.list_count = list_count;
-    A.slot_of = (uint16_t*)(ws + G.slot_of);
-    A.status = status;
-    A.flags = flags;
-    const size_t per_wave = (size_t)17 << G.L;  // key cells (8 B) + cursors + first rows (4 B each) + tag bytes
-    constexpr int wpb = 4;
-    int64_t g = (A.parts + wpb - 1) / wpb;
-    if (g > 256 * 32) g = 256 * 32;
-    static unsigned long long attr_set = 0;
-    if (hs_first_on_device(attr_set))
-        (void)hipFuncSetAttribute((const void*)k_js_assemble<JH_L_LARGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (17 << JH_L_LARGE) * wpb);
-    if (G.L == JH_L_SMALL) hipLaunchKernelGGL(k_js_assemble<JH_L_SMALL>, dim3((unsigned)g), dim3(HS_WAVE * wpb), per_wave * wpb, stream, A);
-    else hipLaunchKernelGGL(k_js_assemble<JH_L_LARGE>, dim3((unsigned)g), dim3(HS_WAVE * wpb), per_wave * wpb, stream, A);
-    RX_CHECK_LAUNCH("hs_join_hash_str_build (assemble)");
-    return HS_OK;
+    // the partition key is the window number itself (RxPass.range = 1, no bias); the fingerprint travels along
+    JxTuples T;
+    const int rc = jx_partition(stream, "hs_join_hash_str_build", ws, Y, n, win, 1, 0, 0, fp, T);
+    if (rc != HS_OK) return rc;
+    return jh_assemble<true>(stream, "hs_join_hash_str_build", Y, T, *build_key, ws, table, rows, list_count, status, flags);
 }
 
 struct JsProbe {
@@ -2946,17 +2628,17 @@ __global__ void __launch_bounds__(256) k_js_count(const JsProbe A) {
 
 extern "C" int hs_join_hash_str_count(void* stream, const hs_col* build_key, const hs_col* probe_key, int64_t n_probe, int64_t n_build,
                                       const void* table, const uint32_t* rows, const uint32_t* list_count, int64_t* counts, void* aux) {
-    JsLayout Y;
+    JxLayout Y;
     if (n_probe < 0 || !build_key || !probe_key || (n_probe > 0 && !js_str_col(probe_key)) || (n_build > 0 && !js_str_col(build_key)) ||
-        !table || !rows || !list_count || !counts || !aux || ((uintptr_t)counts & 15) || ((uintptr_t)aux & 15) || !js_layout(n_build, Y)) {
+        !table || !rows || !list_count || !counts || !aux || ((uintptr_t)counts & 15) || ((uintptr_t)aux & 15) || !jx_layout(JX_HASH_STR, n_build, 0, Y)) {
         hs_set_error("hs_join_hash_str_count: bad arguments (STRING key columns, counts and aux 16-byte aligned; n_build as given to the build)");
         return HS_E_ARG;
     }
     if (n_probe == 0) return HS_OK;
-    JsProbe A{*build_key, *probe_key, n_probe, (uint32_t)Y.h.windows, 0, (const uint2*)table, rows, list_count, counts, (uint32_t*)aux};
+    JsProbe A{*build_key, *probe_key, n_probe, (uint32_t)Y.windows, 0, (const uint2*)table, rows, list_count, counts, (uint32_t*)aux};
     int64_t g = (n_probe + 255) / 256;
     if (g > 256 * 64) g = 256 * 64;
-    if (Y.h.L == JH_L_SMALL) hipLaunchKernelGGL(k_js_count<JH_L_SMALL>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, A);
+    if (Y.L == JH_L_SMALL) hipLaunchKernelGGL(k_js_count<JH_L_SMALL>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, A);
     else hipLaunchKernelGGL(k_js_count<JH_L_LARGE>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, A);
     RX_CHECK_LAUNCH("hs_join_hash_str_count");
     return HS_OK;

@@ -2245,23 +2245,11 @@ class Device:
         hs.check(self.lib.hs_join_dense_build(self.stream, left_key.data.data_ptr(), n_left, lo, slots, words.data_ptr(),
                                               rows.data_ptr(), list_count.data_ptr(), ws.data_ptr(), self.flags.data_ptr()),
                  "hs_join_dense_build")
-        counts = self.empty(max(n_right, 1), torch.int64)
-        aux = self.workspace(self.lib.hs_join_dense_aux_bytes(n_right))
-        hs.check(self.lib.hs_join_dense_count(self.stream, right_key.data.data_ptr(), n_right, lo, slots, words.data_ptr(),
-                                              rows.data_ptr(), list_count.data_ptr(), counts.data_ptr(), aux.data_ptr()),
-                 "hs_join_dense_count")
-        out_start = self.empty(n_right + 1, torch.int64)
-        ws2 = self.workspace(self.lib.hs_scan_ws_bytes(n_right))
-        hs.check(self.lib.hs_exclusive_scan_i64(self.stream, counts.data_ptr(), n_right, out_start.data_ptr(), ws2.data_ptr()),
-                 "hs_exclusive_scan_i64")
-        n_out = self.host_int(out_start[n_right])  # sizes the pair lists: the run is data-dependent (not replayable)
-        out_left = self.empty(max(n_out, 1), torch.int64)
-        out_right = self.empty(max(n_out, 1), torch.int64)
-        hs.check(self.lib.hs_join_dense_fill(self.stream, n_right, rows.data_ptr(), aux.data_ptr(), out_start.data_ptr(),
-                                             out_left.data_ptr(), out_right.data_ptr()), "hs_join_dense_fill")
+        pairs = self._join_probe_pairs(n_right, rows, "hs_join_dense_count", lambda counts, aux: self.lib.hs_join_dense_count(
+            self.stream, right_key.data.data_ptr(), n_right, lo, slots, words.data_ptr(), rows.data_ptr(), list_count.data_ptr(), counts, aux))
         self.last_join = {"mode": "dense csr", "slots": slots, "n_build": n_left}
         self.dense_joins = getattr(self, "dense_joins", 0) + 1
-        return out_left, out_right, out_start, n_out
+        return pairs
 
     def _join_indices_hashed(self, left_key: DCol, right_key: DCol) -> tuple | None:
         """Any INTEGER keys (round 4, hs_join_hash_*): the build rows are moved into the order of their hash windows and every
@@ -2282,25 +2270,35 @@ class Device:
         overflowed = self.empty(1, torch.int32)  # a status word of this build's own: "a window overflowed" is not an error
         overflowed.zero_()
         hs.check(self.lib.hs_join_hash_build(self.stream, left_key.data.data_ptr(), n_left, table.data_ptr(), rows.data_ptr(),
-                                             list_count.data_ptr(), ws.data_ptr(), overflowed.data_ptr()), "hs_join_hash_build")
+                                             list_count.data_ptr(), ws.data_ptr(), overflowed.data_ptr(), self.flags.data_ptr()),
+                 "hs_join_hash_build")
+        pairs = self._join_probe_pairs(n_right, rows, "hs_join_hash_count", lambda counts, aux: self.lib.hs_join_hash_count(
+            self.stream, right_key.data.data_ptr(), n_right, n_left, table.data_ptr(), rows.data_ptr(), list_count.data_ptr(), counts, aux),
+            overflowed)
+        if pairs is None:
+            return None
+        self.last_join = {"mode": "hashed windows", "slots": slots, "n_build": n_left}
+        self.hashed_joins = getattr(self, "hashed_joins", 0) + 1
+        return pairs
+
+    def _join_probe_pairs(self, n_right: int, rows: torch.Tensor, name: str, count, overflowed: torch.Tensor | None = None) -> tuple | None:
+        """The probe side of the dense and hashed joins after their build: count(counts_ptr, aux_ptr) launches the form's count
+        pass (`name`), then exclusive scan -> pair count on the host -> hs_join_dense_fill (both forms leave the dense form's
+        counts / aux).  None: the build's `overflowed` status word is set - checked after the host read, before the fill."""
         counts = self.empty(max(n_right, 1), torch.int64)
         aux = self.workspace(self.lib.hs_join_dense_aux_bytes(n_right))
-        hs.check(self.lib.hs_join_hash_count(self.stream, right_key.data.data_ptr(), n_right, n_left, table.data_ptr(),
-                                             rows.data_ptr(), list_count.data_ptr(), counts.data_ptr(), aux.data_ptr()),
-                 "hs_join_hash_count")
+        hs.check(count(counts.data_ptr(), aux.data_ptr()), name)
         out_start = self.empty(n_right + 1, torch.int64)
         ws2 = self.workspace(self.lib.hs_scan_ws_bytes(n_right))
         hs.check(self.lib.hs_exclusive_scan_i64(self.stream, counts.data_ptr(), n_right, out_start.data_ptr(), ws2.data_ptr()),
                  "hs_exclusive_scan_i64")
         n_out = self.host_int(out_start[n_right])  # sizes the pair lists: the run is data-dependent (not replayable)
-        if int(overflowed.item()) != 0:  # (the stream is idle after the read above: this one costs no second wait)
+        if overflowed is not None and int(overflowed.item()) != 0:  # (the stream is idle after the read above: this one costs no second wait)
             return None
         out_left = self.empty(max(n_out, 1), torch.int64)
         out_right = self.empty(max(n_out, 1), torch.int64)
         hs.check(self.lib.hs_join_dense_fill(self.stream, n_right, rows.data_ptr(), aux.data_ptr(), out_start.data_ptr(),
                                              out_left.data_ptr(), out_right.data_ptr()), "hs_join_dense_fill")
-        self.last_join = {"mode": "hashed windows", "slots": slots, "n_build": n_left}
-        self.hashed_joins = getattr(self, "hashed_joins", 0) + 1
         return out_left, out_right, out_start, n_out
 
     def join_indices(self, left_key: DCol, right_key: DCol) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:

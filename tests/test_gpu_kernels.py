@@ -182,7 +182,8 @@ def test_join_matches_reference_order(dev):
 
 
 @pytest.mark.parametrize("n_left,n_right,spread,seed", [(1, 5, 1, 0), (3000, 5000, 2, 1), (70_000, 200_000, 4, 2),
-                                                        (2_000_000, 3_000_000, 10, 3), (300_000, 100_000, 30, 4)])
+                                                        (2_000_000, 3_000_000, 10, 3), (300_000, 100_000, 30, 4),
+                                                        (3_000_000, 1_000_000, 30, 5)])
 def test_dense_integer_join_matches_reference_order(dev, n_left, n_right, spread, seed):
     """Round 4: INTEGER keys over a dense range take hs_join_dense_* - two stable range-partition passes over the build
     rows, a CSR over key SLOTS assembled per partition in LDS (rows of a slot ascending, no sort, no global atomic), probe by

@@ -123,7 +123,8 @@ hpk = dev.empty(N, torch.int32); hpk.copy_(torch.where(hp >= 2**31, hp - 2**32, 
 hslots = int(lib.hs_join_hash_slots(nb))
 htable = dev.empty(hslots, torch.int64); hrows = dev.empty(nb, torch.int32); hlc = dev.empty(nb, torch.int32)
 hws = dev.workspace(lib.hs_join_hash_ws_bytes(nb))
-ms_b = timed(lambda: lib.hs_join_hash_build(dev.stream, hbk.data_ptr(), nb, htable.data_ptr(), hrows.data_ptr(), hlc.data_ptr(), hws.data_ptr(), dev.flags.data_ptr()))
+hstatus = dev.empty(1, torch.int32); hstatus.zero_()  # the build's own status word: HS_FLAG_DICT_FULL (a window overflowed)
+ms_b = timed(lambda: lib.hs_join_hash_build(dev.stream, hbk.data_ptr(), nb, htable.data_ptr(), hrows.data_ptr(), hlc.data_ptr(), hws.data_ptr(), hstatus.data_ptr(), dev.flags.data_ptr()))
 report(f"A8 hs_join_hash_build (any int32 keys, {hslots} slots)", ms_b, nb * (4 + 4) + hslots * 8, f"{nb / ms_b / 1e3:.0f} M keys/s; keys in, rows + the 8-byte slots out")
 aux = dev.workspace(lib.hs_join_dense_aux_bytes(N))
 ms_c = timed(lambda: lib.hs_join_hash_count(dev.stream, hpk.data_ptr(), N, nb, htable.data_ptr(), hrows.data_ptr(), hlc.data_ptr(), counts.data_ptr(), aux.data_ptr()))
@@ -133,7 +134,7 @@ nout3 = int(ost[N].item()); assert nout3 == nout, (nout3, nout)
 ms_f = timed(lambda: lib.hs_join_dense_fill(dev.stream, N, hrows.data_ptr(), aux.data_ptr(), ost.data_ptr(), ol.data_ptr(), orr.data_ptr()))
 report("A8 hs_join_dense_fill (after the hashed count)", ms_f, N * (8 + 4) + nout * 16, f"{nout} pairs")
 report("A8 hashed count + fill", ms_c + ms_f, N * (4 + 8 + 8 + 8) + N * (8 + 4) + nout * 16)
-assert dev.read_flags() == 0
+assert dev.read_flags() == 0 and int(hstatus.item()) == 0
 
 # A5 global-tier group build + fold (high cardinality)
 ng_keys = torch.randint(0, N // 16, (N,), dtype=torch.int32, device="cuda", generator=g)
