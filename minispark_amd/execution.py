@@ -138,6 +138,24 @@ def _plain_names(expr: Any) -> list[str]:
     return [c.name for c in expr.all_nested_columns if _cls(c) in ("Col", "SchemaCol")]
 
 
+def probe_side_streams(join_stage: Any, no_stream: set, no_fused: set) -> bool:
+    """Whether a join stage reads a probe side beyond the HBM budget range by range (HipExecutionEngine.
+    _run_join_stage_streamed): the join writes the result file, or it feeds the short-tail partial aggregate through WHERE
+    conditions only (the byte-table join) and neither is in a fallback set.  ``no_stream`` holds the join task ids whose
+    range-by-range run found a shape it cannot finish; ``no_fused`` the join task ids the byte table does not hold and
+    the partial AggregateTask ids that lost the short tail.  Every other join has its probe side streamed through its
+    scan stage, concatenated and joined resident.  Decided from the plan and the two sets alone."""
+    task = join_stage.producer
+    if _uid(task) in no_stream:
+        return False
+    if _cls(join_stage.writer) == "WriteToLocalFileTask":
+        return True
+    first_real = next((t for t in join_stage.consumers if _cls(t) != "FilterTask"), None)
+    return (first_real is not None and _cls(first_real) == "AggregateTask" and first_real.before_shuffle
+            and getattr(first_real, "_hs_short_tail", False) and _uid(task) not in no_fused
+            and _uid(first_real) not in no_fused)
+
+
 class _DeferredScan:
     """Output of a scan stage that was NOT run: the probe side of a join, larger than the HBM budget.  The join stage
     reads it block range by block range (HipExecutionEngine._run_join_stage_streamed)."""
@@ -181,6 +199,12 @@ class HipExecutionEngine(ExecutionEngine):
         budget = os.environ.get("HIPSPARK_HBM_BUDGET")
         self.hbm_budget: int | None = int(float(budget)) if budget else None  # bytes of referenced columns kept resident
         self.streamed_ranges = 0
+        self.streamed_join_fallbacks = 0  # probe sides beyond the budget streamed, concatenated and joined resident
+        # how the last query's join over a probe side beyond the budget ran: "ranges" (the join stage read it range by
+        # range), "resident" (streamed through its scan stage, concatenated, joined resident) or None (no such join)
+        self.last_probe_route: str | None = None
+        self._no_streamed_join: set[Any] = set()  # join task ids whose probe side must not be read range by range
+        self._join8_reuse: dict | None = None  # the byte table of a streamed join, built for its first range only
         self._version = 0  # bumped by everything that could invalidate a validated recording (see _execute_full_task)
         self.fused_joins = 0
         self._no_short_tail: set[Any] = set()  # partial AggregateTask ids that must take the general path
@@ -396,12 +420,15 @@ class HipExecutionEngine(ExecutionEngine):
             self._version += 1  # a full run may load / re-code tables, grow capacities, replace recordings
             self.dev.reset_flags()
             self._fused_join_tasks.clear()
+            self._join8_reuse = None
+            self.last_probe_route = None
             self._lds_merges: list[int] = []
             outputs: dict[int, Any] = {}
             results: list[JobResult] = []
-            # scan stages that feed a join's probe (right) side: one that does not fit HBM is not materialised - the join
-            # stage streams it block range by block range (the reference's right side is streamed too: tasks.py:224-240)
-            self._probe_stages = {id(st.dependencies[1]) for st in plan.stages
+            # scan stages that feed a join's probe (right) side -> the join stage: one that does not fit HBM may be left
+            # unmaterialised for the join stage to read block range by range (the reference streams its right side too:
+            # tasks.py:224-240)
+            self._probe_stages = {id(st.dependencies[1]): st for st in plan.stages
                                   if _cls(st.producer) == "BroadcastHashJoinTask" and len(st.dependencies) == 2}
             # record the second (cache-warm) run of a plan: by then every buffer it needs is prepared
             want_record = self.replay_enabled and self._plan_runs.get(rec_key, 0) >= 1
@@ -573,10 +600,15 @@ class HipExecutionEngine(ExecutionEngine):
         if kind == "LoadTableBlockTask":
             ranges = self._stream_ranges(producer, consumers)
             if ranges is not None:
-                if id(stage) in getattr(self, "_probe_stages", ()) and _cls(writer) == "WriteToShufflePartitions":
-                    outputs[id(stage)] = _DeferredScan(stage, ranges)  # read by the join stage, range by range
-                    self._job_seq += 1
-                    return [JobResult(f"{self._job_prefix}-{self._job_seq}", self._executor_id, [])]
+                join_stage = getattr(self, "_probe_stages", {}).get(id(stage))
+                if join_stage is not None and _cls(writer) == "WriteToShufflePartitions":
+                    no_fused = self._no_join8 | self._no_fused_join | self._no_short_tail
+                    if probe_side_streams(join_stage, self._no_streamed_join, no_fused):
+                        outputs[id(stage)] = _DeferredScan(stage, ranges)  # read by the join stage, range by range
+                        self._job_seq += 1
+                        return [JobResult(f"{self._job_prefix}-{self._job_seq}", self._executor_id, [])]
+                    self.streamed_join_fallbacks += 1  # the ranges are concatenated; the join runs resident
+                    self.last_probe_route = "resident"
                 return self._run_scan_stage_streamed(stage, outputs, ranges)
             batch = self._scan(producer, consumers, writer)
         elif kind == "LoadShuffleFilesTask":
@@ -857,13 +889,19 @@ class HipExecutionEngine(ExecutionEngine):
     def _run_join_stage_streamed(self, stage: Any, outputs: dict[int, Any], feeds_aggregate: bool) -> list[JobResult]:
         """A join whose probe (right) side does not fit HBM (reference: the right side is streamed block by
         block through the build side's hash map, tasks.py:224-240).  The build side is resident; the probe side's scan
-        stage was deferred and runs here range by range: read (pruned, pipelined) -> its own consumers -> join ->
+        stage was deferred (probe_side_streams) and runs here range by range: read (pruned, pipelined) -> its own
+        consumers -> join ->
         * join feeding a GROUP BY (the byte-table join with the probe inside the aggregate): the table is
           built ONCE; every range leaves the RAW per-JoinJob tables; they are added up in range order before the one
           rounding the reference applies per JoinJob, then the short tail runs as for a resident table;
-        * join feeding the result file: the joined rows of every range go through the stage's consumers and are appended
-          to the result BlockFile with the reference's append-merge rule (io.py:231-252).
-        One rank only (a streamed stage is a per-rank decision, see _stream_ranges)."""
+        * join feeding the result file (any key kind, duplicate keys, columns of both sides): the joined rows of every
+          range go through the stage's consumers and are appended to the result BlockFile with the reference's
+          append-merge rule (io.py:231-252).
+        A join feeding a GROUP BY that the byte table turns out not to hold on some range (no byte table for these keys,
+        a second build-side column, a GROUP BY the fused probe's tier cannot hold, ...) is refused here: the query
+        restarts, and from then on the probe side's scan stage is streamed, concatenated and joined resident, as
+        the resident engine's _no_join8 rule does for the fused probe.  One rank only (a streamed stage is a per-rank
+        decision, see _stream_ranges)."""
         from . import table as tbl  # noqa: PLC0415
         from .device import SlabUnsupported, TierExceeded  # noqa: PLC0415
         from .hipspark import HipSparkLimit  # noqa: PLC0415
@@ -879,54 +917,63 @@ class HipExecutionEngine(ExecutionEngine):
         if self.dev.rec is not None:
             self.dev.rec.poisoned = True  # host data flows in on every run
         to_file = _cls(writer) == "WriteToLocalFileTask"
+
+        def refuse() -> RestartQuery:
+            self._no_streamed_join.add(_uid(producer))
+            return RestartQuery()
+
         if not feeds_aggregate and not to_file:
-            raise ExecutionError("a join over a probe side larger than the HBM budget must feed a GROUP BY or the result file")
+            raise refuse()
         self.streamed_ranges += len(deferred.ranges)
         agg = next((t for t in consumers if _cls(t) == "AggregateTask"), None)
         raw_tables: list = []
         prepared = None
         out_path, rows_written = None, 0
         schema = writer.inferred_schema
-        self._join8_reuse = {}
         left = self.dev.resolve(left)
-        for blocks in deferred.ranges:
-            sub = tbl.sub_table(table, blocks)
-            tbl.load_columns(self.dev, sub, col_ids)
-            if self.dict_enabled:
-                self._encode_string_columns(sub, col_ids)
-            right = tbl.table_batch(sub, col_ids, scan.producer.alias)
-            right = self.dev.resolve(self._quantise_batch(self.dev.resolve(self._consume(right, scan_consumers)), scan.writer.inferred_schema))
-            joined = self._join(producer, left, right, needed, feeds_aggregate, consumers)
-            if feeds_aggregate:
-                if joined.join8 is None:
-                    raise ExecutionError("this join shape cannot stream its probe side: only the byte-table join (unique dense "
-                                         "INTEGER build keys, at most one dictionary-coded build column) adds partial "
-                                         "aggregates up across block ranges before the per-JoinJob rounding")
-                pending = [t.condition for t in consumers[: consumers.index(agg)] if _cls(t) == "FilterTask"]
-                if any(_cls(t) not in ("FilterTask",) for t in consumers[: consumers.index(agg)]):
-                    raise ExecutionError("a projection between a streamed join and its GROUP BY is not supported")
-                try:
-                    p = self.dev.aggregate_join8(joined, pending, agg.group_by_column, agg.agg_columns, agg.inferred_schema,
-                                                 self.group_cap_hint, cache_key=None, raw_tables=raw_tables)
-                except (TierExceeded, SlabUnsupported, HipSparkLimit) as e:
-                    raise ExecutionError(f"streamed join: {e}") from e
-                if prepared is not None and (p["unit_cap"], p["slots"], p["table_bytes"]) != (
-                        prepared["unit_cap"], prepared["slots"], prepared["table_bytes"]):
-                    raise ExecutionError("streamed join: the ranges' unit tables differ in shape")
-                prepared = p
-            else:
-                batch = self.dev.resolve(self._consume(joined, consumers))
-                raw, nrows, flags = self.dev.download_batch(self.dev.resolve(self._quantise_batch(batch, schema)), schema, None)
-                self._act_on_flags(flags)
-                if nrows:
-                    if out_path is None:
-                        out_path = self._result_path(stage.stage_id)
-                        out_path.parent.mkdir(parents=True, exist_ok=True)
-                        out_path.unlink(missing_ok=True)
-                    BlockFile(out_path, list(schema)).append_raw(raw)
-                    rows_written += nrows
-            del sub, right, joined
-        self._join8_reuse = None
+        self._join8_reuse = {}
+        try:
+            for blocks in deferred.ranges:
+                sub = tbl.sub_table(table, blocks)
+                tbl.load_columns(self.dev, sub, col_ids)
+                if self.dict_enabled:
+                    self._encode_string_columns(sub, col_ids)
+                right = tbl.table_batch(sub, col_ids, scan.producer.alias)
+                right = self.dev.resolve(self._quantise_batch(self.dev.resolve(self._consume(right, scan_consumers)),
+                                                              scan.writer.inferred_schema))
+                joined = self._join(producer, left, right, needed, feeds_aggregate, consumers)
+                if feeds_aggregate:
+                    between = consumers[: consumers.index(agg)]
+                    if joined.join8 is None or any(_cls(t) != "FilterTask" for t in between):
+                        raise refuse()
+                    pending = [t.condition for t in between]
+                    try:
+                        p = self.dev.aggregate_join8(joined, pending, agg.group_by_column, agg.agg_columns,
+                                                     agg.inferred_schema, self.group_cap_hint, cache_key=None,
+                                                     raw_tables=raw_tables)
+                    except (TierExceeded, SlabUnsupported, HipSparkLimit):
+                        self._no_join8.add(_uid(producer))
+                        raise refuse() from None
+                    if prepared is not None and (p["unit_cap"], p["slots"], p["table_bytes"]) != (
+                            prepared["unit_cap"], prepared["slots"], prepared["table_bytes"]):
+                        raise refuse()
+                    prepared = p
+                else:
+                    batch = self.dev.resolve(self._consume(joined, consumers))
+                    raw, nrows, flags = self.dev.download_batch(self.dev.resolve(self._quantise_batch(batch, schema)),
+                                                                schema, None)
+                    self._act_on_flags(flags)
+                    if nrows:
+                        if out_path is None:
+                            out_path = self._result_path(stage.stage_id)
+                            out_path.parent.mkdir(parents=True, exist_ok=True)
+                            out_path.unlink(missing_ok=True)
+                        BlockFile(out_path, list(schema)).append_raw(raw)
+                        rows_written += nrows
+                del sub, right, joined
+        finally:
+            self._join8_reuse = None  # a later join must never take this query's byte table
+        self.last_probe_route = "ranges"
         self._job_seq += 1
         job_id = f"{self._job_prefix}-{self._job_seq}"
         if not feeds_aggregate:

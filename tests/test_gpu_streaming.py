@@ -89,6 +89,7 @@ def test_join_streams_a_probe_side_that_does_not_fit(tmp_path, name):
             assert assert_rows_match(frame.collect(), want, max_ulps=1) <= 2
         assert engine.streamed_ranges >= 4 and engine.fused_probes >= 2
         assert engine.dev.last_join["mode"] == "byte table"
+        assert engine.last_probe_route == "ranges" and engine.streamed_join_fallbacks == 0 and engine._join8_reuse is None
 
 
 def test_join_to_the_result_file_streams_its_probe_side(tmp_path):
@@ -112,5 +113,6 @@ def test_join_to_the_result_file_streams_its_probe_side(tmp_path):
         engine.hbm_budget = 60_000
         rows = query(_api(engine)).collect()
         assert engine.streamed_ranges >= 3
+        assert engine.last_probe_route == "ranges" and engine.streamed_join_fallbacks == 0
     assert len(rows) == len(want) > 1000
     assert assert_rows_match(rows, want, max_ulps=0) == 0
