@@ -70,6 +70,11 @@ extern "C" {
  * column; the value of row i is looked up in the hs_join8 byte table while the aggregate scans - never stored. */
 #define HS_JOIN8_CODE 16 /* the table byte of the row's key: the build side's 1-byte payload (a dictionary code) */
 #define HS_JOIN8_UNIT 17 /* python_hash(key) % n_parts (the row's shuffle partition), 0xff = the key has no match */
+/* Pair-indexed columns (hs_join_group_stage, round 5): HS_PAIR OR-ed onto HS_I32 / HS_F32 / HS_I64.  `data` = the table
+ * column as stored, `offs` = the int64 table row of every pair (readable 4 rows past the last pair, where it holds 0); the
+ * value of row i is data[offs[i]], loaded through the index while the shared-dictionary scan runs - never materialised.
+ * Only the run-time compiled shared tier reads them (not as the GROUP BY key); the interpreter kernels refuse them. */
+#define HS_PAIR 0x100
 /* the byte table those lookups read (built by hs_join8_build, see the join section below) */
 typedef struct hs_join8 {
     const uint8_t* table; /* hs_join8_table_bytes(slots) bytes */
@@ -98,6 +103,7 @@ typedef struct hs_col {
 #define HS_MAX_COLS 12
 #define HS_MAX_ACC 16
 #define HS_MAX_OUTS 16 /* output columns of one hs_eval / projection program */
+#define HS_FUSED_COLS 8 /* numeric column slots preloaded per step */
 #define HS_MAX_STACK 8
 
 enum hs_op {
@@ -145,7 +151,7 @@ const char* hs_last_error(void);
 int hs_version(void);
 /* sizeof() of ABI structure `which` as compiled: 0 hs_col, 1 hs_program, 2 hs_agg_spec, 3 hs_agg_geom, 4 hs_chunk,
  * 5 hs_slab_desc, 6 hs_finish_out, 7 hs_finish_spec, 8 hs_stage_plan, 9 hs_result_col, 10 hs_join8, 11 hs_join_stage_plan, 12 hs_select_stage_plan,
- * 14 hs_join_select_stage_plan (13 stays unassigned: it returns 0, the end of the round-4 list)
+ * 14 hs_join_select_stage_plan, 15 hs_join_group_stage_plan (13 stays unassigned: it returns 0, the end of the round-4 list)
  * (0 for anything else) - lets a
  * binding verify its mirror. */
 size_t hs_sizeof(int32_t which);
@@ -963,6 +969,52 @@ int hs_join_select_stage_run(hs_join_select_stage* stage, void* stream, uint32_t
 int hs_join_select_stage_stats(const hs_join_select_stage* stage, int64_t* stats);
 int hs_join_select_result_write_blockfile(const hs_join_select_stage* stage, const char* path, int64_t rows_per_block);
 void hs_join_select_stage_destroy(hs_join_select_stage* stage);
+
+/* ---- the general JOIN feeding a GROUP BY behind the same boundary (round 5) ---------------------------------------------
+ * The reference's JoinJob for every join (tasks.py:201-240 build + probe, tasks.py:284-289 partial aggregate) and the final
+ * stage after it: keys INTEGER or STRING, duplicates on both sides, any columns of either side in the aggregate.  The first
+ * part is hs_join_select_stage_run's: both tables through the native reader (only the named columns), a WHERE per side,
+ * probe rows in JoinJob order, the join on its dense / hashed / hashed-string / global route, the table rows of every pair.
+ * The pairs of one JoinJob are one row-range unit of the shared-dictionary scan (hs_agg_shared), which reads every slot's
+ * column through the pair rows; conjuncts over both sides are the program's filter section.  Then the scan stage's tail:
+ * pack -> merge in unit order -> projection -> rounding -> result image.  HS_FLAG_DICT_FULL / HS_FLAG_MERGE_FULL grow the
+ * capacities (x4, up to 4096) and aggregate the same pairs again; beyond that HS_E_LIMIT.  A variable-length STRING GROUP BY
+ * key (either side) is dictionary-coded at prepare (<= 255 values, else HS_E_LIMIT) and decoded in the result file.  Single
+ * rank; not replayed (sizes depend on the data). */
+typedef struct hs_join_group_stage hs_join_group_stage;
+#define HS_JOIN_GROUP_STAGE_PLAN_VERSION 1
+typedef struct hs_join_group_stage_plan {
+    int32_t version;                          /* HS_JOIN_GROUP_STAGE_PLAN_VERSION */
+    int32_t build_key_col, probe_key_col;     /* both INTEGER or both STRING */
+    int32_t n_parts;                          /* JoinJobs (the reference's SHUFFLE_PARTITIONS, 10) */
+    int32_t n_bcols;                          /* column slots of build_filter */
+    int32_t bcol_ids[HS_MAX_COLS];            /* slot -> build table column */
+    hs_program build_filter;                  /* one HS_OP_OUT 0 = the build row survives; n_ins 0 = no WHERE */
+    int32_t n_pcols;
+    int32_t pcol_ids[HS_MAX_COLS];            /* slot -> probe table column */
+    hs_program probe_filter;
+    int32_t n_cols;                           /* column slots of `prog` (at most HS_FUSED_COLS, 8) */
+    int32_t col_side[HS_MAX_COLS];            /* slot -> 0 build table, 1 probe table */
+    int32_t col_ids[HS_MAX_COLS];             /* slot -> table column of that side */
+    int32_t key_slot;                         /* slot of the GROUP BY column */
+    int32_t group_cap, merge_cap;             /* starting capacities per JoinJob / of the final merge (0 = 16 / 64) */
+    hs_program prog;                          /* [filter ... FILTER]* KEY [argument ... AGG acc]* over the slots */
+    hs_agg_spec spec;
+    hs_finish_spec fin;                       /* as in hs_stage_plan */
+    hs_program fin_prog;
+    int32_t out_types[HS_FINISH_MAX_OUT];
+    char out_names[HS_FINISH_MAX_OUT][64];
+} hs_join_group_stage_plan;
+#define HS_JOIN_AGG_PAIRS 1         /* the aggregate read its numeric columns through the pair rows (HS_PAIR columns) */
+#define HS_JOIN_AGG_GATHERED 2      /* the aggregate read columns gathered through the pair rows (no run-time compiler) */
+int hs_join_group_stage_prepare(hs_engine* engine, hs_table* build, hs_table* probe, const hs_join_group_stage_plan* plan,
+                                size_t plan_bytes, hs_join_group_stage** out);
+int hs_join_group_stage_run(hs_join_group_stage* stage, void* stream, uint32_t* flags_out, int64_t* n_rows_out);
+/* stats[10]: runs, capacity growths, group_cap, merge_cap, join route (HS_JOIN_ROUTE_*), aggregate route (HS_JOIN_AGG_*),
+ * pairs, build rows and probe rows after the WHERE, dictionary entries of a coded GROUP BY key (0: stored key) */
+int hs_join_group_stage_stats(const hs_join_group_stage* stage, int64_t* stats);
+int hs_join_group_result_write_blockfile(const hs_join_group_stage* stage, const char* path);
+void hs_join_group_stage_destroy(hs_join_group_stage* stage);
 
 /* =================================================================================================
  * Launch capture: the native replay of a recorded query (reference: the Zig worker re-runs its compiled plan per job,

@@ -1401,6 +1401,12 @@ static int agg_partial_impl(void* stream, const hs_col* cols, int32_t n_cols, in
             return HS_E_LIMIT;
         }
     }
+    for (int i = 0; i < n_cols; ++i) {
+        if (cols[i].kind & HS_PAIR) {
+            hs_set_error("hs_agg_partial: HS_PAIR columns belong to the run-time compiled shared tier (hs_agg_shared)");
+            return HS_E_ARG;
+        }
+    }
     A.prog = *prog;
     A.spec = *spec;
     A.key_col = key_col;
@@ -1823,6 +1829,8 @@ int hs_jit_launch_agg_shared(const AggMainArgs* args, bool hashed, unsigned grid
                              hipStream_t stream);
 
 static constexpr int HS_SHARED_WG = 1024;
+extern "C" int hs_jit_get_enabled(void);
+extern "C" const char* hs_jit_last_log(void);
 
 extern "C" int hs_agg_shared_geom(const int64_t* host_unit_rows, int64_t n_units, int32_t n_acc, int32_t group_cap,
                                   hs_agg_geom* out) {
@@ -1952,11 +1960,24 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
             return HS_E_LIMIT;
         }
     }
+    bool pairs = false;  // pair-indexed columns: only the run-time compiled scan reads them
     for (int i = 0; i < n_cols; ++i) {
         if ((cols[i].kind == HS_JOIN8_CODE || cols[i].kind == HS_JOIN8_UNIT) && !join) {
             hs_set_error("hs_agg_shared: HS_JOIN8_* columns belong to hs_agg_shared_join8");
             return HS_E_ARG;
         }
+        if (cols[i].kind & HS_PAIR) {
+            const int base = cols[i].kind & ~HS_PAIR;
+            if (join || i == key_col || (base != HS_I32 && base != HS_F32 && base != HS_I64) || !cols[i].offs) {
+                hs_set_error("hs_agg_shared: an HS_PAIR column is an INTEGER / FLOAT / TIMESTAMP argument slot with its pair rows");
+                return HS_E_ARG;
+            }
+            pairs = true;
+        }
+    }
+    if (pairs && !hs_jit_get_enabled()) {
+        hs_set_error("hs_agg_shared: HS_PAIR columns need the run-time compiler (HIPSPARK_JIT=0 here)");
+        return HS_E_LIMIT;
     }
     const int depth = program_depth(prog);
     if (depth > HS_MAX_STACK) {
@@ -2035,6 +2056,9 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
     } else if (join) {
         // the interpreter kernels do not know the virtual columns; the init launch above is harmless
         hs_set_error("hs_agg_shared_join8: needs the run-time compiler (hiprtc): %s", hs_jit_last_log());
+        return HS_E_LIMIT;
+    } else if (pairs) {
+        hs_set_error("hs_agg_shared: HS_PAIR columns need the run-time compiler (hiprtc): %s", hs_jit_last_log());
         return HS_E_LIMIT;
     } else if (hashed) {
         hipLaunchKernelGGL((k_agg_shared<true, 8>), grid, dim3(hs_shared_interp_wg(8)), geom->lds_bytes, s, A);

@@ -22,7 +22,6 @@
 
 #include "hs_device.h"
 
-#define HS_FUSED_COLS 8 /* numeric column slots preloaded per step */
 
 // 16-byte vector types usable with __builtin_nontemporal_load (HIP's float4 & co. are structs)
 typedef float hs_f32x4 __attribute__((ext_vector_type(4)));

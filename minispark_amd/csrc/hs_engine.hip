@@ -652,6 +652,125 @@ extern "C" int hs_table_load(hs_engine* e, hs_table* t, const int32_t* col_ids, 
 // =====================================================================================================
 // Stages
 // =====================================================================================================
+// The shared-dictionary tier's buffers from the scan's unit tables to the result image (the scan stage's tier 1 and the
+// join feeding a GROUP BY share them and the code that fills them)
+struct SharedBufs {
+    DevBuf rep, acc, ngroups, pack_start, dense_rep, order, key, accs, mrep, macc, mgroups, mkey, prog_out, image;
+};
+
+namespace {
+
+// slots = unit tables x slots per unit table; nf = folds of the final merge
+bool shared_alloc(SharedBufs& B, int64_t slots, int64_t n_units, int n_acc, int nf, int merge_cap) {
+    slots = slots > 0 ? slots : 1;
+    return B.rep.alloc((size_t)slots * 8) && B.acc.alloc((size_t)slots * (size_t)(n_acc > 0 ? n_acc : 1) * 8) &&
+           B.ngroups.alloc((size_t)(n_units + 1) * 4) && B.pack_start.alloc((size_t)(n_units + 1) * 8) &&
+           B.dense_rep.alloc((size_t)slots * 8) && B.order.alloc((size_t)slots * 8) && B.key.alloc((size_t)slots * 8) &&
+           B.accs.alloc((size_t)slots * 4 * (size_t)(n_acc > 0 ? n_acc : 1)) && B.mrep.alloc((size_t)merge_cap * 8) &&
+           B.macc.alloc((size_t)merge_cap * 8 * (size_t)(nf > 0 ? nf : 1)) && B.mgroups.alloc(8) &&
+           B.mkey.alloc((size_t)merge_cap * 8) && B.prog_out.alloc((size_t)merge_cap * 8 * HS_MAX_OUTS);
+}
+
+// result image of the on-chip path: header 16 bytes, then every column at a 16-byte aligned offset, cap elements each
+int64_t image_layout(hs_finish_spec& fin, int key_bytes, int cap) {
+    int64_t pos = 16;
+    for (int o = 0; o < fin.n_out; ++o) {
+        hs_finish_out& out = fin.outs[o];
+        const int width = out.src == 0 ? key_bytes : (out.kind == HS_I64 ? 8 : 4);
+        out.offset = pos;
+        pos = (pos + (int64_t)cap * width + 15) & ~(int64_t)15;
+    }
+    return pos;
+}
+
+// After hs_agg_shared filled B.rep / B.acc / B.ngroups: dense partial rows -> merge in unit order -> projection -> rounding ->
+// result image on the host.  kc: the key column the scan read (key_rows rows); *flags_out / *rows_out: the run's result.
+int shared_tail(hipStream_t stream, SharedBufs& B, const hs_agg_spec& spec, const hs_finish_spec& fin, const hs_program& fin_prog,
+                const hs_col& kc, int key_bytes, int64_t key_rows, int64_t n_units, int unit_cap, int64_t slots, int cap,
+                void* image_host, int64_t image_bytes, uint32_t* flags, uint32_t* flags_out, int64_t* rows_out) {
+    const int n_acc = spec.n_acc, nf = fin.n_fold;
+    // dense partial rows = the reference's shuffle-file content: accumulators in their stored kinds, unit of every row
+    void* acc_ptrs[HS_MAX_ACC] = {};
+    int32_t acc_kinds[HS_MAX_ACC] = {};
+    for (int a = 0; a < n_acc; ++a) {
+        acc_ptrs[a] = (char*)B.accs.p + (size_t)a * (size_t)slots * 4;
+        acc_kinds[a] = spec.is_int[a] ? HS_I32 : HS_F32;
+    }
+    int rc = hs_agg_pack(stream, (const int64_t*)B.rep.p, (const uint64_t*)B.acc.p, (const int32_t*)B.ngroups.p, n_units, unit_cap,
+                         &spec, (int64_t*)B.pack_start.p, (int64_t*)B.dense_rep.p, acc_ptrs, acc_kinds, nullptr, (int64_t*)B.order.p);
+    if (rc) return rc;
+    const int64_t* n_dense = (const int64_t*)B.pack_start.p + n_units;
+    rc = hs_gather_fixed(stream, kc.data, key_bytes, key_rows, (const int64_t*)B.dense_rep.p, slots, n_dense, B.key.p, flags);
+    if (rc) return rc;
+    // final merge (tasks.py:290-292): fold j = fold_op[j] over the dense accumulator column fold_src[j], partials in unit order
+    hs_col key_dense{kc.kind, kc.kind == HS_STR ? kc.fixed_len : -1, B.key.p, nullptr, nullptr};
+    hs_col fold_cols[HS_MAX_ACC];
+    hs_agg_spec mspec{};
+    mspec.n_acc = nf;
+    for (int j = 0; j < nf; ++j) {
+        const int src = fin.fold_src[j];
+        fold_cols[j] = hs_col{acc_kinds[src], -1, acc_ptrs[src], nullptr, nullptr};
+        mspec.op[j] = (uint8_t)fin.fold_op[j];
+        mspec.is_int[j] = spec.is_int[src];
+    }
+    rc = hs_agg_merge(stream, &key_dense, fold_cols, &mspec, (const int64_t*)B.order.p, n_units, slots, n_dense, cap,
+                      (int64_t*)B.mrep.p, (uint64_t*)B.macc.p, (int64_t*)B.mgroups.p, flags);
+    if (rc) return rc;  // HS_E_LIMIT: more partial rows than the on-chip merge holds
+    const int64_t* ng = (const int64_t*)B.mgroups.p;
+    rc = hs_gather_fixed(stream, B.key.p, key_bytes, slots, (const int64_t*)B.mrep.p, cap, ng, B.mkey.p, flags);
+    if (rc) return rc;
+    // projection after the merge (AVG = sum / count ...): the merged cells are its columns (slot -> key / fold j)
+    int n_prog_out = 0;
+    for (int o = 0; o < fin.n_out; ++o)
+        if (fin.outs[o].src == 2 && fin.outs[o].index + 1 > n_prog_out) n_prog_out = fin.outs[o].index + 1;
+    int32_t prog_kinds[HS_MAX_OUTS] = {};
+    if (n_prog_out > 0) {
+        hs_col pcols[HS_MAX_COLS];
+        for (int i = 0; i < HS_MAX_COLS; ++i) {
+            const int j = fin.prog_src[i];
+            if (j >= 0 && j < nf) pcols[i] = hs_col{mspec.is_int[j] ? HS_I64 : HS_F64, -1, (char*)B.macc.p + (size_t)j * (size_t)cap * 8, nullptr, nullptr};
+            else pcols[i] = hs_col{kc.kind == HS_STR ? HS_U8 : kc.kind, -1, B.mkey.p, nullptr, nullptr};
+        }
+        void* outs[HS_MAX_OUTS] = {};
+        for (int o = 0; o < fin.n_out; ++o) {
+            const hs_finish_out& d = fin.outs[o];
+            if (d.src == 2) prog_kinds[d.index] = d.kind == HS_F32 ? HS_F64 : HS_I64;
+        }
+        for (int k = 0; k < n_prog_out; ++k) outs[k] = (char*)B.prog_out.p + (size_t)k * (size_t)cap * 8;
+        rc = hs_eval(stream, pcols, HS_MAX_COLS, &fin_prog, nullptr, cap, ng, outs, prog_kinds, n_prog_out, flags);
+        if (rc) return rc;
+    }
+    // result columns in their stored kinds, at the image's offsets
+    for (int o = 0; o < fin.n_out; ++o) {
+        const hs_finish_out& d = fin.outs[o];
+        char* dst = (char*)B.image.p + d.offset;
+        if (d.src == 0) {
+            if (hipMemcpyAsync(dst, B.mkey.p, (size_t)cap * (size_t)key_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) return HS_E_LAUNCH;
+            continue;
+        }
+        const void* cells = d.src == 1 ? (const char*)B.macc.p + (size_t)d.index * (size_t)cap * 8
+                                       : (const char*)B.prog_out.p + (size_t)d.index * (size_t)cap * 8;
+        const bool is_int = d.src == 1 ? mspec.is_int[d.index] != 0 : prog_kinds[d.index] == HS_I64;
+        if (d.kind == HS_I64) {
+            if (hipMemcpyAsync(dst, cells, (size_t)cap * 8, hipMemcpyDeviceToDevice, stream) != hipSuccess) return HS_E_LAUNCH;
+        } else {
+            rc = hs_quantise(stream, cells, is_int ? HS_I64 : HS_F64, cap, ng, dst, flags);
+            if (rc) return rc;
+        }
+    }
+    int64_t n_groups = 0;
+    uint32_t f = 0;
+    if (hipMemcpyAsync((char*)image_host, B.image.p, (size_t)image_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipMemcpyAsync(&n_groups, ng, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipMemcpyAsync(&f, flags, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+        return HS_E_LAUNCH;
+    *flags_out = f;
+    *rows_out = n_groups < cap ? n_groups : cap;
+    return HS_OK;
+}
+
+}  // namespace
+
 struct hs_stage {
     hs_engine* engine = nullptr;
     hs_table* table = nullptr;
@@ -672,8 +791,7 @@ struct hs_stage {
     int32_t tier = 0;  // 0: per-lane tables + the one-launch finish; 1: shared dictionary + general tail
     DevBuf key_col, key_wide;  // a computed GROUP BY key (plan version 2): the 4-byte column the scan reads + its i64 evaluation
     hs_col kcols[HS_MAX_COLS];
-    DevBuf sh_rep, sh_acc, sh_ngroups, sh_pack_start, sh_dense_rep, sh_order, sh_key, sh_accs, sh_mrep, sh_macc, sh_mgroups, sh_mkey,
-        sh_prog_out, sh_image;
+    SharedBufs sh;
     int64_t sh_slots = 0;
     void* image_host = nullptr;  // pinned, mapped
     void* image_dev = nullptr;
@@ -887,27 +1005,14 @@ int shared_prepare(hs_stage* s) {
     const int64_t slots = s->sh_slots > 0 ? s->sh_slots : 1;
     bool ok = s->chunks.alloc(chunks.size() * sizeof(hs_chunk)) &&
               hipMemcpy(s->chunks.p, chunks.data(), chunks.size() * sizeof(hs_chunk), hipMemcpyHostToDevice) == hipSuccess &&
-              s->ws.alloc(s->geom.ws_bytes, true) && s->sh_rep.alloc((size_t)slots * 8) &&
-              s->sh_acc.alloc((size_t)slots * (size_t)(n_acc > 0 ? n_acc : 1) * 8) && s->sh_ngroups.alloc((size_t)(s->n_units + 1) * 4) &&
-              s->sh_pack_start.alloc((size_t)(s->n_units + 1) * 8) && s->sh_dense_rep.alloc((size_t)slots * 8) &&
-              s->sh_order.alloc((size_t)slots * 8) && s->sh_key.alloc((size_t)slots * 8) &&
-              s->sh_accs.alloc((size_t)slots * 4 * (size_t)(n_acc > 0 ? n_acc : 1)) && s->sh_mrep.alloc((size_t)s->merge_cap * 8) &&
-              s->sh_macc.alloc((size_t)s->merge_cap * 8 * (size_t)(nf > 0 ? nf : 1)) && s->sh_mgroups.alloc(8) &&
-              s->sh_mkey.alloc((size_t)s->merge_cap * 8) && s->sh_prog_out.alloc((size_t)s->merge_cap * 8 * HS_MAX_OUTS);
+              s->ws.alloc(s->geom.ws_bytes, true) && shared_alloc(s->sh, slots, s->n_units, n_acc, nf, s->merge_cap);
     // result image: the layout of the on-chip path (hs_result_columns / hs_result_write_blockfile read it)
     s->fin = P.fin;
-    int64_t pos = 16;
-    for (int o = 0; o < s->fin.n_out; ++o) {
-        hs_finish_out& out = s->fin.outs[o];
-        const int width = out.src == 0 ? s->key_bytes : (out.kind == HS_I64 ? 8 : 4);
-        out.offset = pos;
-        pos = (pos + (int64_t)s->merge_cap * width + 15) & ~(int64_t)15;
-    }
-    s->image_bytes = pos;
+    s->image_bytes = image_layout(s->fin, s->key_bytes, s->merge_cap);
     if (s->image_host) (void)hipHostFree(s->image_host);
     s->image_host = s->image_dev = nullptr;
     ok = ok && hipHostMalloc(&s->image_host, (size_t)s->image_bytes + kPad, hipHostMallocDefault) == hipSuccess &&
-         s->sh_image.alloc((size_t)s->image_bytes, true);
+         s->sh.image.alloc((size_t)s->image_bytes, true);
     if (!ok) {
         hs_set_error("hs_stage: out of device / pinned memory");
         return HS_E_LAUNCH;
@@ -925,7 +1030,6 @@ int shared_run(hs_stage* s, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const hs_stage_plan& P = s->plan;
     uint32_t* flags = (uint32_t*)s->engine->flags.p;
-    const int n_acc = P.spec.n_acc, nf = s->fin.n_fold, unit_cap = s->geom.pad, cap = s->merge_cap;
     const int64_t slots = s->sh_slots;
     s->last_rows = 0;
     if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
@@ -936,87 +1040,10 @@ int shared_run(hs_stage* s, void* stream_) {
     int rc = compute_key(s, stream);
     if (rc) return rc;
     rc = hs_agg_shared(stream, s->cols, P.n_cols, P.key_slot, &P.prog, &P.spec, (const hs_chunk*)s->chunks.p, s->n_units, &s->geom,
-                           (int64_t*)s->sh_rep.p, (uint64_t*)s->sh_acc.p, (int32_t*)s->sh_ngroups.p, s->ws.p, flags, nullptr, nullptr);
+                           (int64_t*)s->sh.rep.p, (uint64_t*)s->sh.acc.p, (int32_t*)s->sh.ngroups.p, s->ws.p, flags, nullptr, nullptr);
     if (rc) return rc;
-    // dense partial rows = the reference's shuffle-file content: accumulators in their stored kinds, unit of every row
-    void* acc_ptrs[HS_MAX_ACC] = {};
-    int32_t acc_kinds[HS_MAX_ACC] = {};
-    for (int a = 0; a < n_acc; ++a) {
-        acc_ptrs[a] = (char*)s->sh_accs.p + (size_t)a * (size_t)slots * 4;
-        acc_kinds[a] = P.spec.is_int[a] ? HS_I32 : HS_F32;
-    }
-    rc = hs_agg_pack(stream, (const int64_t*)s->sh_rep.p, (const uint64_t*)s->sh_acc.p, (const int32_t*)s->sh_ngroups.p, s->n_units, unit_cap,
-                     &P.spec, (int64_t*)s->sh_pack_start.p, (int64_t*)s->sh_dense_rep.p, acc_ptrs, acc_kinds, nullptr, (int64_t*)s->sh_order.p);
-    if (rc) return rc;
-    const int64_t* n_dense = (const int64_t*)s->sh_pack_start.p + s->n_units;
-    const hs_col& kc = s->cols[P.key_slot];
-    rc = hs_gather_fixed(stream, kc.data, s->key_bytes, s->table->nrows, (const int64_t*)s->sh_dense_rep.p, slots, n_dense, s->sh_key.p, flags);
-    if (rc) return rc;
-    // final merge (tasks.py:290-292): fold j = fold_op[j] over the dense accumulator column fold_src[j], partials in unit order
-    hs_col key_dense{kc.kind, kc.kind == HS_STR ? kc.fixed_len : -1, s->sh_key.p, nullptr, nullptr};
-    hs_col fold_cols[HS_MAX_ACC];
-    hs_agg_spec mspec{};
-    mspec.n_acc = nf;
-    for (int j = 0; j < nf; ++j) {
-        const int src = s->fin.fold_src[j];
-        fold_cols[j] = hs_col{acc_kinds[src], -1, acc_ptrs[src], nullptr, nullptr};
-        mspec.op[j] = (uint8_t)s->fin.fold_op[j];
-        mspec.is_int[j] = P.spec.is_int[src];
-    }
-    rc = hs_agg_merge(stream, &key_dense, fold_cols, &mspec, (const int64_t*)s->sh_order.p, s->n_units, slots, n_dense, cap,
-                      (int64_t*)s->sh_mrep.p, (uint64_t*)s->sh_macc.p, (int64_t*)s->sh_mgroups.p, flags);
-    if (rc) return rc;  // HS_E_LIMIT: more partial rows than the on-chip merge holds
-    const int64_t* ng = (const int64_t*)s->sh_mgroups.p;
-    rc = hs_gather_fixed(stream, s->sh_key.p, s->key_bytes, slots, (const int64_t*)s->sh_mrep.p, cap, ng, s->sh_mkey.p, flags);
-    if (rc) return rc;
-    // projection after the merge (AVG = sum / count ...): the merged cells are its columns (slot -> key / fold j)
-    int n_prog_out = 0;
-    for (int o = 0; o < s->fin.n_out; ++o)
-        if (s->fin.outs[o].src == 2 && s->fin.outs[o].index + 1 > n_prog_out) n_prog_out = s->fin.outs[o].index + 1;
-    int32_t prog_kinds[HS_MAX_OUTS] = {};
-    if (n_prog_out > 0) {
-        hs_col pcols[HS_MAX_COLS];
-        for (int i = 0; i < HS_MAX_COLS; ++i) {
-            const int j = s->fin.prog_src[i];
-            if (j >= 0 && j < nf) pcols[i] = hs_col{mspec.is_int[j] ? HS_I64 : HS_F64, -1, (char*)s->sh_macc.p + (size_t)j * (size_t)cap * 8, nullptr, nullptr};
-            else pcols[i] = hs_col{kc.kind == HS_STR ? HS_U8 : kc.kind, -1, s->sh_mkey.p, nullptr, nullptr};
-        }
-        void* outs[HS_MAX_OUTS] = {};
-        for (int o = 0; o < s->fin.n_out; ++o) {
-            const hs_finish_out& d = s->fin.outs[o];
-            if (d.src == 2) prog_kinds[d.index] = d.kind == HS_F32 ? HS_F64 : HS_I64;
-        }
-        for (int k = 0; k < n_prog_out; ++k) outs[k] = (char*)s->sh_prog_out.p + (size_t)k * (size_t)cap * 8;
-        rc = hs_eval(stream, pcols, HS_MAX_COLS, &P.fin_prog, nullptr, cap, ng, outs, prog_kinds, n_prog_out, flags);
-        if (rc) return rc;
-    }
-    // result columns in their stored kinds, at the image's offsets
-    for (int o = 0; o < s->fin.n_out; ++o) {
-        const hs_finish_out& d = s->fin.outs[o];
-        char* dst = (char*)s->sh_image.p + d.offset;
-        if (d.src == 0) {
-            if (hipMemcpyAsync(dst, s->sh_mkey.p, (size_t)cap * (size_t)s->key_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) return HS_E_LAUNCH;
-            continue;
-        }
-        const void* cells = d.src == 1 ? (const char*)s->sh_macc.p + (size_t)d.index * (size_t)cap * 8
-                                       : (const char*)s->sh_prog_out.p + (size_t)d.index * (size_t)cap * 8;
-        const bool is_int = d.src == 1 ? mspec.is_int[d.index] != 0 : prog_kinds[d.index] == HS_I64;
-        if (d.kind == HS_I64) {
-            if (hipMemcpyAsync(dst, cells, (size_t)cap * 8, hipMemcpyDeviceToDevice, stream) != hipSuccess) return HS_E_LAUNCH;
-        } else {
-            rc = hs_quantise(stream, cells, is_int ? HS_I64 : HS_F64, cap, ng, dst, flags);
-            if (rc) return rc;
-        }
-    }
-    int64_t n_groups = 0;
-    uint32_t f = 0;
-    if (hipMemcpyAsync((char*)s->image_host, s->sh_image.p, (size_t)s->image_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(&n_groups, ng, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(&f, flags, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-        return HS_E_LAUNCH;
-    s->last_flags = f;
-    s->last_rows = n_groups < cap ? n_groups : cap;
-    return HS_OK;
+    return shared_tail(stream, s->sh, P.spec, s->fin, P.fin_prog, s->cols[P.key_slot], s->key_bytes, s->table->nrows, s->n_units,
+                       s->geom.pad, slots, s->merge_cap, s->image_host, s->image_bytes, flags, &s->last_flags, &s->last_rows);
 }
 
 }  // namespace
@@ -1350,12 +1377,13 @@ bool fetch_string(const hs_col& c, int64_t row, std::string& out) {
 
 // Device.dict_encode natively: distinct strings of the column (device set, representative rows read back), sorted, codes
 // named BY STRING, one code byte per row.  HS_E_LIMIT when the column has more than 255 distinct values.
-int join_encode_payload(hs_join_stage* s, const hs_col& col, int64_t n) {
+// `who`: the stage and column named in the errors; dict / codes: the result
+int join_encode_payload(const char* who, const hs_col& col, int64_t n, std::vector<std::string>& dict, DevBuf& codes) {
     const int32_t cap = 4096;
     DevBuf words, reps, state, slot_code;
     if (!words.alloc((size_t)cap * 8) || !reps.alloc((size_t)cap * 8) || !state.alloc(8, true) || !slot_code.alloc(cap, true) ||
-        !s->codes.alloc((size_t)(n > 0 ? n : 1))) {
-        hs_set_error("hs_join_stage: out of device memory");
+        !codes.alloc((size_t)(n > 0 ? n : 1))) {
+        hs_set_error("%s: out of device memory", who);
         return HS_E_LAUNCH;
     }
     int rc = hs_dict_build(nullptr, &col, n, cap, (uint64_t*)words.p, (int64_t*)reps.p, (int32_t*)state.p, (uint32_t*)state.p + 1);
@@ -1366,7 +1394,7 @@ int join_encode_payload(hs_join_stage* s, const hs_col& col, int64_t n) {
         hipMemcpy(host_reps.data(), reps.p, (size_t)cap * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return HS_E_LAUNCH;
     if (st[1]) {
-        hs_set_error("hs_join_stage: the build-side column has too many distinct values for a code byte");
+        hs_set_error("%s has too many distinct values for a code byte", who);
         return HS_E_LIMIT;
     }
     std::vector<std::pair<int, std::string>> found;  // (slot, string)
@@ -1376,20 +1404,20 @@ int join_encode_payload(hs_join_stage* s, const hs_col& col, int64_t n) {
         if (!fetch_string(col, host_reps[(size_t)sl], text)) return HS_E_LAUNCH;
         found.emplace_back(sl, std::move(text));
     }
-    s->dict.clear();
-    for (const auto& f : found) s->dict.push_back(f.second);
-    std::sort(s->dict.begin(), s->dict.end());
-    s->dict.erase(std::unique(s->dict.begin(), s->dict.end()), s->dict.end());
-    if (s->dict.size() > 255) {
-        hs_set_error("hs_join_stage: the build-side column has %zu distinct values (> 255)", s->dict.size());
+    dict.clear();
+    for (const auto& f : found) dict.push_back(f.second);
+    std::sort(dict.begin(), dict.end());
+    dict.erase(std::unique(dict.begin(), dict.end()), dict.end());
+    if (dict.size() > 255) {
+        hs_set_error("%s has %zu distinct values (> 255)", who, dict.size());
         return HS_E_LIMIT;
     }
     std::vector<uint8_t> codes_of_slot((size_t)cap, 0);
     for (const auto& f : found)
-        codes_of_slot[(size_t)f.first] = (uint8_t)(std::lower_bound(s->dict.begin(), s->dict.end(), f.second) - s->dict.begin());
+        codes_of_slot[(size_t)f.first] = (uint8_t)(std::lower_bound(dict.begin(), dict.end(), f.second) - dict.begin());
     if (hipMemcpy(slot_code.p, codes_of_slot.data(), (size_t)cap, hipMemcpyHostToDevice) != hipSuccess) return HS_E_LAUNCH;
     if (n > 0) {
-        rc = hs_dict_assign(nullptr, &col, n, cap, (uint64_t*)words.p, (int64_t*)reps.p, (const uint8_t*)slot_code.p, (uint8_t*)s->codes.p,
+        rc = hs_dict_assign(nullptr, &col, n, cap, (uint64_t*)words.p, (int64_t*)reps.p, (const uint8_t*)slot_code.p, (uint8_t*)codes.p,
                             (uint32_t*)state.p + 1);
         if (rc) return rc;
     }
@@ -1541,7 +1569,7 @@ extern "C" int hs_join_stage_prepare(hs_engine* e, hs_table* build, hs_table* pr
             hs_set_error("hs_join_stage_prepare: the build-side column must be a STRING column");
             return fail(HS_E_LIMIT);
         }
-        rc = join_encode_payload(s, pc, build->nrows);
+        rc = join_encode_payload("hs_join_stage: the build-side column", pc, build->nrows, s->dict, s->codes);
         if (rc) return fail(rc);
     }
     // key range of the build side -> direct addressing
@@ -1672,52 +1700,52 @@ extern "C" int hs_join_stage_stats(const hs_join_stage* s, int64_t* stats) {
     return HS_OK;
 }
 
-// The result as a one-block BlockFile (tasks.py:400-410, io.py:47-109).  A key that is the build-side column arrives as
-// code bytes: decoded through the stage's dictionary here.
-extern "C" int hs_join_result_write_blockfile(const hs_join_stage* s, const char* path) {
-    if (!s || !s->ready || !path) {
-        hs_set_error("hs_join_result_write_blockfile: bad arguments");
-        return HS_E_ARG;
-    }
-    if (s->last_rows == 0) return HS_OK;  // empty result: the reference writes no file (tasks.py:405)
+namespace {
+
+// The on-chip path's result image as a one-block BlockFile (tasks.py:400-410, io.py:47-109); a key of dictionary codes
+// (dict != NULL) is decoded through the dictionary.  `who` names the entry point in errors.
+int write_image_blockfile(const char* who, const char* path, const hs_finish_spec& fin, const int32_t* out_types,
+                          const char (*out_names)[64], const void* image_host, int64_t last_rows, int key_kind, int key_bytes,
+                          const std::vector<std::string>* dict) {
+    if (last_rows == 0) return HS_OK;  // empty result: the reference writes no file (tasks.py:405)
     FILE* f = fopen(path, "wb");
     if (!f) {
-        hs_set_error("hs_join_result_write_blockfile: cannot create %s", path);
+        hs_set_error("%s: cannot create %s", who, path);
         return HS_E_ARG;
     }
-    const int n_out = s->fin.n_out;
+    const int n_out = fin.n_out;
     const uint8_t nc = (uint8_t)n_out;
     fwrite(&nc, 1, 1, f);
     for (int o = 0; o < n_out; ++o) {
-        const uint8_t type = (uint8_t)s->plan.out_types[o];
-        const uint8_t len = (uint8_t)strnlen(s->plan.out_names[o], sizeof(s->plan.out_names[o]));
+        const uint8_t type = (uint8_t)out_types[o];
+        const uint8_t len = (uint8_t)strnlen(out_names[o], 64);
         fwrite(&type, 1, 1, f);
         fwrite(&len, 1, 1, f);
-        fwrite(s->plan.out_names[o], 1, len, f);
+        fwrite(out_names[o], 1, len, f);
     }
     const uint64_t block_start = (uint64_t)ftell(f);
-    const uint32_t rows = (uint32_t)s->last_rows;
+    const uint32_t rows = (uint32_t)last_rows;
     fwrite(&rows, 4, 1, f);
     bool ok = true;
     for (int o = 0; o < n_out; ++o) {
-        const hs_finish_out& d = s->fin.outs[o];
-        const uint8_t* col = (const uint8_t*)s->image_host + d.offset;
-        if (d.src == 0 && s->key_is_payload) {  // code bytes -> the strings they stand for
+        const hs_finish_out& d = fin.outs[o];
+        const uint8_t* col = (const uint8_t*)image_host + d.offset;
+        if (d.src == 0 && dict) {  // code bytes -> the strings they stand for
             uint64_t bytes = rows;
             for (uint32_t r = 0; r < rows; ++r) {
-                if (col[r] >= s->dict.size()) ok = false;
-                else bytes += s->dict[col[r]].size();
+                if (col[r] >= dict->size()) ok = false;
+                else bytes += (*dict)[col[r]].size();
             }
             fwrite(&bytes, 8, 1, f);
             for (uint32_t r = 0; ok && r < rows; ++r) {
-                const uint8_t len = (uint8_t)s->dict[col[r]].size();
+                const uint8_t len = (uint8_t)(*dict)[col[r]].size();
                 fwrite(&len, 1, 1, f);
             }
-            for (uint32_t r = 0; ok && r < rows; ++r) fwrite(s->dict[col[r]].data(), 1, s->dict[col[r]].size(), f);
+            for (uint32_t r = 0; ok && r < rows; ++r) fwrite((*dict)[col[r]].data(), 1, (*dict)[col[r]].size(), f);
             continue;
         }
-        const bool is_key_string = d.src == 0 && s->key_kind == HS_STR;
-        const int width = d.src == 0 ? s->key_bytes : (d.kind == HS_I64 ? 8 : 4);
+        const bool is_key_string = d.src == 0 && key_kind == HS_STR;
+        const int width = d.src == 0 ? key_bytes : (d.kind == HS_I64 ? 8 : 4);
         const uint64_t bytes = (uint64_t)rows * (uint64_t)width + (is_key_string ? rows : 0);
         fwrite(&bytes, 8, 1, f);
         if (is_key_string) {
@@ -1731,10 +1759,23 @@ extern "C" int hs_join_result_write_blockfile(const hs_join_stage* s, const char
     fwrite(&nblocks, 4, 1, f);
     ok = (fclose(f) == 0) && ok;
     if (!ok) {
-        hs_set_error("hs_join_result_write_blockfile: write to %s failed (or a key code outside the dictionary)", path);
+        hs_set_error("%s: write to %s failed (or a key code outside the dictionary)", who, path);
         return HS_E_ARG;
     }
     return HS_OK;
+}
+
+}  // namespace
+
+// The result as a one-block BlockFile (tasks.py:400-410, io.py:47-109).  A key that is the build-side column arrives as
+// code bytes: decoded through the stage's dictionary here.
+extern "C" int hs_join_result_write_blockfile(const hs_join_stage* s, const char* path) {
+    if (!s || !s->ready || !path) {
+        hs_set_error("hs_join_result_write_blockfile: bad arguments");
+        return HS_E_ARG;
+    }
+    return write_image_blockfile("hs_join_result_write_blockfile", path, s->fin, s->plan.out_types, s->plan.out_names, s->image_host,
+                                 s->last_rows, s->key_kind, s->key_bytes, s->key_is_payload ? &s->dict : nullptr);
 }
 
 // =====================================================================================================================
@@ -2200,6 +2241,60 @@ int join_pairs(hipStream_t stream, const hs_col& bk, int64_t nb, const hs_col& p
     return rc;
 }
 
+// The first part of a join stage's run (tasks.py:201-240): the WHERE per side, the probe rows in JoinJob order, the join over
+// the key columns of the surviving rows, the table rows of every pair.  pstart: JoinJob starts among the ordered probe rows.
+struct JoinedRows {
+    DevBuf brows, porder, pstart, bidx, pidx;  // bidx / pidx: build / probe table row of every pair
+    JoinPairs J;
+    int64_t nb = 0, np = 0;
+};
+
+int join_rows(hipStream_t stream, hs_table* build, hs_table* probe, int32_t build_key_col, int32_t probe_key_col, int32_t n_parts,
+              const hs_col* bcols, int32_t n_bcols, const hs_program& build_filter, const hs_col* pcols, int32_t n_pcols,
+              const hs_program& probe_filter, uint32_t* flags, JoinedRows& R) {
+    const int64_t nb_all = build->nrows, np_all = probe->nrows;
+    const hs_col& bkey = build->cols[build_key_col].col;
+    const hs_col& pkey = probe->cols[probe_key_col].col;
+    // 1. WHERE per side
+    DevBuf prows;
+    int64_t nb = 0, np = 0;
+    int rc = side_rows(stream, bcols, n_bcols, build_filter, nb_all, R.brows, nb, flags);
+    if (!rc) rc = side_rows(stream, pcols, n_pcols, probe_filter, np_all, prows, np, flags);
+    if (rc) return rc;
+    R.nb = nb;
+    R.np = np;
+    // 2. probe rows in JoinJob order: partition ids of the surviving rows, a stable counting sort, the row ids through it
+    DevBuf part, perm, pws;
+    if (!R.porder.alloc((size_t)(np > 0 ? np : 1) * 8) || !R.pstart.alloc((size_t)(n_parts + 1) * 8, true)) return HS_E_LAUNCH;
+    if (np > 0) {
+        if (!part.alloc((size_t)np) || !perm.alloc((size_t)np * 8) || !pws.alloc(hs_partition_ws_bytes(np, n_parts)))
+            return HS_E_LAUNCH;
+        rc = hs_partition_ids(stream, &pkey, (const int64_t*)prows.p, np, n_parts, (uint8_t*)part.p);
+        if (!rc) rc = hs_partition_perm(stream, (const uint8_t*)part.p, np, n_parts, (int64_t*)perm.p, (int64_t*)R.pstart.p, pws.p);
+        if (!rc) rc = hs_gather_fixed(stream, prows.p, 8, np, (const int64_t*)perm.p, np, nullptr, R.porder.p, flags);
+        if (rc) return rc;
+    }
+    // 3. the join over the key columns of the surviving rows
+    if (nb > 0 && np > 0) {
+        DevBuf bk_data, bk_lens, bk_offs, pk_data, pk_lens, pk_offs;
+        hs_col bk{}, pk{};
+        int64_t payload = 0;
+        rc = gather_col(stream, bkey, nb_all, (const int64_t*)R.brows.p, nb, bk_data, bk_lens, bk_offs, bk, payload, flags);
+        if (!rc) rc = gather_col(stream, pkey, np_all, (const int64_t*)R.porder.p, np, pk_data, pk_lens, pk_offs, pk, payload, flags);
+        if (!rc) rc = join_pairs(stream, bk, nb, pk, np, flags, R.J);
+        if (rc) return rc;
+    }
+    // 4. table rows of every pair
+    const int64_t n_out = R.J.n_out;
+    if (n_out > 0) {
+        if (!R.bidx.alloc((size_t)n_out * 8) || !R.pidx.alloc((size_t)n_out * 8)) return HS_E_LAUNCH;
+        rc = hs_gather_fixed(stream, R.brows.p, 8, nb, (const int64_t*)R.J.out_left.p, n_out, nullptr, R.bidx.p, flags);
+        if (!rc) rc = hs_gather_fixed(stream, R.porder.p, 8, np, (const int64_t*)R.J.out_right.p, n_out, nullptr, R.pidx.p, flags);
+        if (rc) return rc;
+    }
+    return HS_OK;
+}
+
 }  // namespace
 
 extern "C" int hs_join_select_stage_run(hs_join_select_stage* s, void* stream_, uint32_t* flags_out, int64_t* n_rows_out) {
@@ -2212,47 +2307,12 @@ extern "C" int hs_join_select_stage_run(hs_join_select_stage* s, void* stream_, 
     const hs_join_select_stage_plan& P = s->plan;
     uint32_t* flags = (uint32_t*)s->engine->flags.p;
     if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
-    const int64_t nb_all = s->build->nrows, np_all = s->probe->nrows;
-    const hs_col& bkey = s->build->cols[P.build_key_col].col;
-    const hs_col& pkey = s->probe->cols[P.probe_key_col].col;
-    // 1. WHERE per side
-    DevBuf brows, prows;
-    int64_t nb = 0, np = 0;
-    int rc = side_rows(stream, s->bcols, P.n_bcols, P.build_filter, nb_all, brows, nb, flags);
-    if (!rc) rc = side_rows(stream, s->pcols, P.n_pcols, P.probe_filter, np_all, prows, np, flags);
+    JoinedRows R;
+    int rc = join_rows(stream, s->build, s->probe, P.build_key_col, P.probe_key_col, P.n_parts, s->bcols, P.n_bcols, P.build_filter,
+                       s->pcols, P.n_pcols, P.probe_filter, flags, R);
     if (rc) return rc;
-    // 2. probe rows in JoinJob order: partition ids of the surviving rows, a stable counting sort, the row ids through it
-    DevBuf part, perm, pstart, pws, porder;
-    if (!porder.alloc((size_t)(np > 0 ? np : 1) * 8)) return HS_E_LAUNCH;
-    if (np > 0) {
-        if (!part.alloc((size_t)np) || !perm.alloc((size_t)np * 8) || !pstart.alloc((size_t)(P.n_parts + 1) * 8) ||
-            !pws.alloc(hs_partition_ws_bytes(np, P.n_parts)))
-            return HS_E_LAUNCH;
-        rc = hs_partition_ids(stream, &pkey, (const int64_t*)prows.p, np, P.n_parts, (uint8_t*)part.p);
-        if (!rc) rc = hs_partition_perm(stream, (const uint8_t*)part.p, np, P.n_parts, (int64_t*)perm.p, (int64_t*)pstart.p, pws.p);
-        if (!rc) rc = hs_gather_fixed(stream, prows.p, 8, np, (const int64_t*)perm.p, np, nullptr, porder.p, flags);
-        if (rc) return rc;
-    }
-    // 3. the join over the key columns of the surviving rows
-    JoinPairs J;
-    if (nb > 0 && np > 0) {
-        DevBuf bk_data, bk_lens, bk_offs, pk_data, pk_lens, pk_offs;
-        hs_col bk{}, pk{};
-        int64_t payload = 0;
-        rc = gather_col(stream, bkey, nb_all, (const int64_t*)brows.p, nb, bk_data, bk_lens, bk_offs, bk, payload, flags);
-        if (!rc) rc = gather_col(stream, pkey, np_all, (const int64_t*)porder.p, np, pk_data, pk_lens, pk_offs, pk, payload, flags);
-        if (!rc) rc = join_pairs(stream, bk, nb, pk, np, flags, J);
-        if (rc) return rc;
-    }
-    // 4. table rows of every pair, then every output column through them -> host
-    const int64_t n_out = J.n_out;
-    DevBuf bidx, pidx;
-    if (n_out > 0) {
-        if (!bidx.alloc((size_t)n_out * 8) || !pidx.alloc((size_t)n_out * 8)) return HS_E_LAUNCH;
-        rc = hs_gather_fixed(stream, brows.p, 8, nb, (const int64_t*)J.out_left.p, n_out, nullptr, bidx.p, flags);
-        if (!rc) rc = hs_gather_fixed(stream, porder.p, 8, np, (const int64_t*)J.out_right.p, n_out, nullptr, pidx.p, flags);
-        if (rc) return rc;
-    }
+    // every output column through the pair rows -> host
+    const int64_t n_out = R.J.n_out;
     s->outs.assign((size_t)P.n_out, HostCol());
     for (int o = 0; o < P.n_out && n_out > 0; ++o) {
         hs_table* t = P.out_side[o] ? s->probe : s->build;
@@ -2260,7 +2320,7 @@ extern "C" int hs_join_select_stage_run(hs_join_select_stage* s, void* stream_, 
         DevBuf data, lens, offs;
         hs_col g{};
         int64_t payload = 0;
-        rc = gather_col(stream, c, t->nrows, (const int64_t*)(P.out_side[o] ? pidx.p : bidx.p), n_out, data, lens, offs, g, payload, flags);
+        rc = gather_col(stream, c, t->nrows, (const int64_t*)(P.out_side[o] ? R.pidx.p : R.bidx.p), n_out, data, lens, offs, g, payload, flags);
         if (rc) return rc;
         HostCol& out = s->outs[(size_t)o];
         if (c.kind != HS_STR) {
@@ -2280,9 +2340,9 @@ extern "C" int hs_join_select_stage_run(hs_join_select_stage* s, void* stream_, 
     if (hipMemcpyAsync(&f, flags, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return HS_E_LAUNCH;
     s->runs += 1;
     s->last_rows = n_out;
-    s->route = J.route;
-    s->n_build = nb;
-    s->n_probe = np;
+    s->route = R.J.route;
+    s->n_build = R.nb;
+    s->n_probe = R.np;
     if (flags_out) *flags_out = f;
     if (n_rows_out) *n_rows_out = n_out;
     return HS_OK;
@@ -2355,4 +2415,324 @@ extern "C" int hs_join_select_result_write_blockfile(const hs_join_select_stage*
         return HS_E_ARG;
     }
     return HS_OK;
+}
+
+// =====================================================================================================================
+// Round 5: the general JOIN feeding a GROUP BY behind the same boundary - the reference's JoinJob for every join
+// (tasks.py:201-240 build + probe, tasks.py:284-289 partial aggregate, plan.py:99-109) and the final stage after it.  The
+// join is hs_join_select_stage_run's (join_rows); the pairs of one JoinJob are one row-range unit of the shared-dictionary
+// scan, which reads every slot's column gathered through the pair rows; the tail is the scan stage's (shared_tail).
+// =====================================================================================================================
+struct hs_join_group_stage {
+    hs_engine* engine = nullptr;
+    hs_table *build = nullptr, *probe = nullptr;
+    hs_join_group_stage_plan plan{};
+    hs_col bcols[HS_MAX_COLS]{}, pcols[HS_MAX_COLS]{};  // the side filters' columns
+    hs_col src[HS_MAX_COLS]{};                          // table column behind every slot (a coded key: its code bytes)
+    std::vector<std::string> dict;                      // a coded GROUP BY key's strings, sorted: code = index
+    DevBuf codes;                                       // one code byte per row of the key's table
+    bool key_coded = false;
+    int32_t key_kind = HS_I32, key_bytes = 4;
+    // the last run's pairs and the slots' columns through them (a capacity retry aggregates them again): numeric argument
+    // slots as HS_PAIR columns (table column + pair rows, read by the compiled scan), the others gathered
+    JoinedRows R;
+    int32_t agg_route = HS_JOIN_AGG_PAIRS;
+    DevBuf gdata[HS_MAX_COLS], glens[HS_MAX_COLS], goffs[HS_MAX_COLS];
+    hs_col cols[HS_MAX_COLS]{};
+    std::vector<int64_t> unit_rows;  // pairs before JoinJob u, u = 0 .. n_parts
+    // the aggregate over the pairs (rebuilt when a capacity grows)
+    bool ready = false;
+    int32_t group_cap = 16, merge_cap = 64;
+    hs_agg_geom geom{};
+    DevBuf chunks, ws;
+    SharedBufs sh;
+    hs_finish_spec fin{};
+    int64_t slots = 0, image_bytes = 0;
+    void* image_host = nullptr;
+    int64_t runs = 0, grows = 0;
+    uint32_t last_flags = 0;
+    int64_t last_rows = 0;
+    ~hs_join_group_stage() {
+        if (image_host) (void)hipHostFree(image_host);
+    }
+};
+
+extern "C" int hs_join_group_stage_prepare(hs_engine* e, hs_table* build, hs_table* probe, const hs_join_group_stage_plan* plan,
+                                           size_t plan_bytes, hs_join_group_stage** out) {
+    if (!e || !build || !probe || !plan || !out || plan_bytes != sizeof(hs_join_group_stage_plan) ||
+        plan->version != HS_JOIN_GROUP_STAGE_PLAN_VERSION || plan->n_bcols < 0 || plan->n_bcols > HS_MAX_COLS || plan->n_pcols < 0 ||
+        plan->n_pcols > HS_MAX_COLS || plan->n_cols < 1 || plan->n_cols > HS_FUSED_COLS || plan->key_slot < 0 ||
+        plan->key_slot >= plan->n_cols || plan->n_parts < 1 || plan->n_parts > 255 || plan->fin.n_out < 1 ||
+        plan->fin.n_out > HS_FINISH_MAX_OUT) {
+        hs_set_error("hs_join_group_stage_prepare: bad plan blob (size %zu, expected %zu)", plan_bytes, sizeof(hs_join_group_stage_plan));
+        return HS_E_ARG;
+    }
+    std::vector<int32_t> need[2];
+    need[0].assign(plan->bcol_ids, plan->bcol_ids + plan->n_bcols);
+    need[1].assign(plan->pcol_ids, plan->pcol_ids + plan->n_pcols);
+    need[0].push_back(plan->build_key_col);
+    need[1].push_back(plan->probe_key_col);
+    for (int i = 0; i < plan->n_cols; ++i) {
+        if (plan->col_side[i] != 0 && plan->col_side[i] != 1) {
+            hs_set_error("hs_join_group_stage_prepare: slot %d names no side", i);
+            return HS_E_ARG;
+        }
+        need[plan->col_side[i]].push_back(plan->col_ids[i]);
+    }
+    hs_table* tables[2] = {build, probe};
+    for (int side = 0; side < 2; ++side)
+        for (int32_t c : need[side])
+            if (c < 0 || c >= (int)tables[side]->cols.size()) {
+                hs_set_error("hs_join_group_stage_prepare: no such column %d in the %s table", c, side ? "probe" : "build");
+                return HS_E_ARG;
+            }
+    const int32_t bt = build->cols[plan->build_key_col].type, pt = probe->cols[plan->probe_key_col].type;
+    if (bt != pt || (bt != 0 && bt != 1)) {
+        hs_set_error("hs_join_group_stage_prepare: join keys must be both INTEGER or both STRING (types %d, %d)", bt, pt);
+        return HS_E_LIMIT;
+    }
+    if (hipSetDevice(e->device) != hipSuccess) return HS_E_LAUNCH;
+    for (int side = 0; side < 2; ++side) {
+        const int rc = hs_table_load(e, tables[side], need[side].data(), (int32_t)need[side].size());
+        if (rc) return rc;
+    }
+    hs_join_group_stage* s = new hs_join_group_stage();
+    s->engine = e;
+    s->build = build;
+    s->probe = probe;
+    s->plan = *plan;
+    // starting capacities: powers of two (the geometry and the x4 growth need them), at most the on-chip tiers' 4096
+    while (s->group_cap < plan->group_cap && s->group_cap < 4096) s->group_cap *= 2;
+    while (s->merge_cap < plan->merge_cap && s->merge_cap < 4096) s->merge_cap *= 2;
+    for (int i = 0; i < plan->n_bcols; ++i) s->bcols[i] = build->cols[plan->bcol_ids[i]].col;
+    for (int i = 0; i < plan->n_pcols; ++i) s->pcols[i] = probe->cols[plan->pcol_ids[i]].col;
+    for (int i = 0; i < plan->n_cols; ++i) s->src[i] = tables[plan->col_side[i]]->cols[plan->col_ids[i]].col;
+    // the GROUP BY key: INTEGER / FLOAT / TIMESTAMP and 1 / 2 / 4-byte strings as stored, other strings as code bytes
+    const hs_table* kt = tables[plan->col_side[plan->key_slot]];
+    hs_col& kc = s->src[plan->key_slot];
+    if (kc.kind == HS_STR && kc.fixed_len != 1 && kc.fixed_len != 2 && kc.fixed_len != 4) {
+        const int rc = kt->nrows > 0 ? join_encode_payload("hs_join_group_stage: the GROUP BY column", kc, kt->nrows, s->dict, s->codes)
+                                     : (s->codes.alloc(1, true) ? HS_OK : HS_E_LAUNCH);
+        if (rc) {
+            delete s;
+            return rc;
+        }
+        kc = hs_col{HS_STR, 1, s->codes.p, nullptr, nullptr};
+        s->key_coded = true;
+    }
+    if (kc.kind == HS_STR) {
+        s->key_kind = HS_STR;
+        s->key_bytes = kc.fixed_len;
+    } else if (kc.kind == HS_I32 || kc.kind == HS_F32 || kc.kind == HS_I64) {
+        s->key_kind = kc.kind;
+        s->key_bytes = elem_bytes(kc.kind);
+    } else {
+        delete s;
+        hs_set_error("hs_join_group_stage_prepare: GROUP BY key is not a stored column kind");
+        return HS_E_LIMIT;
+    }
+    *out = s;
+    return HS_OK;
+}
+
+extern "C" void hs_join_group_stage_destroy(hs_join_group_stage* s) { delete s; }
+
+namespace {
+
+// geometry, unit tables and result image of the aggregate over the pairs, at the stage's current capacities
+int join_group_prepare(hs_join_group_stage* s) {
+    const hs_join_group_stage_plan& P = s->plan;
+    s->ready = false;
+    const int64_t n_units = P.n_parts;
+    int rc = hs_agg_shared_geom(s->unit_rows.data(), n_units, P.spec.n_acc, s->group_cap, &s->geom);
+    if (rc) return rc;
+    std::vector<hs_chunk> chunks((size_t)(s->geom.n_chunks > 0 ? s->geom.n_chunks : 1));
+    std::vector<int64_t> chunk0((size_t)n_units + 1, 0);
+    rc = hs_agg_partial_chunks(s->unit_rows.data(), n_units, &s->geom, chunks.data(), chunk0.data());
+    if (rc) return rc;
+    s->slots = n_units * (int64_t)s->geom.pad;
+    s->fin = P.fin;
+    s->image_bytes = image_layout(s->fin, s->key_bytes, s->merge_cap);
+    if (s->image_host) (void)hipHostFree(s->image_host);
+    s->image_host = nullptr;
+    const bool ok = s->chunks.alloc(chunks.size() * sizeof(hs_chunk)) &&
+                    hipMemcpy(s->chunks.p, chunks.data(), chunks.size() * sizeof(hs_chunk), hipMemcpyHostToDevice) == hipSuccess &&
+                    s->ws.alloc(s->geom.ws_bytes, true) && shared_alloc(s->sh, s->slots, n_units, P.spec.n_acc, P.fin.n_fold, s->merge_cap) &&
+                    hipHostMalloc(&s->image_host, (size_t)s->image_bytes + kPad, hipHostMallocDefault) == hipSuccess &&
+                    s->sh.image.alloc((size_t)s->image_bytes, true);
+    if (!ok) {
+        hs_set_error("hs_join_group_stage: out of device / pinned memory");
+        return HS_E_LAUNCH;
+    }
+    memset(s->image_host, 0, (size_t)s->image_bytes + kPad);
+    s->ready = true;
+    return HS_OK;
+}
+
+// every slot's column over the pairs: with `pairs`, a numeric argument slot is the table column read through the pair rows
+// (HS_PAIR); the key and the string slots - and every slot without `pairs` - are gathered through them
+int join_group_columns(hs_join_group_stage* s, hipStream_t stream, uint32_t* flags, bool pairs) {
+    const hs_join_group_stage_plan& P = s->plan;
+    const int64_t n = s->R.J.n_out;
+    s->agg_route = pairs ? HS_JOIN_AGG_PAIRS : HS_JOIN_AGG_GATHERED;
+    for (int i = 0; i < P.n_cols; ++i) {
+        const hs_table* t = P.col_side[i] ? s->probe : s->build;
+        const int64_t* idx = (const int64_t*)(P.col_side[i] ? s->R.pidx.p : s->R.bidx.p);
+        const hs_col& c = s->src[i];
+        int rc = HS_OK;
+        if (pairs && i != P.key_slot && (c.kind == HS_I32 || c.kind == HS_F32 || c.kind == HS_I64)) {
+            s->gdata[i].release();
+            s->cols[i] = hs_col{HS_PAIR | c.kind, -1, c.data, nullptr, idx};
+        } else if (c.kind == HS_STR && i == P.key_slot) {  // a fixed-width key stays fixed-width: the scan packs it into the key word
+            if (!s->gdata[i].alloc((size_t)n * (size_t)c.fixed_len)) return HS_E_LAUNCH;
+            rc = hs_gather_fixed(stream, c.data, c.fixed_len, t->nrows, idx, n, nullptr, s->gdata[i].p, flags);
+            s->cols[i] = hs_col{HS_STR, c.fixed_len, s->gdata[i].p, nullptr, nullptr};
+        } else {
+            int64_t payload = 0;
+            rc = gather_col(stream, c, t->nrows, idx, n, s->gdata[i], s->glens[i], s->goffs[i], s->cols[i], payload, flags);
+        }
+        if (rc) return rc;
+    }
+    return HS_OK;
+}
+
+// the join, the JoinJob boundaries among the pairs, every slot's column over the pairs
+int join_group_pairs(hs_join_group_stage* s, hipStream_t stream, uint32_t* flags) {
+    const hs_join_group_stage_plan& P = s->plan;
+    s->R = JoinedRows();  // the previous run's pairs go before this run's are made (peak HBM: one set)
+    for (int i = 0; i < HS_MAX_COLS; ++i) {
+        s->gdata[i].release();
+        s->glens[i].release();
+        s->goffs[i].release();
+    }
+    JoinedRows R;
+    int rc = join_rows(stream, s->build, s->probe, P.build_key_col, P.probe_key_col, P.n_parts, s->bcols, P.n_bcols, P.build_filter,
+                       s->pcols, P.n_pcols, P.probe_filter, flags, R);
+    if (rc) return rc;
+    R.J.out_left.release();  // (the table rows of the pairs are in bidx / pidx)
+    R.J.out_right.release();
+    s->R = std::move(R);
+    const int64_t n = s->R.J.n_out;
+    std::vector<int64_t> unit_rows((size_t)P.n_parts + 1, 0);
+    if (n > 0) {
+        // the compiled scan reads a lane's four pair rows at once: the 4 past the last pair hold row 0, not stale bytes
+        if (hipMemsetAsync((char*)s->R.bidx.p + n * 8, 0, 32, stream) != hipSuccess ||
+            hipMemsetAsync((char*)s->R.pidx.p + n * 8, 0, 32, stream) != hipSuccess)
+            return HS_E_LAUNCH;
+        // JoinJob u's pairs start where its first probe row's do: out_start at the partition starts, one readback
+        DevBuf starts;
+        if (!starts.alloc((size_t)(P.n_parts + 1) * 8)) return HS_E_LAUNCH;
+        rc = hs_gather_fixed(stream, s->R.J.out_start.p, 8, s->R.np + 1, (const int64_t*)s->R.pstart.p, P.n_parts + 1, nullptr, starts.p, flags);
+        if (rc) return rc;
+        if (hipMemcpyAsync(unit_rows.data(), starts.p, (size_t)(P.n_parts + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess)
+            return HS_E_LAUNCH;
+        unit_rows[0] = 0;
+        unit_rows[(size_t)P.n_parts] = n;
+    }
+    if (unit_rows != s->unit_rows) s->ready = false;  // the chunk geometry follows the JoinJob boundaries
+    s->unit_rows = std::move(unit_rows);
+    if (n == 0) return HS_OK;
+    return join_group_columns(s, stream, flags, hs_jit_get_enabled() != 0);
+}
+
+}  // namespace
+
+// One query on one GPU: join -> aggregate over the pairs -> final merge + projection -> result image on the host.  A
+// dictionary overflow grows the capacities and aggregates the same pairs again; beyond the on-chip tiers: HS_E_LIMIT.
+extern "C" int hs_join_group_stage_run(hs_join_group_stage* s, void* stream_, uint32_t* flags_out, int64_t* n_rows_out) {
+    if (!s) {
+        hs_set_error("hs_join_group_stage_run: null stage");
+        return HS_E_ARG;
+    }
+    if (hipSetDevice(s->engine->device) != hipSuccess) return HS_E_LAUNCH;
+    hipStream_t stream = (hipStream_t)stream_;
+    const hs_join_group_stage_plan& P = s->plan;
+    uint32_t* flags = (uint32_t*)s->engine->flags.p;
+    if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
+    int rc = join_group_pairs(s, stream, flags);
+    if (rc) return rc;
+    uint32_t join_flags = 0;  // errors of the side filters and gathers (the aggregate starts from clear flags)
+    if (hipMemcpyAsync(&join_flags, flags, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+        return HS_E_LAUNCH;
+    ++s->runs;
+    s->last_rows = 0;
+    s->last_flags = join_flags;
+    const int64_t n_pairs = s->R.J.n_out;
+    for (int attempt = 0; n_pairs > 0 && attempt < 14; ++attempt) {
+        s->last_rows = 0;
+        if (!s->ready) rc = join_group_prepare(s);
+        if (rc) return rc;
+        if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
+        rc = hs_agg_shared(stream, s->cols, P.n_cols, P.key_slot, &P.prog, &P.spec, (const hs_chunk*)s->chunks.p, P.n_parts, &s->geom,
+                           (int64_t*)s->sh.rep.p, (uint64_t*)s->sh.acc.p, (int32_t*)s->sh.ngroups.p, s->ws.p, flags, nullptr, nullptr);
+        if (rc == HS_E_LIMIT && s->agg_route == HS_JOIN_AGG_PAIRS) {
+            // the run-time compiler could not take this program: the interpreter reads the same columns gathered
+            rc = join_group_columns(s, stream, flags, false);
+            if (rc) return rc;
+            continue;
+        }
+        uint32_t f = 0;
+        if (!rc)
+            rc = shared_tail(stream, s->sh, P.spec, s->fin, P.fin_prog, s->cols[P.key_slot], s->key_bytes, n_pairs, P.n_parts, s->geom.pad,
+                             s->slots, s->merge_cap, s->image_host, s->image_bytes, flags, &f, &s->last_rows);
+        if (rc) return rc;
+        if (f & HS_FLAG_MERGE_ROWS) {
+            hs_set_error("hs_join_group_stage_run: more partial rows than the on-chip final merge holds (the HBM tier belongs to the per-operator ABI)");
+            return HS_E_LIMIT;
+        }
+        if (f & (HS_FLAG_DICT_FULL | HS_FLAG_MERGE_FULL)) {  // as hs_stage_run's shared-dictionary tier
+            const bool unit_full = f & HS_FLAG_DICT_FULL, merge_full = f & HS_FLAG_MERGE_FULL;
+            if ((unit_full && s->group_cap >= 4096) || (merge_full && s->merge_cap >= 4096)) {
+                hs_set_error("hs_join_group_stage_run: GROUP BY cardinality exceeds the on-chip tiers of this path");
+                return HS_E_LIMIT;
+            }
+            if (unit_full) s->group_cap *= 4;
+            if (merge_full) s->merge_cap *= 4;
+            if (s->merge_cap < s->group_cap) s->merge_cap = s->group_cap;
+            if (s->merge_cap > 4096) s->merge_cap = 4096;
+            s->ready = false;
+            ++s->grows;
+            continue;
+        }
+        s->last_flags = join_flags | f;
+        if (flags_out) *flags_out = s->last_flags;
+        if (n_rows_out) *n_rows_out = s->last_rows;
+        return HS_OK;
+    }
+    if (n_pairs > 0) {
+        hs_set_error("hs_join_group_stage_run: capacities did not settle");
+        return HS_E_LIMIT;
+    }
+    if (flags_out) *flags_out = s->last_flags;
+    if (n_rows_out) *n_rows_out = 0;
+    return HS_OK;
+}
+
+extern "C" int hs_join_group_stage_stats(const hs_join_group_stage* s, int64_t* stats) {
+    if (!s || !stats) {
+        hs_set_error("hs_join_group_stage_stats: bad arguments");
+        return HS_E_ARG;
+    }
+    stats[0] = s->runs;
+    stats[1] = s->grows;
+    stats[2] = s->group_cap;
+    stats[3] = s->merge_cap;
+    stats[4] = s->R.J.route;
+    stats[5] = s->agg_route;
+    stats[6] = s->R.J.n_out;
+    stats[7] = s->R.nb;
+    stats[8] = s->R.np;
+    stats[9] = (int64_t)s->dict.size();
+    return HS_OK;
+}
+
+// The result as a one-block BlockFile; a coded key is decoded through the stage's dictionary (as hs_join_result_write_blockfile)
+extern "C" int hs_join_group_result_write_blockfile(const hs_join_group_stage* s, const char* path) {
+    if (!s || !path || (s->last_rows > 0 && (!s->ready || !s->image_host))) {
+        hs_set_error("hs_join_group_result_write_blockfile: bad arguments");
+        return HS_E_ARG;
+    }
+    return write_image_blockfile("hs_join_group_result_write_blockfile", path, s->fin, s->plan.out_types, s->plan.out_names,
+                                 s->image_host, s->last_rows, s->key_kind, s->key_bytes, s->key_coded ? &s->dict : nullptr);
 }

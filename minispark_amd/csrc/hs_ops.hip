@@ -38,6 +38,7 @@ extern "C" size_t hs_sizeof(int32_t which) {
         case 11: return sizeof(hs_join_stage_plan);
         case 12: return sizeof(hs_select_stage_plan);
         case 14: return sizeof(hs_join_select_stage_plan);
+        case 15: return sizeof(hs_join_group_stage_plan);
         default: return 0;
     }
 }

@@ -240,6 +240,38 @@ class hs_join_select_stage_plan(C.Structure):
     ]
 
 
+HS_JOIN_GROUP_STAGE_PLAN_VERSION = 1
+JOIN_AGG_ROUTES = {1: "pairs", 2: "gathered"}  # HS_JOIN_AGG_*
+PAIR = 0x100  # HS_PAIR: OR-ed onto HS_I32 / HS_F32 / HS_I64, the column read through its pair rows (hs_col.offs)
+
+
+class hs_join_group_stage_plan(C.Structure):
+    _fields_ = [
+        ("version", C.c_int32),
+        ("build_key_col", C.c_int32),
+        ("probe_key_col", C.c_int32),
+        ("n_parts", C.c_int32),
+        ("n_bcols", C.c_int32),
+        ("bcol_ids", C.c_int32 * HS_MAX_COLS),
+        ("build_filter", hs_program),
+        ("n_pcols", C.c_int32),
+        ("pcol_ids", C.c_int32 * HS_MAX_COLS),
+        ("probe_filter", hs_program),
+        ("n_cols", C.c_int32),
+        ("col_side", C.c_int32 * HS_MAX_COLS),
+        ("col_ids", C.c_int32 * HS_MAX_COLS),
+        ("key_slot", C.c_int32),
+        ("group_cap", C.c_int32),
+        ("merge_cap", C.c_int32),
+        ("prog", hs_program),
+        ("spec", hs_agg_spec),
+        ("fin", hs_finish_spec),
+        ("fin_prog", hs_program),
+        ("out_types", C.c_int32 * HS_FINISH_MAX_OUT),
+        ("out_names", (C.c_char * 64) * HS_FINISH_MAX_OUT),
+    ]
+
+
 class hs_trace_slice(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("start_us", C.c_double), ("dur_us", C.c_double)]
 
@@ -391,6 +423,11 @@ SIGNATURES: dict[str, tuple] = {
     "hs_join_select_stage_stats": (C.c_int, [_P, C.POINTER(_I64)]),
     "hs_join_select_result_write_blockfile": (C.c_int, [_P, C.c_char_p, _I64]),
     "hs_join_select_stage_destroy": (None, [_P]),
+    "hs_join_group_stage_prepare": (C.c_int, [_P, _P, _P, C.POINTER(hs_join_group_stage_plan), C.c_size_t, C.POINTER(_P)]),
+    "hs_join_group_stage_run": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(_I64)]),
+    "hs_join_group_stage_stats": (C.c_int, [_P, C.POINTER(_I64)]),
+    "hs_join_group_result_write_blockfile": (C.c_int, [_P, C.c_char_p]),
+    "hs_join_group_stage_destroy": (None, [_P]),
     "hs_join_stage_prepare": (C.c_int, [_P, _P, _P, C.POINTER(hs_join_stage_plan), C.c_size_t, C.POINTER(_P)]),
     "hs_join_stage_run": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(_I64)]),
     "hs_join_stage_stats": (C.c_int, [_P, C.POINTER(_I64)]),

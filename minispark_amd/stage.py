@@ -7,7 +7,8 @@ behind the ABI.  The query shape it covers is the hot path's: ``table -> [filter
 reference's two stages [Load -> Filter* -> Aggregate(before) -> shuffle] + [shuffle -> Aggregate(after) -> (Project) ->
 result] (plan.py:182-204); round 3: a SELECT in front of the GROUP BY (its columns inlined, a computed INTEGER key
 materialised by the library), and any number of groups per block the on-chip tiers hold; round 5: a join whose rows go to
-the result file (lower_join_select_stage_plan / NativeJoinSelectStage).
+the result file (lower_join_select_stage_plan / NativeJoinSelectStage) and any join feeding a GROUP BY
+(lower_join_group_stage_plan / NativeJoinGroupStage).
 """
 
 from __future__ import annotations
@@ -454,6 +455,21 @@ def lower_join_select_stage_plan(full_task: Any, plan: Any = None,
     blob.build_key_col = scope_per_side[0][lname][1]
     blob.probe_key_col = scope_per_side[1][rname][1]
     blob.n_parts = n_parts if n_parts is not None else constants.SHUFFLE_PARTITIONS
+    _lower_side_filters(blob, tables, filters)
+    blob.n_out = len(order)
+    for o, ((name, ctype), (side, col)) in enumerate(zip(out_schema, order)):
+        if tables[side][1][col][1] != ctype:
+            raise StageUnsupported("a result column changes its type")
+        blob.out_side[o], blob.out_col[o] = side, col
+        blob.out_types[o] = _TYPE_CODE[ctype]
+        blob.out_names[o].value = name.encode()[:63]
+    return blob, Path(tables[0][0].file_path), Path(tables[1][0].file_path), out_schema
+
+
+def _lower_side_filters(blob: Any, tables: list, filters: tuple) -> None:
+    """The pushed-down WHERE of either side -> its filter program and column slots in a join plan blob."""
+    from .lowering import ProgramBuilder  # noqa: PLC0415
+
     for side, (n_field, ids_field, prog_field) in enumerate((("n_bcols", "bcol_ids", "build_filter"), ("n_pcols", "pcol_ids", "probe_filter"))):
         if not filters[side]:
             continue
@@ -473,24 +489,20 @@ def lower_join_select_stage_plan(full_task: Any, plan: Any = None,
         for slot, idx in enumerate(prog.columns):
             ids[slot] = idx
         setattr(blob, prog_field, prog.to_struct())
-    blob.n_out = len(order)
-    for o, ((name, ctype), (side, col)) in enumerate(zip(out_schema, order)):
-        if tables[side][1][col][1] != ctype:
-            raise StageUnsupported("a result column changes its type")
-        blob.out_side[o], blob.out_col[o] = side, col
-        blob.out_types[o] = _TYPE_CODE[ctype]
-        blob.out_names[o].value = name.encode()[:63]
-    return blob, Path(tables[0][0].file_path), Path(tables[1][0].file_path), out_schema
 
 
-def _push_filter(condition: Any, scope: dict, filters: tuple, table_names: list) -> None:
-    """Every conjunct of a WHERE -> over the table columns of the one side it reads -> that side's filters."""
+def _push_filter(condition: Any, scope: dict, filters: tuple, table_names: list, cross: list | None = None) -> None:
+    """Every conjunct of a WHERE -> over the table columns of the one side it reads -> that side's filters.  A conjunct
+    over both sides goes to ``cross`` as it is (over the names in scope) when given, else it is refused."""
     for conj in _conjuncts(condition):
         names = _walk_names(conj)
         missing = [n for n in names if n not in scope]
         if missing:
             raise ValueError(f'Column "{missing[0]}" not found in schema {list(scope)}')
         sides = {scope[n][0] for n in names}
+        if len(sides) > 1 and cross is not None:
+            cross.append(conj)
+            continue
         if len(sides) > 1:
             raise StageUnsupported("a WHERE conjunct over both sides of the join")
         side = sides.pop() if sides else 1
@@ -514,6 +526,110 @@ def _pass_through(task: Any, scope: dict, filters: tuple, table_names: list) -> 
     if len(new) != len(task.columns):
         raise StageUnsupported("a projection that repeats a column name before the join")
     return new
+
+
+GROUP_KEY = "__hs_group_key"
+
+
+def lower_join_group_stage_plan(full_task: Any, plan: Any = None,
+                                n_parts: int | None = None) -> tuple[hs.hs_join_group_stage_plan, Path, Path, Schema]:
+    """[scan, scan, join -> partial aggregate, final] for any join (keys INTEGER or STRING, duplicates on both sides, columns of
+    either side) -> (plan blob of the native JOIN-to-GROUP-BY stage, build table path, probe table path, result schema).
+    Projections may only pass columns through or rename them; a WHERE conjunct over one side is pushed to that side's scan,
+    one over both sides is the aggregate program's filter.  After the final aggregate at most a projection."""
+    from . import constants  # noqa: PLC0415
+
+    if plan is None:
+        from .plan import PhysicalPlan  # noqa: PLC0415
+
+        plan = PhysicalPlan.generate_physical_plan(full_task)
+    stages = list(plan.stages)
+    join = next((st for st in stages if _cls(st.producer) == "BroadcastHashJoinTask"), None)
+    final = next((st for st in stages if _cls(st.producer) == "LoadShuffleFilesTask" and _cls(st.writer) == "WriteToLocalFileTask"), None)
+    if join is None or final is None or len(stages) != 4 or len(join.dependencies) != 2:
+        raise StageUnsupported("not a [scan, scan, join -> partial aggregate, final] plan")
+    tables, scope_per_side, filters, cross = [], [], ([], []), []
+    for dep in join.dependencies:
+        if _cls(dep.producer) != "LoadTableBlockTask":
+            raise StageUnsupported("a join input is not a table scan")
+        tables.append((dep.producer, list(dep.producer.inferred_schema)))
+    table_names = [[n for n, _ in schema] for _, schema in tables]
+    for side, dep in enumerate(join.dependencies):
+        scope = {n: (side, i) for i, n in enumerate(table_names[side])}
+        for task in dep.consumers:
+            scope = _pass_through(task, scope, filters, table_names)
+        scope_per_side.append(scope)
+    task = join.producer
+    lname, rname = task.left_key.name, task.right_key.name
+    if lname not in scope_per_side[0] or rname not in scope_per_side[1]:
+        raise StageUnsupported("join keys are not plain columns of the two inputs")
+    scope = dict(scope_per_side[1])
+    scope.update(scope_per_side[0])  # a name on both sides reads the build side's, as the engine's column lookup does
+    partial = None
+    for t in join.consumers:
+        if _cls(t) == "FilterTask" and partial is None:
+            _push_filter(t.condition, scope, filters, table_names, cross)
+        elif _cls(t) == "ProjectTask" and partial is None:
+            new = {}
+            for (n, _), c in zip(t.inferred_schema, t.columns):
+                bare = _bare(c)
+                if _cls(bare) not in ("Col", "SchemaCol") or bare.name == "*" or bare.name not in scope:
+                    raise StageUnsupported("a computed column before the aggregate")
+                new.setdefault(n, scope[bare.name])
+            scope = new
+        elif _cls(t) == "AggregateTask" and t.before_shuffle and partial is None:
+            partial = t
+        else:
+            raise StageUnsupported(f"{_cls(t)} in the join stage")
+    consumers = list(final.consumers)
+    if partial is None or not consumers or _cls(consumers[0]) != "AggregateTask" or consumers[0].before_shuffle:
+        raise StageUnsupported("no partial / final aggregate pair")
+    if any(_cls(t) != "ProjectTask" for t in consumers[1:]):
+        raise StageUnsupported("more than a projection after the final aggregate (HAVING)")
+    merge, project = consumers[0], None
+    for t in consumers[1:]:  # projections in a row are one projection: each one's names inlined into the next
+        defs = {n: _bare(c) for (n, _), c in zip(prev.inferred_schema, project)} if project is not None else None
+        project, prev = [_substitute(c, defs) if defs is not None else c for c in t.columns], t
+    out_schema = list(final.writer.inferred_schema)
+    ltype = tables[0][1][scope_per_side[0][lname][1]][1]
+    rtype = tables[1][1][scope_per_side[1][rname][1]][1]
+    if ltype != rtype or ltype not in (ColumnType.INTEGER, ColumnType.STRING):
+        raise StageUnsupported(f"join keys of kinds {ltype} / {rtype}: both INTEGER or both STRING")
+    key = _bare(partial.group_by_column)
+    if _cls(key) not in ("Col", "SchemaCol") or key.name not in scope:
+        raise StageUnsupported("a computed GROUP BY key after the join")
+    # the aggregate's view: every name in scope, and the GROUP BY column once more under a name of its own - its slot may
+    # hold dictionary codes, which no predicate or argument may read
+    where = [*scope.items(), (GROUP_KEY, scope[key.name])]
+    schema = [(n, tables[side][1][col][1]) for n, (side, col) in where]
+    kinds = [_FILE_KIND[t] for _, t in schema]
+    low = lower_aggregate(schema, kinds, cross, Col(GROUP_KEY), partial.agg_columns)
+    if len(low.program.columns) > hs.HS_FUSED_COLS:
+        raise StageUnsupported(f"more than {hs.HS_FUSED_COLS} column slots")
+    acc_kinds = [hs.I32 if is_int else hs.F32 for is_int in low.acc_is_int]
+    key_idx = low.program.columns[low.key_slot]
+    fin, fin_prog, _ = lower_finish(low.agg_to_acc, acc_kinds, kinds[key_idx], merge.agg_columns, merge.inferred_schema,
+                                    project, out_schema)
+    blob = hs.hs_join_group_stage_plan()
+    blob.version = hs.HS_JOIN_GROUP_STAGE_PLAN_VERSION
+    blob.build_key_col = scope_per_side[0][lname][1]
+    blob.probe_key_col = scope_per_side[1][rname][1]
+    blob.n_parts = n_parts if n_parts is not None else constants.SHUFFLE_PARTITIONS
+    _lower_side_filters(blob, tables, filters)
+    blob.n_cols = len(low.program.columns)
+    for slot, idx in enumerate(low.program.columns):
+        blob.col_side[slot], blob.col_ids[slot] = where[idx][1]
+    blob.key_slot = low.key_slot
+    blob.group_cap, blob.merge_cap = 16, 64
+    blob.prog = low.program.to_struct()
+    blob.spec = low.spec()
+    blob.fin = fin
+    if fin_prog is not None:
+        blob.fin_prog = fin_prog
+    for o, (name, ctype) in enumerate(out_schema):
+        blob.out_types[o] = _TYPE_CODE[ctype]
+        blob.out_names[o].value = name.split(".", 1)[-1].encode()[:63] if "." in name else name.encode()[:63]
+    return blob, Path(tables[0][0].file_path), Path(tables[1][0].file_path), out_schema
 
 
 class NativeSelectStage:
@@ -621,6 +737,43 @@ class NativeJoinStage:
     def close(self) -> None:
         if self.handle:
             self.lib.hs_join_stage_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+class NativeJoinGroupStage:
+    """A prepared join feeding a GROUP BY (any join keys and columns) behind the C ABI: ``run(path)`` -> rows (through the
+    result BlockFile the library writes)."""
+
+    def __init__(self, engine: "NativeEngine", full_task: Any, plan: Any = None, n_parts: int | None = None) -> None:
+        self.engine, self.lib = engine, engine.lib
+        self.blob, self.build_path, self.probe_path, self.schema = lower_join_group_stage_plan(full_task, plan, n_parts)
+        self.handle = C.c_void_p()
+        hs.check(self.lib.hs_join_group_stage_prepare(engine.handle, engine.table(self.build_path), engine.table(self.probe_path),
+                                                      C.byref(self.blob), C.sizeof(self.blob), C.byref(self.handle)),
+                 "hs_join_group_stage_prepare")
+
+    def run(self, out_path: Path | str, stream: int | None = None) -> list[Row]:
+        flags, nrows = C.c_uint32(0), C.c_int64(0)
+        hs.check(self.lib.hs_join_group_stage_run(self.handle, stream, C.byref(flags), C.byref(nrows)), "hs_join_group_stage_run")
+        raise_for_flags(flags.value)
+        if nrows.value == 0:
+            return []
+        Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+        hs.check(self.lib.hs_join_group_result_write_blockfile(self.handle, str(out_path).encode()),
+                 "hs_join_group_result_write_blockfile")
+        return read_result_file(out_path)
+
+    def stats(self) -> dict:
+        s = (C.c_int64 * 10)()
+        hs.check(self.lib.hs_join_group_stage_stats(self.handle, s), "hs_join_group_stage_stats")
+        v = [int(x) for x in s]
+        return {"runs": v[0], "grows": v[1], "group_cap": v[2], "merge_cap": v[3], "route": hs.JOIN_ROUTES.get(v[4], v[4]),
+                "aggregate": hs.JOIN_AGG_ROUTES.get(v[5], v[5]), "pairs": v[6], "build_rows": v[7], "probe_rows": v[8],
+                "dictionary": v[9]}
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.hs_join_group_stage_destroy(self.handle)
             self.handle = C.c_void_p()
 
 
