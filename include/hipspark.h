@@ -415,6 +415,31 @@ int hs_group_radix_run(void* stream, const hs_radix_plan* plan, const hs_col* ke
                        const int64_t* unit_bounds, const hs_col* val_cols, const uint64_t* const_cells,
                        const hs_agg_spec* spec, void* ws, int64_t* out_unit_groups, uint32_t* flags);
 int hs_group_radix_emit(void* stream, const hs_radix_plan* plan, void* ws, void* out_key, void* const* out_acc);
+/* ---- the row-forming pass in front of the radix tier (csrc/hs_rows.hip; reference FilterTask.execute tasks.py:167-177 and the
+ * argument evaluation of fill_aggregators tasks.py:295-310) ----
+ * From table columns plus ONE stage program `[filter ... FILTER]* KEY [argument ... AGG acc]*` to what hs_group_radix_run
+ * reads: position p of the output is the p-th row, in ascending row order, that passes every filter.  One sweep over the
+ * table, two with a WHERE (a count sweep over the filters' columns, an exclusive scan, the write sweep); ranks come from
+ * ballots and per-wave counts, never from an atomic: the output is the same on every run.
+ *   hs_agg_rows_classify  host only, from the program alone: val_kinds[a] = -1 the argument is a literal (COUNT's 1; its cell
+ *                         goes to const_cells[a], nothing travels), HS_I32 / HS_F32 / HS_I64 a bare stored column
+ *                         (val_slots[a] = its slot; it travels in its stored width), else HS_F64 / HS_I64: the expression's
+ *                         cell as the interpreter computes it.  *n_filters: FILTER instructions of the program.
+ *   hs_agg_rows           unit_rows: DEVICE, [n_units + 1] row boundaries ([0] = 0, [n_units] = n_rows).  out_key (may be
+ *                         NULL): the surviving rows' keys in the key column's stored kind; out_vals[a] (NULL: not written)
+ *                         in kind out_val_kinds[a] - what hs_agg_rows_classify says or the cell kind, which is always
+ *                         correct; every output holds n_rows elements.  out_bounds (device, [n_units + 1]): survivors in
+ *                         front of unit u, [n_units] = all.  Without a FILTER position = row (one sweep, out_bounds =
+ *                         unit_rows: a caller may then hand the table's own key and stored columns to the radix run and pass
+ *                         NULL for them here).  Expression errors are raised in *flags for surviving rows only.  Numeric
+ *                         columns and the key lie in slots 0 .. HS_FUSED_COLS - 1; pair-indexed columns: HS_E_LIMIT.
+ *                         ws: hs_agg_rows_ws_bytes(n_rows, n_units) bytes, 16-byte aligned. */
+int hs_agg_rows_classify(const hs_col* cols, int32_t n_cols, int32_t key_slot, const hs_program* prog, const hs_agg_spec* spec,
+                         int32_t* val_kinds, int32_t* val_slots, uint64_t* const_cells, int32_t* n_filters);
+size_t hs_agg_rows_ws_bytes(int64_t n_rows, int32_t n_units);
+int hs_agg_rows(void* stream, const hs_col* cols, int32_t n_cols, int32_t key_slot, const hs_program* prog,
+                const hs_agg_spec* spec, const int64_t* unit_rows, int32_t n_units, int64_t n_rows, void* out_key,
+                void* const* out_vals, const int32_t* out_val_kinds, int64_t* out_bounds, void* ws, uint32_t* flags);
 /* ---- the general inner join on INTEGER keys over a dense key range (round 4; csrc/hs_radix.hip) -------------------------
  * Reference: BroadcastHashJoinTask.generate_chunks tasks.py:201-240 (zig twin tasks.zig:70-194; duplicate keys multiply,
  * tasks.zig:258-326).  Replaces hs_join_build / hs_join_count / hs_join_fill when both key columns are INTEGER and the
@@ -863,6 +888,19 @@ int hs_stage_wait(hs_stage* stage, void* stream, uint32_t* flags_out, int64_t* n
 int hs_stage_grow(hs_stage* stage);
 /* stats[6]: runs, replayed runs, capacity growths, group_cap, merge_cap, scan chunks */
 int hs_stage_stats(const hs_stage* stage, int64_t* stats);
+/* The HBM (radix) aggregation tier behind hs_stage_run, off by default (a stage without it answers HS_E_LIMIT beyond the
+ * on-chip tiers, as before).  With it on, a GROUP BY whose cardinality leaves the on-chip tiers (per-unit dictionary or
+ * final merge at 4096 groups, more partial rows than the on-chip merge holds) moves the stage to the HBM tier instead: the
+ * row-forming pass (hs_agg_rows), hs_group_radix_plan / run / emit over the file blocks (quantising: the shuffle-file
+ * rows), the same three calls over the partial rows as one unit, projection and rounding as on the shared tier, result
+ * columns sized from the real group count.  The move is sticky - later runs start there - and frees a recorded capture;
+ * HBM-tier runs are neither captured nor replayed (their output sizes depend on the data).  A shape the radix tier does
+ * not move, or a partition that outgrows its dictionary: HS_E_LIMIT, the error text says "radix".  A result beyond
+ * 2 Mi rows is written in blocks of that many rows.  HS_E_ARG on a null stage or a stage of world != 1. */
+int hs_stage_set_hbm_tier(hs_stage* stage, int32_t on);
+/* out[4]: tier of the last run (0 per-lane tables, 1 shared dictionary, 2 HBM), partial rows and result rows of the last
+ * HBM-tier run, tier switches so far */
+int hs_stage_tier_stats(const hs_stage* stage, int64_t* out);
 int hs_result_columns(const hs_stage* stage, hs_result_col* out, int32_t cap, int32_t* n);
 int hs_result_write_blockfile(const hs_stage* stage, const char* path);
 
@@ -1013,6 +1051,10 @@ int hs_join_group_stage_run(hs_join_group_stage* stage, void* stream, uint32_t* 
 /* stats[10]: runs, capacity growths, group_cap, merge_cap, join route (HS_JOIN_ROUTE_*), aggregate route (HS_JOIN_AGG_*),
  * pairs, build rows and probe rows after the WHERE, dictionary entries of a coded GROUP BY key (0: stored key) */
 int hs_join_group_stage_stats(const hs_join_group_stage* stage, int64_t* stats);
+/* The same switch and report for the join feeding a GROUP BY (see hs_stage_set_hbm_tier): the units are the JoinJobs' pair
+ * ranges, the columns are gathered through the pair rows.  tier_stats: 1 = shared dictionary, 2 = HBM. */
+int hs_join_group_stage_set_hbm_tier(hs_join_group_stage* stage, int32_t on);
+int hs_join_group_stage_tier_stats(const hs_join_group_stage* stage, int64_t* out);
 int hs_join_group_result_write_blockfile(const hs_join_group_stage* stage, const char* path);
 void hs_join_group_stage_destroy(hs_join_group_stage* stage);
 

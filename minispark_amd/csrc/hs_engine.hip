@@ -769,6 +769,259 @@ int shared_tail(hipStream_t stream, SharedBufs& B, const hs_agg_spec& spec, cons
     return HS_OK;
 }
 
+
+// ---- the HBM (radix) tier's tail, shared by the scan stage and the join feeding a GROUP BY ------------------------------------
+// What device.py's aggregate_partial_global / aggregate_merge_global issue per operator, behind the stage boundary: row-forming
+// pass -> radix partial aggregate over the units (quantised: the shuffle-file rows, in unit order) -> radix merge of the
+// partial rows as one unit -> projection -> rounding -> result image sized from the real group count, one copy to the host.
+constexpr int64_t kResultBlockRows = 2 * 1024 * 1024;  // ROWS_PER_BLOCK of a result file (constants.py)
+
+struct HbmBufs {
+    DevBuf units, rows_ws, key, vals[HS_MAX_ACC], bounds, ws, status, pkey, pacc[HS_MAX_ACC], one_unit, mkey, macc, prog_out, image;
+    int64_t partial_rows = 0, result_rows = 0;
+};
+
+bool hbm_grow(DevBuf& b, size_t bytes) { return b.bytes >= bytes && b.p ? true : b.alloc(bytes > 0 ? bytes : 16); }
+
+// group counts [n_units + 1] and the radix run's status word behind them, in ONE read-back.  HS_FLAG_DICT_FULL -> HS_E_LIMIT.
+int hbm_radix(hipStream_t stream, HbmBufs& H, const char* who, int32_t key_code, const hs_col& key, int64_t n, int32_t n_units,
+              int64_t max_unit_rows, const int64_t* bounds_dev, const hs_col* vcols, const int32_t* vkinds, const uint64_t* cells,
+              const hs_agg_spec& spec, int quantise, hs_radix_plan& plan, std::vector<int64_t>& groups, uint32_t& extra_flags) {
+    int rc = hs_group_radix_plan(key_code, n, n_units, max_unit_rows > 0 ? max_unit_rows : 1, vkinds, &spec, quantise, &plan);
+    if (rc == HS_E_LIMIT) {
+        std::string why = hs_last_error();
+        hs_set_error("%s: the radix tier does not move this key / aggregate shape (%s)", who, why.c_str());
+    }
+    if (rc) return rc;
+    if (!hbm_grow(H.ws, hs_group_radix_ws_bytes(&plan)) || !hbm_grow(H.status, (size_t)(n_units + 2) * 8)) {
+        hs_set_error("%s: out of device memory for the radix tier (%zu bytes of workspace)", who, hs_group_radix_ws_bytes(&plan));
+        return HS_E_LAUNCH;
+    }
+    if (hipMemsetAsync(H.status.p, 0, (size_t)(n_units + 2) * 8, stream) != hipSuccess) return HS_E_LAUNCH;
+    int64_t* unit_groups = (int64_t*)H.status.p;
+    rc = hs_group_radix_run(stream, &plan, &key, nullptr, 0, bounds_dev, vcols, cells, &spec, H.ws.p, unit_groups,
+                            (uint32_t*)(unit_groups + n_units + 1));
+    if (rc == HS_E_LIMIT) {
+        std::string why = hs_last_error();
+        hs_set_error("%s: the radix tier does not move this key / aggregate shape (%s)", who, why.c_str());
+    }
+    if (rc) return rc;
+    groups.assign((size_t)n_units + 2, 0);
+    if (hipMemcpyAsync(groups.data(), H.status.p, (size_t)(n_units + 2) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) {
+        hs_set_error("%s: the radix run failed (%s)", who, hipGetErrorString(hipGetLastError()));
+        return HS_E_LAUNCH;
+    }
+    const uint32_t f = (uint32_t)groups[(size_t)n_units + 1];
+    if (f & HS_FLAG_DICT_FULL) {
+        hs_set_error("%s: a radix partition outgrew its dictionary (the hash-table tier belongs to the per-operator ABI)", who);
+        return HS_E_LIMIT;
+    }
+    extra_flags |= f;
+    return HS_OK;
+}
+
+// fin: the stage's copy of the plan's finish description (its offsets are rewritten for this run's group count);
+// image_host / image_cap: the pinned result buffer the stage owns, re-grown as needed.
+int hbm_tail(hipStream_t stream, HbmBufs& H, const char* who, const hs_col* cols, int32_t n_cols, int32_t key_slot, const hs_program& prog,
+             const hs_agg_spec& spec, const std::vector<int64_t>& unit_rows, int64_t n_rows, hs_finish_spec& fin, const hs_program& fin_prog,
+             int key_bytes, void*& image_host, size_t& image_cap, uint32_t* flags, uint32_t* flags_out, int64_t* rows_out) {
+    const int32_t n_units = (int32_t)unit_rows.size() - 1;
+    const int n_acc = spec.n_acc, nf = fin.n_fold;
+    H.partial_rows = H.result_rows = 0;
+    *rows_out = 0;
+    uint32_t extra = 0;
+    auto finish_empty = [&]() -> int {  // no rows: only the flags travel
+        uint32_t f = 0;
+        // (the engine's status word goes back to zero: the per-lane tier of another stage on this engine ORs into it as found)
+        if (hipMemcpyAsync(&f, flags, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemsetAsync(flags, 0, 4, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess)
+            return HS_E_LAUNCH;
+        *flags_out = f | extra;
+        return HS_OK;
+    };
+    int32_t vk[HS_MAX_ACC] = {}, vslot[HS_MAX_ACC] = {}, n_filters = 0;
+    uint64_t cells[HS_MAX_ACC] = {};
+    // a program or column shape the row-forming pass refuses (a stage can get here from a shape refusal of the shared tier,
+    // not only from cardinality) is a refusal of this tier: HS_E_LIMIT, and the text names it
+    auto refused = [&](int rc_) -> int {
+        if (rc_ == HS_E_ARG || rc_ == HS_E_LIMIT) {
+            const std::string why = hs_last_error();
+            hs_set_error("%s: the radix tier's row-forming pass does not take this program (%s)", who, why.c_str());
+            return HS_E_LIMIT;
+        }
+        return rc_;
+    };
+    int rc = hs_agg_rows_classify(cols, n_cols, key_slot, &prog, &spec, vk, vslot, cells, &n_filters);
+    if (rc) return refused(rc);
+    if (n_units < 1 || n_rows == 0) return finish_empty();
+    const hs_col& kc = cols[key_slot];
+    const int32_t key_code = kc.kind == HS_STR ? HS_STR + 256 * kc.fixed_len : kc.kind;
+    // 1. the row-forming pass: without a WHERE only the computed arguments are written (the table's own columns travel)
+    bool ok = hbm_grow(H.units, (size_t)(n_units + 1) * 8) && hbm_grow(H.bounds, (size_t)(n_units + 1) * 8);
+    ok = ok && hipMemcpyAsync(H.units.p, unit_rows.data(), (size_t)(n_units + 1) * 8, hipMemcpyHostToDevice, stream) == hipSuccess;
+    void* out_vals[HS_MAX_ACC] = {};
+    bool any_cell = false;
+    for (int a = 0; a < n_acc && ok; ++a) {
+        const bool stored = vk[a] >= 0 && vslot[a] >= 0;
+        if (vk[a] < 0 || (stored && !n_filters)) continue;
+        ok = hbm_grow(H.vals[a], (size_t)n_rows * (size_t)elem_bytes(vk[a]));
+        out_vals[a] = H.vals[a].p;
+        any_cell = any_cell || !stored;
+    }
+    if (n_filters) ok = ok && hbm_grow(H.key, (size_t)n_rows * (size_t)key_bytes);
+    if (!ok) {
+        hs_set_error("%s: out of device memory for the row-forming pass", who);
+        return HS_E_LAUNCH;
+    }
+    std::vector<int64_t> pos(unit_rows);  // unit boundaries as positions
+    if (n_filters || any_cell) {
+        if (!hbm_grow(H.rows_ws, hs_agg_rows_ws_bytes(n_rows, n_units))) return HS_E_LAUNCH;
+        rc = hs_agg_rows(stream, cols, n_cols, key_slot, &prog, &spec, (const int64_t*)H.units.p, n_units, n_rows, n_filters ? H.key.p : nullptr,
+                         out_vals, vk, (int64_t*)H.bounds.p, H.rows_ws.p, flags);
+        if (rc) return refused(rc);
+    }
+    if (n_filters) {
+        if (hipMemcpyAsync(pos.data(), H.bounds.p, (size_t)(n_units + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess) {
+            hs_set_error("%s: the row-forming pass failed (%s)", who, hipGetErrorString(hipGetLastError()));
+            return HS_E_LAUNCH;
+        }
+    }
+    const int64_t n = pos[(size_t)n_units];
+    if (n == 0) return finish_empty();
+    int64_t biggest = 1;
+    for (int32_t u = 0; u < n_units; ++u) biggest = std::max(biggest, pos[(size_t)u + 1] - pos[(size_t)u]);
+    // 2. partial aggregate per unit, rounded to what a shuffle file holds
+    const hs_col key = n_filters ? hs_col{kc.kind, kc.kind == HS_STR ? kc.fixed_len : -1, H.key.p, nullptr, nullptr} : kc;
+    hs_col vcols[HS_MAX_ACC];
+    for (int a = 0; a < n_acc; ++a) {
+        if (vk[a] < 0) vcols[a] = hs_col{HS_U8, -1, nullptr, nullptr, nullptr};
+        else if (out_vals[a]) vcols[a] = hs_col{vk[a], -1, out_vals[a], nullptr, nullptr};
+        else vcols[a] = cols[vslot[a]];
+    }
+    hs_radix_plan plan;
+    std::vector<int64_t> groups;
+    rc = hbm_radix(stream, H, who, key_code, key, n, n_units, biggest, n_filters ? (const int64_t*)H.bounds.p : (const int64_t*)H.units.p,
+                   vcols, vk, cells, spec, 1, plan, groups, extra);
+    if (rc) return rc;
+    const int64_t np = groups[(size_t)n_units];
+    H.partial_rows = np;
+    if (np <= 0) return finish_empty();
+    ok = hbm_grow(H.pkey, (size_t)np * (size_t)key_bytes);
+    void* pacc[HS_MAX_ACC] = {};
+    for (int a = 0; a < n_acc && ok; ++a) {
+        ok = hbm_grow(H.pacc[a], (size_t)np * 4);
+        pacc[a] = H.pacc[a].p;
+    }
+    if (!ok) {
+        hs_set_error("%s: out of device memory for %lld partial rows", who, (long long)np);
+        return HS_E_LAUNCH;
+    }
+    rc = hs_group_radix_emit(stream, &plan, H.ws.p, H.pkey.p, pacc);
+    if (rc) return rc;
+    // 3. final merge (tasks.py:290-292): the partial rows, already in merge order on one GPU, as ONE unit
+    hs_agg_spec mspec{};
+    mspec.n_acc = nf;
+    hs_col fold_cols[HS_MAX_ACC];
+    int32_t fold_kinds[HS_MAX_ACC] = {};
+    uint64_t zero_cells[HS_MAX_ACC] = {};
+    for (int j = 0; j < nf; ++j) {
+        const int src = fin.fold_src[j];
+        fold_kinds[j] = spec.is_int[src] ? HS_I32 : HS_F32;
+        fold_cols[j] = hs_col{fold_kinds[j], -1, pacc[src], nullptr, nullptr};
+        mspec.op[j] = (uint8_t)fin.fold_op[j];
+        mspec.is_int[j] = spec.is_int[src];
+    }
+    const int64_t one_unit[2] = {0, np};
+    if (!hbm_grow(H.one_unit, 16) || hipMemcpyAsync(H.one_unit.p, one_unit, 16, hipMemcpyHostToDevice, stream) != hipSuccess) return HS_E_LAUNCH;
+    const hs_col pkey{kc.kind, kc.kind == HS_STR ? kc.fixed_len : -1, H.pkey.p, nullptr, nullptr};
+    hs_radix_plan mplan;
+    rc = hbm_radix(stream, H, who, key_code, pkey, np, 1, np, (const int64_t*)H.one_unit.p, fold_cols, fold_kinds, zero_cells, mspec, 0, mplan,
+                   groups, extra);
+    if (rc) return rc;
+    const int64_t ng = groups[1];
+    if (ng <= 0) return finish_empty();
+    const int64_t cap = ng;
+    ok = hbm_grow(H.mkey, (size_t)ng * (size_t)key_bytes) && hbm_grow(H.macc, (size_t)ng * 8 * (size_t)(nf > 0 ? nf : 1));
+    if (!ok) {
+        hs_set_error("%s: out of device memory for %lld result rows", who, (long long)ng);
+        return HS_E_LAUNCH;
+    }
+    void* macc[HS_MAX_ACC] = {};
+    for (int j = 0; j < nf; ++j) macc[j] = (char*)H.macc.p + (size_t)j * (size_t)cap * 8;
+    rc = hs_group_radix_emit(stream, &mplan, H.ws.p, H.mkey.p, macc);
+    if (rc) return rc;
+    // 4. projection after the merge and rounding to the stored kinds: what shared_tail issues, over the real group count
+    int n_prog_out = 0;
+    for (int o = 0; o < fin.n_out; ++o)
+        if (fin.outs[o].src == 2 && fin.outs[o].index + 1 > n_prog_out) n_prog_out = fin.outs[o].index + 1;
+    int32_t prog_kinds[HS_MAX_OUTS] = {};
+    if (n_prog_out > 0) {
+        if (!hbm_grow(H.prog_out, (size_t)cap * 8 * (size_t)n_prog_out)) return HS_E_LAUNCH;
+        hs_col pcols[HS_MAX_COLS];
+        for (int i = 0; i < HS_MAX_COLS; ++i) {
+            const int j = fin.prog_src[i];
+            if (j >= 0 && j < nf) pcols[i] = hs_col{mspec.is_int[j] ? HS_I64 : HS_F64, -1, macc[j], nullptr, nullptr};
+            else pcols[i] = hs_col{kc.kind == HS_STR ? HS_U8 : kc.kind, -1, H.mkey.p, nullptr, nullptr};
+        }
+        void* outs[HS_MAX_OUTS] = {};
+        for (int o = 0; o < fin.n_out; ++o) {
+            const hs_finish_out& d = fin.outs[o];
+            if (d.src == 2) prog_kinds[d.index] = d.kind == HS_F32 ? HS_F64 : HS_I64;
+        }
+        for (int k = 0; k < n_prog_out; ++k) outs[k] = (char*)H.prog_out.p + (size_t)k * (size_t)cap * 8;
+        rc = hs_eval(stream, pcols, HS_MAX_COLS, &fin_prog, nullptr, cap, nullptr, outs, prog_kinds, n_prog_out, flags);
+        if (rc) return rc;
+    }
+    // 5. result image: header (the flags word), then every column at its offset, ng elements each; ONE copy to the host
+    const int64_t image_bytes = image_layout(fin, key_bytes, (int)cap);
+    if (!hbm_grow(H.image, (size_t)image_bytes)) return HS_E_LAUNCH;
+    if (image_cap < (size_t)image_bytes + kPad || !image_host) {
+        if (image_host) (void)hipHostFree(image_host);
+        image_host = nullptr;
+        image_cap = 0;
+        const size_t want = (size_t)image_bytes + (size_t)image_bytes / 4 + kPad;
+        if (hipHostMalloc(&image_host, want, hipHostMallocDefault) != hipSuccess) {
+            image_host = nullptr;
+            hs_set_error("%s: out of pinned memory for %lld result rows", who, (long long)ng);
+            return HS_E_LAUNCH;
+        }
+        image_cap = want;
+    }
+    for (int o = 0; o < fin.n_out; ++o) {
+        const hs_finish_out& d = fin.outs[o];
+        char* dst = (char*)H.image.p + d.offset;
+        if (d.src == 0) {
+            if (hipMemcpyAsync(dst, H.mkey.p, (size_t)cap * (size_t)key_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) return HS_E_LAUNCH;
+            continue;
+        }
+        const void* src = d.src == 1 ? (const char*)macc[d.index] : (const char*)H.prog_out.p + (size_t)d.index * (size_t)cap * 8;
+        const bool is_int = d.src == 1 ? mspec.is_int[d.index] != 0 : prog_kinds[d.index] == HS_I64;
+        if (d.kind == HS_I64) {
+            if (hipMemcpyAsync(dst, src, (size_t)cap * 8, hipMemcpyDeviceToDevice, stream) != hipSuccess) return HS_E_LAUNCH;
+        } else {
+            rc = hs_quantise(stream, src, is_int ? HS_I64 : HS_F64, cap, nullptr, dst, flags);
+            if (rc) return rc;
+        }
+    }
+    if (hipMemcpyAsync(H.image.p, flags, 4, hipMemcpyDeviceToDevice, stream) != hipSuccess || hipMemsetAsync(flags, 0, 4, stream) != hipSuccess ||
+        hipMemcpyAsync(image_host, H.image.p, (size_t)image_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) {
+        hs_set_error("%s: the HBM tier's tail failed (%s)", who, hipGetErrorString(hipGetLastError()));
+        return HS_E_LAUNCH;
+    }
+    *flags_out = *(const uint32_t*)image_host | extra;
+    *rows_out = ng;
+    H.result_rows = ng;
+    return HS_OK;
+}
+
+// (defined with the join stage below) the result image as a BlockFile of rows_per_block-row blocks; 0 = one block
+int write_image_blockfile(const char* who, const char* path, const hs_finish_spec& fin, const int32_t* out_types,
+                          const char (*out_names)[64], const void* image_host, int64_t last_rows, int key_kind, int key_bytes,
+                          const std::vector<std::string>* dict, int64_t rows_per_block = 0);
+
 }  // namespace
 
 struct hs_stage {
@@ -788,7 +1041,7 @@ struct hs_stage {
     DevBuf chunks, chunk0, unit_ids, slab, ws, scratch;
     // round 3: tens to thousands of groups per block - the shared-dictionary tier + the general operator sequence after it
     // (pack -> key gather -> merge -> key gather / projection -> rounding), all behind hs_stage_run
-    int32_t tier = 0;  // 0: per-lane tables + the one-launch finish; 1: shared dictionary + general tail
+    int32_t tier = 0;  // 0: per-lane tables + the one-launch finish; 1: shared dictionary + general tail; 2: HBM (radix) tier
     DevBuf key_col, key_wide;  // a computed GROUP BY key (plan version 2): the 4-byte column the scan reads + its i64 evaluation
     hs_col kcols[HS_MAX_COLS];
     SharedBufs sh;
@@ -797,6 +1050,13 @@ struct hs_stage {
     void* image_dev = nullptr;
     void* capture = nullptr;     // steady state: the launches of one run
     int64_t runs = 0, replays = 0, grows = 0;
+    // the HBM (radix) tier (tier 2), taken past the on-chip tiers when the stage's switch is on
+    bool hbm_on = false;
+    HbmBufs hbm;
+    size_t image_host_cap = 0;
+    std::vector<int64_t> unit_rows;
+    int32_t last_tier = 0;
+    int64_t tier_switches = 0;
     // last result
     uint32_t last_flags = 0;
     int64_t last_rows = 0;
@@ -1048,6 +1308,55 @@ int shared_run(hs_stage* s, void* stream_) {
 
 }  // namespace
 
+namespace {
+
+// past the on-chip tiers with the switch on: the stage moves to the HBM tier and stays there
+void hbm_enter(hs_stage* s) {
+    if (s->capture) {
+        hs_capture_free(s->capture);
+        s->capture = nullptr;
+    }
+    if (s->image_host) (void)hipHostFree(s->image_host);  // (the on-chip tiers' image; this tier's is sized per run)
+    s->image_host = s->image_dev = nullptr;
+    s->image_host_cap = 0;
+    s->sh = SharedBufs();
+    s->slab.release();
+    s->ws.release();
+    s->scratch.release();
+    s->tier = 2;
+    s->ready = false;
+    ++s->tier_switches;
+}
+
+int hbm_run(hs_stage* s, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    hs_table* t = s->table;
+    const hs_stage_plan& P = s->plan;
+    uint32_t* flags = (uint32_t*)s->engine->flags.p;
+    s->last_rows = 0;
+    s->last_flags = 0;
+    if (!s->ready) {
+        if (const int rc0 = bind_columns(s)) return rc0;
+        const hs_col& kc = s->cols[P.key_slot];
+        s->key_bytes = kc.kind == HS_STR ? kc.fixed_len : elem_bytes(kc.kind);
+        memset(&s->desc, 0, sizeof(s->desc));
+        s->desc.key_kind = kc.kind;
+        s->desc.key_len = kc.kind == HS_STR ? kc.fixed_len : 0;
+        s->n_units = (int64_t)t->block_rows.size();
+        s->unit_rows.assign((size_t)s->n_units + 1, 0);
+        for (int64_t u = 0; u < s->n_units; ++u) s->unit_rows[(size_t)u + 1] = s->unit_rows[(size_t)u] + t->block_rows[(size_t)u];
+        s->ready = true;
+    }
+    s->fin = P.fin;
+    if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
+    int rc = compute_key(s, stream);
+    if (rc) return rc;
+    return hbm_tail(stream, s->hbm, "hs_stage_run", s->cols, P.n_cols, P.key_slot, P.prog, P.spec, s->unit_rows, t->nrows, s->fin,
+                    P.fin_prog, s->key_bytes, s->image_host, s->image_host_cap, flags, &s->last_flags, &s->last_rows);
+}
+
+}  // namespace
+
 extern "C" int hs_stage_prepare(hs_engine* e, hs_table* t, const hs_stage_plan* plan, size_t plan_bytes, int32_t world,
                                 hs_stage** out) {
     if (!e || !t || !plan || !out || plan_bytes != sizeof(hs_stage_plan) || plan->version != HS_STAGE_PLAN_VERSION ||
@@ -1104,19 +1413,42 @@ extern "C" int hs_stage_run(hs_stage* s, void* stream, uint32_t* flags_out, int6
     }
     for (int attempt = 0; attempt < 14; ++attempt) {
         int rc = HS_OK;
+        if (s->tier == 2) {
+            // any number of groups: the row-forming pass + the radix tier (not captured: output sizes depend on the data)
+            rc = hbm_run(s, stream);
+            if (rc) return rc;
+            ++s->runs;
+            s->last_tier = 2;
+            if (flags_out) *flags_out = s->last_flags;
+            if (n_rows_out) *n_rows_out = s->last_rows;
+            return HS_OK;
+        }
         if (s->tier == 1) {
             // tens to thousands of groups per block: shared-dictionary scan + the general operator sequence
             if (!s->ready) rc = shared_prepare(s);
             if (!rc) rc = shared_run(s, stream);
+            if (rc == HS_E_LIMIT && s->hbm_on) {  // more rows than the on-chip merge takes, or a shape this tier does not hold
+                hbm_enter(s);
+                continue;
+            }
             if (rc) return rc;
             ++s->runs;
+            s->last_tier = 1;
             if (s->last_flags & HS_FLAG_MERGE_ROWS) {
+                if (s->hbm_on) {
+                    hbm_enter(s);
+                    continue;
+                }
                 hs_set_error("hs_stage_run: more partial rows than the on-chip final merge holds (the HBM tier belongs to the per-operator ABI)");
                 return HS_E_LIMIT;
             }
             if (s->last_flags & (HS_FLAG_DICT_FULL | HS_FLAG_MERGE_FULL)) {
                 const bool unit_full = s->last_flags & HS_FLAG_DICT_FULL, merge_full = s->last_flags & HS_FLAG_MERGE_FULL;
                 if ((unit_full && s->group_cap >= 4096) || (merge_full && s->merge_cap >= 4096)) {
+                    if (s->hbm_on) {
+                        hbm_enter(s);
+                        continue;
+                    }
                     hs_set_error("hs_stage_run: GROUP BY cardinality exceeds the on-chip tiers of this path");
                     return HS_E_LIMIT;
                 }
@@ -1135,6 +1467,7 @@ extern "C" int hs_stage_run(hs_stage* s, void* stream, uint32_t* flags_out, int6
         if (!s->ready) rc = stage_prepare(s);
         if (rc == HS_E_LIMIT && s->world == 1) {  // the per-lane tables do not hold this query: the shared dictionary may
             s->tier = 1;
+            ++s->tier_switches;
             if (s->group_cap < 16) s->group_cap = 16;
             if (s->merge_cap < 64) s->merge_cap = 64;
             continue;
@@ -1160,10 +1493,15 @@ extern "C" int hs_stage_run(hs_stage* s, void* stream, uint32_t* flags_out, int6
         rc = wait_result(s, stream);
         if (rc) return rc;
         ++s->runs;
+        s->last_tier = 0;
         if (s->last_flags & (HS_FLAG_DICT_FULL | HS_FLAG_MERGE_FULL)) {
             // more groups than a dictionary was sized for: x2 per workgroup (per-lane tables), x4 for the merge - each
             // grows on its own flag; the merge also keeps up with the per-unit capacity (it holds at least as many keys)
             const bool unit_full = s->last_flags & HS_FLAG_DICT_FULL, merge_full = s->last_flags & HS_FLAG_MERGE_FULL;
+            if (merge_full && s->merge_cap >= 4096 && s->hbm_on) {
+                hbm_enter(s);
+                continue;
+            }
             if (merge_full && s->merge_cap >= 4096) {
                 hs_set_error("hs_stage_run: GROUP BY cardinality exceeds the on-chip tiers of this path");
                 return HS_E_LIMIT;
@@ -1175,6 +1513,7 @@ extern "C" int hs_stage_run(hs_stage* s, void* stream, uint32_t* flags_out, int6
                     s->capture = nullptr;
                 }
                 s->tier = 1;
+                ++s->tier_switches;
                 s->group_cap = 64;
                 if (s->merge_cap < 256) s->merge_cap = 256;
                 s->ready = false;
@@ -1200,8 +1539,9 @@ extern "C" int hs_stage_run(hs_stage* s, void* stream, uint32_t* flags_out, int6
 
 // Multi-rank form: launch the rank's scan into its slab, let the caller all-gather the slabs (hs_stage_slab: device
 // pointer + bytes), then launch the finish over the gathered slabs and wait.
+// (a stage that moved to the HBM tier has none of the buffers these entry points launch on: HS_E_ARG)
 extern "C" int hs_stage_launch_partial(hs_stage* s, void* stream) {
-    if (!s) return HS_E_ARG;
+    if (!s || s->tier == 2) return HS_E_ARG;
     if (!s->ready) {
         const int rc = stage_prepare(s);
         if (rc) return rc;
@@ -1209,16 +1549,16 @@ extern "C" int hs_stage_launch_partial(hs_stage* s, void* stream) {
     return launch_partial(s, stream);
 }
 extern "C" void* hs_stage_slab(hs_stage* s, int64_t* bytes) {
-    if (!s || !s->ready) return nullptr;
+    if (!s || !s->ready || s->tier == 2) return nullptr;
     if (bytes) *bytes = s->slab_bytes;
     return s->slab.p;
 }
 extern "C" int hs_stage_launch_finish(hs_stage* s, void* stream, const void* gathered, int32_t world) {
-    if (!s || !s->ready || world < 1) return HS_E_ARG;
+    if (!s || !s->ready || world < 1 || s->tier == 2) return HS_E_ARG;
     return launch_finish(s, stream, gathered, world);
 }
 extern "C" int hs_stage_wait(hs_stage* s, void* stream, uint32_t* flags_out, int64_t* n_rows_out) {
-    if (!s || !s->ready) return HS_E_ARG;
+    if (!s || !s->ready || s->tier == 2) return HS_E_ARG;
     const int rc = wait_result(s, stream);
     if (rc) return rc;
     if (flags_out) *flags_out = s->last_flags;
@@ -1227,7 +1567,7 @@ extern "C" int hs_stage_wait(hs_stage* s, void* stream, uint32_t* flags_out, int
 }
 // After HS_FLAG_DICT_FULL / HS_FLAG_MERGE_FULL in the multi-rank form (every rank sees the same flags): grow and prepare again.
 extern "C" int hs_stage_grow(hs_stage* s) {
-    if (!s) return HS_E_ARG;
+    if (!s || s->tier == 2) return HS_E_ARG;
     const bool unit_full = s->last_flags & HS_FLAG_DICT_FULL, merge_full = s->last_flags & HS_FLAG_MERGE_FULL;
     if ((unit_full && s->group_cap >= 16) || (merge_full && s->merge_cap >= 4096)) return HS_E_LIMIT;
     if (unit_full) s->group_cap *= 2;
@@ -1246,6 +1586,27 @@ extern "C" int hs_stage_stats(const hs_stage* s, int64_t* stats) {
     stats[3] = s->group_cap;
     stats[4] = s->merge_cap;
     stats[5] = s->geom.n_chunks;
+    return HS_OK;
+}
+
+extern "C" int hs_stage_set_hbm_tier(hs_stage* s, int32_t on) {
+    if (!s || s->world != 1) {
+        hs_set_error("hs_stage_set_hbm_tier: null stage, or a stage of several ranks (the HBM tier runs on one GPU)");
+        return HS_E_ARG;
+    }
+    s->hbm_on = on != 0;
+    return HS_OK;
+}
+
+extern "C" int hs_stage_tier_stats(const hs_stage* s, int64_t* out) {
+    if (!s || !out) {
+        hs_set_error("hs_stage_tier_stats: bad arguments");
+        return HS_E_ARG;
+    }
+    out[0] = s->last_tier;
+    out[1] = s->hbm.partial_rows;
+    out[2] = s->hbm.result_rows;
+    out[3] = s->tier_switches;
     return HS_OK;
 }
 
@@ -1273,6 +1634,9 @@ extern "C" int hs_result_write_blockfile(const hs_stage* s, const char* path) {
         hs_set_error("hs_result_write_blockfile: bad arguments");
         return HS_E_ARG;
     }
+    if (s->tier == 2)  // any number of rows: blocks of ROWS_PER_BLOCK rows (io.py:217-252)
+        return write_image_blockfile("hs_result_write_blockfile", path, s->fin, s->plan.out_types, s->plan.out_names, s->image_host,
+                                     s->last_rows, s->desc.key_kind, s->key_bytes, nullptr, kResultBlockRows);
     if (s->last_rows == 0) return HS_OK;  // empty result: the reference writes no file (tasks.py:405)
     FILE* f = fopen(path, "wb");
     if (!f) {
@@ -1702,11 +2066,12 @@ extern "C" int hs_join_stage_stats(const hs_join_stage* s, int64_t* stats) {
 
 namespace {
 
-// The on-chip path's result image as a one-block BlockFile (tasks.py:400-410, io.py:47-109); a key of dictionary codes
-// (dict != NULL) is decoded through the dictionary.  `who` names the entry point in errors.
+// A result image as a BlockFile (tasks.py:400-410, io.py:47-109): one block for the on-chip path (rows_per_block 0), blocks of
+// rows_per_block rows for the HBM tier; a key of dictionary codes (dict != NULL) is decoded through the dictionary.  `who`
+// names the entry point in errors.
 int write_image_blockfile(const char* who, const char* path, const hs_finish_spec& fin, const int32_t* out_types,
                           const char (*out_names)[64], const void* image_host, int64_t last_rows, int key_kind, int key_bytes,
-                          const std::vector<std::string>* dict) {
+                          const std::vector<std::string>* dict, int64_t rows_per_block) {
     if (last_rows == 0) return HS_OK;  // empty result: the reference writes no file (tasks.py:405)
     FILE* f = fopen(path, "wb");
     if (!f) {
@@ -1723,39 +2088,43 @@ int write_image_blockfile(const char* who, const char* path, const hs_finish_spe
         fwrite(&len, 1, 1, f);
         fwrite(out_names[o], 1, len, f);
     }
-    const uint64_t block_start = (uint64_t)ftell(f);
-    const uint32_t rows = (uint32_t)last_rows;
-    fwrite(&rows, 4, 1, f);
+    if (rows_per_block < 1) rows_per_block = last_rows;
+    std::vector<uint64_t> starts;
     bool ok = true;
-    for (int o = 0; o < n_out; ++o) {
-        const hs_finish_out& d = fin.outs[o];
-        const uint8_t* col = (const uint8_t*)image_host + d.offset;
-        if (d.src == 0 && dict) {  // code bytes -> the strings they stand for
-            uint64_t bytes = rows;
-            for (uint32_t r = 0; r < rows; ++r) {
-                if (col[r] >= dict->size()) ok = false;
-                else bytes += (*dict)[col[r]].size();
+    for (int64_t lo = 0; lo < last_rows; lo += rows_per_block) {  // a result larger than a block continues in further blocks
+        const uint32_t rows = (uint32_t)(lo + rows_per_block < last_rows ? rows_per_block : last_rows - lo);
+        starts.push_back((uint64_t)ftell(f));
+        fwrite(&rows, 4, 1, f);
+        for (int o = 0; o < n_out; ++o) {
+            const hs_finish_out& d = fin.outs[o];
+            const int width = d.src == 0 ? key_bytes : (d.kind == HS_I64 ? 8 : 4);
+            const uint8_t* col = (const uint8_t*)image_host + d.offset + (size_t)lo * (size_t)width;
+            if (d.src == 0 && dict) {  // code bytes -> the strings they stand for
+                uint64_t bytes = rows;
+                for (uint32_t r = 0; r < rows; ++r) {
+                    if (col[r] >= dict->size()) ok = false;
+                    else bytes += (*dict)[col[r]].size();
+                }
+                fwrite(&bytes, 8, 1, f);
+                for (uint32_t r = 0; ok && r < rows; ++r) {
+                    const uint8_t len = (uint8_t)(*dict)[col[r]].size();
+                    fwrite(&len, 1, 1, f);
+                }
+                for (uint32_t r = 0; ok && r < rows; ++r) fwrite((*dict)[col[r]].data(), 1, (*dict)[col[r]].size(), f);
+                continue;
             }
+            const bool is_key_string = d.src == 0 && key_kind == HS_STR;
+            const uint64_t bytes = (uint64_t)rows * (uint64_t)width + (is_key_string ? rows : 0);
             fwrite(&bytes, 8, 1, f);
-            for (uint32_t r = 0; ok && r < rows; ++r) {
-                const uint8_t len = (uint8_t)(*dict)[col[r]].size();
-                fwrite(&len, 1, 1, f);
+            if (is_key_string) {
+                const std::vector<uint8_t> lens(rows, (uint8_t)width);
+                fwrite(lens.data(), 1, rows, f);
             }
-            for (uint32_t r = 0; ok && r < rows; ++r) fwrite((*dict)[col[r]].data(), 1, (*dict)[col[r]].size(), f);
-            continue;
+            fwrite(col, 1, (size_t)rows * (size_t)width, f);
         }
-        const bool is_key_string = d.src == 0 && key_kind == HS_STR;
-        const int width = d.src == 0 ? key_bytes : (d.kind == HS_I64 ? 8 : 4);
-        const uint64_t bytes = (uint64_t)rows * (uint64_t)width + (is_key_string ? rows : 0);
-        fwrite(&bytes, 8, 1, f);
-        if (is_key_string) {
-            const uint8_t w = (uint8_t)width;
-            for (uint32_t r = 0; r < rows; ++r) fwrite(&w, 1, 1, f);
-        }
-        fwrite(col, 1, (size_t)rows * (size_t)width, f);
     }
-    fwrite(&block_start, 8, 1, f);
-    const uint32_t nblocks = 1;
+    fwrite(starts.data(), 8, starts.size(), f);
+    const uint32_t nblocks = (uint32_t)starts.size();
     fwrite(&nblocks, 4, 1, f);
     ok = (fclose(f) == 0) && ok;
     if (!ok) {
@@ -2450,6 +2819,12 @@ struct hs_join_group_stage {
     int64_t slots = 0, image_bytes = 0;
     void* image_host = nullptr;
     int64_t runs = 0, grows = 0;
+    // the HBM (radix) tier, taken past the on-chip tiers when the stage's switch is on (sticky)
+    bool hbm_on = false, hbm = false;
+    HbmBufs hbm_bufs;
+    size_t image_host_cap = 0;
+    int32_t last_tier = 1;
+    int64_t tier_switches = 0;
     uint32_t last_flags = 0;
     int64_t last_rows = 0;
     ~hs_join_group_stage() {
@@ -2633,7 +3008,7 @@ int join_group_pairs(hs_join_group_stage* s, hipStream_t stream, uint32_t* flags
     if (unit_rows != s->unit_rows) s->ready = false;  // the chunk geometry follows the JoinJob boundaries
     s->unit_rows = std::move(unit_rows);
     if (n == 0) return HS_OK;
-    return join_group_columns(s, stream, flags, hs_jit_get_enabled() != 0);
+    return join_group_columns(s, stream, flags, hs_jit_get_enabled() != 0 && !s->hbm);  // (the HBM tier reads gathered columns)
 }
 
 }  // namespace
@@ -2659,9 +3034,42 @@ extern "C" int hs_join_group_stage_run(hs_join_group_stage* s, void* stream_, ui
     s->last_rows = 0;
     s->last_flags = join_flags;
     const int64_t n_pairs = s->R.J.n_out;
+    // past the on-chip tiers with the switch on: the stage moves to the HBM tier and stays there
+    auto hbm_enter = [&]() {
+        if (s->image_host) (void)hipHostFree(s->image_host);  // (the on-chip tail's image; this tier's is sized per run)
+        s->image_host = nullptr;
+        s->image_host_cap = 0;
+        s->sh = SharedBufs();
+        s->ws.release();
+        s->chunks.release();
+        s->ready = false;
+        s->hbm = true;
+        ++s->tier_switches;
+    };
     for (int attempt = 0; n_pairs > 0 && attempt < 14; ++attempt) {
         s->last_rows = 0;
+        if (s->hbm) {
+            // any number of groups: the JoinJobs' pair ranges are the units of the row-forming pass + the radix tier
+            if (s->agg_route != HS_JOIN_AGG_GATHERED) rc = join_group_columns(s, stream, flags, false);
+            if (rc) return rc;
+            if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
+            s->fin = P.fin;
+            uint32_t f = 0;
+            rc = hbm_tail(stream, s->hbm_bufs, "hs_join_group_stage_run", s->cols, P.n_cols, P.key_slot, P.prog, P.spec, s->unit_rows, n_pairs,
+                          s->fin, P.fin_prog, s->key_bytes, s->image_host, s->image_host_cap, flags, &f, &s->last_rows);
+            if (rc) return rc;
+            s->last_tier = 2;
+            s->last_flags = join_flags | f;
+            if (flags_out) *flags_out = s->last_flags;
+            if (n_rows_out) *n_rows_out = s->last_rows;
+            return HS_OK;
+        }
         if (!s->ready) rc = join_group_prepare(s);
+        if (rc == HS_E_LIMIT && s->hbm_on) {
+            hbm_enter();
+            rc = HS_OK;
+            continue;
+        }
         if (rc) return rc;
         if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
         rc = hs_agg_shared(stream, s->cols, P.n_cols, P.key_slot, &P.prog, &P.spec, (const hs_chunk*)s->chunks.p, P.n_parts, &s->geom,
@@ -2676,13 +3084,27 @@ extern "C" int hs_join_group_stage_run(hs_join_group_stage* s, void* stream_, ui
         if (!rc)
             rc = shared_tail(stream, s->sh, P.spec, s->fin, P.fin_prog, s->cols[P.key_slot], s->key_bytes, n_pairs, P.n_parts, s->geom.pad,
                              s->slots, s->merge_cap, s->image_host, s->image_bytes, flags, &f, &s->last_rows);
+        if (rc == HS_E_LIMIT && s->hbm_on) {  // more rows than the on-chip merge takes, or a shape this tier does not hold
+            hbm_enter();
+            rc = HS_OK;
+            continue;
+        }
         if (rc) return rc;
+        s->last_tier = 1;
+        if ((f & HS_FLAG_MERGE_ROWS) && s->hbm_on) {
+            hbm_enter();
+            continue;
+        }
         if (f & HS_FLAG_MERGE_ROWS) {
             hs_set_error("hs_join_group_stage_run: more partial rows than the on-chip final merge holds (the HBM tier belongs to the per-operator ABI)");
             return HS_E_LIMIT;
         }
         if (f & (HS_FLAG_DICT_FULL | HS_FLAG_MERGE_FULL)) {  // as hs_stage_run's shared-dictionary tier
             const bool unit_full = f & HS_FLAG_DICT_FULL, merge_full = f & HS_FLAG_MERGE_FULL;
+            if (((unit_full && s->group_cap >= 4096) || (merge_full && s->merge_cap >= 4096)) && s->hbm_on) {
+                hbm_enter();
+                continue;
+            }
             if ((unit_full && s->group_cap >= 4096) || (merge_full && s->merge_cap >= 4096)) {
                 hs_set_error("hs_join_group_stage_run: GROUP BY cardinality exceeds the on-chip tiers of this path");
                 return HS_E_LIMIT;
@@ -2709,6 +3131,27 @@ extern "C" int hs_join_group_stage_run(hs_join_group_stage* s, void* stream_, ui
     return HS_OK;
 }
 
+extern "C" int hs_join_group_stage_set_hbm_tier(hs_join_group_stage* s, int32_t on) {
+    if (!s) {
+        hs_set_error("hs_join_group_stage_set_hbm_tier: null stage");
+        return HS_E_ARG;
+    }
+    s->hbm_on = on != 0;
+    return HS_OK;
+}
+
+extern "C" int hs_join_group_stage_tier_stats(const hs_join_group_stage* s, int64_t* out) {
+    if (!s || !out) {
+        hs_set_error("hs_join_group_stage_tier_stats: bad arguments");
+        return HS_E_ARG;
+    }
+    out[0] = s->last_tier;
+    out[1] = s->hbm_bufs.partial_rows;
+    out[2] = s->hbm_bufs.result_rows;
+    out[3] = s->tier_switches;
+    return HS_OK;
+}
+
 extern "C" int hs_join_group_stage_stats(const hs_join_group_stage* s, int64_t* stats) {
     if (!s || !stats) {
         hs_set_error("hs_join_group_stage_stats: bad arguments");
@@ -2729,10 +3172,11 @@ extern "C" int hs_join_group_stage_stats(const hs_join_group_stage* s, int64_t* 
 
 // The result as a one-block BlockFile; a coded key is decoded through the stage's dictionary (as hs_join_result_write_blockfile)
 extern "C" int hs_join_group_result_write_blockfile(const hs_join_group_stage* s, const char* path) {
-    if (!s || !path || (s->last_rows > 0 && (!s->ready || !s->image_host))) {
+    if (!s || !path || (s->last_rows > 0 && ((!s->ready && !s->hbm) || !s->image_host))) {
         hs_set_error("hs_join_group_result_write_blockfile: bad arguments");
         return HS_E_ARG;
     }
     return write_image_blockfile("hs_join_group_result_write_blockfile", path, s->fin, s->plan.out_types, s->plan.out_names,
-                                 s->image_host, s->last_rows, s->key_kind, s->key_bytes, s->key_coded ? &s->dict : nullptr);
+                                 s->image_host, s->last_rows, s->key_kind, s->key_bytes, s->key_coded ? &s->dict : nullptr,
+                                 s->hbm ? kResultBlockRows : 0);
 }

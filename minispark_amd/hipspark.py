@@ -242,6 +242,7 @@ class hs_join_select_stage_plan(C.Structure):
 
 HS_JOIN_GROUP_STAGE_PLAN_VERSION = 1
 JOIN_AGG_ROUTES = {1: "pairs", 2: "gathered"}  # HS_JOIN_AGG_*
+STAGE_TIERS = {0: "per-lane", 1: "shared", 2: "hbm"}  # hs_stage_tier_stats / hs_join_group_stage_tier_stats, out[0]
 PAIR = 0x100  # HS_PAIR: OR-ed onto HS_I32 / HS_F32 / HS_I64, the column read through its pair rows (hs_col.offs)
 
 
@@ -442,6 +443,14 @@ SIGNATURES: dict[str, tuple] = {
     "hs_stage_wait": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(_I64)]),
     "hs_stage_grow": (C.c_int, [_P]),
     "hs_stage_stats": (C.c_int, [_P, C.POINTER(_I64)]),
+    "hs_stage_set_hbm_tier": (C.c_int, [_P, _I32]),
+    "hs_stage_tier_stats": (C.c_int, [_P, C.POINTER(_I64)]),
+    "hs_join_group_stage_set_hbm_tier": (C.c_int, [_P, _I32]),
+    "hs_join_group_stage_tier_stats": (C.c_int, [_P, C.POINTER(_I64)]),
+    "hs_agg_rows_classify": (C.c_int, [_COLP, _I32, _I32, _PROGP, _P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(C.c_uint64),
+                                      C.POINTER(_I32)]),
+    "hs_agg_rows_ws_bytes": (C.c_size_t, [_I64, _I32]),
+    "hs_agg_rows": (C.c_int, [_P, _COLP, _I32, _I32, _PROGP, _P, _P, _I32, _I64, _P, C.POINTER(_P), C.POINTER(_I32), _P, _P, _P]),
     "hs_result_columns": (C.c_int, [_P, C.POINTER(hs_result_col), _I32, C.POINTER(_I32)]),
     "hs_result_write_blockfile": (C.c_int, [_P, C.c_char_p]),
     "hs_trace_begin": (C.c_int, [_P]),

@@ -744,13 +744,16 @@ class NativeJoinGroupStage:
     """A prepared join feeding a GROUP BY (any join keys and columns) behind the C ABI: ``run(path)`` -> rows (through the
     result BlockFile the library writes)."""
 
-    def __init__(self, engine: "NativeEngine", full_task: Any, plan: Any = None, n_parts: int | None = None) -> None:
+    def __init__(self, engine: "NativeEngine", full_task: Any, plan: Any = None, n_parts: int | None = None,
+                 hbm_tier: bool = False) -> None:
         self.engine, self.lib = engine, engine.lib
         self.blob, self.build_path, self.probe_path, self.schema = lower_join_group_stage_plan(full_task, plan, n_parts)
         self.handle = C.c_void_p()
         hs.check(self.lib.hs_join_group_stage_prepare(engine.handle, engine.table(self.build_path), engine.table(self.probe_path),
                                                       C.byref(self.blob), C.sizeof(self.blob), C.byref(self.handle)),
                  "hs_join_group_stage_prepare")
+        if hbm_tier:  # past the on-chip tiers the stage moves to the HBM (radix) tier instead of answering HS_E_LIMIT
+            hs.check(self.lib.hs_join_group_stage_set_hbm_tier(self.handle, 1), "hs_join_group_stage_set_hbm_tier")
 
     def run(self, out_path: Path | str, stream: int | None = None) -> list[Row]:
         flags, nrows = C.c_uint32(0), C.c_int64(0)
@@ -767,9 +770,12 @@ class NativeJoinGroupStage:
         s = (C.c_int64 * 10)()
         hs.check(self.lib.hs_join_group_stage_stats(self.handle, s), "hs_join_group_stage_stats")
         v = [int(x) for x in s]
+        t = (C.c_int64 * 4)()
+        hs.check(self.lib.hs_join_group_stage_tier_stats(self.handle, t), "hs_join_group_stage_tier_stats")
         return {"runs": v[0], "grows": v[1], "group_cap": v[2], "merge_cap": v[3], "route": hs.JOIN_ROUTES.get(v[4], v[4]),
                 "aggregate": hs.JOIN_AGG_ROUTES.get(v[5], v[5]), "pairs": v[6], "build_rows": v[7], "probe_rows": v[8],
-                "dictionary": v[9]}
+                "dictionary": v[9], "tier": hs.STAGE_TIERS.get(int(t[0]), int(t[0])), "partial_rows": int(t[1]),
+                "result_rows": int(t[2]), "tier_switches": int(t[3])}
 
     def close(self) -> None:
         if self.handle:
@@ -812,12 +818,15 @@ class NativeEngine:
 class NativeStage:
     """A prepared query: ``run()`` -> result rows; ``write(path)`` -> the result BlockFile."""
 
-    def __init__(self, engine: NativeEngine, full_task: Any, plan: Any = None, world: int = 1, rank: int = 0) -> None:
+    def __init__(self, engine: NativeEngine, full_task: Any, plan: Any = None, world: int = 1, rank: int = 0,
+                 hbm_tier: bool = False) -> None:
         self.engine, self.lib = engine, engine.lib
         self.blob, self.table_path, self.schema = lower_stage_plan(full_task, plan)
         self.handle = C.c_void_p()
         hs.check(self.lib.hs_stage_prepare(engine.handle, engine.table(self.table_path, rank, world), C.byref(self.blob),
                                            C.sizeof(self.blob), world, C.byref(self.handle)), "hs_stage_prepare")
+        if hbm_tier:  # past the on-chip tiers the stage moves to the HBM (radix) tier instead of answering HS_E_LIMIT
+            hs.check(self.lib.hs_stage_set_hbm_tier(self.handle, 1), "hs_stage_set_hbm_tier")
 
     def run(self, stream: int | None = None) -> list[Row]:
         flags, nrows = C.c_uint32(0), C.c_int64(0)
@@ -845,7 +854,11 @@ class NativeStage:
     def stats(self) -> dict:
         s = (C.c_int64 * 6)()
         hs.check(self.lib.hs_stage_stats(self.handle, s), "hs_stage_stats")
-        return dict(zip(("runs", "replays", "grows", "group_cap", "merge_cap", "chunks"), (int(v) for v in s)))
+        out = dict(zip(("runs", "replays", "grows", "group_cap", "merge_cap", "chunks"), (int(v) for v in s)))
+        t = (C.c_int64 * 4)()
+        hs.check(self.lib.hs_stage_tier_stats(self.handle, t), "hs_stage_tier_stats")
+        out.update(tier=hs.STAGE_TIERS.get(int(t[0]), int(t[0])), partial_rows=int(t[1]), result_rows=int(t[2]), tier_switches=int(t[3]))
+        return out
 
     def close(self) -> None:
         if self.handle:
