@@ -683,6 +683,162 @@ int64_t image_layout(hs_finish_spec& fin, int key_bytes, int cap) {
     return pos;
 }
 
+// exchange slab: [flags u32][pad][row count i64] | order key i64 x slab_rows | key column | accumulator columns (4 bytes per
+// row), every part 16-byte aligned; keys in their stored kinds, packed into the 64-bit key word by the finish launch.  Returns
+// the slab's bytes (= the stride from one rank's slab to the next)
+int64_t slab_layout(hs_slab_desc& d, int64_t slab_rows, int32_t key_kind, int32_t key_bytes, const hs_agg_spec& spec) {
+    memset(&d, 0, sizeof(d));
+    d.slab_rows = slab_rows;
+    int64_t pos = 16;
+    d.order_off = pos;
+    pos += 8 * d.slab_rows;
+    pos = (pos + 15) & ~(int64_t)15;
+    d.key_off = pos;
+    pos += (int64_t)key_bytes * d.slab_rows;
+    d.n_acc = spec.n_acc;
+    for (int a = 0; a < spec.n_acc; ++a) {
+        pos = (pos + 15) & ~(int64_t)15;
+        d.acc_off[a] = pos;
+        d.acc_kind[a] = spec.is_int[a] ? HS_I32 : HS_F32;
+        pos += 4 * d.slab_rows;
+    }
+    d.stride = (pos + 15) & ~(int64_t)15;
+    d.key_kind = key_kind;
+    d.key_len = key_kind == HS_STR ? key_bytes : 0;
+    return d.stride;
+}
+
+// the GROUP BY key kinds the aggregate stages take as stored, and their widths: INTEGER / FLOAT / TIMESTAMP, strings of a
+// fixed length of 1, 2 or 4 bytes (they pack into the 64-bit key word).  `who` names the stage in the errors
+int group_key_shape(const char* who, const hs_col& kc, int32_t& kind, int32_t& bytes) {
+    if (kc.kind == HS_STR) {
+        if (kc.fixed_len != 1 && kc.fixed_len != 2 && kc.fixed_len != 4) {
+            hs_set_error("%s: a string GROUP BY key needs a fixed length of 1, 2 or 4 bytes on this path", who);
+            return HS_E_LIMIT;
+        }
+        bytes = kc.fixed_len;
+    } else if (kc.kind == HS_I32 || kc.kind == HS_F32 || kc.kind == HS_I64) {
+        bytes = elem_bytes(kc.kind);
+    } else {
+        hs_set_error("%s: GROUP BY key is not a stored column kind", who);
+        return HS_E_LIMIT;
+    }
+    kind = kc.kind;
+    return HS_OK;
+}
+
+// rows before unit u, u = 0 .. n: what the geometry functions and the HBM tier take
+std::vector<int64_t> rows_before(const std::vector<int64_t>& block_rows) {
+    std::vector<int64_t> before(block_rows.size() + 1, 0);
+    for (size_t u = 0; u < block_rows.size(); ++u) before[u + 1] = before[u] + block_rows[u];
+    return before;
+}
+
+// the chunks of this geometry over the units, on the device; chunk0 (optional, host): the first chunk of every unit
+int chunks_upload(const char* who, const int64_t* unit_rows, int64_t n_units, const hs_agg_geom& geom, DevBuf& chunks,
+                  std::vector<int64_t>* chunk0 = nullptr) {
+    std::vector<hs_chunk> host((size_t)(geom.n_chunks > 0 ? geom.n_chunks : 1));
+    std::vector<int64_t> first((size_t)n_units + 1, 0);
+    const int rc = hs_agg_partial_chunks(unit_rows, n_units, &geom, host.data(), first.data());
+    if (rc) return rc;
+    if (!chunks.alloc(host.size() * sizeof(hs_chunk)) ||
+        hipMemcpy(chunks.p, host.data(), host.size() * sizeof(hs_chunk), hipMemcpyHostToDevice) != hipSuccess) {
+        hs_set_error("%s: out of device / pinned memory", who);
+        return HS_E_LAUNCH;
+    }
+    if (chunk0) *chunk0 = std::move(first);
+    return HS_OK;
+}
+
+// a stage's pinned result image of image_bytes, zeroed, in place of the one it had.  dev != NULL: mapped, *dev = the address
+// the finish launch writes it at
+bool image_alloc(void*& host, void** dev, int64_t image_bytes) {
+    if (host) (void)hipHostFree(host);
+    host = nullptr;
+    if (dev) *dev = nullptr;
+    if (hipHostMalloc(&host, (size_t)image_bytes + kPad, dev ? hipHostMallocMapped : hipHostMallocDefault) != hipSuccess) {
+        host = nullptr;
+        return false;
+    }
+    if (dev && (hipHostGetDevicePointer(dev, host, 0) != hipSuccess || !*dev)) return false;
+    memset(host, 0, (size_t)image_bytes + kPad);
+    return true;
+}
+
+// The launches of one run: issued as they are on the first run with the stage's capacities, recorded on the second (the
+// one that is kept), replayed from then on
+template <class Launch>
+int run_or_replay(void*& capture, int64_t runs, int64_t& replays, void* stream, Launch launch) {
+    if (capture) {
+        ++replays;
+        return hs_capture_replay(capture, stream);
+    }
+    const bool record = runs >= 1;
+    int rc = record ? hs_capture_begin() : HS_OK;
+    if (!rc) rc = launch();
+    if (record) {
+        int32_t n_ops = 0;
+        void* handle = nullptr;
+        const int rc2 = hs_capture_end(&handle, &n_ops);
+        if (!rc && !rc2 && n_ops > 0) capture = handle;
+        else if (handle) hs_capture_free(handle);
+    }
+    return rc;
+}
+
+// the finish launch's hand-over through the mapped image: [flags u32][done u32][row count i64]
+int wait_result(const char* who, void* image_host, int32_t merge_cap, void* stream, uint32_t* flags, int64_t* rows) {
+    volatile uint32_t* done = (volatile uint32_t*)image_host + 1;
+    for (int64_t spins = 0; *done == 0; ++spins) {
+        if (spins > 2000000) {  // a long scan: let the runtime wait instead of this core
+            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || *done == 0) {
+                hs_set_error("%s: the finish launch did not hand its result over", who);
+                return HS_E_LAUNCH;
+            }
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    *flags = *(volatile uint32_t*)image_host;
+    const int64_t n = *(volatile int64_t*)((char*)image_host + 8);
+    *rows = n < merge_cap ? n : merge_cap;
+    *done = 0;  // ready for the next launch into this image
+    return HS_OK;
+}
+
+// What the shared-dictionary tier does about the flags of a run: nothing (the result stands), x4 on the capacity that was
+// full (the merge holds at least as many keys as a unit table; 4096 is the on-chip tiers' cap) and run again, or - past the
+// cap, or with more partial rows than the on-chip merge holds - the HBM tier where its switch is on, else HS_E_LIMIT
+enum class SharedNext { done, grown, to_hbm, limit };
+
+SharedNext shared_next(const char* who, uint32_t f, bool hbm_on, int32_t& group_cap, int32_t& merge_cap) {
+    const bool unit_full = f & HS_FLAG_DICT_FULL, merge_full = f & HS_FLAG_MERGE_FULL;
+    if (f & HS_FLAG_MERGE_ROWS) {
+        if (hbm_on) return SharedNext::to_hbm;
+        hs_set_error("%s: more partial rows than the on-chip final merge holds (the HBM tier belongs to the per-operator ABI)", who);
+        return SharedNext::limit;
+    }
+    if (!unit_full && !merge_full) return SharedNext::done;
+    if ((unit_full && group_cap >= 4096) || (merge_full && merge_cap >= 4096)) {
+        if (hbm_on) return SharedNext::to_hbm;
+        hs_set_error("%s: GROUP BY cardinality exceeds the on-chip tiers of this path", who);
+        return SharedNext::limit;
+    }
+    if (unit_full) group_cap *= 4;
+    if (merge_full) merge_cap *= 4;
+    if (merge_cap < group_cap) merge_cap = group_cap;
+    if (merge_cap > 4096) merge_cap = 4096;
+    return SharedNext::grown;
+}
+
+// a stage leaves the on-chip tiers for the HBM tier: their buffers go (the HBM tier's image is sized per run)
+void onchip_release(void*& image_host, size_t& image_host_cap, SharedBufs& sh, DevBuf& ws) {
+    if (image_host) (void)hipHostFree(image_host);
+    image_host = nullptr;
+    image_host_cap = 0;
+    sh = SharedBufs();
+    ws.release();
+}
+
 // After hs_agg_shared filled B.rep / B.acc / B.ngroups: dense partial rows -> merge in unit order -> projection -> rounding ->
 // result image on the host.  kc: the key column the scan read (key_rows rows); *flags_out / *rows_out: the run's result.
 int shared_tail(hipStream_t stream, SharedBufs& B, const hs_agg_spec& spec, const hs_finish_spec& fin, const hs_program& fin_prog,
@@ -1017,10 +1173,129 @@ int hbm_tail(hipStream_t stream, HbmBufs& H, const char* who, const hs_col* cols
     return HS_OK;
 }
 
-// (defined with the join stage below) the result image as a BlockFile of rows_per_block-row blocks; 0 = one block
+// ---- result files: the BlockFile format (reference io.py:47-109), written from a result image or from host columns ----------
+// schema header: column count, then type code, name length and name of every column.  NULL (error set): the file cannot be made
+FILE* blockfile_begin(const char* who, const char* path, int n_out, const int32_t* out_types, const char (*out_names)[64]) {
+    FILE* f = fopen(path, "wb");
+    if (!f) {
+        hs_set_error("%s: cannot create %s", who, path);
+        return nullptr;
+    }
+    const uint8_t nc = (uint8_t)n_out;
+    fwrite(&nc, 1, 1, f);
+    for (int o = 0; o < n_out; ++o) {
+        const uint8_t type = (uint8_t)out_types[o];
+        const uint8_t len = (uint8_t)strnlen(out_names[o], 64);
+        fwrite(&type, 1, 1, f);
+        fwrite(&len, 1, 1, f);
+        fwrite(out_names[o], 1, len, f);
+    }
+    return f;
+}
+
+// footer: where every block starts, the block count; false when the file did not take every byte written since blockfile_begin
+bool blockfile_end(FILE* f, const std::vector<uint64_t>& starts) {
+    fwrite(starts.data(), 8, starts.size(), f);
+    const uint32_t nblocks = (uint32_t)starts.size();
+    fwrite(&nblocks, 4, 1, f);
+    return fclose(f) == 0;
+}
+
+// A result image as a BlockFile (tasks.py:400-410): one block for the on-chip path (rows_per_block 0), blocks of
+// rows_per_block rows for the HBM tier; a key of dictionary codes (dict != NULL) is decoded through the dictionary.  `who`
+// names the entry point in errors.
 int write_image_blockfile(const char* who, const char* path, const hs_finish_spec& fin, const int32_t* out_types,
                           const char (*out_names)[64], const void* image_host, int64_t last_rows, int key_kind, int key_bytes,
-                          const std::vector<std::string>* dict, int64_t rows_per_block = 0);
+                          const std::vector<std::string>* dict, int64_t rows_per_block = 0) {
+    if (last_rows == 0) return HS_OK;  // empty result: the reference writes no file (tasks.py:405)
+    const int n_out = fin.n_out;
+    FILE* f = blockfile_begin(who, path, n_out, out_types, out_names);
+    if (!f) return HS_E_ARG;
+    if (rows_per_block < 1) rows_per_block = last_rows;
+    std::vector<uint64_t> starts;
+    bool ok = true;
+    for (int64_t lo = 0; lo < last_rows; lo += rows_per_block) {  // a result larger than a block continues in further blocks
+        const uint32_t rows = (uint32_t)(lo + rows_per_block < last_rows ? rows_per_block : last_rows - lo);
+        starts.push_back((uint64_t)ftell(f));
+        fwrite(&rows, 4, 1, f);
+        for (int o = 0; o < n_out; ++o) {
+            const hs_finish_out& d = fin.outs[o];
+            const int width = d.src == 0 ? key_bytes : (d.kind == HS_I64 ? 8 : 4);
+            const uint8_t* col = (const uint8_t*)image_host + d.offset + (size_t)lo * (size_t)width;
+            if (d.src == 0 && dict) {  // code bytes -> the strings they stand for
+                uint64_t bytes = rows;
+                for (uint32_t r = 0; r < rows; ++r) {
+                    if (col[r] >= dict->size()) ok = false;
+                    else bytes += (*dict)[col[r]].size();
+                }
+                fwrite(&bytes, 8, 1, f);
+                for (uint32_t r = 0; ok && r < rows; ++r) {
+                    const uint8_t len = (uint8_t)(*dict)[col[r]].size();
+                    fwrite(&len, 1, 1, f);
+                }
+                for (uint32_t r = 0; ok && r < rows; ++r) fwrite((*dict)[col[r]].data(), 1, (*dict)[col[r]].size(), f);
+                continue;
+            }
+            const bool is_key_string = d.src == 0 && key_kind == HS_STR;
+            const uint64_t bytes = (uint64_t)rows * (uint64_t)width + (is_key_string ? rows : 0);
+            fwrite(&bytes, 8, 1, f);
+            if (is_key_string) {  // STRING payload: the length bytes, then the strings
+                const std::vector<uint8_t> lens(rows, (uint8_t)width);
+                fwrite(lens.data(), 1, rows, f);
+            }
+            fwrite(col, 1, (size_t)rows * (size_t)width, f);
+        }
+    }
+    ok = blockfile_end(f, starts) && ok;
+    if (!ok) {
+        hs_set_error("%s: write to %s failed (or a key code outside the dictionary)", who, path);
+        return HS_E_ARG;
+    }
+    return HS_OK;
+}
+
+struct HostCol {  // one result column on the host: fixed-width values, or lens + payload (width -1)
+    std::vector<uint8_t> data, lens;
+    int width = 0;
+};
+
+// Host columns as a BlockFile of rows_per_block-row blocks (reference tasks.py:391-410 + io.py:217-252: a result larger
+// than a block continues in further blocks; an empty result writes no file).
+int write_rows_blockfile(const char* who, const char* path, int n_out, const int32_t* out_types, const char (*out_names)[64],
+                         const std::vector<HostCol>& outs, int64_t last_rows, int64_t rows_per_block) {
+    if (last_rows == 0) return HS_OK;
+    FILE* f = blockfile_begin(who, path, n_out, out_types, out_names);
+    if (!f) return HS_E_ARG;
+    std::vector<uint64_t> starts;
+    std::vector<int64_t> str_pos((size_t)n_out, 0);  // byte position inside a string column's payload
+    for (int64_t lo = 0; lo < last_rows; lo += rows_per_block) {
+        const int64_t hi = lo + rows_per_block < last_rows ? lo + rows_per_block : last_rows;
+        const uint32_t rows = (uint32_t)(hi - lo);
+        starts.push_back((uint64_t)ftell(f));
+        fwrite(&rows, 4, 1, f);
+        for (int o = 0; o < n_out; ++o) {
+            const HostCol& out = outs[(size_t)o];
+            if (out.width > 0) {
+                const uint64_t bytes = (uint64_t)rows * (uint64_t)out.width;
+                fwrite(&bytes, 8, 1, f);
+                fwrite(out.data.data() + (size_t)lo * (size_t)out.width, 1, (size_t)bytes, f);
+            } else {
+                uint64_t payload = 0;
+                for (int64_t r = lo; r < hi; ++r) payload += out.lens[(size_t)r];
+                const uint64_t bytes = rows + payload;
+                fwrite(&bytes, 8, 1, f);
+                fwrite(out.lens.data() + lo, 1, rows, f);
+                fwrite(out.data.data() + str_pos[(size_t)o], 1, (size_t)payload, f);
+                str_pos[(size_t)o] += (int64_t)payload;
+            }
+        }
+    }
+    if (!blockfile_end(f, starts)) {
+        hs_set_error("%s: write to %s failed", who, path);
+        return HS_E_ARG;
+    }
+    return HS_OK;
+}
 
 }  // namespace
 
@@ -1107,77 +1382,30 @@ int stage_prepare(hs_stage* s) {
     s->ready = false;
     if (const int rc0 = bind_columns(s)) return rc0;
     const hs_col& kc = s->cols[P.key_slot];
-    // the exchange slab holds keys in their stored kinds, packed into the 64-bit key word by the finish launch
-    if (kc.kind == HS_STR) {
-        if (kc.fixed_len != 1 && kc.fixed_len != 2 && kc.fixed_len != 4) {
-            hs_set_error("hs_stage: a string GROUP BY key needs a fixed length of 1, 2 or 4 bytes on this path");
-            return HS_E_LIMIT;
-        }
-        s->key_bytes = kc.fixed_len;
-    } else if (kc.kind == HS_I32 || kc.kind == HS_F32 || kc.kind == HS_I64) {
-        s->key_bytes = elem_bytes(kc.kind);
-    } else {
-        hs_set_error("hs_stage: GROUP BY key is not a stored column kind");
-        return HS_E_LIMIT;
-    }
+    int32_t key_kind = 0;
+    if (const int rck = group_key_shape("hs_stage", kc, key_kind, s->key_bytes)) return rck;
     // units = the table's local blocks (reference: one ScanJob per block, plan.py:90-93)
-    s->n_units = (int64_t)t->block_rows.size();
-    std::vector<int64_t> unit_rows(s->n_units + 1, 0);
-    for (int64_t u = 0; u < s->n_units; ++u) unit_rows[u + 1] = unit_rows[u] + t->block_rows[u];
-    int rc = hs_agg_partial_geom(unit_rows.data(), s->n_units, P.spec.n_acc, s->group_cap, &s->geom);
+    int rc = hs_agg_partial_geom(s->unit_rows.data(), s->n_units, P.spec.n_acc, s->group_cap, &s->geom);
     if (rc) return rc;  // HS_E_LIMIT: the private-table tier does not hold this query
-    std::vector<hs_chunk> chunks((size_t)(s->geom.n_chunks > 0 ? s->geom.n_chunks : 1));
-    std::vector<int64_t> chunk0((size_t)s->n_units + 1, 0);
-    rc = hs_agg_partial_chunks(unit_rows.data(), s->n_units, &s->geom, chunks.data(), chunk0.data());
+    std::vector<int64_t> chunk0;
+    rc = chunks_upload("hs_stage", s->unit_rows.data(), s->n_units, s->geom, s->chunks, &chunk0);
     if (rc) return rc;
     std::vector<int64_t> ids(t->file_blocks.begin(), t->file_blocks.end());
-    bool ok = s->chunks.alloc(chunks.size() * sizeof(hs_chunk)) && s->chunk0.alloc(chunk0.size() * 8) &&
-              s->unit_ids.alloc((ids.size() ? ids.size() : 1) * 8) && s->ws.alloc(s->geom.ws_bytes, true);
-    ok = ok && hipMemcpy(s->chunks.p, chunks.data(), chunks.size() * sizeof(hs_chunk), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(s->chunk0.p, chunk0.data(), chunk0.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
+    bool ok = s->chunk0.alloc(chunk0.size() * 8) && s->unit_ids.alloc((ids.size() ? ids.size() : 1) * 8) && s->ws.alloc(s->geom.ws_bytes, true);
+    ok = ok && hipMemcpy(s->chunk0.p, chunk0.data(), chunk0.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
          (ids.empty() || hipMemcpy(s->unit_ids.p, ids.data(), ids.size() * 8, hipMemcpyHostToDevice) == hipSuccess);
-    // slab: [flags u32][pad][row count i64] | order key i64 x M | key column | accumulator columns (4 bytes per row)
+    // slab rows: group_cap per unit, for the rank with the most units; order keys start at -1 (no row)
     const int64_t max_local = (t->total_blocks + s->world - 1) / s->world;
     const int64_t M = (s->n_units > max_local ? s->n_units : max_local) * s->group_cap;
     hs_slab_desc& d = s->desc;
-    memset(&d, 0, sizeof(d));
-    d.slab_rows = M > 0 ? M : s->group_cap;
-    int64_t pos = 16;
-    d.order_off = pos;
-    pos += 8 * d.slab_rows;
-    pos = (pos + 15) & ~(int64_t)15;
-    d.key_off = pos;
-    pos += (int64_t)s->key_bytes * d.slab_rows;
-    d.n_acc = P.spec.n_acc;
-    for (int a = 0; a < P.spec.n_acc; ++a) {
-        pos = (pos + 15) & ~(int64_t)15;
-        d.acc_off[a] = pos;
-        d.acc_kind[a] = P.spec.is_int[a] ? HS_I32 : HS_F32;
-        pos += 4 * d.slab_rows;
-    }
-    s->slab_bytes = (pos + 15) & ~(int64_t)15;
-    d.stride = s->slab_bytes;
-    d.key_kind = kc.kind;
-    d.key_len = kc.kind == HS_STR ? kc.fixed_len : 0;
+    s->slab_bytes = slab_layout(d, M > 0 ? M : s->group_cap, key_kind, s->key_bytes, P.spec);
     std::vector<uint8_t> slab_image((size_t)s->slab_bytes, 0);
     for (int64_t r = 0; r < d.slab_rows; ++r) ((int64_t*)(slab_image.data() + d.order_off))[r] = -1;
     ok = ok && s->slab.alloc((size_t)s->slab_bytes) &&
          hipMemcpy(s->slab.p, slab_image.data(), slab_image.size(), hipMemcpyHostToDevice) == hipSuccess;
-    // result image: header 16 bytes, then every column at a 16-byte aligned offset, cap elements each
     s->fin = P.fin;
-    pos = 16;
-    for (int o = 0; o < s->fin.n_out; ++o) {
-        hs_finish_out& out = s->fin.outs[o];
-        const int width = out.src == 0 ? s->key_bytes : (out.kind == HS_I64 ? 8 : 4);
-        out.offset = pos;
-        pos = (pos + (int64_t)s->merge_cap * width + 15) & ~(int64_t)15;
-    }
-    s->image_bytes = pos;
-    if (s->image_host) (void)hipHostFree(s->image_host);
-    s->image_host = s->image_dev = nullptr;
-    ok = ok && hipHostMalloc(&s->image_host, (size_t)s->image_bytes + kPad, hipHostMallocMapped) == hipSuccess &&
-         hipHostGetDevicePointer(&s->image_dev, s->image_host, 0) == hipSuccess && s->image_dev;
-    if (ok) memset(s->image_host, 0, (size_t)s->image_bytes + kPad);
+    s->image_bytes = image_layout(s->fin, s->key_bytes, s->merge_cap);
+    ok = ok && image_alloc(s->image_host, &s->image_dev, s->image_bytes);
     ok = ok && s->scratch.alloc(hs_agg_finish_scratch_bytes(s->merge_cap, s->fin.n_fold), true);
     if (!ok) {
         hs_set_error("hs_stage: out of device / pinned memory");
@@ -1206,31 +1434,12 @@ int launch_finish(hs_stage* s, void* stream, const void* gathered, int32_t world
                          s->scratch.p, engine_flags(s), (uint32_t*)s->slab.p);
 }
 
-int wait_result(hs_stage* s, void* stream) {
-    volatile uint32_t* done = (volatile uint32_t*)s->image_host + 1;
-    for (int64_t spins = 0; *done == 0; ++spins) {
-        if (spins > 2000000) {  // a long scan: let the runtime wait instead of this core
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || *done == 0) {
-                hs_set_error("hs_stage_run: the finish launch did not hand its result over");
-                return HS_E_LAUNCH;
-            }
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    s->last_flags = *(volatile uint32_t*)s->image_host;
-    const int64_t n = *(volatile int64_t*)((char*)s->image_host + 8);
-    s->last_rows = n < s->merge_cap ? n : s->merge_cap;
-    *done = 0;  // ready for the next launch into this image
-    return HS_OK;
-}
-
 }  // namespace
 
 namespace {
 
 // ---- the shared-dictionary tier behind hs_stage_run ------------------------------------------------------------------------
 int shared_prepare(hs_stage* s) {
-    hs_table* t = s->table;
     const hs_stage_plan& P = s->plan;
     s->ready = false;
     if (s->world != 1) {
@@ -1239,48 +1448,27 @@ int shared_prepare(hs_stage* s) {
     }
     if (const int rc0 = bind_columns(s)) return rc0;
     const hs_col& kc = s->cols[P.key_slot];
-    if (kc.kind == HS_STR) {
-        if (kc.fixed_len != 1 && kc.fixed_len != 2 && kc.fixed_len != 4) {
-            hs_set_error("hs_stage: a string GROUP BY key needs a fixed length of 1, 2 or 4 bytes on this path");
-            return HS_E_LIMIT;
-        }
-        s->key_bytes = kc.fixed_len;
-    } else if (kc.kind == HS_I32 || kc.kind == HS_F32 || kc.kind == HS_I64) {
-        s->key_bytes = elem_bytes(kc.kind);
-    } else {
-        hs_set_error("hs_stage: GROUP BY key is not a stored column kind");
-        return HS_E_LIMIT;
-    }
-    s->n_units = (int64_t)t->block_rows.size();
-    std::vector<int64_t> unit_rows(s->n_units + 1, 0);
-    for (int64_t u = 0; u < s->n_units; ++u) unit_rows[u + 1] = unit_rows[u] + t->block_rows[u];
-    int rc = hs_agg_shared_geom(unit_rows.data(), s->n_units, P.spec.n_acc, s->group_cap, &s->geom);
+    int32_t key_kind = 0;
+    if (const int rck = group_key_shape("hs_stage", kc, key_kind, s->key_bytes)) return rck;
+    int rc = hs_agg_shared_geom(s->unit_rows.data(), s->n_units, P.spec.n_acc, s->group_cap, &s->geom);
     if (rc) return rc;
-    std::vector<hs_chunk> chunks((size_t)(s->geom.n_chunks > 0 ? s->geom.n_chunks : 1));
-    std::vector<int64_t> chunk0((size_t)s->n_units + 1, 0);
-    rc = hs_agg_partial_chunks(unit_rows.data(), s->n_units, &s->geom, chunks.data(), chunk0.data());
+    rc = chunks_upload("hs_stage", s->unit_rows.data(), s->n_units, s->geom, s->chunks);
     if (rc) return rc;
     const int unit_cap = s->geom.pad, n_acc = P.spec.n_acc, nf = s->plan.fin.n_fold;
     s->sh_slots = s->n_units * (int64_t)unit_cap;
     const int64_t slots = s->sh_slots > 0 ? s->sh_slots : 1;
-    bool ok = s->chunks.alloc(chunks.size() * sizeof(hs_chunk)) &&
-              hipMemcpy(s->chunks.p, chunks.data(), chunks.size() * sizeof(hs_chunk), hipMemcpyHostToDevice) == hipSuccess &&
-              s->ws.alloc(s->geom.ws_bytes, true) && shared_alloc(s->sh, slots, s->n_units, n_acc, nf, s->merge_cap);
     // result image: the layout of the on-chip path (hs_result_columns / hs_result_write_blockfile read it)
     s->fin = P.fin;
     s->image_bytes = image_layout(s->fin, s->key_bytes, s->merge_cap);
-    if (s->image_host) (void)hipHostFree(s->image_host);
-    s->image_host = s->image_dev = nullptr;
-    ok = ok && hipHostMalloc(&s->image_host, (size_t)s->image_bytes + kPad, hipHostMallocDefault) == hipSuccess &&
-         s->sh.image.alloc((size_t)s->image_bytes, true);
-    if (!ok) {
+    s->image_dev = nullptr;
+    if (!s->ws.alloc(s->geom.ws_bytes, true) || !shared_alloc(s->sh, slots, s->n_units, n_acc, nf, s->merge_cap) ||
+        !image_alloc(s->image_host, nullptr, s->image_bytes) || !s->sh.image.alloc((size_t)s->image_bytes, true)) {
         hs_set_error("hs_stage: out of device / pinned memory");
         return HS_E_LAUNCH;
     }
-    memset(s->image_host, 0, (size_t)s->image_bytes + kPad);
     memset(&s->desc, 0, sizeof(s->desc));
-    s->desc.key_kind = kc.kind;
-    s->desc.key_len = kc.kind == HS_STR ? kc.fixed_len : 0;
+    s->desc.key_kind = key_kind;
+    s->desc.key_len = key_kind == HS_STR ? s->key_bytes : 0;
     s->ready = true;
     return HS_OK;
 }
@@ -1316,12 +1504,9 @@ void hbm_enter(hs_stage* s) {
         hs_capture_free(s->capture);
         s->capture = nullptr;
     }
-    if (s->image_host) (void)hipHostFree(s->image_host);  // (the on-chip tiers' image; this tier's is sized per run)
-    s->image_host = s->image_dev = nullptr;
-    s->image_host_cap = 0;
-    s->sh = SharedBufs();
+    onchip_release(s->image_host, s->image_host_cap, s->sh, s->ws);
+    s->image_dev = nullptr;
     s->slab.release();
-    s->ws.release();
     s->scratch.release();
     s->tier = 2;
     s->ready = false;
@@ -1337,14 +1522,11 @@ int hbm_run(hs_stage* s, void* stream_) {
     s->last_flags = 0;
     if (!s->ready) {
         if (const int rc0 = bind_columns(s)) return rc0;
-        const hs_col& kc = s->cols[P.key_slot];
-        s->key_bytes = kc.kind == HS_STR ? kc.fixed_len : elem_bytes(kc.kind);
+        int32_t key_kind = 0;
+        if (const int rck = group_key_shape("hs_stage", s->cols[P.key_slot], key_kind, s->key_bytes)) return rck;
         memset(&s->desc, 0, sizeof(s->desc));
-        s->desc.key_kind = kc.kind;
-        s->desc.key_len = kc.kind == HS_STR ? kc.fixed_len : 0;
-        s->n_units = (int64_t)t->block_rows.size();
-        s->unit_rows.assign((size_t)s->n_units + 1, 0);
-        for (int64_t u = 0; u < s->n_units; ++u) s->unit_rows[(size_t)u + 1] = s->unit_rows[(size_t)u] + t->block_rows[(size_t)u];
+        s->desc.key_kind = key_kind;
+        s->desc.key_len = key_kind == HS_STR ? s->key_bytes : 0;
         s->ready = true;
     }
     s->fin = P.fin;
@@ -1389,6 +1571,8 @@ extern "C" int hs_stage_prepare(hs_engine* e, hs_table* t, const hs_stage_plan* 
     s->world = world;
     s->group_cap = plan->group_cap > 0 ? plan->group_cap : 4;
     s->merge_cap = plan->merge_cap > 0 ? plan->merge_cap : 16;
+    s->n_units = (int64_t)t->block_rows.size();
+    s->unit_rows = rows_before(t->block_rows);
     rc = stage_prepare(s);
     if (rc) {
         delete s;
@@ -1434,28 +1618,13 @@ extern "C" int hs_stage_run(hs_stage* s, void* stream, uint32_t* flags_out, int6
             if (rc) return rc;
             ++s->runs;
             s->last_tier = 1;
-            if (s->last_flags & HS_FLAG_MERGE_ROWS) {
-                if (s->hbm_on) {
-                    hbm_enter(s);
-                    continue;
-                }
-                hs_set_error("hs_stage_run: more partial rows than the on-chip final merge holds (the HBM tier belongs to the per-operator ABI)");
-                return HS_E_LIMIT;
+            const SharedNext next = shared_next("hs_stage_run", s->last_flags, s->hbm_on, s->group_cap, s->merge_cap);
+            if (next == SharedNext::limit) return HS_E_LIMIT;
+            if (next == SharedNext::to_hbm) {
+                hbm_enter(s);
+                continue;
             }
-            if (s->last_flags & (HS_FLAG_DICT_FULL | HS_FLAG_MERGE_FULL)) {
-                const bool unit_full = s->last_flags & HS_FLAG_DICT_FULL, merge_full = s->last_flags & HS_FLAG_MERGE_FULL;
-                if ((unit_full && s->group_cap >= 4096) || (merge_full && s->merge_cap >= 4096)) {
-                    if (s->hbm_on) {
-                        hbm_enter(s);
-                        continue;
-                    }
-                    hs_set_error("hs_stage_run: GROUP BY cardinality exceeds the on-chip tiers of this path");
-                    return HS_E_LIMIT;
-                }
-                if (unit_full) s->group_cap *= 4;
-                if (merge_full) s->merge_cap *= 4;
-                if (s->merge_cap < s->group_cap) s->merge_cap = s->group_cap;
-                if (s->merge_cap > 4096) s->merge_cap = 4096;
+            if (next == SharedNext::grown) {
                 s->ready = false;
                 ++s->grows;
                 continue;
@@ -1473,24 +1642,12 @@ extern "C" int hs_stage_run(hs_stage* s, void* stream, uint32_t* flags_out, int6
             continue;
         }
         if (rc) return rc;
-        if (s->capture) {
-            rc = hs_capture_replay(s->capture, stream);
-            ++s->replays;
-        } else {
-            const bool record = s->runs >= 1;  // the second run with these capacities is the one that is kept
-            if (record) rc = hs_capture_begin();
-            if (!rc) rc = launch_partial(s, stream);
-            if (!rc) rc = launch_finish(s, stream, nullptr, 1);
-            if (record) {
-                int32_t n_ops = 0;
-                void* handle = nullptr;
-                const int rc2 = hs_capture_end(&handle, &n_ops);
-                if (!rc && !rc2 && n_ops > 0) s->capture = handle;
-                else if (handle) hs_capture_free(handle);
-            }
-        }
+        rc = run_or_replay(s->capture, s->runs, s->replays, stream, [&]() {
+            const int rcp = launch_partial(s, stream);
+            return rcp ? rcp : launch_finish(s, stream, nullptr, 1);
+        });
         if (rc) return rc;
-        rc = wait_result(s, stream);
+        rc = wait_result("hs_stage_run", s->image_host, s->merge_cap, stream, &s->last_flags, &s->last_rows);
         if (rc) return rc;
         ++s->runs;
         s->last_tier = 0;
@@ -1559,7 +1716,7 @@ extern "C" int hs_stage_launch_finish(hs_stage* s, void* stream, const void* gat
 }
 extern "C" int hs_stage_wait(hs_stage* s, void* stream, uint32_t* flags_out, int64_t* n_rows_out) {
     if (!s || !s->ready || s->tier == 2) return HS_E_ARG;
-    const int rc = wait_result(s, stream);
+    const int rc = wait_result("hs_stage_run", s->image_host, s->merge_cap, stream, &s->last_flags, &s->last_rows);
     if (rc) return rc;
     if (flags_out) *flags_out = s->last_flags;
     if (n_rows_out) *n_rows_out = s->last_rows;
@@ -1634,50 +1791,9 @@ extern "C" int hs_result_write_blockfile(const hs_stage* s, const char* path) {
         hs_set_error("hs_result_write_blockfile: bad arguments");
         return HS_E_ARG;
     }
-    if (s->tier == 2)  // any number of rows: blocks of ROWS_PER_BLOCK rows (io.py:217-252)
-        return write_image_blockfile("hs_result_write_blockfile", path, s->fin, s->plan.out_types, s->plan.out_names, s->image_host,
-                                     s->last_rows, s->desc.key_kind, s->key_bytes, nullptr, kResultBlockRows);
-    if (s->last_rows == 0) return HS_OK;  // empty result: the reference writes no file (tasks.py:405)
-    FILE* f = fopen(path, "wb");
-    if (!f) {
-        hs_set_error("hs_result_write_blockfile: cannot create %s", path);
-        return HS_E_ARG;
-    }
-    const int n_out = s->fin.n_out;
-    const uint8_t nc = (uint8_t)n_out;
-    fwrite(&nc, 1, 1, f);
-    for (int o = 0; o < n_out; ++o) {
-        const uint8_t type = (uint8_t)s->plan.out_types[o];
-        const uint8_t len = (uint8_t)strnlen(s->plan.out_names[o], sizeof(s->plan.out_names[o]));
-        fwrite(&type, 1, 1, f);
-        fwrite(&len, 1, 1, f);
-        fwrite(s->plan.out_names[o], 1, len, f);
-    }
-    const uint64_t block_start = (uint64_t)ftell(f);
-    const uint32_t rows = (uint32_t)s->last_rows;
-    fwrite(&rows, 4, 1, f);
-    for (int o = 0; o < n_out; ++o) {
-        const hs_finish_out& d = s->fin.outs[o];
-        const uint8_t* col = (const uint8_t*)s->image_host + d.offset;
-        const bool is_key_string = d.src == 0 && s->desc.key_kind == HS_STR;
-        const int width = d.src == 0 ? s->key_bytes : (d.kind == HS_I64 ? 8 : 4);
-        const uint64_t bytes = (uint64_t)rows * (uint64_t)width + (is_key_string ? rows : 0);
-        fwrite(&bytes, 8, 1, f);
-        if (is_key_string) {  // STRING payload: the length bytes, then the strings
-            const uint8_t w = (uint8_t)width;
-            for (uint32_t r = 0; r < rows; ++r) fwrite(&w, 1, 1, f);
-        }
-        fwrite(col, 1, (size_t)rows * (size_t)width, f);
-    }
-    fwrite(&block_start, 8, 1, f);
-    const uint32_t nblocks = 1;
-    fwrite(&nblocks, 4, 1, f);
-    const bool ok = fclose(f) == 0;
-    if (!ok) {
-        hs_set_error("hs_result_write_blockfile: write to %s failed", path);
-        return HS_E_ARG;
-    }
-    return HS_OK;
+    // the HBM tier holds any number of rows: blocks of ROWS_PER_BLOCK rows (io.py:217-252)
+    return write_image_blockfile("hs_result_write_blockfile", path, s->fin, s->plan.out_types, s->plan.out_names, s->image_host,
+                                 s->last_rows, s->desc.key_kind, s->key_bytes, nullptr, s->tier == 2 ? kResultBlockRows : 0);
 }
 
 // =====================================================================================================================
@@ -1803,9 +1919,7 @@ int join_prepare_aggregate(hs_join_stage* s) {
     const int64_t unit_rows[2] = {0, s->probe->nrows};
     int rc = hs_agg_shared_geom(unit_rows, 1, P.spec.n_acc, cap, &s->geom);
     if (rc) return rc;
-    std::vector<hs_chunk> chunks((size_t)(s->geom.n_chunks > 0 ? s->geom.n_chunks : 1));
-    int64_t chunk0[2] = {0, 0};
-    rc = hs_agg_partial_chunks(unit_rows, 1, &s->geom, chunks.data(), chunk0);
+    rc = chunks_upload("hs_join_stage", unit_rows, 1, s->geom, s->chunks);
     if (rc) return rc;
     int per_unit = cap / s->n_units, small = 16;
     if (per_unit < 4) per_unit = 4;
@@ -1814,45 +1928,14 @@ int join_prepare_aggregate(hs_join_stage* s) {
     s->unit_cap = s->geom.pad;
     const int64_t slots = (int64_t)s->n_units * s->unit_cap;
     const int n_acc = P.spec.n_acc;
-    bool ok = s->chunks.alloc(chunks.size() * sizeof(hs_chunk)) &&
-              hipMemcpy(s->chunks.p, chunks.data(), chunks.size() * sizeof(hs_chunk), hipMemcpyHostToDevice) == hipSuccess &&
-              s->out_rep.alloc((size_t)slots * 8) && s->xbuf.alloc((size_t)(16 + slots * 8 * (1 + n_acc)), true) &&
+    bool ok = s->out_rep.alloc((size_t)slots * 8) && s->xbuf.alloc((size_t)(16 + slots * 8 * (1 + n_acc)), true) &&
               s->ws.alloc((size_t)(s->geom.n_chunks > 0 ? s->geom.n_chunks : 1) * (size_t)slots * (size_t)(n_acc > 0 ? n_acc : 1) * 8, true);
-    // slab: header | order key i64 x M | key column | accumulator columns (4 bytes per row); unit u owns rows [u * cap, (u + 1) * cap)
-    hs_slab_desc& d = s->desc;
-    memset(&d, 0, sizeof(d));
-    d.slab_rows = slots;
-    int64_t pos = 16;
-    d.order_off = pos;
-    pos += 8 * d.slab_rows;
-    pos = (pos + 15) & ~(int64_t)15;
-    d.key_off = pos;
-    pos += (int64_t)s->key_bytes * d.slab_rows;
-    d.n_acc = n_acc;
-    for (int a = 0; a < n_acc; ++a) {
-        pos = (pos + 15) & ~(int64_t)15;
-        d.acc_off[a] = pos;
-        d.acc_kind[a] = P.spec.is_int[a] ? HS_I32 : HS_F32;
-        pos += 4 * d.slab_rows;
-    }
-    d.stride = (pos + 15) & ~(int64_t)15;
-    d.key_kind = s->key_kind;
-    d.key_len = s->key_kind == HS_STR ? s->key_bytes : 0;
-    ok = ok && s->slab.alloc((size_t)d.stride, true);
+    // slab: unit u owns rows [u * cap, (u + 1) * cap); zero-filled
+    const int64_t slab_bytes = slab_layout(s->desc, slots, s->key_kind, s->key_bytes, P.spec);
+    ok = ok && s->slab.alloc((size_t)slab_bytes, true);
     s->fin = P.fin;
-    pos = 16;
-    for (int o = 0; o < s->fin.n_out; ++o) {
-        hs_finish_out& out = s->fin.outs[o];
-        const int width = out.src == 0 ? s->key_bytes : (out.kind == HS_I64 ? 8 : 4);
-        out.offset = pos;
-        pos = (pos + (int64_t)s->merge_cap * width + 15) & ~(int64_t)15;
-    }
-    s->image_bytes = pos;
-    if (s->image_host) (void)hipHostFree(s->image_host);
-    s->image_host = s->image_dev = nullptr;
-    ok = ok && hipHostMalloc(&s->image_host, (size_t)s->image_bytes + kPad, hipHostMallocMapped) == hipSuccess &&
-         hipHostGetDevicePointer(&s->image_dev, s->image_host, 0) == hipSuccess && s->image_dev;
-    if (ok) memset(s->image_host, 0, (size_t)s->image_bytes + kPad);
+    s->image_bytes = image_layout(s->fin, s->key_bytes, s->merge_cap);
+    ok = ok && image_alloc(s->image_host, &s->image_dev, s->image_bytes);
     ok = ok && s->scratch.alloc(hs_agg_finish_scratch_bytes(s->merge_cap, s->fin.n_fold), true);
     if (!ok) {
         hs_set_error("hs_join_stage: out of device / pinned memory");
@@ -1993,36 +2076,9 @@ extern "C" int hs_join_stage_run(hs_join_stage* s, void* stream, uint32_t* flags
         int rc = HS_OK;
         if (!s->ready) rc = join_prepare_aggregate(s);
         if (rc) return rc;
-        if (s->capture) {
-            rc = hs_capture_replay(s->capture, stream);
-            ++s->replays;
-        } else {
-            const bool record = s->runs >= 1;
-            if (record) rc = hs_capture_begin();
-            if (!rc) rc = join_launch(s, stream);
-            if (record) {
-                int32_t n_ops = 0;
-                void* handle = nullptr;
-                const int rc2 = hs_capture_end(&handle, &n_ops);
-                if (!rc && !rc2 && n_ops > 0) s->capture = handle;
-                else if (handle) hs_capture_free(handle);
-            }
-        }
+        rc = run_or_replay(s->capture, s->runs, s->replays, stream, [&]() { return join_launch(s, stream); });
+        if (!rc) rc = wait_result("hs_join_stage_run", s->image_host, s->merge_cap, stream, &s->last_flags, &s->last_rows);
         if (rc) return rc;
-        volatile uint32_t* done = (volatile uint32_t*)s->image_host + 1;
-        for (int64_t spins = 0; *done == 0; ++spins) {
-            if (spins > 2000000) {
-                if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || *done == 0) {
-                    hs_set_error("hs_join_stage_run: the finish launch did not hand its result over");
-                    return HS_E_LAUNCH;
-                }
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        s->last_flags = *(volatile uint32_t*)s->image_host;
-        const int64_t n = *(volatile int64_t*)((char*)s->image_host + 8);
-        s->last_rows = n < s->merge_cap ? n : s->merge_cap;
-        *done = 0;
         ++s->runs;
         if (s->last_flags & HS_FLAG_JOIN_DUP) {
             hs_set_error("hs_join_stage_run: the build side holds a key twice: not a primary-key / foreign-key join (use hs_join_build / count / fill)");
@@ -2064,78 +2120,6 @@ extern "C" int hs_join_stage_stats(const hs_join_stage* s, int64_t* stats) {
     return HS_OK;
 }
 
-namespace {
-
-// A result image as a BlockFile (tasks.py:400-410, io.py:47-109): one block for the on-chip path (rows_per_block 0), blocks of
-// rows_per_block rows for the HBM tier; a key of dictionary codes (dict != NULL) is decoded through the dictionary.  `who`
-// names the entry point in errors.
-int write_image_blockfile(const char* who, const char* path, const hs_finish_spec& fin, const int32_t* out_types,
-                          const char (*out_names)[64], const void* image_host, int64_t last_rows, int key_kind, int key_bytes,
-                          const std::vector<std::string>* dict, int64_t rows_per_block) {
-    if (last_rows == 0) return HS_OK;  // empty result: the reference writes no file (tasks.py:405)
-    FILE* f = fopen(path, "wb");
-    if (!f) {
-        hs_set_error("%s: cannot create %s", who, path);
-        return HS_E_ARG;
-    }
-    const int n_out = fin.n_out;
-    const uint8_t nc = (uint8_t)n_out;
-    fwrite(&nc, 1, 1, f);
-    for (int o = 0; o < n_out; ++o) {
-        const uint8_t type = (uint8_t)out_types[o];
-        const uint8_t len = (uint8_t)strnlen(out_names[o], 64);
-        fwrite(&type, 1, 1, f);
-        fwrite(&len, 1, 1, f);
-        fwrite(out_names[o], 1, len, f);
-    }
-    if (rows_per_block < 1) rows_per_block = last_rows;
-    std::vector<uint64_t> starts;
-    bool ok = true;
-    for (int64_t lo = 0; lo < last_rows; lo += rows_per_block) {  // a result larger than a block continues in further blocks
-        const uint32_t rows = (uint32_t)(lo + rows_per_block < last_rows ? rows_per_block : last_rows - lo);
-        starts.push_back((uint64_t)ftell(f));
-        fwrite(&rows, 4, 1, f);
-        for (int o = 0; o < n_out; ++o) {
-            const hs_finish_out& d = fin.outs[o];
-            const int width = d.src == 0 ? key_bytes : (d.kind == HS_I64 ? 8 : 4);
-            const uint8_t* col = (const uint8_t*)image_host + d.offset + (size_t)lo * (size_t)width;
-            if (d.src == 0 && dict) {  // code bytes -> the strings they stand for
-                uint64_t bytes = rows;
-                for (uint32_t r = 0; r < rows; ++r) {
-                    if (col[r] >= dict->size()) ok = false;
-                    else bytes += (*dict)[col[r]].size();
-                }
-                fwrite(&bytes, 8, 1, f);
-                for (uint32_t r = 0; ok && r < rows; ++r) {
-                    const uint8_t len = (uint8_t)(*dict)[col[r]].size();
-                    fwrite(&len, 1, 1, f);
-                }
-                for (uint32_t r = 0; ok && r < rows; ++r) fwrite((*dict)[col[r]].data(), 1, (*dict)[col[r]].size(), f);
-                continue;
-            }
-            const bool is_key_string = d.src == 0 && key_kind == HS_STR;
-            const uint64_t bytes = (uint64_t)rows * (uint64_t)width + (is_key_string ? rows : 0);
-            fwrite(&bytes, 8, 1, f);
-            if (is_key_string) {
-                const std::vector<uint8_t> lens(rows, (uint8_t)width);
-                fwrite(lens.data(), 1, rows, f);
-            }
-            fwrite(col, 1, (size_t)rows * (size_t)width, f);
-        }
-    }
-    fwrite(starts.data(), 8, starts.size(), f);
-    const uint32_t nblocks = (uint32_t)starts.size();
-    fwrite(&nblocks, 4, 1, f);
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) {
-        hs_set_error("%s: write to %s failed (or a key code outside the dictionary)", who, path);
-        return HS_E_ARG;
-    }
-    return HS_OK;
-}
-
-}  // namespace
-
 // The result as a one-block BlockFile (tasks.py:400-410, io.py:47-109).  A key that is the build-side column arrives as
 // code bytes: decoded through the stage's dictionary here.
 extern "C" int hs_join_result_write_blockfile(const hs_join_stage* s, const char* path) {
@@ -2146,6 +2130,113 @@ extern "C" int hs_join_result_write_blockfile(const hs_join_stage* s, const char
     return write_image_blockfile("hs_join_result_write_blockfile", path, s->fin, s->plan.out_types, s->plan.out_names, s->image_host,
                                  s->last_rows, s->key_kind, s->key_bytes, s->key_is_payload ? &s->dict : nullptr);
 }
+
+// ---- what the stages that write rows share: the surviving rows of a WHERE, a column gathered through a row list ------------
+namespace {
+
+__global__ void __launch_bounds__(256) k_js_iota(int64_t* out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = i;
+}
+
+int grid_of(int64_t n) {
+    const int64_t g = (n + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+bool read_i64(hipStream_t stream, const void* dev, int64_t& out) {
+    return hipMemcpyAsync(&out, dev, 8, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+}
+
+// the rows of one side the WHERE keeps, ascending (every row without a WHERE) -> rows (int64), n_kept
+int side_rows(hipStream_t stream, const hs_col* cols, int32_t n_cols, const hs_program& filter, int64_t n, DevBuf& rows,
+              int64_t& kept, uint32_t* flags) {
+    kept = n;
+    if (!rows.alloc((size_t)(n > 0 ? n : 1) * 8)) return HS_E_LAUNCH;
+    if (n == 0) return HS_OK;
+    if (filter.n_ins == 0) {
+        hipLaunchKernelGGL(k_js_iota, dim3(grid_of(n)), dim3(256), 0, stream, (int64_t*)rows.p, n);
+        return hipGetLastError() == hipSuccess ? HS_OK : HS_E_LAUNCH;
+    }
+    DevBuf mask, count, ws;
+    if (!mask.alloc((size_t)n) || !count.alloc(8) || !ws.alloc(hs_scan_ws_bytes(n))) return HS_E_LAUNCH;
+    void* outs[1] = {mask.p};
+    const int32_t kinds[1] = {HS_U8};
+    int rc = hs_eval(stream, cols, n_cols, &filter, nullptr, n, nullptr, outs, kinds, 1, flags);
+    if (!rc) rc = hs_compact(stream, (const uint8_t*)mask.p, n, (int64_t*)rows.p, (int64_t*)count.p, ws.p);
+    if (rc) return rc;
+    return read_i64(stream, count.p, kept) ? HS_OK : HS_E_LAUNCH;
+}
+
+// column c at rows idx[0 .. n) as a new device column (strings: lens, offsets, payload); out describes it
+int gather_col(hipStream_t stream, const hs_col& c, int64_t src_rows, const int64_t* idx, int64_t n, DevBuf& data, DevBuf& lens,
+               DevBuf& offs, hs_col& out, int64_t& payload, uint32_t* flags) {
+    payload = 0;
+    if (c.kind != HS_STR) {
+        const int w = elem_bytes(c.kind);
+        if (!data.alloc((size_t)(n > 0 ? n : 1) * (size_t)w)) return HS_E_LAUNCH;
+        out = hs_col{c.kind, -1, data.p, nullptr, nullptr};
+        return n > 0 ? hs_gather_fixed(stream, c.data, w, src_rows, idx, n, nullptr, data.p, flags) : HS_OK;
+    }
+    DevBuf mm, ws;
+    if (!lens.alloc((size_t)(n > 0 ? n : 1)) || !offs.alloc((size_t)(n + 1) * 8, true) || !mm.alloc(8)) return HS_E_LAUNCH;
+    if (n > 0) {
+        if (!ws.alloc(hs_scan_ws_bytes(n))) return HS_E_LAUNCH;
+        int rc = hs_gather_str_lens(stream, &c, src_rows, idx, n, (uint8_t*)lens.p, flags);
+        if (!rc) rc = hs_str_offsets(stream, (const uint8_t*)lens.p, n, (int64_t*)offs.p, (int32_t*)mm.p, ws.p);
+        if (rc) return rc;
+        if (!read_i64(stream, (const int64_t*)offs.p + n, payload)) return HS_E_LAUNCH;
+    }
+    if (!data.alloc((size_t)(payload > 0 ? payload : 1))) return HS_E_LAUNCH;
+    out = hs_col{HS_STR, -1, data.p, (const uint8_t*)lens.p, (const int64_t*)offs.p};
+    return n > 0 ? hs_gather_str_bytes(stream, &c, src_rows, idx, n, (const int64_t*)offs.p, (uint8_t*)data.p) : HS_OK;
+}
+
+// column c at rows idx[0 .. n) as a result column on the host (the stream is idle afterwards)
+int gather_to_host(hipStream_t stream, const hs_col& c, int64_t src_rows, const int64_t* idx, int64_t n, HostCol& out, uint32_t* flags) {
+    DevBuf data, lens, offs;
+    hs_col g{};
+    int64_t payload = 0;
+    const int rc = gather_col(stream, c, src_rows, idx, n, data, lens, offs, g, payload, flags);
+    if (rc) return rc;
+    if (c.kind != HS_STR) {
+        out.width = elem_bytes(c.kind);
+        out.data.resize((size_t)n * (size_t)out.width);
+    } else {
+        out.width = -1;
+        out.lens.resize((size_t)n);
+        out.data.resize((size_t)payload);
+        if (hipMemcpyAsync(out.lens.data(), lens.p, (size_t)n, hipMemcpyDeviceToHost, stream) != hipSuccess) return HS_E_LAUNCH;
+    }
+    if ((!out.data.empty() && hipMemcpyAsync(out.data.data(), data.p, out.data.size(), hipMemcpyDeviceToHost, stream) != hipSuccess) ||
+        hipStreamSynchronize(stream) != hipSuccess)
+        return HS_E_LAUNCH;
+    return HS_OK;
+}
+
+// The two tables of a join stage (0 build, 1 probe): every column id in need[side] names a column, the join keys are both
+// INTEGER or both STRING, the columns are on the device.  `who` names the entry point in the errors
+int join_sides_load(const char* who, hs_engine* e, hs_table* const tables[2], const std::vector<int32_t> need[2], int32_t build_key_col,
+                    int32_t probe_key_col) {
+    for (int side = 0; side < 2; ++side)
+        for (int32_t c : need[side])
+            if (c < 0 || c >= (int)tables[side]->cols.size()) {
+                hs_set_error("%s: no such column %d in the %s table", who, c, side ? "probe" : "build");
+                return HS_E_ARG;
+            }
+    const int32_t bt = tables[0]->cols[build_key_col].type, pt = tables[1]->cols[probe_key_col].type;
+    if (bt != pt || (bt != 0 && bt != 1)) {
+        hs_set_error("%s: join keys must be both INTEGER or both STRING (types %d, %d)", who, bt, pt);
+        return HS_E_LIMIT;
+    }
+    if (hipSetDevice(e->device) != hipSuccess) return HS_E_LAUNCH;
+    for (int side = 0; side < 2; ++side) {
+        const int rc = hs_table_load(e, tables[side], need[side].data(), (int32_t)need[side].size());
+        if (rc) return rc;
+    }
+    return HS_OK;
+}
+
+}  // namespace
 
 // =====================================================================================================================
 // Round 3: the SELECT / WHERE stage behind the same boundary - a ScanJob whose rows go to the result file
@@ -2159,12 +2250,7 @@ struct hs_select_stage {
     hs_table* table = nullptr;
     hs_select_stage_plan plan{};
     hs_col cols[HS_MAX_COLS]{}, pcols[HS_MAX_COLS]{};
-    // last result, host side: per output column the stored values (strings: lens + payload)
-    struct Out {
-        std::vector<uint8_t> data, lens;
-        int width = 0;
-    };
-    std::vector<Out> outs;
+    std::vector<HostCol> outs;  // last result, host side: per output column the stored values
     int64_t last_rows = 0;
     uint32_t last_flags = 0;
 };
@@ -2221,21 +2307,12 @@ extern "C" int hs_select_stage_run(hs_select_stage* s, void* stream_, uint32_t* 
     if (hipMemsetAsync(flags, 0, 4, stream) != hipSuccess) return HS_E_LAUNCH;
     int rc = HS_OK;
     // WHERE: mask -> ascending list of the surviving rows
-    DevBuf mask, sel, count, scan_ws;
+    DevBuf sel, all_rows;  // all_rows: every row, for the gathers of a STRING column without a WHERE (made once per run)
     int64_t kept = n;
     const bool filtered = P.filter.n_ins > 0;
     if (filtered && n > 0) {
-        if (!mask.alloc((size_t)n) || !sel.alloc((size_t)n * 8) || !count.alloc(8) || !scan_ws.alloc(hs_scan_ws_bytes(n))) {
-            hs_set_error("hs_select_stage_run: out of device memory");
-            return HS_E_LAUNCH;
-        }
-        void* outs[1] = {mask.p};
-        const int32_t kinds[1] = {HS_U8};
-        rc = hs_eval(stream, s->cols, P.n_cols, &P.filter, nullptr, n, nullptr, outs, kinds, 1, flags);
-        if (!rc) rc = hs_compact(stream, (const uint8_t*)mask.p, n, (int64_t*)sel.p, (int64_t*)count.p, scan_ws.p);
+        rc = side_rows(stream, s->cols, P.n_cols, P.filter, n, sel, kept, flags);
         if (rc) return rc;
-        if (hipMemcpyAsync(&kept, count.p, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-            return HS_E_LAUNCH;
     }
     const int64_t* rows = filtered && n > 0 ? (const int64_t*)sel.p : nullptr;
     // computed columns over the surviving rows (in-flight f64 / i64), then rounded to what the file stores
@@ -2259,9 +2336,9 @@ extern "C" int hs_select_stage_run(hs_select_stage* s, void* stream_, uint32_t* 
         if (rc) return rc;
     }
     // every output column -> host
-    s->outs.assign((size_t)P.n_out, hs_select_stage::Out());
+    s->outs.assign((size_t)P.n_out, HostCol());
     for (int o = 0; o < P.n_out && kept > 0; ++o) {
-        hs_select_stage::Out& out = s->outs[(size_t)o];
+        HostCol& out = s->outs[(size_t)o];
         const int src = P.out_src[o];
         if (src < 0) {
             out.width = 4;
@@ -2270,53 +2347,21 @@ extern "C" int hs_select_stage_run(hs_select_stage* s, void* stream_, uint32_t* 
             continue;
         }
         const hs_col& c = t->cols[src].col;
-        if (c.kind != HS_STR) {
-            const int w = elem_bytes(c.kind);
-            out.width = w;
-            out.data.resize((size_t)kept * (size_t)w);
-            if (!rows) {
-                if (hipMemcpyAsync(out.data.data(), c.data, out.data.size(), hipMemcpyDeviceToHost, stream) != hipSuccess) return HS_E_LAUNCH;
-            } else {
-                DevBuf g;
-                if (!g.alloc(out.data.size())) return HS_E_LAUNCH;
-                rc = hs_gather_fixed(stream, c.data, w, n, rows, kept, nullptr, g.p, flags);
-                if (rc) return rc;
-                if (hipMemcpyAsync(out.data.data(), g.p, out.data.size(), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                    hipStreamSynchronize(stream) != hipSuccess)
-                    return HS_E_LAUNCH;
-            }
+        if (c.kind != HS_STR && !rows) {  // no WHERE: the column as loaded
+            out.width = elem_bytes(c.kind);
+            out.data.resize((size_t)kept * (size_t)out.width);
+            if (hipMemcpyAsync(out.data.data(), c.data, out.data.size(), hipMemcpyDeviceToHost, stream) != hipSuccess) return HS_E_LAUNCH;
             continue;
         }
-        // STRING: lengths, offsets, bytes of the surviving rows
-        DevBuf lens, offs, mm, ws, data;
-        if (!lens.alloc((size_t)kept) || !offs.alloc((size_t)(kept + 1) * 8) || !mm.alloc(8) || !ws.alloc(hs_scan_ws_bytes(kept))) return HS_E_LAUNCH;
-        std::vector<int64_t> iota;
-        DevBuf all_rows;
         const int64_t* idx = rows;
-        if (!idx) {  // no WHERE: the gathers still want a row list
-            iota.resize((size_t)kept);
-            for (int64_t i = 0; i < kept; ++i) iota[(size_t)i] = i;
-            if (!all_rows.alloc((size_t)kept * 8) || hipMemcpy(all_rows.p, iota.data(), (size_t)kept * 8, hipMemcpyHostToDevice) != hipSuccess)
-                return HS_E_LAUNCH;
+        if (!idx) {  // no WHERE: the gathers of a STRING column still want a row list
+            int64_t n_all = 0;
+            if (!all_rows.p) rc = side_rows(stream, s->cols, P.n_cols, P.filter, n, all_rows, n_all, flags);
+            if (rc) return rc;
             idx = (const int64_t*)all_rows.p;
         }
-        rc = hs_gather_str_lens(stream, &c, n, idx, kept, (uint8_t*)lens.p, flags);
-        if (!rc) rc = hs_str_offsets(stream, (const uint8_t*)lens.p, kept, (int64_t*)offs.p, (int32_t*)mm.p, ws.p);
+        rc = gather_to_host(stream, c, n, idx, kept, out, flags);
         if (rc) return rc;
-        int64_t total = 0;
-        if (hipMemcpyAsync(&total, (const int64_t*)offs.p + kept, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess)
-            return HS_E_LAUNCH;
-        if (!data.alloc((size_t)(total > 0 ? total : 1))) return HS_E_LAUNCH;
-        rc = hs_gather_str_bytes(stream, &c, n, idx, kept, (const int64_t*)offs.p, (uint8_t*)data.p);
-        if (rc) return rc;
-        out.width = -1;
-        out.lens.resize((size_t)kept);
-        out.data.resize((size_t)total);
-        if (hipMemcpyAsync(out.lens.data(), lens.p, (size_t)kept, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            (total > 0 && hipMemcpyAsync(out.data.data(), data.p, (size_t)total, hipMemcpyDeviceToHost, stream) != hipSuccess) ||
-            hipStreamSynchronize(stream) != hipSuccess)
-            return HS_E_LAUNCH;
     }
     uint32_t f = 0;
     if (hipMemcpyAsync(&f, flags, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return HS_E_LAUNCH;
@@ -2334,54 +2379,8 @@ extern "C" int hs_select_result_write_blockfile(const hs_select_stage* s, const 
         hs_set_error("hs_select_result_write_blockfile: bad arguments");
         return HS_E_ARG;
     }
-    if (s->last_rows == 0) return HS_OK;
-    FILE* f = fopen(path, "wb");
-    if (!f) {
-        hs_set_error("hs_select_result_write_blockfile: cannot create %s", path);
-        return HS_E_ARG;
-    }
-    const hs_select_stage_plan& P = s->plan;
-    const uint8_t nc = (uint8_t)P.n_out;
-    fwrite(&nc, 1, 1, f);
-    for (int o = 0; o < P.n_out; ++o) {
-        const uint8_t type = (uint8_t)P.out_types[o];
-        const uint8_t len = (uint8_t)strnlen(P.out_names[o], sizeof(P.out_names[o]));
-        fwrite(&type, 1, 1, f);
-        fwrite(&len, 1, 1, f);
-        fwrite(P.out_names[o], 1, len, f);
-    }
-    std::vector<uint64_t> starts;
-    std::vector<int64_t> str_pos((size_t)P.n_out, 0);  // byte position inside a string column's payload
-    for (int64_t lo = 0; lo < s->last_rows; lo += rows_per_block) {
-        const int64_t hi = lo + rows_per_block < s->last_rows ? lo + rows_per_block : s->last_rows;
-        const uint32_t rows = (uint32_t)(hi - lo);
-        starts.push_back((uint64_t)ftell(f));
-        fwrite(&rows, 4, 1, f);
-        for (int o = 0; o < P.n_out; ++o) {
-            const hs_select_stage::Out& out = s->outs[(size_t)o];
-            if (out.width > 0) {
-                const uint64_t bytes = (uint64_t)rows * (uint64_t)out.width;
-                fwrite(&bytes, 8, 1, f);
-                fwrite(out.data.data() + (size_t)lo * (size_t)out.width, 1, (size_t)bytes, f);
-            } else {
-                uint64_t payload = 0;
-                for (int64_t r = lo; r < hi; ++r) payload += out.lens[(size_t)r];
-                const uint64_t bytes = rows + payload;
-                fwrite(&bytes, 8, 1, f);
-                fwrite(out.lens.data() + lo, 1, rows, f);
-                fwrite(out.data.data() + str_pos[(size_t)o], 1, (size_t)payload, f);
-                str_pos[(size_t)o] += (int64_t)payload;
-            }
-        }
-    }
-    fwrite(starts.data(), 8, starts.size(), f);
-    const uint32_t nblocks = (uint32_t)starts.size();
-    fwrite(&nblocks, 4, 1, f);
-    if (fclose(f) != 0) {
-        hs_set_error("hs_select_result_write_blockfile: write to %s failed", path);
-        return HS_E_ARG;
-    }
-    return HS_OK;
+    return write_rows_blockfile("hs_select_result_write_blockfile", path, s->plan.n_out, s->plan.out_types, s->plan.out_names, s->outs,
+                                s->last_rows, rows_per_block);
 }
 
 // =====================================================================================================================
@@ -2391,72 +2390,6 @@ extern "C" int hs_select_result_write_blockfile(const hs_select_stage* s, const 
 // hs_partition_perm) -> join (dense / hashed INTEGER, hashed STRING windows, or the global table) -> pair lists -> gathers
 // of every output column through them -> host -> BlockFile blocks of rows_per_block rows.
 // =====================================================================================================================
-namespace {
-
-__global__ void __launch_bounds__(256) k_js_iota(int64_t* out, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = i;
-}
-
-struct HostCol {  // one result column on the host: fixed-width values, or lens + payload (width -1)
-    std::vector<uint8_t> data, lens;
-    int width = 0;
-};
-
-int grid_of(int64_t n) {
-    const int64_t g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
-
-bool read_i64(hipStream_t stream, const void* dev, int64_t& out) {
-    return hipMemcpyAsync(&out, dev, 8, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-}
-
-// the rows of one side the WHERE keeps, ascending (every row without a WHERE) -> rows (int64), n_kept
-int side_rows(hipStream_t stream, const hs_col* cols, int32_t n_cols, const hs_program& filter, int64_t n, DevBuf& rows,
-              int64_t& kept, uint32_t* flags) {
-    kept = n;
-    if (!rows.alloc((size_t)(n > 0 ? n : 1) * 8)) return HS_E_LAUNCH;
-    if (n == 0) return HS_OK;
-    if (filter.n_ins == 0) {
-        hipLaunchKernelGGL(k_js_iota, dim3(grid_of(n)), dim3(256), 0, stream, (int64_t*)rows.p, n);
-        return hipGetLastError() == hipSuccess ? HS_OK : HS_E_LAUNCH;
-    }
-    DevBuf mask, count, ws;
-    if (!mask.alloc((size_t)n) || !count.alloc(8) || !ws.alloc(hs_scan_ws_bytes(n))) return HS_E_LAUNCH;
-    void* outs[1] = {mask.p};
-    const int32_t kinds[1] = {HS_U8};
-    int rc = hs_eval(stream, cols, n_cols, &filter, nullptr, n, nullptr, outs, kinds, 1, flags);
-    if (!rc) rc = hs_compact(stream, (const uint8_t*)mask.p, n, (int64_t*)rows.p, (int64_t*)count.p, ws.p);
-    if (rc) return rc;
-    return read_i64(stream, count.p, kept) ? HS_OK : HS_E_LAUNCH;
-}
-
-// column c at rows idx[0 .. n) as a new device column (strings: lens, offsets, payload); out describes it
-int gather_col(hipStream_t stream, const hs_col& c, int64_t src_rows, const int64_t* idx, int64_t n, DevBuf& data, DevBuf& lens,
-               DevBuf& offs, hs_col& out, int64_t& payload, uint32_t* flags) {
-    payload = 0;
-    if (c.kind != HS_STR) {
-        const int w = elem_bytes(c.kind);
-        if (!data.alloc((size_t)(n > 0 ? n : 1) * (size_t)w)) return HS_E_LAUNCH;
-        out = hs_col{c.kind, -1, data.p, nullptr, nullptr};
-        return n > 0 ? hs_gather_fixed(stream, c.data, w, src_rows, idx, n, nullptr, data.p, flags) : HS_OK;
-    }
-    DevBuf mm, ws;
-    if (!lens.alloc((size_t)(n > 0 ? n : 1)) || !offs.alloc((size_t)(n + 1) * 8, true) || !mm.alloc(8)) return HS_E_LAUNCH;
-    if (n > 0) {
-        if (!ws.alloc(hs_scan_ws_bytes(n))) return HS_E_LAUNCH;
-        int rc = hs_gather_str_lens(stream, &c, src_rows, idx, n, (uint8_t*)lens.p, flags);
-        if (!rc) rc = hs_str_offsets(stream, (const uint8_t*)lens.p, n, (int64_t*)offs.p, (int32_t*)mm.p, ws.p);
-        if (rc) return rc;
-        if (!read_i64(stream, (const int64_t*)offs.p + n, payload)) return HS_E_LAUNCH;
-    }
-    if (!data.alloc((size_t)(payload > 0 ? payload : 1))) return HS_E_LAUNCH;
-    out = hs_col{HS_STR, -1, data.p, (const uint8_t*)lens.p, (const int64_t*)offs.p};
-    return n > 0 ? hs_gather_str_bytes(stream, &c, src_rows, idx, n, (const int64_t*)offs.p, (uint8_t*)data.p) : HS_OK;
-}
-
-}  // namespace
-
 struct hs_join_select_stage {
     hs_engine* engine = nullptr;
     hs_table *build = nullptr, *probe = nullptr;
@@ -2486,23 +2419,8 @@ extern "C" int hs_join_select_stage_prepare(hs_engine* e, hs_table* build, hs_ta
         }
         need[plan->out_side[o]].push_back(plan->out_col[o]);
     }
-    hs_table* tables[2] = {build, probe};
-    for (int side = 0; side < 2; ++side)
-        for (int32_t c : need[side])
-            if (c < 0 || c >= (int)tables[side]->cols.size()) {
-                hs_set_error("hs_join_select_stage_prepare: no such column %d in the %s table", c, side ? "probe" : "build");
-                return HS_E_ARG;
-            }
-    const int32_t bt = build->cols[plan->build_key_col].type, pt = probe->cols[plan->probe_key_col].type;
-    if (bt != pt || (bt != 0 && bt != 1)) {
-        hs_set_error("hs_join_select_stage_prepare: join keys must be both INTEGER or both STRING (types %d, %d)", bt, pt);
-        return HS_E_LIMIT;
-    }
-    if (hipSetDevice(e->device) != hipSuccess) return HS_E_LAUNCH;
-    for (int side = 0; side < 2; ++side) {
-        const int rc = hs_table_load(e, tables[side], need[side].data(), (int32_t)need[side].size());
-        if (rc) return rc;
-    }
+    hs_table* const tables[2] = {build, probe};
+    if (const int rc = join_sides_load("hs_join_select_stage_prepare", e, tables, need, plan->build_key_col, plan->probe_key_col)) return rc;
     hs_join_select_stage* s = new hs_join_select_stage();
     s->engine = e;
     s->build = build;
@@ -2686,24 +2604,8 @@ extern "C" int hs_join_select_stage_run(hs_join_select_stage* s, void* stream_, 
     for (int o = 0; o < P.n_out && n_out > 0; ++o) {
         hs_table* t = P.out_side[o] ? s->probe : s->build;
         const hs_col& c = t->cols[P.out_col[o]].col;
-        DevBuf data, lens, offs;
-        hs_col g{};
-        int64_t payload = 0;
-        rc = gather_col(stream, c, t->nrows, (const int64_t*)(P.out_side[o] ? R.pidx.p : R.bidx.p), n_out, data, lens, offs, g, payload, flags);
+        rc = gather_to_host(stream, c, t->nrows, (const int64_t*)(P.out_side[o] ? R.pidx.p : R.bidx.p), n_out, s->outs[(size_t)o], flags);
         if (rc) return rc;
-        HostCol& out = s->outs[(size_t)o];
-        if (c.kind != HS_STR) {
-            out.width = elem_bytes(c.kind);
-            out.data.resize((size_t)n_out * (size_t)out.width);
-        } else {
-            out.width = -1;
-            out.lens.resize((size_t)n_out);
-            out.data.resize((size_t)payload);
-            if (hipMemcpyAsync(out.lens.data(), lens.p, (size_t)n_out, hipMemcpyDeviceToHost, stream) != hipSuccess) return HS_E_LAUNCH;
-        }
-        if ((!out.data.empty() && hipMemcpyAsync(out.data.data(), data.p, out.data.size(), hipMemcpyDeviceToHost, stream) != hipSuccess) ||
-            hipStreamSynchronize(stream) != hipSuccess)
-            return HS_E_LAUNCH;
     }
     uint32_t f = 0;
     if (hipMemcpyAsync(&f, flags, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return HS_E_LAUNCH;
@@ -2736,54 +2638,8 @@ extern "C" int hs_join_select_result_write_blockfile(const hs_join_select_stage*
         hs_set_error("hs_join_select_result_write_blockfile: bad arguments");
         return HS_E_ARG;
     }
-    if (s->last_rows == 0) return HS_OK;
-    FILE* f = fopen(path, "wb");
-    if (!f) {
-        hs_set_error("hs_join_select_result_write_blockfile: cannot create %s", path);
-        return HS_E_ARG;
-    }
-    const hs_join_select_stage_plan& P = s->plan;
-    const uint8_t nc = (uint8_t)P.n_out;
-    fwrite(&nc, 1, 1, f);
-    for (int o = 0; o < P.n_out; ++o) {
-        const uint8_t type = (uint8_t)P.out_types[o];
-        const uint8_t len = (uint8_t)strnlen(P.out_names[o], sizeof(P.out_names[o]));
-        fwrite(&type, 1, 1, f);
-        fwrite(&len, 1, 1, f);
-        fwrite(P.out_names[o], 1, len, f);
-    }
-    std::vector<uint64_t> starts;
-    std::vector<int64_t> str_pos((size_t)P.n_out, 0);
-    for (int64_t lo = 0; lo < s->last_rows; lo += rows_per_block) {
-        const int64_t hi = lo + rows_per_block < s->last_rows ? lo + rows_per_block : s->last_rows;
-        const uint32_t rows = (uint32_t)(hi - lo);
-        starts.push_back((uint64_t)ftell(f));
-        fwrite(&rows, 4, 1, f);
-        for (int o = 0; o < P.n_out; ++o) {
-            const HostCol& out = s->outs[(size_t)o];
-            if (out.width > 0) {
-                const uint64_t bytes = (uint64_t)rows * (uint64_t)out.width;
-                fwrite(&bytes, 8, 1, f);
-                fwrite(out.data.data() + (size_t)lo * (size_t)out.width, 1, (size_t)bytes, f);
-            } else {
-                uint64_t payload = 0;
-                for (int64_t r = lo; r < hi; ++r) payload += out.lens[(size_t)r];
-                const uint64_t bytes = rows + payload;
-                fwrite(&bytes, 8, 1, f);
-                fwrite(out.lens.data() + lo, 1, rows, f);
-                fwrite(out.data.data() + str_pos[(size_t)o], 1, (size_t)payload, f);
-                str_pos[(size_t)o] += (int64_t)payload;
-            }
-        }
-    }
-    fwrite(starts.data(), 8, starts.size(), f);
-    const uint32_t nblocks = (uint32_t)starts.size();
-    fwrite(&nblocks, 4, 1, f);
-    if (fclose(f) != 0) {
-        hs_set_error("hs_join_select_result_write_blockfile: write to %s failed", path);
-        return HS_E_ARG;
-    }
-    return HS_OK;
+    return write_rows_blockfile("hs_join_select_result_write_blockfile", path, s->plan.n_out, s->plan.out_types, s->plan.out_names,
+                                s->outs, s->last_rows, rows_per_block);
 }
 
 // =====================================================================================================================
@@ -2854,23 +2710,8 @@ extern "C" int hs_join_group_stage_prepare(hs_engine* e, hs_table* build, hs_tab
         }
         need[plan->col_side[i]].push_back(plan->col_ids[i]);
     }
-    hs_table* tables[2] = {build, probe};
-    for (int side = 0; side < 2; ++side)
-        for (int32_t c : need[side])
-            if (c < 0 || c >= (int)tables[side]->cols.size()) {
-                hs_set_error("hs_join_group_stage_prepare: no such column %d in the %s table", c, side ? "probe" : "build");
-                return HS_E_ARG;
-            }
-    const int32_t bt = build->cols[plan->build_key_col].type, pt = probe->cols[plan->probe_key_col].type;
-    if (bt != pt || (bt != 0 && bt != 1)) {
-        hs_set_error("hs_join_group_stage_prepare: join keys must be both INTEGER or both STRING (types %d, %d)", bt, pt);
-        return HS_E_LIMIT;
-    }
-    if (hipSetDevice(e->device) != hipSuccess) return HS_E_LAUNCH;
-    for (int side = 0; side < 2; ++side) {
-        const int rc = hs_table_load(e, tables[side], need[side].data(), (int32_t)need[side].size());
-        if (rc) return rc;
-    }
+    hs_table* const tables[2] = {build, probe};
+    if (const int rc = join_sides_load("hs_join_group_stage_prepare", e, tables, need, plan->build_key_col, plan->probe_key_col)) return rc;
     hs_join_group_stage* s = new hs_join_group_stage();
     s->engine = e;
     s->build = build;
@@ -2895,16 +2736,9 @@ extern "C" int hs_join_group_stage_prepare(hs_engine* e, hs_table* build, hs_tab
         kc = hs_col{HS_STR, 1, s->codes.p, nullptr, nullptr};
         s->key_coded = true;
     }
-    if (kc.kind == HS_STR) {
-        s->key_kind = HS_STR;
-        s->key_bytes = kc.fixed_len;
-    } else if (kc.kind == HS_I32 || kc.kind == HS_F32 || kc.kind == HS_I64) {
-        s->key_kind = kc.kind;
-        s->key_bytes = elem_bytes(kc.kind);
-    } else {
+    if (const int rc = group_key_shape("hs_join_group_stage_prepare", kc, s->key_kind, s->key_bytes)) {
         delete s;
-        hs_set_error("hs_join_group_stage_prepare: GROUP BY key is not a stored column kind");
-        return HS_E_LIMIT;
+        return rc;
     }
     *out = s;
     return HS_OK;
@@ -2921,25 +2755,16 @@ int join_group_prepare(hs_join_group_stage* s) {
     const int64_t n_units = P.n_parts;
     int rc = hs_agg_shared_geom(s->unit_rows.data(), n_units, P.spec.n_acc, s->group_cap, &s->geom);
     if (rc) return rc;
-    std::vector<hs_chunk> chunks((size_t)(s->geom.n_chunks > 0 ? s->geom.n_chunks : 1));
-    std::vector<int64_t> chunk0((size_t)n_units + 1, 0);
-    rc = hs_agg_partial_chunks(s->unit_rows.data(), n_units, &s->geom, chunks.data(), chunk0.data());
+    rc = chunks_upload("hs_join_group_stage", s->unit_rows.data(), n_units, s->geom, s->chunks);
     if (rc) return rc;
     s->slots = n_units * (int64_t)s->geom.pad;
     s->fin = P.fin;
     s->image_bytes = image_layout(s->fin, s->key_bytes, s->merge_cap);
-    if (s->image_host) (void)hipHostFree(s->image_host);
-    s->image_host = nullptr;
-    const bool ok = s->chunks.alloc(chunks.size() * sizeof(hs_chunk)) &&
-                    hipMemcpy(s->chunks.p, chunks.data(), chunks.size() * sizeof(hs_chunk), hipMemcpyHostToDevice) == hipSuccess &&
-                    s->ws.alloc(s->geom.ws_bytes, true) && shared_alloc(s->sh, s->slots, n_units, P.spec.n_acc, P.fin.n_fold, s->merge_cap) &&
-                    hipHostMalloc(&s->image_host, (size_t)s->image_bytes + kPad, hipHostMallocDefault) == hipSuccess &&
-                    s->sh.image.alloc((size_t)s->image_bytes, true);
-    if (!ok) {
+    if (!s->ws.alloc(s->geom.ws_bytes, true) || !shared_alloc(s->sh, s->slots, n_units, P.spec.n_acc, P.fin.n_fold, s->merge_cap) ||
+        !image_alloc(s->image_host, nullptr, s->image_bytes) || !s->sh.image.alloc((size_t)s->image_bytes, true)) {
         hs_set_error("hs_join_group_stage: out of device / pinned memory");
         return HS_E_LAUNCH;
     }
-    memset(s->image_host, 0, (size_t)s->image_bytes + kPad);
     s->ready = true;
     return HS_OK;
 }
@@ -3036,11 +2861,7 @@ extern "C" int hs_join_group_stage_run(hs_join_group_stage* s, void* stream_, ui
     const int64_t n_pairs = s->R.J.n_out;
     // past the on-chip tiers with the switch on: the stage moves to the HBM tier and stays there
     auto hbm_enter = [&]() {
-        if (s->image_host) (void)hipHostFree(s->image_host);  // (the on-chip tail's image; this tier's is sized per run)
-        s->image_host = nullptr;
-        s->image_host_cap = 0;
-        s->sh = SharedBufs();
-        s->ws.release();
+        onchip_release(s->image_host, s->image_host_cap, s->sh, s->ws);
         s->chunks.release();
         s->ready = false;
         s->hbm = true;
@@ -3091,28 +2912,13 @@ extern "C" int hs_join_group_stage_run(hs_join_group_stage* s, void* stream_, ui
         }
         if (rc) return rc;
         s->last_tier = 1;
-        if ((f & HS_FLAG_MERGE_ROWS) && s->hbm_on) {
+        const SharedNext next = shared_next("hs_join_group_stage_run", f, s->hbm_on, s->group_cap, s->merge_cap);
+        if (next == SharedNext::limit) return HS_E_LIMIT;
+        if (next == SharedNext::to_hbm) {
             hbm_enter();
             continue;
         }
-        if (f & HS_FLAG_MERGE_ROWS) {
-            hs_set_error("hs_join_group_stage_run: more partial rows than the on-chip final merge holds (the HBM tier belongs to the per-operator ABI)");
-            return HS_E_LIMIT;
-        }
-        if (f & (HS_FLAG_DICT_FULL | HS_FLAG_MERGE_FULL)) {  // as hs_stage_run's shared-dictionary tier
-            const bool unit_full = f & HS_FLAG_DICT_FULL, merge_full = f & HS_FLAG_MERGE_FULL;
-            if (((unit_full && s->group_cap >= 4096) || (merge_full && s->merge_cap >= 4096)) && s->hbm_on) {
-                hbm_enter();
-                continue;
-            }
-            if ((unit_full && s->group_cap >= 4096) || (merge_full && s->merge_cap >= 4096)) {
-                hs_set_error("hs_join_group_stage_run: GROUP BY cardinality exceeds the on-chip tiers of this path");
-                return HS_E_LIMIT;
-            }
-            if (unit_full) s->group_cap *= 4;
-            if (merge_full) s->merge_cap *= 4;
-            if (s->merge_cap < s->group_cap) s->merge_cap = s->group_cap;
-            if (s->merge_cap > 4096) s->merge_cap = 4096;
+        if (next == SharedNext::grown) {
             s->ready = false;
             ++s->grows;
             continue;
