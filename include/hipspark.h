@@ -512,6 +512,31 @@ int hs_join_hash_str_count(void* stream, const hs_col* build_key, const hs_col* 
 size_t hs_sort_by_order_ws_bytes(int64_t n);
 int hs_sort_by_order(void* stream, const int64_t* order, int64_t n, int64_t n_order, int64_t* out_perm, int64_t* out_sorted,
                      void* ws);
+/* ORDER BY / LIMIT over result rows (no reference counterpart: the reference has no ordering).  out_perm[j] = input row
+ * of the j-th output row, *out_count (HOST int64) = min(rows, limit).  The order is lexicographic over keys[0 .. n_keys),
+ * key k ascending or (descending[k] != 0) descending, and STABLE: rows equal on every key keep their input order, for
+ * descending keys too (the key is inverted, the output is never reversed).  With limit >= 0 the result is exactly the
+ * first `limit` entries of that full stable sort.
+ * Keys: HS_I32, HS_I64, HS_F32, HS_F64, HS_U8, HS_STR (any length the column format allows, <= 255 bytes; a dictionary-
+ * coded column passes as HS_STR of fixed length 1 and is ordered by its code byte, i.e. by its strings when the
+ * dictionary is sorted).  Every key becomes a run of bytes whose unsigned order is the wanted order - integers big-endian
+ * with the sign bit flipped; floats with the usual sign-dependent flip, -0.0 as +0.0 (equal in Python: a later key
+ * decides), every NaN after +inf; strings as their bytes, zero-padded to the column's longest, then the length byte (UTF-8
+ * byte order = Python's str order, a prefix sorts before its extensions); descending: all bits inverted - and the runs of
+ * all keys, concatenated, are cut into 64-bit words (two HS_I32 keys share one).  The words are sorted least significant
+ * word and byte first with the radix tier's stable partition passes, carrying (word, row); a byte that is the same in
+ * every row costs no pass.  0 <= limit < rows: a histogram-only radix select over the first word finds the limit-th
+ * smallest word, one ranked compaction keeps the rows at or below it in input order, and only those are sorted.
+ * rows = min(nrows, *nrows_dev) (nrows_dev: device int64, may be null).  n_keys == 0 with limit >= 0: the first rows in
+ * input order.  At most HS_MAX_COLS keys.  The call reads a few words back between its steps (which bytes vary, how
+ * many candidates): it synchronises the stream and must not be captured (hs_capture_begin).
+ * ws: hs_order_by_ws_bytes(nrows, n_keys, max_key_words) bytes; the layout forms one word at a time, so max_key_words
+ * (an upper bound of the words per row) does not enter the size at present.  flags: the device status word of the
+ * other calls; no bit of it is raised at present (may be null). */
+size_t hs_order_by_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words);
+int hs_order_by(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_keys, int64_t nrows,
+                const int64_t* nrows_dev, int64_t limit /* <0: none */, int64_t* out_perm, int64_t* out_count, void* ws,
+                uint32_t* flags);
 /* out[i] = values[s] for bounds[s] <= i < bounds[s+1], i in [0, n) (device arrays; bounds has n_seg + 1 entries,
  * bounds[0] = 0): the global block id of every partial row of a multi-rank partial aggregate. */
 int hs_expand_by_bounds(void* stream, const int64_t* bounds, const int64_t* values, int64_t n_seg, int64_t n, int64_t* out);

@@ -93,7 +93,8 @@ struct RxPass {
     const int64_t* seg_start;  // [n_seg + 1] positions in the row list
     const int64_t* tile_base;  // [n_seg + 1]
     int64_t n_seg;
-    int32_t shift, bits;       // bin = (mix(key word) >> shift) & (2^bits - 1); raw: ((key + 1) >> shift) & ... (hs_sort_by_order)
+    int32_t shift, bits;       // bin = (mix(key word) >> shift) & (2^bits - 1); raw 1: ((key + 1) >> shift) & ... (hs_sort_by_order),
+                               // raw 2: (key >> shift) & ... (hs_order_by)
     int32_t n_cols, first;     // columns that travel (0 = key); first pass reads the key through `key` / `sel`
     int32_t range, range_bias; // range (4-byte keys only): 1: bin = ((key - range_bias) >> shift) & (2^bits - 1) - partitions are KEY RANGES,
                                // most significant bits first (the dense join build); 2: bin = bits of the key's hash WINDOW
@@ -115,7 +116,7 @@ __device__ __forceinline__ uint64_t rx_key(const RxPass& A, int64_t i) {
     return A.esize[0] == 4 ? (uint64_t)(int64_t)((const int32_t*)A.src[0])[i] : ((const uint64_t*)A.src[0])[i];
 }
 __device__ __forceinline__ uint32_t rx_bin(uint64_t word, int shift, int bits, int raw) {
-    return (uint32_t)((raw ? word + 1 : hs_mix64(word)) >> shift) & ((1u << bits) - 1u);
+    return (uint32_t)((raw ? word + (uint64_t)(raw & 1) : hs_mix64(word)) >> shift) & ((1u << bits) - 1u);
 }
 // 4-byte keys: which partition a key lands in only has to be a function of the key that spreads well - one 32-bit multiply
 // and a fold of the high half into the low (the passes take bits 0 .. 15) instead of hs_mix64's 64-bit multiplies, in the
@@ -1699,6 +1700,459 @@ extern "C" int hs_sort_by_order(void* stream_, const int64_t* order, int64_t n, 
         P.bits = bits - 8 * k < 8 ? bits - 8 * k : 8;
         const int rc = rx_pass(stream, P, tiles, counters, scanned, scan_ws, n, nullptr);
         if (rc != HS_OK) return rc;
+    }
+    return HS_OK;
+}
+
+// =====================================================================================================
+// ORDER BY / LIMIT over result rows (include/hipspark.h hs_order_by; the reference has no ordering).
+//
+// Every key column becomes a run of bytes whose unsigned order is the wanted order; the runs of all keys, one after the
+// other, are the row's sort key, cut into 64-bit words (byte 0 of the key = most significant byte of word 0).  The words
+// are sorted least significant first with the stable partition passes above (raw = 2: the bin is a byte of the word),
+// carrying (word, row): k_ob_keys forms ONE word per launch - for rows in place (coalesced) when it is the first word to
+// be sorted, through the row list the earlier words left behind otherwise, which is the gather any multi-word LSD sort
+// pays - so the workspace does not grow with the key's length.  The kernel also folds the AND and the OR of its words: a
+// byte in which they agree is the same in every row, its histogram would have one occupied bin, and its pass is skipped
+// (timestamps, small integers, string padding, the unused tail of the last word).
+//
+// 0 <= limit < rows: k_ob_select / k_ob_pick walk the first word's bytes, most significant first, with one 256-bin
+// histogram of the rows that still match the prefix - nothing is moved - until the limit-th smallest word is known;
+// k_ob_count / k_ob_compact keep the rows at or below it, in input order (ballot ranks inside a wave, a scan over the
+// tiles: no atomics decide a position), and only those rows are sorted.  Rows beyond the cut that tie with it on the first
+// word stay candidates, so the first `limit` rows of the candidates' stable sort are those of the full one.
+// =====================================================================================================
+constexpr int OB_THREADS = 256;
+constexpr int OB_WAVES = OB_THREADS / HS_WAVE;
+constexpr int OB_STEPS = 8;                              // 64-row steps a wave ranks in the compaction
+constexpr int OB_TILE = OB_THREADS * OB_STEPS;           // 2048 rows
+constexpr int OB_MAX_PARTS = 8;                          // a word has 8 bytes: at most 8 keys meet in it
+
+struct ObPart {
+    int32_t key, off, nbytes, pos;  // bytes [off, off + nbytes) of the key's run are bytes [pos, pos + nbytes) of the word (0 = most significant)
+};
+struct ObKeys {
+    hs_col col[HS_MAX_COLS];
+    int32_t width[HS_MAX_COLS];    // bytes of the key's run
+    int32_t str_cap[HS_MAX_COLS];  // HS_STR: bytes of the (zero-padded) string; width = str_cap + 1 when a length byte follows
+    int32_t desc[HS_MAX_COLS];
+    ObPart part[OB_MAX_PARTS];
+    int32_t n_parts, first;        // first: the launch also writes out_rows and the passes' one segment {0, n}
+    const int64_t* rows;           // the rows in their present order (null: position = row)
+    int64_t n;
+    uint64_t* out_words;
+    int64_t* out_rows;
+    unsigned long long* and_or;    // [2]: AND and OR of all words
+    int64_t* seg;
+};
+static_assert(sizeof(ObKeys) % 8 == 0, "ObKeys");
+
+// a numeric cell as an unsigned number of the column's width whose order is the cell's order
+__device__ __forceinline__ uint64_t ob_numeric(const hs_col& c, int64_t row) {
+    switch (c.kind) {
+        case HS_I32: return (uint64_t)(((const uint32_t*)c.data)[row] ^ 0x80000000u);
+        case HS_I64: return ((const uint64_t*)c.data)[row] ^ 0x8000000000000000ull;
+        case HS_F32: {
+            uint32_t b = ((const uint32_t*)c.data)[row];
+            if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;  // every NaN: one value, after +inf
+            if (b == 0x80000000u) b = 0u;                          // -0.0 == +0.0
+            return (uint64_t)((b & 0x80000000u) ? ~b : (b | 0x80000000u));
+        }
+        case HS_F64: {
+            uint64_t b = ((const uint64_t*)c.data)[row];
+            if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) b = 0x7ff8000000000000ull;
+            if (b == 0x8000000000000000ull) b = 0ull;
+            return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+        }
+        default: return (uint64_t)((const uint8_t*)c.data)[row];  // HS_U8
+    }
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_ob_keys(const ObKeys A_kernarg) {
+    HS_KERNARG(ObKeys, A);
+    const int lane = threadIdx.x & (HS_WAVE - 1);
+    unsigned long long all_and = ~0ull, all_or = 0ull;
+    for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * OB_THREADS) {
+        const int64_t row = A.rows ? A.rows[i] : i;
+        uint64_t word = 0;
+        for (int p = 0; p < A.n_parts; ++p) {
+            const ObPart part = A.part[p];
+            const hs_col& c = A.col[part.key];
+            const uint64_t mask = part.nbytes == 8 ? ~0ull : (1ull << (8 * part.nbytes)) - 1ull;
+            uint64_t chunk = 0;
+            if (c.kind == HS_STR) {
+                const HsStr s = hs_str_at(c, row);
+                const uint32_t cap = (uint32_t)A.str_cap[part.key];
+                for (uint32_t j = (uint32_t)part.off; j < (uint32_t)(part.off + part.nbytes); ++j)
+                    chunk = (chunk << 8) | (uint64_t)(j < cap ? (j < s.len ? s.p[j] : 0u) : s.len);
+            } else {
+                chunk = (ob_numeric(c, row) >> (8 * (A.width[part.key] - part.off - part.nbytes))) & mask;
+            }
+            if (A.desc[part.key]) chunk ^= mask;
+            word |= chunk << (8 * (8 - part.pos - part.nbytes));
+        }
+        A.out_words[i] = word;
+        if (A.first) A.out_rows[i] = row;
+        all_and &= word;
+        all_or |= word;
+    }
+    for (int d = HS_WAVE / 2; d > 0; d >>= 1) {
+        all_and &= __shfl_xor(all_and, d, HS_WAVE);
+        all_or |= __shfl_xor(all_or, d, HS_WAVE);
+    }
+    if (lane == 0) {  // two folds per wave of a grid of at most 1024 workgroups; no position depends on them
+        atomicAnd(&A.and_or[0], all_and);
+        atomicOr(&A.and_or[1], all_or);
+    }
+    if (A.first && blockIdx.x == 0 && threadIdx.x == 0) {
+        A.seg[0] = 0;
+        A.seg[1] = A.n;
+    }
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_ob_iota(int64_t* out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * OB_THREADS) out[i] = i;
+}
+
+// the longest string of a variable-length column
+__global__ void __launch_bounds__(OB_THREADS) k_ob_maxlen(const uint8_t* lens, int64_t n, uint32_t* out) {
+    uint32_t m = 0;
+    for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * OB_THREADS)
+        m = lens[i] > m ? lens[i] : m;
+    for (int d = HS_WAVE / 2; d > 0; d >>= 1) {
+        const uint32_t o = __shfl_xor(m, d, HS_WAVE);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & (HS_WAVE - 1)) == 0 && m) atomicMax(out, m);
+}
+
+// selection state: the bytes of the limit-th smallest first word found so far
+struct ObSelect {
+    uint64_t prefix, mask;  // rows still in the race: (word & mask) == prefix
+    int64_t k;              // the word looked for is the k-th smallest (1-based) among them
+};
+
+// one round of the radix select: histogram of byte `shift / 8` over the rows that match the prefix.  Nothing is moved.
+__global__ void __launch_bounds__(OB_THREADS) k_ob_select(const uint64_t* words, int64_t n, const ObSelect* state, int shift,
+                                                          unsigned long long* hist) {
+    __shared__ uint32_t s_hist[OB_WAVES][256];  // one per wave: LDS atomics of different waves never meet
+    const int tid = threadIdx.x, w = tid / HS_WAVE;
+    for (int i = tid; i < OB_WAVES * 256; i += OB_THREADS) s_hist[i >> 8][i & 255] = 0;
+    __syncthreads();
+    const uint64_t prefix = state->prefix, mask = state->mask;
+    for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + tid; i < n; i += (int64_t)gridDim.x * OB_THREADS) {
+        const uint64_t word = words[i];
+        if ((word & mask) == prefix) atomicAdd(&s_hist[w][(uint32_t)(word >> shift) & 0xffu], 1u);
+    }
+    __syncthreads();
+    uint32_t total = 0;
+#pragma unroll
+    for (int k = 0; k < OB_WAVES; ++k) total += s_hist[k][tid];
+    if (total) atomicAdd(&hist[tid], (unsigned long long)total);  // a count, not a rank: the order of the adds is immaterial
+}
+
+// ... and the bin that holds the k-th row: its byte joins the prefix.  One workgroup; clears the histogram for the next round.
+__global__ void __launch_bounds__(256) k_ob_pick(ObSelect* state, int shift, unsigned long long* hist) {
+    __shared__ int64_t s_wave[4];
+    const int tid = threadIdx.x, lane = tid & (HS_WAVE - 1), w = tid / HS_WAVE;
+    const int64_t mine = (int64_t)hist[tid];
+    hist[tid] = 0;
+    int64_t x = mine;
+    for (int d = 1; d < HS_WAVE; d <<= 1) {
+        const int64_t up = __shfl_up(x, d, HS_WAVE);
+        if (lane >= d) x += up;
+    }
+    if (lane == HS_WAVE - 1) s_wave[w] = x;
+    const int64_t k = state->k;
+    const uint64_t prefix = state->prefix, mask = state->mask;
+    __syncthreads();
+    for (int j = 0; j < w; ++j) x += s_wave[j];
+    if (x - mine < k && k <= x) {  // exactly one bin
+        state->prefix = prefix | ((uint64_t)tid << shift);
+        state->mask = mask | (0xffull << shift);
+        state->k = k - (x - mine);
+    }
+}
+
+// rows whose first word is at or below the selected one, per tile ...
+__global__ void __launch_bounds__(OB_THREADS) k_ob_count(const uint64_t* words, int64_t n, const ObSelect* state, int64_t* counts) {
+    __shared__ uint32_t s_cnt[OB_WAVES];
+    const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE;
+    const uint64_t cut = state->prefix;
+    const int64_t first = (int64_t)blockIdx.x * OB_TILE + (int64_t)w * (OB_STEPS * HS_WAVE) + lane;
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < OB_STEPS; ++j) {
+        const int64_t i = first + j * HS_WAVE;
+        c += (uint32_t)__popcll(__ballot(i < n && words[i] <= cut));
+    }
+    if (lane == 0) s_cnt[w] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = (int64_t)s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+// ... and their row numbers in input order: the tile's scanned count, the waves before mine, the steps before this one,
+// the lanes below me
+__global__ void __launch_bounds__(OB_THREADS) k_ob_compact(const uint64_t* words, int64_t n, const ObSelect* state,
+                                                           const int64_t* start, int64_t* out_rows) {
+    __shared__ uint32_t s_cnt[OB_WAVES];
+    const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE;
+    const uint64_t cut = state->prefix;
+    const int64_t first = (int64_t)blockIdx.x * OB_TILE + (int64_t)w * (OB_STEPS * HS_WAVE) + lane;
+    uint64_t bal[OB_STEPS];
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < OB_STEPS; ++j) {
+        const int64_t i = first + j * HS_WAVE;
+        bal[j] = __ballot(i < n && words[i] <= cut);
+        c += (uint32_t)__popcll(bal[j]);
+    }
+    if (lane == 0) s_cnt[w] = c;
+    __syncthreads();
+    int64_t at = start[blockIdx.x];
+    for (int j = 0; j < w; ++j) at += s_cnt[j];
+    const uint64_t below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int j = 0; j < OB_STEPS; ++j) {
+        if ((bal[j] >> lane) & 1ull) out_rows[at + __popcll(bal[j] & below)] = first + j * HS_WAVE;
+        at += __popcll(bal[j]);
+    }
+}
+
+static_assert(OB_WAVES == 4, "k_ob_count adds four wave counts");
+
+static unsigned ob_grid(int64_t n) {
+    const int64_t g = (n + OB_THREADS - 1) / OB_THREADS;
+    return (unsigned)(g > 1024 ? 1024 : (g < 1 ? 1 : g));
+}
+
+extern "C" size_t hs_order_by_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words) {
+    (void)n_keys;
+    (void)max_key_words;
+    if (nrows < 0) return 0;
+    const int64_t tiles = nrows / RX_TILE + 2;
+    return rx_align((size_t)nrows * 8) * 4 + 256 + 256 + rx_align(256 * 8) + rx_align((size_t)(tiles << 8) * 8) +
+           rx_align((size_t)((tiles << 8) + 1) * 8) + rx_align(hs_scan_ws_bytes(tiles << 8));
+}
+
+static bool ob_kind_ok(const hs_col& c) {
+    switch (c.kind) {
+        case HS_I32:
+        case HS_F32:
+        case HS_I64:
+        case HS_F64:
+        case HS_U8: return c.data != nullptr;
+        case HS_STR: return c.fixed_len == 0 || (c.data && c.fixed_len <= 255 && (c.fixed_len > 0 || (c.lens && c.offs)));
+        default: return false;
+    }
+}
+
+extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_keys, int64_t nrows,
+                           const int64_t* nrows_dev, int64_t limit, int64_t* out_perm, int64_t* out_count, void* ws_,
+                           uint32_t* flags) {
+    (void)flags;
+    if (n_keys < 0 || nrows < 0 || !out_perm || !out_count || !ws_ || (n_keys > 0 && (!keys || !descending)) ||
+        (n_keys == 0 && limit < 0)) {
+        hs_set_error("hs_order_by: bad arguments");
+        return HS_E_ARG;
+    }
+    if (n_keys > HS_MAX_COLS) {
+        hs_set_error("hs_order_by: more than %d keys", HS_MAX_COLS);
+        return HS_E_LIMIT;
+    }
+    *out_count = 0;
+    if (nrows == 0 || limit == 0) return HS_OK;
+    for (int k = 0; k < n_keys; ++k)
+        if (!ob_kind_ok(keys[k])) {
+            hs_set_error("hs_order_by: key %d is not a column that can be ordered", k);
+            return HS_E_ARG;
+        }
+    hipStream_t stream = (hipStream_t)stream_;
+    uint8_t* ws = (uint8_t*)ws_;
+    const int64_t tiles_max = nrows / RX_TILE + 2;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        uint8_t* p = ws + off;
+        off += rx_align(bytes);
+        return p;
+    };
+    uint64_t* K[2];
+    int64_t* R[2];
+    K[0] = (uint64_t*)take((size_t)nrows * 8);
+    K[1] = (uint64_t*)take((size_t)nrows * 8);
+    R[0] = (int64_t*)take((size_t)nrows * 8);
+    R[1] = (int64_t*)take((size_t)nrows * 8);
+    unsigned long long* state = (unsigned long long*)take(256);  // [0] AND, [1] OR, [2..4] ObSelect, [5] longest string, [6..7] segment
+    int64_t* tile_base = (int64_t*)take(256);
+    unsigned long long* hist = (unsigned long long*)take(256 * 8);
+    int64_t* counters = (int64_t*)take((size_t)(tiles_max << 8) * 8);
+    int64_t* scanned = (int64_t*)take((size_t)((tiles_max << 8) + 1) * 8);
+    void* scan_ws = take(hs_scan_ws_bytes(tiles_max << 8));
+    ObSelect* select = (ObSelect*)(state + 2);
+    int64_t* seg = (int64_t*)(state + 6);
+
+    auto read_back = [&](void* host, const void* dev, size_t bytes) {
+        return hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+               hipStreamSynchronize(stream) == hipSuccess;
+    };
+    int64_t n = nrows;
+    if (nrows_dev) {
+        int64_t exact = 0;
+        if (!read_back(&exact, nrows_dev, 8)) {
+            hs_set_error("hs_order_by: reading the row count failed");
+            return HS_E_LAUNCH;
+        }
+        n = exact < n ? (exact < 0 ? 0 : exact) : n;
+    }
+    const int64_t count = limit < 0 || limit > n ? n : limit;
+    *out_count = count;
+    if (count == 0) return HS_OK;
+
+    // the key's layout: widths of the runs, then the parts of every word
+    ObKeys A;
+    std::memset(&A, 0, sizeof(A));
+    int64_t total_bytes = 0;
+    for (int k = 0; k < n_keys; ++k) {
+        const hs_col& c = keys[k];
+        A.col[k] = c;
+        A.desc[k] = descending[k] ? 1 : 0;
+        if (c.kind == HS_STR && c.fixed_len < 0) {
+            hs_memset_async(state + 5, 0, 8, stream);
+            hipLaunchKernelGGL(k_ob_maxlen, dim3(ob_grid(n)), dim3(OB_THREADS), 0, stream, c.lens, n, (uint32_t*)(state + 5));
+            RX_CHECK_LAUNCH("hs_order_by (longest string)");
+            uint32_t longest = 0;
+            if (!read_back(&longest, state + 5, 4)) {
+                hs_set_error("hs_order_by: reading the longest string failed");
+                return HS_E_LAUNCH;
+            }
+            A.str_cap[k] = (int32_t)longest;
+            A.width[k] = (int32_t)longest + 1;  // the length byte: a prefix sorts before its extensions
+        } else if (c.kind == HS_STR) {
+            A.str_cap[k] = A.width[k] = c.fixed_len;  // one length: no tie left to break
+        } else {
+            A.width[k] = rx_esize(c.kind);
+        }
+        total_bytes += A.width[k];
+    }
+    const int n_words = (int)((total_bytes + 7) / 8);
+    auto iota_out = [&]() {
+        hipLaunchKernelGGL(k_ob_iota, dim3(ob_grid(count)), dim3(OB_THREADS), 0, stream, out_perm, count);
+        RX_CHECK_LAUNCH("hs_order_by (rows in place)");
+        return HS_OK;
+    };
+    if (n_words == 0) return iota_out();
+
+    // word w of `m` rows (in place, or those of `rows`) -> out_words; -> the bytes of the word that differ between rows
+    auto form = [&](int w, const int64_t* rows, int64_t m, uint64_t* out_words, int64_t* out_rows, uint64_t& and_bits,
+                    uint64_t& varying) {
+        A.n_parts = 0;
+        int64_t at = 0;
+        for (int k = 0; k < n_keys; ++k) {
+            const int64_t b = at > (int64_t)w * 8 ? at : (int64_t)w * 8;
+            const int64_t e = at + A.width[k] < (int64_t)(w + 1) * 8 ? at + A.width[k] : (int64_t)(w + 1) * 8;
+            if (b < e) A.part[A.n_parts++] = ObPart{k, (int32_t)(b - at), (int32_t)(e - b), (int32_t)(b - (int64_t)w * 8)};
+            at += A.width[k];
+        }
+        A.rows = rows;
+        A.n = m;
+        A.out_words = out_words;
+        A.out_rows = out_rows;
+        A.first = out_rows ? 1 : 0;
+        A.and_or = state;
+        A.seg = seg;
+        hs_memset_async(state, 0xff, 8, stream);
+        hs_memset_async(state + 1, 0, 8, stream);
+        hipLaunchKernelGGL(k_ob_keys, dim3(ob_grid(m)), dim3(OB_THREADS), 0, stream, A);
+        RX_CHECK_LAUNCH("hs_order_by (key words)");
+        unsigned long long ao[2] = {0, 0};
+        if (!read_back(ao, state, 16)) {
+            hs_set_error("hs_order_by: reading the key summary failed");
+            return HS_E_LAUNCH;
+        }
+        and_bits = ao[0];
+        varying = ao[0] ^ ao[1];
+        return HS_OK;
+    };
+    // stable sort of m rows (in place, or the list `rows`, which may be K[1]) by all words -> the buffer that holds them
+    auto sort_rows = [&](const int64_t* rows, int64_t m, const int64_t*& sorted) {
+        int cur = 0;
+        RxPass P;
+        std::memset(&P, 0, sizeof(P));
+        P.seg_start = seg;
+        P.tile_base = tile_base;
+        P.n_seg = 1;
+        P.n_cols = 2;
+        P.esize[0] = P.esize[1] = 8;
+        P.raw = 2;
+        P.bits = 8;
+        const int64_t tiles = m / RX_TILE + 2;
+        for (int w = n_words - 1; w >= 0; --w) {
+            const bool first = w == n_words - 1;
+            uint64_t and_bits = 0, varying = 0;
+            int rc = form(w, first ? rows : R[cur], m, K[cur], first ? R[cur] : nullptr, and_bits, varying);
+            if (rc != HS_OK) return rc;
+            for (int b = 0; b < 8; ++b) {
+                if (((varying >> (8 * b)) & 0xffull) == 0) continue;  // one occupied bin: the pass would move nothing
+                P.src[0] = K[cur];
+                P.src[1] = R[cur];
+                P.dst[0] = K[cur ^ 1];
+                P.dst[1] = R[cur ^ 1];
+                P.shift = 8 * b;
+                rc = rx_pass(stream, P, tiles, counters, scanned, scan_ws, m, nullptr);
+                if (rc != HS_OK) return rc;
+                cur ^= 1;
+            }
+        }
+        sorted = R[cur];
+        return HS_OK;
+    };
+
+    const int64_t* sorted = nullptr;
+    if (count == n) {
+        const int rc = sort_rows(nullptr, n, sorted);
+        if (rc != HS_OK) return rc;
+    } else {
+        // the count-th smallest first word, then the rows at or below it
+        uint64_t and_bits = 0, varying = 0;
+        int rc = form(0, nullptr, n, K[0], nullptr, and_bits, varying);
+        if (rc != HS_OK) return rc;
+        ObSelect init{0, 0, count};
+        for (int b = 0; b < 8; ++b)
+            if (((varying >> (8 * b)) & 0xffull) == 0) init.mask |= 0xffull << (8 * b);
+        init.prefix = and_bits & init.mask;
+        if (hipMemcpyAsync(select, &init, sizeof(init), hipMemcpyHostToDevice, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess) {  // `init` leaves scope
+            hs_set_error("hs_order_by: writing the selection state failed");
+            return HS_E_LAUNCH;
+        }
+        hs_memset_async(hist, 0, 256 * 8, stream);
+        for (int b = 7; b >= 0; --b) {
+            if ((init.mask >> (8 * b)) & 0xffull) continue;
+            hipLaunchKernelGGL(k_ob_select, dim3(ob_grid(n)), dim3(OB_THREADS), 0, stream, (const uint64_t*)K[0], n,
+                               (const ObSelect*)select, 8 * b, hist);
+            hipLaunchKernelGGL(k_ob_pick, dim3(1), dim3(256), 0, stream, select, 8 * b, hist);
+            RX_CHECK_LAUNCH("hs_order_by (select)");
+        }
+        const int64_t nct = (n + OB_TILE - 1) / OB_TILE;
+        hipLaunchKernelGGL(k_ob_count, dim3((unsigned)nct), dim3(OB_THREADS), 0, stream, (const uint64_t*)K[0], n,
+                           (const ObSelect*)select, counters);
+        RX_CHECK_LAUNCH("hs_order_by (count)");
+        rc = hs_exclusive_scan_i64(stream, counters, nct, scanned, scan_ws);
+        if (rc != HS_OK) return rc;
+        hipLaunchKernelGGL(k_ob_compact, dim3((unsigned)nct), dim3(OB_THREADS), 0, stream, (const uint64_t*)K[0], n,
+                           (const ObSelect*)select, (const int64_t*)scanned, (int64_t*)K[1]);
+        RX_CHECK_LAUNCH("hs_order_by (compact)");
+        int64_t candidates = 0;
+        if (!read_back(&candidates, scanned + nct, 8) || candidates < count || candidates > n) {
+            hs_set_error("hs_order_by: the selection kept %lld rows of %lld for a limit of %lld", (long long)candidates,
+                         (long long)n, (long long)count);
+            return HS_E_LAUNCH;
+        }
+        rc = sort_rows((const int64_t*)K[1], candidates, sorted);
+        if (rc != HS_OK) return rc;
+    }
+    if (hipMemcpyAsync(out_perm, sorted, (size_t)count * 8, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+        hs_set_error("hs_order_by: copying the row list failed");
+        return HS_E_LAUNCH;
     }
     return HS_OK;
 }

@@ -16,6 +16,7 @@ from typing import Any, Callable
 
 from . import tasks as _t
 from .plan import PhysicalPlan
+from .sql import SortKey
 
 # builder call -> (task class, arguments -> keyword fields of that class)
 _APPENDERS: dict[str, tuple[type, Callable[..., dict[str, Any]]]] = {
@@ -56,6 +57,19 @@ class DataFrame:
 
     def join(self, other_df: "DataFrame", on: Any, how: _t.JoinType) -> "DataFrame":
         return self._append(_t.BroadcastHashJoinTask, right_side_task=other_df.task, join_condition=on, how=how)
+
+    def order_by(self, *keys: Any) -> "DataFrame":
+        """ORDER BY: ``Col`` (ascending), ``Col.asc()`` or ``Col.desc()``, the first key the most significant."""
+        pairs = [(k.column, k.ascending) if isinstance(k, SortKey) else (k, True) for k in keys]
+        return self._append(_t.SortTask, keys=pairs)
+
+    def limit(self, n: int) -> "DataFrame":
+        """LIMIT: of an ``order_by`` directly below, else the first ``n`` rows in the engine's own order."""
+        _t.check_limit(n)
+        if type(self.task) is _t.SortTask:
+            self.task.limit = n
+            return self
+        return self._append(_t.SortTask, keys=[], limit=n)
 
     # ---- binding + execution ---------------------------------------------------------------------------------
     @property

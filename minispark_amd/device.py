@@ -652,7 +652,10 @@ class Device:
         """Make a lazily-sized batch exact (one D2H of the row count)."""
         if not batch.lazy:
             return batch
-        n = min(batch.nrows, self.host_int(batch.nrows_dev[0]))
+        return self.head(batch, min(batch.nrows, self.host_int(batch.nrows_dev[0])))
+
+    def head(self, batch: DBatch, n: int) -> DBatch:
+        """The first ``n`` rows (n <= the rows the buffers hold) as views of the same buffers: nothing is copied."""
         cols = []
         for c in batch.cols:
             if c.kind == hs.STR:
@@ -1497,6 +1500,42 @@ class Device:
         zero = self.to_device(np.zeros(1, dtype=np.int64))
         n_pad = self.host_int(self.lower_bound(srt, n, zero))  # rows with order < 0
         return perm[n_pad:n], n - n_pad
+
+    def order_by(self, batch: DBatch, keys: Sequence[tuple[Any, bool]], limit: int | None = None) -> tuple[torch.Tensor, int]:
+        """ORDER BY keys [LIMIT limit] over the rows of ``batch`` -> (row list, its length): row ``perm[j]`` of the batch
+        is the j-th row of the answer; ``gather_batch`` moves the columns.  ``keys`` = (column index or name, ascending)
+        pairs, the first the most significant; no keys: the first ``limit`` rows as they stand.  Stable (hs_order_by).  A
+        dictionary-coded STRING key is ordered by its code byte where the dictionary is sorted (``_dict_encode`` sorts
+        it: the code is the string's rank) and decoded otherwise.  The call learns sizes on the host between its steps,
+        so a run that contains it is not replayable."""
+        batch = self.resolve(batch)
+        n = batch.nrows
+        if self.rec is not None:
+            self.rec.poisoned = True
+        cols = []
+        for which, _ in keys:
+            col = batch.cols[batch.column_index(which) if isinstance(which, str) else which]
+            if col.virtual:
+                raise DeviceError("a virtual column of the fused join cannot be a sort key")
+            if col.dict is not None and list(col.dict) != sorted(col.dict):
+                col = self.decoded(col)
+            cols.append(col)
+        count = n if limit is None else min(n, int(limit))
+        perm = self.empty(max(count, 1), torch.int64)
+        if count == 0 or not cols:
+            if count:
+                torch.arange(count, out=perm)
+            return perm[:count], count
+        arr = (hs.hs_col * len(cols))(*[c.as_hs() for c in cols])
+        desc = (C.c_int32 * len(cols))(*[0 if ascending else 1 for _, ascending in keys])
+        ws = self.workspace(self._raw_lib.hs_order_by_ws_bytes(n, len(cols), 32 * len(cols)))  # a key: <= 256 bytes
+        out_count = C.c_int64(0)
+        hs.check(self._raw_lib.hs_order_by(self.stream, arr, desc, len(cols), n, None, -1 if limit is None else int(limit),
+                                           perm.data_ptr(), C.byref(out_count), ws.data_ptr(), self.flags.data_ptr()),
+                 "hs_order_by")
+        if out_count.value != count:
+            raise DeviceError(f"hs_order_by returned {out_count.value} rows, expected {count}")
+        return perm[:count], count
 
     def unit_ids_per_row(self, unit_rows: Sequence[int], unit_ids: Sequence[int]) -> torch.Tensor:
         """Global block id of every partial row: unit_ids[u] for rows unit_rows[u] .. unit_rows[u + 1]."""

@@ -431,7 +431,9 @@ class HipExecutionEngine(ExecutionEngine):
             self._probe_stages = {id(st.dependencies[1]): st for st in plan.stages
                                   if _cls(st.producer) == "BroadcastHashJoinTask" and len(st.dependencies) == 2}
             # record the second (cache-warm) run of a plan: by then every buffer it needs is prepared
-            want_record = self.replay_enabled and self._plan_runs.get(rec_key, 0) >= 1
+            # (a plan with ORDER BY / LIMIT is never recorded: hs_order_by decides its launches from what it reads back)
+            has_sort = any(_cls(t) == "SortTask" for st in plan.stages for t in st.consumers)
+            want_record = self.replay_enabled and self._plan_runs.get(rec_key, 0) >= 1 and not has_sort
             recording = self.dev.start_recording() if want_record else None
             try:
                 for stage in plan.stages:
@@ -580,6 +582,8 @@ class HipExecutionEngine(ExecutionEngine):
                 continue
             if not consumers or _cls(consumers[0]) != "AggregateTask" or consumers[0].before_shuffle:
                 continue
+            if any(_cls(t) == "SortTask" for t in consumers):
+                continue  # ORDER BY / LIMIT: the finish launch hands its rows straight to the host; _run_stage orders them
             if len(consumers) > 2 or (len(consumers) == 2 and _cls(consumers[1]) != "ProjectTask"):
                 continue
             if len(stage.dependencies) != 1:
@@ -596,6 +600,10 @@ class HipExecutionEngine(ExecutionEngine):
         from .device import SlabUnsupported, TierExceeded  # noqa: PLC0415
 
         producer, consumers, writer = stage.producer, list(stage.consumers), stage.writer
+        # ORDER BY / LIMIT is not a step of the stage's pipeline: it runs once, on the finished (gathered, rounded) result
+        sort = next((t for t in consumers if _cls(t) == "SortTask"), None)
+        if sort is not None:
+            consumers, stage = self._without_sort(stage, sort)
         kind = _cls(producer)
         if kind == "LoadTableBlockTask":
             ranges = self._stream_ranges(producer, consumers)
@@ -609,6 +617,7 @@ class HipExecutionEngine(ExecutionEngine):
                         return [JobResult(f"{self._job_prefix}-{self._job_seq}", self._executor_id, [])]
                     self.streamed_join_fallbacks += 1  # the ranges are concatenated; the join runs resident
                     self.last_probe_route = "resident"
+                self._refuse_sort_in_pieces(sort, writer)
                 return self._run_scan_stage_streamed(stage, outputs, ranges)
             batch = self._scan(producer, consumers, writer)
         elif kind == "LoadShuffleFilesTask":
@@ -621,6 +630,7 @@ class HipExecutionEngine(ExecutionEngine):
             first_real = next((t for t in consumers if _cls(t) != "FilterTask"), None)
             feeds_aggregate = first_real is not None and _cls(first_real) == "AggregateTask" and first_real.before_shuffle
             if isinstance(outputs[id(stage.dependencies[1])], _DeferredScan):
+                self._refuse_sort_in_pieces(sort, writer)
                 return self._run_join_stage_streamed(stage, outputs, feeds_aggregate)
             batch = self._join(producer, outputs[id(stage.dependencies[0])], outputs[id(stage.dependencies[1])],
                                self._needed_names(consumers), feeds_aggregate, consumers)
@@ -639,8 +649,44 @@ class HipExecutionEngine(ExecutionEngine):
         if wname == "WriteToLocalFileTask":
             if self.dist is not None and batch.partitioned:
                 batch = self._gather_to_root(batch)
+            if sort is not None:
+                batch = self._order_rows(batch, sort, schema)
             return [self._write_result(batch, schema, stage.stage_id)]
         raise NotImplementedError(f"writer {wname}")
+
+    @staticmethod
+    def _without_sort(stage: Any, sort: Any) -> tuple[list, Any]:
+        """The stage as its pipeline sees it: every consumer but the SortTask (only the planner's rename-only
+        ProjectTask may follow it, plan.check_sort_is_last)."""
+        import copy  # noqa: PLC0415
+
+        consumers = [t for t in stage.consumers if t is not sort]
+        view = copy.copy(stage)
+        view.consumers = consumers
+        return consumers, view
+
+    @staticmethod
+    def _refuse_sort_in_pieces(sort: Any, writer: Any) -> None:
+        """A result that is written range by range is never whole on the device, so it cannot be ordered (a LIMIT
+        without keys could be served, but which rows it keeps would then depend on the budget: refused alike)."""
+        if sort is not None and _cls(writer) == "WriteToLocalFileTask":
+            raise ExecutionError("ORDER BY / LIMIT needs the whole result on the device, and this query's result is "
+                                 "produced in pieces because its input exceeds HIPSPARK_HBM_BUDGET: raise the budget")
+
+    def _order_rows(self, batch: Any, sort: Any, schema: Schema) -> Any:
+        """ORDER BY / LIMIT over the finished result: the rows are first rounded to the types they are stored in, so
+        they are ordered by the values the user reads back.  Keys are looked up by POSITION in the SortTask's input
+        schema: the planner's rename-only projection above it changes names, never positions.  On N ranks rank 0 holds
+        every row by now (_gather_to_root) and the others none."""
+        batch = self.dev.resolve(self._quantise_batch(self.dev.resolve(batch), schema))
+        names = [name for name, _ in sort.inferred_schema]
+        if len(names) != len(batch.cols):
+            raise ExecutionError(f"ORDER BY schema {sort.inferred_schema} does not match the result {batch.schema}")
+        keys = [(names.index(col.name), ascending) for col, ascending in sort.keys]
+        if not keys:
+            return self.dev.head(batch, min(batch.nrows, sort.limit))  # LIMIT alone: one slice of the rows as they stand
+        perm, count = self.dev.order_by(batch, keys, sort.limit)
+        return self.dev.gather_batch(batch, perm, count)
 
     def _consume(self, batch: Any, consumers: Sequence[Any]) -> Any:
         """Run a stage's consumer tasks (filters, projections, aggregates) over one batch."""

@@ -5,14 +5,16 @@ requirements, so `.sql()` would not work next to the HIP engine without this mod
 A hand-written backtracking recursive-descent parser for the same language:
 
     SELECT select_list FROM 'path' [AS t] { [LEFT|RIGHT|INNER|FULL] JOIN 'path' [AS t] ON cond }
-           [WHERE cond] [GROUP BY col [HAVING cond]] ;
+           [WHERE cond] [GROUP BY col [HAVING cond]] [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] [LIMIT n] ;
 
 * select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e) [AS name]``, ``expr [AS name]``;
 * conditions: OR < AND < NOT < comparison | ( cond ) | BETWEEN | LIKE, comparators = != <= >= < >;
 * expressions: + - over * / over atoms (number, column, string literal, ( expr ), COUNT()/SUM(e));
 * like the reference: whitespace is required around keywords, the closing ``;`` is mandatory, every join kind
   is executed as an inner join (parser.py:131-133), numbers are integers (parser.py:349), NOT raises
-  NotImplementedError (sql.py:44-45), GROUP BY takes one column (dataframe.py:64).
+  NotImplementedError (sql.py:44-45), GROUP BY takes one column (dataframe.py:64);
+* beyond the reference: ORDER BY takes names of the RESULT (a select item's alias, or its generated name), each ascending
+  unless DESC follows, and LIMIT a non-negative integer; both become one ``order_by`` / ``limit`` after the final select.
 
 Alternatives are tried in the grammar's order and the first that fits wins (ordered choice), so texts the
 reference accepts build the same task tree here (tests/test_parser.py compares both renderings).
@@ -25,7 +27,7 @@ import re
 from typing import Any, Callable
 
 from .dataframe import DataFrame
-from .sql import AggCol, Col, Lit
+from .sql import AggCol, Col, Lit, SortKey
 from .sql import Functions as F
 
 
@@ -50,6 +52,7 @@ _TABLE = re.compile(r"[a-zA-Z0-9_\-\./ ]+")
 _COLUMN = re.compile(r"[A-Za-z_][A-Za-z0-9_\.]*")
 _IDENT = re.compile(r"[A-Za-z_][A-Za-z0-9_]*")
 _NUMBER = re.compile(r"-?[0-9]+(\.[0-9]+)?")
+_DIGITS = re.compile(r"[0-9]+")
 _STRING = re.compile(r"[^']*")
 _COMPARATORS: list[tuple[str, Callable[[Any, Any], Any]]] = [
     ("=", operator.eq), ("!=", operator.ne), ("<=", operator.le), (">=", operator.ge), ("<", operator.lt),
@@ -127,6 +130,8 @@ class _Parser:
         joins = self.repeat(lambda: (self.ws(), self.join_clause())[1])
         has_where, where = self.attempt(lambda: (self.ws(), self.where_clause())[1])
         has_group, group = self.attempt(lambda: (self.ws(), self.group_by_clause())[1])
+        has_order, order = self.attempt(lambda: (self.ws(), self.order_by_clause())[1])
+        has_limit, limit = self.attempt(lambda: (self.ws(), self.limit_clause())[1])
         self.ows()
         self.lit(";")
         self.ows()
@@ -155,8 +160,18 @@ class _Parser:
             df = df.group_by(*group_cols).agg(*agg_cols)
             if having is not None:
                 df = df.filter(having.normalize_agg_columns())
-            return df.select(*[Col(c.name) for c in select_list])
-        return df.select(*select_list)
+            df = df.select(*[Col(c.name) for c in select_list])
+        else:
+            df = df.select(*select_list)
+        if has_order:
+            names = {c.name for c in select_list}
+            for key in order:
+                if "*" not in names and key.column.name not in names:
+                    raise ValueError(f'Column "{key.column.name}" of ORDER BY is not in the select list {sorted(names)}')
+            df = df.order_by(*order)
+        if has_limit:
+            df = df.limit(limit)
+        return df
 
     def select_list(self) -> list[Col]:
         items = [self.select_item()]
@@ -243,6 +258,27 @@ class _Parser:
 
         has_having, cond = self.attempt(having)
         return cols, cond if has_having else None
+
+    def order_by_clause(self) -> list[SortKey]:
+        self.lit("ORDER")
+        self.ws()
+        self.lit("BY")
+        self.ws()
+
+        def key() -> SortKey:
+            col = self.column_name()
+            has_direction, word = self.attempt(lambda: (self.ws(), self.first_of(lambda: self.lit("ASC"),
+                                                                                 lambda: self.lit("DESC")))[1])
+            return col.desc() if has_direction and word == "DESC" else col.asc()
+
+        keys = [key()]
+        keys += self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), key())[3])
+        return keys
+
+    def limit_clause(self) -> int:
+        self.lit("LIMIT")
+        self.ws()
+        return int(self.rx(_DIGITS))
 
     # ---- conditions -------------------------------------------------------------------------------------------
     def condition(self) -> Col:

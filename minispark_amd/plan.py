@@ -15,6 +15,9 @@ Rewrites applied, in the reference's order (plan.py:224-235):
    join inputs each get a WriteToShufflePartitions on their key (plan.py:186-189);
 3. strip ``alias.`` prefixes from the output column names with a final ProjectTask (plan.py:207-222);
 4. cut the chain into stages at every shuffle write / join, dependencies first.
+
+A ``SortTask`` (ORDER BY / LIMIT, this build's own) must top the chain; it ends up among the consumers of the stage that
+writes the result, below rewrite 3's rename-only ProjectTask, and the engine runs it on the finished rows.
 """
 
 from __future__ import annotations
@@ -29,6 +32,7 @@ from .tasks import (
     LoadShuffleFilesTask,
     ProducerTask,
     ProjectTask,
+    SortTask,
     Task,
     VoidTask,
     WriterTask,
@@ -151,7 +155,21 @@ class PhysicalPlan:
         task.inferred_schema = clean
 
     @staticmethod
+    def check_sort_is_last(task: Task, *, top: bool = True) -> None:
+        """ORDER BY / LIMIT orders the query's RESULT: the engine runs it once, on the finished rows, so a SortTask
+        anywhere but on top of the chain has no meaning here."""
+        node: Task | None = task
+        while node is not None and type(node) is not VoidTask:
+            if type(node) is SortTask and not top:
+                raise ValueError("ORDER BY / LIMIT must be the last operation")
+            if type(node) is BroadcastHashJoinTask:
+                PhysicalPlan.check_sort_is_last(node.right_side_task, top=False)
+            top = False
+            node = node.parent_task
+
+    @staticmethod
     def generate_physical_plan(full_task: Task) -> "PhysicalPlan":
+        PhysicalPlan.check_sort_is_last(full_task)
         # planning rewrites nodes in place; work on a copy so the caller's DataFrame stays reusable
         root: Task = WriteToLocalFileTask(deepcopy(full_task))
         PhysicalPlan.infer_schema(root)

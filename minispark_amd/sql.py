@@ -111,6 +111,12 @@ class Col:
     def alias(self, name: str) -> "Col":
         return AliasColumn(self, name)
 
+    def asc(self) -> "SortKey":
+        return SortKey(self, True)
+
+    def desc(self) -> "SortKey":
+        return SortKey(self, False)
+
     # -- tree protocol ---------------------------------------------------------------------------------
     @property
     def children(self) -> tuple["Col", ...]:
@@ -133,6 +139,19 @@ class Col:
 
     def __str__(self) -> str:
         return self.name
+
+    __repr__ = __str__
+
+
+class SortKey:
+    """``Col("a").asc()`` / ``.desc()``: one key of ``DataFrame.order_by`` (no reference counterpart - the reference has
+    no ordering).  Not an expression: it cannot be selected, compared or nested."""
+
+    def __init__(self, column: Col, ascending: bool) -> None:
+        self.column, self.ascending = column, ascending
+
+    def __str__(self) -> str:
+        return f"{self.column} {'ASC' if self.ascending else 'DESC'}"
 
     __repr__ = __str__
 

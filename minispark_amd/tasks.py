@@ -218,6 +218,39 @@ class AggregateTask(ConsumerTask):
         )
 
 
+@dataclass(kw_only=True)
+class SortTask(ConsumerTask):
+    """ORDER BY / LIMIT over the query's result rows (no reference counterpart).  ``keys`` = (plain column of the input
+    schema, ascending) pairs, the first the most significant; ``limit`` = rows kept (None: all).  Without keys the
+    first ``limit`` rows are kept in the engine's own order.  Always the last logical operation: the engine runs it on
+    the finished result, after the values were rounded to their stored types."""
+
+    keys: list[tuple[Col, bool]] = field(default_factory=list)
+    limit: int | None = None
+
+    def __post_init__(self) -> None:
+        for col, _ in self.keys:
+            if type(col).__name__ not in {"Col", "SchemaCol"}:
+                raise ValueError(f"ORDER BY takes plain columns, not the expression {col}: select(... .alias()) first")
+        if self.limit is not None:
+            check_limit(self.limit)
+
+    def validate_schema(self) -> Schema:
+        schema = self.parent_task.validate_schema()
+        for col, _ in self.keys:
+            col.infer_type(schema)  # ValueError('Column "x" not found in schema ...')
+        return schema
+
+    def describe(self) -> str:
+        keys = ", ".join(f"{col} {'ASC' if ascending else 'DESC'}" for col, ascending in self.keys)
+        return f"Sort({keys}; limit={self.limit})"
+
+
+def check_limit(n: object) -> None:
+    if type(n) is not int or n < 0:
+        raise ValueError(f"LIMIT takes an int >= 0, not {n!r}")
+
+
 @dataclass
 class WriteToShufflePartitions(WriterTask):
     """Stage boundary: rows are routed by ``hash(key) % SHUFFLE_PARTITIONS`` and quantised to the
@@ -259,6 +292,7 @@ __all__ = [
     "LoadTableBlockTask",
     "ProducerTask",
     "ProjectTask",
+    "SortTask",
     "Task",
     "VoidTask",
     "WriteToLocalFileTask",
