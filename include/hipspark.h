@@ -258,6 +258,29 @@ int hs_agg_partial(void* stream, const hs_col* cols, int32_t n_cols, int32_t key
                    const hs_agg_geom* geom, int64_t* out_rep, uint64_t* out_acc, int32_t* out_ngroups, void* ws,
                    uint32_t* flags, void* ev_begin, void* ev_end);
 
+/* Keyless tier: aggregates WITHOUT GROUP BY (SELECT SUM(x) FROM t WHERE ...).  The value is that of
+ * grouping by a column that is equal in every row, without that column: per unit f64 / i64 partial sums, the unit row
+ * quantised like a shuffle-file write, unit rows merged in unit order by the caller (hs_agg_merge / hs_agg_finish
+ * under a constant key).  prog: [filter ops ... HS_OP_FILTER]* then [value ops ... HS_OP_AGG a]* - the form
+ * hs_agg_partial takes without HS_OP_KEY; no key column among cols.  No key bytes are read and no table is kept: every
+ * lane folds its rows into n_acc register accumulators (a filtered-out row folds the identity), lanes meet in a shuffle
+ * tree, waves through LDS, every workgroup leaves one cell row per chunk in ws, and the workgroup that finishes a unit's
+ * last chunk folds the unit's chunk rows IN CHUNK ORDER.  No floating-point atomics: two runs of one launch give the
+ * same bits.  Outputs per unit:
+ *   out_acc[n_units * n_acc] : 64-bit cells, ALREADY QUANTISED (FLOAT rounded to f32 and widened back, INTEGER range-
+ *                              checked: HS_FLAG_INT_OVERFLOW as hs_agg_partial raises it)
+ *   out_rows[n_units]        : rows of the unit that passed the WHERE
+ *   out_rep[n_units], out_ngroups[n_units] : u / 1 for a unit with such rows, -1 / 0 for one without - the unit
+ *                              contributes NO partial row (zero-row rule: no row anywhere, no result row); with
+ *                              group_cap = 1 this is the form hs_agg_pack reads
+ * chunks / unit_chunk0: hs_agg_partial_chunks of the geometry made by hs_agg_scalar_geom (group_cap 1, 256 lanes).
+ * ws: geom->ws_bytes, zero-filled before the first launch (arrival counters; every launch leaves them at zero). */
+int hs_agg_scalar_geom(const int64_t* host_unit_rows, int64_t n_units, int32_t n_acc, hs_agg_geom* out);
+int hs_agg_scalar(void* stream, const hs_col* cols, int32_t n_cols, const hs_program* prog, const hs_agg_spec* spec,
+                  const hs_chunk* chunks, const int64_t* unit_chunk0, int64_t n_units, const hs_agg_geom* geom,
+                  uint64_t* out_acc, int64_t* out_rows, int64_t* out_rep, int32_t* out_ngroups, void* ws,
+                  uint32_t* flags, void* ev_begin, void* ev_end);
+
 /* Shared-dictionary tier of the same operator, for tens to thousands of groups per unit: one
  * 1024-lane workgroup per chunk keeps ONE table of geom->group_cap slots in LDS and updates it with LDS atomics;
  * chunk tables are merged into per-unit tables of geom->pad slots with global atomics; cells are then rounded like
@@ -813,6 +836,9 @@ int hs_jit_compile_check(const hs_col* cols, int32_t n_cols, int32_t key_col, co
 int hs_jit_compile_check_shared(const hs_col* cols, int32_t n_cols, int32_t key_col, int32_t unit_col,
                                 const hs_program* prog, const hs_agg_spec* spec, const char* arch, int64_t* code_bytes,
                                 char* src_out, int64_t src_cap);
+/* The same for the keyless tier's kernel (hs_agg_scalar: no key column, no HS_OP_KEY). */
+int hs_jit_compile_check_scalar(const hs_col* cols, int32_t n_cols, const hs_program* prog, const hs_agg_spec* spec,
+                                const char* arch, int64_t* code_bytes, char* src_out, int64_t src_cap);
 /* The same for an expression program of hs_eval (the compiled form evaluates four rows per lane with 16-byte
  * loads and stores; hs_eval uses it when sel == NULL and the numeric buffers are 16-byte aligned, and then reads
  * up to 3 rows past nrows of every column it loads - buffers carry that slack). */

@@ -27,6 +27,13 @@ __global__ void __launch_bounds__(256) k_agg_main(const AggMainArgs A_kernarg) {
     hs_agg_main_body<InterpProg<HASHED, D>>(A);
 }
 
+// keyless tier (hs_agg_kernel.h, hs_agg_scalar): the interpreter with register accumulators
+template <int D>
+__global__ void __launch_bounds__(256) k_agg_scalar(const AggMainArgs A_kernarg) {
+    HS_KERNARG(AggMainArgs, A);
+    hs_agg_scalar_body<InterpProg<false, D>>(A);
+}
+
 // shared-dictionary tier (hs_agg_kernel.h): interpreter instantiations.  512 lanes, not the compiled programs' 1024: the
 // interpreter's operand stack (D x 4 rows x 64 bits) does not fit 128 VGPRs - at 1024 lanes it lived in scratch memory
 // (440-712 bytes per lane, ~5 400 scratch instructions).  A stack of depth 4 fits the 256 VGPRs of a 512-lane workgroup,
@@ -1193,6 +1200,9 @@ static size_t agg_main_lds(int32_t group_cap, int32_t n_acc, int wg) {
     return (size_t)group_cap * 16 + (size_t)group_cap * (size_t)n_acc * (size_t)wg * 8;
 }
 
+static int agg_geom_chunks(const char* who, const int64_t* host_unit_rows, int64_t n_units, int wg, size_t lds,
+                           hs_agg_geom* out);
+
 extern "C" int hs_agg_partial_geom(const int64_t* host_unit_rows, int64_t n_units, int32_t n_acc, int32_t group_cap,
                                    hs_agg_geom* out) {
     if (!host_unit_rows || !out || n_units < 0 || n_acc < 0 || n_acc > HS_MAX_ACC || group_cap < 1 ||
@@ -1218,11 +1228,24 @@ extern "C" int hs_agg_partial_geom(const int64_t* host_unit_rows, int64_t n_unit
                      group_cap, n_acc, agg_main_lds(group_cap, n_acc, 64), HS_LDS_HARD);
         return HS_E_LIMIT;
     }
+    const int rc = agg_geom_chunks("hs_agg_partial_geom", host_unit_rows, n_units, wg, lds, out);
+    if (rc) return rc;
+    out->group_cap = group_cap;
+    // chunk partials + 256 spare bytes + one arrival counter per unit (fused combine)
+    out->ws_bytes = hs_agg_partials_bytes(out->n_chunks, group_cap, n_acc) + (size_t)n_units * 4 + 64;
+    return HS_OK;
+}
+
+// The chunking shared by the tiers that give every workgroup one row range (private tables, keyless): fills chunk_rows,
+// wg_threads, n_chunks, lds_bytes and pad (HS_GEOM_FUSABLE when every unit owns a chunk) for `wg` lanes and `lds` bytes
+// of LDS per workgroup.
+static int agg_geom_chunks(const char* who, const int64_t* host_unit_rows, int64_t n_units, int wg, size_t lds,
+                           hs_agg_geom* out) {
     int64_t total = 0;
     for (int64_t u = 0; u < n_units; ++u) {
         const int64_t r = host_unit_rows[u + 1] - host_unit_rows[u];
         if (r < 0) {
-            hs_set_error("hs_agg_partial_geom: unit_rows not ascending at %lld", (long long)u);
+            hs_set_error("%s: unit_rows not ascending at %lld", who, (long long)u);
             return HS_E_ARG;
         }
         total += r;
@@ -1288,7 +1311,6 @@ extern "C" int hs_agg_partial_geom(const int64_t* host_unit_rows, int64_t n_unit
     }
     bool every_unit_has_rows = n_units > 0;
     for (int64_t u = 0; u < n_units; ++u) every_unit_has_rows = every_unit_has_rows && host_unit_rows[u + 1] > host_unit_rows[u];
-    out->group_cap = group_cap;
     out->chunk_rows = (int32_t)chunk;
     out->wg_threads = wg;
     // a unit without rows owns no chunk, so no workgroup would ever combine it: such launches keep the separate
@@ -1296,8 +1318,6 @@ extern "C" int hs_agg_partial_geom(const int64_t* host_unit_rows, int64_t n_unit
     out->pad = every_unit_has_rows ? HS_GEOM_FUSABLE : 0;
     out->n_chunks = n_chunks;
     out->lds_bytes = lds;
-    // chunk partials + 256 spare bytes + one arrival counter per unit (fused combine)
-    out->ws_bytes = hs_agg_partials_bytes(n_chunks, group_cap, n_acc) + (size_t)n_units * 4 + 64;
     return HS_OK;
 }
 
@@ -1491,6 +1511,7 @@ static int agg_partial_impl(void* stream, const hs_col* cols, int32_t n_cols, in
     A.pad3 = 0;
     A.chunk_acc = nullptr;
     A.stamps = hs_scan_stamps_for(geom->n_chunks);
+    A.scalar_rows = nullptr;
     bool fused = false;
     if (geom->pad == HS_GEOM_FUSABLE && spec->n_acc > 0) {
         int fbatch = ubatch;
@@ -1545,6 +1566,137 @@ extern "C" int hs_agg_partial_slab(void* stream, const hs_col* cols, int32_t n_c
     }
     return agg_partial_impl(stream, cols, n_cols, key_col, prog, spec, chunks, unit_chunk0, n_units, geom, nullptr,
                             nullptr, nullptr, unit_ids, slab, desc, ws, flags, ev_begin, ev_end);
+}
+
+// ---- aggregates without GROUP BY (kernel: hs_agg_kernel.h, keyless tier) ------------------------------------------
+int hs_jit_launch_agg_scalar(const AggMainArgs* args, unsigned grid, unsigned block, size_t lds_bytes, hipStream_t stream);
+static constexpr int HS_SCALAR_WG = 256;
+// workspace: one cell row [n_acc + 1] per chunk, then one arrival counter per unit
+static size_t hs_agg_scalar_cells_bytes(int64_t n_chunks, int32_t n_acc) {
+    return ((size_t)n_chunks * (size_t)(n_acc + 1) * 8 + 256 + 15) & ~(size_t)15;
+}
+
+extern "C" int hs_agg_scalar_geom(const int64_t* host_unit_rows, int64_t n_units, int32_t n_acc, hs_agg_geom* out) {
+    if (!host_unit_rows || !out || n_units < 0 || n_acc < 1 || n_acc > HS_MAX_ACC) {
+        hs_set_error("hs_agg_scalar_geom: bad arguments");
+        return HS_E_ARG;
+    }
+    // no table in LDS: one cell row per wave; the workgroups per CU are bounded by wave slots and registers alone
+    const size_t lds = (size_t)(HS_SCALAR_WG / HS_WAVE) * (size_t)(n_acc + 1) * 8;
+    const int rc = agg_geom_chunks("hs_agg_scalar_geom", host_unit_rows, n_units, HS_SCALAR_WG, lds, out);
+    if (rc) return rc;
+    out->group_cap = 1;
+    out->ws_bytes = hs_agg_scalar_cells_bytes(out->n_chunks, n_acc) + (size_t)n_units * 4 + 64;
+    return HS_OK;
+}
+
+extern "C" int hs_agg_scalar(void* stream, const hs_col* cols, int32_t n_cols, const hs_program* prog,
+                             const hs_agg_spec* spec, const hs_chunk* chunks, const int64_t* unit_chunk0, int64_t n_units,
+                             const hs_agg_geom* geom, uint64_t* out_acc, int64_t* out_rows, int64_t* out_rep,
+                             int32_t* out_ngroups, void* ws, uint32_t* flags, void* ev_begin, void* ev_end) {
+    if (!cols || !prog || !spec || !chunks || !unit_chunk0 || !geom || !ws || !flags || !out_acc || !out_rows || !out_rep ||
+        !out_ngroups || n_units < 0 || n_cols < 0 || spec->n_acc < 1 || spec->n_acc > HS_MAX_ACC) {
+        hs_set_error("hs_agg_scalar: null or out-of-range argument");
+        return HS_E_ARG;
+    }
+    if (prog->n_ins > HS_MAX_INS || prog->n_lit > HS_MAX_LIT) {
+        hs_set_error("hs_agg_scalar: program too long");
+        return HS_E_LIMIT;
+    }
+    if (geom->wg_threads != HS_SCALAR_WG || geom->group_cap != 1 || geom->chunk_rows < HS_V ||
+        geom->lds_bytes != (size_t)(HS_SCALAR_WG / HS_WAVE) * (size_t)(spec->n_acc + 1) * 8) {
+        hs_set_error("hs_agg_scalar: geometry not made by hs_agg_scalar_geom for these aggregates");
+        return HS_E_ARG;
+    }
+    uint32_t fed = 0;
+    for (uint32_t i = 0; i < prog->n_ins; ++i) {
+        const int op = (int)(prog->ins[i] & 0xff);
+        const uint32_t a = (uint32_t)((prog->ins[i] >> 16) & 0xffff);
+        if (op == HS_OP_KEY || op == HS_OP_OUT) {
+            hs_set_error("hs_agg_scalar: a keyless program holds no KEY / OUT instruction");
+            return HS_E_ARG;
+        }
+        if (op == HS_OP_AGG) {
+            if (a >= (uint32_t)spec->n_acc) {
+                hs_set_error("hs_agg_scalar: AGG names accumulator %u of %d", a, spec->n_acc);
+                return HS_E_ARG;
+            }
+            fed |= 1u << a;
+        }
+    }
+    if (fed != (1u << spec->n_acc) - 1) {
+        hs_set_error("hs_agg_scalar: an accumulator is never fed");
+        return HS_E_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // a unit without rows owns no chunk and no workgroup writes its row: "no kept rows" is written here
+    if (n_units > 0 && geom->pad != HS_GEOM_FUSABLE) {
+        if (hipMemsetAsync(out_rows, 0, (size_t)n_units * 8, s) != hipSuccess ||
+            hipMemsetAsync(out_rep, 0xff, (size_t)n_units * 8, s) != hipSuccess ||
+            hipMemsetAsync(out_ngroups, 0, (size_t)n_units * 4, s) != hipSuccess) {
+            hs_set_error("hs_agg_scalar: clearing the unit rows failed");
+            return HS_E_LAUNCH;
+        }
+    }
+    if (n_units == 0 || geom->n_chunks == 0) return HS_OK;
+    if (geom->n_chunks > 0x7fffffffll) {
+        hs_set_error("hs_agg_scalar: too many chunks");
+        return HS_E_LIMIT;
+    }
+    AggMainArgs A;
+    memset(&A, 0, sizeof(A));
+    int rc = fill_cols(A.cols, cols, n_cols);
+    if (rc) return rc;
+    for (int i = 0; i < n_cols; ++i) {
+        if (i >= HS_FUSED_COLS && cols[i].kind != HS_STR) {
+            hs_set_error("hs_agg_scalar: more than %d numeric column slots", HS_FUSED_COLS);
+            return HS_E_LIMIT;
+        }
+        if ((cols[i].kind & HS_PAIR) || cols[i].kind == HS_JOIN8_CODE || cols[i].kind == HS_JOIN8_UNIT) {
+            hs_set_error("hs_agg_scalar: HS_PAIR / HS_JOIN8 columns belong to the shared tier");
+            return HS_E_ARG;
+        }
+    }
+    const int depth = program_depth(prog);
+    if (depth > HS_MAX_STACK) {
+        hs_set_error("hs_agg_scalar: expression stack depth %d > %d", depth, HS_MAX_STACK);
+        return HS_E_LIMIT;
+    }
+    A.prog = *prog;
+    A.spec = *spec;
+    A.key_col = -1;
+    A.group_cap = 1;
+    A.chunk_rows = geom->chunk_rows;
+    A.chunks = chunks;
+    A.unit_chunk0 = unit_chunk0;
+    A.n_units = n_units;
+    A.part_acc = (uint64_t*)ws;
+    A.flags = flags;
+    A.unit_arrivals = (uint32_t*)((char*)ws + hs_agg_scalar_cells_bytes(geom->n_chunks, spec->n_acc));
+    A.unit.spec = *spec;
+    A.unit.group_cap = 1;
+    A.unit.out_rep = out_rep;
+    A.unit.out_acc = out_acc;
+    A.unit.out_ngroups = out_ngroups;
+    A.unit.flags = flags;
+    A.unit_col = -1;
+    A.stamps = hs_scan_stamps_for(geom->n_chunks);
+    A.scalar_rows = out_rows;
+    dim3 grid((unsigned)geom->n_chunks), block((unsigned)geom->wg_threads);
+    if (ev_begin) hs_event_record((hipEvent_t)ev_begin, s);
+    if (hs_jit_launch_agg_scalar(&A, grid.x, block.x, geom->lds_bytes, s) == HS_OK) {
+        // launched the program compiled for exactly this bytecode
+    } else if (depth <= 4) {
+        hipLaunchKernelGGL((k_agg_scalar<4>), grid, block, geom->lds_bytes, s, A);
+    } else {
+        hipLaunchKernelGGL((k_agg_scalar<8>), grid, block, geom->lds_bytes, s, A);
+    }
+    if (ev_end) hs_event_record((hipEvent_t)ev_end, s);
+    if (hipGetLastError() != hipSuccess) {
+        hs_set_error("hs_agg_scalar: kernel launch failed");
+        return HS_E_LAUNCH;
+    }
+    return HS_OK;
 }
 
 extern "C" int hs_agg_pack(void* stream, const int64_t* rep, const uint64_t* acc, const int32_t* ngroups,
@@ -2012,6 +2164,7 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
     if (join) A.join = *join;
     else memset(&A.join, 0, sizeof(A.join));
     A.stamps = nullptr;
+    A.scalar_rows = nullptr;
     {  // the replica count the geometry sized the LDS block for
         const size_t per_replica = (size_t)geom->group_cap * (size_t)(spec->n_acc > 0 ? spec->n_acc : 1) * 8;
         const size_t r = (geom->lds_bytes - (size_t)geom->group_cap * 16) / per_replica;

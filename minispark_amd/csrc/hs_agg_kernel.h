@@ -311,6 +311,8 @@ struct AggMainArgs {
     // debug (HIPSPARK_SCAN_STAMPS=1; tools/scan_stamps.py): [n_chunks][16] wall_clock64() at the phase boundaries of every
     // workgroup of the private-table scan + the hardware id; NULL otherwise
     int64_t* stamps;
+    // keyless tier (hs_agg_scalar_body): [n_units] rows of the unit that passed the WHERE; NULL on every other tier
+    int64_t* scalar_rows;
 };
 #define HS_SCAN_STAMP(i) do { if (A.stamps && threadIdx.x == 0) A.stamps[(int64_t)blockIdx.x * 16 + (i)] = (int64_t)wall_clock64(); } while (0)
 
@@ -791,6 +793,197 @@ __device__ __forceinline__ void hs_agg_main_body(const AggMainArgs& A) {
     }
     HS_SCAN_STAMP(4);
     hs_agg_main_arrive(A, desc.unit, hs_lds);
+    HS_SCAN_STAMP(6);
+}
+
+// ======================================================================================================
+// Keyless tier: aggregates without GROUP BY (SELECT SUM(x) FROM t WHERE ...).
+//
+// The degenerate, fastest case of the scan: no key column is read and no table is kept.  Every lane folds its rows into
+// n_acc REGISTER accumulators (a row the WHERE dropped folds the aggregate's identity, and the lane counts the rows it
+// kept, so MIN / MAX of nothing never leaves the unit); lanes -> wave by a shuffle tree, waves -> workgroup through
+// n_waves x (n_acc + 1) x 8 bytes of LDS folded in wave order; the workgroup stores ONE cell row per chunk
+// (part_acc[chunk][n_acc + 1], the last cell = kept rows).  The workgroup that finishes a unit's last chunk (arrival counter
+// as in hs_agg_main_arrive, left at zero) folds the unit's chunk rows in CHUNK ORDER, quantises them like a shuffle-file
+// write and stores the unit row.  No atomics on values anywhere: the reduction tree is a function of the launch geometry
+// alone, two runs of one launch give the same bits.
+// Outputs (AggMainArgs): unit.out_acc[u][n_acc] quantised cells, scalar_rows[u] kept rows, unit.out_rep[u] = u or -1 and
+// unit.out_ngroups[u] = 1 or 0 (the partial-row form hs_agg_pack reads: a unit without kept rows has no partial row).
+// ======================================================================================================
+struct ScalarCtx {
+    int64_t row0;
+    bool alive[HS_V];
+    int slot[HS_V];
+    uint64_t acc[HS_MAX_ACC];
+    int64_t rows;
+    uint32_t err;
+    HsSpecBits sb;
+
+    // a keyless program holds no KEY instruction (the host checks); the evaluator's switch still names these
+    template <bool HASHED>
+    __device__ __forceinline__ int find(const hs_col&, uint64_t, int64_t, bool& live) {
+        err |= HS_FLAG_BAD_PROGRAM;
+        live = false;
+        return 0;
+    }
+    __device__ __forceinline__ int find_byte(const hs_col&, uint64_t, int64_t, bool& live) {
+        err |= HS_FLAG_BAD_PROGRAM;
+        live = false;
+        return 0;
+    }
+    // interpreter: `a` comes from the instruction word (wave-uniform), so the switch is a scalar branch and the
+    // accumulators stay in registers
+    __device__ __forceinline__ void fold(const hs_agg_spec&, uint32_t a, int, bool live, uint64_t x) {
+        const uint32_t op = hs_spec_op(sb, a);
+        const bool is_int = hs_spec_int(sb, a);
+        const uint64_t v = live ? x : hs_acc_identity(op, is_int);
+        switch (a) {
+#define HS_CASE(K) case K: acc[K] = hs_acc_fold(op, is_int, acc[K], v); break;
+            HS_CASE(0) HS_CASE(1) HS_CASE(2) HS_CASE(3) HS_CASE(4) HS_CASE(5) HS_CASE(6) HS_CASE(7)
+            HS_CASE(8) HS_CASE(9) HS_CASE(10) HS_CASE(11) HS_CASE(12) HS_CASE(13) HS_CASE(14) HS_CASE(15)
+#undef HS_CASE
+            default: err |= HS_FLAG_BAD_PROGRAM; break;
+        }
+    }
+};
+
+template <class Prog>
+__device__ __forceinline__ void hs_agg_scalar_body(const AggMainArgs& A) {
+    static_assert(HS_MAX_ACC == 16, "ScalarCtx::fold names 16 accumulators");
+    extern __shared__ __align__(16) uint64_t hs_lds[];  // [n_waves][n_acc + 1]
+    constexpr int CNA = Prog::STATIC_SPEC ? Prog::NA : HS_MAX_ACC;  // accumulators the code names
+    const uint32_t tid = threadIdx.x, nthr = blockDim.x;
+    const int NA = A.spec.n_acc, NC = NA + 1;
+    const int64_t chunk = blockIdx.x;
+    HS_SCAN_STAMP(0);
+    const hs_chunk desc = A.chunks[chunk];
+    const int64_t us = desc.unit_begin, c0 = desc.row_begin, c1 = desc.row_end;
+    const int64_t stride = (int64_t)nthr * HS_V;
+    int64_t base = c0 + (int64_t)tid * HS_V;
+    typename Prog::Cells cur, nxt;
+    if (base < c1) Prog::load(A, base, nxt);
+    const HsSpecBits sb = hs_spec_bits(A.spec);
+    // kind of accumulator a: a compile-time constant in compiled programs, two scalars otherwise
+    auto op_of = [&](int a) -> uint32_t { return Prog::STATIC_SPEC ? Prog::acc_op(a) : hs_spec_op(sb, (uint32_t)a); };
+    auto int_of = [&](int a) -> bool { return Prog::STATIC_SPEC ? Prog::acc_int(a) : hs_spec_int(sb, (uint32_t)a); };
+
+    ScalarCtx ctx;
+    ctx.sb = sb;
+    ctx.err = 0;
+    ctx.rows = 0;
+#pragma unroll
+    for (int a = 0; a < HS_MAX_ACC; ++a) ctx.acc[a] = a < CNA ? hs_acc_identity(op_of(a), int_of(a)) : 0ull;
+    HS_SCAN_STAMP(2);
+
+    // software pipeline: the loads of step i+1 are in flight while step i is evaluated
+    while (base < c1) {
+        cur = nxt;
+        const int64_t next_base = base + stride;
+        if (next_base < c1) Prog::load(A, next_base, nxt);
+        ctx.row0 = base;
+#pragma unroll
+        for (int j = 0; j < HS_V; ++j) {
+            const int64_t r = base + j;
+            ctx.alive[j] = (r >= us) && (r < c1);  // the first quad of a unit may begin in the previous unit's rows
+            ctx.slot[j] = 0;
+        }
+        Prog::run(A, cur, ctx);
+        if constexpr (!Prog::STATIC_SPEC) {  // (compiled programs count inside run(): their `live` is a local)
+#pragma unroll
+            for (int j = 0; j < HS_V; ++j) ctx.rows += ctx.alive[j] ? 1 : 0;
+        }
+        base = next_base;
+    }
+    HS_SCAN_STAMP(3);
+
+    // lanes -> wave: a fixed shuffle tree per accumulator (all chains in flight together), lane 0 holds the wave's cell
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / HS_WAVE)), lane = tid % HS_WAVE, nwaves = nthr / HS_WAVE;
+    uint64_t rows = (uint64_t)ctx.rows;
+#pragma unroll
+    for (int d = HS_WAVE / 2; d >= 1; d >>= 1) {
+        uint64_t t[CNA > 0 ? CNA : 1];
+#pragma unroll
+        for (int a = 0; a < CNA; ++a) t[a] = hs_shfl_down64(ctx.acc[a], d);
+        const uint64_t tr = hs_shfl_down64(rows, d);
+#pragma unroll
+        for (int a = 0; a < CNA; ++a) ctx.acc[a] = hs_acc_fold(op_of(a), int_of(a), ctx.acc[a], t[a]);
+        rows += tr;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < CNA; ++a)
+            if (a < NA) hs_lds[wave * (uint32_t)NC + (uint32_t)a] = ctx.acc[a];
+        hs_lds[wave * (uint32_t)NC + (uint32_t)NA] = rows;
+    }
+    __syncthreads();
+    HS_SCAN_STAMP(14);
+    // waves -> workgroup: lane a folds cell a of every wave in wave order; the chunk's cell row goes to the workspace
+    if (tid < (uint32_t)NC) {
+        const bool is_rows = tid == (uint32_t)NA;
+        const uint32_t op = is_rows ? (uint32_t)HS_AGG_SUM : hs_spec_op(sb, tid);
+        const bool is_int = is_rows ? true : hs_spec_int(sb, tid);
+        uint64_t v = hs_acc_identity(op, is_int);
+        for (uint32_t w = 0; w < nwaves; ++w) v = hs_acc_fold(op, is_int, v, hs_lds[w * (uint32_t)NC + tid]);
+        hs_st_part(&A.part_acc[chunk * NC + tid], v);
+    }
+    if (ctx.err) atomicOr(A.flags, ctx.err);
+    HS_SCAN_STAMP(4);
+
+    // arrival: the workgroup that brings the unit's count to its number of chunks combines the unit
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __shared__ int s_last;
+    __shared__ int64_t s_bounds[2];
+    __shared__ uint64_t s_rows;
+    const int64_t unit = desc.unit;
+    if (tid == 0) {
+        const int64_t cb = A.unit_chunk0[unit], ce = A.unit_chunk0[unit + 1];
+        s_bounds[0] = cb;
+        s_bounds[1] = ce;
+        const uint32_t need = (uint32_t)(ce - cb);
+        const uint32_t prev = __hip_atomic_fetch_add(&A.unit_arrivals[unit], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = prev + 1 == need;
+        if (s_last) __hip_atomic_store(&A.unit_arrivals[unit], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    HS_SCAN_STAMP(5);
+    if (!s_last) return;  // workgroup-uniform
+    uint64_t v = 0;
+    uint32_t op = HS_AGG_SUM;
+    bool is_int = true;
+    if (tid < (uint32_t)NC) {
+        const bool is_rows = tid == (uint32_t)NA;
+        op = is_rows ? (uint32_t)HS_AGG_SUM : hs_spec_op(sb, tid);
+        is_int = is_rows ? true : hs_spec_int(sb, tid);
+        v = hs_acc_identity(op, is_int);
+        const int64_t cb = s_bounds[0], ce = s_bounds[1];
+        int64_t c = cb;
+        for (; c + 8 <= ce; c += 8) {  // eight chunk cells in flight, folded in chunk order
+            uint64_t t[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t[k] = hs_ld_part<true>(&A.part_acc[(c + k) * NC + tid]);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v = hs_acc_fold(op, is_int, v, t[k]);
+        }
+        for (; c < ce; ++c) v = hs_acc_fold(op, is_int, v, hs_ld_part<true>(&A.part_acc[c * NC + tid]));
+        if (is_rows) s_rows = v;
+    }
+    __syncthreads();
+    const uint64_t kept = s_rows;
+    uint32_t err = 0;
+    if (tid < (uint32_t)NA) {
+        uint64_t q = v;
+        if (kept > 0) {  // a unit without kept rows has no partial row: nothing of it is checked or read
+            if (hs_float_identity_left(op, is_int, v)) err |= HS_FLAG_TYPE_ASSERT;
+            q = hs_quantise_cell(is_int, v, err);
+        }
+        A.unit.out_acc[unit * NA + tid] = q;
+    } else if (tid == (uint32_t)NA) {
+        A.scalar_rows[unit] = (int64_t)kept;
+        A.unit.out_rep[unit] = kept > 0 ? unit : (int64_t)-1;
+        A.unit.out_ngroups[unit] = kept > 0 ? 1 : 0;
+    }
+    if (err) atomicOr(A.flags, err);
     HS_SCAN_STAMP(6);
 }
 

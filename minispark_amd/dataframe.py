@@ -55,6 +55,13 @@ class DataFrame:
     def group_by(self, column: Any) -> GroupedData:
         return GroupedData(self, column)
 
+    def agg(self, *agg_columns: Any) -> "DataFrame":
+        """Aggregates over the whole input, without GROUP BY: one row holding the aggregate columns in the order given,
+        or no row when no input row is left (the value of grouping by a column that is equal in every row)."""
+        if not agg_columns:
+            raise ValueError("agg() needs at least one aggregate column")
+        return self._append(_t.AggregateTask, group_by_column=None, agg_columns=list(agg_columns))
+
     def join(self, other_df: "DataFrame", on: Any, how: _t.JoinType) -> "DataFrame":
         return self._append(_t.BroadcastHashJoinTask, right_side_task=other_df.task, join_condition=on, how=how)
 

@@ -934,7 +934,10 @@ class Device:
         batch = self.resolve(batch)  # units are row ranges: the row count must be exact
         if batch.nrows == 0:  # e.g. a rank that owns no block of a small table
             return self._empty_partial(batch, filters, group_by, agg_columns, out_schema, slab_rows, tail)
-        cap = max(1, int(group_cap_hint))
+        keyless = group_by is None  # an aggregate over the whole input: hs_agg_scalar, one partial row per unit at most
+        cap = 1 if keyless else max(1, int(group_cap_hint))
+        if keyless and (tail or shared or batch.unit_col is not None):
+            raise SlabUnsupported("an aggregate without GROUP BY takes the general tail over row-range units")
         key = None
         if cache_key is not None:
             # every pointer the prepared column table holds: a computed string column is rebuilt per run and the
@@ -982,6 +985,14 @@ class Device:
                                             p["out_rep"].data_ptr(), p["out_acc"].data_ptr(), p["ngroups"].data_ptr(),
                                             p["ws"].data_ptr(), self.flags.data_ptr(), self._event_handle(0),
                                             self._event_handle(1)), "hs_agg_shared")
+        elif keyless:
+            # no key column is read and no table kept: register accumulators, chunk rows folded in chunk order
+            hs.check(self.lib.hs_agg_scalar(self.stream, p["cols"], p["n_cols"], C.byref(p["prog"]), C.byref(p["spec"]),
+                                            p["d_units"].data_ptr(), p["d_chunk0"].data_ptr(), p["n_units"],
+                                            C.byref(p["geom"]), p["out_acc"].data_ptr(), p["out_rows"].data_ptr(),
+                                            p["out_rep"].data_ptr(), p["ngroups"].data_ptr(), p["ws"].data_ptr(),
+                                            self.flags.data_ptr(), self._event_handle(0), self._event_handle(1)),
+                     "hs_agg_scalar")
         else:
             hs.check(self.lib.hs_agg_partial(self.stream, p["cols"], p["n_cols"], p["key_slot"], C.byref(p["prog"]),
                                              C.byref(p["spec"]), p["d_units"].data_ptr(), p["d_chunk0"].data_ptr(),
@@ -999,7 +1010,8 @@ class Device:
         # a dictionary overflow is noticed at the query's final read-back and the query re-run.
         n_max = p["slots"]
         n_dev = p["pack_start"][p["n_units"]:]
-        key_col = self.gather_col(batch.cols[p["key_idx"]], p["dense_rep"], n_max, n_dev, out=p["key_out"])
+        key_src = p["key_src"] if keyless else batch.cols[p["key_idx"]]
+        key_col = self.gather_col(key_src, p["dense_rep"], n_max, n_dev, out=p["key_out"])
         if key_col.n != n_max:  # variable-length string keys made the count exact
             n_max, n_dev = key_col.n, None
         out_cols = [key_col]
@@ -1018,7 +1030,8 @@ class Device:
         """Partial aggregate of zero rows (a rank that owns no block): no launch, but the same column /
         slab layout as the other ranks so the exchange stays symmetric."""
         low = lower_aggregate(batch.schema, batch.kinds, filters, group_by, agg_columns, batch.dicts)
-        key_src = batch.cols[low.program.columns[low.key_slot]]
+        key_src = (batch.cols[low.program.columns[low.key_slot]] if group_by is not None
+                   else DCol(hs.I32, self.empty(0, torch.int32), 0))  # the constant key the partial rows merge under
         acc_kinds = [hs.I32 if is_int else hs.F32 for is_int in low.acc_is_int]
         if tail:
             if slab_rows is None:
@@ -1078,6 +1091,7 @@ class Device:
             raise TierExceeded(f"aggregate reads more than {hs.HS_FUSED_COLS} numeric columns")
         n_units = batch.n_units
         n_acc = len(low.acc_ops)
+        keyless = group_by is None
         computed = batch.unit_col is not None
         if computed:
             # units are per-row ids: ONE row range for the chunking, batch.n_unit_ids unit tables for the outputs
@@ -1093,7 +1107,9 @@ class Device:
         else:
             host_units = (C.c_int64 * (n_units + 1))(*batch.unit_rows)
         geom = hs.hs_agg_geom()
-        if shared:
+        if keyless:
+            rc = self.lib.hs_agg_scalar_geom(host_units, n_units, n_acc, C.byref(geom))
+        elif shared:
             rc = self.lib.hs_agg_shared_geom(host_units, n_units, n_acc, cap, C.byref(geom))
         else:
             rc = self.lib.hs_agg_partial_geom(host_units, n_units, n_acc, cap, C.byref(geom))
@@ -1123,9 +1139,14 @@ class Device:
             n_units = batch.n_unit_ids  # from here on: the unit tables
         slots = n_units * unit_cap
         acc_kinds = [hs.I32 if is_int else hs.F32 for is_int in low.acc_is_int]
-        key_idx = low.program.columns[low.key_slot]
+        key_idx = low.program.columns[low.key_slot] if not keyless else None
+        # keyless: the partial rows are merged under ONE constant INTEGER key, a column of n_units zeros (never per-row
+        # traffic); the unit rows name their own entry of it
+        key_src = DCol(hs.I32, torch.zeros(max(n_units, 1), dtype=torch.int32, device=self.device), n_units) if keyless else None
         slab = layout = key_out = out_unit = None
         if tail:
+            if keyless:  # (hs_agg_scalar has no slab form of the unit row: _aggregate_partial refuses before it gets here)
+                raise SlabUnsupported("an aggregate without GROUP BY takes the general tail")
             rows = slab_rows if slab_rows is not None else slots
             if slots > rows:
                 raise DeviceError(f"exchange slab of {rows} rows cannot hold {slots} partial rows")
@@ -1151,7 +1172,7 @@ class Device:
 
             if slots > slab_rows:
                 raise DeviceError(f"exchange slab of {slab_rows} rows cannot hold {slots} partial rows")
-            kc = batch.cols[key_idx]
+            kc = key_src if keyless else batch.cols[key_idx]
             if kc.kind == hs.STR:
                 if kc.fixed_len not in (1, 2, 4, 8):
                     raise SlabUnsupported("variable-length string GROUP BY key")
@@ -1184,7 +1205,8 @@ class Device:
         return {
             "slab": slab, "layout": layout, "key_out": key_out, "out_unit": out_unit, "d_unit_ids": d_unit_ids,
             "cols": cols_arr, "n_cols": n_cols, "unit_slot": unit_slot,
-            "key_slot": low.key_slot, "key_idx": key_idx, "prog": low.program.to_struct(),
+            "key_slot": low.key_slot, "key_idx": key_idx, "key_src": key_src, "prog": low.program.to_struct(),
+            "out_rows": self.empty(max(n_units, 1), torch.int64) if keyless else None,
             "spec": low.spec(), "geom": geom, "n_units": n_units, "slots": slots, "unit_cap": unit_cap,
             "agg_to_acc": low.agg_to_acc,
             "d_units": self.to_device(chunks.reshape(-1)), "d_chunk0": self.to_device(chunk0),
@@ -1196,7 +1218,7 @@ class Device:
             "kinds_arr": (C.c_int32 * max(n_acc, 1))(*acc_kinds),
             "info": {"rows": batch.nrows, "chunks": int(geom.n_chunks), "chunk_rows": int(geom.chunk_rows),
                      "wg_threads": int(geom.wg_threads), "group_cap": cap, "lds_bytes": int(geom.lds_bytes),
-                     "tier": "shared" if shared else "private"},
+                     "tier": "scalar" if keyless else "shared" if shared else "private"},
         }
 
     # ---- final merge (A7) ------------------------------------------------------------------------------

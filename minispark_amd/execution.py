@@ -20,6 +20,7 @@ Inter-stage "shuffle files" stay in HBM as device batches (already quantised to 
 
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 import sys
@@ -41,6 +42,9 @@ class ExecutionError(Exception):
         super().__init__(message)
 
 
+# name of the constant INTEGER key under which the partial rows of an aggregate without GROUP BY are merged: it exists
+# between the partial aggregate and the final merge only and is no column of any result
+KEYLESS_KEY = "__hs_whole_input"
 PRIVATE_TIER_MAX = 16    # dictionary slots per workgroup up to which every lane keeps private accumulators
 SHARED_TIER_MAX = 4096   # ... and up to which one LDS dictionary per workgroup is used; beyond: the HBM tier
 
@@ -565,11 +569,34 @@ class HipExecutionEngine(ExecutionEngine):
         for stage in plan.stages:
             for task in (stage.producer, *stage.consumers, stage.writer):
                 getattr(task, "__dict__", {}).pop("_hs_uid", None)
+        self._mark_keyless(plan)
         self._mark_short_tails(plan)
         if len(self._plans) >= 16:
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = (full_task, plan)
         return plan
+
+    @staticmethod
+    def _mark_keyless(plan: Any) -> None:
+        """An aggregate without GROUP BY runs as the query grouped by a constant: between the partial aggregate and the
+        final merge its rows carry the KEYLESS_KEY column (n_units zeros made on the device - never a column of the
+        table), so shuffle write, exchange, streaming in ranges and merge are the grouped query's.  The planner's
+        schemas of exactly these four nodes get the key in front (the plan is the engine's own copy); _consume drops
+        the column right after the merge."""
+        from .constants import ColumnType  # noqa: PLC0415
+
+        key = (KEYLESS_KEY, ColumnType.INTEGER)
+        for stage in plan.stages:
+            for task in stage.consumers:
+                if _cls(task) != "AggregateTask" or task.group_by_column is not None:
+                    continue
+                edge = stage.writer if task.before_shuffle else stage.producer
+                want = "WriteToShufflePartitions" if task.before_shuffle else "LoadShuffleFilesTask"
+                if _cls(edge) != want:
+                    raise ExecutionError(f"aggregate without GROUP BY: unexpected stage shape around {task.describe()}")
+                for node in (task, edge):
+                    if not node.inferred_schema or node.inferred_schema[0] != key:
+                        node.inferred_schema = [key, *(node.inferred_schema or [])]
 
     @staticmethod
     def _mark_short_tails(plan: Any) -> None:
@@ -582,6 +609,8 @@ class HipExecutionEngine(ExecutionEngine):
                 continue
             if not consumers or _cls(consumers[0]) != "AggregateTask" or consumers[0].before_shuffle:
                 continue
+            if consumers[0].group_by_column is None:
+                continue  # an aggregate without GROUP BY: its few partial rows take the general merge
             if any(_cls(t) == "SortTask" for t in consumers):
                 continue  # ORDER BY / LIMIT: the finish launch hands its rows straight to the host; _run_stage orders them
             if len(consumers) > 2 or (len(consumers) == 2 and _cls(consumers[1]) != "ProjectTask"):
@@ -628,7 +657,9 @@ class HipExecutionEngine(ExecutionEngine):
                 batch = self._exchange_partials(batch) if batch.slab is not None else self._exchange_partial_rows(batch)
         elif kind == "BroadcastHashJoinTask":
             first_real = next((t for t in consumers if _cls(t) != "FilterTask"), None)
-            feeds_aggregate = first_real is not None and _cls(first_real) == "AggregateTask" and first_real.before_shuffle
+            # (an aggregate without GROUP BY reads the join's materialised rows: none of the fused join forms carries it)
+            feeds_aggregate = (first_real is not None and _cls(first_real) == "AggregateTask" and first_real.before_shuffle
+                               and first_real.group_by_column is not None)
             if isinstance(outputs[id(stage.dependencies[1])], _DeferredScan):
                 self._refuse_sort_in_pieces(sort, writer)
                 return self._run_join_stage_streamed(stage, outputs, feeds_aggregate)
@@ -709,6 +740,10 @@ class HipExecutionEngine(ExecutionEngine):
                 batch = self._project(batch, pending, task)
                 pending = []
             elif tname == "AggregateTask":
+                if task.before_shuffle and task.group_by_column is None:
+                    batch = self._aggregate_whole_input(batch, pending, task)
+                    pending = []
+                    continue
                 if task.before_shuffle and batch.join8 is not None:
                     # the join's probe runs inside this aggregate's scan; what it cannot hold sends the
                     # query back through the materialising joins
@@ -815,9 +850,35 @@ class HipExecutionEngine(ExecutionEngine):
                             self._global_merge.add(_uid(task))
                         batch = self.dev.aggregate_merge_global(batch, task.agg_columns, task.inferred_schema)
                     batch.partitioned = was_partitioned
+                    if task.group_by_column is None:
+                        # the constant merge key has done its work: the result holds the aggregate columns only
+                        batch = dataclasses.replace(batch, schema=list(batch.schema)[1:], cols=list(batch.cols)[1:])
             else:
                 raise NotImplementedError(f"consumer {tname}")
         return self._materialise(batch, pending)
+
+    def _aggregate_whole_input(self, batch: Any, pending: Sequence[Any], task: Any) -> Any:
+        """The partial phase of an aggregate without GROUP BY (hs_agg_scalar): at most one partial row per unit, under
+        the constant KEYLESS_KEY; everything after it is the grouped query's general path."""
+        from .device import SlabUnsupported, TierExceeded  # noqa: PLC0415
+
+        if batch.join8 is not None or batch.unit_col is not None:
+            raise ExecutionError("aggregate without GROUP BY over a join left in place: the join must materialise its rows")
+        slab_rows = None
+        if self.dist is not None:
+            from .distributed import max_local_units  # noqa: PLC0415
+
+            if batch.total_units is None:
+                raise ExecutionError("aggregate without GROUP BY on N ranks needs a block-partitioned input")
+            slab_rows = max(batch.n_units, max_local_units(batch.total_units, self.world))
+        try:
+            batch = self.dev.aggregate_partial(batch, pending, None, task.agg_columns, task.inferred_schema, 1,
+                                               cache_key=(_uid(task), "scalar"), slab_rows=slab_rows)
+        except (SlabUnsupported, TierExceeded) as e:
+            # there is no other tier to fall back to, and a wrong answer is never acceptable
+            raise ExecutionError(f"aggregate without GROUP BY: {e}") from None
+        batch.partitioned = self.dist is not None and batch.slab is None
+        return batch
 
     # ---- producers -------------------------------------------------------------------------------------
     # ---- tables beyond HBM (SURVEY 8f N2): the scan stage in block ranges -------------------------------------------------
@@ -1057,7 +1118,8 @@ class HipExecutionEngine(ExecutionEngine):
                     needed += _plain_names(col)
                 break
             elif tname == "AggregateTask":
-                needed += _plain_names(task.group_by_column)
+                if task.group_by_column is not None:
+                    needed += _plain_names(task.group_by_column)
                 for agg in task.agg_columns:
                     needed += _plain_names(agg)
                 break
@@ -1150,7 +1212,8 @@ class HipExecutionEngine(ExecutionEngine):
                     needed.update(_plain_names(col))
                 return needed
             elif tname == "AggregateTask":
-                needed.update(_plain_names(task.group_by_column))
+                if task.group_by_column is not None:
+                    needed.update(_plain_names(task.group_by_column))
                 for agg in task.agg_columns:
                     needed.update(_plain_names(agg))
                 return needed

@@ -323,6 +323,8 @@ SIGNATURES: dict[str, tuple] = {
                                       _P, _P, _P, _P, _P, _P, _P]),
     "hs_agg_units_merge": (C.c_int, [_P, _P, _I32, _I32, _I32, _SPECP, _P, _P, _P]),
     "hs_agg_units_to_slab": (C.c_int, [_P, _P, _P, _I32, _I32, _SPECP, _P, C.POINTER(hs_slab_desc), _P]),
+    "hs_agg_scalar_geom": (C.c_int, [C.POINTER(_I64), _I64, _I32, _GEOMP]),
+    "hs_agg_scalar": (C.c_int, [_P, _COLP, _I32, _PROGP, _SPECP, _P, _P, _I64, _GEOMP, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hs_agg_partial_slab": (
         C.c_int,
         [_P, _COLP, _I32, _I32, _PROGP, _SPECP, _P, _P, _I64, _GEOMP, _P, _P, C.POINTER(hs_slab_desc), _P, _P, _P, _P],
@@ -404,6 +406,7 @@ SIGNATURES: dict[str, tuple] = {
     "hs_jit_compile_check": (C.c_int, [_COLP, _I32, _I32, _PROGP, _SPECP, C.c_char_p, C.POINTER(_I64), C.c_char_p, _I64]),
     "hs_jit_compile_check_shared": (C.c_int, [_COLP, _I32, _I32, _I32, _PROGP, _SPECP, C.c_char_p, C.POINTER(_I64),
                                               C.c_char_p, _I64]),
+    "hs_jit_compile_check_scalar": (C.c_int, [_COLP, _I32, _PROGP, _SPECP, C.c_char_p, C.POINTER(_I64), C.c_char_p, _I64]),
     "hs_jit_compile_check_eval": (C.c_int, [_COLP, _I32, _PROGP, C.POINTER(_I32), _I32, C.c_char_p, C.POINTER(_I64),
                                             C.c_char_p, _I64]),
     "hs_engine_create": (C.c_int, [_I32, C.POINTER(_P)]),

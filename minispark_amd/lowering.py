@@ -459,15 +459,18 @@ def lower_aggregate(schema: Schema, kinds: Sequence[int], filters: Sequence[Any]
     """[filter ... FILTER]* KEY [arg ... AGG acc]* for one partial-aggregate launch.
 
     Aggregates with the same function and structurally equal argument share an accumulator (Q1's
-    eleven aggregate columns need six)."""
+    eleven aggregate columns need six).  ``group_by=None`` (an aggregate over the whole input, hs_agg_scalar): the same
+    program without KEY, no key column among ``Program.columns``, ``key_slot`` -1."""
     b = ProgramBuilder(schema, kinds, dicts)
     for cond in filters:
         b.emit_filter(cond)
-    key = unalias(group_by)
-    if _cls(key) not in ("Col", "SchemaCol"):
-        raise ValueError(f"Unknown columns in GroupBy: {[getattr(key, 'name', key)]}")
-    key_col = b.use_column(key.name)
-    b.emit_key()
+    key_col = None
+    if group_by is not None:
+        key = unalias(group_by)
+        if _cls(key) not in ("Col", "SchemaCol"):
+            raise ValueError(f"Unknown columns in GroupBy: {[getattr(key, 'name', key)]}")
+        key_col = b.use_column(key.name)
+        b.emit_key()
     acc_index: dict[tuple, int] = {}
     acc_ops: list[int] = []
     acc_is_int: list[bool] = []
@@ -487,7 +490,8 @@ def lower_aggregate(schema: Schema, kinds: Sequence[int], filters: Sequence[Any]
         agg_to_acc.append(acc_index[ident])
     prog = b.finish(key_column=key_col)
     numeric_slots = sum(1 for c in prog.columns if kinds[c] != hs.STR or c == key_col or c in prog.code_columns)
-    return AggregateLowering(prog, prog.columns.index(key_col), acc_ops, acc_is_int, agg_to_acc, numeric_slots)
+    key_slot = prog.columns.index(key_col) if key_col is not None else -1
+    return AggregateLowering(prog, key_slot, acc_ops, acc_is_int, agg_to_acc, numeric_slots)
 
 
 class FinishUnsupported(Exception):
@@ -498,11 +502,14 @@ _FILE_KIND = {ColumnType.INTEGER: hs.I32, ColumnType.FLOAT: hs.F32, ColumnType.T
 
 
 def lower_finish(agg_to_acc: Sequence[int], acc_kinds: Sequence[int], key_kind: int, agg_columns: Sequence[Any],
-                 merged_schema: Schema, project: Sequence[Any] | None, out_schema: Schema) -> tuple:
+                 merged_schema: Schema, project: Sequence[Any] | None, out_schema: Schema,
+                 keyless: bool = False) -> tuple:
     """The final stage - merge of the partial rows (reference tasks.py:290-292), the projection after it
     (plan.py:190-203: AVG = sum / count, renames) and the stored kinds of the result file (io.py:87-94) - as the
     description hs_agg_finish takes: -> (hs_finish_spec without offsets, hs_program or None, [(src, index, stored kind)]).
-    Pure lowering (no device): used by the engine's short tail and by the stage-level ABI (minispark_amd/stage.py)."""
+    Pure lowering (no device): used by the engine's short tail and by the stage-level ABI (minispark_amd/stage.py).
+    ``keyless``: the partial rows of an aggregate without GROUP BY - column 0 of ``merged_schema`` is the constant key
+    they are merged under, which is no column of the result: no (0, 0, key_kind) output, no program slot reading it."""
     ops = {"sum": hs.AGG_SUM, "min": hs.AGG_MIN, "max": hs.AGG_MAX}
     fin = hs.hs_finish_spec()
     folds: dict[tuple[int, int], int] = {}
@@ -530,11 +537,13 @@ def lower_finish(agg_to_acc: Sequence[int], acc_kinds: Sequence[int], key_kind: 
     outs: list[tuple[int, int, int]] = []  # (src, index, stored kind)
     prog = None
     if project is None:
-        if len(out_schema) != len(merged_kinds):
+        if len(out_schema) != len(merged_kinds) - (1 if keyless else 0):
             raise AssertionError(f"writer schema {out_schema} does not match merged columns {merged_schema}")
-        outs.append((0, 0, key_kind))
+        if not keyless:
+            outs.append((0, 0, key_kind))
+        shift = 0 if keyless else 1
         for i in range(len(agg_columns)):
-            outs.append((1, col_fold[i], stored(merged_kinds[i + 1], out_schema[i + 1][1])))
+            outs.append((1, col_fold[i], stored(merged_kinds[i + 1], out_schema[i + shift][1])))
     else:
         if len(out_schema) != len(project):
             raise AssertionError(f"writer schema {out_schema} does not match the projection")
@@ -547,6 +556,8 @@ def lower_finish(agg_to_acc: Sequence[int], acc_kinds: Sequence[int], key_kind: 
                 idx = names.index(bare.name) if bare.name in names else -1
                 if idx < 0:
                     raise ValueError(f'Column "{bare.name}" not found in schema {merged_schema}')
+                if idx == 0 and keyless:
+                    raise ValueError(f'Column "{bare.name}" not found in schema {merged_schema[1:]}')
                 if idx == 0:
                     outs.append((0, 0, key_kind))
                 else:
@@ -565,6 +576,8 @@ def lower_finish(agg_to_acc: Sequence[int], acc_kinds: Sequence[int], key_kind: 
         if n_prog:
             lowered = b.finish()
             for slot, idx in enumerate(lowered.columns):
+                if idx == 0 and keyless:
+                    raise ValueError(f"the projection reads the merge key of an aggregate without GROUP BY: {merged_schema[0]}")
                 if idx == 0 and key_kind == hs.STR:
                     raise FinishUnsupported("expression over a string key after the merge")
                 fin.prog_src[slot] = -1 if idx == 0 else col_fold[idx - 1]

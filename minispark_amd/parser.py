@@ -10,6 +10,9 @@ A hand-written backtracking recursive-descent parser for the same language:
 * select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e) [AS name]``, ``expr [AS name]``;
 * conditions: OR < AND < NOT < comparison | ( cond ) | BETWEEN | LIKE, comparators = != <= >= < >;
 * expressions: + - over * / over atoms (number, column, string literal, ( expr ), COUNT()/SUM(e));
+* a select list of aggregate calls only and no GROUP BY aggregates the whole table (``DataFrame.agg``): one row, or none
+  when no row survives the WHERE; mixing aggregates and plain columns without GROUP BY raises ``GroupByError``, HAVING
+  without GROUP BY stays a syntax error, arithmetic over aggregates (``SUM(a) / SUM(b)``) is not part of this form;
 * like the reference: whitespace is required around keywords, the closing ``;`` is mandatory, every join kind
   is executed as an inner join (parser.py:131-133), numbers are integers (parser.py:349), NOT raises
   NotImplementedError (sql.py:44-45), GROUP BY takes one column (dataframe.py:64);
@@ -161,6 +164,14 @@ class _Parser:
             if having is not None:
                 df = df.filter(having.normalize_agg_columns())
             df = df.select(*[Col(c.name) for c in select_list])
+        elif any(type(c) is AggCol for c in select_list):
+            stray = [c for c in select_list if type(c) is not AggCol]
+            if stray:
+                raise GroupByError(
+                    "Without GROUP BY a select list holds either aggregate functions only or none at all:\n"
+                    f"{stray}"
+                )
+            df = df.agg(*select_list)
         else:
             df = df.select(*select_list)
         if has_order:

@@ -11,7 +11,8 @@ Rewrites applied, in the reference's order (plan.py:224-235):
 
 1. wrap the chain in ``WriteToLocalFileTask``; infer schemas bottom-up;
 2. ``expand``: AggregateTask -> [Aggregate(before_shuffle) -> WriteToShufflePartitions(key) ->
-   LoadShuffleFiles -> Aggregate(after)] (+ ProjectTask computing AVG = sum/count, plan.py:190-203);
+   LoadShuffleFiles -> Aggregate(after)] (+ ProjectTask computing AVG = sum/count, plan.py:190-203); an aggregate
+   without GROUP BY (this build's own) expands alike with ``key=None`` and no key column in the projection;
    join inputs each get a WriteToShufflePartitions on their key (plan.py:186-189);
 3. strip ``alias.`` prefixes from the output column names with a final ProjectTask (plan.py:207-222);
 4. cut the chain into stages at every shuffle write / join, dependencies first.
@@ -136,9 +137,8 @@ class PhysicalPlan:
             task.before_shuffle = False
             task.agg_columns = [AggCol(agg.type, Col(agg.name)) for agg in carried]
             if any(agg.type == "avg" for agg in requested):
-                return ProjectTask(
-                    task, columns=[Col(task.group_by_column.name), *[agg.projection() for agg in requested]]
-                )
+                key = [] if task.group_by_column is None else [Col(task.group_by_column.name)]
+                return ProjectTask(task, columns=[*key, *[agg.projection() for agg in requested]])
         return task
 
     @staticmethod

@@ -118,7 +118,13 @@ def read_result_file(path: Path | str) -> list[Row]:
 # ---- what the five lowerings share ---------------------------------------------------------------------------------------
 def _plan_of(full_task: Any, plan: Any) -> list:
     """The stages of ``plan``, or of the physical plan of ``full_task`` when none is given."""
-    return list((plan if plan is not None else PhysicalPlan.generate_physical_plan(full_task)).stages)
+    stages = list((plan if plan is not None else PhysicalPlan.generate_physical_plan(full_task)).stages)
+    for stage in stages:
+        for task in stage.consumers:
+            if _cls(task) == "AggregateTask" and task.group_by_column is None:
+                # (the stage blobs describe a key column; the engine runs this form through hs_agg_scalar)
+                raise StageUnsupported("an aggregate without GROUP BY")
+    return stages
 
 
 def _partial_of(consumers: Any, where: str, before: Any) -> Any:

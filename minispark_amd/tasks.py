@@ -195,9 +195,10 @@ class BroadcastHashJoinTask(ProducerTask):
 class AggregateTask(ConsumerTask):
     """Hash group-by on ONE plain column.  ``before_shuffle`` = the per-job partial phase, otherwise
     the merge phase that combines column i+1 of the shuffled partial rows with aggregate i
-    (tasks.py:263-340)."""
+    (tasks.py:263-340).  ``group_by_column=None`` (no reference counterpart) aggregates the whole input: the value of
+    grouping by a column that is equal in every row, without that column - one row, or none when no row came in."""
 
-    group_by_column: Col
+    group_by_column: Col | None
     agg_columns: list[AggCol]
     before_shuffle: bool = True
 
@@ -205,6 +206,9 @@ class AggregateTask(ConsumerTask):
         schema = self.parent_task.validate_schema()
         if not self.before_shuffle:
             return schema
+        if self.group_by_column is None:
+            _check_known(list(self.agg_columns), schema, "aggregation")
+            return [(agg.name, agg.infer_type(schema)) for agg in self.agg_columns]
         _check_known([*self.agg_columns, self.group_by_column], schema, "aggregation")
         return [
             (self.group_by_column.name, self.group_by_column.infer_type(schema)),
@@ -212,6 +216,8 @@ class AggregateTask(ConsumerTask):
         ]
 
     def describe(self) -> str:
+        if self.group_by_column is None:
+            return f"AggregateTask(whole input, agg: {self.agg_columns}, before_shuffle:{self.before_shuffle})"
         return (
             f"AggregateTask(group_by: {self.group_by_column}, agg: {self.agg_columns}, "
             f"before_shuffle:{self.before_shuffle})"

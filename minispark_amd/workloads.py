@@ -57,6 +57,23 @@ def q1(api: Any, path: str, cutoff: str = Q1_CUTOFF) -> Any:
     )
 
 
+Q6_FROM, Q6_TO = "1994-01-01", "1995-01-01"
+
+
+def q6(api: Any, path: str, date_from: str = Q6_FROM, date_to: str = Q6_TO, group_by: str | None = None) -> Any:
+    """TPC-H Q6's shape: a selective WHERE (date range, discount band, quantity cap) and ONE SUM over the whole
+    table - an aggregate without GROUP BY (``DataFrame.agg``; reads 3 x f32 + i64 = 20 B/row, no key column).  The
+    WHERE is three filters in a row: AND joins conditions over one type only (the reference's type inference).
+    ``group_by``: the same under GROUP BY that column (benchmarks: a column holding one value in every row)."""
+    C, F, Lit = api.Col, api.F, api.Lit
+    frame = (api.DataFrame().table(path)
+             .filter((C("l_shipdate") >= date_from) & (C("l_shipdate") < date_to))
+             .filter((C("l_discount") >= Lit(0.05)) & (C("l_discount") <= Lit(0.07)))
+             .filter(C("l_quantity") < Lit(24)))
+    revenue = F.sum(C("l_extendedprice") * C("l_discount")).alias("revenue")
+    return frame.group_by(C(group_by)).agg(revenue) if group_by else frame.agg(revenue)
+
+
 def join_group(api: Any, orders_path: str, lineitem_path: str) -> Any:
     """BASELINE config 4.  The build side is ``orders`` (the reference builds its hash table over the LEFT input,
     tasks.py:201-222), the probe side ``lineitem``; aggregates: COUNT, SUM(l_quantity), SUM and MAX of
