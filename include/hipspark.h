@@ -560,6 +560,24 @@ size_t hs_order_by_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words
 int hs_order_by(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_keys, int64_t nrows,
                 const int64_t* nrows_dev, int64_t limit /* <0: none */, int64_t* out_perm, int64_t* out_count, void* ws,
                 uint32_t* flags);
+/* SELECT DISTINCT over result rows (no reference counterpart: the reference has no DISTINCT).  out_perm[0 .. *out_count)
+ * (*out_count: HOST int64) = the surviving input rows in ASCENDING order; out_perm has room for nrows entries.  Two rows
+ * are equal iff all their key words are equal, the words being hs_order_by's over keys[0 .. n_keys), all ascending:
+ * integers by value, -0.0 = +0.0, every NaN equal to every other NaN, strings by bytes and length ('a' is not 'a\0'), a
+ * dictionary-coded column by its code byte.  Of every set of equal rows the FIRST in input order survives (the caller
+ * gathers the columns through out_perm, so the survivor keeps its own bits: a -0.0 that comes first is returned as -0.0),
+ * and the survivors keep their input order: the result is a function of the rows alone.
+ * Steps: hs_order_by's stable sort by all keys without a limit (equal rows become neighbours, in input order); one
+ * pass marks the first row of every run, forming the words of a row and of its left neighbour again, and scatters the
+ * marks into a byte mask in input order; hs_compact's ranked compaction of the mask gives out_perm - no second sort, no
+ * atomics.  rows = min(nrows, *nrows_dev) (nrows_dev: device int64, may be null).  1 <= n_keys <= HS_MAX_COLS
+ * (HS_E_LIMIT above, before anything is launched).  Like hs_order_by the call reads words back between its steps (which
+ * bytes vary, the longest string, how many rows survive): it synchronises the stream and must not be captured
+ * (hs_capture_begin).  ws: hs_distinct_ws_bytes(nrows, n_keys, max_key_words) bytes (the sort's workspace + nrows mask
+ * bytes + the compaction's).  flags: as for hs_order_by; no bit is raised at present (may be null). */
+size_t hs_distinct_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words);
+int hs_distinct(void* stream, const hs_col* keys, int32_t n_keys, int64_t nrows, const int64_t* nrows_dev,
+                int64_t* out_perm, int64_t* out_count /* HOST */, void* ws, uint32_t* flags);
 /* out[i] = values[s] for bounds[s] <= i < bounds[s+1], i in [0, n) (device arrays; bounds has n_seg + 1 entries,
  * bounds[0] = 0): the global block id of every partial row of a multi-rank partial aggregate. */
 int hs_expand_by_bounds(void* stream, const int64_t* bounds, const int64_t* values, int64_t n_seg, int64_t n, int64_t* out);

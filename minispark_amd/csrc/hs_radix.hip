@@ -1768,6 +1768,34 @@ __device__ __forceinline__ uint64_t ob_numeric(const hs_col& c, int64_t row) {
     }
 }
 
+// bytes [off, off + nbytes) of key k's run (which starts at byte `at` of the row's key) that fall into word w: one
+// layout rule for the host, which lists a word's parts for k_ob_keys, and for k_distinct_heads, which walks every word
+__host__ __device__ inline bool ob_part_of(int32_t k, int64_t at, int32_t width, int32_t w, ObPart& out) {
+    const int64_t b = at > (int64_t)w * 8 ? at : (int64_t)w * 8;
+    const int64_t e = at + width < (int64_t)(w + 1) * 8 ? at + width : (int64_t)(w + 1) * 8;
+    if (b >= e) return false;
+    out = ObPart{k, (int32_t)(b - at), (int32_t)(e - b), (int32_t)(b - (int64_t)w * 8)};
+    return true;
+}
+
+// one part of a row's key word, in its place in the word: the encoding of every key type (k_ob_keys ORs the parts of
+// one word; k_distinct_heads re-forms the words of two rows with it, so its equality IS the sort's)
+__device__ __forceinline__ uint64_t ob_part_bits(const ObKeys& A, const ObPart part, int64_t row) {
+    const hs_col& c = A.col[part.key];
+    const uint64_t mask = part.nbytes == 8 ? ~0ull : (1ull << (8 * part.nbytes)) - 1ull;
+    uint64_t chunk = 0;
+    if (c.kind == HS_STR) {
+        const HsStr s = hs_str_at(c, row);
+        const uint32_t cap = (uint32_t)A.str_cap[part.key];
+        for (uint32_t j = (uint32_t)part.off; j < (uint32_t)(part.off + part.nbytes); ++j)
+            chunk = (chunk << 8) | (uint64_t)(j < cap ? (j < s.len ? s.p[j] : 0u) : s.len);
+    } else {
+        chunk = (ob_numeric(c, row) >> (8 * (A.width[part.key] - part.off - part.nbytes))) & mask;
+    }
+    if (A.desc[part.key]) chunk ^= mask;
+    return chunk << (8 * (8 - part.pos - part.nbytes));
+}
+
 __global__ void __launch_bounds__(OB_THREADS) k_ob_keys(const ObKeys A_kernarg) {
     HS_KERNARG(ObKeys, A);
     const int lane = threadIdx.x & (HS_WAVE - 1);
@@ -1775,22 +1803,7 @@ __global__ void __launch_bounds__(OB_THREADS) k_ob_keys(const ObKeys A_kernarg) 
     for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * OB_THREADS) {
         const int64_t row = A.rows ? A.rows[i] : i;
         uint64_t word = 0;
-        for (int p = 0; p < A.n_parts; ++p) {
-            const ObPart part = A.part[p];
-            const hs_col& c = A.col[part.key];
-            const uint64_t mask = part.nbytes == 8 ? ~0ull : (1ull << (8 * part.nbytes)) - 1ull;
-            uint64_t chunk = 0;
-            if (c.kind == HS_STR) {
-                const HsStr s = hs_str_at(c, row);
-                const uint32_t cap = (uint32_t)A.str_cap[part.key];
-                for (uint32_t j = (uint32_t)part.off; j < (uint32_t)(part.off + part.nbytes); ++j)
-                    chunk = (chunk << 8) | (uint64_t)(j < cap ? (j < s.len ? s.p[j] : 0u) : s.len);
-            } else {
-                chunk = (ob_numeric(c, row) >> (8 * (A.width[part.key] - part.off - part.nbytes))) & mask;
-            }
-            if (A.desc[part.key]) chunk ^= mask;
-            word |= chunk << (8 * (8 - part.pos - part.nbytes));
-        }
+        for (int p = 0; p < A.n_parts; ++p) word |= ob_part_bits(A, A.part[p], row);
         A.out_words[i] = word;
         if (A.first) A.out_rows[i] = row;
         all_and &= word;
@@ -1946,27 +1959,28 @@ static bool ob_kind_ok(const hs_col& c) {
     }
 }
 
-extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_keys, int64_t nrows,
-                           const int64_t* nrows_dev, int64_t limit, int64_t* out_perm, int64_t* out_count, void* ws_,
-                           uint32_t* flags) {
-    (void)flags;
-    if (n_keys < 0 || nrows < 0 || !out_perm || !out_count || !ws_ || (n_keys > 0 && (!keys || !descending)) ||
-        (n_keys == 0 && limit < 0)) {
-        hs_set_error("hs_order_by: bad arguments");
-        return HS_E_ARG;
+// a launch inside ob_sort: the error names the entry point that called
+#define OB_CHECK_LAUNCH(what)                                        \
+    if (hipGetLastError() != hipSuccess) {                           \
+        hs_set_error("%s (" what "): kernel launch failed", name);   \
+        return HS_E_LAUNCH;                                          \
     }
-    if (n_keys > HS_MAX_COLS) {
-        hs_set_error("hs_order_by: more than %d keys", HS_MAX_COLS);
-        return HS_E_LIMIT;
-    }
-    *out_count = 0;
-    if (nrows == 0 || limit == 0) return HS_OK;
-    for (int k = 0; k < n_keys; ++k)
-        if (!ob_kind_ok(keys[k])) {
-            hs_set_error("hs_order_by: key %d is not a column that can be ordered", k);
-            return HS_E_ARG;
-        }
-    hipStream_t stream = (hipStream_t)stream_;
+
+// what the sort leaves behind for its callers
+struct ObSorted {
+    ObKeys keys;          // col / width / str_cap / desc as the sort used them
+    int32_t n_words;      // 64-bit words of a row's key
+    int64_t n, count;     // rows = min(nrows, *nrows_dev); rows of the answer = min(rows, limit)
+    const int64_t* rows;  // the answer's rows in order (in the workspace); null: the rows in place (the keys have no byte)
+    size_t ws_bytes;      // bytes of the workspace the sort laid out: what follows them is the caller's
+    const uint64_t* words;  // word 0 of the answer's rows, in their order (null with `rows`)
+};
+
+// The sort of hs_order_by, shared with hs_distinct: checked arguments in, *out_count (HOST) and `S` out.  nrows > 0,
+// limit != 0, 0 <= n_keys <= HS_MAX_COLS, every key ob_kind_ok.  `name`: the calling entry point, for the error texts.
+static int ob_sort(hipStream_t stream, const hs_col* keys, const int32_t* descending, int32_t n_keys, int64_t nrows,
+                   const int64_t* nrows_dev, int64_t limit, int64_t* out_count, void* ws_, const char* name, ObSorted& S) {
+    std::memset(&S, 0, sizeof(S));
     uint8_t* ws = (uint8_t*)ws_;
     const int64_t tiles_max = nrows / RX_TILE + 2;
     size_t off = 0;
@@ -1987,6 +2001,7 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
     int64_t* counters = (int64_t*)take((size_t)(tiles_max << 8) * 8);
     int64_t* scanned = (int64_t*)take((size_t)((tiles_max << 8) + 1) * 8);
     void* scan_ws = take(hs_scan_ws_bytes(tiles_max << 8));
+    S.ws_bytes = off;
     ObSelect* select = (ObSelect*)(state + 2);
     int64_t* seg = (int64_t*)(state + 6);
 
@@ -1998,18 +2013,19 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
     if (nrows_dev) {
         int64_t exact = 0;
         if (!read_back(&exact, nrows_dev, 8)) {
-            hs_set_error("hs_order_by: reading the row count failed");
+            hs_set_error("%s: reading the row count failed", name);
             return HS_E_LAUNCH;
         }
         n = exact < n ? (exact < 0 ? 0 : exact) : n;
     }
     const int64_t count = limit < 0 || limit > n ? n : limit;
     *out_count = count;
+    S.n = n;
+    S.count = count;
     if (count == 0) return HS_OK;
 
     // the key's layout: widths of the runs, then the parts of every word
-    ObKeys A;
-    std::memset(&A, 0, sizeof(A));
+    ObKeys& A = S.keys;
     int64_t total_bytes = 0;
     for (int k = 0; k < n_keys; ++k) {
         const hs_col& c = keys[k];
@@ -2018,10 +2034,10 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
         if (c.kind == HS_STR && c.fixed_len < 0) {
             hs_memset_async(state + 5, 0, 8, stream);
             hipLaunchKernelGGL(k_ob_maxlen, dim3(ob_grid(n)), dim3(OB_THREADS), 0, stream, c.lens, n, (uint32_t*)(state + 5));
-            RX_CHECK_LAUNCH("hs_order_by (longest string)");
+            OB_CHECK_LAUNCH("longest string");
             uint32_t longest = 0;
             if (!read_back(&longest, state + 5, 4)) {
-                hs_set_error("hs_order_by: reading the longest string failed");
+                hs_set_error("%s: reading the longest string failed", name);
                 return HS_E_LAUNCH;
             }
             A.str_cap[k] = (int32_t)longest;
@@ -2034,12 +2050,8 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
         total_bytes += A.width[k];
     }
     const int n_words = (int)((total_bytes + 7) / 8);
-    auto iota_out = [&]() {
-        hipLaunchKernelGGL(k_ob_iota, dim3(ob_grid(count)), dim3(OB_THREADS), 0, stream, out_perm, count);
-        RX_CHECK_LAUNCH("hs_order_by (rows in place)");
-        return HS_OK;
-    };
-    if (n_words == 0) return iota_out();
+    S.n_words = n_words;
+    if (n_words == 0) return HS_OK;
 
     // word w of `m` rows (in place, or those of `rows`) -> out_words; -> the bytes of the word that differ between rows
     auto form = [&](int w, const int64_t* rows, int64_t m, uint64_t* out_words, int64_t* out_rows, uint64_t& and_bits,
@@ -2047,9 +2059,8 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
         A.n_parts = 0;
         int64_t at = 0;
         for (int k = 0; k < n_keys; ++k) {
-            const int64_t b = at > (int64_t)w * 8 ? at : (int64_t)w * 8;
-            const int64_t e = at + A.width[k] < (int64_t)(w + 1) * 8 ? at + A.width[k] : (int64_t)(w + 1) * 8;
-            if (b < e) A.part[A.n_parts++] = ObPart{k, (int32_t)(b - at), (int32_t)(e - b), (int32_t)(b - (int64_t)w * 8)};
+            ObPart part;
+            if (ob_part_of(k, at, A.width[k], w, part)) A.part[A.n_parts++] = part;
             at += A.width[k];
         }
         A.rows = rows;
@@ -2062,10 +2073,10 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
         hs_memset_async(state, 0xff, 8, stream);
         hs_memset_async(state + 1, 0, 8, stream);
         hipLaunchKernelGGL(k_ob_keys, dim3(ob_grid(m)), dim3(OB_THREADS), 0, stream, A);
-        RX_CHECK_LAUNCH("hs_order_by (key words)");
+        OB_CHECK_LAUNCH("key words");
         unsigned long long ao[2] = {0, 0};
         if (!read_back(ao, state, 16)) {
-            hs_set_error("hs_order_by: reading the key summary failed");
+            hs_set_error("%s: reading the key summary failed", name);
             return HS_E_LAUNCH;
         }
         and_bits = ao[0];
@@ -2103,6 +2114,7 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
             }
         }
         sorted = R[cur];
+        S.words = K[cur];  // word 0 was formed last and travelled with the rows
         return HS_OK;
     };
 
@@ -2121,7 +2133,7 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
         init.prefix = and_bits & init.mask;
         if (hipMemcpyAsync(select, &init, sizeof(init), hipMemcpyHostToDevice, stream) != hipSuccess ||
             hipStreamSynchronize(stream) != hipSuccess) {  // `init` leaves scope
-            hs_set_error("hs_order_by: writing the selection state failed");
+            hs_set_error("%s: writing the selection state failed", name);
             return HS_E_LAUNCH;
         }
         hs_memset_async(hist, 0, 256 * 8, stream);
@@ -2130,30 +2142,194 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
             hipLaunchKernelGGL(k_ob_select, dim3(ob_grid(n)), dim3(OB_THREADS), 0, stream, (const uint64_t*)K[0], n,
                                (const ObSelect*)select, 8 * b, hist);
             hipLaunchKernelGGL(k_ob_pick, dim3(1), dim3(256), 0, stream, select, 8 * b, hist);
-            RX_CHECK_LAUNCH("hs_order_by (select)");
+            OB_CHECK_LAUNCH("select");
         }
         const int64_t nct = (n + OB_TILE - 1) / OB_TILE;
         hipLaunchKernelGGL(k_ob_count, dim3((unsigned)nct), dim3(OB_THREADS), 0, stream, (const uint64_t*)K[0], n,
                            (const ObSelect*)select, counters);
-        RX_CHECK_LAUNCH("hs_order_by (count)");
+        OB_CHECK_LAUNCH("count");
         rc = hs_exclusive_scan_i64(stream, counters, nct, scanned, scan_ws);
         if (rc != HS_OK) return rc;
         hipLaunchKernelGGL(k_ob_compact, dim3((unsigned)nct), dim3(OB_THREADS), 0, stream, (const uint64_t*)K[0], n,
                            (const ObSelect*)select, (const int64_t*)scanned, (int64_t*)K[1]);
-        RX_CHECK_LAUNCH("hs_order_by (compact)");
+        OB_CHECK_LAUNCH("compact");
         int64_t candidates = 0;
         if (!read_back(&candidates, scanned + nct, 8) || candidates < count || candidates > n) {
-            hs_set_error("hs_order_by: the selection kept %lld rows of %lld for a limit of %lld", (long long)candidates,
+            hs_set_error("%s: the selection kept %lld rows of %lld for a limit of %lld", name, (long long)candidates,
                          (long long)n, (long long)count);
             return HS_E_LAUNCH;
         }
         rc = sort_rows((const int64_t*)K[1], candidates, sorted);
         if (rc != HS_OK) return rc;
     }
-    if (hipMemcpyAsync(out_perm, sorted, (size_t)count * 8, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+    S.rows = sorted;
+    return HS_OK;
+}
+
+extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_keys, int64_t nrows,
+                           const int64_t* nrows_dev, int64_t limit, int64_t* out_perm, int64_t* out_count, void* ws_,
+                           uint32_t* flags) {
+    (void)flags;
+    if (n_keys < 0 || nrows < 0 || !out_perm || !out_count || !ws_ || (n_keys > 0 && (!keys || !descending)) ||
+        (n_keys == 0 && limit < 0)) {
+        hs_set_error("hs_order_by: bad arguments");
+        return HS_E_ARG;
+    }
+    if (n_keys > HS_MAX_COLS) {
+        hs_set_error("hs_order_by: more than %d keys", HS_MAX_COLS);
+        return HS_E_LIMIT;
+    }
+    *out_count = 0;
+    if (nrows == 0 || limit == 0) return HS_OK;
+    for (int k = 0; k < n_keys; ++k)
+        if (!ob_kind_ok(keys[k])) {
+            hs_set_error("hs_order_by: key %d is not a column that can be ordered", k);
+            return HS_E_ARG;
+        }
+    hipStream_t stream = (hipStream_t)stream_;
+    ObSorted S;
+    const int rc = ob_sort(stream, keys, descending, n_keys, nrows, nrows_dev, limit, out_count, ws_, "hs_order_by", S);
+    if (rc != HS_OK || S.count == 0) return rc;
+    if (!S.rows) {
+        hipLaunchKernelGGL(k_ob_iota, dim3(ob_grid(S.count)), dim3(OB_THREADS), 0, stream, out_perm, S.count);
+        RX_CHECK_LAUNCH("hs_order_by (rows in place)");
+        return HS_OK;
+    }
+    if (hipMemcpyAsync(out_perm, S.rows, (size_t)S.count * 8, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
         hs_set_error("hs_order_by: copying the row list failed");
         return HS_E_LAUNCH;
     }
+    return HS_OK;
+}
+
+// =====================================================================================================
+// SELECT DISTINCT over result rows (include/hipspark.h hs_distinct; the reference has no DISTINCT).
+//
+// Rows are equal iff all their key words are equal, the words being hs_order_by's.  ob_sort orders the rows by every key,
+// ascending: equal rows become neighbours and, the sort being stable, stand in input order, so the first row of a run of
+// equal rows - its HEAD - is the run's smallest input row.  k_distinct_heads marks the heads in INPUT order
+// (keep[perm[j]] = 1 iff j == 0 or row perm[j] differs from row perm[j - 1] in some word) and hs_compact turns the mask
+// into the ascending list of surviving rows: no second sort.  The sort keeps one word per row at a time, so the words of
+// both rows are formed again, with ob_part_bits: a lane forms its own row's word and takes its left neighbour's through a
+// wave shuffle; lane 0, whose neighbour belongs to the previous wave step or to the previous workgroup's tile, loads
+// that row from the list and forms its word itself.  A key of ONE word (one INTEGER, two INTEGERs, a code and an
+// INTEGER) needs none of that: the sorted words the sort leaves behind are the rows' keys, read coalesced.  No LDS, no
+// atomics; the pass is bound by the gathers of the key cells (one per row and word) and the byte scattered into keep.
+// =====================================================================================================
+struct DhArgs {
+    ObKeys K;             // col / width / str_cap / desc of the sort
+    int32_t n_keys, n_words;
+    const int64_t* perm;  // the rows, sorted by all keys (null: position = row)
+    const uint64_t* words;  // a key of ONE word: that word of the sorted rows, as the sort left it - compared instead of
+                          // formed again (null: the words are formed from the columns)
+    int64_t n;
+    uint8_t* keep;        // [n], input order
+};
+static_assert(sizeof(DhArgs) % 8 == 0, "DhArgs");
+
+__device__ __forceinline__ uint64_t dh_word(const DhArgs& A, int32_t w, int64_t row) {
+    uint64_t word = 0;
+    int64_t at = 0;
+    for (int k = 0; k < A.n_keys; ++k) {
+        ObPart part;
+        if (ob_part_of(k, at, A.K.width[k], w, part)) word |= ob_part_bits(A.K, part, row);
+        at += A.K.width[k];
+    }
+    return word;
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_distinct_heads(const DhArgs A_kernarg) {
+    HS_KERNARG(DhArgs, A);
+    const int lane = threadIdx.x & (HS_WAVE - 1), wave = threadIdx.x / HS_WAVE;
+    const int64_t first = (int64_t)blockIdx.x * OB_TILE + (int64_t)wave * (OB_STEPS * HS_WAVE) + lane;
+    for (int j = 0; j < OB_STEPS; ++j) {
+        const int64_t i = first + j * HS_WAVE;
+        if (i - lane >= A.n) break;                   // the whole wave step lies past the rows
+        const bool live = i < A.n;
+        const int64_t pos = live ? i : A.n - 1;       // lanes past the end repeat the last row: every read stays inside
+        const int64_t row = A.perm ? A.perm[pos] : pos;
+        // lane 0's left neighbour sits in no lane of this step: sorted position i - 1, loaded explicitly
+        const int64_t before = (lane == 0 && i > 0) ? (A.perm ? A.perm[i - 1] : i - 1) : row;
+        bool differs = false;
+        if (A.words) {  // coalesced: the sort's own words, no gather from the columns
+            const unsigned long long mine = A.words[pos];
+            unsigned long long left = __shfl_up(mine, 1, HS_WAVE);
+            if (lane == 0 && i > 0) left = A.words[i - 1];
+            differs = mine != left;
+        } else for (int32_t w = 0; w < A.n_words; ++w) {
+            const unsigned long long mine = dh_word(A, w, row);
+            unsigned long long left = __shfl_up(mine, 1, HS_WAVE);
+            if (lane == 0) left = dh_word(A, w, before);
+            differs |= mine != left;
+            if (__ballot(!differs) == 0) break;       // every lane of the step has found its difference
+        }
+        if (live) A.keep[row] = (i == 0 || differs) ? 1 : 0;
+    }
+}
+
+extern "C" int hs_compact(void* stream, const uint8_t* mask, int64_t nrows, int64_t* sel, int64_t* count, void* ws);
+
+extern "C" size_t hs_distinct_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words) {
+    if (nrows < 0) return 0;
+    // the sort's workspace, then the keep mask, the device count and the compaction's scan workspace
+    return hs_order_by_ws_bytes(nrows, n_keys, max_key_words) + rx_align((size_t)nrows) + 256 + rx_align(hs_scan_ws_bytes(nrows));
+}
+
+extern "C" int hs_distinct(void* stream_, const hs_col* keys, int32_t n_keys, int64_t nrows, const int64_t* nrows_dev,
+                           int64_t* out_perm, int64_t* out_count, void* ws_, uint32_t* flags) {
+    (void)flags;
+    if (n_keys <= 0 || nrows < 0 || !keys || !out_perm || !out_count || !ws_) {
+        hs_set_error("hs_distinct: bad arguments");
+        return HS_E_ARG;
+    }
+    if (n_keys > HS_MAX_COLS) {
+        hs_set_error("hs_distinct: more than %d columns", HS_MAX_COLS);
+        return HS_E_LIMIT;
+    }
+    *out_count = 0;
+    if (nrows == 0) return HS_OK;
+    for (int k = 0; k < n_keys; ++k)
+        if (!ob_kind_ok(keys[k])) {
+            hs_set_error("hs_distinct: column %d is not a column that can be compared", k);
+            return HS_E_ARG;
+        }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int32_t ascending[HS_MAX_COLS] = {0};
+    DhArgs D;
+    std::memset(&D, 0, sizeof(D));
+    int64_t sorted_rows = 0;
+    size_t sort_bytes = 0;
+    {
+        ObSorted S;
+        const int rc = ob_sort(stream, keys, ascending, n_keys, nrows, nrows_dev, -1, &sorted_rows, ws_, "hs_distinct", S);
+        if (rc != HS_OK || S.count == 0) return rc;
+        D.K = S.keys;
+        D.n_keys = n_keys;
+        D.n_words = S.n_words;
+        D.perm = S.rows;
+        D.n = S.n;
+        // one word per row: the sorted words ARE the rows' keys.  HIPSPARK_DISTINCT_GATHER=1 keeps the general path,
+        // so that tools/bench_distinct.py can time one against the other
+        const char* gather = std::getenv("HIPSPARK_DISTINCT_GATHER");
+        if (S.n_words == 1 && S.rows && !(gather && gather[0] == '1')) D.words = S.words;
+        sort_bytes = S.ws_bytes;
+    }
+    uint8_t* extra = (uint8_t*)ws_ + sort_bytes;  // behind what the sort laid out (hs_distinct_ws_bytes: at most hs_order_by_ws_bytes)
+    D.keep = extra;
+    int64_t* count_dev = (int64_t*)(extra + rx_align((size_t)nrows));
+    void* scan_ws = (uint8_t*)count_dev + 256;
+    const int64_t tiles = (D.n + OB_TILE - 1) / OB_TILE;
+    hipLaunchKernelGGL(k_distinct_heads, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, D);
+    RX_CHECK_LAUNCH("hs_distinct (heads)");
+    const int rc = hs_compact(stream, D.keep, D.n, out_perm, count_dev, scan_ws);
+    if (rc != HS_OK) return rc;
+    int64_t kept = 0;
+    if (hipMemcpyAsync(&kept, count_dev, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess || kept < 1 || kept > D.n) {
+        hs_set_error("hs_distinct: the compaction kept %lld rows of %lld", (long long)kept, (long long)D.n);
+        return HS_E_LAUNCH;
+    }
+    *out_count = kept;
     return HS_OK;
 }
 

@@ -68,7 +68,22 @@ class DataFrame:
     def order_by(self, *keys: Any) -> "DataFrame":
         """ORDER BY: ``Col`` (ascending), ``Col.asc()`` or ``Col.desc()``, the first key the most significant."""
         pairs = [(k.column, k.ascending) if isinstance(k, SortKey) else (k, True) for k in keys]
+        top = self.task
+        if type(top) is _t.SortTask and top.distinct and not top.keys and top.limit is None:
+            _t.check_sort_keys(pairs)  # directly above distinct(): one task carries both, as limit() does
+            top.keys = pairs
+            return self
+        if type(top) is _t.SortTask and top.distinct:
+            raise ValueError("order_by() comes directly after distinct(), once, and before limit()")
         return self._append(_t.SortTask, keys=pairs)
+
+    def distinct(self) -> "DataFrame":
+        """SELECT DISTINCT: of the rows that are equal in every column the first stays.  It comes before ``order_by`` /
+        ``limit``, which then apply to the rows that are left."""
+        if type(self.task) is _t.SortTask:
+            raise ValueError("distinct() was already applied" if self.task.distinct and not self.task.keys
+                             and self.task.limit is None else "distinct() comes before order_by() / limit()")
+        return self._append(_t.SortTask, keys=[], limit=None, distinct=True)
 
     def limit(self, n: int) -> "DataFrame":
         """LIMIT: of an ``order_by`` directly below, else the first ``n`` rows in the engine's own order."""

@@ -1559,6 +1559,33 @@ class Device:
             raise DeviceError(f"hs_order_by returned {out_count.value} rows, expected {count}")
         return perm[:count], count
 
+    def distinct(self, batch: DBatch) -> tuple[torch.Tensor, int]:
+        """SELECT DISTINCT over the rows of ``batch`` -> (row list, its length): the rows that survive, ascending - of the
+        rows equal in EVERY column the first stays, so ``gather_batch`` through the list returns it with its own bits.
+        Equality is that of hs_order_by's key words (hs_distinct): -0.0 = +0.0, NaN = NaN, strings by bytes and length,
+        a dictionary-coded column by its code (one code, one string: the dictionary need not be sorted).  A lazily
+        sized batch passes its device row count along.  Like ``order_by`` the call learns sizes on the host between
+        its steps, so a run that contains it is not replayable."""
+        n = batch.nrows
+        if self.rec is not None:
+            self.rec.poisoned = True
+        if len(batch.cols) > hs.HS_MAX_COLS:
+            raise DeviceError(f"DISTINCT over {len(batch.cols)} columns: at most {hs.HS_MAX_COLS}")
+        if any(col.virtual for col in batch.cols):
+            raise DeviceError("a virtual column of the fused join cannot be compared by DISTINCT")
+        perm = self.empty(max(n, 1), torch.int64)
+        if n == 0 or not batch.cols:
+            return perm[:0], 0
+        arr = (hs.hs_col * len(batch.cols))(*[c.as_hs() for c in batch.cols])
+        ws = self.workspace(self._raw_lib.hs_distinct_ws_bytes(n, len(batch.cols), 32 * len(batch.cols)))
+        out_count = C.c_int64(0)
+        hs.check(self._raw_lib.hs_distinct(self.stream, arr, len(batch.cols), n, batch.n_dev_ptr,
+                                           perm.data_ptr(), C.byref(out_count), ws.data_ptr(), self.flags.data_ptr()),
+                 "hs_distinct")
+        if not 0 <= out_count.value <= n:
+            raise DeviceError(f"hs_distinct returned {out_count.value} rows of {n}")
+        return perm[:out_count.value], out_count.value
+
     def unit_ids_per_row(self, unit_rows: Sequence[int], unit_ids: Sequence[int]) -> torch.Tensor:
         """Global block id of every partial row: unit_ids[u] for rows unit_rows[u] .. unit_rows[u + 1]."""
         n = int(unit_rows[-1])

@@ -701,19 +701,30 @@ class HipExecutionEngine(ExecutionEngine):
         """A result that is written range by range is never whole on the device, so it cannot be ordered (a LIMIT
         without keys could be served, but which rows it keeps would then depend on the budget: refused alike)."""
         if sort is not None and _cls(writer) == "WriteToLocalFileTask":
-            raise ExecutionError("ORDER BY / LIMIT needs the whole result on the device, and this query's result is "
+            raise ExecutionError("DISTINCT / ORDER BY / LIMIT needs the whole result on the device, and this query's result is "
                                  "produced in pieces because its input exceeds HIPSPARK_HBM_BUDGET: raise the budget")
 
     def _order_rows(self, batch: Any, sort: Any, schema: Schema) -> Any:
         """ORDER BY / LIMIT over the finished result: the rows are first rounded to the types they are stored in, so
         they are ordered by the values the user reads back.  Keys are looked up by POSITION in the SortTask's input
         schema: the planner's rename-only projection above it changes names, never positions.  On N ranks rank 0 holds
-        every row by now (_gather_to_root) and the others none."""
+        every row by now (_gather_to_root) and the others none.  SELECT DISTINCT (``sort.distinct``) comes between the
+        rounding and the keys: rows equal in every column of the values the user reads back are removed, the first of
+        them stays, and keys and limit apply to the survivors (a LIMIT without keys is then their head)."""
         batch = self.dev.resolve(self._quantise_batch(self.dev.resolve(batch), schema))
         names = [name for name, _ in sort.inferred_schema]
         if len(names) != len(batch.cols):
             raise ExecutionError(f"ORDER BY schema {sort.inferred_schema} does not match the result {batch.schema}")
+        if sort.distinct:
+            from . import hipspark as hs  # noqa: PLC0415
+
+            if len(batch.cols) > hs.HS_MAX_COLS:
+                raise ExecutionError(f"SELECT DISTINCT compares at most {hs.HS_MAX_COLS} columns; the result has {len(batch.cols)}")
+            perm, count = self.dev.distinct(batch)
+            batch = self.dev.gather_batch(batch, perm, count)
         keys = [(names.index(col.name), ascending) for col, ascending in sort.keys]
+        if not keys and sort.limit is None:
+            return batch
         if not keys:
             return self.dev.head(batch, min(batch.nrows, sort.limit))  # LIMIT alone: one slice of the rows as they stand
         perm, count = self.dev.order_by(batch, keys, sort.limit)

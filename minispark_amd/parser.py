@@ -4,7 +4,7 @@ requirements, so `.sql()` would not work next to the HIP engine without this mod
 
 A hand-written backtracking recursive-descent parser for the same language:
 
-    SELECT select_list FROM 'path' [AS t] { [LEFT|RIGHT|INNER|FULL] JOIN 'path' [AS t] ON cond }
+    SELECT [DISTINCT] select_list FROM 'path' [AS t] { [LEFT|RIGHT|INNER|FULL] JOIN 'path' [AS t] ON cond }
            [WHERE cond] [GROUP BY col [HAVING cond]] [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] [LIMIT n] ;
 
 * select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e) [AS name]``, ``expr [AS name]``;
@@ -17,7 +17,10 @@ A hand-written backtracking recursive-descent parser for the same language:
   is executed as an inner join (parser.py:131-133), numbers are integers (parser.py:349), NOT raises
   NotImplementedError (sql.py:44-45), GROUP BY takes one column (dataframe.py:64);
 * beyond the reference: ORDER BY takes names of the RESULT (a select item's alias, or its generated name), each ascending
-  unless DESC follows, and LIMIT a non-negative integer; both become one ``order_by`` / ``limit`` after the final select.
+  unless DESC follows, and LIMIT a non-negative integer; both become one ``order_by`` / ``limit`` after the final select;
+  ``SELECT DISTINCT`` (the keyword, then whitespace) becomes ``distinct()`` between the final select and ``order_by``:
+  rows equal in every result column are removed, the first of them stays, and ORDER BY / LIMIT apply to what is left.
+  The form without the keyword is tried first, so a text that was accepted before builds the tree it built then.
 
 Alternatives are tried in the grammar's order and the first that fits wins (ordered choice), so texts the
 reference accepts build the same task tree here (tests/test_parser.py compares both renderings).
@@ -122,9 +125,18 @@ class _Parser:
 
     # ---- query ------------------------------------------------------------------------------------------------
     def query(self) -> DataFrame:
+        # ordered choice: the grammar without DISTINCT first, so a text that was accepted before DISTINCT existed (a
+        # column may be called DISTINCT) still builds the tree it built then
+        matched, df = self.attempt(lambda: self.query_body(distinct=False))
+        return df if matched else self.query_body(distinct=True)
+
+    def query_body(self, distinct: bool) -> DataFrame:
         self.ows()
         self.lit("SELECT")
         self.ws()
+        if distinct:
+            self.lit("DISTINCT")
+            self.ws()
         select_list = self.select_list()
         self.ws()
         self.lit("FROM")
@@ -174,6 +186,8 @@ class _Parser:
             df = df.agg(*select_list)
         else:
             df = df.select(*select_list)
+        if distinct:
+            df = df.distinct()
         if has_order:
             names = {c.name for c in select_list}
             for key in order:

@@ -161,7 +161,7 @@ class PhysicalPlan:
         node: Task | None = task
         while node is not None and type(node) is not VoidTask:
             if type(node) is SortTask and not top:
-                raise ValueError("ORDER BY / LIMIT must be the last operation")
+                raise ValueError("DISTINCT / ORDER BY / LIMIT must be the last operation")
             if type(node) is BroadcastHashJoinTask:
                 PhysicalPlan.check_sort_is_last(node.right_side_task, top=False)
             top = False

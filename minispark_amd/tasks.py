@@ -12,6 +12,7 @@ terminates the list.
 
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Iterator, Literal
@@ -229,15 +230,16 @@ class SortTask(ConsumerTask):
     """ORDER BY / LIMIT over the query's result rows (no reference counterpart).  ``keys`` = (plain column of the input
     schema, ascending) pairs, the first the most significant; ``limit`` = rows kept (None: all).  Without keys the
     first ``limit`` rows are kept in the engine's own order.  Always the last logical operation: the engine runs it on
-    the finished result, after the values were rounded to their stored types."""
+    the finished result, after the values were rounded to their stored types.  ``distinct`` (SELECT DISTINCT): rows
+    equal in EVERY column are removed first - the first of them in the result's order stays - and keys and limit apply
+    to the survivors.  It rides on this task so that every guard ORDER BY has holds for it unchanged."""
 
     keys: list[tuple[Col, bool]] = field(default_factory=list)
     limit: int | None = None
+    distinct: bool = False
 
     def __post_init__(self) -> None:
-        for col, _ in self.keys:
-            if type(col).__name__ not in {"Col", "SchemaCol"}:
-                raise ValueError(f"ORDER BY takes plain columns, not the expression {col}: select(... .alias()) first")
+        check_sort_keys(self.keys)
         if self.limit is not None:
             check_limit(self.limit)
 
@@ -247,9 +249,20 @@ class SortTask(ConsumerTask):
             col.infer_type(schema)  # ValueError('Column "x" not found in schema ...')
         return schema
 
+    def __repr__(self) -> str:
+        """The dataclass form; ``distinct`` is named only when set, so a plain task prints as it did before the field."""
+        shown = [f for f in dataclasses.fields(self) if f.repr and (f.name != "distinct" or self.distinct)]
+        return f"{type(self).__name__}(" + ", ".join(f"{f.name}={getattr(self, f.name)!r}" for f in shown) + ")"
+
     def describe(self) -> str:
         keys = ", ".join(f"{col} {'ASC' if ascending else 'DESC'}" for col, ascending in self.keys)
-        return f"Sort({keys}; limit={self.limit})"
+        return f"Sort({'DISTINCT ' if self.distinct else ''}{keys}; limit={self.limit})"
+
+
+def check_sort_keys(keys: list) -> None:
+    for col, _ in keys:
+        if type(col).__name__ not in {"Col", "SchemaCol"}:
+            raise ValueError(f"ORDER BY takes plain columns, not the expression {col}: select(... .alias()) first")
 
 
 def check_limit(n: object) -> None:
