@@ -123,9 +123,12 @@ enum hs_op {
     HS_OP_AGG = 33,     /* pop; fold into accumulator a (tasks.py:295-310) */
     HS_OP_OUT = 34,     /* pop; store as output a (hs_eval) */
     HS_OP_KEY = 35,     /* resolve the GROUP BY slot of the surviving rows (between filters and AGGs) */
-    HS_OP_DICTBIT = 36  /* a = slot of a dictionary-coded column (one code byte per row), b = index of the first of
+    HS_OP_DICTBIT = 36, /* a = slot of a dictionary-coded column (one code byte per row), b = index of the first of
                            c (1..4) literal words holding one bit per dictionary entry; push bit[code]: LIKE and
                            string comparisons with a literal, evaluated once per dictionary entry on the host */
+    HS_OP_SEL = 37      /* c x y -> (c != 0 ? x : y): pops three, pushes one (needs sp >= 3).  Acts on the raw 64-bit cells,
+                           so it serves f64 and i64 alike (NaN payloads, -0.0 and i64 extremes pass through); raises no
+                           flag.  CASE WHEN c THEN x ELSE y END: both branches are evaluated, then one is chosen */
 };
 
 typedef struct hs_program {

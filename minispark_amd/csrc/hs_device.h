@@ -379,6 +379,12 @@ __device__ __forceinline__ void hs_exec_at(uint64_t w, const hs_program& P, cons
                 }
             }
             break;
+        case HS_OP_SEL:  // c x y -> (c != 0 ? x : y) on the raw cells: one opcode for f64 and i64, no error, no `live`
+            if constexpr (SP >= 3) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) st[SP - 3][j] = st[SP - 3][j] != 0 ? st[S][j] : st[T][j];
+            }
+            break;
         case HS_OP_STRCMP_LIT:
             if constexpr (SP < D) {
 #pragma unroll
@@ -499,6 +505,10 @@ __device__ __forceinline__ void hs_run_compact(const hs_program& P, const HsCols
             case HS_OP_I2F:
                 if (a == 0) st(t) = hs_d2u((double)(int64_t)y);
                 else st(s2) = hs_d2u((double)(int64_t)x);
+                break;
+            case HS_OP_SEL:
+                if (sp >= 3) st(sp - 3) = st(sp - 3) != 0 ? x : y;
+                else err |= HS_FLAG_BAD_PROGRAM;
                 break;
             case HS_OP_STRCMP_LIT: st(nx) = live ? hs_strcmp_lit(P, C.c[a], sink.row(0), hs_ins_b(w), hs_ins_c(w)) : 0; break;
             case HS_OP_STRCMP_COL: st(nx) = live ? hs_strcmp_col(C.c[a], C.c[hs_ins_b(w)], sink.row(0), hs_ins_c(w)) : 0; break;

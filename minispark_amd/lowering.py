@@ -64,6 +64,8 @@ def expr_key(node: Any) -> tuple:
         return ("like", expr_key(node.original_col), node.pattern)
     if name == "BinaryOperatorColumn":
         return (node.operator.__name__, expr_key(node.left_side), expr_key(node.right_side))
+    if name == "CaseColumn":
+        return ("case", expr_key(node.condition), expr_key(node.then_col), expr_key(node.else_col))
     raise LoweringError(f"unsupported expression node {name}")
 
 
@@ -239,7 +241,65 @@ class ProgramBuilder:
             return "B"
         if name == "BinaryOperatorColumn":
             return self._lower_binary(node)
+        if name == "CaseColumn":
+            return self._lower_case(node)
         raise LoweringError(f"unsupported expression node {name}")
+
+    def value_tag(self, node: Any) -> str:
+        """The tag lower(node) returns, without emitting anything (what is wrong with ``node`` is reported by lower())."""
+        name = _cls(node)
+        if name in ("AliasColumn", "AggCol"):
+            return self.value_tag(node.original_col)
+        if name in ("Col", "SchemaCol"):
+            for i, (col_name, ctype) in enumerate(self.schema):
+                if col_name == node.name:
+                    if self.kinds[i] == hs.STR:
+                        return "S"
+                    return "T" if ctype == ColumnType.TIMESTAMP else _STORAGE_TAG[self.kinds[i]]
+            raise ValueError(f'Column "{node.name}" not found in schema {self.schema}')
+        if name == "Lit":
+            return {bool: "B", int: "I", float: "F", datetime: "T"}.get(type(node.value), "S")
+        if name == "LikeColumn":
+            return "B"
+        if name == "BinaryOperatorColumn":
+            opname = node.operator.__name__
+            if opname == "truediv":
+                return "F"
+            if opname in _CMP:
+                return "B"
+            tags = (self.value_tag(node.left_side), self.value_tag(node.right_side))
+            if opname in _LOGIC:
+                return "B" if tags == ("B", "B") else "I"
+            return "S" if "S" in tags else "F" if "F" in tags else "I"
+        if name == "CaseColumn":
+            return "F" if "F" in (self.value_tag(node.then_col), self.value_tag(node.else_col)) else "I"
+        raise LoweringError(f"unsupported expression node {name}")
+
+    def _lower_case(self, node: Any) -> str:
+        """condition, THEN value, ELSE value, HS_OP_SEL: all three are evaluated, then one cell is chosen.  The result tag
+        is decided first (FLOAT if either branch is) because an INTEGER branch can only be converted while it is the top
+        cell.  Branches go through lower(): no ISO-string-to-timestamp rewrite, a branch is a number."""
+        tags = [self.value_tag(branch) for branch in (node.then_col, node.else_col)]
+        for i, branch in enumerate((node.then_col, node.else_col)):
+            inner = unalias(branch)  # AND / OR is boolean by its shape, whatever its operands (as infer_type has it)
+            if _cls(inner) == "BinaryOperatorColumn" and inner.operator.__name__ in _LOGIC:
+                tags[i] = "B"
+        for tag, branch in zip(tags, (node.then_col, node.else_col)):
+            if tag not in ("I", "F"):
+                what = {"B": "boolean", "T": "TIMESTAMP", "S": "STRING"}[tag]
+                raise TypeError(f"CASE branches are INTEGER or FLOAT values, not {what}: {branch} in {node}")
+        result = "F" if "F" in tags else "I"
+        cond_tag = self.lower(node.condition)
+        if cond_tag not in ("B", "I"):
+            self._to_bool(cond_tag)
+        for predicted, branch in zip(tags, (node.then_col, node.else_col)):
+            tag = self.lower(branch)
+            if tag != predicted:  # value_tag restates lower()'s typing: a drift would choose an I cell as F, silently
+                raise AssertionError(f"value_tag gives {predicted} where lower gives {tag}: {branch}")
+            if result == "F":
+                self._to_float(tag, second=False)
+        self._emit(hs.OP_SEL, push=-2)
+        return result
 
     def _lower_literal(self, value: Any) -> str:
         if type(value) is bool:

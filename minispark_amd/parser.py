@@ -9,7 +9,8 @@ A hand-written backtracking recursive-descent parser for the same language:
 
 * select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e) [AS name]``, ``expr [AS name]``;
 * conditions: OR < AND < NOT < comparison | ( cond ) | BETWEEN | LIKE, comparators = != <= >= < >;
-* expressions: + - over * / over atoms (number, column, string literal, ( expr ), COUNT()/SUM(e));
+* expressions: + - over * / over atoms (number, column, string literal, ( expr ), COUNT()/SUM(e),
+  ``CASE WHEN cond THEN expr {WHEN cond THEN expr} ELSE expr END``);
 * a select list of aggregate calls only and no GROUP BY aggregates the whole table (``DataFrame.agg``): one row, or none
   when no row survives the WHERE; mixing aggregates and plain columns without GROUP BY raises ``GroupByError``, HAVING
   without GROUP BY stays a syntax error, arithmetic over aggregates (``SUM(a) / SUM(b)``) is not part of this form;
@@ -21,6 +22,9 @@ A hand-written backtracking recursive-descent parser for the same language:
   ``SELECT DISTINCT`` (the keyword, then whitespace) becomes ``distinct()`` between the final select and ``order_by``:
   rows equal in every result column are removed, the first of them stays, and ORDER BY / LIMIT apply to what is left.
   The form without the keyword is tried first, so a text that was accepted before builds the tree it built then.
+  ``CASE`` (searched form only, ELSE mandatory, INTEGER / FLOAT branches, several WHEN arms nest to the right) stands
+  wherever an expression may: a select item, an aggregate's argument, either side of a comparison, inside arithmetic or
+  another CASE.  A column called ``CASE`` still parses as a column (no old text holds ``CASE`` whitespace ``WHEN``).
 
 Alternatives are tried in the grammar's order and the first that fits wins (ordered choice), so texts the
 reference accepts build the same task tree here (tests/test_parser.py compares both renderings).
@@ -33,7 +37,7 @@ import re
 from typing import Any, Callable
 
 from .dataframe import DataFrame
-from .sql import AggCol, Col, Lit, SortKey
+from .sql import AggCol, CaseColumn, Col, Lit, SortKey
 from .sql import Functions as F
 
 
@@ -57,6 +61,7 @@ _WS = re.compile(r"\s+")
 _TABLE = re.compile(r"[a-zA-Z0-9_\-\./ ]+")
 _COLUMN = re.compile(r"[A-Za-z_][A-Za-z0-9_\.]*")
 _IDENT = re.compile(r"[A-Za-z_][A-Za-z0-9_]*")
+_IDENT_CHAR = re.compile(r"[A-Za-z0-9_]")
 _NUMBER = re.compile(r"-?[0-9]+(\.[0-9]+)?")
 _DIGITS = re.compile(r"[0-9]+")
 _STRING = re.compile(r"[^']*")
@@ -388,8 +393,36 @@ class _Parser:
         return self._binary_chain(self.atom, {"*": operator.mul, "/": operator.truediv})
 
     def atom(self) -> Any:
-        return self.first_of(self.function_call, self.number, self.column_name, self.parenthised_expr,
+        return self.first_of(self.function_call, self.number, self.case_expr, self.column_name, self.parenthised_expr,
                              self.string_literal)
+
+    def case_expr(self) -> Col:
+        """CASE WHEN cond THEN expr {WHEN cond THEN expr} ELSE expr END.  Tried before column_name: no text accepted
+        without it holds a column followed by whitespace and WHEN, so a column called CASE still parses as a column."""
+        def arm() -> tuple[Col, Any]:
+            self.ws()
+            self.lit("WHEN")
+            self.ws()
+            cond = self.condition()
+            self.ws()
+            self.lit("THEN")
+            self.ws()
+            return cond, self.expr()
+
+        self.lit("CASE")
+        arms = [arm()]
+        arms += self.repeat(arm)
+        self.ws()
+        self.lit("ELSE")
+        self.ws()
+        col = _as_col(self.expr())
+        self.ws()
+        self.lit("END")
+        if _IDENT_CHAR.match(self.text, self.pos):  # ENDFROM is no END; the other keywords are followed by whitespace
+            self.fail()
+        for cond, then in reversed(arms):
+            col = CaseColumn(cond, _as_col(then), col)
+        return col
 
     def function_call(self) -> Col:
         name = self.rx(_IDENT)

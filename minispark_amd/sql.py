@@ -300,6 +300,97 @@ class BinaryOperatorColumn(Col):
     __repr__ = __str__
 
 
+_BOOLEAN_OPERATORS = (_op.eq, _op.ne, _op.lt, _op.le, _op.gt, _op.ge, _op.and_, _op.or_)
+
+
+def _is_boolean(node: Col) -> bool:
+    """A comparison, AND / OR, LIKE or a bool literal: there is no BOOL column type, so the node's shape decides."""
+    while isinstance(node, AliasColumn):
+        node = node.original_col
+    if isinstance(node, BinaryOperatorColumn):
+        return node.operator in _BOOLEAN_OPERATORS
+    return isinstance(node, LikeColumn) or (isinstance(node, Lit) and type(node.value) is bool)
+
+
+class CaseColumn(Col):
+    """``CASE WHEN condition THEN then_col ELSE else_col END`` (no reference counterpart: DESIGN.md 4.4b).  Several WHEN
+    arms nest to the right in ``else_col``.  Both branches are numeric; the value is FLOAT if either is.  Both branches
+    are evaluated for every surviving row, then one is chosen (an error inside the branch not taken is still raised)."""
+
+    def __init__(self, condition: Any, then_col: Any, else_col: Any) -> None:
+        self.condition = _wrap(condition)
+        self.then_col = _wrap(then_col)
+        self.else_col = _wrap(else_col)
+        super().__init__(f"case_{self.condition.name}_then_{self.then_col.name}_else_{self.else_col.name}")
+
+    def __hash__(self) -> int:
+        return hash(("CaseColumn", hash(self.condition), hash(self.then_col), hash(self.else_col)))
+
+    @property
+    def children(self) -> tuple[Col, ...]:
+        return (self.condition, self.then_col, self.else_col)
+
+    def infer_type(self, schema: Schema) -> ColumnType:
+        self.condition.infer_type(schema)
+        types = []
+        for branch in (self.then_col, self.else_col):
+            branch_type = branch.infer_type(schema)
+            if branch_type not in (ColumnType.INTEGER, ColumnType.FLOAT) or _is_boolean(branch):
+                what = "boolean" if _is_boolean(branch) else branch_type.name
+                raise TypeError(f"CASE branches are INTEGER or FLOAT values, not {what}: {branch} in {self}")
+            types.append(branch_type)
+        return ColumnType.FLOAT if ColumnType.FLOAT in types else ColumnType.INTEGER
+
+    def normalize_agg_columns(self) -> Col:
+        return CaseColumn(self.condition.normalize_agg_columns(), self.then_col.normalize_agg_columns(),
+                          self.else_col.normalize_agg_columns())
+
+    def _arms(self) -> str:
+        tail = self.else_col
+        rest = tail._arms() if type(tail) is CaseColumn else f"ELSE {tail} END"
+        return f"WHEN {self.condition} THEN {self.then_col} {rest}"
+
+    def __str__(self) -> str:
+        return f"CASE {self._arms()}"
+
+    __repr__ = __str__
+
+
+# instance fields of the column classes that code reads without calling anything
+_COL_FIELDS = frozenset({"name", "original_col", "left_side", "right_side", "operator", "value", "pattern", "type",
+                         "condition", "then_col", "else_col"})
+
+
+class CaseBuilder:
+    """``Functions.when(cond, value)[.when(cond, value)...]``: unfinished until ``.otherwise(value)`` (ELSE is mandatory:
+    the data model has no NULL).  Not a column."""
+
+    def __init__(self, arms: list[tuple[Any, Any]]) -> None:
+        self._arms = arms
+
+    def when(self, condition: Any, value: Any) -> "CaseBuilder":
+        return CaseBuilder([*self._arms, (condition, value)])
+
+    def otherwise(self, value: Any) -> CaseColumn:
+        col = _wrap(value)
+        for condition, then in reversed(self._arms):
+            col = CaseColumn(condition, then, col)
+        return col  # type: ignore[return-value]
+
+    def _unfinished(self, *args: Any, **kwargs: Any) -> Any:
+        raise TypeError("CASE without ELSE: finish Functions.when(...) with .otherwise(value) before using it as a column")
+
+    def __getattr__(self, name: str) -> Any:
+        # only what a column is asked for: hasattr() / getattr(builder, name, default) of anything else answer as usual
+        if not name.startswith("__") and hasattr(Col, name) or name in _COL_FIELDS:
+            self._unfinished()
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    __add__ = __radd__ = __sub__ = __mul__ = __truediv__ = __floordiv__ = __mod__ = _unfinished
+    __lt__ = __le__ = __gt__ = __ge__ = __eq__ = __ne__ = __and__ = __or__ = _unfinished  # type: ignore[assignment]
+    __hash__ = None  # type: ignore[assignment]
+
+
 class AggCol(Col):
     """``type`` in {"sum","min","max","avg"} applied to ``original_col`` (reference sql.py:399-446)."""
 
@@ -365,3 +456,8 @@ class Functions:
     @staticmethod
     def count() -> AggCol:
         return AggCol("sum", Lit(1)).alias("count")
+
+    @staticmethod
+    def when(condition: Any, value: Any) -> CaseBuilder:
+        """``when(c, x).otherwise(y)`` = CASE WHEN c THEN x ELSE y END; further ``.when`` arms nest to the right."""
+        return CaseBuilder([(condition, value)])

@@ -60,6 +60,8 @@ def _substitute(node: Any, defs: dict[str, Any] | None) -> Any:
         return type(node)(_substitute(node.original_col, defs), node.pattern)
     if name == "BinaryOperatorColumn":
         return type(node)(_substitute(node.left_side, defs), _substitute(node.right_side, defs), node.operator)
+    if name == "CaseColumn":
+        return type(node)(_substitute(node.condition, defs), _substitute(node.then_col, defs), _substitute(node.else_col, defs))
     raise StageUnsupported(f"{name} over a projected column")
 
 
@@ -432,6 +434,8 @@ def _walk_names(node: Any) -> list[str]:
         return _walk_names(node.original_col)
     if name == "BinaryOperatorColumn":
         return _walk_names(node.left_side) + _walk_names(node.right_side)
+    if name == "CaseColumn":
+        return _walk_names(node.condition) + _walk_names(node.then_col) + _walk_names(node.else_col)
     raise StageUnsupported(f"{name} in a join predicate")
 
 
