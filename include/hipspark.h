@@ -706,6 +706,26 @@ int hs_dict_assign(void* stream, const hs_col* col, int64_t nrows, int32_t cap, 
 int hs_dict_combine(void* stream, int32_t n_parts, const uint8_t* const* codes, const int32_t* strides, int64_t nrows,
                     uint8_t* out_codes);
 
+/* Composite GROUP BY keys: the key parts of every row as ONE run of `width` bytes, which the aggregation
+ * tiers take as a STRING column of that fixed length.
+ *   hs_key_pack    out[r * width ...] = the bytes of parts[0], parts[1], ... of row r, each at its fixed offset (the sum of
+ *                  the widths before it).  A part is HS_I32 (4 bytes) or HS_I64 (8), stored as the raw little-endian word,
+ *                  or HS_STR with fixed_len L in 1..16 (L bytes from data + r * L: a dictionary code byte is L = 1).
+ *                  HS_E_ARG for a null pointer, any other kind, a string without a fixed length, n_parts outside
+ *                  1..HS_KEY_MAX_PARTS, width != the sum of the part widths or > HS_KEY_MAX_WIDTH, `out` not 16-byte
+ *                  aligned.  Every part is read over all nrows rows; a part whose data is 16-byte aligned may be read up to
+ *                  15 bytes past its last row, `out` is written for nrows * width bytes exactly.  nrows == 0: no launch.
+ *   hs_key_unpack  the inverse over min(nrows, *nrows_dev) rows (nrows_dev may be NULL; a device-resident count as
+ *                  hs_gather_fixed takes it): outs[k][r] = bytes [off_k, off_k + part_widths[k]) of key r.  outs[k]: 16-byte
+ *                  aligned, nrows * part_widths[k] bytes; nothing behind the last row is written.  HS_E_ARG as above. */
+#define HS_KEY_MAX_PARTS 8
+#define HS_KEY_MAX_WIDTH 16
+#define HS_KEY_TILE_ROWS 1024  /* rows a workgroup packs per step */
+#define HS_KEY_MAX_BLOCKS 2048 /* grid cap: beyond HS_KEY_TILE_ROWS * HS_KEY_MAX_BLOCKS rows a workgroup takes several tiles */
+int hs_key_pack(void* stream, const hs_col* parts, int32_t n_parts, int64_t nrows, uint8_t* out, int32_t width);
+int hs_key_unpack(void* stream, const uint8_t* keys, int32_t width, int64_t nrows, const int64_t* nrows_dev,
+                  const int32_t* part_widths, int32_t n_parts, void* const* outs);
+
 /* Exclusive scan of int64 counts -> start[n+1] (start[n] = total).  ws: hs_scan_ws_bytes(n). */
 int hs_exclusive_scan_i64(void* stream, const int64_t* counts, int64_t n, int64_t* start, void* ws);
 

@@ -568,3 +568,295 @@ extern "C" int hs_agg_rows(void* stream_, const hs_col* cols, int32_t n_cols, in
     ROWS_CHECK_LAUNCH("hs_agg_rows (write sweep)");
     return HS_OK;
 }
+
+// =====================================================================================================
+// Composite GROUP BY keys: hs_key_pack / hs_key_unpack
+// =====================================================================================================
+// Row r of the packed column is the bytes of the key parts of row r, back to back: a column-to-row transposition of byte
+// runs.  A workgroup takes a tile of HS_KEY_TILE_ROWS rows through LDS (at most 16 KiB): every part is read as the
+// contiguous byte range of the tile with 16-byte loads and laid into the tile image at row * width + offset, then the
+// image - contiguous in the output as well - leaves with 16-byte stores.  The unpack runs the same two steps the other
+// way round.  A tuple made of single bytes only (dictionary codes) skips LDS: k_key_pack_bytes.  Buffers of the engine carry 64 bytes of slack and start 16-byte aligned, so the last vector of a part's
+// range may be read past its last row; a source that is not aligned is read byte by byte.  Nothing is written past the
+// last row.
+namespace {
+
+struct KeyArgs {
+    const uint8_t* part[HS_KEY_MAX_PARTS];  // pack: sources; unpack: destinations (written through key_dst)
+    int32_t width[HS_KEY_MAX_PARTS];
+    int32_t off[HS_KEY_MAX_PARTS];
+    int32_t n_parts, W;
+};
+
+constexpr int KEY_WG = 256;
+
+// bytes [16 v, 16 v + 16) of a part's tile range -> the tile image.  `e`: elements (rows) of the part in the tile.
+__device__ __forceinline__ void key_scatter16(uint8_t* tile, const uint32_t w[4], int64_t v, int32_t pw, int32_t off, int32_t W,
+                                              int32_t nbytes) {
+    const int32_t b0 = (int32_t)v * 16;
+    if (pw == 4 && !((W | off) & 3)) {  // whole words, word-aligned in the image
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (b0 + 4 * j < nbytes) *reinterpret_cast<uint32_t*>(tile + ((b0 >> 2) + j) * W + off) = w[j];
+        return;
+    }
+    if (pw == 8 && !((W | off) & 3)) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (b0 + 4 * j < nbytes) *reinterpret_cast<uint32_t*>(tile + ((b0 >> 3) + (j >> 1)) * W + off + 4 * (j & 1)) = w[j];
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int32_t b = b0 + j;
+        if (b < nbytes) {
+            const int32_t row = pw == 1 ? b : pw == 4 ? b >> 2 : pw == 8 ? b >> 3 : b / pw;
+            tile[row * W + off + (b - row * pw)] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+        }
+    }
+}
+
+__global__ void __launch_bounds__(KEY_WG) k_key_pack(const KeyArgs A, int64_t n, uint8_t* out) {
+    __shared__ uint4 s_tile[HS_KEY_TILE_ROWS * HS_KEY_MAX_WIDTH / 16];
+    uint8_t* tile = reinterpret_cast<uint8_t*>(s_tile);
+    const int64_t n_tiles = (n + HS_KEY_TILE_ROWS - 1) / HS_KEY_TILE_ROWS;
+    const int32_t W = A.W;
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int64_t row0 = t * HS_KEY_TILE_ROWS;
+        const int32_t rows = (int32_t)(n - row0 < HS_KEY_TILE_ROWS ? n - row0 : HS_KEY_TILE_ROWS);
+        for (int k = 0; k < A.n_parts; ++k) {
+            const int32_t pw = A.width[k], off = A.off[k], nbytes = rows * pw;
+            const uint8_t* src = A.part[k] + row0 * pw;  // row0 * pw is a multiple of 16: aligned iff the part is
+            if (!((uintptr_t)src & 15)) {
+                const int32_t nvec = (nbytes + 15) >> 4;
+                for (int32_t v = threadIdx.x; v < nvec; v += KEY_WG) {
+                    const uint4 x = *reinterpret_cast<const uint4*>(src + (int64_t)v * 16);  // (slack behind the last row)
+                    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+                    key_scatter16(tile, w, v, pw, off, W, nbytes);
+                }
+            } else {
+                for (int32_t b = threadIdx.x; b < nbytes; b += KEY_WG) {
+                    const int32_t row = b / pw;
+                    tile[row * W + off + (b - row * pw)] = src[b];
+                }
+            }
+        }
+        __syncthreads();
+        const int32_t total = rows * W;
+        uint8_t* dst = out + row0 * W;  // 16-byte aligned: `out` is, and row0 * W is a multiple of 16
+        const int32_t full = total >> 4;
+        for (int32_t v = threadIdx.x; v < full; v += KEY_WG) *reinterpret_cast<uint4*>(dst + (int64_t)v * 16) = s_tile[v];
+        for (int32_t b = (full << 4) + threadIdx.x; b < total; b += KEY_WG) dst[b] = tile[b];  // the last rows' tail bytes
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(KEY_WG) k_key_unpack(const KeyArgs A, int64_t n, const int64_t* n_dev, const uint8_t* keys) {
+    __shared__ uint4 s_tile[HS_KEY_TILE_ROWS * HS_KEY_MAX_WIDTH / 16];
+    uint8_t* tile = reinterpret_cast<uint8_t*>(s_tile);
+    if (n_dev) {
+        const int64_t d = *n_dev;
+        n = d < n ? (d < 0 ? 0 : d) : n;
+    }
+    const int64_t n_tiles = (n + HS_KEY_TILE_ROWS - 1) / HS_KEY_TILE_ROWS;
+    const int32_t W = A.W;
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int64_t row0 = t * HS_KEY_TILE_ROWS;
+        const int32_t rows = (int32_t)(n - row0 < HS_KEY_TILE_ROWS ? n - row0 : HS_KEY_TILE_ROWS);
+        const int32_t total = rows * W;
+        const uint8_t* src = keys + row0 * W;
+        if (!((uintptr_t)src & 15)) {
+            const int32_t nvec = (total + 15) >> 4;
+            for (int32_t v = threadIdx.x; v < nvec; v += KEY_WG)
+                s_tile[v] = *reinterpret_cast<const uint4*>(src + (int64_t)v * 16);  // (slack behind the last row)
+        } else {
+            for (int32_t b = threadIdx.x; b < total; b += KEY_WG) tile[b] = src[b];
+        }
+        __syncthreads();
+        for (int k = 0; k < A.n_parts; ++k) {
+            const int32_t pw = A.width[k], off = A.off[k], nbytes = rows * pw;
+            uint8_t* dst = const_cast<uint8_t*>(A.part[k]) + row0 * pw;  // 16-byte aligned (hs_key_unpack checks the base)
+            const int32_t full = nbytes >> 4;
+            for (int32_t v = threadIdx.x; v < full; v += KEY_WG) {
+                uint32_t o[4] = {0, 0, 0, 0};
+                const int32_t b0 = v * 16;
+                if ((pw == 4 || pw == 8) && !((W | off) & 3)) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int32_t b = b0 + 4 * j;
+                        const int32_t row = pw == 4 ? b >> 2 : b >> 3;
+                        o[j] = *reinterpret_cast<const uint32_t*>(tile + row * W + off + (b - row * pw));
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const int32_t b = b0 + j;
+                        const int32_t row = pw == 1 ? b : pw == 4 ? b >> 2 : pw == 8 ? b >> 3 : b / pw;
+                        o[j >> 2] |= (uint32_t)tile[row * W + off + (b - row * pw)] << (8 * (j & 3));
+                    }
+                }
+                *reinterpret_cast<uint4*>(dst + (int64_t)v * 16) = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+            for (int32_t b = (full << 4) + threadIdx.x; b < nbytes; b += KEY_WG) {
+                const int32_t row = b / pw;
+                dst[b] = tile[row * W + off + (b - row * pw)];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Every part one byte wide (a tuple of dictionary codes - TPC-H Q1's key): no LDS.  Sixteen rows per lane as in
+// k_dict_combine: one 16-byte load per part, the bytes interleaved in registers (every index below is a compile-time
+// constant once unrolled), NP 16-byte stores.  The last, partial group of rows is copied byte by byte.
+constexpr int KEY_BYTES_MAX_BLOCKS = 1024;  // x 256 lanes x 16 rows = 4 Mi rows per trip of the grid-stride loop
+
+template <int NP>
+__global__ void __launch_bounds__(KEY_WG) k_key_pack_bytes(const KeyArgs A, int64_t n, uint8_t* out) {
+    const int64_t ngroups = (n + 15) / 16;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t base = g * 16;
+        uint8_t* dst = out + base * NP;
+        if (base + 16 > n) {
+            for (int64_t r = base; r < n; ++r) {
+#pragma unroll
+                for (int k = 0; k < NP; ++k) out[r * NP + k] = A.part[k][r];
+            }
+            continue;
+        }
+        uint32_t w[NP][4];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const uint4 v = *reinterpret_cast<const uint4*>(A.part[k] + base);
+            w[k][0] = v.x, w[k][1] = v.y, w[k][2] = v.z, w[k][3] = v.w;
+        }
+        uint32_t o[NP * 4];
+#pragma unroll
+        for (int i = 0; i < NP * 4; ++i) o[i] = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                const int b = r * NP + k;
+                o[b >> 2] |= ((w[k][r >> 2] >> (8 * (r & 3))) & 0xffu) << (8 * (b & 3));
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NP; ++q)
+            reinterpret_cast<uint4*>(dst)[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+    }
+}
+
+template <int NP>
+void key_launch_bytes(hipStream_t stream, const KeyArgs& A, int64_t n, uint8_t* out) {
+    int64_t blocks = ((n + 15) / 16 + KEY_WG - 1) / KEY_WG;
+    if (blocks > KEY_BYTES_MAX_BLOCKS) blocks = KEY_BYTES_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_key_pack_bytes<NP>, dim3((unsigned)blocks), dim3(KEY_WG), 0, stream, A, n, out);
+}
+
+unsigned key_grid(int64_t n) {
+    int64_t b = (n + HS_KEY_TILE_ROWS - 1) / HS_KEY_TILE_ROWS;
+    if (b < 1) b = 1;
+    if (b > HS_KEY_MAX_BLOCKS) b = HS_KEY_MAX_BLOCKS;
+    return (unsigned)b;
+}
+
+// the layout both calls share: widths -> offsets, checked against `width`
+int key_layout(const char* who, const int32_t* widths, int32_t n_parts, int32_t width, KeyArgs& A) {
+    int32_t sum = 0;
+    for (int k = 0; k < HS_KEY_MAX_PARTS; ++k) {
+        A.part[k] = nullptr;
+        A.width[k] = 0;
+        A.off[k] = 0;
+    }
+    for (int k = 0; k < n_parts; ++k) {
+        if (widths[k] < 1 || widths[k] > HS_KEY_MAX_WIDTH) {
+            hs_set_error("%s: part %d is %d bytes wide (1..%d)", who, k, (int)widths[k], HS_KEY_MAX_WIDTH);
+            return HS_E_ARG;
+        }
+        A.width[k] = widths[k];
+        A.off[k] = sum;
+        sum += widths[k];
+    }
+    if (sum != width || width > HS_KEY_MAX_WIDTH) {
+        hs_set_error("%s: width %d, the parts add up to %d (at most %d bytes)", who, (int)width, (int)sum, HS_KEY_MAX_WIDTH);
+        return HS_E_ARG;
+    }
+    A.n_parts = n_parts;
+    A.W = width;
+    return HS_OK;
+}
+
+}  // namespace
+
+extern "C" int hs_key_pack(void* stream, const hs_col* parts, int32_t n_parts, int64_t nrows, uint8_t* out, int32_t width) {
+    if (!parts || !out || nrows < 0 || n_parts < 1 || n_parts > HS_KEY_MAX_PARTS) {
+        hs_set_error("hs_key_pack: bad arguments (1..%d parts, non-null buffers)", HS_KEY_MAX_PARTS);
+        return HS_E_ARG;
+    }
+    int32_t widths[HS_KEY_MAX_PARTS];
+    for (int k = 0; k < n_parts; ++k) {
+        const hs_col& c = parts[k];
+        if (!c.data) {
+            hs_set_error("hs_key_pack: part %d has no data", k);
+            return HS_E_ARG;
+        }
+        if (c.kind == HS_I32) widths[k] = 4;
+        else if (c.kind == HS_I64) widths[k] = 8;
+        else if (c.kind == HS_STR && c.fixed_len >= 1) widths[k] = c.fixed_len;
+        else {
+            hs_set_error("hs_key_pack: part %d of kind %d / fixed_len %d: INTEGER, TIMESTAMP or a fixed-length STRING", k,
+                         (int)c.kind, (int)c.fixed_len);
+            return HS_E_ARG;
+        }
+    }
+    KeyArgs A;
+    const int rc = key_layout("hs_key_pack", widths, n_parts, width, A);
+    if (rc) return rc;
+    if ((uintptr_t)out & 15) {
+        hs_set_error("hs_key_pack: output must be 16-byte aligned");
+        return HS_E_ARG;
+    }
+    for (int k = 0; k < n_parts; ++k) A.part[k] = (const uint8_t*)parts[k].data;
+    if (nrows == 0) return HS_OK;  // nothing to launch
+    bool bytes = n_parts >= 2;  // a tuple of single bytes, every part 16-byte aligned: interleaved in registers
+    for (int k = 0; k < n_parts; ++k) bytes = bytes && widths[k] == 1 && !((uintptr_t)parts[k].data & 15);
+    hipStream_t s = (hipStream_t)stream;
+    if (bytes) {
+        switch (n_parts) {
+            case 2: key_launch_bytes<2>(s, A, nrows, out); break;
+            case 3: key_launch_bytes<3>(s, A, nrows, out); break;
+            case 4: key_launch_bytes<4>(s, A, nrows, out); break;
+            case 5: key_launch_bytes<5>(s, A, nrows, out); break;
+            case 6: key_launch_bytes<6>(s, A, nrows, out); break;
+            case 7: key_launch_bytes<7>(s, A, nrows, out); break;
+            default: key_launch_bytes<8>(s, A, nrows, out); break;
+        }
+    } else {
+        hipLaunchKernelGGL(k_key_pack, dim3(key_grid(nrows)), dim3(KEY_WG), 0, s, A, nrows, out);
+    }
+    ROWS_CHECK_LAUNCH("hs_key_pack");
+    return HS_OK;
+}
+
+extern "C" int hs_key_unpack(void* stream, const uint8_t* keys, int32_t width, int64_t nrows, const int64_t* nrows_dev,
+                             const int32_t* part_widths, int32_t n_parts, void* const* outs) {
+    if (!keys || !part_widths || !outs || nrows < 0 || n_parts < 1 || n_parts > HS_KEY_MAX_PARTS) {
+        hs_set_error("hs_key_unpack: bad arguments (1..%d parts, non-null buffers)", HS_KEY_MAX_PARTS);
+        return HS_E_ARG;
+    }
+    KeyArgs A;
+    const int rc = key_layout("hs_key_unpack", part_widths, n_parts, width, A);
+    if (rc) return rc;
+    for (int k = 0; k < n_parts; ++k) {
+        if (!outs[k] || ((uintptr_t)outs[k] & 15)) {
+            hs_set_error("hs_key_unpack: output %d is null or not 16-byte aligned", k);
+            return HS_E_ARG;
+        }
+        A.part[k] = (const uint8_t*)outs[k];
+    }
+    if (nrows == 0) return HS_OK;  // nothing to launch
+    hipLaunchKernelGGL(k_key_unpack, dim3(key_grid(nrows)), dim3(KEY_WG), 0, (hipStream_t)stream, A, nrows, nrows_dev, keys);
+    ROWS_CHECK_LAUNCH("hs_key_unpack");
+    return HS_OK;
+}

@@ -16,7 +16,7 @@ from typing import Any, Callable
 
 from . import tasks as _t
 from .plan import PhysicalPlan
-from .sql import SortKey
+from .sql import KeyTupleCol, SortKey
 
 # builder call -> (task class, arguments -> keyword fields of that class)
 _APPENDERS: dict[str, tuple[type, Callable[..., dict[str, Any]]]] = {
@@ -27,7 +27,7 @@ _APPENDERS: dict[str, tuple[type, Callable[..., dict[str, Any]]]] = {
 
 
 class GroupedData:
-    """``df.group_by(col)``: waits for ``agg(...)`` to become an aggregate node over ``df``'s chain."""
+    """``df.group_by(col)`` / ``df.group_by(col, col, ...)``: waits for ``agg(...)`` to become an aggregate node over ``df``'s chain."""
 
     def __init__(self, df: "DataFrame", column: Any) -> None:
         self.df, self.group_column = df, column
@@ -52,8 +52,24 @@ class DataFrame:
         self.task.alias = alias_name
         return self
 
-    def group_by(self, column: Any) -> GroupedData:
-        return GroupedData(self, column)
+    def group_by(self, *columns: Any) -> GroupedData:
+        """GROUP BY one column, or a tuple of up to eight plain columns of the input: the result then
+        holds the key columns under their own names and types, in the order given, then the aggregates."""
+        if not columns:
+            raise TypeError("group_by() needs at least one column")
+        if len(columns) == 1:
+            return GroupedData(self, columns[0])
+        if len(columns) > KeyTupleCol.MAX_PARTS:
+            raise ValueError(f"GROUP BY takes at most {KeyTupleCol.MAX_PARTS} columns, not {len(columns)}")
+        for col in columns:
+            if type(col).__name__ not in {"Col", "SchemaCol"}:
+                raise ValueError(f"GROUP BY over several columns takes plain columns, not the expression {col}: "
+                                 "select(... .alias()) first")
+        names = [col.name for col in columns]
+        repeated = sorted({name for name in names if names.count(name) > 1})
+        if repeated:
+            raise ValueError(f"GROUP BY names a column twice: {repeated}")
+        return GroupedData(self, KeyTupleCol(columns))
 
     def agg(self, *agg_columns: Any) -> "DataFrame":
         """Aggregates over the whole input, without GROUP BY: one row holding the aggregate columns in the order given,

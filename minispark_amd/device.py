@@ -25,7 +25,7 @@ import torch
 from . import hipspark as hs
 from .constants import ColumnType, Schema
 from .io import LazyRaw, StrCol, timestamp_to_datetime
-from .lowering import NeedsDecoded, ProgramBuilder, StringParts, lower_aggregate
+from .lowering import KeySpec, NeedsDecoded, ProgramBuilder, StringParts, key_tuple_spec, lower_aggregate
 
 PAD = 64  # bytes of slack behind every buffer
 
@@ -816,6 +816,54 @@ class Device:
             strd = (C.c_int32 * len(col_parts))(*strides)
             hs.check(self.lib.hs_dict_combine(self.stream, len(col_parts), ptrs, strd, n, out.data_ptr()), "hs_dict_combine")
         return DCol(hs.STR, out, n, lens=self.const_lens(1, n), offs=None, fixed_len=1, dict=tuple(entries))
+
+    # ---- composite GROUP BY keys ---------------------------------------------------------------
+    @staticmethod
+    def key_spec(batch: DBatch, parts: Sequence[int]) -> KeySpec:
+        """The byte layout of the key tuple made of the batch's columns ``parts`` (lowering.key_tuple_spec): every refusal
+        - FLOAT, a STRING without dictionary or fixed length, more than 16 bytes - is raised here, before any launch."""
+        return key_tuple_spec([(batch.schema[i][0], batch.schema[i][1], batch.cols[i].kind, batch.cols[i].fixed_len,
+                                batch.cols[i].dict) for i in parts])
+
+    def pack_key(self, batch: DBatch, parts: Sequence[int]) -> DCol:
+        """The columns ``parts`` of every row of the batch (WHERE or not) as one STRING column of fixed length W, the sum
+        of the parts' widths: ONE launch (hs_key_pack).  To every aggregation tier it is a fixed-length string key."""
+        spec = self.key_spec(batch, parts)
+        if batch.lazy:
+            raise DeviceError("pack_key needs an exact row count")
+        if any(batch.cols[i].virtual for i in parts):
+            raise DeviceError("virtual columns of a join left in place cannot be packed")
+        n, width = batch.nrows, spec.width
+        out = self.empty(max(n, 1) * width, torch.uint8)
+        if n > 0:
+            arr = (hs.hs_col * len(parts))()
+            for k, i in enumerate(parts):
+                arr[k] = batch.cols[i].as_hs()
+            hs.check(self.lib.hs_key_pack(self.stream, arr, len(parts), n, out.data_ptr(), width), "hs_key_pack")
+        return DCol(hs.STR, out, n, lens=self.const_lens(width, n), offs=None, fixed_len=width)
+
+    def unpack_key(self, col: DCol, spec: KeySpec, n_dev: torch.Tensor | None = None) -> list[DCol]:
+        """The inverse over result groups: the packed column's rows cut back into the parts ``spec`` names (hs_key_unpack,
+        one launch).  ``n_dev``: the device-resident count of a lazy batch - only that many rows are written.  A code-byte
+        part comes back as a coded STRING column with the dictionary it was packed from."""
+        n = col.n
+        if col.kind != hs.STR or (n > 0 and col.fixed_len != spec.width):
+            raise DeviceError(f"unpack_key: a STRING column of fixed length {spec.width} expected, got kind {col.kind} / "
+                              f"fixed_len {col.fixed_len}")
+        outs = [self.empty(max(n, 1) * p.width, torch.uint8) for p in spec.parts]
+        if n > 0:
+            widths = (C.c_int32 * len(outs))(*[p.width for p in spec.parts])
+            ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+            hs.check(self.lib.hs_key_unpack(self.stream, col.data.data_ptr(), spec.width, n,
+                                            n_dev.data_ptr() if n_dev is not None else None, widths, len(outs), ptrs),
+                     "hs_key_unpack")
+        cols = []
+        for p, o in zip(spec.parts, outs):
+            if p.kind == hs.STR:
+                cols.append(DCol(hs.STR, o, n, lens=self.const_lens(p.width, n), offs=None, fixed_len=p.width, dict=p.dict))
+            else:
+                cols.append(DCol(p.kind, o.view(_TORCH_DTYPE[p.kind]), n))
+        return cols
 
     # ---- string concat -------------------------------------------------------------------------------
     def concat_strings(self, batch: DBatch, parts: StringParts, n: int) -> DCol:

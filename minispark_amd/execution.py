@@ -200,6 +200,7 @@ class HipExecutionEngine(ExecutionEngine):
         self._no_fused_join: set[Any] = set()  # join task ids whose build side turned out to hold duplicate keys
         self._fused_join_tasks: set[Any] = set()  # join task ids the running query took the in-place path for
         self._lds_merges: list[int] = []  # final-merge tasks the running query folded on chip (see HS_FLAG_MERGE_ROWS)
+        self._key_specs: dict[str, Any] = {}  # packed key tuple name -> its byte layout in the running query
         budget = os.environ.get("HIPSPARK_HBM_BUDGET")
         self.hbm_budget: int | None = int(float(budget)) if budget else None  # bytes of referenced columns kept resident
         self.streamed_ranges = 0
@@ -424,6 +425,7 @@ class HipExecutionEngine(ExecutionEngine):
             self._version += 1  # a full run may load / re-code tables, grow capacities, replace recordings
             self.dev.reset_flags()
             self._fused_join_tasks.clear()
+            self._key_specs.clear()
             self._join8_reuse = None
             self.last_probe_route = None
             self._lds_merges: list[int] = []
@@ -750,11 +752,18 @@ class HipExecutionEngine(ExecutionEngine):
                         continue
                 batch = self._project(batch, pending, task)
                 pending = []
+            elif tname == "UnpackKeyTask":
+                batch = self._unpack_key_tuple(self._materialise(batch, pending), task)
+                pending = []
             elif tname == "AggregateTask":
                 if task.before_shuffle and task.group_by_column is None:
                     batch = self._aggregate_whole_input(batch, pending, task)
                     pending = []
                     continue
+                if task.before_shuffle and _cls(task.group_by_column) == "KeyTupleCol":
+                    # several key columns: packed into one fixed-width column the ladder below groups by;
+                    # the WHERE stays pending
+                    batch, pending = self._pack_key_tuple(batch, pending, task)
                 if task.before_shuffle and batch.join8 is not None:
                     # the join's probe runs inside this aggregate's scan; what it cannot hold sends the
                     # query back through the materialising joins
@@ -867,6 +876,54 @@ class HipExecutionEngine(ExecutionEngine):
             else:
                 raise NotImplementedError(f"consumer {tname}")
         return self._materialise(batch, pending)
+
+    def _pack_key_tuple(self, batch: Any, pending: list, task: Any) -> tuple[Any, list]:
+        """In front of the partial aggregate of a GROUP BY over several columns: the key parts of EVERY row of the batch
+        (as the stage ABI's computed key: WHERE or not) packed into one STRING column of fixed width, appended under the
+        tuple's reserved name - the aggregation ladder then groups by that column as by any fixed-length string.  Parts must
+        be in their stored kinds; an INTEGER held wider is range-checked to its stored kind as the shuffle write would,
+        over the rows the WHERE leaves.  A join left in place has virtual columns: the query goes back through the
+        materialising join.  Every refusal (lowering.key_tuple_spec) is raised before the pack's launch."""
+        from . import hipspark as hs  # noqa: PLC0415
+        from .constants import ColumnType  # noqa: PLC0415
+
+        key = task.group_by_column
+        if self.dist is not None:
+            raise NotImplementedError(f"GROUP BY {key} over several columns runs on one GPU: on N ranks the key parts' "
+                                      "dictionaries and widths would have to be agreed first")
+        if batch.join8 is not None:
+            self._no_join8.add(batch.join_task_id)
+            raise RestartQuery
+        if batch.unit_col is not None:
+            self._no_fused_join.add(batch.join_task_id)
+            raise RestartQuery
+        batch = self.dev.resolve(batch)
+        parts = [batch.column_index(part.name) for part in key.parts]
+        wide = [i for i in parts if batch.schema[i][1] == ColumnType.INTEGER and batch.cols[i].kind == hs.I64]
+        if wide:
+            self.dev.key_spec(dataclasses.replace(batch, cols=[dataclasses.replace(c, kind=hs.I32) if i in wide else c
+                                                               for i, c in enumerate(batch.cols)]), parts)  # refusals first
+            batch, pending = self._materialise(batch, pending), []
+            cols = list(batch.cols)
+            for i in wide:
+                cols[i] = self.dev.quantise_col(cols[i], ColumnType.INTEGER)
+            batch = dataclasses.replace(batch, cols=cols)
+        spec = self.dev.key_spec(batch, parts)
+        known = self._key_specs.setdefault(key.name, spec)
+        if known != spec:
+            raise ExecutionError(f"GROUP BY {key}: the key parts change their width or dictionary between block ranges")
+        packed = self.dev.pack_key(batch, parts)
+        return dataclasses.replace(batch, schema=[*batch.schema, (key.name, ColumnType.STRING)],
+                                   cols=[*batch.cols, packed]), pending
+
+    def _unpack_key_tuple(self, batch: Any, task: Any) -> Any:
+        """Directly above the merge of a GROUP BY over several columns: column 0, the packed tuple of every result group,
+        becomes the key columns again (the group count may still live on the device)."""
+        spec = self._key_specs.get(task.key.name)
+        if spec is None:
+            raise ExecutionError(f"GROUP BY {task.key}: no partial aggregate of this query packed the key")
+        key_cols = self.dev.unpack_key(batch.cols[0], spec, batch.nrows_dev)
+        return dataclasses.replace(batch, schema=list(task.inferred_schema), cols=[*key_cols, *batch.cols[1:]])
 
     def _aggregate_whole_input(self, batch: Any, pending: Sequence[Any], task: Any) -> Any:
         """The partial phase of an aggregate without GROUP BY (hs_agg_scalar): at most one partial row per unit, under
@@ -1025,6 +1082,9 @@ class HipExecutionEngine(ExecutionEngine):
         from .hipspark import HipSparkLimit  # noqa: PLC0415
 
         producer, consumers, writer = stage.producer, list(stage.consumers), stage.writer
+        if feeds_aggregate and any(_cls(t) == "AggregateTask" and _cls(t.group_by_column) == "KeyTupleCol" for t in consumers):
+            raise NotImplementedError("a join whose probe side is read in block ranges cannot feed a GROUP BY over several "
+                                      "columns: raise HIPSPARK_HBM_BUDGET so that the probe side stays resident")
         left = outputs[id(stage.dependencies[0])]
         deferred = outputs[id(stage.dependencies[1])]
         scan = deferred.stage

@@ -18,6 +18,11 @@ HS_MAX_ACC = 16
 HS_MAX_STACK = 8
 HS_MAX_OUTS = 16
 HS_MAX_PARTS = 8
+KEY_MAX_PARTS = 8      # hs_key_pack / hs_key_unpack: parts of a composite GROUP BY key ...
+KEY_MAX_WIDTH = 16     # ... and bytes of the packed key
+KEY_TILE_ROWS = 1024   # rows a workgroup packs per step
+KEY_MAX_BLOCKS = 2048  # grid cap: beyond KEY_TILE_ROWS * KEY_MAX_BLOCKS rows a workgroup takes several tiles
+KEY_BYTES_PASS_ROWS = 1024 * 256 * 16  # the all-code-bytes form of hs_key_pack: rows one trip of its capped grid covers
 HS_FUSED_COLS = 8
 
 # storage kinds
@@ -391,6 +396,8 @@ SIGNATURES: dict[str, tuple] = {
     "hs_dict_build": (C.c_int, [_P, _COLP, _I64, _I32, _P, _P, _P, _P]),
     "hs_dict_assign": (C.c_int, [_P, _COLP, _I64, _I32, _P, _P, _P, _P, _P]),
     "hs_dict_combine": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _I64, _P]),
+    "hs_key_pack": (C.c_int, [_P, _COLP, _I32, _I64, _P, _I32]),
+    "hs_key_unpack": (C.c_int, [_P, _P, _I32, _I64, _P, C.POINTER(_I32), _I32, C.POINTER(_P)]),
     "hs_quantise": (C.c_int, [_P, _P, _I32, _I64, _P, _P, _P]),
     "hs_quantise_many": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _I64, _P, C.POINTER(_P), _P]),
     "hs_slab_unpack": (C.c_int, [_P, _P, _I32, _I64, _I64, _I64, _I32, C.POINTER(_I64), C.POINTER(_I32),

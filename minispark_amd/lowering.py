@@ -527,7 +527,7 @@ def lower_aggregate(schema: Schema, kinds: Sequence[int], filters: Sequence[Any]
     key_col = None
     if group_by is not None:
         key = unalias(group_by)
-        if _cls(key) not in ("Col", "SchemaCol"):
+        if _cls(key) not in ("Col", "SchemaCol", "KeyTupleCol"):  # (a key tuple: its packed column, looked up by name)
             raise ValueError(f"Unknown columns in GroupBy: {[getattr(key, 'name', key)]}")
         key_col = b.use_column(key.name)
         b.emit_key()
@@ -552,6 +552,62 @@ def lower_aggregate(schema: Schema, kinds: Sequence[int], filters: Sequence[Any]
     numeric_slots = sum(1 for c in prog.columns if kinds[c] != hs.STR or c == key_col or c in prog.code_columns)
     key_slot = prog.columns.index(key_col) if key_col is not None else -1
     return AggregateLowering(prog, key_slot, acc_ops, acc_is_int, agg_to_acc, numeric_slots)
+
+
+KEY_MAX_PARTS = 8    # HS_KEY_MAX_PARTS
+KEY_MAX_WIDTH = 16   # HS_KEY_MAX_WIDTH: what the radix tier's two key words hold
+
+
+@dataclass(frozen=True)
+class KeyPart:
+    """One part of a packed composite GROUP BY key: ``width`` bytes at a fixed offset of every key.
+    ``dict``: the part is a dictionary code byte; the dictionary stays on the host and is re-attached at unpack."""
+    name: str
+    type: ColumnType
+    kind: int
+    width: int
+    dict: tuple | None = None
+
+
+@dataclass(frozen=True)
+class KeySpec:
+    parts: tuple
+    width: int
+
+
+def key_tuple_spec(parts: Sequence[tuple]) -> KeySpec:
+    """The byte layout of a composite GROUP BY key from its parts' (name, column type, device kind, fixed_len, dictionary):
+    INTEGER 4 bytes, TIMESTAMP 8, a dictionary-coded STRING its code byte, a plain STRING of one fixed length L its L
+    bytes.  Pure (no device).  Every refusal is a NotImplementedError naming the column, raised before any launch."""
+    if not 1 <= len(parts) <= KEY_MAX_PARTS:
+        raise NotImplementedError(f"a composite GROUP BY key has 1 .. {KEY_MAX_PARTS} parts, not {len(parts)}")
+    out = []
+    for name, col_type, kind, fixed_len, entries in parts:
+        if col_type == ColumnType.FLOAT or kind in (hs.F32, hs.F64):
+            raise NotImplementedError(f'GROUP BY over several columns: "{name}" is FLOAT, and -0.0 == 0.0 / NaN have no byte '
+                                      "form to group by")
+        if col_type == ColumnType.INTEGER and kind == hs.I32:
+            width = 4
+        elif col_type == ColumnType.TIMESTAMP and kind == hs.I64:
+            width = 8
+        elif col_type == ColumnType.STRING and kind == hs.STR:
+            if entries is not None:
+                width = 1
+            elif fixed_len is not None and 1 <= fixed_len <= 255:
+                width = fixed_len
+            else:
+                raise NotImplementedError(f'GROUP BY over several columns: STRING "{name}" has neither a dictionary nor one '
+                                          "fixed length (variable-length key parts are not packed)")
+        else:
+            raise NotImplementedError(f'GROUP BY over several columns: "{name}" of type {col_type} is held as device kind '
+                                      f"{kind}, not in its stored kind")
+        out.append(KeyPart(name, col_type, kind, width, tuple(entries) if entries is not None else None))
+    total = sum(p.width for p in out)
+    if total > KEY_MAX_WIDTH:
+        widths = ", ".join(f"{p.name}: {p.width}" for p in out)
+        raise NotImplementedError(f"GROUP BY over several columns: the key is {total} bytes wide ({widths}), more than the "
+                                  f"{KEY_MAX_WIDTH} the aggregation tiers take")
+    return KeySpec(tuple(out), total)
 
 
 class FinishUnsupported(Exception):

@@ -5,7 +5,7 @@ requirements, so `.sql()` would not work next to the HIP engine without this mod
 A hand-written backtracking recursive-descent parser for the same language:
 
     SELECT [DISTINCT] select_list FROM 'path' [AS t] { [LEFT|RIGHT|INNER|FULL] JOIN 'path' [AS t] ON cond }
-           [WHERE cond] [GROUP BY col [HAVING cond]] [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] [LIMIT n] ;
+           [WHERE cond] [GROUP BY col | (col {, col}) [HAVING cond]] [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] [LIMIT n] ;
 
 * select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e) [AS name]``, ``expr [AS name]``;
 * conditions: OR < AND < NOT < comparison | ( cond ) | BETWEEN | LIKE, comparators = != <= >= < >;
@@ -16,7 +16,7 @@ A hand-written backtracking recursive-descent parser for the same language:
   without GROUP BY stays a syntax error, arithmetic over aggregates (``SUM(a) / SUM(b)``) is not part of this form;
 * like the reference: whitespace is required around keywords, the closing ``;`` is mandatory, every join kind
   is executed as an inner join (parser.py:131-133), numbers are integers (parser.py:349), NOT raises
-  NotImplementedError (sql.py:44-45), GROUP BY takes one column (dataframe.py:64);
+  NotImplementedError (sql.py:44-45), the unparenthesised GROUP BY takes one column (dataframe.py:64);
 * beyond the reference: ORDER BY takes names of the RESULT (a select item's alias, or its generated name), each ascending
   unless DESC follows, and LIMIT a non-negative integer; both become one ``order_by`` / ``limit`` after the final select;
   ``SELECT DISTINCT`` (the keyword, then whitespace) becomes ``distinct()`` between the final select and ``order_by``:
@@ -25,6 +25,12 @@ A hand-written backtracking recursive-descent parser for the same language:
   ``CASE`` (searched form only, ELSE mandatory, INTEGER / FLOAT branches, several WHEN arms nest to the right) stands
   wherever an expression may: a select item, an aggregate's argument, either side of a comparison, inside arithmetic or
   another CASE.  A column called ``CASE`` still parses as a column (no old text holds ``CASE`` whitespace ``WHEN``).
+
+* GROUP BY over several columns is spelled in the row form, ``GROUP BY (a, b {, c})``: parentheses around a comma list of
+  up to eight plain columns, optional whitespace inside; it becomes ``group_by(a, b, ...)`` and the result holds the key
+  columns under their own names.  ``GROUP BY (a)`` is ``GROUP BY a``.  The row form is tried after the
+  bare column, so every text accepted before builds the tree it built.  The unparenthesised list ``GROUP BY a, b`` is
+  still rejected with a ``TypeError`` (its message points at the row form): tests/test_parser.py pins that rejection.
 
 Alternatives are tried in the grammar's order and the first that fits wins (ordered choice), so texts the
 reference accepts build the same task tree here (tests/test_parser.py compares both renderings).
@@ -163,7 +169,10 @@ class _Parser:
         if has_where:
             df = df.filter(where)
         if has_group:
-            group_cols, having = group
+            group_cols, having, row_form = group
+            if len(group_cols) > 1 and not row_form:
+                raise TypeError(f"GROUP BY {', '.join(c.name for c in group_cols)}: a bare GROUP BY takes one column; "
+                                f"write the row form GROUP BY ({', '.join(c.name for c in group_cols)}) for several")
             key_names = {c.name for c in group_cols}
             agg_cols = [c for c in select_list if type(c) is AggCol]
             stray = [c for c in select_list if type(c) is not AggCol and c.name not in key_names]
@@ -272,13 +281,30 @@ class _Parser:
         self.ws()
         return self.condition()
 
-    def group_by_clause(self) -> tuple[list[Col], Col | None]:
+    def group_by_clause(self) -> tuple[list[Col], Col | None, bool]:
         self.lit("GROUP")
         self.ws()
         self.lit("BY")
         self.ws()
-        cols = [self.column_name()]
-        cols += self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), self.column_name())[3])
+
+        def bare() -> list[Col]:
+            cols = [self.column_name()]
+            cols += self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), self.column_name())[3])
+            return cols
+
+        def row() -> list[Col]:
+            self.lit("(")
+            self.ows()
+            cols = bare()
+            self.ows()
+            self.lit(")")
+            return cols
+
+        # ordered choice: the bare form first (a column name never starts with a parenthesis), then the row form
+        row_form, cols = False, None
+        matched, cols = self.attempt(bare)
+        if not matched:
+            row_form, cols = True, row()
 
         def having() -> Col:
             self.ws()
@@ -287,7 +313,7 @@ class _Parser:
             return self.condition()
 
         has_having, cond = self.attempt(having)
-        return cols, cond if has_having else None
+        return cols, cond if has_having else None, row_form
 
     def order_by_clause(self) -> list[SortKey]:
         self.lit("ORDER")

@@ -14,6 +14,9 @@ Rewrites applied, in the reference's order (plan.py:224-235):
    LoadShuffleFiles -> Aggregate(after)] (+ ProjectTask computing AVG = sum/count, plan.py:190-203); an aggregate
    without GROUP BY (this build's own) expands alike with ``key=None`` and no key column in the projection;
    join inputs each get a WriteToShufflePartitions on their key (plan.py:186-189);
+   2a. a GROUP BY over several columns (``KeyTupleCol``, this build's own): both aggregates and the shuffle write see the
+   tuple as ONE packed STRING column under the tuple's reserved name, and an ``UnpackKeyTask`` directly above the merging
+   aggregate - below the AVG projection, HAVING, the final select and any ``SortTask`` - restores the key columns;
 3. strip ``alias.`` prefixes from the output column names with a final ProjectTask (plan.py:207-222);
 4. cut the chain into stages at every shuffle write / join, dependencies first.
 
@@ -25,7 +28,7 @@ from __future__ import annotations
 
 from copy import deepcopy
 
-from .sql import AggCol, Col
+from .sql import AggCol, Col, KeyTupleCol
 from .tasks import (
     AggregateTask,
     BroadcastHashJoinTask,
@@ -35,6 +38,7 @@ from .tasks import (
     ProjectTask,
     SortTask,
     Task,
+    UnpackKeyTask,
     VoidTask,
     WriterTask,
     WriteToLocalFileTask,
@@ -131,14 +135,26 @@ class PhysicalPlan:
         if type(task) is AggregateTask and task.before_shuffle:
             requested = task.agg_columns
             carried = [part for agg in requested for part in agg.expand_avg()]
+            key_tuple = task.group_by_column if type(task.group_by_column) is KeyTupleCol else None
+            if key_tuple is not None:
+                # several key columns: from the partial aggregate to the merge they are ONE packed column (rewrite 2a)
+                part_schema = list(task.inferred_schema[: len(key_tuple.parts)])
+                task.group_by_column = key_tuple.as_packed()
             partial = AggregateTask(task.parent_task, group_by_column=task.group_by_column, agg_columns=carried)
             shuffled = WriteToShufflePartitions(partial, key_column=task.group_by_column)
             task.parent_task = LoadShuffleFilesTask(shuffled)
             task.before_shuffle = False
             task.agg_columns = [AggCol(agg.type, Col(agg.name)) for agg in carried]
+            top: Task = task
+            if key_tuple is not None:
+                top = UnpackKeyTask(task, key=task.group_by_column, part_schema=part_schema)
             if any(agg.type == "avg" for agg in requested):
-                key = [] if task.group_by_column is None else [Col(task.group_by_column.name)]
-                return ProjectTask(task, columns=[*key, *[agg.projection() for agg in requested]])
+                if key_tuple is not None:
+                    key = [Col(part.name) for part in key_tuple.parts]
+                else:
+                    key = [] if task.group_by_column is None else [Col(task.group_by_column.name)]
+                return ProjectTask(top, columns=[*key, *[agg.projection() for agg in requested]])
+            return top
         return task
 
     @staticmethod

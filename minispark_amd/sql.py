@@ -356,6 +356,44 @@ class CaseColumn(Col):
     __repr__ = __str__
 
 
+class KeyTupleCol(Col):
+    """The key of a GROUP BY over several columns (no reference counterpart: DESIGN.md 4.4c): ``parts`` are plain columns
+    of the aggregate's input, in the order given.  Between the partial aggregate and the final merge the tuple travels as
+    ONE column of fixed-width bytes under this node's reserved name - parentheses and commas, which no column the parser
+    reads can carry - so its type is STRING; ``packed`` marks the nodes of the physical plan that see that column, the
+    logical aggregate (``packed`` False) yields the parts themselves."""
+
+    MAX_PARTS = 8
+
+    def __init__(self, parts: Iterable[Col], packed: bool = False) -> None:
+        self.parts = tuple(parts)
+        self.packed = packed
+        super().__init__("__hs_key(" + ",".join(p.name for p in self.parts) + ")")
+
+    def __hash__(self) -> int:
+        return hash(("KeyTupleCol", tuple(hash(p) for p in self.parts)))
+
+    @property
+    def children(self) -> tuple[Col, ...]:
+        return self.parts
+
+    def as_packed(self) -> "KeyTupleCol":
+        return KeyTupleCol(self.parts, packed=True)
+
+    def part_schema(self, schema: Schema) -> Schema:
+        return [(p.name, p.infer_type(schema)) for p in self.parts]
+
+    def infer_type(self, schema: Schema) -> ColumnType:
+        if not any(name == self.name for name, _ in schema):  # (behind the partial aggregate only the packed column is left)
+            self.part_schema(schema)  # ValueError('Column "x" not found in schema ...')
+        return ColumnType.STRING
+
+    def __str__(self) -> str:
+        return "(" + ", ".join(str(p) for p in self.parts) + ")"
+
+    __repr__ = __str__
+
+
 # instance fields of the column classes that code reads without calling anything
 _COL_FIELDS = frozenset({"name", "original_col", "left_side", "right_side", "operator", "value", "pattern", "type",
                          "condition", "then_col", "else_col"})

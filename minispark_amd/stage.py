@@ -126,6 +126,9 @@ def _plan_of(full_task: Any, plan: Any) -> list:
             if _cls(task) == "AggregateTask" and task.group_by_column is None:
                 # (the stage blobs describe a key column; the engine runs this form through hs_agg_scalar)
                 raise StageUnsupported("an aggregate without GROUP BY")
+            if _cls(task) == "UnpackKeyTask" or (_cls(task) == "AggregateTask" and _cls(task.group_by_column) == "KeyTupleCol"):
+                # (the stage blobs describe ONE key column of the table; the engine packs the tuple first: DESIGN.md 4.4c)
+                raise StageUnsupported("GROUP BY over several columns")
     return stages
 
 

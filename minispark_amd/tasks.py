@@ -19,7 +19,7 @@ from typing import Iterator, Literal
 
 from .constants import Schema
 from .io import BlockFile
-from .sql import AggCol, BinaryOperatorColumn, Col, LikeColumn
+from .sql import AggCol, BinaryOperatorColumn, Col, KeyTupleCol, LikeColumn
 
 JoinType = Literal["inner", "left", "right", "outer"]
 
@@ -197,7 +197,10 @@ class AggregateTask(ConsumerTask):
     """Hash group-by on ONE plain column.  ``before_shuffle`` = the per-job partial phase, otherwise
     the merge phase that combines column i+1 of the shuffled partial rows with aggregate i
     (tasks.py:263-340).  ``group_by_column=None`` (no reference counterpart) aggregates the whole input: the value of
-    grouping by a column that is equal in every row, without that column - one row, or none when no row came in."""
+    grouping by a column that is equal in every row, without that column - one row, or none when no row came in.
+    A ``KeyTupleCol`` (no reference counterpart either) groups by several columns: the logical node yields the key columns
+    under their own names and types, then the aggregates; in the physical plan the partial and the merging node see the
+    tuple as one packed STRING column and an ``UnpackKeyTask`` above the merge restores the key columns."""
 
     group_by_column: Col | None
     agg_columns: list[AggCol]
@@ -211,10 +214,10 @@ class AggregateTask(ConsumerTask):
             _check_known(list(self.agg_columns), schema, "aggregation")
             return [(agg.name, agg.infer_type(schema)) for agg in self.agg_columns]
         _check_known([*self.agg_columns, self.group_by_column], schema, "aggregation")
-        return [
-            (self.group_by_column.name, self.group_by_column.infer_type(schema)),
-            *[(agg.name, agg.infer_type(schema)) for agg in self.agg_columns],
-        ]
+        key = self.group_by_column
+        key_schema = (key.part_schema(schema) if type(key) is KeyTupleCol and not key.packed
+                      else [(key.name, key.infer_type(schema))])
+        return [*key_schema, *[(agg.name, agg.infer_type(schema)) for agg in self.agg_columns]]
 
     def describe(self) -> str:
         if self.group_by_column is None:
@@ -223,6 +226,25 @@ class AggregateTask(ConsumerTask):
             f"AggregateTask(group_by: {self.group_by_column}, agg: {self.agg_columns}, "
             f"before_shuffle:{self.before_shuffle})"
         )
+
+
+@dataclass(kw_only=True)
+class UnpackKeyTask(ConsumerTask):
+    """Directly above the merging aggregate of a GROUP BY over several columns (no reference counterpart): column 0, the
+    packed key tuple, is cut back into the key columns ``part_schema`` names - their own names and types, in the order
+    given - and the aggregates follow unchanged."""
+
+    key: KeyTupleCol
+    part_schema: Schema
+
+    def validate_schema(self) -> Schema:
+        schema = self.parent_task.validate_schema()
+        if not schema or schema[0][0] != self.key.name:
+            raise AssertionError(f"UnpackKeyTask expects the packed key {self.key.name} in column 0, got {schema}")
+        return [*self.part_schema, *schema[1:]]
+
+    def describe(self) -> str:
+        return f"UnpackKey({self.key} <- {self.key.name})"
 
 
 @dataclass(kw_only=True)
@@ -282,6 +304,8 @@ class WriteToShufflePartitions(WriterTask):
         if self.key_column is None:
             return schema
         known = {name for name, _ in schema}
+        if type(self.key_column) is KeyTupleCol and self.key_column.name in known:
+            return schema  # the packed key tuple: its parts stayed behind the partial aggregate
         unknown = [n for n in _plain_column_names(self.key_column) if n not in known]
         if unknown:
             raise ValueError(f"Unknown columns in GroupBy: {unknown}")
@@ -313,6 +337,7 @@ __all__ = [
     "ProjectTask",
     "SortTask",
     "Task",
+    "UnpackKeyTask",
     "VoidTask",
     "WriteToLocalFileTask",
     "WriteToShufflePartitions",
