@@ -126,9 +126,23 @@ enum hs_op {
     HS_OP_DICTBIT = 36, /* a = slot of a dictionary-coded column (one code byte per row), b = index of the first of
                            c (1..4) literal words holding one bit per dictionary entry; push bit[code]: LIKE and
                            string comparisons with a literal, evaluated once per dictionary entry on the host */
-    HS_OP_SEL = 37      /* c x y -> (c != 0 ? x : y): pops three, pushes one (needs sp >= 3).  Acts on the raw 64-bit cells,
+    HS_OP_SEL = 37,     /* c x y -> (c != 0 ? x : y): pops three, pushes one (needs sp >= 3).  Acts on the raw 64-bit cells,
                            so it serves f64 and i64 alike (NaN payloads, -0.0 and i64 extremes pass through); raises no
                            flag.  CASE WHEN c THEN x ELSE y END: both branches are evaluated, then one is chosen */
+    HS_OP_DATEPART = 38 /* a = selector; t -> part(t): pops one i64 cell of microseconds since 1970-01-01T00:00:00, pushes
+                           one i64 cell (needs sp >= 1).  Proleptic Gregorian calendar, no time zone, floor division; total
+                           over i64, raises no flag.  a = 0 .. 8: HS_DP_YEAR ... HS_DP_DAYOFYEAR (an integer); a = 16 .. 23:
+                           HS_DT_YEAR ... HS_DT_SECOND (the first microsecond of the unit holding t); any other a is a bad
+                           program */
+};
+
+/* selectors of HS_OP_DATEPART */
+enum hs_datepart {
+    HS_DP_YEAR = 0, HS_DP_QUARTER = 1 /* 1-4 */, HS_DP_MONTH = 2 /* 1-12 */, HS_DP_DAY = 3 /* 1-31 */, HS_DP_HOUR = 4,
+    HS_DP_MINUTE = 5, HS_DP_SECOND = 6 /* whole seconds */, HS_DP_DAYOFWEEK = 7 /* ISO: Monday 1 ... Sunday 7 */,
+    HS_DP_DAYOFYEAR = 8 /* 1-366 */,
+    HS_DT_YEAR = 16, HS_DT_QUARTER = 17, HS_DT_MONTH = 18, HS_DT_WEEK = 19 /* starts on Monday */, HS_DT_DAY = 20,
+    HS_DT_HOUR = 21, HS_DT_MINUTE = 22, HS_DT_SECOND = 23
 };
 
 typedef struct hs_program {

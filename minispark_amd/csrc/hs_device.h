@@ -241,6 +241,117 @@ __device__ __forceinline__ void hs_divmod_f(double vx, double wx, double& floord
     }
 }
 
+// ---- calendar: HS_OP_DATEPART ------------------------------------------------------------------
+// A TIMESTAMP cell is microseconds since 1970-01-01T00:00:00, proleptic Gregorian, no time zone.  ONE floor division of
+// the cell by the microseconds of a day gives the day number (|days| <= 106 751 992) and the microsecond of the day; all
+// that follows is 32-bit arithmetic with compile-time divisors (multiply-high sequences, no division instruction
+// sequence, no double): the era / day-of-era / year-of-era decomposition (civil_from_days; an era is 400 years = 146 097
+// days, eras start on 0000-03-01 so the leap day is an era's last).  Total over i64, no flag.  Truncation rebuilds the
+// cell in wrapping 64-bit arithmetic: only a unit that starts before the first representable microsecond (the day, week,
+// month, quarter and year holding INT64_MIN) wraps.
+#define HS_US_PER_DAY 86400000000ll
+
+struct HsCivil {
+    int32_t year;    // of the calendar (January-based)
+    uint32_t month;  // 1 .. 12
+    uint32_t day;    // 1 .. 31
+    uint32_t yday;   // 1 .. 366
+};
+
+__device__ __forceinline__ void hs_split_days(int64_t cell, int32_t& days, uint64_t& us_of_day) {
+    int64_t q = cell / HS_US_PER_DAY;
+    int64_t r = cell - q * HS_US_PER_DAY;
+    if (r < 0) {
+        r += HS_US_PER_DAY;
+        --q;
+    }
+    days = (int32_t)q;
+    us_of_day = (uint64_t)r;
+}
+
+__device__ __forceinline__ HsCivil hs_civil_from_days(int32_t days) {
+    const int32_t z = days + 719468;  // days since 0000-03-01
+    const int32_t era = (z >= 0 ? z : z - 146096) / 146097;
+    const uint32_t doe = (uint32_t)(z - era * 146097);                               // [0, 146096]
+    const uint32_t yoe = (doe - doe / 1460u + doe / 36524u - doe / 146096u) / 365u;  // [0, 399]
+    const uint32_t doy = doe - (365u * yoe + yoe / 4u - yoe / 100u);                 // [0, 365], March-based
+    const uint32_t mp = (5u * doy + 2u) / 153u;                                      // [0, 11], March = 0
+    HsCivil c;
+    c.day = doy - (153u * mp + 2u) / 5u + 1u;
+    c.month = mp < 10u ? mp + 3u : mp - 9u;
+    c.year = (int32_t)yoe + era * 400 + (c.month <= 2u ? 1 : 0);
+    // January and February (doy >= 306) lie in front of any leap day of their calendar year; March .. December follow the
+    // one of year-of-era's own calendar year (year-of-era 0 is the multiple of 400)
+    const uint32_t leap = ((yoe & 3u) == 0u && (yoe % 100u != 0u || yoe == 0u)) ? 1u : 0u;
+    c.yday = doy >= 306u ? doy - 305u : doy + 60u + leap;
+    return c;
+}
+
+__device__ __forceinline__ int32_t hs_days_from_civil(int32_t y, uint32_t m, uint32_t d) {
+    y -= m <= 2u ? 1 : 0;
+    const int32_t era = (y >= 0 ? y : y - 399) / 400;
+    const uint32_t yoe = (uint32_t)(y - era * 400);
+    const uint32_t doy = (153u * (m > 2u ? m - 3u : m + 9u) + 2u) / 5u + d - 1u;
+    const uint32_t doe = yoe * 365u + yoe / 4u - yoe / 100u + doy;
+    return era * 146097 + (int32_t)doe - 719468;
+}
+
+// ISO weekday of a day number, Monday = 1 ... Sunday = 7: 1970-01-01 is a Thursday; 106 751 995 = 7 x 15 250 285 keeps the
+// dividend positive over the whole range
+__device__ __forceinline__ uint32_t hs_iso_weekday(int32_t days) { return (uint32_t)(days + 3 + 106751995) % 7u + 1u; }
+
+// `sel` valid (0 .. 8, 16 .. 23).  Force-inlined with a constant selector (generated kernels) only that part's code is left.
+__device__ __forceinline__ uint64_t hs_datepart_cell(uint32_t sel, uint64_t cell) {
+    int32_t days;
+    uint64_t us;
+    hs_split_days((int64_t)cell, days, us);
+    if (sel == HS_DT_DAY) return cell - us;
+    if (sel == HS_DP_DAYOFWEEK) return (uint64_t)hs_iso_weekday(days);
+    if (sel == HS_DT_WEEK) return cell - us - (uint64_t)(hs_iso_weekday(days) - 1u) * (uint64_t)HS_US_PER_DAY;
+    if ((sel >= HS_DP_HOUR && sel <= HS_DP_SECOND) || (sel >= HS_DT_HOUR && sel <= HS_DT_SECOND)) {
+        // us < 2^37 and 1 000 000 = 64 x 15 625: the second of the day is a 32-bit division of us >> 6
+        const uint32_t sod = (uint32_t)(us >> 6) / 15625u;
+        switch (sel) {
+            case HS_DP_HOUR: return (uint64_t)(sod / 3600u);
+            case HS_DP_MINUTE: return (uint64_t)(sod / 60u % 60u);
+            case HS_DP_SECOND: return (uint64_t)(sod % 60u);
+            case HS_DT_HOUR: return cell - (us - (uint64_t)(sod / 3600u * 3600u) * 1000000ull);
+            case HS_DT_MINUTE: return cell - (us - (uint64_t)(sod / 60u * 60u) * 1000000ull);
+            default: return cell - (us - (uint64_t)sod * 1000000ull);
+        }
+    }
+    const HsCivil c = hs_civil_from_days(days);
+    switch (sel) {
+        case HS_DP_YEAR: return (uint64_t)(int64_t)c.year;
+        case HS_DP_QUARTER: return (uint64_t)((c.month + 2u) / 3u);
+        case HS_DP_MONTH: return (uint64_t)c.month;
+        case HS_DP_DAY: return (uint64_t)c.day;
+        case HS_DP_DAYOFYEAR: return (uint64_t)c.yday;
+        case HS_DT_YEAR: return (uint64_t)(int64_t)hs_days_from_civil(c.year, 1u, 1u) * (uint64_t)HS_US_PER_DAY;
+        case HS_DT_QUARTER:
+            return (uint64_t)(int64_t)hs_days_from_civil(c.year, (c.month - 1u) / 3u * 3u + 1u, 1u) * (uint64_t)HS_US_PER_DAY;
+        default: return (uint64_t)(int64_t)hs_days_from_civil(c.year, c.month, 1u) * (uint64_t)HS_US_PER_DAY;
+    }
+}
+
+__device__ __forceinline__ bool hs_datepart_valid(uint32_t sel) { return sel <= HS_DP_DAYOFYEAR || (sel >= HS_DT_YEAR && sel <= HS_DT_SECOND); }
+
+// generated kernels: the selector is a compile-time constant
+template <uint32_t SEL>
+__device__ __forceinline__ uint64_t hs_datepart_c(uint64_t cell) {
+    static_assert(SEL <= HS_DP_DAYOFYEAR || (SEL >= HS_DT_YEAR && SEL <= HS_DT_SECOND), "HS_OP_DATEPART selector");
+    return hs_datepart_cell(SEL, cell);
+}
+
+// interpreters: the selector is wave-uniform run-time data; an invalid one is a bad program (the cell is left alone)
+__device__ __forceinline__ uint64_t hs_datepart(uint32_t sel, uint64_t cell, uint32_t& err) {
+    if (!hs_datepart_valid(sel)) {
+        err |= HS_FLAG_BAD_PROGRAM;
+        return cell;
+    }
+    return hs_datepart_cell(sel, cell);
+}
+
 // ---- binary operators: ONE definition shared by the interpreter and by JIT-generated code -------------------
 // x = second-from-top cell, y = top cell; `live` gates data-dependent error reporting (rows that failed
 // the WHERE clause are never evaluated by the reference and must not raise).
@@ -385,6 +496,14 @@ __device__ __forceinline__ void hs_exec_at(uint64_t w, const hs_program& P, cons
                 for (int j = 0; j < V; ++j) st[SP - 3][j] = st[SP - 3][j] != 0 ? st[S][j] : st[T][j];
             }
             break;
+        case HS_OP_DATEPART:  // t -> part(t), a = selector: total over i64, no error but a bad selector, no `live`
+            if constexpr (SP >= 1) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) st[T][j] = hs_datepart(a, st[T][j], err);
+            } else {
+                err |= HS_FLAG_BAD_PROGRAM;
+            }
+            break;
         case HS_OP_STRCMP_LIT:
             if constexpr (SP < D) {
 #pragma unroll
@@ -508,6 +627,10 @@ __device__ __forceinline__ void hs_run_compact(const hs_program& P, const HsCols
                 break;
             case HS_OP_SEL:
                 if (sp >= 3) st(sp - 3) = st(sp - 3) != 0 ? x : y;
+                else err |= HS_FLAG_BAD_PROGRAM;
+                break;
+            case HS_OP_DATEPART:
+                if (sp >= 1) st(t) = hs_datepart(a, y, err);
                 else err |= HS_FLAG_BAD_PROGRAM;
                 break;
             case HS_OP_STRCMP_LIT: st(nx) = live ? hs_strcmp_lit(P, C.c[a], sink.row(0), hs_ins_b(w), hs_ins_c(w)) : 0; break;

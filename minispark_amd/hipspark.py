@@ -56,7 +56,12 @@ OP_LT_F, OP_LE_F, OP_GT_F, OP_GE_F, OP_EQ_F, OP_NE_F = 14, 15, 16, 17, 18, 19
 OP_LT_I, OP_LE_I, OP_GT_I, OP_GE_I, OP_EQ_I, OP_NE_I = 20, 21, 22, 23, 24, 25
 OP_AND, OP_OR, OP_I2F = 26, 27, 28
 OP_STRCMP_LIT, OP_STRCMP_COL, OP_LIKE = 29, 30, 31
-OP_FILTER, OP_AGG, OP_OUT, OP_KEY, OP_DICTBIT, OP_SEL = 32, 33, 34, 35, 36, 37
+OP_FILTER, OP_AGG, OP_OUT, OP_KEY, OP_DICTBIT, OP_SEL, OP_DATEPART = 32, 33, 34, 35, 36, 37, 38
+
+# selectors of OP_DATEPART (enum hs_datepart): the parts are INTEGER-valued, the truncation units TIMESTAMP-valued
+DATE_PARTS = ("year", "quarter", "month", "day", "hour", "minute", "second", "dayofweek", "dayofyear")  # selector = index
+DATE_TRUNC_UNITS = ("year", "quarter", "month", "week", "day", "hour", "minute", "second")            # selector = 16 + index
+DATE_TRUNC_BASE = 16
 
 
 class HipSparkError(RuntimeError):

@@ -12,7 +12,7 @@ Typing of in-flight values (reference: rows hold Python objects, sql.py:262-266)
  ``I``  int (unbounded)             i64
  ``F``  float (fp64)                f64
  ``B``  bool                        i64 0/1
- ``T``  datetime                    i64 microseconds (compare only)
+ ``T``  datetime                    i64 microseconds (compare, date functions)
  ``S``  str                         not a cell: string ops read the column bytes
 ====== =========================== ==========================================
 """
@@ -66,6 +66,10 @@ def expr_key(node: Any) -> tuple:
         return (node.operator.__name__, expr_key(node.left_side), expr_key(node.right_side))
     if name == "CaseColumn":
         return ("case", expr_key(node.condition), expr_key(node.then_col), expr_key(node.else_col))
+    if name == "DatePartColumn":
+        return ("datepart", node.part, expr_key(node.original_col))
+    if name == "DateTruncColumn":
+        return ("datetrunc", node.unit, expr_key(node.original_col))
     raise LoweringError(f"unsupported expression node {name}")
 
 
@@ -243,6 +247,8 @@ class ProgramBuilder:
             return self._lower_binary(node)
         if name == "CaseColumn":
             return self._lower_case(node)
+        if name in ("DatePartColumn", "DateTruncColumn"):
+            return self._lower_date_function(node)
         raise LoweringError(f"unsupported expression node {name}")
 
     def value_tag(self, node: Any) -> str:
@@ -273,6 +279,10 @@ class ProgramBuilder:
             return "S" if "S" in tags else "F" if "F" in tags else "I"
         if name == "CaseColumn":
             return "F" if "F" in (self.value_tag(node.then_col), self.value_tag(node.else_col)) else "I"
+        if name == "DatePartColumn":
+            return "I"
+        if name == "DateTruncColumn":
+            return "T"
         raise LoweringError(f"unsupported expression node {name}")
 
     def _lower_case(self, node: Any) -> str:
@@ -300,6 +310,21 @@ class ProgramBuilder:
                 self._to_float(tag, second=False)
         self._emit(hs.OP_SEL, push=-2)
         return result
+
+    def _lower_date_function(self, node: Any) -> str:
+        """The TIMESTAMP operand, then HS_OP_DATEPART with the part's or the unit's selector: one cell in, one cell out.
+        The operand is checked first: anything but a TIMESTAMP value - a bare string literal too, which has no neighbour
+        to take a type from - is a TypeError naming the expression, raised before anything is emitted."""
+        if self.value_tag(node.original_col) != "T":
+            what = {"I": "INTEGER", "F": "FLOAT", "B": "boolean", "S": "STRING"}[self.value_tag(node.original_col)]
+            raise TypeError(f"{node}: the argument of a date function is a TIMESTAMP value, not {what}")
+        if self.lower(node.original_col) != "T":
+            raise AssertionError(f"value_tag gives T where lower does not: {node.original_col}")
+        if _cls(node) == "DatePartColumn":
+            self._emit(hs.OP_DATEPART, a=hs.DATE_PARTS.index(node.part))
+            return "I"
+        self._emit(hs.OP_DATEPART, a=hs.DATE_TRUNC_BASE + hs.DATE_TRUNC_UNITS.index(node.unit))
+        return "T"
 
     def _lower_literal(self, value: Any) -> str:
         if type(value) is bool:
@@ -428,6 +453,8 @@ class ProgramBuilder:
                     return ctype == ColumnType.TIMESTAMP
         if _cls(node) == "Lit":
             return type(node.value) is datetime
+        if _cls(node) == "DateTruncColumn":
+            return True
         return False
 
     def _lower_operand(self, node: Any, other: Any) -> str:

@@ -10,7 +10,12 @@ A hand-written backtracking recursive-descent parser for the same language:
 * select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e) [AS name]``, ``expr [AS name]``;
 * conditions: OR < AND < NOT < comparison | ( cond ) | BETWEEN | LIKE, comparators = != <= >= < >;
 * expressions: + - over * / over atoms (number, column, string literal, ( expr ), COUNT()/SUM(e),
-  ``CASE WHEN cond THEN expr {WHEN cond THEN expr} ELSE expr END``);
+  ``CASE WHEN cond THEN expr {WHEN cond THEN expr} ELSE expr END``, the date functions ``YEAR(e)`` ``QUARTER(e)``
+  ``MONTH(e)`` ``DAY(e)`` ``HOUR(e)`` ``MINUTE(e)`` ``SECOND(e)`` ``DAYOFWEEK(e)`` ``DAYOFYEAR(e)`` and
+  ``DATE_TRUNC('unit', e)`` over a TIMESTAMP value; any other function name is a ``SemanticError``);
+* a name in GROUP BY that is the alias of a select item made of one date-function call groups by that item
+  (``SELECT YEAR(d) AS y, SUM(x) AS s FROM 't' GROUP BY y;``): the parser projects the item under its alias, next to the
+  other keys and the plain columns the aggregates read, and groups by the projected column;
 * a select list of aggregate calls only and no GROUP BY aggregates the whole table (``DataFrame.agg``): one row, or none
   when no row survives the WHERE; mixing aggregates and plain columns without GROUP BY raises ``GroupByError``, HAVING
   without GROUP BY stays a syntax error, arithmetic over aggregates (``SUM(a) / SUM(b)``) is not part of this form;
@@ -43,7 +48,7 @@ import re
 from typing import Any, Callable
 
 from .dataframe import DataFrame
-from .sql import AggCol, CaseColumn, Col, Lit, SortKey
+from .sql import DATE_PARTS, AggCol, AliasColumn, CaseColumn, Col, DatePartColumn, DateTruncColumn, Lit, SortKey
 from .sql import Functions as F
 
 
@@ -186,6 +191,7 @@ class _Parser:
                 for c in extra:
                     c.name = f"_having_{c.name}"
                 agg_cols.extend(extra)
+            df = self.project_date_keys(df, select_list, group_cols, agg_cols)
             df = df.group_by(*group_cols).agg(*agg_cols)
             if having is not None:
                 df = df.filter(having.normalize_agg_columns())
@@ -211,6 +217,27 @@ class _Parser:
         if has_limit:
             df = df.limit(limit)
         return df
+
+    @staticmethod
+    def project_date_keys(df: DataFrame, select_list: list[Col], group_cols: list[Col], agg_cols: list[AggCol]) -> DataFrame:
+        """GROUP BY on the alias of a select item that is a date-function call (``SELECT YEAR(d) AS y, ... GROUP BY y``): the
+        DataFrame idiom for a computed key - a projection of that item under its alias, the other keys and every plain
+        column the aggregates (HAVING's among them) read, in front of the group_by.  Limited to date-function items: for any
+        other aliased item the text parsed before these functions existed and keeps its tree."""
+        items = {c.name: c for c in select_list
+                 if type(c) is AliasColumn and type(c.original_col) in (DatePartColumn, DateTruncColumn)}
+        if not any(g.name in items for g in group_cols):
+            return df
+        columns: list[Col] = [items.get(g.name, g) for g in group_cols]
+        names = [c.name for c in columns]
+        for agg in agg_cols:
+            for c in agg.all_nested_columns:
+                if type(c) is Col and c.name in items:
+                    raise ValueError(f'"{c.name}" names a date function of the select list and is read by {agg} as a column')
+                if type(c) is Col and c.name not in names:
+                    names.append(c.name)
+                    columns.append(Col(c.name))
+        return df.select(*columns)
 
     def select_list(self) -> list[Col]:
         items = [self.select_item()]
@@ -473,6 +500,14 @@ class _Parser:
             if len(args) != 1:
                 raise AssertionError("SUM takes one argument")
             return F.sum(_as_col(args[0]))
+        if name.lower() in DATE_PARTS and name.isupper():
+            if len(args) != 1:
+                raise AssertionError(f"{name} takes one argument")
+            return DatePartColumn(name.lower(), _as_col(args[0]))
+        if name == "DATE_TRUNC":
+            if len(args) != 2:
+                raise AssertionError("DATE_TRUNC takes a unit and one argument")
+            return DateTruncColumn(args[0], _as_col(args[1]))  # the unit: a string literal, else ValueError
         raise SemanticError(f"Unsupported function: {name}")
 
     def parenthised_expr(self) -> Any:

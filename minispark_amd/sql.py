@@ -356,6 +356,91 @@ class CaseColumn(Col):
     __repr__ = __str__
 
 
+DATE_PARTS = ("year", "quarter", "month", "day", "hour", "minute", "second", "dayofweek", "dayofyear")
+DATE_TRUNC_UNITS = ("year", "quarter", "month", "week", "day", "hour", "minute", "second")
+
+
+class _DateFunctionColumn(Col):
+    """What the two date functions share (no reference counterpart: DESIGN.md 4.4d): one TIMESTAMP-valued argument - a
+    TIMESTAMP column, a ``datetime`` literal or a DATE_TRUNC - read in the proleptic Gregorian calendar without a time
+    zone.  The functions are total: they raise on no value of the column."""
+
+    _WORDS: tuple[str, ...] = ()
+    _KIND = ""
+
+    def __init__(self, word: str, col: Any) -> None:
+        if not isinstance(word, str) or word.lower() not in self._WORDS:
+            raise ValueError(f"{self._KIND} {word!r}: one of {', '.join(self._WORDS)}")
+        self.original_col = _wrap(col)
+        self._word = word.lower()
+        super().__init__(f"{self._prefix()}_{self.original_col.name}")
+
+    def _prefix(self) -> str:
+        raise NotImplementedError
+
+    def __hash__(self) -> int:
+        return hash((type(self).__name__, self._word, hash(self.original_col)))
+
+    @property
+    def children(self) -> tuple[Col, ...]:
+        return (self.original_col,)
+
+    def _check_argument(self, schema: Schema) -> None:
+        arg_type = self.original_col.infer_type(schema)
+        if arg_type != ColumnType.TIMESTAMP:
+            raise TypeError(f"{self}: the argument of a date function is a TIMESTAMP value, not {arg_type.name}")
+
+    def normalize_agg_columns(self) -> Col:
+        return type(self)(self._word, self.original_col.normalize_agg_columns())
+
+
+class DatePartColumn(_DateFunctionColumn):
+    """``YEAR(ts)`` ... ``DAYOFYEAR(ts)``: an INTEGER.  QUARTER 1-4, MONTH 1-12, DAY 1-31, HOUR 0-23, MINUTE and SECOND
+    0-59 (whole seconds), DAYOFWEEK in ISO numbering (Monday 1 ... Sunday 7), DAYOFYEAR 1-366; division is floor division,
+    so the microsecond before 1970 has year 1969, day 31, hour 23."""
+
+    _WORDS, _KIND = DATE_PARTS, "date part"
+
+    def __init__(self, part: str, col: Any) -> None:
+        super().__init__(part, col)
+        self.part = self._word
+
+    def _prefix(self) -> str:
+        return self._word
+
+    def infer_type(self, schema: Schema) -> ColumnType:
+        self._check_argument(schema)
+        return ColumnType.INTEGER
+
+    def __str__(self) -> str:
+        return f"{self.part.upper()}({self.original_col})"
+
+    __repr__ = __str__
+
+
+class DateTruncColumn(_DateFunctionColumn):
+    """``DATE_TRUNC('unit', ts)``: the first microsecond of the unit that holds ``ts``, a TIMESTAMP; a week starts on
+    Monday."""
+
+    _WORDS, _KIND = DATE_TRUNC_UNITS, "DATE_TRUNC unit"
+
+    def __init__(self, unit: str, col: Any) -> None:
+        super().__init__(unit, col)
+        self.unit = self._word
+
+    def _prefix(self) -> str:
+        return f"date_trunc_{self._word}"
+
+    def infer_type(self, schema: Schema) -> ColumnType:
+        self._check_argument(schema)
+        return ColumnType.TIMESTAMP
+
+    def __str__(self) -> str:
+        return f"DATE_TRUNC('{self.unit}', {self.original_col})"
+
+    __repr__ = __str__
+
+
 class KeyTupleCol(Col):
     """The key of a GROUP BY over several columns (no reference counterpart: DESIGN.md 4.4c): ``parts`` are plain columns
     of the aggregate's input, in the order given.  Between the partial aggregate and the final merge the tuple travels as
@@ -396,7 +481,7 @@ class KeyTupleCol(Col):
 
 # instance fields of the column classes that code reads without calling anything
 _COL_FIELDS = frozenset({"name", "original_col", "left_side", "right_side", "operator", "value", "pattern", "type",
-                         "condition", "then_col", "else_col"})
+                         "condition", "then_col", "else_col", "part", "unit"})
 
 
 class CaseBuilder:
@@ -499,3 +584,44 @@ class Functions:
     def when(condition: Any, value: Any) -> CaseBuilder:
         """``when(c, x).otherwise(y)`` = CASE WHEN c THEN x ELSE y END; further ``.when`` arms nest to the right."""
         return CaseBuilder([(condition, value)])
+
+    # date parts of a TIMESTAMP value (DatePartColumn) and DATE_TRUNC (DateTruncColumn): DESIGN.md 4.4d
+    @staticmethod
+    def year(col: Any) -> DatePartColumn:
+        return DatePartColumn("year", col)
+
+    @staticmethod
+    def quarter(col: Any) -> DatePartColumn:
+        return DatePartColumn("quarter", col)
+
+    @staticmethod
+    def month(col: Any) -> DatePartColumn:
+        return DatePartColumn("month", col)
+
+    @staticmethod
+    def day(col: Any) -> DatePartColumn:
+        return DatePartColumn("day", col)
+
+    @staticmethod
+    def hour(col: Any) -> DatePartColumn:
+        return DatePartColumn("hour", col)
+
+    @staticmethod
+    def minute(col: Any) -> DatePartColumn:
+        return DatePartColumn("minute", col)
+
+    @staticmethod
+    def second(col: Any) -> DatePartColumn:
+        return DatePartColumn("second", col)
+
+    @staticmethod
+    def dayofweek(col: Any) -> DatePartColumn:
+        return DatePartColumn("dayofweek", col)
+
+    @staticmethod
+    def dayofyear(col: Any) -> DatePartColumn:
+        return DatePartColumn("dayofyear", col)
+
+    @staticmethod
+    def date_trunc(unit: str, col: Any) -> DateTruncColumn:
+        return DateTruncColumn(unit, col)

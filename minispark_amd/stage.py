@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+from datetime import datetime
 from pathlib import Path
 from typing import Any
 
@@ -62,7 +63,15 @@ def _substitute(node: Any, defs: dict[str, Any] | None) -> Any:
         return type(node)(_substitute(node.left_side, defs), _substitute(node.right_side, defs), node.operator)
     if name == "CaseColumn":
         return type(node)(_substitute(node.condition, defs), _substitute(node.then_col, defs), _substitute(node.else_col, defs))
+    if name == "DatePartColumn":
+        return type(node)(node.part, _substitute(node.original_col, defs))
+    if name == "DateTruncColumn":
+        return type(node)(node.unit, _substitute(node.original_col, defs))
     raise StageUnsupported(f"{name} over a projected column")
+
+
+_DATE_PART_BITS = {"year": 19, "quarter": 3, "month": 4, "day": 5, "hour": 5, "minute": 6, "second": 6, "dayofweek": 3,
+                   "dayofyear": 9}
 
 
 def _int_bits(node: Any, schema: Schema) -> int | None:
@@ -77,6 +86,18 @@ def _int_bits(node: Any, schema: Schema) -> int | None:
         return 31 if types.get(node.name) == ColumnType.INTEGER else None
     if name == "Lit":
         return node.value.bit_length() if type(node.value) is int else None
+    if name == "DatePartColumn":
+        # total over i64 (no flag, no exception), so only the argument's type is asked for: a TIMESTAMP column, a datetime
+        # literal or a DATE_TRUNC of one.  |year| <= 292 278 < 2**19; the other parts are bounded by their calendar
+        arg = unalias(node.original_col)
+        while _cls(arg) == "DateTruncColumn":
+            arg = unalias(arg.original_col)
+        if _cls(arg) in ("Col", "SchemaCol"):
+            if dict(schema).get(arg.name) != ColumnType.TIMESTAMP:
+                return None
+        elif _cls(arg) != "Lit" or type(arg.value) is not datetime:
+            return None
+        return _DATE_PART_BITS[node.part]
     if name != "BinaryOperatorColumn":
         return None
     op = node.operator.__name__
@@ -439,6 +460,8 @@ def _walk_names(node: Any) -> list[str]:
         return _walk_names(node.left_side) + _walk_names(node.right_side)
     if name == "CaseColumn":
         return _walk_names(node.condition) + _walk_names(node.then_col) + _walk_names(node.else_col)
+    if name in ("DatePartColumn", "DateTruncColumn"):
+        return _walk_names(node.original_col)
     raise StageUnsupported(f"{name} in a join predicate")
 
 
