@@ -595,6 +595,26 @@ int hs_order_by(void* stream, const hs_col* keys, const int32_t* descending, int
 size_t hs_distinct_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words);
 int hs_distinct(void* stream, const hs_col* keys, int32_t n_keys, int64_t nrows, const int64_t* nrows_dev,
                 int64_t* out_perm, int64_t* out_count /* HOST */, void* ws, uint32_t* flags);
+/* First-occurrence marks over input rows (no reference counterpart: the reference has no COUNT(DISTINCT)).  marks[r], one
+ * HS_I32 cell per input row r in [0, nrows): 1 iff r is a CONSIDERED row and no considered row r' < r has the same key
+ * words, else 0 - every row outside the considered ones too.  Considered: the rows sel[0 .. n_sel) (device int64,
+ * ascending, each below nrows), or all rows when sel is null.  Equality is hs_distinct's over keys[0 .. n_keys): integers
+ * by value, -0.0 = +0.0, every NaN one value, strings by bytes and length, a dictionary-coded column by its code byte.
+ * The marks are a function of the rows alone, so SUM(marks) GROUP BY k over the keys (k, e) is COUNT(DISTINCT e) GROUP BY k,
+ * reproducibly; HS_I32 is the kind the partial aggregate reads as a SUM argument as it stands.
+ * mode 1, the sort path (any key): hs_order_by's stable sort of the considered rows, then hs_distinct's pass over the runs
+ * of equal rows writes the heads into the zeroed marks.  mode 2, the dense path: a key of ONE 64-bit word whose varying
+ * bits V (AND ^ OR over the considered rows) number at most 24 in at most 8 contiguous runs and nrows < 2^32 - 1 - the V
+ * bits, squeezed together, index a table of row numbers, an integer atomicMin per row claims the slot for the smallest
+ * row and a second pass compares; any other key: HS_E_LIMIT.  mode 0: the dense path where it applies, else the sort path;
+ * all three write the same marks.  1 <= n_keys <= HS_MAX_COLS (HS_E_LIMIT above); bad arguments, kinds that cannot be
+ * compared and the key count are refused before anything is launched.  Like hs_order_by the call reads words back between
+ * its steps: it synchronises the stream and must not be captured (hs_capture_begin).
+ * ws: hs_mark_first_ws_bytes(nrows, n_keys, max_key_words) bytes (the sort's workspace + the dense table at its largest,
+ * 64 MB).  flags: as for hs_order_by; no bit is raised at present (may be null). */
+size_t hs_mark_first_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words);
+int hs_mark_first(void* stream, const hs_col* keys, int32_t n_keys, int64_t nrows, const int64_t* sel /* null: all rows */,
+                  int64_t n_sel, int32_t mode, int32_t* marks, void* ws, uint32_t* flags);
 /* out[i] = values[s] for bounds[s] <= i < bounds[s+1], i in [0, n) (device arrays; bounds has n_seg + 1 entries,
  * bounds[0] = 0): the global block id of every partial row of a multi-rank partial aggregate. */
 int hs_expand_by_bounds(void* stream, const int64_t* bounds, const int64_t* values, int64_t n_seg, int64_t n, int64_t* out);

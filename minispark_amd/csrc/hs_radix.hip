@@ -1974,12 +1974,23 @@ struct ObSorted {
     const int64_t* rows;  // the answer's rows in order (in the workspace); null: the rows in place (the keys have no byte)
     size_t ws_bytes;      // bytes of the workspace the sort laid out: what follows them is the caller's
     const uint64_t* words;  // word 0 of the answer's rows, in their order (null with `rows`)
+    uint64_t varying;     // `unsorted`: the bits of the first word formed that differ between rows
+    int32_t unsorted;     // `dense` ended the sort before any pass moved a row: `rows` / `words` stand in input order
 };
 
-// The sort of hs_order_by, shared with hs_distinct: checked arguments in, *out_count (HOST) and `S` out.  nrows > 0,
-// limit != 0, 0 <= n_keys <= HS_MAX_COLS, every key ob_kind_ok.  `name`: the calling entry point, for the error texts.
+// hs_mark_first's dense path holds a key of ONE word whose varying bits are few (defined with its kernels, below)
+static bool mf_dense_fits(int32_t n_words, uint64_t varying);
+enum { OB_SORT = 0, OB_DENSE_IF_FITS = 1, OB_DENSE_ONLY = 2 };  // ob_sort's `dense`
+
+// The sort of hs_order_by, shared with hs_distinct and hs_mark_first: checked arguments in, *out_count (HOST) and `S`
+// out.  nrows > 0, limit != 0, 0 <= n_keys <= HS_MAX_COLS, every key ob_kind_ok.  `name`: the calling entry point, for
+// the error texts.  `in_rows` (device, n_in of them, each below nrows; limit < 0 and no nrows_dev with it): only these
+// rows are sorted, in the order they are listed - the list the LIMIT path hands sort_rows, given by the caller.
+// `dense` (hs_mark_first alone): OB_DENSE_IF_FITS returns after the first word is formed, before any pass, when the key
+// fits the dense path (S.unsorted); OB_DENSE_ONLY returns there whatever the key, and the caller refuses what does not fit.
 static int ob_sort(hipStream_t stream, const hs_col* keys, const int32_t* descending, int32_t n_keys, int64_t nrows,
-                   const int64_t* nrows_dev, int64_t limit, int64_t* out_count, void* ws_, const char* name, ObSorted& S) {
+                   const int64_t* nrows_dev, int64_t limit, int64_t* out_count, void* ws_, const char* name, ObSorted& S,
+                   const int64_t* in_rows = nullptr, int64_t n_in = 0, int dense = OB_SORT) {
     std::memset(&S, 0, sizeof(S));
     uint8_t* ws = (uint8_t*)ws_;
     const int64_t tiles_max = nrows / RX_TILE + 2;
@@ -2018,6 +2029,8 @@ static int ob_sort(hipStream_t stream, const hs_col* keys, const int32_t* descen
         }
         n = exact < n ? (exact < 0 ? 0 : exact) : n;
     }
+    const int64_t cells = n;  // rows of the columns: a variable-length key's longest string is looked for among all of them
+    if (in_rows) n = n_in;
     const int64_t count = limit < 0 || limit > n ? n : limit;
     *out_count = count;
     S.n = n;
@@ -2033,7 +2046,7 @@ static int ob_sort(hipStream_t stream, const hs_col* keys, const int32_t* descen
         A.desc[k] = descending[k] ? 1 : 0;
         if (c.kind == HS_STR && c.fixed_len < 0) {
             hs_memset_async(state + 5, 0, 8, stream);
-            hipLaunchKernelGGL(k_ob_maxlen, dim3(ob_grid(n)), dim3(OB_THREADS), 0, stream, c.lens, n, (uint32_t*)(state + 5));
+            hipLaunchKernelGGL(k_ob_maxlen, dim3(ob_grid(cells)), dim3(OB_THREADS), 0, stream, c.lens, cells, (uint32_t*)(state + 5));
             OB_CHECK_LAUNCH("longest string");
             uint32_t longest = 0;
             if (!read_back(&longest, state + 5, 4)) {
@@ -2101,6 +2114,11 @@ static int ob_sort(hipStream_t stream, const hs_col* keys, const int32_t* descen
             uint64_t and_bits = 0, varying = 0;
             int rc = form(w, first ? rows : R[cur], m, K[cur], first ? R[cur] : nullptr, and_bits, varying);
             if (rc != HS_OK) return rc;
+            if (first && (dense == OB_DENSE_ONLY || (dense == OB_DENSE_IF_FITS && mf_dense_fits(n_words, varying)))) {
+                S.unsorted = 1;
+                S.varying = varying;
+                break;
+            }
             for (int b = 0; b < 8; ++b) {
                 if (((varying >> (8 * b)) & 0xffull) == 0) continue;  // one occupied bin: the pass would move nothing
                 P.src[0] = K[cur];
@@ -2120,7 +2138,7 @@ static int ob_sort(hipStream_t stream, const hs_col* keys, const int32_t* descen
 
     const int64_t* sorted = nullptr;
     if (count == n) {
-        const int rc = sort_rows(nullptr, n, sorted);
+        const int rc = sort_rows(in_rows, n, sorted);
         if (rc != HS_OK) return rc;
     } else {
         // the count-th smallest first word, then the rows at or below it
@@ -2224,6 +2242,7 @@ struct DhArgs {
                           // formed again (null: the words are formed from the columns)
     int64_t n;
     uint8_t* keep;        // [n], input order
+    int32_t* mark;        // hs_mark_first: INTEGER cells, input order, instead of `keep` (rows outside perm are not written)
 };
 static_assert(sizeof(DhArgs) % 8 == 0, "DhArgs");
 
@@ -2263,7 +2282,11 @@ __global__ void __launch_bounds__(OB_THREADS) k_distinct_heads(const DhArgs A_ke
             differs |= mine != left;
             if (__ballot(!differs) == 0) break;       // every lane of the step has found its difference
         }
-        if (live) A.keep[row] = (i == 0 || differs) ? 1 : 0;
+        if (live) {
+            const int head = (i == 0 || differs) ? 1 : 0;
+            if (A.mark) A.mark[row] = head;
+            else A.keep[row] = (uint8_t)head;
+        }
     }
 }
 
@@ -2330,6 +2353,161 @@ extern "C" int hs_distinct(void* stream_, const hs_col* keys, int32_t n_keys, in
         return HS_E_LAUNCH;
     }
     *out_count = kept;
+    return HS_OK;
+}
+
+// =====================================================================================================
+// First-occurrence marks (include/hipspark.h hs_mark_first; the reference has no COUNT(DISTINCT)).
+//
+// marks[r] = 1 iff r is a considered row and no considered row before it has the same key words - hs_distinct's equality,
+// hs_distinct's heads, written as an INTEGER column the partial aggregate SUMs: COUNT(DISTINCT e) GROUP BY k is the SUM of
+// the marks over the keys (k, e).  Two ways to the same function of the rows:
+//  * sort path: ob_sort over the considered rows (their list, or all), then k_distinct_heads into the zeroed marks.
+//  * dense path, a key of ONE word whose varying bits V = AND ^ OR are few: the V bits of a word, squeezed together, index
+//    a table first_row[1 << popcount(V)] of row numbers; k_mf_claim takes the minimum per slot (integer atomicMin: the
+//    minimum does not depend on the order the atomics land in), k_mf_mark compares.  Rows are read once per kernel, marks
+//    are written in input order, nothing is moved.
+// =====================================================================================================
+constexpr int MF_DENSE_BITS = 24;  // the table: 64 MB at most (profiles/r14_count_distinct.txt)
+constexpr int MF_MAX_RUNS = 8;     // contiguous runs of V
+
+struct MfArgs {
+    const uint64_t* words;  // the key word of considered row i
+    const int64_t* rows;    // its row number (null: i)
+    int64_t n;
+    uint32_t* first_row;    // [1 << popcount(V)]
+    int32_t* marks;
+    uint64_t run_mask[MF_MAX_RUNS];  // (1 << bits of the run) - 1
+    int32_t run_shift[MF_MAX_RUNS];  // the run's lowest bit in the word
+    int32_t run_at[MF_MAX_RUNS];     // ... and in the slot
+    int32_t n_runs, pad;
+};
+static_assert(sizeof(MfArgs) % 8 == 0, "MfArgs");
+
+__device__ __forceinline__ uint32_t mf_slot(const MfArgs& A, uint64_t word) {
+    uint64_t slot = 0;
+    for (int r = 0; r < A.n_runs; ++r) slot |= ((word >> A.run_shift[r]) & A.run_mask[r]) << A.run_at[r];
+    return (uint32_t)slot;
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_mf_claim(const MfArgs A_kernarg) {
+    HS_KERNARG(MfArgs, A);
+    for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * OB_THREADS) {
+        const uint32_t row = (uint32_t)(A.rows ? A.rows[i] : i);
+        uint32_t* cell = A.first_row + mf_slot(A, A.words[i]);
+        // a value read here is one some row wrote or the fill: never below the final minimum, so skipping is safe, and
+        // with rows visited in rising order most values of a small domain skip the atomic
+        if (*(volatile uint32_t*)cell > row) atomicMin(cell, row);
+    }
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_mf_mark(const MfArgs A_kernarg) {
+    HS_KERNARG(MfArgs, A);
+    for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * OB_THREADS) {
+        const int64_t row = A.rows ? A.rows[i] : i;
+        A.marks[row] = A.first_row[mf_slot(A, A.words[i])] == (uint32_t)row ? 1 : 0;
+    }
+}
+
+// the runs of `varying`, lowest first -> their number, or -1 when the dense path does not hold the word
+static int mf_runs(uint64_t varying, MfArgs* A) {
+    if (__builtin_popcountll(varying) > MF_DENSE_BITS) return -1;
+    int n_runs = 0, at = 0;
+    while (varying) {
+        const int lo = __builtin_ctzll(varying);
+        const int len = __builtin_ctzll(~(varying >> lo));  // at most MF_DENSE_BITS: the shifted word has a zero bit
+        if (n_runs == MF_MAX_RUNS) return -1;
+        if (A) {
+            A->run_mask[n_runs] = (1ull << len) - 1ull;
+            A->run_shift[n_runs] = lo;
+            A->run_at[n_runs] = at;
+        }
+        ++n_runs;
+        at += len;
+        varying &= ~(((1ull << len) - 1ull) << lo);
+    }
+    return n_runs;
+}
+static bool mf_dense_fits(int32_t n_words, uint64_t varying) { return n_words == 1 && mf_runs(varying, nullptr) >= 0; }
+
+extern "C" size_t hs_mark_first_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words) {
+    if (nrows < 0) return 0;
+    // the sort's workspace, then the dense path's table at its largest
+    return hs_order_by_ws_bytes(nrows, n_keys, max_key_words) + rx_align((size_t)4 << MF_DENSE_BITS);
+}
+
+extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, int64_t nrows, const int64_t* sel,
+                             int64_t n_sel, int32_t mode, int32_t* marks, void* ws_, uint32_t* flags) {
+    (void)flags;
+    if (n_keys <= 0 || nrows < 0 || !keys || !marks || !ws_ || mode < 0 || mode > 2 || (sel && (n_sel < 0 || n_sel > nrows))) {
+        hs_set_error("hs_mark_first: bad arguments");
+        return HS_E_ARG;
+    }
+    if (n_keys > HS_MAX_COLS) {
+        hs_set_error("hs_mark_first: more than %d columns", HS_MAX_COLS);
+        return HS_E_LIMIT;
+    }
+    if (nrows == 0) return HS_OK;
+    for (int k = 0; k < n_keys; ++k)
+        if (!ob_kind_ok(keys[k])) {
+            hs_set_error("hs_mark_first: column %d is not a column that can be compared", k);
+            return HS_E_ARG;
+        }
+    const bool rows_fit = nrows < 0xffffffffll;  // a row number and the table's fill must differ
+    if (mode == 2 && !rows_fit) {
+        hs_set_error("hs_mark_first: the dense path holds row numbers below 2^32 - 1, not %lld rows", (long long)nrows);
+        return HS_E_LIMIT;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    if (sel && hipMemsetAsync(marks, 0, (size_t)nrows * 4, stream) != hipSuccess) {  // without a list every row is written
+        hs_set_error("hs_mark_first: clearing the marks failed");
+        return HS_E_LAUNCH;
+    }
+    if (sel && n_sel == 0) return HS_OK;
+    const int32_t ascending[HS_MAX_COLS] = {0};
+    ObSorted S;
+    int64_t considered = 0;
+    const int dense = mode == 2 ? OB_DENSE_ONLY : (mode == 0 && rows_fit) ? OB_DENSE_IF_FITS : OB_SORT;
+    const int rc = ob_sort(stream, keys, ascending, n_keys, nrows, nullptr, -1, &considered, ws_, "hs_mark_first", S, sel,
+                           sel ? n_sel : 0, dense);
+    if (rc != HS_OK || S.count == 0) return rc;
+    if (S.unsorted) {
+        MfArgs M;
+        std::memset(&M, 0, sizeof(M));
+        M.n_runs = S.n_words == 1 ? mf_runs(S.varying, &M) : -1;
+        if (M.n_runs < 0) {  // mode 2 only: in mode 0 the sort went on unless the key fits
+            hs_set_error("hs_mark_first: the dense path takes a key of one word whose varying bits are at most %d in at most "
+                         "%d runs (this key: %d words, varying bits %016llx)", MF_DENSE_BITS, MF_MAX_RUNS, S.n_words,
+                         (unsigned long long)S.varying);
+            return HS_E_LIMIT;
+        }
+        M.words = S.words;
+        M.rows = sel ? S.rows : nullptr;  // without a list the sort's row list is 0, 1, 2 ...: not read
+        M.n = S.n;
+        M.first_row = (uint32_t*)((uint8_t*)ws_ + S.ws_bytes);
+        M.marks = marks;
+        const size_t table_bytes = (size_t)4 << __builtin_popcountll(S.varying);
+        if (hipMemsetAsync(M.first_row, 0xff, table_bytes, stream) != hipSuccess) {
+            hs_set_error("hs_mark_first: filling the table failed");
+            return HS_E_LAUNCH;
+        }
+        hipLaunchKernelGGL(k_mf_claim, dim3(ob_grid(M.n)), dim3(OB_THREADS), 0, stream, M);
+        hipLaunchKernelGGL(k_mf_mark, dim3(ob_grid(M.n)), dim3(OB_THREADS), 0, stream, M);
+        RX_CHECK_LAUNCH("hs_mark_first (dense)");
+        return HS_OK;
+    }
+    DhArgs D;
+    std::memset(&D, 0, sizeof(D));
+    D.K = S.keys;
+    D.n_keys = n_keys;
+    D.n_words = S.n_words;
+    D.perm = S.n_words ? S.rows : sel;  // a key without a byte: every considered row is equal, the first of them the head
+    D.n = S.n;
+    if (S.n_words == 1 && S.rows) D.words = S.words;
+    D.mark = marks;
+    const int64_t tiles = (D.n + OB_TILE - 1) / OB_TILE;
+    hipLaunchKernelGGL(k_distinct_heads, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, D);
+    RX_CHECK_LAUNCH("hs_mark_first (heads)");
     return HS_OK;
 }
 

@@ -1634,6 +1634,33 @@ class Device:
             raise DeviceError(f"hs_distinct returned {out_count.value} rows of {n}")
         return perm[:out_count.value], out_count.value
 
+    def mark_first(self, batch: DBatch, key_indices: Sequence[int], sel: torch.Tensor | None = None, n_sel: int = 0,
+                   mode: int = 0) -> DCol:
+        """First-occurrence marks over the rows of ``batch`` (hs_mark_first) -> an INTEGER column of ``nrows`` cells: 1
+        where the row is among ``sel[:n_sel]`` (ascending row list; None: every row) and no earlier row of the list holds
+        the same values in the columns ``key_indices``, else 0.  Summed per group over the keys (group key parts, e) the
+        marks are COUNT(DISTINCT e).  Equality is ``distinct``'s; nothing is decoded - a dictionary-coded column compares
+        by its code (one code, one string).  ``mode``: hs_mark_first's (0: the library chooses its path).  Like
+        ``distinct`` the call learns sizes on the host between its steps, so a run that contains it is not replayable."""
+        batch = self.resolve(batch)
+        n = batch.nrows
+        if self.rec is not None:
+            self.rec.poisoned = True
+        cols = [batch.cols[i] for i in key_indices]
+        if not 1 <= len(cols) <= hs.HS_MAX_COLS:
+            raise DeviceError(f"COUNT(DISTINCT) compares 1 to {hs.HS_MAX_COLS} columns, not {len(cols)}")
+        if any(col.virtual for col in cols):
+            raise DeviceError("a virtual column of the fused join cannot be compared by COUNT(DISTINCT)")
+        marks = self.empty(n, torch.int32)
+        if n == 0:
+            return DCol(hs.I32, marks, 0)
+        arr = (hs.hs_col * len(cols))(*[c.as_hs() for c in cols])
+        ws = self.workspace(self._raw_lib.hs_mark_first_ws_bytes(n, len(cols), 32 * len(cols)))
+        hs.check(self._raw_lib.hs_mark_first(self.stream, arr, len(cols), n, sel.data_ptr() if sel is not None else None,
+                                             int(n_sel) if sel is not None else 0, int(mode), marks.data_ptr(),
+                                             ws.data_ptr(), self.flags.data_ptr()), "hs_mark_first")
+        return DCol(hs.I32, marks, n)
+
     def unit_ids_per_row(self, unit_rows: Sequence[int], unit_ids: Sequence[int]) -> torch.Tensor:
         """Global block id of every partial row: unit_ids[u] for rows unit_rows[u] .. unit_rows[u + 1]."""
         n = int(unit_rows[-1])

@@ -406,6 +406,7 @@ class HipExecutionEngine(ExecutionEngine):
             full_task._hs_fast = None
         for _attempt in range(12):
             plan = self._cached_plan(full_task)
+            self._refuse_marks_on_ranks(plan)
             self._select_caps(plan)
             rec_key = self._recording_key(plan)
             rec = self._recordings.get(rec_key) if self.replay_enabled else None
@@ -649,6 +650,7 @@ class HipExecutionEngine(ExecutionEngine):
                     self.streamed_join_fallbacks += 1  # the ranges are concatenated; the join runs resident
                     self.last_probe_route = "resident"
                 self._refuse_sort_in_pieces(sort, writer)
+                self._refuse_marks_in_pieces(consumers)
                 return self._run_scan_stage_streamed(stage, outputs, ranges)
             batch = self._scan(producer, consumers, writer)
         elif kind == "LoadShuffleFilesTask":
@@ -664,6 +666,7 @@ class HipExecutionEngine(ExecutionEngine):
                                and first_real.group_by_column is not None)
             if isinstance(outputs[id(stage.dependencies[1])], _DeferredScan):
                 self._refuse_sort_in_pieces(sort, writer)
+                self._refuse_marks_in_pieces(consumers)
                 return self._run_join_stage_streamed(stage, outputs, feeds_aggregate)
             batch = self._join(producer, outputs[id(stage.dependencies[0])], outputs[id(stage.dependencies[1])],
                                self._needed_names(consumers), feeds_aggregate, consumers)
@@ -705,6 +708,21 @@ class HipExecutionEngine(ExecutionEngine):
         if sort is not None and _cls(writer) == "WriteToLocalFileTask":
             raise ExecutionError("DISTINCT / ORDER BY / LIMIT needs the whole result on the device, and this query's result is "
                                  "produced in pieces because its input exceeds HIPSPARK_HBM_BUDGET: raise the budget")
+
+    @staticmethod
+    def _refuse_marks_in_pieces(consumers: Sequence[Any]) -> None:
+        """COUNT(DISTINCT)'s marks are first occurrences over the WHOLE input: a stage that reads its input range by range
+        would mark a value once per range."""
+        if any(_cls(t) == "MarkFirstTask" for t in consumers):
+            raise ExecutionError("COUNT(DISTINCT) needs the whole input on the device, and this query's input is read in "
+                                 "pieces because it exceeds HIPSPARK_HBM_BUDGET: raise the budget")
+
+    def _refuse_marks_on_ranks(self, plan: Any) -> None:
+        """... and on N ranks the same (key, value) pair may sit on two ranks, each of which would mark it.  Raised from
+        the plan alone, on every rank alike, before a launch or a collective."""
+        if self.dist is not None and any(_cls(t) == "MarkFirstTask" for st in plan.stages for t in st.consumers):
+            raise NotImplementedError("COUNT(DISTINCT) runs on one GPU: on N ranks the same (key, value) pair may sit on two "
+                                      "ranks; run the query on one rank, or SELECT DISTINCT the pairs and count them")
 
     def _order_rows(self, batch: Any, sort: Any, schema: Schema) -> Any:
         """ORDER BY / LIMIT over the finished result: the rows are first rounded to the types they are stored in, so
@@ -755,6 +773,8 @@ class HipExecutionEngine(ExecutionEngine):
             elif tname == "UnpackKeyTask":
                 batch = self._unpack_key_tuple(self._materialise(batch, pending), task)
                 pending = []
+            elif tname == "MarkFirstTask":
+                batch, pending = self._mark_first(batch, pending, task)
             elif tname == "AggregateTask":
                 if task.before_shuffle and task.group_by_column is None:
                     batch = self._aggregate_whole_input(batch, pending, task)
@@ -915,6 +935,56 @@ class HipExecutionEngine(ExecutionEngine):
         packed = self.dev.pack_key(batch, parts)
         return dataclasses.replace(batch, schema=[*batch.schema, (key.name, ColumnType.STRING)],
                                    cols=[*batch.cols, packed]), pending
+
+    def _mark_first(self, batch: Any, pending: list, task: Any) -> tuple[Any, list]:
+        """In front of the partial aggregate of a query with COUNT(DISTINCT e): one first-occurrence mark
+        column per item, appended under its reserved name, over the keys (GROUP BY key parts, e).  A pending WHERE over
+        plain-column arguments becomes the ascending list of surviving rows the marks consider, and STAYS pending: the
+        aggregate still applies it while it scans, and a dropped row's mark is 0 anyway.  An argument that has to be
+        computed (an expression, or an INTEGER / FLOAT column held wider than it is stored) is evaluated and rounded as
+        ``select`` would, over the surviving rows only - an error in a row the WHERE drops must not be raised - so the
+        WHERE is applied first, as in front of any projection.  Every refusal is raised before a launch."""
+        from . import hipspark as hs  # noqa: PLC0415
+        from .constants import ColumnType  # noqa: PLC0415
+        from .device import FILE_KIND  # noqa: PLC0415
+        from .lowering import unalias  # noqa: PLC0415
+
+        if batch.join8 is not None:
+            self._no_join8.add(batch.join_task_id)
+            raise RestartQuery
+        if batch.unit_col is not None:
+            self._no_fused_join.add(batch.join_task_id)
+            raise RestartQuery
+        batch = self.dev.resolve(batch)
+        parts = [batch.column_index(part.name) for part in task.key_parts()]
+        if len(parts) + 1 > hs.HS_MAX_COLS:
+            raise ExecutionError(f"COUNT(DISTINCT) under a GROUP BY over {len(parts)} columns: at most {hs.HS_MAX_COLS - 1}")
+
+        def stored(i: int) -> bool:
+            ctype = batch.schema[i][1]
+            return batch.cols[i].kind == hs.STR or batch.cols[i].kind == FILE_KIND[ctype]
+
+        plain = [_cls(unalias(expr)) in ("Col", "SchemaCol") and stored(batch.column_index(unalias(expr).name))
+                 for _, expr in task.items]
+        if pending and not all(plain):
+            batch, pending = self._materialise(batch, pending), []
+        sel, n_sel = self.dev.filter_select(batch, pending) if pending else (None, 0)
+        schema, cols = list(batch.schema), list(batch.cols)
+        computed = [(name, expr) for (name, expr), is_plain in zip(task.items, plain) if not is_plain]
+        values = dict(zip((name for name, _ in computed),
+                          self.dev.eval_numeric(batch, [expr for _, expr in computed]))) if computed else {}
+        for (name, expr), is_plain in zip(task.items, plain):
+            if is_plain:
+                arg = batch.cols[batch.column_index(unalias(expr).name)]
+            else:
+                dcol, tag = values[name]
+                if tag == "B":
+                    raise ExecutionError(f"COUNT(DISTINCT {expr}): a comparison is not a value")
+                arg = self.dev.quantise_col(dcol, expr.infer_type(batch.schema))
+            keyed = dataclasses.replace(batch, cols=[*batch.cols, arg], schema=[*batch.schema, (name, ColumnType.INTEGER)])
+            cols.append(self.dev.mark_first(keyed, [*parts, len(batch.cols)], sel, n_sel))
+            schema.append((name, ColumnType.INTEGER))
+        return dataclasses.replace(batch, schema=schema, cols=cols), pending
 
     def _unpack_key_tuple(self, batch: Any, task: Any) -> Any:
         """Directly above the merge of a GROUP BY over several columns: column 0, the packed tuple of every result group,
@@ -1180,6 +1250,7 @@ class HipExecutionEngine(ExecutionEngine):
         prefix = f"{producer.alias}." if producer.alias else ""
         names = [prefix + n for n, _ in table.schema]
         needed: list[str] | None = []
+        made: set[str] = set()  # COUNT(DISTINCT)'s mark columns: the MarkFirstTask makes them, no table holds them
         for task in consumers:
             tname = _cls(task)
             if tname == "FilterTask":
@@ -1188,11 +1259,15 @@ class HipExecutionEngine(ExecutionEngine):
                 for col in task.columns:
                     needed += _plain_names(col)
                 break
+            elif tname == "MarkFirstTask":
+                made |= {name for name, _ in task.items}
+                for _, expr in task.items:
+                    needed += _plain_names(expr)
             elif tname == "AggregateTask":
                 if task.group_by_column is not None:
                     needed += _plain_names(task.group_by_column)
                 for agg in task.agg_columns:
-                    needed += _plain_names(agg)
+                    needed += [n for n in _plain_names(agg) if n not in made]
                 break
         else:
             needed = None  # rows reach the writer unprojected: every column is needed
@@ -1274,6 +1349,7 @@ class HipExecutionEngine(ExecutionEngine):
         """Column names the consumers of a producer reference before the schema changes (projection /
         aggregate); None = rows reach the writer as they are, every column is needed."""
         needed: set[str] = set()
+        made: set[str] = set()  # COUNT(DISTINCT)'s mark columns: the MarkFirstTask makes them, no input holds them
         for task in consumers:
             tname = _cls(task)
             if tname == "FilterTask":
@@ -1282,11 +1358,15 @@ class HipExecutionEngine(ExecutionEngine):
                 for col in task.columns:
                     needed.update(_plain_names(col))
                 return needed
+            elif tname == "MarkFirstTask":
+                made |= {name for name, _ in task.items}
+                for _, expr in task.items:
+                    needed.update(_plain_names(expr))
             elif tname == "AggregateTask":
                 if task.group_by_column is not None:
                     needed.update(_plain_names(task.group_by_column))
                 for agg in task.agg_columns:
-                    needed.update(_plain_names(agg))
+                    needed.update(n for n in _plain_names(agg) if n not in made)
                 return needed
         return None
 

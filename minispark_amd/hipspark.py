@@ -367,6 +367,8 @@ SIGNATURES: dict[str, tuple] = {
     "hs_order_by": (C.c_int, [_P, _COLP, _P, _I32, _I64, _P, _I64, _P, _P, _P, _P]),
     "hs_distinct_ws_bytes": (C.c_size_t, [_I64, _I32, _I32]),
     "hs_distinct": (C.c_int, [_P, _COLP, _I32, _I64, _P, _P, _P, _P, _P]),
+    "hs_mark_first_ws_bytes": (C.c_size_t, [_I64, _I32, _I32]),
+    "hs_mark_first": (C.c_int, [_P, _COLP, _I32, _I64, _P, _I64, _I32, _P, _P, _P]),
     "hs_expand_by_bounds": (C.c_int, [_P, _P, _P, _I64, _I64, _P]),
     "hs_group_mask": (C.c_int, [_P, _P, _I64, _P]),
     "hs_group_fold": (C.c_int, [_P, _COLP, _SPECP, _P, _I64, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),

@@ -7,7 +7,7 @@ A hand-written backtracking recursive-descent parser for the same language:
     SELECT [DISTINCT] select_list FROM 'path' [AS t] { [LEFT|RIGHT|INNER|FULL] JOIN 'path' [AS t] ON cond }
            [WHERE cond] [GROUP BY col | (col {, col}) [HAVING cond]] [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] [LIMIT n] ;
 
-* select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e) [AS name]``, ``expr [AS name]``;
+* select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e)/COUNT(DISTINCT e) [AS name]``, ``expr [AS name]``;
 * conditions: OR < AND < NOT < comparison | ( cond ) | BETWEEN | LIKE, comparators = != <= >= < >;
 * expressions: + - over * / over atoms (number, column, string literal, ( expr ), COUNT()/SUM(e),
   ``CASE WHEN cond THEN expr {WHEN cond THEN expr} ELSE expr END``, the date functions ``YEAR(e)`` ``QUARTER(e)``
@@ -36,6 +36,11 @@ A hand-written backtracking recursive-descent parser for the same language:
   columns under their own names.  ``GROUP BY (a)`` is ``GROUP BY a``.  The row form is tried after the
   bare column, so every text accepted before builds the tree it built.  The unparenthesised list ``GROUP BY a, b`` is
   still rejected with a ``TypeError`` (its message points at the row form): tests/test_parser.py pins that rejection.
+
+* ``COUNT(DISTINCT e)`` - the keyword, whitespace, exactly one expression - is ``Functions.count_distinct(e)``: the number
+  of different values of ``e`` in the group, as a select item and inside HAVING.  It is tried after the
+  forms above, so ``COUNT(DISTINCT)`` still reads a column called DISTINCT and raises what it raised, and every text
+  accepted before builds the tree it built.  ``COUNT(DISTINCT a, b)`` and ``SUM(DISTINCT a)`` are not part of the language.
 
 Alternatives are tried in the grammar's order and the first that fits wins (ordered choice), so texts the
 reference accepts build the same task tree here (tests/test_parser.py compares both renderings).
@@ -252,6 +257,20 @@ class _Parser:
         return Col("*")
 
     def aggregate_call(self) -> AggCol:
+        # ordered choice: the five aggregates as they were first, so COUNT(DISTINCT) - a column called DISTINCT - still
+        # raises what it raised; COUNT(DISTINCT expr) did not parse at all before
+        return self.first_of(self.plain_aggregate_call, self.count_distinct_call)
+
+    def count_distinct_call(self) -> AggCol:
+        self.lit("COUNT(DISTINCT")
+        self.ws()
+        arg = self.expr()
+        self.lit(")")
+        agg = F.count_distinct(_as_col(arg))
+        has_alias, alias = self.attempt(self.alias)
+        return agg.alias(alias) if has_alias else agg
+
+    def plain_aggregate_call(self) -> AggCol:
         name = self.first_of(*[(lambda n=n: self.lit(n)) for n in _AGGREGATES])
         self.lit("(")
         has_arg, arg = self.attempt(self.expr)
@@ -478,6 +497,22 @@ class _Parser:
         return col
 
     def function_call(self) -> Col:
+        # COUNT(DISTINCT expr) after every form there was (HAVING COUNT(DISTINCT x) > 1, arithmetic over it)
+        return self.first_of(self.plain_function_call, self.count_distinct_function)
+
+    def count_distinct_function(self) -> Col:
+        self.lit("COUNT")
+        self.ows()
+        self.lit("(")
+        self.ows()
+        self.lit("DISTINCT")
+        self.ws()
+        arg = self.expr()
+        self.ows()
+        self.lit(")")
+        return F.count_distinct(_as_col(arg))
+
+    def plain_function_call(self) -> Col:
         name = self.rx(_IDENT)
         self.ows()
         self.lit("(")

@@ -17,6 +17,9 @@ Rewrites applied, in the reference's order (plan.py:224-235):
    2a. a GROUP BY over several columns (``KeyTupleCol``, this build's own): both aggregates and the shuffle write see the
    tuple as ONE packed STRING column under the tuple's reserved name, and an ``UnpackKeyTask`` directly above the merging
    aggregate - below the AVG projection, HAVING, the final select and any ``SortTask`` - restores the key columns;
+   2b. ``COUNT(DISTINCT e)`` (this build's own): one ``MarkFirstTask`` directly under the partial aggregate
+   appends a first-occurrence mark column per distinct argument, and the aggregate carries ``SUM(mark)`` under the
+   requested name in its place (the ``expand_avg`` pattern) - the merge and everything above it see an integer SUM;
 3. strip ``alias.`` prefixes from the output column names with a final ProjectTask (plan.py:207-222);
 4. cut the chain into stages at every shuffle write / join, dependencies first.
 
@@ -34,6 +37,7 @@ from .tasks import (
     BroadcastHashJoinTask,
     ConsumerTask,
     LoadShuffleFilesTask,
+    MarkFirstTask,
     ProducerTask,
     ProjectTask,
     SortTask,
@@ -134,13 +138,25 @@ class PhysicalPlan:
             return task
         if type(task) is AggregateTask and task.before_shuffle:
             requested = task.agg_columns
-            carried = [part for agg in requested for part in agg.expand_avg()]
+            # COUNT(DISTINCT e) is carried as SUM(mark) (rewrite 2b); counts of one argument share a mark column
+            marks: dict[str, tuple[str, Col]] = {}
+            carried = []
+            for agg in requested:
+                if agg.type != "count_distinct":
+                    carried.extend(agg.expand_avg())
+                    continue
+                arg = agg.original_col
+                name, _ = marks.setdefault(str(arg), (f"__hs_mark{len(marks)}({arg.name})", arg))
+                carried.append(AggCol("sum", Col(name)).alias(agg.name))
+            below = task.parent_task
+            if marks:
+                below = MarkFirstTask(below, key=task.group_by_column, items=list(marks.values()))
             key_tuple = task.group_by_column if type(task.group_by_column) is KeyTupleCol else None
             if key_tuple is not None:
                 # several key columns: from the partial aggregate to the merge they are ONE packed column (rewrite 2a)
                 part_schema = list(task.inferred_schema[: len(key_tuple.parts)])
                 task.group_by_column = key_tuple.as_packed()
-            partial = AggregateTask(task.parent_task, group_by_column=task.group_by_column, agg_columns=carried)
+            partial = AggregateTask(below, group_by_column=task.group_by_column, agg_columns=carried)
             shuffled = WriteToShufflePartitions(partial, key_column=task.group_by_column)
             task.parent_task = LoadShuffleFilesTask(shuffled)
             task.before_shuffle = False

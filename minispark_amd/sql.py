@@ -515,7 +515,9 @@ class CaseBuilder:
 
 
 class AggCol(Col):
-    """``type`` in {"sum","min","max","avg"} applied to ``original_col`` (reference sql.py:399-446)."""
+    """``type`` in {"sum","min","max","avg"} applied to ``original_col`` (reference sql.py:399-446), or
+    ``"count_distinct"`` (no reference counterpart: DESIGN.md 4.4e), the number of different values of ``original_col``,
+    an INTEGER; the planner carries it as the SUM of a first-occurrence mark column (``MarkFirstTask``)."""
 
     def __init__(self, agg_type: str, original_col: Col) -> None:
         self.original_col = original_col
@@ -534,6 +536,9 @@ class AggCol(Col):
         return (self.original_col,)
 
     def infer_type(self, schema: Schema) -> ColumnType:
+        if self.type == "count_distinct":
+            self.original_col.infer_type(schema)  # ValueError('Column "x" not found in schema ...')
+            return ColumnType.INTEGER
         return ColumnType.FLOAT if self.type == "avg" else self.original_col.infer_type(schema)
 
     def normalize_agg_columns(self) -> Col:
@@ -579,6 +584,12 @@ class Functions:
     @staticmethod
     def count() -> AggCol:
         return AggCol("sum", Lit(1)).alias("count")
+
+    @staticmethod
+    def count_distinct(col: Col) -> AggCol:
+        """COUNT(DISTINCT col): the number of different values of ``col`` (a column, or an INTEGER / FLOAT / TIMESTAMP
+        valued expression) among the rows of the group; named ``count_distinct_<name>``."""
+        return AggCol("count_distinct", _wrap(col))
 
     @staticmethod
     def when(condition: Any, value: Any) -> CaseBuilder:

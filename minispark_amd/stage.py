@@ -144,6 +144,9 @@ def _plan_of(full_task: Any, plan: Any) -> list:
     stages = list((plan if plan is not None else PhysicalPlan.generate_physical_plan(full_task)).stages)
     for stage in stages:
         for task in stage.consumers:
+            if _cls(task) == "MarkFirstTask":
+                # (the marks are a pass over the whole batch in front of the scan: DESIGN.md 4.4e)
+                raise StageUnsupported("COUNT(DISTINCT)")
             if _cls(task) == "AggregateTask" and task.group_by_column is None:
                 # (the stage blobs describe a key column; the engine runs this form through hs_agg_scalar)
                 raise StageUnsupported("an aggregate without GROUP BY")

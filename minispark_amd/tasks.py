@@ -17,9 +17,9 @@ from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Iterator, Literal
 
-from .constants import Schema
+from .constants import ColumnType, Schema
 from .io import BlockFile
-from .sql import AggCol, BinaryOperatorColumn, Col, KeyTupleCol, LikeColumn
+from .sql import BINOP_SYMBOLS, AggCol, BinaryOperatorColumn, Col, KeyTupleCol, LikeColumn
 
 JoinType = Literal["inner", "left", "right", "outer"]
 
@@ -247,6 +247,59 @@ class UnpackKeyTask(ConsumerTask):
         return f"UnpackKey({self.key} <- {self.key.name})"
 
 
+MARK_TYPES = (ColumnType.INTEGER, ColumnType.FLOAT, ColumnType.TIMESTAMP)
+
+
+@dataclass(kw_only=True)
+class MarkFirstTask(ConsumerTask):
+    """Directly under the partial aggregate of a query with COUNT(DISTINCT e) (no reference counterpart: DESIGN.md 4.4e).
+    For every item (reserved mark name, argument expression) the input gains one INTEGER column: 1 in a row that survives
+    the WHERE and is the first such row, in input order, with its values of (the parts of ``key``, the argument), else 0 -
+    so the partial aggregate's ``SUM(mark)`` per group is the number of different arguments.  ``key`` = the GROUP BY key
+    of that aggregate: None (whole input), a plain column, or the ``KeyTupleCol`` in its unpacked form.  An argument is a
+    plain column of any type or an INTEGER / FLOAT / TIMESTAMP valued expression, compared as the value ``select`` would
+    store.  Refused here, at planning: a FLOAT key column (the aggregation tiers group floats by their own rule, and the
+    marks must not disagree with them about -0.0 or NaN), a computed key, a string-valued or boolean argument expression."""
+
+    key: Col | None
+    items: list[tuple[str, Col]]
+
+    def key_parts(self) -> list[Col]:
+        if self.key is None:
+            return []
+        return list(self.key.parts) if type(self.key) is KeyTupleCol else [self.key]
+
+    def validate_schema(self) -> Schema:
+        schema = self.parent_task.validate_schema()
+        for part in self.key_parts():
+            if type(part).__name__ not in {"Col", "SchemaCol"}:
+                raise NotImplementedError(f"COUNT(DISTINCT) under GROUP BY {part}: the key must be a plain column, not an "
+                                          "expression: select(... .alias()) it first")
+            if part.infer_type(schema) == ColumnType.FLOAT:
+                raise NotImplementedError(f"COUNT(DISTINCT) under GROUP BY {part.name}: a FLOAT key column is not supported "
+                                          "(group by an INTEGER, STRING or TIMESTAMP column instead)")
+        _check_known([expr for _, expr in self.items], schema, "COUNT(DISTINCT)")
+        for _, expr in self.items:
+            bare = expr
+            while type(bare).__name__ == "AliasColumn":
+                bare = bare.original_col
+            if type(bare).__name__ in {"Col", "SchemaCol"}:
+                bare.infer_type(schema)
+                continue
+            boolean = (type(bare).__name__ == "LikeColumn" or
+                       (type(bare).__name__ == "BinaryOperatorColumn" and
+                        BINOP_SYMBOLS[bare.operator] in {"==", "!=", "<", "<=", ">", ">=", "and", "or"}))
+            if boolean or bare.infer_type(schema) not in MARK_TYPES:
+                raise NotImplementedError(f"COUNT(DISTINCT {expr}): the argument is a column or an INTEGER / FLOAT / TIMESTAMP "
+                                          "valued expression; select(... .alias()) a string expression first and count the "
+                                          "column")
+        return [*schema, *[(name, ColumnType.INTEGER) for name, _ in self.items]]
+
+    def describe(self) -> str:
+        key = "whole input" if self.key is None else f"key: {self.key}"
+        return f"MarkFirst({key}; " + ", ".join(f"{name} <- {expr}" for name, expr in self.items) + ")"
+
+
 @dataclass(kw_only=True)
 class SortTask(ConsumerTask):
     """ORDER BY / LIMIT over the query's result rows (no reference counterpart).  ``keys`` = (plain column of the input
@@ -333,6 +386,7 @@ __all__ = [
     "LikeColumn",
     "LoadShuffleFilesTask",
     "LoadTableBlockTask",
+    "MarkFirstTask",
     "ProducerTask",
     "ProjectTask",
     "SortTask",
