@@ -615,6 +615,31 @@ int hs_distinct(void* stream, const hs_col* keys, int32_t n_keys, int64_t nrows,
 size_t hs_mark_first_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words);
 int hs_mark_first(void* stream, const hs_col* keys, int32_t n_keys, int64_t nrows, const int64_t* sel /* null: all rows */,
                   int64_t n_sel, int32_t mode, int32_t* marks, void* ws, uint32_t* flags);
+/* Window ranking over result rows (no reference counterpart: the reference has no window functions).  keys[0 .. n_part)
+ * are the PARTITION BY columns, keys[n_part .. n_keys) the ORDER BY keys of the window; descending[k] (n_keys entries)
+ * is read for the order keys only, partition columns are always ascending.  Rows are in one partition iff they are
+ * equal in every partition column and peers iff equal in every key, under hs_distinct's equality (hs_order_by's key
+ * words); inside a partition the order is hs_order_by's, ties in input order.  out[f] (HOST array of n_funcs device
+ * pointers, each nrows HS_I32 cells, in INPUT order) receives funcs[f]:
+ *   HS_WIN_ROW_NUMBER  1, 2, 3 ... along the partition's order (n_part == n_keys: in input order)
+ *   HS_WIN_RANK        1 + the rows of the partition before the row's first peer
+ *   HS_WIN_DENSE_RANK  1 + the groups of peers of the partition before the row's
+ * Steps: hs_order_by's stable sort over all keys without a limit; one pass writes two bits per SORTED position (the row
+ * differs from its left neighbour in any key byte / in the partition prefix of the key bytes); a three-pass segmented
+ * scan over 2048-row tiles carries the last partition head, the last peer head and the peer heads since the partition
+ * head (a non-commutative combine, always carry-left); the last pass scatters the requested values through the sort's
+ * row list.  No atomics.  Refused before anything is launched or any pointer is read: n_keys > HS_MAX_COLS, n_funcs >
+ * HS_WIN_MAX_FUNCS or nrows >= 2^31 (HS_E_LIMIT); n_part outside [0, n_keys], an unknown function, or a rank function
+ * with n_part == n_keys (HS_E_ARG).  nrows == 0: HS_OK, nothing launched.  Like hs_order_by the call synchronises the
+ * stream between its steps and must not be captured.  ws: hs_window_ws_bytes(nrows, n_keys, max_key_words) bytes (the
+ * sort's workspace + one byte per row + 16 bytes per tile).  flags: no bit is raised at present (may be null). */
+#define HS_WIN_ROW_NUMBER 0
+#define HS_WIN_RANK 1
+#define HS_WIN_DENSE_RANK 2
+#define HS_WIN_MAX_FUNCS 8
+size_t hs_window_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words);
+int hs_window(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows,
+              const int32_t* funcs, int32_t n_funcs, int32_t* const* out, void* ws, uint32_t* flags);
 /* out[i] = values[s] for bounds[s] <= i < bounds[s+1], i in [0, n) (device arrays; bounds has n_seg + 1 entries,
  * bounds[0] = 0): the global block id of every partial row of a multi-rank partial aggregate. */
 int hs_expand_by_bounds(void* stream, const int64_t* bounds, const int64_t* values, int64_t n_seg, int64_t n, int64_t* out);

@@ -2246,16 +2246,18 @@ struct DhArgs {
 };
 static_assert(sizeof(DhArgs) % 8 == 0, "DhArgs");
 
-__device__ __forceinline__ uint64_t dh_word(const DhArgs& A, int32_t w, int64_t row) {
+// word w of a row's key, formed again from the columns (k_distinct_heads, k_win_heads)
+__device__ __forceinline__ uint64_t ob_word(const ObKeys& K, int32_t n_keys, int32_t w, int64_t row) {
     uint64_t word = 0;
     int64_t at = 0;
-    for (int k = 0; k < A.n_keys; ++k) {
+    for (int k = 0; k < n_keys; ++k) {
         ObPart part;
-        if (ob_part_of(k, at, A.K.width[k], w, part)) word |= ob_part_bits(A.K, part, row);
-        at += A.K.width[k];
+        if (ob_part_of(k, at, K.width[k], w, part)) word |= ob_part_bits(K, part, row);
+        at += K.width[k];
     }
     return word;
 }
+__device__ __forceinline__ uint64_t dh_word(const DhArgs& A, int32_t w, int64_t row) { return ob_word(A.K, A.n_keys, w, row); }
 
 __global__ void __launch_bounds__(OB_THREADS) k_distinct_heads(const DhArgs A_kernarg) {
     HS_KERNARG(DhArgs, A);
@@ -2508,6 +2510,302 @@ extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, 
     const int64_t tiles = (D.n + OB_TILE - 1) / OB_TILE;
     hipLaunchKernelGGL(k_distinct_heads, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, D);
     RX_CHECK_LAUNCH("hs_mark_first (heads)");
+    return HS_OK;
+}
+
+// =====================================================================================================
+// Window ranking over result rows (include/hipspark.h hs_window; the reference has no window functions).
+//
+// ob_sort orders the rows by (partition columns, order keys): a partition is a run of sorted positions, peers are
+// neighbours, and the sort being stable the rows of a group of peers stand in input order.  k_win_heads writes two bits
+// per SORTED position - the row differs from its left neighbour in any key byte (peer head) / in the first `part_bytes`
+// bytes of the key (partition head) - with k_distinct_heads' neighbour shuffle.  Per position j the answers are
+//     row_number = j - P + 1      P: the last partition head at or before j
+//     rank       = Q - P + 1      Q: the last peer head at or before j
+//     dense_rank = D              D: the peer heads in [P, j]
+// P and Q are max-scans of head positions, D a segmented sum that restarts at every partition head:
+//     (p, q, d) (+) (p', q', d') = (max(p, p'), max(q, q'), p' >= 0 ? d' : d + d')      identity (-1, -1, 0)
+// associative, NOT commutative: every level below joins with the earlier positions on the LEFT.  Three passes over
+// OB_TILE-row tiles, a lane holding 8 consecutive positions (one 8-byte load of head bytes): k_win_reduce folds a tile
+// into one summary, k_win_tiles (one workgroup, rounds of 2048 summaries, the carry of the rounds before on the left)
+// turns the summaries into each tile's carry, k_win_emit scans the tile again behind its carry, hands the results over
+// through LDS so that the row list is read coalesced, and scatters ONE function's values to the rows: out[perm[j]] - a
+// launch per requested function, the scan being cheap next to the scatter.
+// A tile without a head has the summary (-1, -1, 0) and passes its carry on as it is.  Positions are int32: rows < 2^31.
+// =====================================================================================================
+constexpr int WIN_PER = OB_TILE / OB_THREADS;  // consecutive sorted positions of a lane in the scan passes
+static_assert(WIN_PER == 8, "a lane's head bytes are one 8-byte load");
+
+struct WinHeads {
+    ObKeys K;               // col / width / str_cap / desc of the sort
+    int32_t n_keys, n_words;
+    const int64_t* perm;    // the rows, sorted by all keys (null: position = row, the keys have no byte)
+    const uint64_t* words;  // a key of ONE word: the sorted words, compared instead of formed again (else null)
+    int64_t n;
+    int64_t part_bytes;     // the partition columns' bytes: the first part_bytes bytes of a row's key
+    uint8_t* heads;         // by sorted position: bit 0 peer head, bit 1 partition head
+};
+static_assert(sizeof(WinHeads) % 8 == 0, "WinHeads");
+
+// the bytes of word w that belong to the partition prefix (byte 0 of the key = most significant byte of word 0)
+__device__ __forceinline__ uint64_t win_part_mask(int64_t part_bytes, int32_t w) {
+    const int64_t in = part_bytes - 8 * (int64_t)w;
+    return in >= 8 ? ~0ull : in <= 0 ? 0ull : ~0ull << (8 * (8 - in));
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_win_heads(const WinHeads A_kernarg) {
+    HS_KERNARG(WinHeads, A);
+    const int lane = threadIdx.x & (HS_WAVE - 1), wave = threadIdx.x / HS_WAVE;
+    const int64_t first = (int64_t)blockIdx.x * OB_TILE + (int64_t)wave * (OB_STEPS * HS_WAVE) + lane;
+    for (int j = 0; j < OB_STEPS; ++j) {
+        const int64_t i = first + j * HS_WAVE;
+        if (i - lane >= A.n) break;                   // the whole wave step lies past the rows
+        const bool live = i < A.n;
+        const int64_t pos = live ? i : A.n - 1;       // lanes past the end repeat the last row: every read stays inside
+        bool peer = false, part = false;
+        if (A.words) {  // coalesced: the sort's own words
+            const unsigned long long mine = A.words[pos];
+            unsigned long long left = __shfl_up(mine, 1, HS_WAVE);
+            if (lane == 0) left = i > 0 ? A.words[i - 1] : mine;
+            const unsigned long long diff = mine ^ left;
+            peer = diff != 0;
+            part = (diff & win_part_mask(A.part_bytes, 0)) != 0;
+        } else if (A.n_words > 0) {
+            const int64_t row = A.perm[pos];
+            // lane 0's left neighbour sits in no lane of this step: sorted position i - 1, loaded explicitly
+            const int64_t before = (lane == 0 && i > 0) ? A.perm[i - 1] : row;
+            for (int32_t w = 0; w < A.n_words; ++w) {  // most significant first: a lane's first differing word decides both bits
+                const unsigned long long mine = ob_word(A.K, A.n_keys, w, row);
+                unsigned long long left = __shfl_up(mine, 1, HS_WAVE);
+                if (lane == 0) left = ob_word(A.K, A.n_keys, w, before);
+                const unsigned long long diff = mine ^ left;
+                peer |= diff != 0;
+                part |= (diff & win_part_mask(A.part_bytes, w)) != 0;
+                if (__ballot(!peer) == 0) break;      // every lane of the step has found its difference
+            }
+        }
+        if (i == 0) peer = part = true;
+        if (live) A.heads[i] = (uint8_t)((peer ? 1 : 0) | (part ? 2 : 0));
+    }
+}
+
+struct WinS {
+    int32_t p, q, d;  // last partition head, last peer head (-1: none in the range), peer heads since the partition head
+};
+__device__ __forceinline__ WinS win_join(const WinS a, const WinS b) {  // a: the EARLIER positions
+    return WinS{a.p > b.p ? a.p : b.p, a.q > b.q ? a.q : b.q, b.p >= 0 ? b.d : a.d + b.d};
+}
+__device__ __forceinline__ WinS win_of(uint32_t head, int32_t j) {
+    return WinS{(head & 2u) ? j : -1, (head & 1u) ? j : -1, (int32_t)(head & 1u)};
+}
+// head bits of position j0 + k, k-th byte of the lane's load; nothing past the rows
+__device__ __forceinline__ uint32_t win_head(uint64_t bytes, int k, int64_t j0, int64_t n) {
+    return j0 + k < n ? (uint32_t)(bytes >> (8 * k)) & 3u : 0u;
+}
+__device__ __forceinline__ WinS win_shfl_up(const WinS v, int d) {
+    return WinS{__shfl_up(v.p, d, HS_WAVE), __shfl_up(v.q, d, HS_WAVE), __shfl_up(v.d, d, HS_WAVE)};
+}
+// exclusive scan of one WinS per thread over the workgroup, in thread order; `total` = the join of all (every thread).
+// Wave shuffles, then one LDS hop across the four waves.  The caller puts a barrier before s_wave is used again.
+__device__ __forceinline__ WinS win_block_excl(const WinS v, WinS* s_wave, WinS& total) {
+    const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE;
+    WinS incl = v;
+#pragma unroll
+    for (int d = 1; d < HS_WAVE; d <<= 1) {
+        const WinS t = win_shfl_up(incl, d);
+        if (lane >= d) incl = win_join(t, incl);
+    }
+    if (lane == HS_WAVE - 1) s_wave[w] = incl;
+    WinS excl = win_shfl_up(incl, 1);
+    if (lane == 0) excl = WinS{-1, -1, 0};
+    __syncthreads();
+    WinS base{-1, -1, 0};
+    total = base;
+#pragma unroll
+    for (int k = 0; k < OB_WAVES; ++k) {
+        if (k == w) base = total;
+        total = win_join(total, s_wave[k]);
+    }
+    return win_join(base, excl);
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_win_reduce(const uint8_t* heads, int64_t n, int4* sums) {
+    __shared__ WinS s_wave[OB_WAVES];
+    const int64_t j0 = (int64_t)blockIdx.x * OB_TILE + (int64_t)threadIdx.x * WIN_PER;
+    const uint64_t bytes = *(const uint64_t*)(heads + j0);  // the buffer holds whole tiles
+    WinS acc{-1, -1, 0};
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) acc = win_join(acc, win_of(win_head(bytes, k, j0, n), (int32_t)(j0 + k)));
+    WinS total;
+    win_block_excl(acc, s_wave, total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = make_int4(total.p, total.q, total.d, 0);
+}
+
+// one workgroup: sums[t] = the join of the summaries of tiles 0 .. t - 1 (tile t's carry), in place
+__global__ void __launch_bounds__(OB_THREADS) k_win_tiles(int4* sums, int64_t ntiles) {
+    __shared__ WinS s_wave[OB_WAVES];
+    WinS carry{-1, -1, 0};  // the rounds before this one: the same in every thread
+    for (int64_t t0 = 0; t0 < ntiles; t0 += OB_TILE) {
+        const int64_t mine = t0 + (int64_t)threadIdx.x * WIN_PER;
+        WinS v[WIN_PER], acc{-1, -1, 0};
+#pragma unroll
+        for (int k = 0; k < WIN_PER; ++k) {
+            v[k] = WinS{-1, -1, 0};
+            if (mine + k < ntiles) {
+                const int4 s = sums[mine + k];
+                v[k] = WinS{s.x, s.y, s.z};
+            }
+            acc = win_join(acc, v[k]);
+        }
+        WinS total;
+        WinS run = win_join(carry, win_block_excl(acc, s_wave, total));
+#pragma unroll
+        for (int k = 0; k < WIN_PER; ++k) {
+            if (mine + k < ntiles) sums[mine + k] = make_int4(run.p, run.q, run.d, 0);
+            run = win_join(run, v[k]);
+        }
+        carry = win_join(carry, total);
+        __syncthreads();
+    }
+}
+
+struct WinEmit {
+    const uint8_t* heads;
+    const int64_t* perm;  // null: position = row
+    const int4* carry;    // per tile (k_win_tiles)
+    int64_t n;
+    int32_t* out;         // one function per launch: three scattered columns at once fall out of the last-level cache
+    int32_t func, pad;    // that one column's partial lines still merge in (profiles/r15_window.txt)
+};
+static_assert(sizeof(WinEmit) % 8 == 0, "WinEmit");
+
+__global__ void __launch_bounds__(OB_THREADS) k_win_emit(const WinEmit A_kernarg) {
+    HS_KERNARG(WinEmit, A);
+    __shared__ WinS s_wave[OB_WAVES];
+    // a lane scans 8 consecutive positions, the row list is read with consecutive lanes on consecutive positions: the
+    // results cross over in LDS, one pad word per lane segment (k_scan_down's layout)
+    __shared__ int32_t s_p[OB_TILE + OB_THREADS], s_q[OB_TILE + OB_THREADS], s_d[OB_TILE + OB_THREADS];
+    const int tid = threadIdx.x;
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
+    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);
+    WinS acc{-1, -1, 0};
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) acc = win_join(acc, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
+    const int4 c = A.carry[blockIdx.x];
+    WinS total;
+    WinS run = win_join(WinS{c.x, c.y, c.z}, win_block_excl(acc, s_wave, total));
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        run = win_join(run, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
+        s_p[tid * (WIN_PER + 1) + k] = run.p;
+        s_q[tid * (WIN_PER + 1) + k] = run.q;
+        s_d[tid * (WIN_PER + 1) + k] = run.d;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t j = tile0 + e;
+        if (j >= A.n) break;
+        const int64_t row = A.perm ? A.perm[j] : j;
+        const int32_t p = s_p[e + e / WIN_PER], q = s_q[e + e / WIN_PER], d = s_d[e + e / WIN_PER];
+        A.out[row] = A.func == HS_WIN_ROW_NUMBER ? (int32_t)j - p + 1 : A.func == HS_WIN_RANK ? q - p + 1 : d;
+    }
+}
+
+static size_t win_heads_bytes(int64_t nrows) { return rx_align((size_t)((nrows + OB_TILE - 1) / OB_TILE) * OB_TILE); }
+
+extern "C" size_t hs_window_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words) {
+    if (nrows < 0) return 0;
+    // the sort's workspace, then the head bytes of whole tiles and a summary per tile
+    return hs_order_by_ws_bytes(nrows, n_keys, max_key_words) + win_heads_bytes(nrows) +
+           rx_align((size_t)((nrows + OB_TILE - 1) / OB_TILE + 1) * sizeof(int4));
+}
+
+extern "C" int hs_window(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
+                         int64_t nrows, const int32_t* funcs, int32_t n_funcs, int32_t* const* out, void* ws_, uint32_t* flags) {
+    (void)flags;
+    if (n_keys < 0 || n_part < 0 || n_part > n_keys || nrows < 0 || n_funcs <= 0 || !funcs || !out) {
+        hs_set_error("hs_window: bad arguments");
+        return HS_E_ARG;
+    }
+    if (n_keys > HS_MAX_COLS) {
+        hs_set_error("hs_window: more than %d partition and order columns", HS_MAX_COLS);
+        return HS_E_LIMIT;
+    }
+    if (n_funcs > HS_WIN_MAX_FUNCS) {
+        hs_set_error("hs_window: more than %d functions in one call", HS_WIN_MAX_FUNCS);
+        return HS_E_LIMIT;
+    }
+    if (nrows >= (1ll << 31)) {
+        hs_set_error("hs_window: %lld rows; the INTEGER result holds positions below 2^31", (long long)nrows);
+        return HS_E_LIMIT;
+    }
+    for (int f = 0; f < n_funcs; ++f) {
+        if (funcs[f] != HS_WIN_ROW_NUMBER && funcs[f] != HS_WIN_RANK && funcs[f] != HS_WIN_DENSE_RANK) {
+            hs_set_error("hs_window: function %d is not one of HS_WIN_*", funcs[f]);
+            return HS_E_ARG;
+        }
+        if (funcs[f] != HS_WIN_ROW_NUMBER && n_part == n_keys) {
+            hs_set_error("hs_window: RANK / DENSE_RANK need an order key");
+            return HS_E_ARG;
+        }
+    }
+    if (nrows == 0) return HS_OK;
+    if (!ws_ || (n_keys > 0 && !keys) || (n_keys > n_part && !descending)) {
+        hs_set_error("hs_window: bad arguments");
+        return HS_E_ARG;
+    }
+    for (int f = 0; f < n_funcs; ++f)
+        if (!out[f]) {
+            hs_set_error("hs_window: output %d is null", f);
+            return HS_E_ARG;
+        }
+    for (int k = 0; k < n_keys; ++k)
+        if (!ob_kind_ok(keys[k])) {
+            hs_set_error("hs_window: key %d is not a column that can be ordered", k);
+            return HS_E_ARG;
+        }
+    hipStream_t stream = (hipStream_t)stream_;
+    int32_t desc[HS_MAX_COLS] = {0};
+    for (int k = n_part; k < n_keys; ++k) desc[k] = descending[k] ? 1 : 0;
+    WinHeads H;
+    std::memset(&H, 0, sizeof(H));
+    size_t sort_bytes = 0;
+    {
+        ObSorted S;
+        int64_t sorted_rows = 0;
+        const int rc = ob_sort(stream, keys, desc, n_keys, nrows, nullptr, -1, &sorted_rows, ws_, "hs_window", S);
+        if (rc != HS_OK) return rc;
+        H.K = S.keys;
+        H.n_keys = n_keys;
+        H.n_words = S.n_words;
+        H.perm = S.rows;
+        H.n = nrows;
+        if (S.n_words == 1 && S.rows) H.words = S.words;  // one word per row: the sorted words ARE the rows' keys
+        for (int k = 0; k < n_part; ++k) H.part_bytes += S.keys.width[k];
+        sort_bytes = S.ws_bytes;
+    }
+    H.heads = (uint8_t*)ws_ + sort_bytes;
+    int4* sums = (int4*)(H.heads + win_heads_bytes(nrows));
+    const int64_t tiles = (nrows + OB_TILE - 1) / OB_TILE;
+    WinEmit E;
+    std::memset(&E, 0, sizeof(E));
+    E.heads = H.heads;
+    E.perm = H.perm;
+    E.carry = sums;
+    E.n = nrows;
+    hipLaunchKernelGGL(k_win_heads, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, H);
+    RX_CHECK_LAUNCH("hs_window (heads)");
+    hipLaunchKernelGGL(k_win_reduce, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, (const uint8_t*)H.heads, nrows, sums);
+    hipLaunchKernelGGL(k_win_tiles, dim3(1), dim3(OB_THREADS), 0, stream, sums, tiles);
+    RX_CHECK_LAUNCH("hs_window (scan)");
+    for (int f = 0; f < n_funcs; ++f) {
+        E.out = out[f];
+        E.func = funcs[f];
+        hipLaunchKernelGGL(k_win_emit, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, E);
+    }
+    RX_CHECK_LAUNCH("hs_window (emit)");
     return HS_OK;
 }
 

@@ -85,17 +85,47 @@ class DataFrame:
         """ORDER BY: ``Col`` (ascending), ``Col.asc()`` or ``Col.desc()``, the first key the most significant."""
         pairs = [(k.column, k.ascending) if isinstance(k, SortKey) else (k, True) for k in keys]
         top = self.task
-        if type(top) is _t.SortTask and top.distinct and not top.keys and top.limit is None:
-            _t.check_sort_keys(pairs)  # directly above distinct(): one task carries both, as limit() does
+        if type(top) is _t.SortTask and (top.distinct or top.windows) and not top.keys and top.limit is None:
+            _t.check_sort_keys(pairs)  # directly above distinct() / window(): one task carries both, as limit() does
             top.keys = pairs
             return self
         if type(top) is _t.SortTask and top.distinct:
             raise ValueError("order_by() comes directly after distinct(), once, and before limit()")
+        if type(top) is _t.SortTask and top.windows:
+            raise ValueError("order_by() comes after window() / qualify() / distinct(), once, and before limit()")
         return self._append(_t.SortTask, keys=pairs)
+
+    def window(self, *items: Any, select_order: list[str] | None = None) -> "DataFrame":
+        """Window ranking over the result rows: every item - ``F.row_number()``, ``F.rank()`` or
+        ``F.dense_rank()`` with ``.over(partition_by=[...], order_by=[...])`` and an optional ``.alias(name)`` - adds one
+        INTEGER column behind the existing ones, in the order given; no row moves.  ``select_order`` (the SQL front end)
+        names all columns in the order wanted instead.  It comes before ``qualify`` / ``distinct`` / ``order_by`` /
+        ``limit``, which may name the new columns."""
+        if not items:
+            raise ValueError("window() needs at least one window item")
+        top = self.task
+        if type(top) is _t.SortTask:
+            raise ValueError("window() comes once, before qualify() / distinct() / order_by() / limit()")
+        return self._append(_t.SortTask, keys=[], limit=None, windows=list(items), select_order=select_order)
+
+    def qualify(self, condition: Any) -> "DataFrame":
+        """QUALIFY: a condition over the result's columns, the window columns among them, applied right after the
+        windows were computed.  It follows ``window`` directly."""
+        top = self.task
+        if type(top) is not _t.SortTask or not top.windows:
+            raise ValueError("qualify() follows window(): it filters on window columns")
+        if top.qualify is not None or top.distinct or top.keys or top.limit is not None:
+            raise ValueError("qualify() comes directly after window(), once, before distinct() / order_by() / limit()")
+        top.qualify = condition
+        return self
 
     def distinct(self) -> "DataFrame":
         """SELECT DISTINCT: of the rows that are equal in every column the first stays.  It comes before ``order_by`` /
         ``limit``, which then apply to the rows that are left."""
+        top = self.task
+        if type(top) is _t.SortTask and top.windows and not top.distinct and not top.keys and top.limit is None:
+            top.distinct = True  # above window() / qualify(): one task carries all of them
+            return self
         if type(self.task) is _t.SortTask:
             raise ValueError("distinct() was already applied" if self.task.distinct and not self.task.keys
                              and self.task.limit is None else "distinct() comes before order_by() / limit()")

@@ -1634,6 +1634,46 @@ class Device:
             raise DeviceError(f"hs_distinct returned {out_count.value} rows of {n}")
         return perm[:out_count.value], out_count.value
 
+    WINDOW_KINDS = {"row_number": hs.WIN_ROW_NUMBER, "rank": hs.WIN_RANK, "dense_rank": hs.WIN_DENSE_RANK}
+
+    def window(self, batch: DBatch, part_idx: Sequence[int], order_keys: Sequence[tuple[int, bool]],
+               funcs: Sequence[str]) -> list[DCol]:
+        """ROW_NUMBER / RANK / DENSE_RANK over the rows of ``batch`` (hs_window) -> one INTEGER column per entry of
+        ``funcs``, in INPUT order: no row moves.  ``part_idx`` = the PARTITION BY columns, ``order_keys`` = (column,
+        ascending) pairs of the window's ORDER BY; all functions share the one sort.  Equality and order are
+        ``distinct``'s and ``order_by``'s.  A dictionary-coded column goes as its code byte where it only partitions (one
+        code, one string) or where the dictionary is sorted, decoded otherwise, as in ``order_by``.  The call learns sizes
+        on the host between its steps, so a run that contains it is not replayable."""
+        batch = self.resolve(batch)
+        n = batch.nrows
+        if self.rec is not None:
+            self.rec.poisoned = True
+        n_keys = len(part_idx) + len(order_keys)
+        if n_keys > hs.HS_MAX_COLS:
+            raise DeviceError(f"a window over {n_keys} partition and order columns: at most {hs.HS_MAX_COLS}")
+        if not 0 < len(funcs) <= hs.WIN_MAX_FUNCS:
+            raise DeviceError(f"{len(funcs)} window functions in one call: 1 to {hs.WIN_MAX_FUNCS}")
+        if n >= 1 << 31:
+            raise DeviceError(f"a window over {n} rows: the INTEGER result numbers fewer than 2^31")
+        cols = []
+        for k, which in enumerate([*part_idx, *[i for i, _ in order_keys]]):
+            col = batch.cols[which]
+            if col.virtual:
+                raise DeviceError("a virtual column of the fused join cannot be a window key")
+            if k >= len(part_idx) and col.dict is not None and list(col.dict) != sorted(col.dict):
+                col = self.decoded(col)
+            cols.append(col)
+        outs = [self.empty(max(n, 1), torch.int32) for _ in funcs]
+        if n:
+            arr = (hs.hs_col * max(n_keys, 1))(*[c.as_hs() for c in cols])
+            desc = (C.c_int32 * max(n_keys, 1))(*([0] * len(part_idx) + [0 if ascending else 1 for _, ascending in order_keys]))
+            kinds = (C.c_int32 * len(funcs))(*[self.WINDOW_KINDS[f] for f in funcs])
+            ptrs = (C.c_void_p * len(funcs))(*[o.data_ptr() for o in outs])
+            ws = self.workspace(self._raw_lib.hs_window_ws_bytes(n, n_keys, 32 * max(n_keys, 1)))
+            hs.check(self._raw_lib.hs_window(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, len(funcs), ptrs,
+                                             ws.data_ptr(), self.flags.data_ptr()), "hs_window")
+        return [DCol(hs.I32, out[:n], n) for out in outs]
+
     def mark_first(self, batch: DBatch, key_indices: Sequence[int], sel: torch.Tensor | None = None, n_sel: int = 0,
                    mode: int = 0) -> DCol:
         """First-occurrence marks over the rows of ``batch`` (hs_mark_first) -> an INTEGER column of ``nrows`` cells: 1

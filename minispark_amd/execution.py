@@ -697,6 +697,10 @@ class HipExecutionEngine(ExecutionEngine):
         import copy  # noqa: PLC0415
 
         consumers = [t for t in stage.consumers if t is not sort]
+        if sort.windows:
+            # the windowed task ADDS columns: the rename-only projection above it names columns the pipeline's rows do not
+            # have yet.  It changes names, never positions, and _order_rows hands its rows over under the writer's schema
+            consumers = list(stage.consumers[: next(i for i, t in enumerate(stage.consumers) if t is sort)])
         view = copy.copy(stage)
         view.consumers = consumers
         return consumers, view
@@ -706,7 +710,7 @@ class HipExecutionEngine(ExecutionEngine):
         """A result that is written range by range is never whole on the device, so it cannot be ordered (a LIMIT
         without keys could be served, but which rows it keeps would then depend on the budget: refused alike)."""
         if sort is not None and _cls(writer) == "WriteToLocalFileTask":
-            raise ExecutionError("DISTINCT / ORDER BY / LIMIT needs the whole result on the device, and this query's result is "
+            raise ExecutionError("OVER / DISTINCT / ORDER BY / LIMIT needs the whole result on the device, and this query's result is "
                                  "produced in pieces because its input exceeds HIPSPARK_HBM_BUDGET: raise the budget")
 
     @staticmethod
@@ -731,7 +735,10 @@ class HipExecutionEngine(ExecutionEngine):
         every row by now (_gather_to_root) and the others none.  SELECT DISTINCT (``sort.distinct``) comes between the
         rounding and the keys: rows equal in every column of the values the user reads back are removed, the first of
         them stays, and keys and limit apply to the survivors (a LIMIT without keys is then their head)."""
-        batch = self.dev.resolve(self._quantise_batch(self.dev.resolve(batch), schema))
+        if sort.windows:
+            batch = self._window_rows(batch, sort)
+        else:
+            batch = self.dev.resolve(self._quantise_batch(self.dev.resolve(batch), schema))
         names = [name for name, _ in sort.inferred_schema]
         if len(names) != len(batch.cols):
             raise ExecutionError(f"ORDER BY schema {sort.inferred_schema} does not match the result {batch.schema}")
@@ -749,6 +756,33 @@ class HipExecutionEngine(ExecutionEngine):
             return self.dev.head(batch, min(batch.nrows, sort.limit))  # LIMIT alone: one slice of the rows as they stand
         perm, count = self.dev.order_by(batch, keys, sort.limit)
         return self.dev.gather_batch(batch, perm, count)
+
+    def _window_rows(self, batch: Any, sort: Any) -> Any:
+        """Window ranking, the first step of a windowed SortTask: the rounded result rows gain one
+        INTEGER column per item - items with one (partition, order) spec share one sort and one launch sequence
+        (Device.window) - the column handles are placed in the task's output order (no row is copied), and QUALIFY
+        filters the rows through the WHERE machinery.  Keys are found by POSITION in the task's input schema."""
+        from .device import DBatch  # noqa: PLC0415
+
+        in_schema = list(sort.input_schema)
+        batch = self.dev.resolve(self._quantise_batch(self.dev.resolve(batch), in_schema))
+        if batch.nrows >= 1 << 31:
+            raise ExecutionError(f"a window column is INTEGER: it numbers fewer than 2^31 rows, the result has {batch.nrows}")
+        in_names = [name for name, _ in in_schema]
+        specs: dict[tuple, list[Any]] = {}
+        for item in sort.windows:
+            specs.setdefault(item.spec(), []).append(item)
+        by_name = dict(zip(in_names, batch.cols))
+        for items in specs.values():
+            part = [in_names.index(col.name) for col in items[0].partition_by]
+            order = [(in_names.index(col.name), ascending) for col, ascending in items[0].order_by]
+            for item, col in zip(items, self.dev.window(batch, part, order, [item.kind for item in items])):
+                by_name[item.name] = col
+        out_schema = list(sort.inferred_schema)
+        batch = DBatch(out_schema, [by_name[name] for name, _ in out_schema], batch.nrows)
+        if sort.qualify is not None:
+            batch = self.dev.resolve(self._materialise(batch, [sort.qualify]))
+        return batch
 
     def _consume(self, batch: Any, consumers: Sequence[Any]) -> Any:
         """Run a stage's consumer tasks (filters, projections, aggregates) over one batch."""

@@ -27,6 +27,13 @@ A hand-written backtracking recursive-descent parser for the same language:
   ``SELECT DISTINCT`` (the keyword, then whitespace) becomes ``distinct()`` between the final select and ``order_by``:
   rows equal in every result column are removed, the first of them stays, and ORDER BY / LIMIT apply to what is left.
   The form without the keyword is tried first, so a text that was accepted before builds the tree it built then.
+* window ranking, tried only after every older form failed, so accepted texts keep their trees:
+      select item:  ROW_NUMBER() | RANK() | DENSE_RANK()  OVER ( [PARTITION BY name {, name}]
+                                                                 [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] )  [AS alias]
+      clause:       ... [GROUP BY ... [HAVING ...]] [QUALIFY cond] [ORDER BY ...] [LIMIT n] ;
+  The items are set aside from the select list (before GROUP BY's stray-column check), the rest of the query is built as
+  ever, and ``window(...)`` / ``qualify(cond)`` follow the final select; names inside OVER are names of the RESULT, as for
+  ORDER BY.  ``ROW_NUMBER()`` without OVER and ``RANK(x)`` stay the unsupported functions they were.
   ``CASE`` (searched form only, ELSE mandatory, INTEGER / FLOAT branches, several WHEN arms nest to the right) stands
   wherever an expression may: a select item, an aggregate's argument, either side of a comparison, inside arithmetic or
   another CASE.  A column called ``CASE`` still parses as a column (no old text holds ``CASE`` whitespace ``WHEN``).
@@ -53,7 +60,8 @@ import re
 from typing import Any, Callable
 
 from .dataframe import DataFrame
-from .sql import DATE_PARTS, AggCol, AliasColumn, CaseColumn, Col, DatePartColumn, DateTruncColumn, Lit, SortKey
+from .sql import (DATE_PARTS, AggCol, AliasColumn, CaseColumn, Col, DatePartColumn, DateTruncColumn, Lit, SortKey,
+                  WindowItem)
 from .sql import Functions as F
 
 
@@ -93,6 +101,7 @@ class _Parser:
     def __init__(self, text: str, engine: Any) -> None:
         self.text, self.pos, self.engine = text, 0, engine
         self.furthest = 0
+        self.saw_window_item = False
 
     # ---- matching primitives --------------------------------------------------------------------------------
     def fail(self) -> None:
@@ -148,17 +157,37 @@ class _Parser:
     def query(self) -> DataFrame:
         # ordered choice: the grammar without DISTINCT first, so a text that was accepted before DISTINCT existed (a
         # column may be called DISTINCT) still builds the tree it built then
-        matched, df = self.attempt(lambda: self.query_body(distinct=False))
-        return df if matched else self.query_body(distinct=True)
+        # ... and the grammar without window items and QUALIFY before the one with them.  The older grammar answers a
+        # window item with an exception (ROW_NUMBER is an unsupported function to it), so that exception is kept and
+        # raised again when the text is no windowed query either
+        try:
+            matched, df = self.attempt(lambda: self.query_body(distinct=False))
+            if matched:
+                return df
+            return self.query_body(distinct=True)
+        except _NoMatch:
+            before: Exception | None = None
+        except Exception as exc:  # noqa: BLE001 - whatever the older grammar raised is raised again below
+            before = exc
+        self.pos = 0
+        matched, df = self.attempt(lambda: self.query_body(distinct=False, windowed=True))
+        if not matched:
+            matched, df = self.attempt(lambda: self.query_body(distinct=True, windowed=True))
+        if matched:
+            return df
+        if before is not None and not self.saw_window_item:
+            raise before
+        self.fail()  # a text with a well-formed window item that is no query: a syntax error at the furthest offset
+        return None
 
-    def query_body(self, distinct: bool) -> DataFrame:
+    def query_body(self, distinct: bool, windowed: bool = False) -> DataFrame:
         self.ows()
         self.lit("SELECT")
         self.ws()
         if distinct:
             self.lit("DISTINCT")
             self.ws()
-        select_list = self.select_list()
+        select_list = self.select_list(windowed)
         self.ws()
         self.lit("FROM")
         self.ws()
@@ -166,6 +195,7 @@ class _Parser:
         joins = self.repeat(lambda: (self.ws(), self.join_clause())[1])
         has_where, where = self.attempt(lambda: (self.ws(), self.where_clause())[1])
         has_group, group = self.attempt(lambda: (self.ws(), self.group_by_clause())[1])
+        has_qualify, qualify = self.attempt(lambda: (self.ws(), self.qualify_clause())[1]) if windowed else (False, None)
         has_order, order = self.attempt(lambda: (self.ws(), self.order_by_clause())[1])
         has_limit, limit = self.attempt(lambda: (self.ws(), self.limit_clause())[1])
         self.ows()
@@ -173,6 +203,17 @@ class _Parser:
         self.ows()
         if self.pos != len(self.text):
             self.fail()
+        # window items are set aside: they read the rows the rest of the query produces
+        result_list = select_list
+        windows = [c for c in select_list if type(c) is WindowItem]
+        select_list = [c for c in select_list if type(c) is not WindowItem]
+        if windowed:
+            if not windows and not has_qualify:
+                self.fail()  # no windowed query: what the older grammar said about the text stands
+            if not windows:
+                raise SemanticError("QUALIFY filters on window columns: the select list has no window item")
+            if not select_list:
+                raise SemanticError("a select list needs at least one column next to its window items")
 
         for other, cond in joins:
             df = df.join(other, on=cond, how="inner")
@@ -211,10 +252,18 @@ class _Parser:
             df = df.agg(*select_list)
         else:
             df = df.select(*select_list)
+        if windows:
+            names = [c.name for c in result_list]
+            trailing = all(type(c) is WindowItem for c in result_list[len(select_list):])
+            if not trailing and "*" in names:
+                raise SemanticError("next to * the window items come last in the select list")
+            df = df.window(*windows, select_order=None if trailing else names)
+            if has_qualify:
+                df = df.qualify(qualify)
         if distinct:
             df = df.distinct()
         if has_order:
-            names = {c.name for c in select_list}
+            names = {c.name for c in result_list}
             for key in order:
                 if "*" not in names and key.column.name not in names:
                     raise ValueError(f'Column "{key.column.name}" of ORDER BY is not in the select list {sorted(names)}')
@@ -244,10 +293,54 @@ class _Parser:
                     columns.append(Col(c.name))
         return df.select(*columns)
 
-    def select_list(self) -> list[Col]:
-        items = [self.select_item()]
-        items += self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), self.select_item())[3])
+    def select_list(self, windowed: bool = False) -> list[Any]:
+        item = self.select_item_or_window if windowed else self.select_item
+        items = [item()]
+        items += self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), item())[3])
         return items
+
+    def select_item_or_window(self) -> Any:
+        return self.first_of(self.star, self.window_item, self.aggregate_call, self.expr_aliased)
+
+    def window_item(self) -> WindowItem:
+        """ROW_NUMBER() | RANK() | DENSE_RANK(), whitespace, OVER ( [PARTITION BY names] [ORDER BY keys] ) [AS alias].
+        Anything else - no OVER, an argument - is no window item and goes on to the function call it was before."""
+        name = self.first_of(*[(lambda n=n: self.lit(n)) for n in ("ROW_NUMBER", "RANK", "DENSE_RANK")])
+        self.ows()
+        self.lit("(")
+        self.ows()
+        self.lit(")")
+        self.ws()
+        self.lit("OVER")
+        self.ows()
+        self.lit("(")
+        self.ows()
+
+        def partition() -> list[Col]:
+            self.lit("PARTITION")
+            self.ws()
+            self.lit("BY")
+            self.ws()
+            cols = [self.column_name()]
+            cols += self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), self.column_name())[3])
+            return cols
+
+        has_partition, part = self.attempt(partition)
+        if has_partition:
+            has_order, order = self.attempt(lambda: (self.ws(), self.order_by_clause())[1])
+        else:
+            has_order, order = self.attempt(self.order_by_clause)
+        self.ows()
+        self.lit(")")
+        item = WindowItem(name.lower()).over(partition_by=part if has_partition else [], order_by=order if has_order else [])
+        has_alias, alias = self.attempt(self.alias)
+        self.saw_window_item = True
+        return item.alias(alias) if has_alias else item
+
+    def qualify_clause(self) -> Col:
+        self.lit("QUALIFY")
+        self.ws()
+        return self.condition()
 
     def select_item(self) -> Col:
         return self.first_of(self.star, self.aggregate_call, self.expr_aliased)

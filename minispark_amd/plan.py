@@ -192,6 +192,9 @@ class PhysicalPlan:
         anywhere but on top of the chain has no meaning here."""
         node: Task | None = task
         while node is not None and type(node) is not VoidTask:
+            if type(node) is SortTask and not top and node.windows:
+                raise ValueError("a window item (OVER) reads the query's result rows: window() / QUALIFY must be the last "
+                                 "operation, not below a join, an aggregate or another operation")
             if type(node) is SortTask and not top:
                 raise ValueError("DISTINCT / ORDER BY / LIMIT must be the last operation")
             if type(node) is BroadcastHashJoinTask:

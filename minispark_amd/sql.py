@@ -156,6 +156,54 @@ class SortKey:
     __repr__ = __str__
 
 
+class WindowItem:
+    """``F.row_number() | F.rank() | F.dense_rank()`` ``.over(partition_by=[...], order_by=[...])`` ``[.alias(name)]``: one
+    window column of ``DataFrame.window`` (no reference counterpart - DESIGN.md 4.4f).  The keys are plain columns of the
+    RESULT the window reads (``Col``, ``Col.asc()``, ``Col.desc()``); the item adds one INTEGER column, named after its
+    function unless ``alias`` says otherwise.  Not an expression: it cannot be selected, compared or nested."""
+
+    KINDS = ("row_number", "rank", "dense_rank")
+
+    def __init__(self, kind: str) -> None:
+        if kind not in self.KINDS:
+            raise ValueError(f"window function {kind!r}: one of {self.KINDS}")
+        self.kind, self.name = kind, kind
+        self.partition_by: list[Col] = []
+        self.order_by: list[tuple[Col, bool]] = []
+        self.is_over = False
+
+    def over(self, partition_by: Any = (), order_by: Any = ()) -> "WindowItem":
+        single = lambda v: [v] if isinstance(v, (Col, SortKey)) else list(v)  # noqa: E731
+        self.partition_by = single(partition_by)
+        self.order_by = [(k.column, k.ascending) if isinstance(k, SortKey) else (k, True) for k in single(order_by)]
+        for col in [*self.partition_by, *[c for c, _ in self.order_by]]:
+            if type(col).__name__ not in {"Col", "SchemaCol"}:
+                raise ValueError(f"OVER takes plain columns of the result, not the expression {col}: select(... .alias()) first")
+        if self.kind != "row_number" and not self.order_by:
+            raise ValueError(f"{self.kind.upper()}() needs an ORDER BY inside OVER: without one every row of a partition is a "
+                             "peer of every other (ROW_NUMBER() may omit it)")
+        self.is_over = True
+        return self
+
+    def alias(self, name: str) -> "WindowItem":
+        self.name = name
+        return self
+
+    def spec(self) -> tuple:
+        """What the sort depends on: items with one spec share one sort."""
+        return (tuple(c.name for c in self.partition_by), tuple((c.name, asc) for c, asc in self.order_by))
+
+    def __str__(self) -> str:
+        parts = []
+        if self.partition_by:
+            parts.append("PARTITION BY " + ", ".join(str(c) for c in self.partition_by))
+        if self.order_by:
+            parts.append("ORDER BY " + ", ".join(f"{c} {'ASC' if asc else 'DESC'}" for c, asc in self.order_by))
+        return f"{self.kind.upper()}() OVER ({' '.join(parts)}) AS {self.name}"
+
+    __repr__ = __str__
+
+
 class Lit(Col):
     def __init__(self, value: ColumnTypePython) -> None:
         self.value = value
@@ -590,6 +638,19 @@ class Functions:
         """COUNT(DISTINCT col): the number of different values of ``col`` (a column, or an INTEGER / FLOAT / TIMESTAMP
         valued expression) among the rows of the group; named ``count_distinct_<name>``."""
         return AggCol("count_distinct", _wrap(col))
+
+    # window ranking (WindowItem): DESIGN.md 4.4f
+    @staticmethod
+    def row_number() -> WindowItem:
+        return WindowItem("row_number")
+
+    @staticmethod
+    def rank() -> WindowItem:
+        return WindowItem("rank")
+
+    @staticmethod
+    def dense_rank() -> WindowItem:
+        return WindowItem("dense_rank")
 
     @staticmethod
     def when(condition: Any, value: Any) -> CaseBuilder:

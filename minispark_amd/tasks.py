@@ -312,26 +312,75 @@ class SortTask(ConsumerTask):
     keys: list[tuple[Col, bool]] = field(default_factory=list)
     limit: int | None = None
     distinct: bool = False
+    # window ranking: ``windows`` = sql.WindowItem list, each one INTEGER column added to the input's
+    # columns; ``qualify`` = a condition over all of them (QUALIFY), applied right after; ``select_order`` = the names of
+    # all output columns in the order wanted (None: the input's columns, then the windows).  They run BEFORE distinct,
+    # keys and limit, which may name the window columns.
+    windows: list = field(default_factory=list)
+    qualify: Col | None = None
+    select_order: list[str] | None = None
+
+    MAX_WINDOWS = 8
 
     def __post_init__(self) -> None:
         check_sort_keys(self.keys)
         if self.limit is not None:
             check_limit(self.limit)
+        check_windows(self.windows)
 
     def validate_schema(self) -> Schema:
         schema = self.parent_task.validate_schema()
+        self.input_schema = list(schema)  # what the windows read: the engine finds their keys here by position
+        if self.windows:
+            check_windows(self.windows)
+            for item in self.windows:
+                for col in [*item.partition_by, *[c for c, _ in item.order_by]]:
+                    col.infer_type(schema)  # a key is a column of the INPUT, never another window item
+            schema = [*schema, *[(item.name, ColumnType.INTEGER) for item in self.windows]]
+            names = [name for name, _ in schema]
+            repeated = sorted({name for name in names if names.count(name) > 1})
+            if repeated:
+                raise ValueError(f"Duplicate column names in window(): {repeated} (alias() the window item)")
+            if self.select_order is not None:
+                if sorted(self.select_order) != sorted(names):
+                    raise ValueError(f"window(): the column order {self.select_order} does not name the columns {names}")
+                types = dict(schema)
+                schema = [(name, types[name]) for name in self.select_order]
+        elif self.qualify is not None:
+            raise ValueError("QUALIFY filters on window columns: the query has no window item")
+        if self.qualify is not None:
+            _check_known([self.qualify], schema, "QUALIFY")
         for col, _ in self.keys:
             col.infer_type(schema)  # ValueError('Column "x" not found in schema ...')
         return schema
 
     def __repr__(self) -> str:
-        """The dataclass form; ``distinct`` is named only when set, so a plain task prints as it did before the field."""
-        shown = [f for f in dataclasses.fields(self) if f.repr and (f.name != "distinct" or self.distinct)]
+        """The dataclass form; ``distinct`` and the window fields are named only when set, so a plain task prints as it
+        did before they existed."""
+        quiet = {"distinct", "windows", "qualify", "select_order"}
+        shown = [f for f in dataclasses.fields(self) if f.repr and (f.name not in quiet or getattr(self, f.name))]
         return f"{type(self).__name__}(" + ", ".join(f"{f.name}={getattr(self, f.name)!r}" for f in shown) + ")"
 
     def describe(self) -> str:
         keys = ", ".join(f"{col} {'ASC' if ascending else 'DESC'}" for col, ascending in self.keys)
-        return f"Sort({'DISTINCT ' if self.distinct else ''}{keys}; limit={self.limit})"
+        plain = f"Sort({'DISTINCT ' if self.distinct else ''}{keys}; limit={self.limit})"
+        if not self.windows and self.qualify is None:
+            return plain
+        qualify = "" if self.qualify is None else f"; QUALIFY {self.qualify}"
+        return f"Window({'; '.join(str(item) for item in self.windows)}{qualify}) -> {plain}"
+
+
+def check_windows(windows: list) -> None:
+    if len(windows) > SortTask.MAX_WINDOWS:
+        raise ValueError(f"a query takes at most {SortTask.MAX_WINDOWS} window items, not {len(windows)}")
+    for item in windows:
+        if type(item).__name__ != "WindowItem" or not item.is_over:
+            raise ValueError(f"window() takes F.row_number() / F.rank() / F.dense_rank() with .over(...), not {item}")
+        if len(item.partition_by) + len(item.order_by) > MAX_WINDOW_KEYS:
+            raise ValueError(f"{item}: partition and order columns together are at most {MAX_WINDOW_KEYS} (HS_MAX_COLS)")
+
+
+MAX_WINDOW_KEYS = 12  # include/hipspark.h HS_MAX_COLS
 
 
 def check_sort_keys(keys: list) -> None:

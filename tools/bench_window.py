@@ -1,0 +1,124 @@
+"""Window ranking microbenchmark (hs_window), HIP events on the launch stream, median and min - max of --reps runs after
+warm-up.  Every case is timed next to hs_order_by without a limit over the same keys, the two alternating run by run:
+the sort is shared, so that is the floor, and hs_window adds the heads pass, the three scan passes and one 4-byte scatter
+per function:
+  (a) PARTITION BY an INTEGER with about --partitions values ORDER BY an INTEGER, ROW_NUMBER only (one key word)
+  (b) the same, ROW_NUMBER + RANK + DENSE_RANK
+  (c) PARTITION BY a TIMESTAMP ORDER BY an INTEGER, all three (two key words: the words are formed again)
+  (d) no PARTITION BY, ORDER BY an INTEGER, all three
+Both calls read a few words back between their steps, so their times include those host round trips.  --case x --reps 3
+under a kernel trace gives the per-kernel split.
+Usage: python tools/bench_window.py [--rows 64M] [--partitions 1M] [--reps 20] [--case abcd] [--out profiles/r15_window.txt]"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import socket
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import torch  # noqa: E402
+
+from minispark_amd import hipspark as hs  # noqa: E402
+
+
+def timed_pair(first, second, reps):
+    """Both functions alternating, run by run -> (median, min, max) ms of each."""
+    for _ in range(2):
+        first()
+        second()
+    torch.cuda.synchronize()
+    times = ([], [])
+    for _ in range(reps):
+        for fn, ts in zip((first, second), times):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+    return [(sorted(ts)[len(ts) // 2], min(ts), max(ts)) for ts in times]
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=float, default=64 * 2**20)
+    ap.add_argument("--partitions", type=float, default=2**20)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--case", default="abcd")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    n, d = int(a.rows), int(a.partitions)
+    lib = hs.load_library()
+    g = torch.Generator(device="cuda")
+    g.manual_seed(15)
+    part = torch.randint(0, d, (n,), device="cuda", generator=g, dtype=torch.int64)
+    part32 = part.to(torch.int32)
+    order32 = torch.randint(0, 1000, (n,), device="cuda", generator=g, dtype=torch.int64).to(torch.int32)
+    stamps = part * 1_000_003 + 1_700_000_000
+    stream = torch.cuda.current_stream().cuda_stream
+    perm = torch.empty(n, dtype=torch.int64, device="cuda")
+    outs = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(3)]
+    ws = torch.empty(int(lib.hs_window_ws_bytes(n, 2, 3)) + 256, dtype=torch.uint8, device="cuda")
+    count = C.c_int64(0)
+    col = lambda kind, t: hs.hs_col(kind, -1, t.data_ptr(), None, None)  # noqa: E731
+    every = [hs.WIN_ROW_NUMBER, hs.WIN_RANK, hs.WIN_DENSE_RANK]
+    cases = {"a": ("(INTEGER | INTEGER), ROW_NUMBER", [col(hs.I32, part32), col(hs.I32, order32)], 1, every[:1]),
+             "b": ("(INTEGER | INTEGER), all three", [col(hs.I32, part32), col(hs.I32, order32)], 1, every),
+             "c": ("(TIMESTAMP | INTEGER), all three", [col(hs.I64, stamps), col(hs.I32, order32)], 1, every),
+             "d": ("( | INTEGER), all three", [col(hs.I32, order32)], 0, every)}
+
+    def window(cols, n_part, funcs):
+        arr = (hs.hs_col * len(cols))(*cols)
+        asc = (C.c_int32 * len(cols))(*[0] * len(cols))
+        kinds = (C.c_int32 * len(funcs))(*funcs)
+        ptrs = (C.c_void_p * len(funcs))(*[o.data_ptr() for o in outs[:len(funcs)]])
+
+        def run():
+            hs.check(lib.hs_window(stream, arr, asc, n_part, len(cols), n, kinds, len(funcs), ptrs, ws.data_ptr(), None), "hs_window")
+        return run
+
+    def order_by(cols):
+        arr = (hs.hs_col * len(cols))(*cols)
+        asc = (C.c_int32 * len(cols))(*[0] * len(cols))
+
+        def run():
+            hs.check(lib.hs_order_by(stream, arr, asc, len(cols), n, None, -1, perm.data_ptr(), C.byref(count), ws.data_ptr(),
+                                     None), "hs_order_by")
+        return run
+
+    lines = [f"tools/bench_window.py --rows {n} --partitions {d} --reps {a.reps}   [{torch.cuda.get_device_name(0)}, host "
+             f"{socket.gethostname()}, torch {torch.__version__}]",
+             "events on the launch stream, the two calls alternating; median (min - max) ms; ratio = hs_window / hs_order_by"]
+    for tag in a.case:
+        what, cols, n_part, funcs = cases[tag]
+        (mw, lw, hw), (ms, lo, hi) = timed_pair(window(cols, n_part, funcs), order_by(cols), a.reps)
+        lines.append(f"({tag}) hs_window    {what:34s} {mw:9.3f} ms ({lw:.3f} - {hw:.3f})   {n / mw / 1e6:8.2f} G rows/s")
+        lines.append(f"({tag}) hs_order_by  {'the same keys, no limit':34s} {ms:9.3f} ms ({lo:.3f} - {hi:.3f})   "
+                     f"{n / ms / 1e6:8.2f} G rows/s   ratio {mw / ms:.2f}   + {mw - ms:.3f} ms")
+    if "b" in a.case:  # checked against the sort's own row list: row_number restarts with the partition, rank <= row_number
+        what, cols, n_part, funcs = cases["b"]
+        window(cols, n_part, funcs)()
+        order_by(cols)()
+        torch.cuda.synchronize()
+        rn, rk, dr = (o[perm].to(torch.int64) for o in outs)
+        p, o = part32[perm], order32[perm]
+        new_part = torch.ones(n, dtype=torch.bool, device="cuda")
+        new_part[1:] = p[1:] != p[:-1]
+        new_peer = new_part.clone()
+        new_peer[1:] |= o[1:] != o[:-1]
+        ok = (bool((rn[new_part] == 1).all()) and bool((rn[1:][~new_part[1:]] == rn[:-1][~new_part[1:]] + 1).all())
+              and bool((rk[new_peer] == rn[new_peer]).all()) and bool((rk[1:][~new_peer[1:]] == rk[:-1][~new_peer[1:]]).all())
+              and bool((dr[new_part] == 1).all())
+              and bool((dr[1:][~new_part[1:]] == dr[:-1][~new_part[1:]] + new_peer[1:][~new_part[1:]].to(torch.int64)).all()))
+        lines.append(f"check (b): along the sorted rows row_number counts up inside a partition, rank is the row_number of the "
+                     f"first peer, dense_rank steps by one per group of peers: {ok}")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        Path(a.out).write_text(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
