@@ -66,6 +66,17 @@ extern "C" {
 #define HS_F64 3 /* in-flight FLOAT (the reference computes in Python floats) */
 #define HS_STR 4 /* STRING: lens[nrows] + payload bytes + (offs[nrows+1] unless fixed_len >= 0) */
 #define HS_U8 5  /* boolean mask */
+/* Narrow forms of a resident numeric column (hs_narrow_for16 / hs_narrow_lut8 make them once, at table open): the fused
+ * scan moves 2 / 1 bytes per row instead of 8 / 4 and decodes in registers.  Both decode EXACTLY to the stored value.
+ *   HS_I64_FOR16  `data` = u16 deltas, `offs` = two device int64 {base, scale}: value = base + (int64)delta * scale
+ *   HS_F32_LUT8   `data` = code bytes, `offs` = device float table of the column's distinct BIT PATTERNS (-0.0 and +0.0,
+ *                 two NaN payloads are different entries), `fixed_len` = its entry count (1..256): value = table[code]
+ * `data` is readable up to 3 rows past the last one (the last row quad is loaded whole), like every preloaded column.
+ * Accepted ONLY as argument / WHERE columns (a bare HS_OP_LD of a preloaded slot < HS_FUSED_COLS) of hs_agg_partial,
+ * hs_agg_partial_slab and hs_agg_scalar - never as the key or unit column.  Every other entry point that takes hs_col
+ * (the shared tier, hs_agg_rows, hs_eval, the radix tier, joins, row operators, ...) refuses them with HS_E_ARG. */
+#define HS_I64_FOR16 6
+#define HS_F32_LUT8 7
 /* Virtual columns of the fused join + aggregate (hs_agg_shared_join8, round 3): `data` = the probe side's INTEGER key
  * column; the value of row i is looked up in the hs_join8 byte table while the aggregate scans - never stored. */
 #define HS_JOIN8_CODE 16 /* the table byte of the row's key: the build side's 1-byte payload (a dictionary code) */
@@ -765,6 +776,26 @@ int hs_dict_assign(void* stream, const hs_col* col, int64_t nrows, int32_t cap, 
 int hs_dict_combine(void* stream, int32_t n_parts, const uint8_t* const* codes, const int32_t* strides, int64_t nrows,
                     uint8_t* out_codes);
 
+/* Narrow forms of a resident numeric column (HS_I64_FOR16 / HS_F32_LUT8 above), made once at table open.
+ * Both calls end on a small read-back and synchronise the stream: table-open work, not part of a query.  "Not eligible"
+ * is a normal answer (HS_OK with *eligible / *n_entries = 0, outputs then hold nothing of value), never an error.  No
+ * verifying re-decode pass is run: exactness follows from the construction.  nrows == 0: not eligible, no launch.
+ *   hs_narrow_for16  TIMESTAMP / int64 column -> u16 deltas.  Pass 1: min, max and the gcd of (v - v[0]) over the column;
+ *                    scale = that gcd (1 for a one-valued column), base = min.  Eligible when max - min - computed in 64
+ *                    unsigned bits, never wrapped - is at most INT64_MAX and (max - min) / scale <= 65535.  Pass 2 writes
+ *                    out_codes[i] = (v[i] - base) / scale and out_params (DEVICE int64[2]) = {base, scale}.
+ *   hs_narrow_lut8   FLOAT column -> code bytes.  Pass 1 collects the distinct BIT PATTERNS (per-workgroup LDS sets merged
+ *                    into one small global set) and gives up as soon as a 257th appears.  The host sorts the patterns as
+ *                    unsigned 32-bit words - codes do not depend on row order - and uploads them to out_lut (DEVICE
+ *                    float[256]); pass 2 writes out_codes[i] = index of v[i]'s pattern.  *n_entries = table entries.
+ * out_codes: nrows elements, 8-byte aligned, and - like every column the fused scan preloads - followed by at least 3
+ * readable elements.  ws: hs_narrow_ws_bytes() bytes, 16-byte aligned. */
+size_t hs_narrow_ws_bytes(void);
+int hs_narrow_for16(void* stream, const int64_t* data, int64_t nrows, uint16_t* out_codes, int64_t* out_params, void* ws,
+                    int32_t* eligible);
+int hs_narrow_lut8(void* stream, const float* data, int64_t nrows, uint8_t* out_codes, float* out_lut, void* ws,
+                   int32_t* n_entries);
+
 /* Composite GROUP BY keys: the key parts of every row as ONE run of `width` bytes, which the aggregation
  * tiers take as a STRING column of that fixed length.
  *   hs_key_pack    out[r * width ...] = the bytes of parts[0], parts[1], ... of row r, each at its fixed offset (the sum of
@@ -944,6 +975,11 @@ int hs_jit_compile_check_scalar(const hs_col* cols, int32_t n_cols, const hs_pro
  * up to 3 rows past nrows of every column it loads - buffers carry that slack). */
 int hs_jit_compile_check_eval(const hs_col* cols, int32_t n_cols, const hs_program* prog, const int32_t* out_kinds,
                               int32_t n_outs, const char* arch, int64_t* code_bytes, char* src_out, int64_t src_cap);
+/* The key the compiled-program cache files a private-table launch (256 lanes; key_col = -1: a keyless launch) of these
+ * columns and this program under, as text (needs no GPU).  Column kinds - narrow ones and the table size of a
+ * HS_F32_LUT8 column included - are part of it; literal values are not. */
+int hs_jit_program_key(const hs_col* cols, int32_t n_cols, int32_t key_col, const hs_program* prog, const hs_agg_spec* spec,
+                       char* out, int64_t cap);
 
 /* =================================================================================================
  * Stage-level ABI (csrc/hs_engine.hip): a GROUP BY query over one BlockFile table, end to end, without Python.

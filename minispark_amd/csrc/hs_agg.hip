@@ -1171,6 +1171,35 @@ static int fill_cols(HsCols& dst, const hs_col* cols, int32_t n) {
     return HS_OK;
 }
 
+// Narrow columns (include/hipspark.h) of a private-table / keyless scan: argument slots only - preloaded, never the key,
+// with their decode parameters, and read by nothing but HS_OP_LD.
+static int check_narrow_cols(const char* who, const hs_col* cols, int32_t n_cols, int32_t key_col, const hs_program* prog) {
+    bool any = false;
+    for (int i = 0; i < n_cols; ++i) {
+        if (!hs_kind_narrow(cols[i].kind)) continue;
+        any = true;
+        if (i == key_col || i >= HS_FUSED_COLS || !cols[i].data || !cols[i].offs ||
+            (cols[i].kind == HS_F32_LUT8 && (cols[i].fixed_len < 1 || cols[i].fixed_len > 256))) {
+            hs_set_error("%s: narrow column %d must be a preloaded argument slot (< %d, not the key) with its decode "
+                         "parameters in offs (HS_F32_LUT8: 1..256 table entries in fixed_len)", who, i, HS_FUSED_COLS);
+            return HS_E_ARG;
+        }
+    }
+    if (!any) return HS_OK;
+    for (uint32_t pc = 0; pc < prog->n_ins && pc < HS_MAX_INS; ++pc) {
+        const uint64_t w = prog->ins[pc];
+        const int op = (int)(w & 0xff);
+        const int a = (int)((w >> 16) & 0xffff), b = (int)((w >> 32) & 0xffff);
+        const bool names_a = op == HS_OP_STRCMP_LIT || op == HS_OP_STRCMP_COL || op == HS_OP_LIKE || op == HS_OP_DICTBIT;
+        if ((names_a && a < n_cols && hs_kind_narrow(cols[a].kind)) ||
+            (op == HS_OP_STRCMP_COL && b < n_cols && hs_kind_narrow(cols[b].kind))) {
+            hs_set_error("%s: a narrow column is read by HS_OP_LD only", who);
+            return HS_E_ARG;
+        }
+    }
+    return HS_OK;
+}
+
 static int program_depth(const hs_program* p) {
     int d = 0;
     for (uint32_t i = 0; i < p->n_ins; ++i) {
@@ -1427,6 +1456,8 @@ static int agg_partial_impl(void* stream, const hs_col* cols, int32_t n_cols, in
             return HS_E_ARG;
         }
     }
+    rc = check_narrow_cols("hs_agg_partial", cols, n_cols, key_col, prog);
+    if (rc) return rc;
     A.prog = *prog;
     A.spec = *spec;
     A.key_col = key_col;
@@ -1657,6 +1688,8 @@ extern "C" int hs_agg_scalar(void* stream, const hs_col* cols, int32_t n_cols, c
             return HS_E_ARG;
         }
     }
+    rc = check_narrow_cols("hs_agg_scalar", cols, n_cols, -1, prog);
+    if (rc) return rc;
     const int depth = program_depth(prog);
     if (depth > HS_MAX_STACK) {
         hs_set_error("hs_agg_scalar: expression stack depth %d > %d", depth, HS_MAX_STACK);
@@ -1750,6 +1783,7 @@ extern "C" int hs_agg_merge(void* stream, const hs_col* key, const hs_col* acc_c
         hs_set_error("hs_agg_merge: bad arguments");
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow("hs_agg_merge", key, 1) || hs_refuse_narrow("hs_agg_merge", acc_cols, spec->n_acc)) return HS_E_ARG;
     if (order && (n_order < 1 || n_order > 65536)) {
         hs_set_error("hs_agg_merge: n_order=%lld out of range", (long long)n_order);
         return HS_E_ARG;
@@ -2091,6 +2125,7 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
         hs_set_error("hs_agg_shared: null or out-of-range argument");
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow("hs_agg_shared", cols, n_cols)) return HS_E_ARG;
     if (prog->n_ins > HS_MAX_INS || prog->n_lit > HS_MAX_LIT) {
         hs_set_error("hs_agg_shared: program too long");
         return HS_E_LIMIT;

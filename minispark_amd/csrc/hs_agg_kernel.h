@@ -395,6 +395,27 @@ __device__ __forceinline__ void hs_load_quad(const hs_col& c, int64_t row0, uint
             cell[3] = v >> 24;
             break;
         }
+        // Narrow columns (include/hipspark.h): the quad's deltas / codes in one load, the decode parameters through
+        // global loads.  The interpreter only has to be right; compiled programs keep the parameters in LDS (hs_jit.hip).
+        case HS_I64_FOR16: {
+            const uint2 v = *reinterpret_cast<const uint2*>((const uint16_t*)c.data + row0);
+            const uint64_t b = (uint64_t)c.offs[0], s = (uint64_t)c.offs[1];
+            cell[0] = b + (uint64_t)(v.x & 0xffff) * s;
+            cell[1] = b + (uint64_t)(v.x >> 16) * s;
+            cell[2] = b + (uint64_t)(v.y & 0xffff) * s;
+            cell[3] = b + (uint64_t)(v.y >> 16) * s;
+            break;
+        }
+        case HS_F32_LUT8: {
+            const uint32_t v = *reinterpret_cast<const uint32_t*>((const uint8_t*)c.data + row0);
+            const float* lut = (const float*)c.offs;
+            const uint32_t last = (uint32_t)c.fixed_len - 1;  // (the bytes past the last row may hold anything)
+            cell[0] = hs_d2u((double)lut[min(v & 0xff, last)]);
+            cell[1] = hs_d2u((double)lut[min((v >> 8) & 0xff, last)]);
+            cell[2] = hs_d2u((double)lut[min((v >> 16) & 0xff, last)]);
+            cell[3] = hs_d2u((double)lut[min(v >> 24, last)]);
+            break;
+        }
         case HS_STR:
             // only the GROUP BY column is preloaded, and only when it packs with a power-of-two width
             if (c.fixed_len == 1) hs_load_packed_quad<1>(c, row0, cell);
@@ -485,6 +506,8 @@ struct InterpProg {
     static constexpr bool TWO_STAGE = false;  // (compiled programs with the join's probe inside load in two stages)
     static constexpr bool STATIC_SPEC = false;  // (compiled programs know their aggregates' kinds at compile time)
     static constexpr int NA = 0;
+    static constexpr bool HAS_TABLES = false;  // (compiled programs with narrow columns keep decode tables in LDS)
+    struct Tables {};
     static __device__ constexpr uint32_t acc_op(int) { return 0; }
     static __device__ constexpr bool acc_int(int) { return false; }
     struct Cells {
@@ -654,6 +677,8 @@ __device__ __forceinline__ void hs_agg_main_body(const AggMainArgs& A) {
     int64_t base = c0 + (int64_t)tid * HS_V;
     typename Prog::Cells cur, nxt;
     if (base < c1) Prog::load(A, base, nxt);
+    typename Prog::Tables tv;  // decode-table entries of narrow columns, on their way behind the first quad (compiled programs)
+    if constexpr (Prog::HAS_TABLES) Prog::load_tables(A, tid, tv);
     const HsSpecBits sb = hs_spec_bits(A.spec);
 
     // a run that has already overflowed a dictionary is going to be repeated with larger tables: later rounds of
@@ -671,6 +696,7 @@ __device__ __forceinline__ void hs_agg_main_body(const AggMainArgs& A) {
     for (int i = tid; i < 256; i += nthr) s_dmap[i] = 0xff;
     for (int cellid = 0; cellid < GC * NA; ++cellid)
         tbl[(uint32_t)cellid * nthr + tid] = hs_acc_identity(hs_spec_op(sb, cellid % NA), hs_spec_int(sb, cellid % NA));
+    if constexpr (Prog::HAS_TABLES) Prog::store_tables(tv, tid);  // decode tables of narrow columns (static LDS)
     __syncthreads();
     HS_SCAN_STAMP(1);
     if (s_overflowed) {
@@ -862,6 +888,8 @@ __device__ __forceinline__ void hs_agg_scalar_body(const AggMainArgs& A) {
     int64_t base = c0 + (int64_t)tid * HS_V;
     typename Prog::Cells cur, nxt;
     if (base < c1) Prog::load(A, base, nxt);
+    typename Prog::Tables tv;
+    if constexpr (Prog::HAS_TABLES) Prog::load_tables(A, tid, tv);
     const HsSpecBits sb = hs_spec_bits(A.spec);
     // kind of accumulator a: a compile-time constant in compiled programs, two scalars otherwise
     auto op_of = [&](int a) -> uint32_t { return Prog::STATIC_SPEC ? Prog::acc_op(a) : hs_spec_op(sb, (uint32_t)a); };
@@ -873,6 +901,10 @@ __device__ __forceinline__ void hs_agg_scalar_body(const AggMainArgs& A) {
     ctx.rows = 0;
 #pragma unroll
     for (int a = 0; a < HS_MAX_ACC; ++a) ctx.acc[a] = a < CNA ? hs_acc_identity(op_of(a), int_of(a)) : 0ull;
+    if constexpr (Prog::HAS_TABLES) {  // decode tables of narrow columns (static LDS)
+        Prog::store_tables(tv, tid);
+        __syncthreads();
+    }
     HS_SCAN_STAMP(2);
 
     // software pipeline: the loads of step i+1 are in flight while step i is evaluated

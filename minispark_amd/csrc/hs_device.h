@@ -95,9 +95,29 @@ __device__ __forceinline__ uint64_t hs_load_cell(const hs_col& c, int64_t row) {
         case HS_I64: return (uint64_t)((const int64_t*)c.data)[row];
         case HS_F64: return hs_d2u(((const double*)c.data)[row]);
         case HS_U8: return (uint64_t)((const uint8_t*)c.data)[row];
+        case HS_I64_FOR16:  // base + delta * scale, exact (unsigned arithmetic: no signed overflow on the way)
+            return (uint64_t)c.offs[0] + (uint64_t)((const uint16_t*)c.data)[row] * (uint64_t)c.offs[1];
+        case HS_F32_LUT8: return hs_d2u((double)((const float*)c.offs)[((const uint8_t*)c.data)[row]]);
         default: return 0;
     }
 }
+
+// Narrow column kinds (include/hipspark.h): only the private-table and keyless fused scans decode them.
+__host__ __device__ __forceinline__ bool hs_kind_narrow(int32_t kind) { return kind == HS_I64_FOR16 || kind == HS_F32_LUT8; }
+#ifndef HS_JIT_BUILD
+// every other entry point starts with this: true (and the error text) when one of `cols` is a narrow column
+void hs_set_error(const char* fmt, ...);
+static inline bool hs_refuse_narrow(const char* who, const hs_col* cols, int64_t n) {
+    for (int64_t i = 0; cols && i < n; ++i) {
+        if (hs_kind_narrow(cols[i].kind)) {
+            hs_set_error("%s: column %d is a narrow column (HS_I64_FOR16 / HS_F32_LUT8): only hs_agg_partial, "
+                         "hs_agg_partial_slab and hs_agg_scalar read them", who, (int)i);
+            return true;
+        }
+    }
+    return false;
+}
+#endif
 
 // ---- strings -------------------------------------------------------------------------------------
 struct HsStr {

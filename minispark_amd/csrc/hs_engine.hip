@@ -328,6 +328,7 @@ extern "C" int hs_table_attach(hs_engine* e, int32_t n_cols, const hs_col* cols,
         hs_set_error("hs_table_attach: bad arguments");
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow("hs_table_attach", cols, n_cols)) return HS_E_ARG;  // (so no stage ever sees one)
     hs_table* t = new hs_table();
     t->engine = e;
     t->attached = true;

@@ -10,6 +10,9 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "hs_agg_kernel.h"
 
 thread_local char g_hs_err[256] = {0};
@@ -832,6 +835,7 @@ extern "C" int hs_eval(void* stream, const hs_col* cols, int32_t n_cols, const h
         hs_set_error("hs_eval: program too long");
         return HS_E_LIMIT;
     }
+    if (hs_refuse_narrow("hs_eval", cols, n_cols)) return HS_E_ARG;
     if (nrows == 0) return HS_OK;
     EvalArgs A;
     A.cols.n = n_cols;
@@ -1031,6 +1035,7 @@ extern "C" int hs_partition_ids(void* stream, const hs_col* key, const int64_t* 
         hs_set_error("hs_partition_ids: bad arguments");
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow("hs_partition_ids", key, 1)) return HS_E_ARG;
     if (key->kind == HS_I32 && !sel && n_parts <= 127 && (((uintptr_t)key->data) & 15) == 0 && (((uintptr_t)part) & 3) == 0) {
         hipLaunchKernelGGL(k_partition_ids_i32, dim3(grid_for((nrows + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream,
                            (const int32_t*)key->data, nrows, n_parts, part);
@@ -1451,6 +1456,7 @@ static int group_build(void* stream, const hs_col* left_key, const int64_t* sel,
         hs_set_error("hs_join_build: bad arguments (table_cap must be a power of two)");
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow("hs_join_build / hs_group_build", left_key, 1)) return HS_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     int64_t* slot_of_row = (int64_t*)ws;
     int64_t* slot_count = slot_of_row + n_left;
@@ -1587,6 +1593,7 @@ extern "C" int hs_group_fold(void* stream, const hs_col* val_cols, const hs_agg_
         hs_set_error("hs_group_fold: bad arguments");
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow("hs_group_fold", val_cols, spec->n_acc)) return HS_E_ARG;
     GroupFoldArgs A;
     for (int a = 0; a < HS_MAX_ACC; ++a)
         A.vals[a] = a < spec->n_acc ? val_cols[a] : hs_col{HS_U8, -1, nullptr, nullptr, nullptr};
@@ -1648,6 +1655,7 @@ static int fill_probe(JoinProbeArgs& A, const hs_col* lk, const hs_col* rk, int6
         hs_set_error("%s: bad arguments", name);
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow(name, lk, 1) || hs_refuse_narrow(name, rk, 1)) return HS_E_ARG;
     const bool ls = lk->kind == HS_STR, rs = rk->kind == HS_STR;
     if (ls != rs) {
         hs_set_error("%s: join keys must both be strings or both be numeric", name);
@@ -1813,5 +1821,285 @@ extern "C" int hs_gen_lineitem(void* stream, uint64_t seed, int64_t row0, int64_
               shipmode_code};
     hipLaunchKernelGGL(k_gen_lineitem, dim3(grid_for(nrows, 1024)), dim3(256), 0, (hipStream_t)stream, A);
     HS_CHECK_LAUNCH("hs_gen_lineitem");
+    return HS_OK;
+}
+
+// ==================================================================================================
+// Narrow forms of resident numeric columns (include/hipspark.h HS_I64_FOR16 / HS_F32_LUT8)
+//
+// Made ONCE per table column, at table open; the fused scan then moves 2 / 1 bytes per row instead of 8 / 4.  Both
+// calls end on a small read-back (the host decides eligibility), so they are table-open work, never part of a query's
+// recorded launches.  "Not eligible" is an answer, not an error.  No verifying re-decode pass: a delta is the exact
+// quotient of a difference the scale divides, a code is the index of the row's own bit pattern.
+// ==================================================================================================
+static constexpr int NARROW_BLOCKS = 2048;
+static constexpr int LUT_SLOTS = 1024;           // open-addressing set of bit patterns: 4 x the 256 a code byte names
+static constexpr uint64_t LUT_EMPTY = ~0ull;     // (a pattern occupies the low word only)
+extern "C" size_t hs_narrow_ws_bytes(void) { return 64 * 1024; }
+
+__device__ __forceinline__ uint64_t hs_gcd_u64(uint64_t a, uint64_t b) {
+    while (b) {
+        const uint64_t t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+// pass 1 of FoR16: per workgroup {min, max, gcd of |v - v[0]|} (gcd is associative: the host folds the workgroups' rows)
+__global__ void __launch_bounds__(256) k_for16_stats(const int64_t* __restrict__ v, int64_t n, uint64_t* __restrict__ out) {
+    __shared__ int64_t s_mn[256], s_mx[256];
+    __shared__ uint64_t s_g[256];
+    const int64_t first = v[0];
+    int64_t mn = first, mx = first;
+    uint64_t g = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t x = v[i];
+        mn = x < mn ? x : mn;
+        mx = x > mx ? x : mx;
+        const uint64_t d = x >= first ? (uint64_t)x - (uint64_t)first : (uint64_t)first - (uint64_t)x;  // no signed wrap
+        if (d != 0 && (g == 0 || d % g != 0)) g = hs_gcd_u64(g, d);
+    }
+    s_mn[threadIdx.x] = mn;
+    s_mx[threadIdx.x] = mx;
+    s_g[threadIdx.x] = g;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            const int o = threadIdx.x + w;
+            s_mn[threadIdx.x] = s_mn[o] < s_mn[threadIdx.x] ? s_mn[o] : s_mn[threadIdx.x];
+            s_mx[threadIdx.x] = s_mx[o] > s_mx[threadIdx.x] ? s_mx[o] : s_mx[threadIdx.x];
+            s_g[threadIdx.x] = hs_gcd_u64(s_g[threadIdx.x], s_g[o]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[blockIdx.x * 3 + 0] = (uint64_t)s_mn[0];
+        out[blockIdx.x * 3 + 1] = (uint64_t)s_mx[0];
+        out[blockIdx.x * 3 + 2] = s_g[0];
+    }
+}
+
+// pass 2 of FoR16: delta = (v - base) / scale, four rows per lane (one 8-byte store for a whole quad)
+__global__ void __launch_bounds__(256) k_for16_encode(const int64_t* __restrict__ v, int64_t n, int64_t base, uint64_t scale,
+                                                      uint16_t* __restrict__ out) {
+    const int64_t nquads = (n + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nquads; q += (int64_t)gridDim.x * 256) {
+        const int64_t r0 = q << 2;
+        uint32_t d[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (r0 + j < n) {
+                const uint64_t diff = (uint64_t)v[r0 + j] - (uint64_t)base;
+                d[j] = (uint32_t)(scale == 1 ? diff : diff / scale);
+            }
+        }
+        if (r0 + 4 <= n) {
+            *reinterpret_cast<uint2*>(out + r0) = make_uint2(d[0] | (d[1] << 16), d[2] | (d[3] << 16));
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (r0 + j < n) out[r0 + j] = (uint16_t)d[j];
+        }
+    }
+}
+
+extern "C" int hs_narrow_for16(void* stream, const int64_t* data, int64_t nrows, uint16_t* out_codes, int64_t* out_params,
+                               void* ws, int32_t* eligible) {
+    if (!eligible || nrows < 0 || (nrows > 0 && (!data || !out_codes || !out_params || !ws)) || ((uintptr_t)out_codes & 7)) {
+        hs_set_error("hs_narrow_for16: bad arguments (non-null buffers, codes 8-byte aligned)");
+        return HS_E_ARG;
+    }
+    *eligible = 0;
+    if (nrows == 0) return HS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = grid_for(nrows, 256 * 16) < (unsigned)NARROW_BLOCKS ? grid_for(nrows, 256 * 16) : (unsigned)NARROW_BLOCKS;
+    hipLaunchKernelGGL(k_for16_stats, dim3(blocks), dim3(256), 0, s, data, nrows, (uint64_t*)ws);
+    HS_CHECK_LAUNCH("hs_narrow_for16");
+    std::vector<uint64_t> rows((size_t)blocks * 3);
+    if (hipMemcpyAsync(rows.data(), ws, rows.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        hs_set_error("hs_narrow_for16: reading the column statistics back failed");
+        return HS_E_LAUNCH;
+    }
+    int64_t mn = (int64_t)rows[0], mx = (int64_t)rows[1];
+    uint64_t g = 0;
+    for (unsigned b = 0; b < blocks; ++b) {
+        const int64_t bmn = (int64_t)rows[b * 3], bmx = (int64_t)rows[b * 3 + 1];
+        mn = bmn < mn ? bmn : mn;
+        mx = bmx > mx ? bmx : mx;
+        uint64_t x = g, y = rows[b * 3 + 2];
+        while (y) {
+            const uint64_t t = x % y;
+            x = y;
+            y = t;
+        }
+        g = x;
+    }
+    const uint64_t range = (uint64_t)mx - (uint64_t)mn;  // exact in 64 unsigned bits, whatever the signs
+    const uint64_t scale = g == 0 ? 1 : g;               // one-valued column: gcd 0
+    // a range beyond INT64_MAX (say INT64_MIN next to INT64_MAX) is refused, not wrapped: base + delta * scale stays
+    // inside int64 arithmetic on the way
+    if (range > (uint64_t)INT64_MAX || range / scale > 65535) return HS_OK;
+    const int64_t params[2] = {mn, (int64_t)scale};
+    if (hipMemcpyAsync(out_params, params, sizeof(params), hipMemcpyHostToDevice, s) != hipSuccess) {
+        hs_set_error("hs_narrow_for16: uploading the parameters failed");
+        return HS_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_for16_encode, dim3(grid_for((nrows + 3) / 4, 256 * 4)), dim3(256), 0, s, data, nrows, mn, scale, out_codes);
+    HS_CHECK_LAUNCH("hs_narrow_for16");
+    if (hipStreamSynchronize(s) != hipSuccess) {  // (`params` lives on this stack frame)
+        hs_set_error("hs_narrow_for16: encoding failed");
+        return HS_E_LAUNCH;
+    }
+    *eligible = 1;
+    return HS_OK;
+}
+
+__device__ __forceinline__ uint32_t hs_lut_hash(uint32_t bits) { return (bits * 0x9E3779B1u) >> 22; }  // 10 bits = LUT_SLOTS
+
+// the pattern's slot in a set of LUT_SLOTS words (LDS or global); `added` = this call put it there.  -1 = the set is full
+// (cannot happen below 257 patterns; a workgroup that is past them has stopped inserting)
+__device__ __forceinline__ int hs_lut_insert(uint64_t* set, uint32_t bits, bool& added) {
+    added = false;
+    uint32_t h = hs_lut_hash(bits);
+    for (int probe = 0; probe < LUT_SLOTS; ++probe, h = (h + 1) & (LUT_SLOTS - 1)) {
+        uint64_t cur = __hip_atomic_load(&set[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == LUT_EMPTY) {
+            cur = atomicCAS((unsigned long long*)&set[h], (unsigned long long)LUT_EMPTY, (unsigned long long)bits);
+            if (cur == LUT_EMPTY) {
+                added = true;
+                return (int)h;
+            }
+        }
+        if (cur == (uint64_t)bits) return (int)h;
+    }
+    return -1;
+}
+
+// pass 1 of LUT8: distinct BIT PATTERNS of the column.  state[0] = patterns in the global set, state[1] = "too many";
+// gset = LUT_SLOTS words.  A workgroup collects in LDS and merges once; it stops reading as soon as it holds a 257th
+// pattern itself, and does not start when another one already said "too many".
+__global__ void __launch_bounds__(256) k_lut8_collect(const uint32_t* __restrict__ v, int64_t n, uint32_t* state, uint64_t* gset) {
+    __shared__ uint64_t s_set[LUT_SLOTS];
+    __shared__ uint32_t s_count, s_stop;
+    for (int i = threadIdx.x; i < LUT_SLOTS; i += 256) s_set[i] = LUT_EMPTY;
+    if (threadIdx.x == 0) {
+        s_count = 0;
+        s_stop = __hip_atomic_load(&state[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (s_stop) return;
+    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < n; i0 += (int64_t)gridDim.x * 256) {  // workgroup-uniform trip count
+        const int64_t i = i0 + threadIdx.x;
+        if (i < n) {
+            bool added;
+            const int slot = hs_lut_insert(s_set, v[i], added);
+            if (added) atomicAdd(&s_count, 1u);
+            if (slot < 0) atomicAdd(&s_count, 257u);
+        }
+        __syncthreads();
+        if (s_count > 256) break;  // (read between two barriers: the same answer for every lane)
+        __syncthreads();
+    }
+    if (s_count > 256) {
+        if (threadIdx.x == 0) atomicOr(&state[1], 1u);
+        return;
+    }
+    for (int i = threadIdx.x; i < LUT_SLOTS; i += 256) {
+        const uint64_t w = s_set[i];
+        if (w == LUT_EMPTY) continue;
+        bool added;
+        const int slot = hs_lut_insert(gset, (uint32_t)w, added);
+        if (slot < 0 || (added && atomicAdd(&state[0], 1u) + 1 > 256)) atomicOr(&state[1], 1u);
+    }
+}
+
+// pass 2 of LUT8: the row's pattern -> its code through the same set (held in LDS with the slot's code beside it)
+__global__ void __launch_bounds__(256) k_lut8_encode(const uint32_t* __restrict__ v, int64_t n, const uint64_t* __restrict__ gset,
+                                                     const uint8_t* __restrict__ slot_code, uint8_t* __restrict__ out) {
+    __shared__ uint32_t s_key[LUT_SLOTS];
+    __shared__ uint8_t s_used[LUT_SLOTS], s_code[LUT_SLOTS];
+    for (int i = threadIdx.x; i < LUT_SLOTS; i += 256) {
+        const uint64_t w = gset[i];
+        s_key[i] = (uint32_t)w;
+        s_used[i] = w != LUT_EMPTY;
+        s_code[i] = slot_code[i];
+    }
+    __syncthreads();
+    const int64_t nquads = (n + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nquads; q += (int64_t)gridDim.x * 256) {
+        const int64_t r0 = q << 2;
+        uint32_t c[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (r0 + j < n) {
+                const uint32_t bits = v[r0 + j];
+                uint32_t h = hs_lut_hash(bits);
+                for (int probe = 0; probe < LUT_SLOTS && s_used[h] && s_key[h] != bits; ++probe) h = (h + 1) & (LUT_SLOTS - 1);
+                c[j] = s_code[h];
+            }
+        }
+        if (r0 + 4 <= n) {
+            *reinterpret_cast<uint32_t*>(out + r0) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (r0 + j < n) out[r0 + j] = (uint8_t)c[j];
+        }
+    }
+}
+
+extern "C" int hs_narrow_lut8(void* stream, const float* data, int64_t nrows, uint8_t* out_codes, float* out_lut, void* ws,
+                              int32_t* n_entries) {
+    if (!n_entries || nrows < 0 || (nrows > 0 && (!data || !out_codes || !out_lut || !ws)) || ((uintptr_t)out_codes & 3) ||
+        ((uintptr_t)ws & 15)) {
+        hs_set_error("hs_narrow_lut8: bad arguments (non-null buffers, codes 4-byte aligned, workspace 16-byte aligned)");
+        return HS_E_ARG;
+    }
+    *n_entries = 0;
+    if (nrows == 0) return HS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t* state = (uint32_t*)ws;                      // [0] patterns, [1] too many
+    uint64_t* gset = (uint64_t*)((char*)ws + 16);         // [LUT_SLOTS]
+    uint8_t* slot_code = (uint8_t*)ws + 16 + LUT_SLOTS * 8;  // [LUT_SLOTS]
+    if (hipMemsetAsync(state, 0, 16, s) != hipSuccess || hipMemsetAsync(gset, 0xff, LUT_SLOTS * 8, s) != hipSuccess) {
+        hs_set_error("hs_narrow_lut8: clearing the pattern set failed");
+        return HS_E_LAUNCH;
+    }
+    const unsigned blocks = grid_for(nrows, 256 * 16) < (unsigned)NARROW_BLOCKS ? grid_for(nrows, 256 * 16) : (unsigned)NARROW_BLOCKS;
+    hipLaunchKernelGGL(k_lut8_collect, dim3(blocks), dim3(256), 0, s, (const uint32_t*)data, nrows, state, gset);
+    HS_CHECK_LAUNCH("hs_narrow_lut8");
+    std::vector<uint64_t> host(2 + LUT_SLOTS);
+    if (hipMemcpyAsync(host.data(), ws, host.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        hs_set_error("hs_narrow_lut8: reading the pattern set back failed");
+        return HS_E_LAUNCH;
+    }
+    const uint32_t count = (uint32_t)host[0], too_many = (uint32_t)(host[0] >> 32);
+    if (too_many || count > 256 || count == 0) return HS_OK;
+    // codes are named by PATTERN, in ascending order of the 32 bits: they do not depend on row order
+    std::vector<uint32_t> patterns;
+    for (int i = 0; i < LUT_SLOTS; ++i)
+        if (host[2 + i] != LUT_EMPTY) patterns.push_back((uint32_t)host[2 + i]);
+    if (patterns.size() != count) {
+        hs_set_error("hs_narrow_lut8: the pattern set holds %zu entries, its counter says %u", patterns.size(), count);
+        return HS_E_LAUNCH;
+    }
+    std::sort(patterns.begin(), patterns.end());
+    std::vector<uint8_t> codes(LUT_SLOTS, 0);
+    for (int i = 0; i < LUT_SLOTS; ++i) {
+        if (host[2 + i] == LUT_EMPTY) continue;
+        codes[i] = (uint8_t)(std::lower_bound(patterns.begin(), patterns.end(), (uint32_t)host[2 + i]) - patterns.begin());
+    }
+    if (hipMemcpyAsync(slot_code, codes.data(), LUT_SLOTS, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(out_lut, patterns.data(), patterns.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
+        hs_set_error("hs_narrow_lut8: uploading the table failed");
+        return HS_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_lut8_encode, dim3(grid_for((nrows + 3) / 4, 256 * 4)), dim3(256), 0, s, (const uint32_t*)data, nrows,
+                       (const uint64_t*)gset, (const uint8_t*)slot_code, out_codes);
+    HS_CHECK_LAUNCH("hs_narrow_lut8");
+    if (hipStreamSynchronize(s) != hipSuccess) {  // (the host vectors above are the copies' sources)
+        hs_set_error("hs_narrow_lut8: encoding failed");
+        return HS_E_LAUNCH;
+    }
+    *n_entries = (int32_t)count;
     return HS_OK;
 }

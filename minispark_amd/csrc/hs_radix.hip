@@ -1375,6 +1375,7 @@ extern "C" int hs_group_radix_run(void* stream_, const hs_radix_plan* plan, cons
         hs_set_error("hs_group_radix_run: bad arguments");
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow("hs_group_radix_run", key, 1) || hs_refuse_narrow("hs_group_radix_run", val_cols, spec->n_acc)) return HS_E_ARG;
     const int64_t* f = plan->f;
     hipStream_t stream = (hipStream_t)stream_;
     uint8_t* ws = (uint8_t*)ws_;
@@ -2197,6 +2198,7 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
         hs_set_error("hs_order_by: more than %d keys", HS_MAX_COLS);
         return HS_E_LIMIT;
     }
+    if (hs_refuse_narrow("hs_order_by", keys, n_keys)) return HS_E_ARG;
     *out_count = 0;
     if (nrows == 0 || limit == 0) return HS_OK;
     for (int k = 0; k < n_keys; ++k)
@@ -2311,6 +2313,7 @@ extern "C" int hs_distinct(void* stream_, const hs_col* keys, int32_t n_keys, in
         hs_set_error("hs_distinct: more than %d columns", HS_MAX_COLS);
         return HS_E_LIMIT;
     }
+    if (hs_refuse_narrow("hs_distinct", keys, n_keys)) return HS_E_ARG;
     *out_count = 0;
     if (nrows == 0) return HS_OK;
     for (int k = 0; k < n_keys; ++k)
@@ -2449,6 +2452,7 @@ extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, 
         hs_set_error("hs_mark_first: more than %d columns", HS_MAX_COLS);
         return HS_E_LIMIT;
     }
+    if (hs_refuse_narrow("hs_mark_first", keys, n_keys)) return HS_E_ARG;
     if (nrows == 0) return HS_OK;
     for (int k = 0; k < n_keys; ++k)
         if (!ob_kind_ok(keys[k])) {
@@ -2733,6 +2737,7 @@ extern "C" int hs_window(void* stream_, const hs_col* keys, const int32_t* desce
         hs_set_error("hs_window: more than %d partition and order columns", HS_MAX_COLS);
         return HS_E_LIMIT;
     }
+    if (hs_refuse_narrow("hs_window", keys, n_keys)) return HS_E_ARG;
     if (n_funcs > HS_WIN_MAX_FUNCS) {
         hs_set_error("hs_window: more than %d functions in one call", HS_WIN_MAX_FUNCS);
         return HS_E_LIMIT;

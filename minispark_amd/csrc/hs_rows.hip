@@ -365,6 +365,7 @@ int rows_shape(const char* who, const hs_col* cols, int32_t n_cols, int32_t key_
         hs_set_error("%s: program too long", who);
         return HS_E_LIMIT;
     }
+    if (hs_refuse_narrow(who, cols, n_cols)) return HS_E_ARG;
     bool have_key = false;
     bool seen[HS_MAX_ACC] = {};
     uint32_t arg0 = 0;
@@ -794,6 +795,7 @@ extern "C" int hs_key_pack(void* stream, const hs_col* parts, int32_t n_parts, i
         hs_set_error("hs_key_pack: bad arguments (1..%d parts, non-null buffers)", HS_KEY_MAX_PARTS);
         return HS_E_ARG;
     }
+    if (hs_refuse_narrow("hs_key_pack", parts, n_parts)) return HS_E_ARG;
     int32_t widths[HS_KEY_MAX_PARTS];
     for (int k = 0; k < n_parts; ++k) {
         const hs_col& c = parts[k];

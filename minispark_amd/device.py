@@ -82,6 +82,12 @@ class DCol:
     # side's key column and the row's value is looked up in the join's byte table while the aggregate scans; only
     # Device.aggregate_join8 understands it
     virtual: int = 0
+    # Narrow side form of a resident FLOAT / TIMESTAMP table column: the same rows as u16 deltas
+    # (hs.I64_FOR16, `offs` = device {base, scale}) or code bytes (hs.F32_LUT8, `offs` = the device value table,
+    # `fixed_len` = its entries).  It hangs off the PLAIN column - the opposite of `plain` above, on purpose: every
+    # consumer sees the stored column, and only the private-table / keyless fused scan swaps the narrow form in
+    # (Device._narrow_slots).  A column derived from this one (a slice, a gather) does not carry it.
+    narrow: "DCol | None" = None
 
     def as_hs(self) -> hs.hs_col:
         c = hs.hs_col()
@@ -255,6 +261,9 @@ class Device:
         self._partial_prepared: dict[Any, dict] = {}
         self._finish_prepared: dict[Any, dict] = {}
         self.zero_copy_results = os.environ.get("HIPSPARK_ZERO_COPY", "1") != "0"
+        # the private-table / keyless fused scan reads DCol.narrow where a column has one (set by the engine from
+        # HIPSPARK_NARROW; part of the prepared-launch key)
+        self.narrow_enabled = True
         self._const_lens: dict[int, torch.Tensor] = {}
         self._raw_lib = self.lib
         self.rec: Recording | None = None
@@ -530,13 +539,75 @@ class Device:
         return raw, n, flags
 
     # ---- expression evaluation (A4) ---------------------------------------------------------------------
-    def _cols_array(self, batch: DBatch, order: Sequence[int], code_columns: Sequence[int] = ()):
+    def _cols_array(self, batch: DBatch, order: Sequence[int], code_columns: Sequence[int] = (),
+                    narrow_slots: Sequence[int] = ()):
         arr = (hs.hs_col * max(len(order), 1))()
         for s, idx in enumerate(order):
-            arr[s] = batch.cols[idx].as_hs()
+            arr[s] = batch.cols[idx].narrow.as_hs() if s in narrow_slots else batch.cols[idx].as_hs()
             if idx in code_columns:  # only its code bytes are read (HS_OP_DICTBIT): a plain byte column to the kernels
                 arr[s].kind, arr[s].fixed_len = hs.U8, -1
         return arr
+
+    def _narrow_slots(self, batch: DBatch, order: Sequence[int], code_columns: Sequence[int], key_slot: int | None) -> list[int]:
+        """Column slots of a private-table / keyless fused scan that read the narrow form of their column (DCol.narrow):
+        a preloaded argument / WHERE slot - never the key - whose column is a stored table column with a narrow form."""
+        if not self.narrow_enabled:
+            return []
+        return [s for s, idx in enumerate(order)
+                if s != key_slot and s < hs.HS_FUSED_COLS and idx not in code_columns
+                and batch.cols[idx].narrow is not None and batch.cols[idx].narrow.n == batch.cols[idx].n
+                and not batch.cols[idx].virtual]
+
+    @staticmethod
+    def _moved_bytes_per_row(batch: DBatch, order: Sequence[int], narrow_slots: Sequence[int]) -> int | None:
+        """Bytes the scan reads per row over its column slots (None with a variable-length string among them)."""
+        total = 0
+        for s, idx in enumerate(order):
+            col = batch.cols[idx]
+            if s in narrow_slots:
+                total += hs.NARROW_BYTES[col.narrow.kind]
+            elif col.kind == hs.STR:
+                if col.fixed_len < 0:
+                    return None
+                total += col.fixed_len
+            else:
+                total += hs.KIND_BYTES.get(col.kind, 4)  # (virtual join columns: the 4-byte probe key)
+        return total
+
+    # ---- narrow forms of resident numeric columns (DESIGN.md 4.5a) ------------------------------------------------
+    def narrow_encode(self, col: DCol) -> DCol | None:
+        """The narrow side form of a stored FLOAT (code bytes + value table) or TIMESTAMP (u16 deltas from one base)
+        column, or None when the column does not qualify.  One native call per kind (hs_narrow_lut8 / hs_narrow_for16:
+        two passes and a small read-back); its wall time goes to ``dict_encode_seconds`` like the strings' coding."""
+        if col.kind not in (hs.F32, hs.I64) or col.n == 0 or col.virtual:
+            return None
+        t0 = time.perf_counter()
+        try:
+            if self.rec is not None:
+                self.rec.poisoned = True  # table-open work with a read-back: not part of a run to replay
+            ws = torch.empty(int(self._raw_lib.hs_narrow_ws_bytes()) + PAD, dtype=torch.uint8, device=self.device)
+            answer = C.c_int32(0)
+            recording, self.rec = self.rec, None  # the buffers belong to the table, not to a recording
+            try:
+                if col.kind == hs.I64:
+                    codes, params = self.empty(col.n, torch.int16), self.empty(2, torch.int64)
+                else:
+                    codes, params = self.empty(col.n, torch.uint8), self.empty(256, torch.float32)
+            finally:
+                self.rec = recording
+            if col.kind == hs.I64:
+                hs.check(self._raw_lib.hs_narrow_for16(self.stream, col.data.data_ptr(), col.n, codes.data_ptr(),
+                                                       params.data_ptr(), ws.data_ptr(), C.byref(answer)), "hs_narrow_for16")
+                if not answer.value:
+                    return None
+                return DCol(hs.I64_FOR16, codes, col.n, offs=params)
+            hs.check(self._raw_lib.hs_narrow_lut8(self.stream, col.data.data_ptr(), col.n, codes.data_ptr(),
+                                                  params.data_ptr(), ws.data_ptr(), C.byref(answer)), "hs_narrow_lut8")
+            if not answer.value:
+                return None
+            return DCol(hs.F32_LUT8, codes, col.n, offs=params, fixed_len=int(answer.value))
+        finally:
+            self.dict_encode_seconds = getattr(self, "dict_encode_seconds", 0.0) + time.perf_counter() - t0
 
     def eval_numeric(self, batch: DBatch, exprs: Sequence[Any], sel: torch.Tensor | None = None,
                      n: int | None = None) -> list[tuple[DCol, str]]:
@@ -992,7 +1063,9 @@ class Device:
             # allocator may hand back the same data block with different lens / offs blocks
             key = (cache_key, cap, batch.nrows,
                    tuple((c.kind, c.fixed_len, c.data.data_ptr(), c.n, c.lens.data_ptr() if c.lens is not None else 0,
-                          c.offs.data_ptr() if c.offs is not None else 0) for c in batch.cols),
+                          c.offs.data_ptr() if c.offs is not None else 0,
+                          (c.narrow.kind, c.narrow.data.data_ptr(), c.narrow.offs.data_ptr(), c.narrow.fixed_len)
+                          if c.narrow is not None and self.narrow_enabled else 0) for c in batch.cols),
                    tuple(batch.unit_rows), tuple(batch.unit_ids) if batch.unit_ids is not None else None, slab_rows,
                    tail, shared, batch.unit_col.data_ptr() if batch.unit_col is not None else 0, batch.n_unit_ids)
         prep = self._partial_prepared.get(key) if key is not None else None
@@ -1141,6 +1214,10 @@ class Device:
         n_acc = len(low.acc_ops)
         keyless = group_by is None
         computed = batch.unit_col is not None
+        # narrow side forms (DCol.narrow) are read by the private-table and keyless scans only
+        narrow_slots = [] if shared or computed else self._narrow_slots(
+            batch, low.program.columns, low.program.code_columns, None if keyless else low.key_slot)
+        moved = self._moved_bytes_per_row(batch, low.program.columns, narrow_slots)
         if computed:
             # units are per-row ids: ONE row range for the chunking, batch.n_unit_ids unit tables for the outputs
             if not shared or tail or slab_rows is not None:
@@ -1202,7 +1279,8 @@ class Device:
             d_unit_ids = self.to_device(np.asarray(batch.unit_ids, dtype=np.int64)) if batch.unit_ids is not None else None
             return {
                 "slab": slab, "layout": layout, "desc": desc, "d_unit_ids": d_unit_ids,
-                "cols": self._cols_array(batch, low.program.columns, low.program.code_columns), "n_cols": len(low.program.columns),
+                "cols": self._cols_array(batch, low.program.columns, low.program.code_columns, narrow_slots),
+                "n_cols": len(low.program.columns),
                 "key_slot": low.key_slot, "prog": low.program.to_struct(), "spec": low.spec(), "geom": geom,
                 "n_units": n_units, "slots": slots,
                 "d_units": self.to_device(chunks.reshape(-1)), "d_chunk0": self.to_device(chunk0),
@@ -1212,7 +1290,8 @@ class Device:
                          "key_len": batch.cols[key_idx].fixed_len, "n_units": n_units,
                          "key_dict": batch.cols[key_idx].dict},
                 "info": {"rows": batch.nrows, "chunks": int(geom.n_chunks), "chunk_rows": int(geom.chunk_rows),
-                         "wg_threads": int(geom.wg_threads), "group_cap": cap, "lds_bytes": int(geom.lds_bytes)},
+                         "wg_threads": int(geom.wg_threads), "group_cap": cap, "lds_bytes": int(geom.lds_bytes),
+                         "tier": "private", "moved_bytes_per_row": moved, "narrow_slots": list(narrow_slots)},
             }
         if slab_rows is not None:
             # multi-GPU: outputs are written straight into the fixed-size slab that gets all-gathered
@@ -1239,7 +1318,7 @@ class Device:
             d_unit_ids = self.to_device(np.asarray(batch.unit_ids, dtype=np.int64))
             if out_unit is None:
                 out_unit = self.empty(max(slots, 1), torch.int64)
-        cols_arr, n_cols, unit_slot = (self._cols_array(batch, low.program.columns, low.program.code_columns),
+        cols_arr, n_cols, unit_slot = (self._cols_array(batch, low.program.columns, low.program.code_columns, narrow_slots),
                                        len(low.program.columns), None)
         ws_bytes = geom.ws_bytes
         if computed:
@@ -1266,7 +1345,8 @@ class Device:
             "kinds_arr": (C.c_int32 * max(n_acc, 1))(*acc_kinds),
             "info": {"rows": batch.nrows, "chunks": int(geom.n_chunks), "chunk_rows": int(geom.chunk_rows),
                      "wg_threads": int(geom.wg_threads), "group_cap": cap, "lds_bytes": int(geom.lds_bytes),
-                     "tier": "scalar" if keyless else "shared" if shared else "private"},
+                     "tier": "scalar" if keyless else "shared" if shared else "private",
+                     "moved_bytes_per_row": moved, "narrow_slots": list(narrow_slots)},
         }
 
     # ---- final merge (A7) ------------------------------------------------------------------------------

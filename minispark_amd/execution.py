@@ -189,6 +189,10 @@ class HipExecutionEngine(ExecutionEngine):
         self.shared_tier_enabled = os.environ.get("HIPSPARK_SHARED_TIER", "1") != "0"
         # round 2: dictionary-coded string columns and the in-place unique-key join (4.6)
         self.dict_enabled = os.environ.get("HIPSPARK_DICT", "1") != "0"
+        # narrow side forms of resident FLOAT / TIMESTAMP columns, read by the private-table / keyless scan
+        # (HIPSPARK_NARROW=0: off; =for16: only the TIMESTAMP form, the first stage measured in profiles/r16_narrow_codes.txt)
+        self.narrow_enabled = os.environ.get("HIPSPARK_NARROW", "1") != "0"
+        self._narrow_float = os.environ.get("HIPSPARK_NARROW", "1") != "for16"
         self.fused_join_enabled = os.environ.get("HIPSPARK_FUSED_JOIN", "1") != "0"
         self.fused_probe_enabled = os.environ.get("HIPSPARK_FUSED_PROBE", "1") != "0"  # round 3: probe inside the aggregate
         self.fused_probes = 0
@@ -241,6 +245,14 @@ class HipExecutionEngine(ExecutionEngine):
             self._gpu_track = self.tracer.new_track(f"GPU {self.dev.index}: every launch (hs_trace)")
             self._scan_track = self.tracer.new_track(f"GPU {self.dev.index}: scan kernel (event pair)")
             self.dev.time_scan_kernel(True)
+
+    @property
+    def narrow_enabled(self) -> bool:
+        return self.dev.narrow_enabled  # the device builds the scan's column table: the switch lives there
+
+    @narrow_enabled.setter
+    def narrow_enabled(self, value: bool) -> None:
+        self.dev.narrow_enabled = bool(value)
 
     @property
     def group_cap_hint(self) -> int:
@@ -493,7 +505,7 @@ class HipExecutionEngine(ExecutionEngine):
         """The run-time switches a recording was made under (tests flip them between runs of one query)."""
         return (self.replay_enabled, self.short_tail_enabled, self.shared_tier_enabled, self.dict_enabled,
                 self.fused_join_enabled, self.fused_probe_enabled, self.sharded_build_enabled, self.dev.zero_copy_results,
-                self.dev.timing_epoch)
+                self.dev.timing_epoch, self.narrow_enabled)
 
     @staticmethod
     def _stamp_of(path: str) -> tuple:
@@ -523,9 +535,10 @@ class HipExecutionEngine(ExecutionEngine):
             plan._hs_scan_keys = scans
         for key in scans:
             t = self._tables.get(key)
-            tables.append((_uid(t), tuple(sorted((cid, c.data.data_ptr()) for cid, c in t.columns.items()))) if t else None)
+            tables.append((_uid(t), tuple(sorted((cid, c.data.data_ptr(), c.narrow.data.data_ptr() if c.narrow is not None else 0)
+                                                 for cid, c in t.columns.items()))) if t else None)
         return (_uid(plan), tuple(tables), self.group_cap_hint, self.merge_cap_hint, len(self._global_partial),
-                len(self._global_merge), self.dev.timing_epoch)
+                len(self._global_merge), self.dev.timing_epoch, self.narrow_enabled)
 
     def _replay(self, rec: Any) -> list[JobResult] | None:
         self.dev.last_scan = getattr(rec, "scan_info", None)
@@ -1315,6 +1328,8 @@ class HipExecutionEngine(ExecutionEngine):
                 self._encode_string_columns_on_ranks(table, col_ids)
         elif self.dict_enabled:
             self._encode_string_columns(table, col_ids)
+        if self.narrow_enabled and self.dist is None and self.hbm_budget is None:
+            self._encode_narrow_columns(table, col_ids)
         batch = tbl.table_batch(table, col_ids, producer.alias)
         batch.partitioned = self.dist is not None
         return batch
@@ -1334,6 +1349,24 @@ class HipExecutionEngine(ExecutionEngine):
             coded = self.dev.dict_encode(col)
             if coded is not None:
                 table.columns[cid] = coded
+
+    def _encode_narrow_columns(self, table: Any, col_ids: Sequence[int]) -> None:
+        """Table open, FLOAT / TIMESTAMP columns with few distinct values: a narrow side form (code bytes + value table,
+        u16 deltas from one base; Device.narrow_encode) hung off the PLAIN column, which stays what every consumer sees.
+        Tried once per table and column.  Resident tables of a single-GPU engine without an HBM budget only: a streamed
+        range is read once (coding it would cost more than it saves), the budget counts the stored bytes alone, and a
+        distributed engine keeps to the stored columns until its tests cover the narrow scan."""
+        from . import hipspark as hs  # noqa: PLC0415
+
+        tried = table.__dict__.setdefault("_hs_narrow_tried", set())
+        for cid in col_ids:
+            col = table.columns[cid]
+            if cid in tried or col.kind not in (hs.F32, hs.I64) or col.dict is not None:
+                continue
+            if col.kind == hs.F32 and not getattr(self, "_narrow_float", True):
+                continue
+            tried.add(cid)
+            col.narrow = self.dev.narrow_encode(col)
 
     def _encode_string_columns_on_ranks(self, table: Any, col_ids: Sequence[int]) -> None:
         """_encode_string_columns when every rank holds other blocks of the table: the ranks code their own rows, then

@@ -27,6 +27,8 @@ HS_FUSED_COLS = 8
 
 # storage kinds
 I32, F32, I64, F64, STR, U8 = 0, 1, 2, 3, 4, 5
+I64_FOR16, F32_LUT8 = 6, 7  # narrow forms of resident TIMESTAMP / FLOAT columns (hs_narrow_for16 / hs_narrow_lut8)
+NARROW_BYTES = {I64_FOR16: 2, F32_LUT8: 1}
 JOIN8_CODE, JOIN8_UNIT = 16, 17  # virtual columns of the fused join + aggregate (hs_agg_shared_join8)
 JOIN8_WINDOW = 65536
 KIND_BYTES = {I32: 4, F32: 4, I64: 8, F64: 8, U8: 1}
@@ -406,6 +408,9 @@ SIGNATURES: dict[str, tuple] = {
     "hs_remap_u8": (C.c_int, [_P, _P, _I64, _P, _P]),
     "hs_dict_build": (C.c_int, [_P, _COLP, _I64, _I32, _P, _P, _P, _P]),
     "hs_dict_assign": (C.c_int, [_P, _COLP, _I64, _I32, _P, _P, _P, _P, _P]),
+    "hs_narrow_ws_bytes": (C.c_size_t, []),
+    "hs_narrow_for16": (C.c_int, [_P, _P, _I64, _P, _P, _P, C.POINTER(_I32)]),
+    "hs_narrow_lut8": (C.c_int, [_P, _P, _I64, _P, _P, _P, C.POINTER(_I32)]),
     "hs_dict_combine": (C.c_int, [_P, _I32, C.POINTER(_P), C.POINTER(_I32), _I64, _P]),
     "hs_key_pack": (C.c_int, [_P, _COLP, _I32, _I64, _P, _I32]),
     "hs_key_unpack": (C.c_int, [_P, _P, _I32, _I64, _P, C.POINTER(_I32), _I32, C.POINTER(_P)]),
@@ -424,6 +429,7 @@ SIGNATURES: dict[str, tuple] = {
     "hs_jit_compile_seconds": (C.c_double, []),
     "hs_jit_last_log": (C.c_char_p, []),
     "hs_jit_compile_check": (C.c_int, [_COLP, _I32, _I32, _PROGP, _SPECP, C.c_char_p, C.POINTER(_I64), C.c_char_p, _I64]),
+    "hs_jit_program_key": (C.c_int, [_COLP, _I32, _I32, _PROGP, _SPECP, C.c_char_p, _I64]),
     "hs_jit_compile_check_shared": (C.c_int, [_COLP, _I32, _I32, _I32, _PROGP, _SPECP, C.c_char_p, C.POINTER(_I64),
                                               C.c_char_p, _I64]),
     "hs_jit_compile_check_scalar": (C.c_int, [_COLP, _I32, _PROGP, _SPECP, C.c_char_p, C.POINTER(_I64), C.c_char_p, _I64]),

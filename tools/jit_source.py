@@ -1,5 +1,5 @@
 """Print the JIT source the library generates for the Q1 scan (no GPU needed; hiprtc cross-compiles for gfx950).
-usage: jit_source.py > q1.hip ; hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -S --cuda-device-only
+usage: jit_source.py [--narrow] > q1.hip ; hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -S --cuda-device-only
        -Iinclude -Iminispark_amd/csrc q1.hip"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,6 +24,13 @@ cols = (hs.hs_col * len(low.program.columns))()
 for slot, ci in enumerate(low.program.columns):
     cols[slot].kind = kinds[ci]
     cols[slot].fixed_len = 1 if kinds[ci] == hs.STR else -1
+if "--narrow" in sys.argv:  # the columns the engine reads in their narrow forms, with TPC-H's entry counts
+    narrow = {"l_quantity": (hs.F32_LUT8, 50), "l_discount": (hs.F32_LUT8, 11), "l_tax": (hs.F32_LUT8, 9), "l_shipdate": (hs.I64_FOR16, -1)}
+    dummy = (C.c_uint64 * 8)()  # only translated and compiled here
+    for slot, ci in enumerate(low.program.columns):
+        if schema[ci][0].split(".")[-1] in narrow and slot != low.key_slot:
+            cols[slot].kind, cols[slot].fixed_len = narrow[schema[ci][0].split(".")[-1]]
+            cols[slot].data = cols[slot].offs = C.cast(dummy, C.c_void_p)
 prog, spec = low.program.to_struct(), low.spec()
 src = C.create_string_buffer(65536)
 nb = C.c_int64(0)
