@@ -426,6 +426,22 @@ __device__ __forceinline__ void hs_load_quad(const hs_col& c, int64_t row0, uint
     }
 }
 
+// WHERE on a frame-of-reference column in the code domain (compiled programs, hs_jit.hip): a bare load of an HS_I64_FOR16
+// slot compared with a literal by < <= > >= is decided on the 16-bit delta as loaded, value(d) = base + d * scale never formed.
+// The threshold T in [0, 65536], computed once per workgroup in exact integer arithmetic (scale >= 1):
+//   strict:      value(d) <  lit  <=>  d < T        and so   value(d) >= lit  <=>  d >= T
+//   not strict:  value(d) <= lit  <=>  d < T        and so   value(d) >  lit  <=>  d >= T
+// A literal below every value gives 0 (never / always), one at or above base + 65535 * scale gives 65536 (always / never).
+__device__ __forceinline__ uint32_t hs_for16_threshold(int64_t base, int64_t scale, int64_t lit, bool strict) {
+    if (strict ? lit <= base : lit < base) return 0u;
+    const uint64_t diff = (uint64_t)lit - (uint64_t)base;  // lit >= base: the exact difference, below 2^64, no wrap
+    const uint64_t s = scale < 1 ? 1ull : (uint64_t)scale;
+    const uint64_t q = diff / s;
+    if (q >= 65536ull) return 65536u;
+    // d * s < diff  <=>  d < ceil(diff / s);   d * s <= diff  <=>  d <= floor(diff / s)
+    return (uint32_t)q + (strict ? (diff % s != 0 ? 1u : 0u) : 1u);
+}
+
 // Per-lane state of the fused kernel: liveness of the quad's rows, their group slots, the workgroup's
 // dictionary and the lane's private accumulator table.
 struct AggCtx {
@@ -440,12 +456,15 @@ struct AggCtx {
     int32_t n_acc;
     uint32_t err;
     HsSpecBits sb;  // the aggregate description in two scalars (hs_spec_bits)
+    // Compiled private-tier programs read a row's liveness as `Ctx::ALL_ALIVE || ctx.alive[j]`: AggCtxInterior (below)
+    // carries steps that lie wholly inside the chunk's rows, where the 64-bit row compares decide nothing.
+    static constexpr bool ALL_ALIVE = false;
 
-    // One-byte string keys (TPC-H flags): the byte indexes a 256-entry LDS map straight to its slot - one
-    // ds_read_u8 instead of hash + probe loop; the dictionary is only walked the first time a lane meets a byte.
-    // Lanes racing on dmap[b] all store the slot the dictionary gave that key, so any order is fine.
-    __device__ __forceinline__ int find_byte(const hs_col& key_col, uint64_t k, int64_t row, bool& live) {
-        if (mask >= 255u) return find<false>(key_col, k, row, live);  // slots would not fit the map's byte
+    // find_byte of compiled private-tier programs whose tables cannot reach 255 slots (the generator proves it from the
+    // LDS a launch may ask for, hs_jit.hip): without the run-time test of `mask`, which the compiler instantiated, both
+    // arms, once per row.  Called from the cold arm of the quad's slot resolution - some live row met a byte its
+    // workgroup has not seen - for the quad's rows in row order.
+    __device__ __forceinline__ int find_byte_small(uint64_t k, int64_t row, bool& live) {
         int s = 0;
         if (live) {
             const uint32_t b = (uint32_t)k & 0xffu;
@@ -462,6 +481,14 @@ struct AggCtx {
             }
         }
         return s;
+    }
+
+    // One-byte string keys (TPC-H flags): the byte indexes a 256-entry LDS map straight to its slot - one
+    // ds_read_u8 instead of hash + probe loop; the dictionary is only walked the first time a lane meets a byte.
+    // Lanes racing on dmap[b] all store the slot the dictionary gave that key, so any order is fine.
+    __device__ __forceinline__ int find_byte(const hs_col& key_col, uint64_t k, int64_t row, bool& live) {
+        if (mask >= 255u) return find<false>(key_col, k, row, live);  // slots would not fit the map's byte
+        return find_byte_small(k, row, live);
     }
 
     // slot of key word `k` held by `row`; marks the row dead and flags overflow when the table is full
@@ -499,6 +526,11 @@ struct AggCtx {
     }
 };
 
+// The same state for a step whose rows all lie inside [unit_begin, row_end): `alive` is not read (hs_agg_main_body).
+struct AggCtxInterior : AggCtx {
+    static constexpr bool ALL_ALIVE = true;
+};
+
 // ---- the interpreter as a Prog ------------------------------------------------------------------------
 template <bool HASHED_, int D>
 struct InterpProg {
@@ -507,6 +539,7 @@ struct InterpProg {
     static constexpr bool STATIC_SPEC = false;  // (compiled programs know their aggregates' kinds at compile time)
     static constexpr int NA = 0;
     static constexpr bool HAS_TABLES = false;  // (compiled programs with narrow columns keep decode tables in LDS)
+    static constexpr bool INTERIOR_STEPS = false;  // (compiled private-tier programs: run<AggCtxInterior> skips liveness)
     struct Tables {};
     static __device__ constexpr uint32_t acc_op(int) { return 0; }
     static __device__ constexpr bool acc_int(int) { return false; }
@@ -716,22 +749,43 @@ __device__ __forceinline__ void hs_agg_main_body(const AggMainArgs& A) {
     ctx.n_acc = NA;
     ctx.err = 0;
     ctx.sb = sb;
+#pragma unroll
+    for (int j = 0; j < HS_V; ++j) {
+        ctx.alive[j] = false;
+        ctx.slot[j] = 0;
+    }
     HS_SCAN_STAMP(2);
 
     // software pipeline: the loads of step i+1 are in flight while step i is evaluated
+    int64_t step_begin = c0;  // first row of the workgroup's step: the same scalar for every lane
     while (base < c1) {
         cur = nxt;
         const int64_t next_base = base + stride;
         if (next_base < c1) Prog::load(A, next_base, nxt);
         ctx.row0 = base;
+        // A step inside [us, c1) holds no dead row on any lane - every step but a chunk's first and last.  One scalar
+        // test sends it through the instantiation of run() that does not read `alive` (two 64-bit compares and a
+        // 64-bit add per row otherwise).  Same rows, same folds, same order.
+        bool interior = false;
+        if constexpr (Prog::INTERIOR_STEPS) interior = us <= step_begin && step_begin + stride <= c1;
+        if (interior) {
+            if constexpr (Prog::INTERIOR_STEPS) {
+                AggCtxInterior ictx;
+                static_cast<AggCtx&>(ictx) = ctx;
+                Prog::run(A, cur, ictx);
+                ctx.err = ictx.err;
+            }
+        } else {
 #pragma unroll
-        for (int j = 0; j < HS_V; ++j) {
-            const int64_t r = base + j;
-            ctx.alive[j] = (r >= us) && (r < c1);
-            ctx.slot[j] = 0;
+            for (int j = 0; j < HS_V; ++j) {
+                const int64_t r = base + j;
+                ctx.alive[j] = (r >= us) && (r < c1);
+                ctx.slot[j] = 0;
+            }
+            Prog::run(A, cur, ctx);
         }
-        Prog::run(A, cur, ctx);
         base = next_base;
+        step_begin += stride;
     }
     HS_SCAN_STAMP(3);
     __syncthreads();

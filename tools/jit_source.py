@@ -36,5 +36,6 @@ src = C.create_string_buffer(65536)
 nb = C.c_int64(0)
 rc = lib.hs_jit_compile_check(cols, len(low.program.columns), low.key_slot, C.byref(prog), C.byref(spec), b"gfx950", C.byref(nb), src, len(src))
 if rc:
-    raise SystemExit(lib.hs_last_error().decode())
+    print(src.value.decode())
+    raise SystemExit(lib.hs_last_error().decode() + "\n" + lib.hs_jit_last_log().decode()[:4000])
 print(src.value.decode())
