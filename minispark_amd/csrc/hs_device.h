@@ -183,7 +183,9 @@ __device__ __forceinline__ bool hs_cmp_result(int d, uint32_t cmp) {
 
 // SQL LIKE with % (any run) and _ (any one byte), anchored both ends; iterative with one
 // backtrack point (classic wildcard matcher).  Reference: re.match("^...$") on the translated
-// pattern, sql.py:178-179,192-194.  '.' does not match '\n' in the reference's regex.
+// pattern, sql.py:178-179,192-194.  '.' does not match '\n' in the reference's regex, so neither % nor _
+// crosses one; and Python's `$` also matches just before ONE trailing '\n' ('AIR\n' LIKE 'AIR' is true):
+// hs_like_impl anchors at the very end, hs_like runs it once more without a trailing '\n' when it failed.
 struct HsBytesMem {  // the string's bytes where they lie
     const uint8_t* p;
     __device__ __forceinline__ uint8_t operator[](uint32_t i) const { return p[i]; }
@@ -216,13 +218,24 @@ __device__ __forceinline__ bool hs_like_impl(const Bytes& b, uint32_t slen, cons
     while (pi < plen && pat[pi] == '%') ++pi;
     return pi == plen;
 }
+// `$` before one trailing '\n': a string that failed and ends in one is matched again, a byte shorter - every other
+// string pays one byte compare.  (One loop around ONE inlined matcher: the second run costs no second copy of its code.)
+template <class Bytes>
+__device__ __forceinline__ bool hs_like_anchored(const Bytes& b, uint32_t slen, const uint8_t* pat, uint32_t plen) {
+    uint32_t len = slen;
+    for (;;) {
+        if (hs_like_impl(b, len, pat, plen)) return true;
+        if (len != slen || len == 0 || b[len - 1] != '\n') return false;
+        --len;
+    }
+}
 __device__ __forceinline__ bool hs_like(HsStr s, const uint8_t* pat, uint32_t plen) {
     if (s.len <= 16) {  // the matcher re-reads bytes while backtracking: keep short strings in registers
         HsBytesReg r;
         hs_str_words16(s.p, s.len, r.w0, r.w1);
-        return hs_like_impl(r, s.len, pat, plen);
+        return hs_like_anchored(r, s.len, pat, plen);
     }
-    return hs_like_impl(HsBytesMem{s.p}, s.len, pat, plen);
+    return hs_like_anchored(HsBytesMem{s.p}, s.len, pat, plen);
 }
 
 // ---- Python arithmetic -----------------------------------------------------------------------------

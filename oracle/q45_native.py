@@ -44,6 +44,8 @@ def lib() -> C.CDLL:
         _lib.q5_run.restype = C.c_int
         _lib.q4_gen_orders.restype = None
         _lib.q4_orders_multiplier.restype = C.c_uint64
+        _lib.q5_like.restype = C.c_int
+        _lib.q5_like.argtypes = [C.c_char_p, C.c_int32, C.c_char_p, C.c_int32]
     return _lib
 
 
@@ -98,6 +100,11 @@ def run_strkey_like(flag: np.ndarray, mode: np.ndarray, modes: list[str], qty: n
         raise ValueError("q5_run: bad arguments")
     return [{"k": f"{chr(rows[i].flag)}-{modes[rows[i].mode]}", "qty": rows[i].qty, "avg_disc": rows[i].avg_disc,
              "count": int(rows[i].count)} for i in range(n)]
+
+
+def like_match(s: bytes, pattern: bytes) -> bool:
+    """The C oracle's LIKE matcher on one string (q5_run filters with it)."""
+    return bool(lib().q5_like(s, len(s), pattern, len(pattern)))
 
 
 def gen_orders(seed: int, row0: int, n_rows: int, n_total: int) -> tuple[np.ndarray, np.ndarray]:

@@ -157,8 +157,9 @@ int q4_run(const int32_t* o_key, const uint8_t* o_code, int64_t n_orders, const 
 }
 
 /* ---- config 5 ------------------------------------------------------------------------------------------------- */
-/* SQL LIKE as the reference's regex reads it: % = any run not crossing '\n', _ = any one char but '\n' */
-static int like_match(const uint8_t* s, int slen, const uint8_t* pat, int plen) {
+/* SQL LIKE as the reference's regex reads it (re.match("^...$")): % = any run not crossing '\n', _ = any one char but
+ * '\n', anchored at both ends - where Python's `$` also matches just before ONE trailing '\n' (like_match below). */
+static int like_match_to_end(const uint8_t* s, int slen, const uint8_t* pat, int plen) {
     int si = 0, pi = 0, star_p = -1, star_s = 0;
     while (si < slen) {
         if (pi < plen && pat[pi] == '%') {
@@ -177,6 +178,12 @@ static int like_match(const uint8_t* s, int slen, const uint8_t* pat, int plen) 
     while (pi < plen && pat[pi] == '%') ++pi;
     return pi == plen;
 }
+static int like_match(const uint8_t* s, int slen, const uint8_t* pat, int plen) {
+    if (like_match_to_end(s, slen, pat, plen)) return 1;
+    return slen > 0 && s[slen - 1] == '\n' && like_match_to_end(s, slen - 1, pat, plen); /* `$` before a trailing '\n' */
+}
+/* the matcher alone, for the tests that pin it against the regex */
+int q5_like(const uint8_t* s, int32_t slen, const uint8_t* pat, int32_t plen) { return like_match(s, slen, pat, plen); }
 
 typedef struct q5_row {
     int32_t flag; /* the l_returnflag byte */
