@@ -89,18 +89,25 @@ __device__ __forceinline__ bool rx_find_tile(const int64_t* tile_base, int64_t n
     return true;
 }
 
+// what a key's bin is cut from: bin = (f(key) >> shift) & (2^bits - 1).  Wave-uniform; every client sets it once.
+enum RxBin : int32_t {
+    RX_BIN_MIX64 = 0,  // hs_mix64 of the key word (GROUP BY)
+    RX_BIN_PLUS1,      // the value + 1 (hs_sort_by_order: -1 sorts first)
+    RX_BIN_VALUE,      // the value itself (ob_sort)
+    RX_BIN_MIX32,      // rx_mix32 of a 4-byte key: what rx_pass makes of RX_BIN_MIX64 when the 4-byte kernels apply
+    RX_BIN_RANGE,      // key - range_bias: partitions are KEY RANGES, most significant bits first (the dense join build)
+    RX_BIN_WINDOW,     // the key's hash WINDOW jh_window(key, range_bias) (the hashed join build)
+    RX_BIN_WORDS,      // a mix of all the word columns of a wide STRING key (k_rx_histw / k_rx_scatterw: rx_binw)
+};
+
 struct RxPass {
     const int64_t* seg_start;  // [n_seg + 1] positions in the row list
     const int64_t* tile_base;  // [n_seg + 1]
     int64_t n_seg;
-    int32_t shift, bits;       // bin = (mix(key word) >> shift) & (2^bits - 1); raw 1: ((key + 1) >> shift) & ... (hs_sort_by_order),
-                               // raw 2: (key >> shift) & ... (hs_order_by)
+    int32_t shift, bits;
     int32_t n_cols, first;     // columns that travel (0 = key); first pass reads the key through `key` / `sel`
-    int32_t range, range_bias; // range (4-byte keys only): 1: bin = ((key - range_bias) >> shift) & (2^bits - 1) - partitions are KEY RANGES,
-                               // most significant bits first (the dense join build); 2: bin = bits of the key's hash WINDOW
-                               // jh_window(key, range_bias) (the hashed join build); 0: a mix of the key's bits
-    int32_t wide, pad_w;       // wide: a STRING key of one fixed length 8 .. 16 travels as this many 4-byte word columns (2 .. 4), round 3
-    int32_t raw, key4;         // key4: the key is a 4-byte integer (bins from a 32-bit mix: a quarter of hs_mix64's multiplies)
+    int32_t mode, range_bias;  // RxBin and its parameter (RX_BIN_RANGE, RX_BIN_WINDOW: 4-byte keys only)
+    int32_t wide;              // a STRING key of one fixed length 8 .. 16 travels as this many 4-byte word columns (2 .. 4), round 3
     hs_col key;
     const int64_t* sel;
     int64_t row0;
@@ -115,9 +122,6 @@ __device__ __forceinline__ uint64_t rx_key(const RxPass& A, int64_t i) {
     if (A.first) return hs_key_at(A.key, A.sel ? A.sel[i] : A.row0 + i);
     return A.esize[0] == 4 ? (uint64_t)(int64_t)((const int32_t*)A.src[0])[i] : ((const uint64_t*)A.src[0])[i];
 }
-__device__ __forceinline__ uint32_t rx_bin(uint64_t word, int shift, int bits, int raw) {
-    return (uint32_t)((raw ? word + (uint64_t)(raw & 1) : hs_mix64(word)) >> shift) & ((1u << bits) - 1u);
-}
 // 4-byte keys: which partition a key lands in only has to be a function of the key that spreads well - one 32-bit multiply
 // and a fold of the high half into the low (the passes take bits 0 .. 15) instead of hs_mix64's 64-bit multiplies, in the
 // histogram and the scatter of either pass alike
@@ -127,18 +131,25 @@ __device__ __forceinline__ uint32_t rx_mix32(uint32_t k) {
     h *= 0x85EBCA77u;
     return h ^ (h >> 16);
 }
-__device__ __forceinline__ uint32_t rx_bin4(uint32_t key, int shift, int bits) { return (rx_mix32(key) >> shift) & ((1u << bits) - 1u); }
-// ... or, for range partitions (RxPass.range; wave-uniform choice), bits of the key's offset itself
 // the hashed join (hs_join_hash_*): a key's window of the table, 0 .. windows - 1 (multiply-shift: no power of two needed)
 __device__ __forceinline__ uint32_t jh_window(uint32_t key, uint32_t windows) {
     return (uint32_t)(((uint64_t)rx_mix32(key) * windows) >> 32);
 }
-__device__ __forceinline__ uint32_t rx_bin4r(const RxPass& A, uint32_t key, int shift, int bits) {
-    if (A.range == 2) return (jh_window(key, (uint32_t)A.range_bias) >> shift) & ((1u << bits) - 1u);
-    return A.range ? ((key - (uint32_t)A.range_bias) >> shift) & ((1u << bits) - 1u) : rx_bin4(key, shift, bits);
-}
-__device__ __forceinline__ uint32_t rx_bin_of(const RxPass& A, uint64_t word) {
-    return A.key4 ? rx_bin4r(A, (uint32_t)word, A.shift, A.bits) : rx_bin(word, A.shift, A.bits, A.raw);
+// W = uint32_t: the 4-byte kernels, which rx_pass launches in the three 32-bit modes only
+template <typename W>
+__device__ __forceinline__ uint32_t rx_bin_of(const RxPass& A, W word, int shift, int bits) {
+    const uint32_t key = (uint32_t)word, mask = (1u << bits) - 1u;
+    switch (A.mode) {
+        case RX_BIN_WINDOW: return (jh_window(key, (uint32_t)A.range_bias) >> shift) & mask;
+        case RX_BIN_RANGE: return ((key - (uint32_t)A.range_bias) >> shift) & mask;
+        case RX_BIN_MIX32: return (rx_mix32(key) >> shift) & mask;
+        default:
+            if constexpr (sizeof(W) == 8) {
+                if (A.mode == RX_BIN_MIX64) return (uint32_t)(hs_mix64(word) >> shift) & mask;
+                return (uint32_t)((word + (A.mode == RX_BIN_PLUS1 ? 1u : 0u)) >> shift) & mask;  // RX_BIN_PLUS1, RX_BIN_VALUE
+            }
+            __builtin_unreachable();
+    }
 }
 __device__ __forceinline__ void rx_move(const void* src, void* dst, int esize, int64_t from, int64_t to) {
     if (esize == 4) ((uint32_t*)dst)[to] = ((const uint32_t*)src)[from];
@@ -146,42 +157,140 @@ __device__ __forceinline__ void rx_move(const void* src, void* dst, int esize, i
     else ((uint8_t*)dst)[to] = ((const uint8_t*)src)[from];
 }
 
-__global__ void __launch_bounds__(RX_THREADS) k_rx_hist(const RxPass A_kernarg) {
-    HS_KERNARG(RxPass, A);
-    __shared__ uint32_t hist[RX_WAVES][1 << RX_MAX_BITS];  // one per wave: LDS atomics of different waves never meet
+// ---- the steps every kernel of the pass shares --------------------------------------------------------------------
+struct RxTile {
+    int64_t b;        // first position of the tile
+    int rows;         // 1 .. RX_TILE
+    int64_t nt;       // tiles of its segment
+    int64_t counter;  // counters[counter + bin * nt]: this tile's cell of a bin
+};
+// the tile of this workgroup; false past the last tile, for the whole workgroup
+__device__ __forceinline__ bool rx_tile(const RxPass& A, RxTile& T) {
     int64_t seg, t;
-    if (!rx_find_tile(A.tile_base, A.n_seg, blockIdx.x, seg, t)) return;
-    const int tid = threadIdx.x, w = tid / HS_WAVE, F = 1 << A.bits;
-    for (int i = tid; i < RX_WAVES * F; i += RX_THREADS) hist[i / F][i % F] = 0;
+    if (!rx_find_tile(A.tile_base, A.n_seg, blockIdx.x, seg, t)) return false;
+    T.b = A.seg_start[seg] + t * RX_TILE;
+    const int64_t left = A.seg_start[seg + 1] - T.b;
+    T.rows = left < RX_TILE ? (int)left : RX_TILE;
+    T.nt = A.tile_base[seg + 1] - A.tile_base[seg];
+    T.counter = (A.tile_base[seg] << A.bits) + t;
+    return true;
+}
+// per-wave counts of the bins (LDS atomics or ranking updates of different waves never meet): zero them - the caller's
+// next barrier makes that visible
+template <int WAVES>
+__device__ __forceinline__ void rx_zero(uint32_t (*hist)[1 << RX_MAX_BITS], int F) {
+    for (int i = threadIdx.x; i < WAVES * F; i += WAVES * HS_WAVE) hist[i / F][i % F] = 0;
+}
+// the tile's histogram: the waves' counts summed into `counters`
+template <int WAVES>
+__device__ __forceinline__ void rx_hist_store(const RxPass& A, const RxTile& T, const uint32_t (*hist)[1 << RX_MAX_BITS]) {
     __syncthreads();
-    const int64_t b = A.seg_start[seg] + t * RX_TILE;
-    const int64_t seg_end = A.seg_start[seg + 1];
-    const int64_t e = (b + RX_TILE) < seg_end ? (b + RX_TILE) : seg_end;
-    uint64_t word[RX_PER];
-#pragma unroll
-    for (int j = 0; j < RX_PER; ++j) {
-        const int64_t i = b + tid + (int64_t)j * RX_THREADS;
-        word[j] = i < e ? rx_key(A, i) : 0;
-    }
-#pragma unroll
-    for (int j = 0; j < RX_PER; ++j)
-        if (b + tid + (int64_t)j * RX_THREADS < e) atomicAdd(&hist[w][rx_bin_of(A, word[j])], 1u);
-    __syncthreads();
-    const int64_t nt = A.tile_base[seg + 1] - A.tile_base[seg];
-    if (tid < F) {
+    const int tid = threadIdx.x;
+    if (tid < (1 << A.bits)) {
         uint32_t total = 0;
-        for (int k = 0; k < RX_WAVES; ++k) total += hist[k][tid];
-        A.counters[(A.tile_base[seg] << A.bits) + (int64_t)tid * nt + t] = total;
+#pragma unroll
+        for (int k = 0; k < WAVES; ++k) total += hist[k][tid];
+        A.counters[T.counter + (int64_t)tid * T.nt] = total;
+    }
+}
+// One histogram body: THREADS threads take the tile's keys CHUNK per thread at a time - all loads of a chunk are issued
+// before the first count.  load(tile-local row, key) and bin(key) are what the three kernels differ in.
+template <int THREADS, int CHUNK, typename Key, typename Load, typename Bin>
+__device__ __forceinline__ void rx_hist_tile(const RxPass& A, uint32_t (*hist)[1 << RX_MAX_BITS], Load load, Bin bin) {
+    constexpr int WAVES = THREADS / HS_WAVE, PER = RX_TILE / THREADS;
+    RxTile T;
+    if (!rx_tile(A, T)) return;
+    const int tid = threadIdx.x, w = tid / HS_WAVE;
+    rx_zero<WAVES>(hist, 1 << A.bits);
+    for (int j0 = 0; j0 < PER; j0 += CHUNK) {
+        Key key[CHUNK];
+#pragma unroll
+        for (int j = 0; j < CHUNK; ++j) {
+            const int i = tid + (j0 + j) * THREADS;
+            if (i < T.rows) load(T, i, key[j]);
+            else key[j] = Key{};
+        }
+        if (j0 == 0) __syncthreads();  // the histograms are zero
+#pragma unroll
+        for (int j = 0; j < CHUNK; ++j)
+            if (tid + (j0 + j) * THREADS < T.rows) atomicAdd(&hist[w][bin(key[j])], 1u);
+    }
+    rx_hist_store<WAVES>(A, T, hist);
+}
+// One step of a wave's ranking (64 rows in order): a row's rank among the rows of its bin that this wave has ranked so
+// far = the wave's running count of the bin + its rank among this step's equal-bin lanes (the AND of one ballot per bin
+// bit).  The bin's first lane of the step is the only writer of whist_w[bin].
+__device__ __forceinline__ uint32_t rx_rank(uint32_t* whist_w, uint32_t bin, bool valid, int bits, uint64_t below) {
+    uint64_t peers = __ballot(valid);
+    for (int bit = 0; bit < bits; ++bit) {
+        const bool on = (bin >> bit) & 1u;
+        const uint64_t bal = __ballot(valid && on);
+        peers &= on ? bal : ~bal;
+    }
+    const uint32_t prior = valid ? whist_w[bin] : 0u;
+    const uint32_t rank = (uint32_t)__popcll(peers & below);
+    if (valid && rank == 0) whist_w[bin] = prior + (uint32_t)__popcll(peers);
+    return prior + rank;
+}
+// From the waves' counts (ranking done) to whist[w][bin] = tile-local start of (wave, bin) and gbase[bin] = "global
+// position minus tile-local position" of the bin's rows: a scan over the waves per bin, an exclusive scan of the bin
+// totals (threads 0 .. 255 = waves 0 .. 3) and the tile's scanned counter.  Barriers at both ends.
+__device__ __forceinline__ void rx_bin_starts(const RxPass& A, const RxTile& T, uint32_t (*whist)[1 << RX_MAX_BITS], int64_t* gbase,
+                                              uint32_t* s_wave_tot) {
+    const int tid = threadIdx.x, lane = tid & (HS_WAVE - 1), w = tid / HS_WAVE, F = 1 << A.bits;
+    __syncthreads();
+    uint32_t bin_total = 0;
+    if (tid < F) {
+        uint32_t run = 0;
+#pragma unroll
+        for (int k = 0; k < RX_WAVES; ++k) {
+            const uint32_t c = whist[k][tid];
+            whist[k][tid] = run;
+            run += c;
+        }
+        bin_total = run;
+        gbase[tid] = A.counters[T.counter + (int64_t)tid * T.nt];
+    }
+    uint32_t x = bin_total;
+    for (int d = 1; d < HS_WAVE; d <<= 1) {
+        const uint32_t up = __shfl_up(x, d, HS_WAVE);
+        if (lane >= d) x += up;
+    }
+    if (w < 4 && lane == HS_WAVE - 1) s_wave_tot[w] = x;
+    __syncthreads();
+    if (tid < F) {
+        const uint32_t before = (w > 0 ? s_wave_tot[0] : 0u) + (w > 1 ? s_wave_tot[1] : 0u) + (w > 2 ? s_wave_tot[2] : 0u);
+        const uint32_t bin_start = before + x - bin_total;
+        gbase[tid] -= bin_start;
+#pragma unroll
+        for (int k = 0; k < RX_WAVES; ++k) whist[k][tid] += bin_start;
+    }
+    __syncthreads();
+}
+// A staged column (the tile in bin order in LDS) leaves by consecutive threads: the rows of a bin (32 on average at
+// fan-out 256) go out as one or two contiguous segments instead of one 4-8 B store per row and bin - the store path of
+// a CU takes a request per distinct line, not per byte.  The barrier in front: the column is staged.
+template <typename E>
+__device__ __forceinline__ void rx_write_out(E* dst, const E* stage, const uint8_t* sbin, const int64_t* gbase, int rows) {
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < RX_PER; ++k) {
+        const int i = threadIdx.x + k * RX_THREADS;
+        if (i < rows) dst[gbase[sbin[i]] + i] = stage[i];
     }
 }
 
-// Stable scatter of a tile.  Wave w ranks rows [w * 512, (w + 1) * 512) of the tile, 64 at a time in order: a row's
-// rank among the rows of its bin = the wave's running count of the bin + its rank among this step's equal-bin lanes
-// (the AND of one ballot per bin bit).  A scan over the waves per bin and the tile's scanned counter finish the address.
-//
-// The tile is first put in bin order in LDS, one column at a time, and written out by consecutive threads: the rows of
-// a bin (32 on average at fan-out 256) leave as one or two contiguous segments instead of one 4-8 B store per row and
-// bin - the store path of a CU takes a request per distinct line, not per byte.
+__global__ void __launch_bounds__(RX_THREADS) k_rx_hist(const RxPass A_kernarg) {
+    HS_KERNARG(RxPass, A);
+    __shared__ uint32_t hist[RX_WAVES][1 << RX_MAX_BITS];
+    rx_hist_tile<RX_THREADS, RX_PER, uint64_t>(
+        A, hist, [&](const RxTile& T, int i, uint64_t& word) { word = rx_key(A, T.b + i); },
+        [&](uint64_t word) { return rx_bin_of(A, word, A.shift, A.bits); });
+}
+
+// Stable scatter of a tile.  Wave w ranks rows [w * 512, (w + 1) * 512) of the tile, 64 at a time in order (rx_rank); a
+// scan over the waves per bin and the tile's scanned counter finish the address (rx_bin_starts).  The tile is first put
+// in bin order in LDS, one column at a time, and written out by consecutive threads (rx_write_out).
 // two workgroups per CU (<= 64 VGPRs, a few spilled) beat one at 94 VGPRs: 560 us against 840 us per pass of 64 M rows
 __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) k_rx_scatter(const RxPass A_kernarg) {
     HS_KERNARG(RxPass, A);
@@ -189,173 +298,103 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
     __shared__ int64_t gbase[1 << RX_MAX_BITS];
     __shared__ uint32_t s_wave_tot[4];
     extern __shared__ __align__(16) uint8_t rx_stage[];  // sbin[RX_TILE] u8, then stage[RX_TILE] of the widest column
-    int64_t seg, t;
-    if (!rx_find_tile(A.tile_base, A.n_seg, blockIdx.x, seg, t)) return;
-    const int tid = threadIdx.x, lane = tid & (HS_WAVE - 1), w = tid / HS_WAVE, F = 1 << A.bits;
-    for (int i = tid; i < RX_WAVES * F; i += RX_THREADS) whist[i / F][i % F] = 0;
+    RxTile T;
+    if (!rx_tile(A, T)) return;
+    const int tid = threadIdx.x, lane = tid & (HS_WAVE - 1), w = tid / HS_WAVE;
+    rx_zero<RX_WAVES>(whist, 1 << A.bits);
     __syncthreads();
-    const int64_t b = A.seg_start[seg] + t * RX_TILE;
-    const int64_t seg_end = A.seg_start[seg + 1];
-    const int64_t e = (b + RX_TILE) < seg_end ? (b + RX_TILE) : seg_end;
     // all loads of a phase are issued before the first dependent use: the kernel would otherwise pay one global
     // round trip per row step (the ranking's LDS updates and the scatter's stores fence the loads behind them)
     uint64_t word[RX_PER];
     uint32_t bin[RX_PER], local[RX_PER];
     const uint64_t below = (1ull << lane) - 1ull;
-    const int64_t first = b + (int64_t)w * RX_SUB + lane;
+    const int first = w * RX_SUB + lane;  // tile-local row of step 0
 #pragma unroll
     for (int j = 0; j < RX_PER; ++j) {
-        const int64_t i = first + j * HS_WAVE;
-        word[j] = i < e ? rx_key(A, i) : 0;
+        const int i = first + j * HS_WAVE;
+        word[j] = i < T.rows ? rx_key(A, T.b + i) : 0;
     }
 #pragma unroll
     for (int j = 0; j < RX_PER; ++j) {
-        const bool valid = first + j * HS_WAVE < e;
-        bin[j] = valid ? rx_bin_of(A, word[j]) : 0u;
-        uint64_t peers = __ballot(valid);
-        for (int bit = 0; bit < A.bits; ++bit) {
-            const bool on = (bin[j] >> bit) & 1u;
-            const uint64_t bal = __ballot(valid && on);
-            peers &= on ? bal : ~bal;
-        }
-        uint32_t prior = 0;
-        if (valid) prior = whist[w][bin[j]];
-        const uint32_t rank = (uint32_t)__popcll(peers & below);
-        local[j] = prior + rank;
-        if (valid && rank == 0) whist[w][bin[j]] = prior + (uint32_t)__popcll(peers);  // the bin's first lane of the step
+        const bool valid = first + j * HS_WAVE < T.rows;
+        bin[j] = valid ? rx_bin_of(A, word[j], A.shift, A.bits) : 0u;
+        local[j] = rx_rank(whist[w], bin[j], valid, A.bits, below);
     }
-    __syncthreads();
-    const int64_t nt = A.tile_base[seg + 1] - A.tile_base[seg];
-    uint32_t bin_total = 0;
-    if (tid < F) {
-        uint32_t run = 0;
-        for (int k = 0; k < RX_WAVES; ++k) {
-            const uint32_t c = whist[k][tid];
-            whist[k][tid] = run;
-            run += c;
-        }
-        bin_total = run;
-        gbase[tid] = A.counters[(A.tile_base[seg] << A.bits) + (int64_t)tid * nt + t];
+    rx_bin_starts(A, T, whist, gbase, s_wave_tot);
+    uint8_t* sbin = rx_stage;
+    uint8_t* stage = rx_stage + RX_TILE;
+    uint32_t lpos2[RX_PER / 2];  // two 16-bit tile-local positions per register; 0xffff: no row
+#pragma unroll
+    for (int j = 0; j < RX_PER; ++j) {
+        const bool valid = first + j * HS_WAVE < T.rows;
+        const uint32_t at = valid ? whist[w][bin[j]] + local[j] : 0xffffu;
+        if (valid) sbin[at] = (uint8_t)bin[j];
+        lpos2[j / 2] = (j & 1) ? (lpos2[j / 2] | (at << 16)) : at;
     }
-    {
-        // tile-local start of every bin: exclusive scan of the bin totals (threads 0 .. 255 = waves 0 .. 3);
-        // gbase becomes "global position minus tile-local position"
-        uint32_t x = bin_total;
-        for (int d = 1; d < HS_WAVE; d <<= 1) {
-            const uint32_t up = __shfl_up(x, d, HS_WAVE);
-            if (lane >= d) x += up;
-        }
-        if (w < 4 && lane == HS_WAVE - 1) s_wave_tot[w] = x;
-        __syncthreads();
-        if (tid < F) {
-            uint32_t before = 0;
-            for (int k = 0; k < w; ++k) before += s_wave_tot[k];
-            const uint32_t bin_start = before + x - bin_total;
-            gbase[tid] -= bin_start;
-            for (int k = 0; k < RX_WAVES; ++k) whist[k][tid] += bin_start;  // now: tile-local start of (wave, bin)
-        }
-        __syncthreads();
-        uint8_t* sbin = rx_stage;
-        uint8_t* stage = rx_stage + RX_TILE;
-        const int rows = (int)(e - b);
-        uint32_t lpos2[RX_PER / 2];  // two 16-bit tile-local positions per register; 0xffff: no row
+    auto lpos = [&](int j) -> uint32_t { return (lpos2[j / 2] >> ((j & 1) * 16)) & 0xffffu; };
+    auto write_out = [&](void* dst, int es) {
+        if (es == 4) rx_write_out((uint32_t*)dst, (const uint32_t*)stage, sbin, gbase, T.rows);
+        else if (es == 8) rx_write_out((uint64_t*)dst, (const uint64_t*)stage, sbin, gbase, T.rows);
+        else rx_write_out((uint8_t*)dst, (const uint8_t*)stage, sbin, gbase, T.rows);
+        __syncthreads();  // the column has left the stage
+    };
+    {   // the key column, from registers
+        const int es = A.esize[0];
 #pragma unroll
         for (int j = 0; j < RX_PER; ++j) {
-            const bool valid = first + j * HS_WAVE < e;
-            const uint32_t at = valid ? whist[w][bin[j]] + local[j] : 0xffffu;
-            if (valid) sbin[at] = (uint8_t)bin[j];
-            lpos2[j / 2] = (j & 1) ? (lpos2[j / 2] | (at << 16)) : at;
+            if (lpos(j) == 0xffffu) continue;
+            if (es == 4) ((uint32_t*)stage)[lpos(j)] = (uint32_t)word[j];
+            else ((uint64_t*)stage)[lpos(j)] = word[j];
         }
-        auto lpos = [&](int j) -> uint32_t { return (lpos2[j / 2] >> ((j & 1) * 16)) & 0xffffu; };
-        auto write_out = [&](void* dst, int es) {
-            __syncthreads();
+        write_out(A.dst[0], es);
+    }
+    for (int c = 1; c < A.n_cols; ++c) {
+        const int es = A.esize[c];
+        const void* src = A.src[c];
+        uint64_t v[RX_PER];
 #pragma unroll
-            for (int k = 0; k < RX_PER; ++k) {
-                const int i = tid + k * RX_THREADS;
-                if (i >= rows) continue;
-                const int64_t to = gbase[sbin[i]] + i;
-                if (es == 4) ((uint32_t*)dst)[to] = ((const uint32_t*)stage)[i];
-                else if (es == 8) ((uint64_t*)dst)[to] = ((const uint64_t*)stage)[i];
-                else ((uint8_t*)dst)[to] = stage[i];
-            }
-            __syncthreads();
-        };
-        {   // the key column, from registers
-            const int es = A.esize[0];
-#pragma unroll
-            for (int j = 0; j < RX_PER; ++j) {
-                if (lpos(j) == 0xffffu) continue;
-                if (es == 4) ((uint32_t*)stage)[lpos(j)] = (uint32_t)word[j];
-                else ((uint64_t*)stage)[lpos(j)] = word[j];
-            }
-            write_out(A.dst[0], es);
+        for (int j = 0; j < RX_PER; ++j) {
+            const int64_t i = T.b + first + j * HS_WAVE;
+            v[j] = lpos(j) == 0xffffu ? 0 : (es == 4 ? (uint64_t)((const uint32_t*)src)[i] : es == 8 ? ((const uint64_t*)src)[i] : (uint64_t)((const uint8_t*)src)[i]);
         }
-        for (int c = 1; c < A.n_cols; ++c) {
-            const int es = A.esize[c];
-            const void* src = A.src[c];
-            uint64_t v[RX_PER];
 #pragma unroll
-            for (int j = 0; j < RX_PER; ++j) {
-                const int64_t i = first + j * HS_WAVE;
-                v[j] = lpos(j) == 0xffffu ? 0 : (es == 4 ? (uint64_t)((const uint32_t*)src)[i] : es == 8 ? ((const uint64_t*)src)[i] : (uint64_t)((const uint8_t*)src)[i]);
-            }
-#pragma unroll
-            for (int j = 0; j < RX_PER; ++j) {
-                if (lpos(j) == 0xffffu) continue;
-                if (es == 4) ((uint32_t*)stage)[lpos(j)] = (uint32_t)v[j];
-                else if (es == 8) ((uint64_t*)stage)[lpos(j)] = v[j];
-                else stage[lpos(j)] = (uint8_t)v[j];
-            }
-            write_out(A.dst[c], es);
+        for (int j = 0; j < RX_PER; ++j) {
+            if (lpos(j) == 0xffffu) continue;
+            if (es == 4) ((uint32_t*)stage)[lpos(j)] = (uint32_t)v[j];
+            else if (es == 8) ((uint64_t*)stage)[lpos(j)] = v[j];
+            else stage[lpos(j)] = (uint8_t)v[j];
         }
+        write_out(A.dst[c], es);
     }
 }
 
 // ---- the pass for 4-byte tuples (round 3) --------------------------------------------------------------------------
 // INTEGER key + up to three 4-byte value columns (f32 / i32: what SUM, AVG, COUNT over stored columns carry): the same
 // tile, ranking and staging as k_rx_hist / k_rx_scatter with everything that was decided per element at run time
-// (element size, first pass or later, selection, key kind) decided at compile time, tile-local 32-bit indexing and the
-// 32-bit bin mix.  FIRST: the key is read from the table's INTEGER column at row0 + position, or through the row list.
+// (element size, first pass or later, selection, key kind) decided at compile time, the value columns waiting in
+// registers, and a 32-bit bin.  FIRST: the key is read from the table's INTEGER column at row0 + position, or through
+// the row list behind a WHERE.
 template <bool FIRST>
-__device__ __forceinline__ const int32_t* rx4_keys(const RxPass& A) {
-    return FIRST ? (const int32_t*)A.key.data + A.row0 : (const int32_t*)A.src[0];
-}
+struct Rx4Keys {
+    const int32_t* keys;  // at the tile's first position
+    const int64_t* sel;
+    const int32_t* table;
+    __device__ __forceinline__ Rx4Keys(const RxPass& A, const RxTile& T)
+        : keys((FIRST ? (const int32_t*)A.key.data + A.row0 : (const int32_t*)A.src[0]) + T.b),
+          sel(FIRST && A.sel ? A.sel + T.b : nullptr), table((const int32_t*)A.key.data) {}
+    __device__ __forceinline__ uint32_t operator()(int i) const { return (uint32_t)(sel ? table[sel[i]] : keys[i]); }
+};
 
 constexpr int RX_H4_THREADS = 256;                   // the histogram of a tile needs no ranking: four waves, 32 keys per lane
 constexpr int RX_H4_PER = RX_TILE / RX_H4_THREADS;
 template <bool FIRST>
 __global__ void __launch_bounds__(RX_H4_THREADS) k_rx_hist4(const RxPass A_kernarg) {
     HS_KERNARG(RxPass, A);
-    constexpr int WAVES = RX_H4_THREADS / HS_WAVE;
-    __shared__ uint32_t hist[WAVES][1 << RX_MAX_BITS];
-    int64_t seg, t;
-    if (!rx_find_tile(A.tile_base, A.n_seg, blockIdx.x, seg, t)) return;
-    const int tid = threadIdx.x, w = tid / HS_WAVE, F = 1 << A.bits;
-    for (int i = tid; i < WAVES * F; i += RX_H4_THREADS) hist[i / F][i % F] = 0;
-    const int64_t b = A.seg_start[seg] + t * RX_TILE;
-    const int64_t left = A.seg_start[seg + 1] - b;
-    const int rows = left < RX_TILE ? (int)left : RX_TILE;
-    const int32_t* keys = rx4_keys<FIRST>(A) + b;
-    const int64_t* sel = FIRST && A.sel ? A.sel + b : nullptr;  // behind a WHERE the first pass reads the key through the row list
-    uint32_t key[RX_H4_PER];
-#pragma unroll
-    for (int j = 0; j < RX_H4_PER; ++j) {
-        const int i = tid + j * RX_H4_THREADS;
-        key[j] = i >= rows ? 0u : (uint32_t)(sel ? ((const int32_t*)A.key.data)[sel[i]] : keys[i]);
-    }
-    __syncthreads();
+    __shared__ uint32_t hist[RX_H4_THREADS / HS_WAVE][1 << RX_MAX_BITS];
     const int shift = A.shift, bits = A.bits;
-#pragma unroll
-    for (int j = 0; j < RX_H4_PER; ++j)
-        if (tid + j * RX_H4_THREADS < rows) atomicAdd(&hist[w][rx_bin4r(A, key[j], shift, bits)], 1u);
-    __syncthreads();
-    const int64_t nt = A.tile_base[seg + 1] - A.tile_base[seg];
-    if (tid < F) {
-        uint32_t total = 0;
-#pragma unroll
-        for (int k = 0; k < WAVES; ++k) total += hist[k][tid];
-        A.counters[(A.tile_base[seg] << A.bits) + (int64_t)tid * nt + t] = total;
-    }
+    rx_hist_tile<RX_H4_THREADS, RX_H4_PER, uint32_t>(
+        A, hist, [&](const RxTile& T, int i, uint32_t& key) { key = Rx4Keys<FIRST>(A, T)(i); },
+        [&](uint32_t key) { return rx_bin_of(A, key, shift, bits); });
 }
 
 template <int NV, bool FIRST>
@@ -366,21 +405,19 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
     __shared__ uint32_t s_wave_tot[4];
     __shared__ uint8_t sbin[RX_TILE];
     __shared__ uint32_t stage[RX_TILE];
-    int64_t seg, t;
-    if (!rx_find_tile(A.tile_base, A.n_seg, blockIdx.x, seg, t)) return;
-    const int tid = threadIdx.x, lane = tid & (HS_WAVE - 1), w = tid / HS_WAVE, F = 1 << A.bits;
-    const int64_t b = A.seg_start[seg] + t * RX_TILE;
-    const int64_t left = A.seg_start[seg + 1] - b;
-    const int rows = left < RX_TILE ? (int)left : RX_TILE;
-    const int32_t* keys = rx4_keys<FIRST>(A) + b;
+    RxTile T;
+    if (!rx_tile(A, T)) return;
+    const int tid = threadIdx.x, lane = tid & (HS_WAVE - 1), w = tid / HS_WAVE;
+    const int64_t b = T.b;
+    const int rows = T.rows;
     constexpr int NVR = NV > 0 ? NV : 1;
     uint32_t key[RX_PER], val[NVR][RX_PER];
     const int first = w * RX_SUB + lane;  // tile-local row of step 0
-    const int64_t* sel = FIRST && A.sel ? A.sel + b : nullptr;
+    const Rx4Keys<FIRST> key_at(A, T);
 #pragma unroll
     for (int j = 0; j < RX_PER; ++j) {
         const int i = first + j * HS_WAVE;
-        key[j] = i >= rows ? 0u : (uint32_t)(sel ? ((const int32_t*)A.key.data)[sel[i]] : keys[i]);
+        key[j] = i >= rows ? 0u : key_at(i);
     }
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
@@ -393,7 +430,7 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int j = 0; j < RX_PER; ++j) val[c][j] = first + j * HS_WAVE < rows ? src[first + j * HS_WAVE] : 0u;
     }
-    for (int i = tid; i < RX_WAVES * F; i += RX_THREADS) whist[i / F][i % F] = 0;
+    rx_zero<RX_WAVES>(whist, 1 << A.bits);
     __syncthreads();
     const int shift = A.shift, bits = A.bits;
     const uint64_t below = (1ull << lane) - 1ull;
@@ -401,47 +438,10 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
     for (int j = 0; j < RX_PER; ++j) {
         const bool valid = first + j * HS_WAVE < rows;
-        const uint32_t bin = valid ? rx_bin4r(A, key[j], shift, bits) : 0u;
-        uint64_t peers = __ballot(valid);
-        for (int bit = 0; bit < bits; ++bit) {
-            const bool on = (bin >> bit) & 1u;
-            const uint64_t bal = __ballot(valid && on);
-            peers &= on ? bal : ~bal;
-        }
-        const uint32_t prior = valid ? whist[w][bin] : 0u;
-        const uint32_t rank = (uint32_t)__popcll(peers & below);
-        bl[j] = bin | ((prior + rank) << 8);
-        if (valid && rank == 0) whist[w][bin] = prior + (uint32_t)__popcll(peers);
+        const uint32_t bin = valid ? rx_bin_of(A, key[j], shift, bits) : 0u;
+        bl[j] = bin | (rx_rank(whist[w], bin, valid, bits, below) << 8);
     }
-    __syncthreads();
-    const int64_t nt = A.tile_base[seg + 1] - A.tile_base[seg];
-    uint32_t bin_total = 0;
-    if (tid < F) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int k = 0; k < RX_WAVES; ++k) {
-            const uint32_t c = whist[k][tid];
-            whist[k][tid] = run;
-            run += c;
-        }
-        bin_total = run;
-        gbase[tid] = A.counters[(A.tile_base[seg] << A.bits) + (int64_t)tid * nt + t];
-    }
-    uint32_t x = bin_total;
-    for (int d = 1; d < HS_WAVE; d <<= 1) {
-        const uint32_t up = __shfl_up(x, d, HS_WAVE);
-        if (lane >= d) x += up;
-    }
-    if (w < 4 && lane == HS_WAVE - 1) s_wave_tot[w] = x;
-    __syncthreads();
-    if (tid < F) {
-        const uint32_t before = (w > 0 ? s_wave_tot[0] : 0u) + (w > 1 ? s_wave_tot[1] : 0u) + (w > 2 ? s_wave_tot[2] : 0u);
-        const uint32_t bin_start = before + x - bin_total;
-        gbase[tid] -= bin_start;  // global position minus tile-local position
-#pragma unroll
-        for (int k = 0; k < RX_WAVES; ++k) whist[k][tid] += bin_start;
-    }
-    __syncthreads();
+    rx_bin_starts(A, T, whist, gbase, s_wave_tot);
     uint32_t at[RX_PER];  // tile-local position of my rows in bin order
 #pragma unroll
     for (int j = 0; j < RX_PER; ++j) {
@@ -452,6 +452,8 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
             stage[at[j]] = key[j];
         }
     }
+    // this kernel writes its staged columns out in its own words: through rx_write_out the compiler spends 2 more VGPRs
+    // (NV = 1) or 4 more bytes of scratch (NV = 2, 3) on it
     __syncthreads();
     {
         int32_t* dst = (int32_t*)A.dst[0];
@@ -463,7 +465,7 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
     }
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
-        __syncthreads();
+        __syncthreads();  // the previous column has left the stage
 #pragma unroll
         for (int j = 0; j < RX_PER; ++j)
             if (at[j] != 0xffffffffu) stage[at[j]] = val[c][j];
@@ -482,6 +484,10 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
 // zero-padded; the value columns follow), so its tuples are 4-byte columns like an INTEGER key's and take the same tile
 // shape, ranking and 32 KB staging at two workgroups per CU; the bin is cut from a mix of all KW words.  FIRST: the words
 // come from the string column itself (any alignment: hs_str_words16), through the row list when there is one.
+template <int KW>
+struct RxWords {
+    uint32_t w[KW];
+};
 template <bool FIRST, int KW>
 __device__ __forceinline__ void rx_words(const RxPass& A, int64_t pos, uint32_t* w) {
     if constexpr (FIRST) {
@@ -498,7 +504,7 @@ __device__ __forceinline__ void rx_words(const RxPass& A, int64_t pos, uint32_t*
     }
 }
 template <int KW>
-__device__ __forceinline__ uint32_t rx_binw(const uint32_t* w, int shift, int bits) {
+__device__ __forceinline__ uint32_t rx_binw(const uint32_t* w, int shift, int bits) {  // RX_BIN_WORDS
     uint32_t h = rx_mix32(w[0]);
 #pragma unroll
     for (int k = 1; k < KW; ++k) h = rx_mix32(h ^ w[k]);
@@ -508,36 +514,11 @@ __device__ __forceinline__ uint32_t rx_binw(const uint32_t* w, int shift, int bi
 template <bool FIRST, int KW>
 __global__ void __launch_bounds__(RX_H4_THREADS) k_rx_histw(const RxPass A_kernarg) {
     HS_KERNARG(RxPass, A);
-    constexpr int WAVES = RX_H4_THREADS / HS_WAVE;
-    __shared__ uint32_t hist[WAVES][1 << RX_MAX_BITS];
-    int64_t seg, t;
-    if (!rx_find_tile(A.tile_base, A.n_seg, blockIdx.x, seg, t)) return;
-    const int tid = threadIdx.x, w = tid / HS_WAVE, F = 1 << A.bits;
-    for (int i = tid; i < WAVES * F; i += RX_H4_THREADS) hist[i / F][i % F] = 0;
-    const int64_t b = A.seg_start[seg] + t * RX_TILE;
-    const int64_t left = A.seg_start[seg + 1] - b;
-    const int rows = left < RX_TILE ? (int)left : RX_TILE;
+    __shared__ uint32_t hist[RX_H4_THREADS / HS_WAVE][1 << RX_MAX_BITS];
     const int shift = A.shift, bits = A.bits;
-    __syncthreads();
-    for (int j0 = 0; j0 < RX_H4_PER; j0 += 8) {
-        uint32_t words[8][KW];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = tid + (j0 + j) * RX_H4_THREADS;
-            if (i < rows) rx_words<FIRST, KW>(A, b + i, words[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (tid + (j0 + j) * RX_H4_THREADS < rows) atomicAdd(&hist[w][rx_binw<KW>(words[j], shift, bits)], 1u);
-    }
-    __syncthreads();
-    const int64_t nt = A.tile_base[seg + 1] - A.tile_base[seg];
-    if (tid < F) {
-        uint32_t total = 0;
-#pragma unroll
-        for (int k = 0; k < WAVES; ++k) total += hist[k][tid];
-        A.counters[(A.tile_base[seg] << A.bits) + (int64_t)tid * nt + t] = total;
-    }
+    rx_hist_tile<RX_H4_THREADS, 8, RxWords<KW>>(
+        A, hist, [&](const RxTile& T, int i, RxWords<KW>& key) { rx_words<FIRST, KW>(A, T.b + i, key.w); },
+        [&](const RxWords<KW>& key) { return rx_binw<KW>(key.w, shift, bits); });
 }
 
 template <bool FIRST, int KW>
@@ -548,14 +529,13 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
     __shared__ uint32_t s_wave_tot[4];
     __shared__ uint8_t sbin[RX_TILE];
     __shared__ uint32_t stage[RX_TILE];
-    int64_t seg, t;
-    if (!rx_find_tile(A.tile_base, A.n_seg, blockIdx.x, seg, t)) return;
-    const int tid = threadIdx.x, lane = tid & (HS_WAVE - 1), w = tid / HS_WAVE, F = 1 << A.bits;
-    const int64_t b = A.seg_start[seg] + t * RX_TILE;
-    const int64_t left = A.seg_start[seg + 1] - b;
-    const int rows = left < RX_TILE ? (int)left : RX_TILE;
+    RxTile T;
+    if (!rx_tile(A, T)) return;
+    const int tid = threadIdx.x, lane = tid & (HS_WAVE - 1), w = tid / HS_WAVE;
+    const int64_t b = T.b;
+    const int rows = T.rows;
     const int first = w * RX_SUB + lane;
-    for (int i = tid; i < RX_WAVES * F; i += RX_THREADS) whist[i / F][i % F] = 0;
+    rx_zero<RX_WAVES>(whist, 1 << A.bits);
     const int shift = A.shift, bits = A.bits;
     uint32_t bin8[RX_PER];
     {
@@ -570,49 +550,8 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
     const uint64_t below = (1ull << lane) - 1ull;
     uint32_t bl[RX_PER];  // bin | rank inside (wave, bin) << 8
 #pragma unroll
-    for (int j = 0; j < RX_PER; ++j) {
-        const bool valid = first + j * HS_WAVE < rows;
-        const uint32_t bin = bin8[j];
-        uint64_t peers = __ballot(valid);
-        for (int bit = 0; bit < bits; ++bit) {
-            const bool on = (bin >> bit) & 1u;
-            const uint64_t bal = __ballot(valid && on);
-            peers &= on ? bal : ~bal;
-        }
-        const uint32_t prior = valid ? whist[w][bin] : 0u;
-        const uint32_t rank = (uint32_t)__popcll(peers & below);
-        bl[j] = bin | ((prior + rank) << 8);
-        if (valid && rank == 0) whist[w][bin] = prior + (uint32_t)__popcll(peers);
-    }
-    __syncthreads();
-    const int64_t nt = A.tile_base[seg + 1] - A.tile_base[seg];
-    uint32_t bin_total = 0;
-    if (tid < F) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int k = 0; k < RX_WAVES; ++k) {
-            const uint32_t c = whist[k][tid];
-            whist[k][tid] = run;
-            run += c;
-        }
-        bin_total = run;
-        gbase[tid] = A.counters[(A.tile_base[seg] << A.bits) + (int64_t)tid * nt + t];
-    }
-    uint32_t x = bin_total;
-    for (int d = 1; d < HS_WAVE; d <<= 1) {
-        const uint32_t up = __shfl_up(x, d, HS_WAVE);
-        if (lane >= d) x += up;
-    }
-    if (w < 4 && lane == HS_WAVE - 1) s_wave_tot[w] = x;
-    __syncthreads();
-    if (tid < F) {
-        const uint32_t before = (w > 0 ? s_wave_tot[0] : 0u) + (w > 1 ? s_wave_tot[1] : 0u) + (w > 2 ? s_wave_tot[2] : 0u);
-        const uint32_t bin_start = before + x - bin_total;
-        gbase[tid] -= bin_start;
-#pragma unroll
-        for (int k = 0; k < RX_WAVES; ++k) whist[k][tid] += bin_start;
-    }
-    __syncthreads();
+    for (int j = 0; j < RX_PER; ++j) bl[j] = bin8[j] | (rx_rank(whist[w], bin8[j], first + j * HS_WAVE < rows, bits, below) << 8);
+    rx_bin_starts(A, T, whist, gbase, s_wave_tot);
     uint32_t at[RX_PER];
 #pragma unroll
     for (int j = 0; j < RX_PER; ++j) {
@@ -643,13 +582,7 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int j = 0; j < RX_PER; ++j)
             if (at[j] != 0xffffffffu) stage[at[j]] = v[j];
-        __syncthreads();
-        uint32_t* dst = (uint32_t*)A.dst[c];
-#pragma unroll
-        for (int k = 0; k < RX_PER; ++k) {
-            const int i = tid + k * RX_THREADS;
-            if (i < rows) dst[gbase[sbin[i]] + i] = stage[i];
-        }
+        rx_write_out((uint32_t*)A.dst[c], stage, sbin, gbase, rows);
     }
 }
 
@@ -1189,60 +1122,55 @@ enum {
     PL_OFF_CNT, PL_OFF_SCAN, PL_OFF_SCANWS, PL_OFF_PKEY, PL_OFF_PACC, PL_OFF_PCOUNT, PL_OFF_PSCAN, PL_OFF_OVERFLOW, PL_TUPLE, PL_ESIZE0 /* .. +16 */
 };
 
-// one partition pass over the segments of P: tiles, histogram, scan, scatter, the next level's segments
-static int rx_pass(hipStream_t stream, RxPass& P, int64_t max_tiles, int64_t* counters, int64_t* scanned, void* scan_ws, int64_t n,
-                   int64_t* next_seg) {
+// the instantiations of the pass's specialised kernels, by [KW - 2][FIRST], [NV][FIRST] and [FIRST]
+using RxKernel = void (*)(const RxPass);
+static constexpr RxKernel RX_HISTW[3][2] = {{k_rx_histw<false, 2>, k_rx_histw<true, 2>},
+                                            {k_rx_histw<false, 3>, k_rx_histw<true, 3>},
+                                            {k_rx_histw<false, 4>, k_rx_histw<true, 4>}};
+static constexpr RxKernel RX_SCATTERW[3][2] = {{k_rx_scatterw<false, 2>, k_rx_scatterw<true, 2>},
+                                               {k_rx_scatterw<false, 3>, k_rx_scatterw<true, 3>},
+                                               {k_rx_scatterw<false, 4>, k_rx_scatterw<true, 4>}};
+static constexpr RxKernel RX_HIST4[2] = {k_rx_hist4<false>, k_rx_hist4<true>};
+static constexpr RxKernel RX_SCATTER4[4][2] = {{k_rx_scatter4<0, false>, k_rx_scatter4<0, true>},
+                                               {k_rx_scatter4<1, false>, k_rx_scatter4<1, true>},
+                                               {k_rx_scatter4<2, false>, k_rx_scatter4<2, true>},
+                                               {k_rx_scatter4<3, false>, k_rx_scatter4<3, true>}};
+
+// one partition pass over the segments of `pass`: tiles, histogram, scan, scatter, the next level's segments
+static int rx_pass(hipStream_t stream, const RxPass& pass, int64_t max_tiles, int64_t* counters, int64_t* scanned, void* scan_ws,
+                   int64_t n, int64_t* next_seg) {
+    RxPass P = pass;
     hipLaunchKernelGGL(k_rx_tiles, dim3(1), dim3(1024), 0, stream, P.seg_start, P.n_seg, (int64_t*)P.tile_base);
     RX_CHECK_LAUNCH("radix pass (tiles)");
     const int64_t ncnt = max_tiles << P.bits;
     hs_memset_async(counters, 0, (size_t)ncnt * 8, stream);
     P.counters = counters;
-    // 4-byte tuples (INTEGER key, f32 / i32 values): the specialised kernels
-    bool four = !P.raw && P.n_cols <= 4 && (P.first ? P.key.kind == HS_I32 : P.esize[0] == 4);
+    // which kernels: a wide key's; for 4-byte tuples (INTEGER key, f32 / i32 values; not the raw sorts, whose bins are
+    // cut from 64-bit words) the specialised ones, and a key mix becomes the 32-bit one; else the generic pair
+    const int first = P.first ? 1 : 0, wide = P.mode == RX_BIN_WORDS ? P.wide : 0;
+    bool four = !wide && P.mode != RX_BIN_PLUS1 && P.mode != RX_BIN_VALUE && P.n_cols <= 4 &&
+                (first ? P.key.kind == HS_I32 : P.esize[0] == 4);
     for (int c = 1; c < P.n_cols; ++c) four = four && P.esize[c] == 4;
-    P.key4 = four ? 1 : 0;
-#define RX_WIDE(KERNEL, THREADS)                                                                                          \
-    switch (P.wide * 2 + (P.first ? 1 : 0)) {                                                                             \
-        case 4: hipLaunchKernelGGL((KERNEL<false, 2>), dim3((unsigned)max_tiles), dim3(THREADS), 0, stream, P); break;    \
-        case 5: hipLaunchKernelGGL((KERNEL<true, 2>), dim3((unsigned)max_tiles), dim3(THREADS), 0, stream, P); break;     \
-        case 6: hipLaunchKernelGGL((KERNEL<false, 3>), dim3((unsigned)max_tiles), dim3(THREADS), 0, stream, P); break;    \
-        case 7: hipLaunchKernelGGL((KERNEL<true, 3>), dim3((unsigned)max_tiles), dim3(THREADS), 0, stream, P); break;     \
-        case 8: hipLaunchKernelGGL((KERNEL<false, 4>), dim3((unsigned)max_tiles), dim3(THREADS), 0, stream, P); break;    \
-        default: hipLaunchKernelGGL((KERNEL<true, 4>), dim3((unsigned)max_tiles), dim3(THREADS), 0, stream, P); break;    \
-    }
-    if (P.wide) {
-        RX_WIDE(k_rx_histw, RX_H4_THREADS)
-    } else if (four) {
-        if (P.first) hipLaunchKernelGGL(k_rx_hist4<true>, dim3((unsigned)max_tiles), dim3(RX_H4_THREADS), 0, stream, P);
-        else hipLaunchKernelGGL(k_rx_hist4<false>, dim3((unsigned)max_tiles), dim3(RX_H4_THREADS), 0, stream, P);
-    } else {
-        hipLaunchKernelGGL(k_rx_hist, dim3((unsigned)max_tiles), dim3(RX_THREADS), 0, stream, P);
-    }
-    RX_CHECK_LAUNCH("radix pass (histogram)");
-    const int rc = hs_exclusive_scan_i64(stream, counters, ncnt, scanned, scan_ws);
-    if (rc != HS_OK) return rc;
-    P.counters = scanned;
+    if (four && P.mode == RX_BIN_MIX64) P.mode = RX_BIN_MIX32;
     int widest = 1;
     for (int c = 0; c < P.n_cols; ++c) widest = P.esize[c] > widest ? P.esize[c] : widest;
+    auto launch = [&](const char* what, RxKernel kernel, int threads, size_t dynamic_lds) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)max_tiles), dim3(threads), dynamic_lds, stream, P);
+        if (hipGetLastError() == hipSuccess) return HS_OK;
+        hs_set_error("radix pass (%s): kernel launch failed", what);
+        return HS_E_LAUNCH;
+    };
+    int rc = launch("histogram", wide ? RX_HISTW[wide - 2][first] : four ? RX_HIST4[first] : k_rx_hist, wide || four ? RX_H4_THREADS : RX_THREADS, 0);
+    if (rc != HS_OK) return rc;
+    rc = hs_exclusive_scan_i64(stream, counters, ncnt, scanned, scan_ws);
+    if (rc != HS_OK) return rc;
+    P.counters = scanned;
     static unsigned long long attr_set = 0;
     if (hs_first_on_device(attr_set))  // 8-byte columns stage 72 KB + 18 KB static: above the 64 KB a launch gets unasked
         (void)hipFuncSetAttribute((const void*)k_rx_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, RX_TILE * 9);
-    if (P.wide) {
-        RX_WIDE(k_rx_scatterw, RX_THREADS)
-    } else if (four) {
-#define RX_S4(NV)                                                                                                         \
-    if (P.first) hipLaunchKernelGGL((k_rx_scatter4<NV, true>), dim3((unsigned)max_tiles), dim3(RX_THREADS), 0, stream, P); \
-    else hipLaunchKernelGGL((k_rx_scatter4<NV, false>), dim3((unsigned)max_tiles), dim3(RX_THREADS), 0, stream, P)
-        switch (P.n_cols - 1) {
-            case 0: RX_S4(0); break;
-            case 1: RX_S4(1); break;
-            case 2: RX_S4(2); break;
-            default: RX_S4(3); break;
-        }
-#undef RX_S4
-#undef RX_WIDE
-    } else hipLaunchKernelGGL(k_rx_scatter, dim3((unsigned)max_tiles), dim3(RX_THREADS), (size_t)RX_TILE * (1 + widest), stream, P);
-    RX_CHECK_LAUNCH("radix pass (scatter)");
+    rc = launch("scatter", wide ? RX_SCATTERW[wide - 2][first] : four ? RX_SCATTER4[P.n_cols - 1][first] : k_rx_scatter, RX_THREADS,
+                wide || four ? 0 : (size_t)RX_TILE * (1 + widest));
+    if (rc != HS_OK) return rc;
     if (next_seg) {
         const int64_t nout = (P.n_seg << P.bits) + 1;
         hipLaunchKernelGGL(k_rx_next, dim3((unsigned)((nout + 255) / 256 > 4096 ? 4096 : (nout + 255) / 256)), dim3(256), 0, stream,
@@ -1401,6 +1329,7 @@ extern "C" int hs_group_radix_run(void* stream_, const hs_radix_plan* plan, cons
     const int kcols = wide ? wide : 1;
     P.n_cols = kcols + (int)f[PL_NCARRIED];
     P.wide = wide;
+    P.mode = wide ? RX_BIN_WORDS : RX_BIN_MIX64;
     P.key = *key;
     P.sel = sel;
     P.row0 = row0;
@@ -1686,7 +1615,7 @@ extern "C" int hs_sort_by_order(void* stream_, const int64_t* order, int64_t n, 
     P.n_seg = 1;
     P.n_cols = 2;
     P.esize[0] = P.esize[1] = 8;
-    P.raw = 1;
+    P.mode = RX_BIN_PLUS1;
     for (int k = 0; k < passes; ++k) {
         const bool to_out = ((passes - 1 - k) & 1) == 0;  // the last pass lands in the caller's arrays
         P.first = k == 0 ? 1 : 0;
@@ -2107,7 +2036,7 @@ static int ob_sort(hipStream_t stream, const hs_col* keys, const int32_t* descen
         P.n_seg = 1;
         P.n_cols = 2;
         P.esize[0] = P.esize[1] = 8;
-        P.raw = 2;
+        P.mode = RX_BIN_VALUE;
         P.bits = 8;
         const int64_t tiles = m / RX_TILE + 2;
         for (int w = n_words - 1; w >= 0; --w) {
@@ -2847,7 +2776,7 @@ extern "C" int hs_expand_by_bounds(void* stream, const int64_t* bounds, const in
 // probe row emits its matches in that order; duplicates on either side multiply (zig twin: tasks.zig:70-194, 258-326).
 // Round 1-3 built one open-addressing table over all build keys with a 64-bit atomic per row scattered over 800 MB
 // (8.6 G keys/s, 5.6 % of the HBM roofline).  Here the build side is MOVED instead, like the radix tier of GROUP BY:
-//   1. two stable partition passes (the kernels above, RxPass.range) on the most significant bits of slot = key - key_min
+//   1. two stable partition passes (the kernels above, RX_BIN_RANGE) on the most significant bits of slot = key - key_min
 //      bring the (key, row) tuples into partitions of 2^L consecutive slots, still in row order;
 //   2. one wave per partition (k_jd_assemble): slot counts in LDS, a scan, then the rows are placed IN ORDER - lanes of a
 //      64-tuple step that share a slot rank themselves with ballots - so every slot's rows come out ascending without a
@@ -3122,10 +3051,10 @@ struct JxTuples {
     const int64_t* seg;  // [parts + 1]
     int64_t parts;
 };
-// Row ids, then one or two stable partition passes (RxPass.range = range, range_bias = bias) on the bits1 + bits2 bits of
+// Row ids, then one or two stable partition passes (RxPass.mode = mode, range_bias = bias) on the bits1 + bits2 bits of
 // the 4-byte partition key `key` above bit `low`; `third` (4 bytes per row, or null) travels along.  Without passes (one
 // partition) the tuples are the columns themselves and the row ids 0 .. n-1; without rows every partition is empty.
-static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const JxLayout& Y, int64_t n, const void* key, int range,
+static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const JxLayout& Y, int64_t n, const void* key, RxBin mode,
                         int32_t bias, int low, const uint32_t* third, JxTuples& T) {
     uint32_t* iota = (uint32_t*)(ws + Y.iota);
     int64_t* seg0 = (int64_t*)(ws + Y.seg0);
@@ -3152,7 +3081,7 @@ static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const 
     P.n_cols = third ? 3 : 2;
     P.esize[0] = P.esize[1] = 4;
     if (third) P.esize[2] = 4;
-    P.range = range;
+    P.mode = mode;
     P.range_bias = bias;
     P.key = hs_col{HS_I32, -1, key, nullptr, nullptr};
     P.row0 = 0;
@@ -3227,7 +3156,7 @@ extern "C" int hs_join_dense_build(void* stream_, const int32_t* build_keys, int
     }
     hipStream_t stream = (hipStream_t)stream_;
     JxTuples T;
-    const int rc = jx_partition(stream, "hs_join_dense_build", (uint8_t*)ws_, Y, n_build, build_keys, 1, key_min, Y.L, nullptr, T);
+    const int rc = jx_partition(stream, "hs_join_dense_build", (uint8_t*)ws_, Y, n_build, build_keys, RX_BIN_RANGE, key_min, Y.L, nullptr, T);
     if (rc != HS_OK) return rc;
     const JdAssemble A{T.seg, T.parts, (const int32_t*)T.keys, T.rows, slots, key_min, Y.L, words, rows, list_count, n_build, flags};
     const size_t per_wave = (size_t)9 << Y.L;  // cursors + first rows (uint32) + tag bytes
@@ -3393,7 +3322,7 @@ extern "C" int hs_join_dense_fill(void* stream, int64_t n_probe, const uint32_t*
 // negative keys, a few hot values.  The table is an open-addressing table of 8-byte slots {key, word} cut into WINDOWS of
 // 2^JH_L slots; a key belongs to window jh_window(key) and probes linearly INSIDE it (wrapping at the window's end), so
 //   * the build never leaves LDS: the (key, row) tuples are brought into window order by the two stable partition passes
-//     (RxPass.range = 2), one wave per window inserts its keys into an LDS copy of the window (ds_cmpst on a 64-bit cell),
+//     (RX_BIN_WINDOW), one wave per window inserts its keys into an LDS copy of the window (ds_cmpst on a 64-bit cell),
 //     counts, scans and places the rows in order exactly like the dense form, and stores the finished window with coalesced
 //     8-byte stores - no global atomic, no scattered store, every list ascending without a sort;
 //   * a probe is ONE scattered 8-byte read in the usual case (the slot holds key and word together; at a load of ~0.57 a
@@ -3517,7 +3446,7 @@ extern "C" int hs_join_hash_build(void* stream_, const int32_t* build_keys, int6
     hipStream_t stream = (hipStream_t)stream_;
     uint8_t* ws = (uint8_t*)ws_;
     JxTuples T;
-    const int rc = jx_partition(stream, "hs_join_hash_build", ws, Y, n_build, build_keys, 2, (int32_t)Y.windows, 0, nullptr, T);
+    const int rc = jx_partition(stream, "hs_join_hash_build", ws, Y, n_build, build_keys, RX_BIN_WINDOW, (int32_t)Y.windows, 0, nullptr, T);
     if (rc != HS_OK) return rc;
     return jh_assemble<false>(stream, "hs_join_hash_build", Y, T, hs_col{}, ws, table, rows, list_count, status, flags);
 }
@@ -3594,7 +3523,7 @@ extern "C" int hs_join_hash_count(void* stream, const int32_t* probe_keys, int64
 // usual case.  A fingerprint never decides a match on its own: the probe compares the key's bytes with the first build row
 // of the slot's list, the build compares bytes with the slot's representative row whenever a fingerprint is met again (a
 // duplicate key, or - rarely - another key of the same fingerprint in the same window, which then takes its own slot).
-// Build: one pass hashes every key (window number, fingerprint), two stable partition passes (RxPass.range = 1 on the
+// Build: one pass hashes every key (window number, fingerprint), two stable partition passes (RX_BIN_RANGE on the
 // window number) bring the (window, row, fingerprint) tuples into window order, and one wave per window inserts, counts,
 // scans and places them in LDS: k_jh_assemble<L, true>.  Geometry (windows, L, workspace arrays) is jx_layout's.
 __device__ __forceinline__ uint32_t js_window(uint64_t m, uint32_t windows) { return (uint32_t)(((m >> 32) * (uint64_t)windows) >> 32); }
@@ -3683,9 +3612,9 @@ extern "C" int hs_join_hash_str_build(void* stream_, const hs_col* build_key, in
         hipLaunchKernelGGL(k_js_hash, dim3((unsigned)g), dim3(256), 0, stream, *build_key, n, (uint32_t)Y.windows, win, fp);
         RX_CHECK_LAUNCH("hs_join_hash_str_build (hash)");
     }
-    // the partition key is the window number itself (RxPass.range = 1, no bias); the fingerprint travels along
+    // the partition key is the window number itself (RX_BIN_RANGE, no bias); the fingerprint travels along
     JxTuples T;
-    const int rc = jx_partition(stream, "hs_join_hash_str_build", ws, Y, n, win, 1, 0, 0, fp, T);
+    const int rc = jx_partition(stream, "hs_join_hash_str_build", ws, Y, n, win, RX_BIN_RANGE, 0, 0, fp, T);
     if (rc != HS_OK) return rc;
     return jh_assemble<true>(stream, "hs_join_hash_str_build", Y, T, *build_key, ws, table, rows, list_count, status, flags);
 }

@@ -223,6 +223,102 @@ def test_radix_tier_takes_float_and_short_string_keys(dev):
     assert dev.lib.hs_group_radix_plan(hs.STR + 256 * 12, 1000, 1, 1000, kinds, C.byref(spec), 1, C.byref(plan)) == 2
 
 
+def _string_groups(dev, rows, sel, bounds, v):
+    """SUM(v), COUNT by the fixed-length STRING rows (through `sel` when given; v is position-indexed) -> per unit
+    {key bytes: (sum as f32, count)}, and the same from a Python dict filled in row order."""
+    import torch
+
+    from minispark_amd import hipspark as hs
+    from minispark_amd.device import DCol
+
+    n_rows, length = rows.shape
+    n = len(sel) if sel is not None else n_rows
+    key = DCol(hs.STR, torch.from_numpy(np.ascontiguousarray(rows).reshape(-1)).cuda(), n_rows,
+               lens=torch.full((n_rows,), length, dtype=torch.uint8, device="cuda"), offs=None, fixed_len=length)
+    tb = torch.from_numpy(np.asarray(bounds, dtype=np.int64)).cuda()
+    done = dev.group_radix(key, torch.from_numpy(sel).cuda() if sel is not None else None, n, tb, len(bounds) - 1,
+                           max(b - a for a, b in zip(bounds, bounds[1:])),
+                           [(DCol(hs.F32, torch.from_numpy(v).cuda(), n), 0, False), (None, 1, True)], [hs.AGG_SUM, hs.AGG_SUM], True)
+    assert done is not None
+    key_col, accs, unit_rows = done
+    assert dev.read_flags() == 0
+    kb = key_col.data[: key_col.n * length].cpu().numpy().reshape(-1, length)
+    a = [c.data[: c.n].cpu().numpy() for c in accs]
+    seen = rows[sel] if sel is not None else rows
+    got, want = [], []
+    for u, (lo, hi) in enumerate(zip(unit_rows, unit_rows[1:])):
+        got.append({bytes(r): (a[0][lo + i].item(), a[1][lo + i].item()) for i, r in enumerate(kb[lo:hi])})
+        assert len(got[-1]) == hi - lo, f"unit {u}: a key twice in one unit"
+        fold: dict = {}
+        for r, x in zip(seen[bounds[u]:bounds[u + 1]], v[bounds[u]:bounds[u + 1]].astype(np.float64).tolist()):
+            s, c = fold.get(bytes(r), (0.0, 0))
+            fold[bytes(r)] = (s + x, c + 1)
+        want.append({k: (np.float32(s).item(), c) for k, (s, c) in fold.items()})
+    return got, want
+
+
+@pytest.mark.parametrize("with_sel", [False, True])
+@pytest.mark.parametrize("shape", ["f32,f64", "1", "f32", "f32,i32", "f32,i32,f32", "str8", "str12", "str16"])
+@pytest.mark.parametrize("n", [8191, 8192, 8193, 16385])
+def test_radix_tier_at_the_edges_of_a_tile(dev, n, shape, with_sel):
+    """A partition tile is 8192 rows: one row short of a tile, a full tile, a tile and a one-row tail, and (16385) a
+    full tile, an EMPTY unit and a unit of a tile and a one-row tail - through every kernel family of the pass: the
+    generic one (an 8-byte column travels), the 4-byte one with 0 .. 3 value columns, the wide STRING one with 2, 3 and
+    4 key words; each also behind a selection that drops every third row (the first pass reads through the row list)."""
+    from minispark_amd import hipspark as hs
+
+    rng = np.random.default_rng(n + len(shape))
+    bounds = [0, 8192, 8192, n] if n > 8192 else [0, n]
+    total = n + n // 2 if with_sel else n
+    sel = np.flatnonzero(np.arange(total) % 3 != 2).astype(np.int64)[:n] if with_sel else None
+    assert sel is None or len(sel) == n
+    if shape.startswith("str"):
+        length = int(shape[3:])
+        alphabet = np.frombuffer(b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghij0123456789", dtype=np.uint8)
+        words = alphabet[rng.integers(0, len(alphabet), (n // 2, length))]
+        words[: len(words) // 2, :8] = words[0, :8]  # many keys that agree in their first two words
+        rows = words[rng.integers(0, len(words), total)]
+        got, want = _string_groups(dev, rows, sel, bounds, rng.normal(0, 10, n).astype(np.float32))
+        assert got == want
+        return
+    keys = rng.integers(-(n // 4), n // 2 - n // 4, total).astype(np.int32)
+    make = {"f32": lambda: (rng.normal(0, 1, n) * np.exp2(rng.integers(-8, 8, n))).astype(np.float32),
+            "f64": lambda: rng.normal(0, 1e3, n), "i32": lambda: rng.integers(-1000, 1000, n).astype(np.int32), "1": lambda: 1}
+    values = [make[c]() for c in shape.split(",")]
+    is_int = [c in ("i32", "1") for c in shape.split(",")]
+    ops = [hs.AGG_SUM] * len(values)
+    got = _run(dev, keys, hs.I32, sel, bounds, values, ops, True)
+    _same(got, _expected(keys[sel] if with_sel else keys, values, ops, is_int, bounds, True))
+
+
+def test_radix_tier_two_passes_at_the_smallest_size_that_has_them(dev):
+    """The plan takes a second pass once the largest unit exceeds (cap / 2) << 8 rows - with three SUMs just over
+    131 072.  One unit of that size plus one and a unit of 5 rows: after the first pass hundreds of segments are
+    shorter than a tile or empty, which is what the tile lookup of the second pass has to walk."""
+    import ctypes as C
+
+    from minispark_amd import hipspark as hs
+
+    rng = np.random.default_rng(131)
+    big = 131_073
+    n, bounds = big + 5, [0, big, big + 5]
+    plan, spec = hs.hs_radix_plan(), hs.hs_agg_spec()
+    spec.n_acc = 3
+    for a in range(3):
+        spec.op[a], spec.is_int[a] = hs.AGG_SUM, int(a == 1)
+    kinds = (C.c_int32 * 3)(hs.F32, hs.I32, hs.F32)
+    assert dev.lib.hs_group_radix_plan(hs.I32, n, 2, big, kinds, C.byref(spec), 1, C.byref(plan)) == 0
+    assert plan.f[3] > 0, "the shape no longer takes two passes (bits2 == 0)"
+    assert dev.lib.hs_group_radix_plan(hs.I32, n - 1, 2, big - 1, kinds, C.byref(spec), 1, C.byref(plan)) == 0
+    assert plan.f[3] == 0, "a smaller shape has two passes too: this one is not the smallest"
+    keys = rng.integers(-30_000, 30_000, n).astype(np.int32)
+    values = [rng.normal(0, 1, n).astype(np.float32), rng.integers(-1000, 1000, n).astype(np.int32),
+              rng.normal(0, 100, n).astype(np.float32)]
+    ops, is_int = [hs.AGG_SUM] * 3, [False, True, False]
+    got = _run(dev, keys, hs.I32, None, bounds, values, ops, True)
+    _same(got, _expected(keys, values, ops, is_int, bounds, True))
+
+
 def test_radix_tier_over_a_selection_and_timestamp_keys(dev):
     """WHERE survivors arrive as an ascending row list; the key is read through it, values are position-indexed."""
     from minispark_amd import hipspark as hs
@@ -294,7 +390,8 @@ def test_engine_takes_the_radix_tier_for_integer_keys(tmp_path):
         assert engine.dev.last_global_tier == "hash"
 
 
-@pytest.mark.parametrize(("n", "n_order"), [(1, 1), (5000, 3), (300_000, 287), (1_000_000, 70_000)])
+@pytest.mark.parametrize(("n", "n_order"), [(1, 1), (5000, 3), (300_000, 287), (1_000_000, 70_000),
+                                                 (8192, 300), (8193, 70_000)])  # two, three passes; a one-row tail
 def test_sort_by_order_is_a_stable_sort_with_padding_first(dev, n, n_order):
     """hs_sort_by_order (the merge order of a multi-rank final aggregate) against numpy's stable argsort."""
     import torch
