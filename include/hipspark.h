@@ -324,12 +324,24 @@ int hs_agg_shared(void* stream, const hs_col* cols, int32_t n_cols, int32_t key_
 /* The same with COMPUTED units: rows are not grouped by unit; cols[unit_col] (HS_U8, a preloaded slot < 8) gives
  * every row's unit id in [0, n_unit_tables), 0xff = the row takes no part.  This is how the probe side of a join is
  * aggregated per shuffle partition (the reference's JoinJob, plan.py:99-109) without ever being partitioned in
- * memory: hs_join_probe_unique writes the id column.  chunks / geom: from hs_agg_shared_geom over the ONE row range
- * [0, nrows); geom->pad = slots of ONE unit's table, which the caller may lower (power of two >= 16) to what a unit
- * is expected to hold - HS_FLAG_DICT_FULL reports a unit that outgrew it; outputs sized for n_unit_tables units of
- * geom->pad slots; ws: (n_unit_tables * geom->pad * 8 + 256, rounded up to 16) + geom->n_chunks * n_unit_tables *
- * geom->pad * n_acc * 8 bytes (every chunk leaves its cells in its own slice, a small kernel folds them per unit
- * cell: no contended global atomics).  The key must fit 56 bits of its key word (INTEGER, or a string of fixed length <= 6): HS_E_LIMIT else. */
+ * memory: hs_join_probe_unique writes the id column.  geom: from hs_agg_shared_units_geom (caller_keys = 0), chunks:
+ * hs_agg_partial_chunks of it over the ONE row range [0, nrows); geom->pad = slots of ONE unit's table -
+ * HS_FLAG_DICT_FULL reports a unit that outgrew it; outputs sized for n_unit_tables units of geom->pad slots; ws:
+ * geom->ws_bytes (every chunk leaves its cells in its own slice, a small kernel folds them per unit cell: no contended
+ * global atomics).  The key must fit 56 bits of its key word (INTEGER, or a string of fixed length <= 6): HS_E_LIMIT else. */
+/* Geometry of a computed-units launch: hs_agg_shared_geom over the one row range [0, nrows), then
+ *   pad      = min(pad, P) with P the smallest power of two >= 16 and >= 4 * max(4, group_cap / n_unit_tables): a
+ *              unit's table is sized for the groups ONE unit holds (its share of the capacity, x4 for open addressing),
+ *              not for the LDS table that holds every (unit, key) pair - so n_unit_tables * pad partial rows stay few
+ *              enough for the on-chip final merge;
+ *   ws_bytes = K + max(n_chunks, 1) * n_unit_tables * pad * max(n_acc, 1) * 8 (the per-chunk cells), with
+ *              K = n_unit_tables * pad * 8 + 256 rounded up to 16 (the unit tables' key words, in front) for
+ *              caller_keys = 0 (hs_agg_shared_units), K = 0 for caller_keys != 0 (hs_agg_shared_join8, whose key words
+ *              are the caller's unit_keys).
+ * The launchers index `ws` by the same rule.  n_unit_tables 1..127, nrows >= 0: HS_E_ARG else; HS_E_LIMIT as
+ * hs_agg_shared_geom. */
+int hs_agg_shared_units_geom(int64_t nrows, int32_t n_unit_tables, int32_t n_acc, int32_t group_cap, int32_t caller_keys,
+                             hs_agg_geom* out);
 int hs_agg_shared_units(void* stream, const hs_col* cols, int32_t n_cols, int32_t key_col, int32_t unit_col,
                         int32_t n_unit_tables, const hs_program* prog, const hs_agg_spec* spec, const hs_chunk* chunks,
                         const hs_agg_geom* geom, int64_t* out_rep, uint64_t* out_acc, int32_t* out_ngroups, void* ws,
@@ -342,8 +354,8 @@ int hs_agg_shared_units(void* stream, const hs_col* cols, int32_t n_cols, int32_
  * with hs_join_probe_unique instead).  Leaves the units' tables RAW - key words unit_keys[n_unit_tables * geom->pad]
  * (HS_EMPTY = free slot; the unit id in the top byte) and un-rounded 64-bit cells unit_acc[n_unit_tables * geom->pad *
  * n_acc] - so that the shares of N ranks can be added up BEFORE the rounding the reference applies once per JoinJob
- * (tasks.py:373 -> io.py:87-94).  ws: geom->n_chunks * n_unit_tables * geom->pad * n_acc * 8 bytes; out_rep scratch
- * [n_unit_tables * geom->pad]. */
+ * (tasks.py:373 -> io.py:87-94).  geom: from hs_agg_shared_units_geom with caller_keys = 1; ws: geom->ws_bytes; out_rep
+ * scratch [n_unit_tables * geom->pad]. */
 int hs_agg_shared_join8(void* stream, const hs_col* cols, int32_t n_cols, int32_t key_col, int32_t unit_col,
                         const hs_join8* join, int32_t n_unit_tables, const hs_program* prog, const hs_agg_spec* spec,
                         const hs_chunk* chunks, const hs_agg_geom* geom, int64_t* out_rep, uint64_t* unit_keys,

@@ -1158,6 +1158,11 @@ void hs_set_error(const char* fmt, ...);
 // hs_jit.cpp: HS_OK = a kernel compiled for this program was launched; anything else = not launched
 int hs_jit_launch_agg_main(const AggMainArgs* args, bool hashed, unsigned grid, unsigned block, size_t lds_bytes,
                            hipStream_t stream);
+int hs_jit_launch_agg_scalar(const AggMainArgs* args, unsigned grid, unsigned block, size_t lds_bytes, hipStream_t stream);
+int hs_jit_launch_agg_shared(const AggMainArgs* args, bool hashed, unsigned grid, unsigned block, size_t lds_bytes,
+                             hipStream_t stream);
+extern "C" int hs_jit_get_enabled(void);
+extern "C" const char* hs_jit_last_log(void);
 
 static int fill_cols(HsCols& dst, const hs_col* cols, int32_t n) {
     if (n < 0 || n > HS_MAX_COLS) {
@@ -1215,6 +1220,68 @@ static int program_depth(const hs_program* p) {
     return d;
 }
 
+// ---- launch prologue: what every tier checks about its columns and program before it launches, stated once -------------
+struct ScanTier {
+    const char* who;            // prefix of every message
+    bool narrow;                // narrow argument columns are read; else any narrow column is refused, first of all
+    bool by_column;             // keyless tier: slot rule and kind rule alternate column by column, not rule by rule
+    bool probe;                 // the fused probe: HS_JOIN8_* columns are its own, HS_PAIR columns are not
+    const char* pair_refusal;   // HS_PAIR columns are refused with this text; NULL = read, as argument slots with pair rows
+    const char* join8_refusal;  // HS_JOIN8_* columns are refused with this text; NULL = not looked at
+};
+
+// Fills `dst` from `cols`; -> HS_OK with the program's stack depth (and whether HS_PAIR columns are read), or the refusal.
+static int scan_check(const ScanTier& T, HsCols& dst, const hs_col* cols, int32_t n_cols, int32_t key_col,
+                      const hs_program* prog, int64_t n_chunks, int* depth, bool* pairs = nullptr) {
+    if (!T.narrow && hs_refuse_narrow(T.who, cols, n_cols)) return HS_E_ARG;
+    if (prog->n_ins > HS_MAX_INS || prog->n_lit > HS_MAX_LIT) {
+        hs_set_error("%s: program too long", T.who);
+        return HS_E_LIMIT;
+    }
+    int rc = fill_cols(dst, cols, n_cols);
+    if (rc) return rc;
+    for (int pass = T.by_column ? 1 : 0; pass < 2; ++pass) {  // pass 0: the slot rule alone; pass 1: the kinds
+        for (int i = 0; i < n_cols; ++i) {
+            const int32_t kind = cols[i].kind;
+            // numeric columns and a preloaded key must sit in the first HS_FUSED_COLS slots
+            if ((pass == 0 || T.by_column) && i >= HS_FUSED_COLS && (kind != HS_STR || i == key_col)) {
+                hs_set_error("%s: more than %d numeric column slots", T.who, HS_FUSED_COLS);
+                return HS_E_LIMIT;
+            }
+            if (pass == 0) continue;
+            if ((kind == HS_JOIN8_CODE || kind == HS_JOIN8_UNIT) && T.join8_refusal) {
+                hs_set_error("%s: %s", T.who, T.join8_refusal);
+                return HS_E_ARG;
+            }
+            if (!(kind & HS_PAIR)) continue;
+            const int base = kind & ~HS_PAIR;
+            if (T.pair_refusal) {
+                hs_set_error("%s: %s", T.who, T.pair_refusal);
+                return HS_E_ARG;
+            }
+            if (T.probe || i == key_col || (base != HS_I32 && base != HS_F32 && base != HS_I64) || !cols[i].offs) {
+                hs_set_error("%s: an HS_PAIR column is an INTEGER / FLOAT / TIMESTAMP argument slot with its pair rows", T.who);
+                return HS_E_ARG;
+            }
+            if (pairs) *pairs = true;  // pair-indexed columns: only the run-time compiled scan reads them
+        }
+    }
+    if (T.narrow) {
+        rc = check_narrow_cols(T.who, cols, n_cols, key_col, prog);
+        if (rc) return rc;
+    }
+    *depth = program_depth(prog);
+    if (*depth > HS_MAX_STACK) {
+        hs_set_error("%s: expression stack depth %d > %d", T.who, *depth, HS_MAX_STACK);
+        return HS_E_LIMIT;
+    }
+    if (n_chunks > 0x7fffffffll) {
+        hs_set_error("%s: too many chunks", T.who);
+        return HS_E_LIMIT;
+    }
+    return HS_OK;
+}
+
 static constexpr size_t HS_LDS_SOFT = 64 * 1024;   // keeps >= 2 workgroups per CU resident
 static constexpr size_t HS_LDS_HARD = 144 * 1024;  // one workgroup per CU (gfx950: 160 KiB per CU)
 
@@ -1227,6 +1294,49 @@ static size_t hs_agg_partials_bytes(int64_t n_chunks, int32_t group_cap, int32_t
 
 static size_t agg_main_lds(int32_t group_cap, int32_t n_acc, int wg) {
     return (size_t)group_cap * 16 + (size_t)group_cap * (size_t)n_acc * (size_t)wg * 8;
+}
+
+// ---- geometry: the rules every tier's *_geom shares, each stated once ----------------------------------------------
+// Rows of all units, or -1 (and the error text) when a boundary runs backwards.
+static int64_t unit_rows_total(const char* who, const int64_t* host_unit_rows, int64_t n_units) {
+    int64_t total = 0;
+    for (int64_t u = 0; u < n_units; ++u) {
+        const int64_t r = host_unit_rows[u + 1] - host_unit_rows[u];
+        if (r < 0) {
+            hs_set_error("%s: unit_rows not ascending at %lld", who, (long long)u);
+            return -1;
+        }
+        total += r;
+    }
+    return total;
+}
+
+// A unit's chunks start at its first row rounded DOWN to a quad (hs_chunk.row_begin is a multiple of HS_V; the rows
+// before the unit are masked by unit_begin) and never span units.
+static int64_t unit_anchor(int64_t unit_begin) { return unit_begin & ~(int64_t)(HS_V - 1); }
+static int64_t count_chunks(const int64_t* host_unit_rows, int64_t n_units, int64_t chunk) {
+    int64_t n = 0;
+    for (int64_t u = 0; u < n_units; ++u) {
+        const int64_t span = host_unit_rows[u + 1] - unit_anchor(host_unit_rows[u]);
+        n += span > 0 ? (span + chunk - 1) / chunk : 0;
+    }
+    return n;
+}
+
+// Compute units of the device the geometry is made for; 256 without one (a host that only does the arithmetic).  An
+// MI355X has 256 as well, so both give the same geometry.
+static int n_cus() {
+    static int n = 0;
+    if (!n) {
+        hipDeviceProp_t prop;
+        int dev = 0;
+        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
+             prop.multiProcessorCount > 0)
+                ? prop.multiProcessorCount
+                : 256;
+        (void)hipGetLastError();
+    }
+    return n;
 }
 
 static int agg_geom_chunks(const char* who, const int64_t* host_unit_rows, int64_t n_units, int wg, size_t lds,
@@ -1270,36 +1380,19 @@ extern "C" int hs_agg_partial_geom(const int64_t* host_unit_rows, int64_t n_unit
 // of LDS per workgroup.
 static int agg_geom_chunks(const char* who, const int64_t* host_unit_rows, int64_t n_units, int wg, size_t lds,
                            hs_agg_geom* out) {
-    int64_t total = 0;
-    for (int64_t u = 0; u < n_units; ++u) {
-        const int64_t r = host_unit_rows[u + 1] - host_unit_rows[u];
-        if (r < 0) {
-            hs_set_error("%s: unit_rows not ascending at %lld", who, (long long)u);
-            return HS_E_ARG;
-        }
-        total += r;
-    }
+    const int64_t total = unit_rows_total(who, host_unit_rows, n_units);
+    if (total < 0) return HS_E_ARG;
     // Rows per workgroup = steps_per_chunk * wg * V.  Model from a chunk-size sweep on MI355X:
     // a workgroup costs ~11 us fixed + ~3.4 us per step, and `wg_slots` workgroups run at once (LDS-limited).
     // Pick the number of full-chip rounds R that keeps chunks <= 128 steps, then the chunk length that
     // fills those rounds exactly: few, long chunks without a ragged last round.
     const int64_t step = (int64_t)wg * HS_V;
-    static int n_cus = 0;
-    if (!n_cus) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        n_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                 prop.multiProcessorCount > 0)
-                    ? prop.multiProcessorCount
-                    : 256;
-        (void)hipGetLastError();
-    }
     int64_t per_cu = (int64_t)(160 * 1024) / (int64_t)(lds > 1 ? lds : 1);
     const int64_t by_waves = 32 / (wg / 64);
     if (per_cu > by_waves) per_cu = by_waves;
     if (per_cu > 8) per_cu = 8;
     if (per_cu < 1) per_cu = 1;
-    const int64_t wg_slots = (int64_t)n_cus * per_cu;
+    const int64_t wg_slots = (int64_t)n_cus() * per_cu;
     const int64_t total_steps = (total + step - 1) / step;
     int64_t steps_per_chunk;
     if (const char* e = getenv("HIPSPARK_CHUNK_STEPS")) {  // tuning knob
@@ -1313,31 +1406,20 @@ static int agg_geom_chunks(const char* who, const int64_t* host_unit_rows, int64
         // every unit rounds its chunk count up: lengthen the chunks until the grid really fits the rounds
         // (a handful of workgroups spilling into an extra round would cost a whole round)
         for (int guard = 0; guard < 64; ++guard) {
-            int64_t n = 0;
-            for (int64_t u = 0; u < n_units; ++u) {
-                const int64_t span = host_unit_rows[u + 1] - (host_unit_rows[u] & ~(int64_t)(HS_V - 1));
-                n += span > 0 ? (span + step * steps_per_chunk - 1) / (step * steps_per_chunk) : 0;
-            }
-            if (n <= wg_slots * rounds) break;
+            if (count_chunks(host_unit_rows, n_units, step * steps_per_chunk) <= wg_slots * rounds) break;
             ++steps_per_chunk;
         }
         // small tables: a workgroup costs ~11 us before its first and after its last step, and the unit combine in the last
         // one's epilogue walks the unit's chunks in batches of 64 - filling every workgroup slot with one- or two-step chunks
         // is slower than fewer, longer ones as long as every CU still gets one.  Measured at sf=1 (6 M rows, 3 units;
         // profiles/r04_chunk_steps_sweep.txt): 8 steps (733 chunks) 94 us, 16 steps (367) 73 us, 32 steps (184) 82 us.
-        int64_t floor = total_steps / n_cus;
+        int64_t floor = total_steps / n_cus();
         floor = floor < 1 ? 1 : (floor > 16 ? 16 : floor);
         if (steps_per_chunk < floor) steps_per_chunk = floor;
     }
     if (steps_per_chunk < 1) steps_per_chunk = 1;
     if (steps_per_chunk > 4096) steps_per_chunk = 4096;
     const int64_t chunk = step * steps_per_chunk;
-    int64_t n_chunks = 0;
-    for (int64_t u = 0; u < n_units; ++u) {
-        const int64_t anchor = host_unit_rows[u] & ~(int64_t)(HS_V - 1);
-        const int64_t span = host_unit_rows[u + 1] - anchor;
-        n_chunks += span > 0 ? (span + chunk - 1) / chunk : 0;
-    }
     bool every_unit_has_rows = n_units > 0;
     for (int64_t u = 0; u < n_units; ++u) every_unit_has_rows = every_unit_has_rows && host_unit_rows[u + 1] > host_unit_rows[u];
     out->chunk_rows = (int32_t)chunk;
@@ -1345,7 +1427,7 @@ static int agg_geom_chunks(const char* who, const int64_t* host_unit_rows, int64
     // a unit without rows owns no chunk, so no workgroup would ever combine it: such launches keep the separate
     // combine kernel (which writes the empty unit's outputs)
     out->pad = every_unit_has_rows ? HS_GEOM_FUSABLE : 0;
-    out->n_chunks = n_chunks;
+    out->n_chunks = count_chunks(host_unit_rows, n_units, chunk);
     out->lds_bytes = lds;
     return HS_OK;
 }
@@ -1360,7 +1442,7 @@ extern "C" int hs_agg_partial_chunks(const int64_t* host_unit_rows, int64_t n_un
     for (int64_t u = 0; u < n_units; ++u) {
         host_unit_chunk0[u] = k;
         const int64_t us = host_unit_rows[u], ue = host_unit_rows[u + 1];
-        for (int64_t c0 = us & ~(int64_t)(HS_V - 1); c0 < ue; c0 += geom->chunk_rows) {
+        for (int64_t c0 = unit_anchor(us); c0 < ue; c0 += geom->chunk_rows) {
             if (k >= geom->n_chunks) {
                 hs_set_error("hs_agg_partial_chunks: geometry does not match the unit boundaries");
                 return HS_E_ARG;
@@ -1408,6 +1490,59 @@ extern "C" int64_t hs_agg_debug_scan_stamps(int64_t* host_out, int64_t max_chunk
     return n;
 }
 
+// ---- the scan launch: the kernel compiled for exactly this bytecode, else the interpreter kernel for (hashed, depth) ---
+// A family = a tier's run-time compiled launch + its interpreter instantiations.
+struct MainScan {
+    static constexpr bool big_lds = true;
+    static int jit(const AggMainArgs* A, bool hashed, unsigned grid, unsigned block, size_t lds, hipStream_t s) {
+        return hs_jit_launch_agg_main(A, hashed, grid, block, lds, s);
+    }
+    template <bool HASHED, int D>
+    static constexpr auto kernel() { return &k_agg_main<HASHED, D>; }
+    static unsigned interp_block(int, unsigned block) { return block; }
+};
+struct ScalarScan {  // (no key: never hashed; its LDS block is a few cell rows)
+    static constexpr bool big_lds = false;
+    static int jit(const AggMainArgs* A, bool, unsigned grid, unsigned block, size_t lds, hipStream_t s) {
+        return hs_jit_launch_agg_scalar(A, grid, block, lds, s);
+    }
+    template <bool HASHED, int D>
+    static constexpr auto kernel() { return &k_agg_scalar<D>; }
+    static unsigned interp_block(int, unsigned block) { return block; }
+};
+struct SharedScan {
+    static constexpr bool big_lds = true;
+    static int jit(const AggMainArgs* A, bool hashed, unsigned grid, unsigned block, size_t lds, hipStream_t s) {
+        return hs_jit_launch_agg_shared(A, hashed, grid, block, lds, s);
+    }
+    template <bool HASHED, int D>
+    static constexpr auto kernel() { return &k_agg_shared<HASHED, D>; }
+    static unsigned interp_block(int depth, unsigned) { return (unsigned)hs_shared_interp_wg(depth); }
+};
+
+// Records ev_begin (optional) right before the launch.  needs_jit: the interpreter kernels cannot run this call - without
+// a compiled kernel it is refused with that text and the compiler's log (HS_E_LIMIT); NULL = fall back to them.
+template <class F>
+static int launch_scan(const AggMainArgs& A, bool hashed, int depth, unsigned grid, unsigned block, size_t lds, hipStream_t s,
+                       void* ev_begin, const char* needs_jit = nullptr) {
+    static unsigned long long attrs_set = 0;  // (one per family)
+    if (F::big_lds && hs_first_on_device(attrs_set)) {
+        allow_big_lds(F::template kernel<true, 8>());
+        allow_big_lds(F::template kernel<false, 4>());
+        allow_big_lds(F::template kernel<false, 8>());
+    }
+    if (ev_begin) hs_event_record((hipEvent_t)ev_begin, s);
+    if (F::jit(&A, hashed, grid, block, lds, s) == HS_OK) return HS_OK;
+    if (needs_jit) {
+        hs_set_error("%s: %s", needs_jit, hs_jit_last_log());
+        return HS_E_LIMIT;
+    }
+    const int d = hashed || depth > 4 ? 8 : 4;
+    const auto interp = hashed ? F::template kernel<true, 8>() : d == 4 ? F::template kernel<false, 4>() : F::template kernel<false, 8>();
+    hipLaunchKernelGGL(interp, dim3(grid), dim3(F::interp_block(d, block)), lds, s, A);
+    return HS_OK;
+}
+
 static int agg_partial_impl(void* stream, const hs_col* cols, int32_t n_cols, int32_t key_col, const hs_program* prog,
                             const hs_agg_spec* spec, const hs_chunk* chunks, const int64_t* unit_chunk0,
                             int64_t n_units, const hs_agg_geom* geom, int64_t* out_rep, uint64_t* out_acc,
@@ -1435,29 +1570,17 @@ static int agg_partial_impl(void* stream, const hs_col* cols, int32_t n_cols, in
             }
         }
     }
-    if (prog->n_ins > HS_MAX_INS || prog->n_lit > HS_MAX_LIT) {
-        hs_set_error("hs_agg_partial: program too long");
-        return HS_E_LIMIT;
-    }
-    if (n_units == 0 || geom->n_chunks == 0) return HS_OK;
+    static const ScanTier tier{"hs_agg_partial", true, false, false,
+                               "HS_PAIR columns belong to the run-time compiled shared tier (hs_agg_shared)", nullptr};
     AggMainArgs A;
-    int rc = fill_cols(A.cols, cols, n_cols);
+    int depth = 0;
+    const int rc = scan_check(tier, A.cols, cols, n_cols, key_col, prog, geom->n_chunks, &depth);
     if (rc) return rc;
-    // numeric columns and a preloaded key must sit in the first HS_FUSED_COLS slots
-    for (int i = HS_FUSED_COLS; i < n_cols; ++i) {
-        if (cols[i].kind != HS_STR || i == key_col) {
-            hs_set_error("hs_agg_partial: more than %d numeric column slots", HS_FUSED_COLS);
-            return HS_E_LIMIT;
-        }
+    if (n_units == 0 || geom->n_chunks == 0) return HS_OK;
+    if (geom->wg_threads != 64 && geom->wg_threads != 128 && geom->wg_threads != 256) {
+        hs_set_error("hs_agg_partial: geometry not made by hs_agg_partial_geom");
+        return HS_E_ARG;
     }
-    for (int i = 0; i < n_cols; ++i) {
-        if (cols[i].kind & HS_PAIR) {
-            hs_set_error("hs_agg_partial: HS_PAIR columns belong to the run-time compiled shared tier (hs_agg_shared)");
-            return HS_E_ARG;
-        }
-    }
-    rc = check_narrow_cols("hs_agg_partial", cols, n_cols, key_col, prog);
-    if (rc) return rc;
     A.prog = *prog;
     A.spec = *spec;
     A.key_col = key_col;
@@ -1475,27 +1598,7 @@ static int agg_partial_impl(void* stream, const hs_col* cols, int32_t n_cols, in
     A.replicas = 0;
     A.pad2 = 0;
     const bool hashed = !hs_col_packs(cols[key_col]);
-    const int depth = program_depth(prog);
-    if (depth > HS_MAX_STACK) {
-        hs_set_error("hs_agg_partial: expression stack depth %d > %d", depth, HS_MAX_STACK);
-        return HS_E_LIMIT;
-    }
     hipStream_t s = (hipStream_t)stream;
-    if (geom->wg_threads != 64 && geom->wg_threads != 128 && geom->wg_threads != 256) {
-        hs_set_error("hs_agg_partial: geometry not made by hs_agg_partial_geom");
-        return HS_E_ARG;
-    }
-    dim3 grid((unsigned)geom->n_chunks), block((unsigned)geom->wg_threads);
-    static unsigned long long attrs_set = 0;
-    if (hs_first_on_device(attrs_set)) {
-        allow_big_lds(k_agg_main<true, 8>);
-        allow_big_lds(k_agg_main<false, 4>);
-        allow_big_lds(k_agg_main<false, 8>);
-    }
-    if (geom->n_chunks > 0x7fffffffll) {
-        hs_set_error("hs_agg_partial: too many chunks");
-        return HS_E_LIMIT;
-    }
     // ---- the unit combine: arguments first, then decide whether it rides in the scan kernel's epilogue ----
     AggUnitArgs U;
     U.key = cols[key_col];
@@ -1553,17 +1656,7 @@ static int agg_partial_impl(void* stream, const hs_col* cols, int32_t n_cols, in
             fused = true;
         }
     }
-    if (ev_begin) hs_event_record((hipEvent_t)ev_begin, s);
-    const int jit_rc = hs_jit_launch_agg_main(&A, hashed, grid.x, block.x, geom->lds_bytes, s);
-    if (jit_rc == HS_OK) {
-        // launched the program compiled for exactly this bytecode
-    } else if (hashed) {
-        hipLaunchKernelGGL((k_agg_main<true, 8>), grid, block, geom->lds_bytes, s, A);
-    } else if (depth <= 4) {
-        hipLaunchKernelGGL((k_agg_main<false, 4>), grid, block, geom->lds_bytes, s, A);
-    } else {
-        hipLaunchKernelGGL((k_agg_main<false, 8>), grid, block, geom->lds_bytes, s, A);
-    }
+    (void)launch_scan<MainScan>(A, hashed, depth, (unsigned)geom->n_chunks, (unsigned)geom->wg_threads, geom->lds_bytes, s, ev_begin);
     if (ev_end) hs_event_record((hipEvent_t)ev_end, s);
     if (!fused) {
         static unsigned long long unit_attr = 0;
@@ -1600,7 +1693,6 @@ extern "C" int hs_agg_partial_slab(void* stream, const hs_col* cols, int32_t n_c
 }
 
 // ---- aggregates without GROUP BY (kernel: hs_agg_kernel.h, keyless tier) ------------------------------------------
-int hs_jit_launch_agg_scalar(const AggMainArgs* args, unsigned grid, unsigned block, size_t lds_bytes, hipStream_t stream);
 static constexpr int HS_SCALAR_WG = 256;
 // workspace: one cell row [n_acc + 1] per chunk, then one arrival counter per unit
 static size_t hs_agg_scalar_cells_bytes(int64_t n_chunks, int32_t n_acc) {
@@ -1630,10 +1722,13 @@ extern "C" int hs_agg_scalar(void* stream, const hs_col* cols, int32_t n_cols, c
         hs_set_error("hs_agg_scalar: null or out-of-range argument");
         return HS_E_ARG;
     }
-    if (prog->n_ins > HS_MAX_INS || prog->n_lit > HS_MAX_LIT) {
-        hs_set_error("hs_agg_scalar: program too long");
-        return HS_E_LIMIT;
-    }
+    static const ScanTier tier{"hs_agg_scalar", true, true, false, "HS_PAIR / HS_JOIN8 columns belong to the shared tier",
+                               "HS_PAIR / HS_JOIN8 columns belong to the shared tier"};
+    AggMainArgs A;
+    memset(&A, 0, sizeof(A));
+    int depth = 0;
+    const int rc = scan_check(tier, A.cols, cols, n_cols, -1, prog, geom->n_chunks, &depth);
+    if (rc) return rc;
     if (geom->wg_threads != HS_SCALAR_WG || geom->group_cap != 1 || geom->chunk_rows < HS_V ||
         geom->lds_bytes != (size_t)(HS_SCALAR_WG / HS_WAVE) * (size_t)(spec->n_acc + 1) * 8) {
         hs_set_error("hs_agg_scalar: geometry not made by hs_agg_scalar_geom for these aggregates");
@@ -1670,31 +1765,6 @@ extern "C" int hs_agg_scalar(void* stream, const hs_col* cols, int32_t n_cols, c
         }
     }
     if (n_units == 0 || geom->n_chunks == 0) return HS_OK;
-    if (geom->n_chunks > 0x7fffffffll) {
-        hs_set_error("hs_agg_scalar: too many chunks");
-        return HS_E_LIMIT;
-    }
-    AggMainArgs A;
-    memset(&A, 0, sizeof(A));
-    int rc = fill_cols(A.cols, cols, n_cols);
-    if (rc) return rc;
-    for (int i = 0; i < n_cols; ++i) {
-        if (i >= HS_FUSED_COLS && cols[i].kind != HS_STR) {
-            hs_set_error("hs_agg_scalar: more than %d numeric column slots", HS_FUSED_COLS);
-            return HS_E_LIMIT;
-        }
-        if ((cols[i].kind & HS_PAIR) || cols[i].kind == HS_JOIN8_CODE || cols[i].kind == HS_JOIN8_UNIT) {
-            hs_set_error("hs_agg_scalar: HS_PAIR / HS_JOIN8 columns belong to the shared tier");
-            return HS_E_ARG;
-        }
-    }
-    rc = check_narrow_cols("hs_agg_scalar", cols, n_cols, -1, prog);
-    if (rc) return rc;
-    const int depth = program_depth(prog);
-    if (depth > HS_MAX_STACK) {
-        hs_set_error("hs_agg_scalar: expression stack depth %d > %d", depth, HS_MAX_STACK);
-        return HS_E_LIMIT;
-    }
     A.prog = *prog;
     A.spec = *spec;
     A.key_col = -1;
@@ -1715,15 +1785,7 @@ extern "C" int hs_agg_scalar(void* stream, const hs_col* cols, int32_t n_cols, c
     A.unit_col = -1;
     A.stamps = hs_scan_stamps_for(geom->n_chunks);
     A.scalar_rows = out_rows;
-    dim3 grid((unsigned)geom->n_chunks), block((unsigned)geom->wg_threads);
-    if (ev_begin) hs_event_record((hipEvent_t)ev_begin, s);
-    if (hs_jit_launch_agg_scalar(&A, grid.x, block.x, geom->lds_bytes, s) == HS_OK) {
-        // launched the program compiled for exactly this bytecode
-    } else if (depth <= 4) {
-        hipLaunchKernelGGL((k_agg_scalar<4>), grid, block, geom->lds_bytes, s, A);
-    } else {
-        hipLaunchKernelGGL((k_agg_scalar<8>), grid, block, geom->lds_bytes, s, A);
-    }
+    (void)launch_scan<ScalarScan>(A, false, depth, (unsigned)geom->n_chunks, (unsigned)geom->wg_threads, geom->lds_bytes, s, ev_begin);
     if (ev_end) hs_event_record((hipEvent_t)ev_end, s);
     if (hipGetLastError() != hipSuccess) {
         hs_set_error("hs_agg_scalar: kernel launch failed");
@@ -2011,12 +2073,7 @@ extern "C" int hs_host_device_pointer(void* host_ptr, void** device_ptr) {
 }
 
 // ---- shared-dictionary tier: geometry and launch ------------------------------------------------------------------
-int hs_jit_launch_agg_shared(const AggMainArgs* args, bool hashed, unsigned grid, unsigned block, size_t lds_bytes,
-                             hipStream_t stream);
-
 static constexpr int HS_SHARED_WG = 1024;
-extern "C" int hs_jit_get_enabled(void);
-extern "C" const char* hs_jit_last_log(void);
 
 extern "C" int hs_agg_shared_geom(const int64_t* host_unit_rows, int64_t n_units, int32_t n_acc, int32_t group_cap,
                                   hs_agg_geom* out) {
@@ -2042,32 +2099,20 @@ extern "C" int hs_agg_shared_geom(const int64_t* host_unit_rows, int64_t n_units
         return HS_E_LIMIT;
     }
     group_cap = slots;
-    int64_t total = 0;
-    for (int64_t u = 0; u < n_units; ++u) {
-        const int64_t r = host_unit_rows[u + 1] - host_unit_rows[u];
-        if (r < 0) {
-            hs_set_error("hs_agg_shared_geom: unit_rows not ascending at %lld", (long long)u);
-            return HS_E_ARG;
-        }
-        total += r;
-    }
+    const int64_t total = unit_rows_total("hs_agg_shared_geom", host_unit_rows, n_units);
+    if (total < 0) return HS_E_ARG;
     // Two rounds of workgroups even out the tail - but never one workgroup more than the rounds hold: the chunks
     // are equally long, so 515 of them on 256 CUs (one resident workgroup each) take three rounds, not two
     // (measured: 1.13 ms instead of 0.76).  Chunks do not span units, hence the re-count per candidate length.
     const int64_t step = (int64_t)HS_SHARED_WG * HS_V;
     const int64_t resident = lds * 2 + 2048 <= 160 * 1024 ? 2 : 1;  // 1024-lane workgroups: at most two per CU
-    const int64_t target = 256 * resident * 2;
+    const int64_t target = (int64_t)n_cus() * resident * 2;
     int64_t chunk = ((total + target - 1) / target + step - 1) / step * step;
     if (chunk < 16 * step) chunk = 16 * step;
     if (chunk > 0x40000000) chunk = 0x40000000 / step * step;
     int64_t n_chunks = 0;
     for (int attempt = 0; attempt < 64; ++attempt) {
-        n_chunks = 0;
-        for (int64_t u = 0; u < n_units; ++u) {
-            const int64_t anchor = host_unit_rows[u] & ~(int64_t)(HS_V - 1);
-            const int64_t span = host_unit_rows[u + 1] - anchor;
-            n_chunks += span > 0 ? (span + chunk - 1) / chunk : 0;
-        }
+        n_chunks = count_chunks(host_unit_rows, n_units, chunk);
         if (n_chunks <= target || n_units >= target || chunk >= 0x40000000 / step * step) break;
         chunk += step * (1 + chunk / step / 32);
     }
@@ -2079,6 +2124,35 @@ extern "C" int hs_agg_shared_geom(const int64_t* host_unit_rows, int64_t n_units
     out->n_chunks = n_chunks;
     out->lds_bytes = lds;
     out->ws_bytes = (size_t)n_units * (size_t)unit_cap * 8 + 256;  // the unit tables' key words
+    return HS_OK;
+}
+
+// Computed units (include/hipspark.h, hs_agg_shared_units_geom): where the per-chunk cells begin in `ws` behind the unit
+// tables' key words, and how many bytes they take.  The geometry entry sizes with these, agg_shared_impl indexes with them.
+static size_t shared_units_cells_offset(int64_t n_unit_tables, int32_t unit_cap) {
+    return ((size_t)n_unit_tables * (size_t)unit_cap * 8 + 256 + 15) & ~(size_t)15;
+}
+static size_t shared_units_cells_bytes(int64_t n_chunks, int64_t n_unit_tables, int32_t unit_cap, int32_t n_acc) {
+    return (size_t)(n_chunks > 0 ? n_chunks : 1) * (size_t)n_unit_tables * (size_t)unit_cap * (size_t)(n_acc > 0 ? n_acc : 1) * 8;
+}
+
+extern "C" int hs_agg_shared_units_geom(int64_t nrows, int32_t n_unit_tables, int32_t n_acc, int32_t group_cap,
+                                        int32_t caller_keys, hs_agg_geom* out) {
+    if (nrows < 0 || n_unit_tables < 1 || n_unit_tables > 127 || !out) {
+        hs_set_error("hs_agg_shared_units_geom: bad arguments");
+        return HS_E_ARG;
+    }
+    const int64_t unit_rows[2] = {0, nrows};
+    const int rc = hs_agg_shared_geom(unit_rows, 1, n_acc, group_cap, out);
+    if (rc) return rc;
+    // a unit's table holds the groups of ONE unit: sized from the per-unit share of the capacity (x4: open addressing),
+    // not from the LDS table that holds every (unit, key) pair
+    int per_unit = group_cap / n_unit_tables, small = 16;
+    if (per_unit < 4) per_unit = 4;
+    while (small < 4 * per_unit) small *= 2;
+    if (out->pad > small) out->pad = small;
+    out->ws_bytes = (caller_keys ? 0 : shared_units_cells_offset(n_unit_tables, out->pad)) +
+                    shared_units_cells_bytes(out->n_chunks, n_unit_tables, out->pad, n_acc);
     return HS_OK;
 }
 
@@ -2125,11 +2199,14 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
         hs_set_error("hs_agg_shared: null or out-of-range argument");
         return HS_E_ARG;
     }
-    if (hs_refuse_narrow("hs_agg_shared", cols, n_cols)) return HS_E_ARG;
-    if (prog->n_ins > HS_MAX_INS || prog->n_lit > HS_MAX_LIT) {
-        hs_set_error("hs_agg_shared: program too long");
-        return HS_E_LIMIT;
-    }
+    static const ScanTier tiers[2] = {
+        {"hs_agg_shared", false, false, false, nullptr, "HS_JOIN8_* columns belong to hs_agg_shared_join8"},
+        {"hs_agg_shared", false, false, true, nullptr, nullptr}};  // the fused probe
+    AggMainArgs A;
+    int depth = 0;
+    bool pairs = false;
+    const int rc = scan_check(tiers[join ? 1 : 0], A.cols, cols, n_cols, key_col, prog, geom->n_chunks, &depth, &pairs);
+    if (rc) return rc;
     // slots of a unit's table: with row-range units at least the LDS table's (a unit sees every group of its chunks);
     // with computed units the caller sizes it for the groups ONE unit holds (an overflow raises HS_FLAG_DICT_FULL)
     if (geom->wg_threads != HS_SHARED_WG || (geom->pad & (geom->pad - 1)) ||
@@ -2138,41 +2215,8 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
         return HS_E_ARG;
     }
     if (n_units == 0 || (geom->n_chunks == 0 && !join)) return HS_OK;  // (a rank without probe rows still clears its tables)
-    AggMainArgs A;
-    int rc = fill_cols(A.cols, cols, n_cols);
-    if (rc) return rc;
-    for (int i = HS_FUSED_COLS; i < n_cols; ++i) {
-        if (cols[i].kind != HS_STR || i == key_col) {
-            hs_set_error("hs_agg_shared: more than %d numeric column slots", HS_FUSED_COLS);
-            return HS_E_LIMIT;
-        }
-    }
-    bool pairs = false;  // pair-indexed columns: only the run-time compiled scan reads them
-    for (int i = 0; i < n_cols; ++i) {
-        if ((cols[i].kind == HS_JOIN8_CODE || cols[i].kind == HS_JOIN8_UNIT) && !join) {
-            hs_set_error("hs_agg_shared: HS_JOIN8_* columns belong to hs_agg_shared_join8");
-            return HS_E_ARG;
-        }
-        if (cols[i].kind & HS_PAIR) {
-            const int base = cols[i].kind & ~HS_PAIR;
-            if (join || i == key_col || (base != HS_I32 && base != HS_F32 && base != HS_I64) || !cols[i].offs) {
-                hs_set_error("hs_agg_shared: an HS_PAIR column is an INTEGER / FLOAT / TIMESTAMP argument slot with its pair rows");
-                return HS_E_ARG;
-            }
-            pairs = true;
-        }
-    }
     if (pairs && !hs_jit_get_enabled()) {
         hs_set_error("hs_agg_shared: HS_PAIR columns need the run-time compiler (HIPSPARK_JIT=0 here)");
-        return HS_E_LIMIT;
-    }
-    const int depth = program_depth(prog);
-    if (depth > HS_MAX_STACK) {
-        hs_set_error("hs_agg_shared: expression stack depth %d > %d", depth, HS_MAX_STACK);
-        return HS_E_LIMIT;
-    }
-    if (geom->n_chunks > 0x7fffffffll) {
-        hs_set_error("hs_agg_shared: too many chunks");
         return HS_E_LIMIT;
     }
     A.prog = *prog;
@@ -2192,10 +2236,10 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
     memset(&A.unit, 0, sizeof(A.unit));
     A.unit_col = unit_col;  // -1: units are the chunks' row ranges; else n_units = number of unit tables
     A.pad3 = 0;
-    // computed units: per-chunk cells behind the unit tables' key words in `ws` (hs_agg_shared_units documents the size);
+    // computed units: per-chunk cells behind the unit tables' key words in `ws` (sized by hs_agg_shared_units_geom);
     // with caller-owned key words (hs_agg_shared_join8) `ws` holds the per-chunk cells only
-    A.chunk_acc = unit_col < 0 ? nullptr : unit_keys ? (uint64_t*)ws
-                : (uint64_t*)((char*)ws + (((size_t)n_units * (size_t)geom->pad * 8 + 256 + 15) & ~(size_t)15));
+    A.chunk_acc = unit_col < 0 ? nullptr
+                               : (uint64_t*)((char*)ws + (unit_keys ? 0 : shared_units_cells_offset(n_units, geom->pad)));
     if (join) A.join = *join;
     else memset(&A.join, 0, sizeof(A.join));
     A.stamps = nullptr;
@@ -2230,31 +2274,13 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
         return hipGetLastError() == hipSuccess ? HS_OK : HS_E_LAUNCH;
     }
     const bool hashed = !hs_col_packs(cols[key_col]);
-    static unsigned long long attrs_set = 0;
-    if (hs_first_on_device(attrs_set)) {
-        allow_big_lds(k_agg_shared<true, 8>);
-        allow_big_lds(k_agg_shared<false, 4>);
-        allow_big_lds(k_agg_shared<false, 8>);
-    }
-    dim3 grid((unsigned)geom->n_chunks), block((unsigned)HS_SHARED_WG);
-    if (ev_begin) hs_event_record((hipEvent_t)ev_begin, s);
-    const int jit_rc = hs_jit_launch_agg_shared(&A, hashed, grid.x, block.x, geom->lds_bytes, s);
-    if (jit_rc == HS_OK) {
-        // launched the program compiled for exactly this bytecode
-    } else if (join) {
-        // the interpreter kernels do not know the virtual columns; the init launch above is harmless
-        hs_set_error("hs_agg_shared_join8: needs the run-time compiler (hiprtc): %s", hs_jit_last_log());
-        return HS_E_LIMIT;
-    } else if (pairs) {
-        hs_set_error("hs_agg_shared: HS_PAIR columns need the run-time compiler (hiprtc): %s", hs_jit_last_log());
-        return HS_E_LIMIT;
-    } else if (hashed) {
-        hipLaunchKernelGGL((k_agg_shared<true, 8>), grid, dim3(hs_shared_interp_wg(8)), geom->lds_bytes, s, A);
-    } else if (depth <= 4) {
-        hipLaunchKernelGGL((k_agg_shared<false, 4>), grid, dim3(hs_shared_interp_wg(4)), geom->lds_bytes, s, A);
-    } else {
-        hipLaunchKernelGGL((k_agg_shared<false, 8>), grid, dim3(hs_shared_interp_wg(8)), geom->lds_bytes, s, A);
-    }
+    // the interpreter kernels know neither the virtual columns nor pair rows; the init launch above is harmless
+    const char* needs_jit = join    ? "hs_agg_shared_join8: needs the run-time compiler (hiprtc)"
+                            : pairs ? "hs_agg_shared: HS_PAIR columns need the run-time compiler (hiprtc)"
+                                    : nullptr;
+    const int scan_rc = launch_scan<SharedScan>(A, hashed, depth, (unsigned)geom->n_chunks, (unsigned)HS_SHARED_WG,
+                                                geom->lds_bytes, s, ev_begin, needs_jit);
+    if (scan_rc) return scan_rc;
     if (A.chunk_acc && spec->n_acc > 0) {
         SharedFoldArgs G;
         G.chunk_acc = A.chunk_acc;
@@ -2292,8 +2318,6 @@ static int agg_shared_impl(void* stream, const hs_col* cols, int32_t n_cols, int
 }
 
 // ---- round 3: the join's probe inside the scan; raw unit tables -> [merge over ranks] -> exchange slab ----------------
-extern "C" const char* hs_jit_last_log(void);
-
 extern "C" int hs_agg_shared_join8(void* stream, const hs_col* cols, int32_t n_cols, int32_t key_col, int32_t unit_col,
                                    const hs_join8* join, int32_t n_unit_tables, const hs_program* prog, const hs_agg_spec* spec,
                                    const hs_chunk* chunks, const hs_agg_geom* geom, int64_t* out_rep, uint64_t* unit_keys,

@@ -1918,19 +1918,15 @@ int join_prepare_aggregate(hs_join_stage* s) {
     while (cap < (s->group_cap > 4 ? s->group_cap : 4) * s->n_units) cap *= 2;
     if (cap > 4096) cap = 4096;
     const int64_t unit_rows[2] = {0, s->probe->nrows};
-    int rc = hs_agg_shared_geom(unit_rows, 1, P.spec.n_acc, cap, &s->geom);
+    int rc = hs_agg_shared_units_geom(s->probe->nrows, s->n_units, P.spec.n_acc, cap, 1, &s->geom);
     if (rc) return rc;
     rc = chunks_upload("hs_join_stage", unit_rows, 1, s->geom, s->chunks);
     if (rc) return rc;
-    int per_unit = cap / s->n_units, small = 16;
-    if (per_unit < 4) per_unit = 4;
-    while (small < 4 * per_unit) small *= 2;
-    if (s->geom.pad > small) s->geom.pad = small;  // slots of ONE unit's table
-    s->unit_cap = s->geom.pad;
+    s->unit_cap = s->geom.pad;  // slots of ONE unit's table
     const int64_t slots = (int64_t)s->n_units * s->unit_cap;
     const int n_acc = P.spec.n_acc;
     bool ok = s->out_rep.alloc((size_t)slots * 8) && s->xbuf.alloc((size_t)(16 + slots * 8 * (1 + n_acc)), true) &&
-              s->ws.alloc((size_t)(s->geom.n_chunks > 0 ? s->geom.n_chunks : 1) * (size_t)slots * (size_t)(n_acc > 0 ? n_acc : 1) * 8, true);
+              s->ws.alloc(s->geom.ws_bytes, true);
     // slab: unit u owns rows [u * cap, (u + 1) * cap); zero-filled
     const int64_t slab_bytes = slab_layout(s->desc, slots, s->key_kind, s->key_bytes, P.spec);
     ok = ok && s->slab.alloc((size_t)slab_bytes, true);

@@ -224,6 +224,36 @@ def _call_void(fn: Any, *args: Any) -> None:
     fn(*args)  # tensor ops return the tensor; a replayed call must report "no error"
 
 
+def _bounded_put(cache: dict, key: Any, value: Any, limit: int) -> Any:
+    """cache[key] = value in a cache of at most `limit` entries: the oldest one makes room."""
+    if len(cache) >= limit:
+        cache.pop(next(iter(cache)))
+    cache[key] = value
+    return value
+
+
+def _scan_info(rows: int, geom: Any, cap: int, tier: str, **more: Any) -> dict:
+    """What a prepared scan reports as Device.last_scan."""
+    return {"rows": rows, "chunks": int(geom.n_chunks), "chunk_rows": int(geom.chunk_rows),
+            "wg_threads": int(geom.wg_threads), "group_cap": cap, "lds_bytes": int(geom.lds_bytes), "tier": tier, **more}
+
+
+def _tail_info(desc: Any, layout: Any, slab: Any, low: Any, acc_kinds: Sequence[int], key_col: "DCol", n_units: int,
+               **more: Any) -> dict:
+    """What the short tail's finish launch needs to know about the exchange slab a partial aggregate left."""
+    return {"desc": desc, "layout": layout, "slab": slab, "agg_to_acc": list(low.agg_to_acc), "acc_kinds": acc_kinds,
+            "key_kind": key_col.kind, "key_len": key_col.fixed_len, "n_units": n_units, "key_dict": key_col.dict, **more}
+
+
+def _slab_key_spec(key_col: "DCol", widths: Sequence[int], refusal: str) -> tuple:
+    """(bytes, dtype) of the key column of an exchange slab; string keys only in the fixed lengths `widths`."""
+    if key_col.kind != hs.STR:
+        return hs.KIND_BYTES[key_col.kind], _TORCH_DTYPE[key_col.kind]
+    if key_col.fixed_len not in widths:
+        raise SlabUnsupported(refusal)
+    return key_col.fixed_len, torch.uint8
+
+
 class _RecordingLib:
     """Stands in for the ctypes library while a run is being recorded: the calls go through unchanged (the library
     itself captures their launches), their argument objects are kept alive with the recording."""
@@ -260,6 +290,7 @@ class Device:
         self.last_global_tier = ""  # "radix" / "hash": what the last HBM-tier partial aggregate ran on
         self._partial_prepared: dict[Any, dict] = {}
         self._finish_prepared: dict[Any, dict] = {}
+        self._join8_prepared: dict[Any, dict] = {}
         self.zero_copy_results = os.environ.get("HIPSPARK_ZERO_COPY", "1") != "0"
         # the private-table / keyless fused scan reads DCol.narrow where a column has one (set by the engine from
         # HIPSPARK_NARROW; part of the prepared-launch key)
@@ -413,6 +444,7 @@ class Device:
         for prep in self._partial_prepared.values():  # slab headers of a run that did not reach its finish launch
             if prep.get("tail") is not None:
                 prep["slab"][:4].zero_()
+        # (_join8_prepared's slabs need none of this: hs_agg_units_to_slab writes rows only, their header stays zero)
         for prep in self._finish_prepared.values():  # ... and "done" words nobody read
             if prep["host_image"] is not None:
                 prep["host_image"][4:8] = 0
@@ -819,9 +851,7 @@ class Device:
                 hit = self.string_col(self.to_device(lens, torch.uint8), self.to_device(data, torch.uint8), len(entries))
             finally:
                 self.rec = recording
-            if len(cache) >= 64:
-                cache.pop(next(iter(cache)))
-            cache[entries] = hit
+            _bounded_put(cache, entries, hit, 64)
         return hit
 
     def decoded(self, col: DCol) -> DCol:
@@ -1036,9 +1066,7 @@ class Device:
             except NeedsDecoded as e:
                 batch = self.decoded_batch(batch, [e.column])
                 if cache_key is not None:
-                    if len(hints) >= 64:
-                        hints.pop(next(iter(hints)))
-                    hints.setdefault(cache_key, set()).add(e.column)
+                    _bounded_put(hints, cache_key, hints.get(cache_key, set()) | {e.column}, 64)
 
     def _aggregate_partial(self, batch: DBatch, filters: Sequence[Any], group_by: Any, agg_columns: Sequence[Any],
                            out_schema: Schema, group_cap_hint: int = 4, cache_key: Any = None,
@@ -1072,9 +1100,7 @@ class Device:
         if prep is None:
             prep = self._prepare_partial(batch, filters, group_by, agg_columns, cap, slab_rows, tail, out_schema, shared)
             if key is not None:
-                if len(self._partial_prepared) >= 8:
-                    self._partial_prepared.pop(next(iter(self._partial_prepared)))
-                self._partial_prepared[key] = prep
+                _bounded_put(self._partial_prepared, key, prep, 8)
         p = prep
         if self.rec is not None:
             # a recording replays raw pointers into this entry's buffers: it must outlive the cache's eviction
@@ -1158,21 +1184,16 @@ class Device:
             if slab_rows is None:
                 raise SlabUnsupported("an empty single-GPU input takes the general path")
             layout, slab, desc = self._tail_slab(key_src, out_schema, acc_kinds, slab_rows)
-            info = {"desc": desc, "layout": layout, "slab": slab, "agg_to_acc": list(low.agg_to_acc),
-                    "acc_kinds": acc_kinds, "key_kind": key_src.kind, "key_len": key_src.fixed_len, "n_units": 0,
-                    "key_dict": key_src.dict}
             return DBatch(list(out_schema), [], 0, [0, 0], None, total_units=batch.total_units, slab=slab,
-                          slab_layout=layout, tail=info)
-        if slab_rows is not None and key_src.kind == hs.STR and key_src.fixed_len not in (1, 2, 4, 8):
-            raise SlabUnsupported("variable-length string GROUP BY key")
+                          slab_layout=layout, tail=_tail_info(desc, layout, slab, low, acc_kinds, key_src, 0))
+        if slab_rows is not None:
+            key_spec = _slab_key_spec(key_src, (1, 2, 4, 8), "variable-length string GROUP BY key")
         cols = [self.gather_col(key_src, self.empty(0, torch.int64), 0)]
         cols += [DCol(acc_kinds[acc], self.empty(0, _TORCH_DTYPE[acc_kinds[acc]]), 0) for acc in low.agg_to_acc]
         out = DBatch(list(out_schema), cols, 0, [0, 0], order=self.empty(0, torch.int64), total_units=batch.total_units)
         if slab_rows is not None:
             from .distributed import SlabLayout  # noqa: PLC0415
 
-            key_spec = ((key_src.fixed_len, torch.uint8) if key_src.kind == hs.STR
-                        else (hs.KIND_BYTES[key_src.kind], _TORCH_DTYPE[key_src.kind]))
             out.slab_layout = SlabLayout.build(slab_rows, [key_spec] + [(4, _TORCH_DTYPE[k]) for k in acc_kinds])
             out.slab = torch.zeros(out.slab_layout.nbytes, dtype=torch.uint8, device=self.device)  # count = 0
             out.slab_cols = [0] + [1 + acc for acc in low.agg_to_acc]
@@ -1183,14 +1204,9 @@ class Device:
         kinds that pack into the 64-bit key word."""
         from .distributed import SlabLayout  # noqa: PLC0415
 
-        if key_col.kind == hs.STR:
-            if key_col.fixed_len not in (1, 2, 4):
-                raise SlabUnsupported("string GROUP BY key without a short fixed length")
-            key_spec = (key_col.fixed_len, torch.uint8)
-        else:
-            if key_col.kind not in (hs.I32, hs.F32, hs.I64) or key_col.kind != FILE_KIND[out_schema[0][1]]:
-                raise SlabUnsupported("GROUP BY key is not in its stored kind")
-            key_spec = (hs.KIND_BYTES[key_col.kind], _TORCH_DTYPE[key_col.kind])
+        if key_col.kind != hs.STR and (key_col.kind not in (hs.I32, hs.F32, hs.I64) or key_col.kind != FILE_KIND[out_schema[0][1]]):
+            raise SlabUnsupported("GROUP BY key is not in its stored kind")
+        key_spec = _slab_key_spec(key_col, (1, 2, 4), "string GROUP BY key without a short fixed length")
         layout = SlabLayout.build(rows, [key_spec] + [(4, _TORCH_DTYPE[k]) for k in acc_kinds])
         slab = torch.zeros(layout.nbytes, dtype=torch.uint8, device=self.device)
         layout.order_view(slab).fill_(-1)
@@ -1203,6 +1219,26 @@ class Device:
             desc.acc_off[a] = layout.columns[1 + a].offset
             desc.acc_kind[a] = k
         return layout, slab, desc
+
+    def _scan_geometry(self, entry: str, bounds: Sequence[int], args: tuple, limit: str, upload: Any) -> tuple:
+        """Geometry -> chunk table -> its device copies, for units with the row boundaries ``bounds``: per-workgroup row
+        ranges + first chunk of every unit, computed by the library, uploaded once.  ``entry(bounds, n_units, *args)``
+        makes the geometry (the computed-units entry takes the row count of its one range instead of the boundaries);
+        HS_E_LIMIT raises TierExceeded(``limit`` + the library's reason).  -> (geom, d_chunks, d_unit_chunk0)."""
+        n_units = len(bounds) - 1
+        host_units = (C.c_int64 * (n_units + 1))(*bounds)
+        where = (bounds[1],) if entry == "hs_agg_shared_units_geom" else (host_units, n_units)
+        geom = hs.hs_agg_geom()
+        rc = getattr(self.lib, entry)(*where, *args, C.byref(geom))
+        if rc == 2:
+            raise TierExceeded(limit + self.lib.hs_last_error().decode())
+        hs.check(rc, entry)
+        chunks = np.zeros((max(int(geom.n_chunks), 1), 4), dtype=np.int64)
+        chunk0 = np.zeros(n_units + 1, dtype=np.int64)
+        hs.check(self.lib.hs_agg_partial_chunks(host_units, n_units, C.byref(geom),
+                                                chunks.ctypes.data_as(C.POINTER(hs.hs_chunk)),
+                                                chunk0.ctypes.data_as(C.POINTER(C.c_int64))), "hs_agg_partial_chunks")
+        return geom, upload(chunks.reshape(-1)), upload(chunk0)
 
     def _prepare_partial(self, batch: DBatch, filters: Sequence[Any], group_by: Any, agg_columns: Sequence[Any],
                          cap: int, slab_rows: int | None = None, tail: bool = False,
@@ -1227,38 +1263,15 @@ class Device:
             kc = batch.cols[low.program.columns[low.key_slot]]
             if not (kc.kind in (hs.I32, hs.U8) or (kc.kind == hs.STR and 1 <= kc.fixed_len <= 6)):
                 raise TierExceeded("computed units need a GROUP BY key of at most 56 bits")
-            host_units = (C.c_int64 * 2)(0, batch.nrows)
-            n_units = 1
+            # (the library sizes a unit's table - geom.pad - and the workspace for batch.n_unit_ids tables)
+            bounds, entry, args = [0, batch.nrows], "hs_agg_shared_units_geom", (batch.n_unit_ids, n_acc, cap, 0)
+        elif keyless:
+            bounds, entry, args = batch.unit_rows, "hs_agg_scalar_geom", (n_acc,)
         else:
-            host_units = (C.c_int64 * (n_units + 1))(*batch.unit_rows)
-        geom = hs.hs_agg_geom()
-        if keyless:
-            rc = self.lib.hs_agg_scalar_geom(host_units, n_units, n_acc, C.byref(geom))
-        elif shared:
-            rc = self.lib.hs_agg_shared_geom(host_units, n_units, n_acc, cap, C.byref(geom))
-        else:
-            rc = self.lib.hs_agg_partial_geom(host_units, n_units, n_acc, cap, C.byref(geom))
-        if rc == 2:
-            raise TierExceeded(
-                f"GROUP BY with more than {cap // 2} groups per workgroup x {n_acc} aggregates exceeds the LDS tier: "
-                + self.lib.hs_last_error().decode()
-            )
-        hs.check(rc, "hs_agg_partial_geom")
-        # per-workgroup row ranges + first chunk of every unit, computed by the library, uploaded once
-        chunks = np.zeros((max(int(geom.n_chunks), 1), 4), dtype=np.int64)
-        chunk0 = np.zeros(n_units + 1, dtype=np.int64)
-        hs.check(self.lib.hs_agg_partial_chunks(host_units, n_units, C.byref(geom),
-                                                chunks.ctypes.data_as(C.POINTER(hs.hs_chunk)),
-                                                chunk0.ctypes.data_as(C.POINTER(C.c_int64))), "hs_agg_partial_chunks")
-        if computed:
-            # a unit's table holds the groups of ONE unit: sized from the per-unit share of the capacity (x4: open
-            # addressing), not from the LDS table that holds every (unit, key) pair - the partial rows' upper bound
-            # n_units x unit_cap then stays small enough for the on-chip final merge
-            per_unit = max(4, cap // max(batch.n_unit_ids, 1))
-            small = 16
-            while small < 4 * per_unit:
-                small *= 2
-            geom.pad = min(int(geom.pad), small)
+            bounds, entry, args = batch.unit_rows, "hs_agg_shared_geom" if shared else "hs_agg_partial_geom", (n_acc, cap)
+        geom, d_units, d_chunk0 = self._scan_geometry(
+            entry, bounds, args, f"GROUP BY with more than {cap // 2} groups per workgroup x {n_acc} aggregates exceeds "
+            "the LDS tier: ", self.to_device)
         unit_cap = int(geom.pad) if shared else cap  # slots per unit of the kernels' output arrays
         if computed:
             n_units = batch.n_unit_ids  # from here on: the unit tables
@@ -1268,86 +1281,64 @@ class Device:
         # keyless: the partial rows are merged under ONE constant INTEGER key, a column of n_units zeros (never per-row
         # traffic); the unit rows name their own entry of it
         key_src = DCol(hs.I32, torch.zeros(max(n_units, 1), dtype=torch.int32, device=self.device), n_units) if keyless else None
-        slab = layout = key_out = out_unit = None
+        key_col = key_src if keyless else batch.cols[key_idx]
+        d_unit_ids = self.to_device(np.asarray(batch.unit_ids, dtype=np.int64)) if batch.unit_ids is not None else None
+        cols_arr, n_cols = self._cols_array(batch, low.program.columns, low.program.code_columns, narrow_slots), len(low.program.columns)
+        unit_slot = None
+        if computed:  # the unit id column rides along as one more preloaded slot
+            base_arr, cols_arr = cols_arr, (hs.hs_col * (n_cols + 1))()
+            for slot in range(n_cols):
+                cols_arr[slot] = base_arr[slot]
+            cols_arr[n_cols] = DCol(hs.U8, batch.unit_col, batch.nrows).as_hs()
+            unit_slot, n_cols = n_cols, n_cols + 1
+        p = {
+            "slab": None, "layout": None, "d_unit_ids": d_unit_ids, "cols": cols_arr, "n_cols": n_cols,
+            "key_slot": low.key_slot, "prog": low.program.to_struct(), "spec": low.spec(), "geom": geom,
+            "n_units": n_units, "slots": slots, "d_units": d_units, "d_chunk0": d_chunk0,
+            "ws": self.workspace(geom.ws_bytes).zero_(),
+            "info": _scan_info(batch.nrows, geom, cap, "scalar" if keyless else "shared" if shared and not tail else "private",
+                               moved_bytes_per_row=moved, narrow_slots=list(narrow_slots)),
+        }
         if tail:
             if keyless:  # (hs_agg_scalar has no slab form of the unit row: _aggregate_partial refuses before it gets here)
                 raise SlabUnsupported("an aggregate without GROUP BY takes the general tail")
             rows = slab_rows if slab_rows is not None else slots
             if slots > rows:
                 raise DeviceError(f"exchange slab of {rows} rows cannot hold {slots} partial rows")
-            layout, slab, desc = self._tail_slab(batch.cols[key_idx], out_schema, acc_kinds, rows)
-            d_unit_ids = self.to_device(np.asarray(batch.unit_ids, dtype=np.int64)) if batch.unit_ids is not None else None
-            return {
-                "slab": slab, "layout": layout, "desc": desc, "d_unit_ids": d_unit_ids,
-                "cols": self._cols_array(batch, low.program.columns, low.program.code_columns, narrow_slots),
-                "n_cols": len(low.program.columns),
-                "key_slot": low.key_slot, "prog": low.program.to_struct(), "spec": low.spec(), "geom": geom,
-                "n_units": n_units, "slots": slots,
-                "d_units": self.to_device(chunks.reshape(-1)), "d_chunk0": self.to_device(chunk0),
-                "ws": self.workspace(geom.ws_bytes).zero_(),
-                "tail": {"desc": desc, "layout": layout, "slab": slab, "agg_to_acc": list(low.agg_to_acc),
-                         "acc_kinds": acc_kinds, "key_kind": batch.cols[key_idx].kind,
-                         "key_len": batch.cols[key_idx].fixed_len, "n_units": n_units,
-                         "key_dict": batch.cols[key_idx].dict},
-                "info": {"rows": batch.nrows, "chunks": int(geom.n_chunks), "chunk_rows": int(geom.chunk_rows),
-                         "wg_threads": int(geom.wg_threads), "group_cap": cap, "lds_bytes": int(geom.lds_bytes),
-                         "tier": "private", "moved_bytes_per_row": moved, "narrow_slots": list(narrow_slots)},
-            }
+            layout, slab, desc = self._tail_slab(key_col, out_schema, acc_kinds, rows)
+            p.update(slab=slab, layout=layout, desc=desc,
+                     tail=_tail_info(desc, layout, slab, low, acc_kinds, key_col, n_units))
+            return p
+        key_out = out_unit = None
         if slab_rows is not None:
             # multi-GPU: outputs are written straight into the fixed-size slab that gets all-gathered
             from .distributed import SlabLayout  # noqa: PLC0415
 
             if slots > slab_rows:
                 raise DeviceError(f"exchange slab of {slab_rows} rows cannot hold {slots} partial rows")
-            kc = key_src if keyless else batch.cols[key_idx]
-            if kc.kind == hs.STR:
-                if kc.fixed_len not in (1, 2, 4, 8):
-                    raise SlabUnsupported("variable-length string GROUP BY key")
-                key_spec = (kc.fixed_len, torch.uint8)
-            else:
-                key_spec = (hs.KIND_BYTES[kc.kind], _TORCH_DTYPE[kc.kind])
+            key_spec = _slab_key_spec(key_col, (1, 2, 4, 8), "variable-length string GROUP BY key")
             layout = SlabLayout.build(slab_rows, [key_spec] + [(4, _TORCH_DTYPE[k]) for k in acc_kinds])
             slab = torch.zeros(layout.nbytes, dtype=torch.uint8, device=self.device)
             key_out = layout.column_view(slab, 0)
             acc_bufs = [layout.column_view(slab, 1 + i) for i in range(n_acc)]
             out_unit = layout.order_view(slab)
+            p.update(slab=slab, layout=layout)
         else:
             acc_bufs = [self.empty(max(slots, 1), _TORCH_DTYPE[k]) for k in acc_kinds]
-        d_unit_ids = None
-        if batch.unit_ids is not None:
-            d_unit_ids = self.to_device(np.asarray(batch.unit_ids, dtype=np.int64))
-            if out_unit is None:
-                out_unit = self.empty(max(slots, 1), torch.int64)
-        cols_arr, n_cols, unit_slot = (self._cols_array(batch, low.program.columns, low.program.code_columns, narrow_slots),
-                                       len(low.program.columns), None)
-        ws_bytes = geom.ws_bytes
-        if computed:
-            cols_arr = (hs.hs_col * (n_cols + 1))()
-            base_arr = self._cols_array(batch, low.program.columns, low.program.code_columns)
-            for slot in range(n_cols):
-                cols_arr[slot] = base_arr[slot]
-            cols_arr[n_cols] = DCol(hs.U8, batch.unit_col, batch.nrows).as_hs()
-            unit_slot, n_cols = n_cols, n_cols + 1
-            ws_bytes = ((n_units * unit_cap * 8 + 256 + 15) & ~15) + int(geom.n_chunks) * n_units * unit_cap * max(n_acc, 1) * 8
-        return {
-            "slab": slab, "layout": layout, "key_out": key_out, "out_unit": out_unit, "d_unit_ids": d_unit_ids,
-            "cols": cols_arr, "n_cols": n_cols, "unit_slot": unit_slot,
-            "key_slot": low.key_slot, "key_idx": key_idx, "key_src": key_src, "prog": low.program.to_struct(),
+        if d_unit_ids is not None and out_unit is None:
+            out_unit = self.empty(max(slots, 1), torch.int64)
+        p.update({
+            "key_out": key_out, "out_unit": out_unit, "unit_slot": unit_slot, "key_idx": key_idx, "key_src": key_src,
             "out_rows": self.empty(max(n_units, 1), torch.int64) if keyless else None,
-            "spec": low.spec(), "geom": geom, "n_units": n_units, "slots": slots, "unit_cap": unit_cap,
-            "agg_to_acc": low.agg_to_acc,
-            "d_units": self.to_device(chunks.reshape(-1)), "d_chunk0": self.to_device(chunk0),
+            "unit_cap": unit_cap, "agg_to_acc": low.agg_to_acc,
             "out_rep": self.empty(slots, torch.int64), "out_acc": self.empty(max(slots * n_acc, 1), torch.int64),
-            "ngroups": self.empty(max(n_units, 1), torch.int32), "ws": self.workspace(ws_bytes).zero_(),
+            "ngroups": self.empty(max(n_units, 1), torch.int32),
             "pack_start": self.empty(n_units + 1, torch.int64), "dense_rep": self.empty(max(slots, 1), torch.int64),
             "acc_kinds": acc_kinds, "acc_bufs": acc_bufs,
             "out_ptrs": (C.c_void_p * max(n_acc, 1))(*[t.data_ptr() for t in acc_bufs]),
             "kinds_arr": (C.c_int32 * max(n_acc, 1))(*acc_kinds),
-            "info": {"rows": batch.nrows, "chunks": int(geom.n_chunks), "chunk_rows": int(geom.chunk_rows),
-                     "wg_threads": int(geom.wg_threads), "group_cap": cap, "lds_bytes": int(geom.lds_bytes),
-                     "tier": "scalar" if keyless else "shared" if shared else "private",
-                     "moved_bytes_per_row": moved, "narrow_slots": list(narrow_slots)},
-        }
+        })
+        return p
 
     # ---- final merge (A7) ------------------------------------------------------------------------------
     def aggregate_merge(self, batch: DBatch, agg_columns: Sequence[Any], out_schema: Schema,
@@ -1413,9 +1404,7 @@ class Device:
         if prep is None:
             prep = self._prepare_finish(tail, agg_columns, merged_schema, project, out_schema, cap)
             if cache_key is not None:
-                if len(self._finish_prepared) >= 8:
-                    self._finish_prepared.pop(next(iter(self._finish_prepared)))
-                self._finish_prepared[key] = prep
+                _bounded_put(self._finish_prepared, key, prep, 8)
         p = prep
         desc = p["desc"]
         # the "done" word of a mapped result image is cleared by the host right after it has read the result (finish()
@@ -2390,23 +2379,11 @@ class Device:
         world = dist_ctx[2] if dist_ctx else 1
         key = (cache_key, cap, batch.nrows, j["table"].data_ptr(), j["key_min"], j["slots"], world,
                tuple((c.kind, c.virtual, c.fixed_len, c.data.data_ptr(), c.n) for c in batch.cols))
-        preps = self.__dict__.setdefault("_join8_prepared", {})
-        p = preps.get(key) if cache_key is not None else None
+        p = self._join8_prepared.get(key) if cache_key is not None else None
         if p is None:
-            host_units = (C.c_int64 * 2)(0, batch.nrows)
-            geom = hs.hs_agg_geom()
-            rc = self.lib.hs_agg_shared_geom(host_units, 1, n_acc, cap, C.byref(geom))
-            if rc == 2:
-                raise TierExceeded("fused probe: " + self.lib.hs_last_error().decode())
-            hs.check(rc, "hs_agg_shared_geom")
-            chunks = np.zeros((max(int(geom.n_chunks), 1), 4), dtype=np.int64)
-            chunk0 = np.zeros(2, dtype=np.int64)
-            hs.check(self.lib.hs_agg_partial_chunks(host_units, 1, C.byref(geom), chunks.ctypes.data_as(C.POINTER(hs.hs_chunk)),
-                                                    chunk0.ctypes.data_as(C.POINTER(C.c_int64))), "hs_agg_partial_chunks")
-            per_unit, small = max(4, cap // n_units), 16
-            while small < 4 * per_unit:
-                small *= 2
-            geom.pad = min(int(geom.pad), small)  # slots of ONE unit's table (x4: open addressing)
+            # geom.pad = slots of ONE unit's table; the workspace holds the per-chunk cells only (the key words are xbuf's)
+            geom, d_units, _ = self._scan_geometry("hs_agg_shared_units_geom", [0, batch.nrows], (n_units, n_acc, cap, 1),
+                                                   "fused probe: ", self.to_device_const)
             unit_cap = int(geom.pad)
             slots = n_units * unit_cap
             acc_kinds = [hs.I32 if is_int else hs.F32 for is_int in low.acc_is_int]
@@ -2420,25 +2397,19 @@ class Device:
             table_bytes = 16 + slots * 8 * (1 + n_acc)
             xbuf = torch.zeros(table_bytes + PAD, dtype=torch.uint8, device=self.device)
             join = hs.hs_join8(j["table"].data_ptr(), j["slots"], j["key_min"], n_units)
-            p = {"geom": geom, "d_units": self.to_device_const(chunks.reshape(-1)), "cols": cols_arr, "n_cols": n_cols + 1,
+            p = {"geom": geom, "d_units": d_units, "cols": cols_arr, "n_cols": n_cols + 1,
                  "unit_slot": n_cols, "key_slot": low.key_slot, "prog": low.program.to_struct(), "spec": low.spec(),
                  "join": join, "n_units": n_units, "unit_cap": unit_cap, "slots": slots, "xbuf": xbuf,
                  "table_bytes": table_bytes, "out_rep": self.empty(slots, torch.int64),
-                 "ws": self.workspace(max(int(geom.n_chunks), 1) * slots * max(n_acc, 1) * 8),
+                 "ws": self.workspace(geom.ws_bytes),
                  "slab": slab, "layout": layout, "desc": desc, "keep": (batch, j),
-                 "tail": {"desc": desc, "layout": layout, "slab": slab, "agg_to_acc": list(low.agg_to_acc),
-                          "acc_kinds": acc_kinds, "key_kind": key_stored.kind, "key_len": key_stored.fixed_len,
-                          "n_units": n_units, "key_dict": key_stored.dict, "replicated": True},
-                 "info": {"rows": batch.nrows, "chunks": int(geom.n_chunks), "chunk_rows": int(geom.chunk_rows),
-                          "wg_threads": int(geom.wg_threads), "group_cap": cap, "lds_bytes": int(geom.lds_bytes),
-                          "tier": "shared, probe fused"}}
+                 "tail": _tail_info(desc, layout, slab, low, acc_kinds, key_stored, n_units, replicated=True),
+                 "info": _scan_info(batch.nrows, geom, cap, "shared, probe fused")}
             if world > 1:
                 p["gathered"] = torch.zeros(world * table_bytes + PAD, dtype=torch.uint8, device=self.device)
                 p["merged"] = torch.zeros(table_bytes + PAD, dtype=torch.uint8, device=self.device)
             if cache_key is not None:
-                if len(preps) >= 8:
-                    preps.pop(next(iter(preps)))
-                preps[key] = p
+                _bounded_put(self._join8_prepared, key, p, 8)
         if self.rec is not None:
             self.rec.keep.append(p)
         xbuf, slots = p["xbuf"], p["slots"]

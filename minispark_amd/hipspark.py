@@ -331,6 +331,7 @@ SIGNATURES: dict[str, tuple] = {
     ),
     "hs_agg_shared_geom": (C.c_int, [C.POINTER(_I64), _I64, _I32, _I32, _GEOMP]),
     "hs_agg_shared": (C.c_int, [_P, _COLP, _I32, _I32, _PROGP, _SPECP, _P, _I64, _GEOMP, _P, _P, _P, _P, _P, _P, _P]),
+    "hs_agg_shared_units_geom": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _GEOMP]),
     "hs_agg_shared_units": (C.c_int, [_P, _COLP, _I32, _I32, _I32, _I32, _PROGP, _SPECP, _P, _GEOMP, _P, _P, _P, _P, _P,
                                       _P, _P]),
     "hs_agg_shared_join8": (C.c_int, [_P, _COLP, _I32, _I32, _I32, C.POINTER(hs_join8), _I32, _PROGP, _SPECP, _P, _GEOMP,

@@ -250,3 +250,68 @@ def test_final_merge_tier_follows_the_real_number_of_partial_rows(tmp_path, grou
         assert not engine._caps["merge_overflowed"]
         if on_chip:
             assert engine.replays >= 1
+
+
+def test_computed_units_at_the_c_abi_with_every_buffer_sized_from_the_geometry(engine):
+    """hs_agg_shared_units called directly: two chunks, three unit tables, rows with unit id 0xff (they take no part).
+    Chunk table, outputs and workspace are sized from hs_agg_shared_units_geom alone - the contract of that entry.
+    Per (unit, key): INTEGER MIN exactly, the FLOAT sum to 1e-12 relative (the values are quarters, so every order of
+    additions and the rounding to f32 give the same number; the tier promises ~1e-13)."""
+    import ctypes as C
+
+    import torch
+
+    from minispark_amd import hipspark as hs
+    from minispark_amd.constants import ColumnType as T
+    from minispark_amd.lowering import lower_aggregate
+    from minispark_amd.sql import Col, Functions as F
+
+    dev, lib = engine.dev, hs.load_library()
+    n, tables = 65536 + 4100, 3
+    rng = np.random.default_rng(19)
+    k = rng.integers(0, 5, n).astype(np.int32) * 1000 - 7
+    f = (rng.integers(-4000, 4000, n) / 4).astype(np.float32)
+    i = rng.integers(-10**6, 10**6, n).astype(np.int32)
+    unit = rng.integers(0, tables + 1, n).astype(np.uint8)
+    unit[unit == tables] = 0xFF
+    schema = [("k", T.INTEGER), ("f", T.FLOAT), ("i", T.INTEGER)]
+    low = lower_aggregate(schema, [hs.I32, hs.F32, hs.I32], [], Col("k"), [F.sum(Col("f")).alias("s"), F.min(Col("i")).alias("m")])
+    host = [k, f, i]
+    tensors = [torch.from_numpy(host[c]).to(dev.device) for c in low.program.columns] + [torch.from_numpy(unit).to(dev.device)]
+    n_cols = len(tensors)
+    cols = (hs.hs_col * n_cols)()
+    for slot, t in enumerate(tensors):
+        cols[slot].kind = hs.U8 if slot == n_cols - 1 else [hs.I32, hs.F32, hs.I32][low.program.columns[slot]]
+        cols[slot].fixed_len, cols[slot].data = -1, t.data_ptr()
+    prog, spec = low.program.to_struct(), low.spec()
+    n_acc = spec.n_acc
+    geom = hs.hs_agg_geom()
+    hs.check(lib.hs_agg_shared_units_geom(n, tables, n_acc, 16, 0, C.byref(geom)), "hs_agg_shared_units_geom")
+    assert geom.n_chunks == 2 and geom.pad >= 16
+    bounds = (C.c_int64 * 2)(0, n)
+    chunks = np.zeros((geom.n_chunks, 4), dtype=np.int64)
+    chunk0 = np.zeros(2, dtype=np.int64)
+    hs.check(lib.hs_agg_partial_chunks(bounds, 1, C.byref(geom), chunks.ctypes.data_as(C.POINTER(hs.hs_chunk)),
+                                       chunk0.ctypes.data_as(C.POINTER(C.c_int64))), "hs_agg_partial_chunks")
+    d_chunks = torch.from_numpy(chunks.reshape(-1)).to(dev.device)
+    slots = tables * geom.pad
+    rep = torch.full((slots,), -7, dtype=torch.int64, device=dev.device)
+    acc = torch.zeros(slots * n_acc, dtype=torch.int64, device=dev.device)
+    ngroups = torch.full((tables,), -7, dtype=torch.int32, device=dev.device)
+    ws = torch.zeros(geom.ws_bytes, dtype=torch.uint8, device=dev.device)
+    dev.reset_flags()
+    hs.check(lib.hs_agg_shared_units(dev.stream, cols, n_cols, low.key_slot, n_cols - 1, tables, C.byref(prog), C.byref(spec),
+                                     d_chunks.data_ptr(), C.byref(geom), rep.data_ptr(), acc.data_ptr(), ngroups.data_ptr(),
+                                     ws.data_ptr(), dev.flags.data_ptr(), None, None), "hs_agg_shared_units")
+    assert dev.read_flags() == 0
+    rep, acc, ngroups = rep.cpu().numpy().reshape(tables, geom.pad), acc.cpu().numpy().reshape(tables, geom.pad, n_acc), ngroups.cpu().numpy()
+    a_sum, a_min = low.agg_to_acc
+    for u in range(tables):
+        got = {int(k[r]): (acc[u, s, a_sum : a_sum + 1].view(np.float64)[0], int(acc[u, s, a_min]))
+               for s, r in enumerate(rep[u]) if r >= 0}
+        assert ngroups[u] == len(got) == 5, (u, ngroups[u], sorted(got))
+        for key, (s, m) in got.items():
+            rows = (unit == u) & (k == key)
+            want = float(f[rows].astype(np.float64).sum())
+            assert m == int(i[rows].min()), (u, key)
+            assert abs(s - want) <= 1e-12 * abs(want), (u, key, s, want)
