@@ -663,6 +663,45 @@ int hs_mark_first(void* stream, const hs_col* keys, int32_t n_keys, int64_t nrow
 size_t hs_window_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words);
 int hs_window(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows,
               const int32_t* funcs, int32_t n_funcs, int32_t* const* out, void* ws, uint32_t* flags);
+/* Window aggregates over result rows, next to the ranking functions (no reference counterpart).  keys, descending,
+ * n_part, n_keys, nrows, partitions, peers and the order inside a partition are hs_window's.  Item i of n_items is
+ * funcs[i] - a ranking function, written exactly as hs_window writes it, or
+ *   HS_WIN_COUNT  the rows of the frame (HS_I32)
+ *   HS_WIN_SUM    the sum of values[i] over the frame: HS_I32 -> HS_I32, accumulated in i64, a value emitted outside i32
+ *                 raises HS_FLAG_INT_OVERFLOW; HS_F32 -> HS_F32, the cells added in f64 in the order of the scan tree (fixed
+ *                 by nrows and the 2048-row tile: the same bits from run to run, not the left-to-right fold), the f64
+ *                 rounded to f32 (RNE), a finite value beyond f32 raises HS_FLAG_FLT_OVERFLOW; NaN and infinities as IEEE
+ *                 adds them, and never beyond their partition
+ *   HS_WIN_AVG    that i64 / f64 sum divided by the frame's rows in f64, rounded to f32 (HS_F32)
+ *   HS_WIN_MIN / HS_WIN_MAX  the least / greatest cell of the frame in hs_order_by's order (-0.0 = 0.0, NaN after +inf:
+ *                 MAX is NaN if the frame holds one, MIN only if it holds nothing else); the cell's kind; which zero and
+ *                 which NaN payload is unspecified
+ * over the frame frames[i] of the row's partition (read for these five only):
+ *   HS_WIN_FRAME_PARTITION  every row of the partition
+ *   HS_WIN_FRAME_RANGE      the partition's first row through the row's LAST peer: peers share one value (without an order
+ *                           key every row is a peer: the whole partition)
+ *   HS_WIN_FRAME_ROWS       the partition's first row through the row itself, ties in input order
+ * values[i] (HOST array of n_items columns; read for SUM / AVG / MIN / MAX only): HS_I32 or HS_F32, nrows cells.  out[i]:
+ * nrows 4-byte cells in INPUT order.  All items share one sort, one heads pass and one tile carry; each then takes a
+ * segmented scan of its argument in sorted order (restart at a partition head by select), one store per frame into a table
+ * indexed by the frame's first position, and one scatter.  No atomics on values.  Refused before anything is launched or
+ * any device pointer is read: what hs_window refuses (HS_E_LIMIT: n_keys > HS_MAX_COLS, n_items > HS_WIN_MAX_FUNCS, nrows
+ * >= 2^31), and with HS_E_ARG and an error text that names the item an unknown function or frame and an argument column of
+ * any other kind (narrow and virtual columns among them).  nrows == 0: HS_OK, nothing launched.  Synchronises the stream
+ * like hs_window; must not be captured.  ws: hs_window_agg_ws_bytes(...) bytes (hs_window's + 16 bytes per row + 16 per
+ * tile; n_items does not enter: the items run one after the other).  flags: the device status word (may be null). */
+#define HS_WIN_COUNT 3
+#define HS_WIN_SUM 4
+#define HS_WIN_AVG 5
+#define HS_WIN_MIN 6
+#define HS_WIN_MAX 7
+#define HS_WIN_FRAME_PARTITION 0
+#define HS_WIN_FRAME_RANGE 1
+#define HS_WIN_FRAME_ROWS 2
+size_t hs_window_agg_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t n_items);
+int hs_window_agg(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows,
+                  const int32_t* funcs, const int32_t* frames, const hs_col* values, int32_t n_items,
+                  void* const* out, void* ws, uint32_t* flags);
 /* out[i] = values[s] for bounds[s] <= i < bounds[s+1], i in [0, n) (device arrays; bounds has n_seg + 1 entries,
  * bounds[0] = 0): the global block id of every partial row of a multi-rank partial aggregate. */
 int hs_expand_by_bounds(void* stream, const int64_t* bounds, const int64_t* values, int64_t n_seg, int64_t n, int64_t* out);

@@ -1677,17 +1677,20 @@ struct ObKeys {
 };
 static_assert(sizeof(ObKeys) % 8 == 0, "ObKeys");
 
+// the bits of a FLOAT cell as an unsigned word whose order is the cell's order (also the MIN / MAX accumulator of
+// hs_window_agg, which turns the winning word back into bits)
+__device__ __forceinline__ uint32_t ob_f32_word(uint32_t b) {
+    if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;  // every NaN: one value, after +inf
+    if (b == 0x80000000u) b = 0u;                          // -0.0 == +0.0
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
 // a numeric cell as an unsigned number of the column's width whose order is the cell's order
 __device__ __forceinline__ uint64_t ob_numeric(const hs_col& c, int64_t row) {
     switch (c.kind) {
         case HS_I32: return (uint64_t)(((const uint32_t*)c.data)[row] ^ 0x80000000u);
         case HS_I64: return ((const uint64_t*)c.data)[row] ^ 0x8000000000000000ull;
-        case HS_F32: {
-            uint32_t b = ((const uint32_t*)c.data)[row];
-            if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;  // every NaN: one value, after +inf
-            if (b == 0x80000000u) b = 0u;                          // -0.0 == +0.0
-            return (uint64_t)((b & 0x80000000u) ? ~b : (b | 0x80000000u));
-        }
+        case HS_F32: return (uint64_t)ob_f32_word(((const uint32_t*)c.data)[row]);
         case HS_F64: {
             uint64_t b = ((const uint64_t*)c.data)[row];
             if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) b = 0x7ff8000000000000ull;
@@ -2655,52 +2658,64 @@ extern "C" size_t hs_window_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_
            rx_align((size_t)((nrows + OB_TILE - 1) / OB_TILE + 1) * sizeof(int4));
 }
 
-extern "C" int hs_window(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
-                         int64_t nrows, const int32_t* funcs, int32_t n_funcs, int32_t* const* out, void* ws_, uint32_t* flags) {
-    (void)flags;
+// What both entries (hs_window, hs_window_agg) refuse before anything is launched or any device pointer is read, under
+// the caller's name.  HS_OK: go on (nrows == 0 included - the caller returns then).
+static int win_refuse(const char* name, const hs_col* keys, int32_t n_part, int32_t n_keys, int64_t nrows, const int32_t* funcs,
+                      int32_t n_funcs, const void* out, int32_t max_func) {
     if (n_keys < 0 || n_part < 0 || n_part > n_keys || nrows < 0 || n_funcs <= 0 || !funcs || !out) {
-        hs_set_error("hs_window: bad arguments");
+        hs_set_error("%s: bad arguments", name);
         return HS_E_ARG;
     }
     if (n_keys > HS_MAX_COLS) {
-        hs_set_error("hs_window: more than %d partition and order columns", HS_MAX_COLS);
+        hs_set_error("%s: more than %d partition and order columns", name, HS_MAX_COLS);
         return HS_E_LIMIT;
     }
-    if (hs_refuse_narrow("hs_window", keys, n_keys)) return HS_E_ARG;
+    if (hs_refuse_narrow(name, keys, n_keys)) return HS_E_ARG;
     if (n_funcs > HS_WIN_MAX_FUNCS) {
-        hs_set_error("hs_window: more than %d functions in one call", HS_WIN_MAX_FUNCS);
+        hs_set_error("%s: more than %d functions in one call", name, HS_WIN_MAX_FUNCS);
         return HS_E_LIMIT;
     }
     if (nrows >= (1ll << 31)) {
-        hs_set_error("hs_window: %lld rows; the INTEGER result holds positions below 2^31", (long long)nrows);
+        hs_set_error("%s: %lld rows; the INTEGER result holds positions below 2^31", name, (long long)nrows);
         return HS_E_LIMIT;
     }
     for (int f = 0; f < n_funcs; ++f) {
-        if (funcs[f] != HS_WIN_ROW_NUMBER && funcs[f] != HS_WIN_RANK && funcs[f] != HS_WIN_DENSE_RANK) {
-            hs_set_error("hs_window: function %d is not one of HS_WIN_*", funcs[f]);
+        if (funcs[f] < 0 || funcs[f] > max_func) {
+            hs_set_error("%s: function %d is not one of HS_WIN_*", name, funcs[f]);
             return HS_E_ARG;
         }
-        if (funcs[f] != HS_WIN_ROW_NUMBER && n_part == n_keys) {
-            hs_set_error("hs_window: RANK / DENSE_RANK need an order key");
+        if ((funcs[f] == HS_WIN_RANK || funcs[f] == HS_WIN_DENSE_RANK) && n_part == n_keys) {
+            hs_set_error("%s: RANK / DENSE_RANK need an order key", name);
             return HS_E_ARG;
         }
     }
-    if (nrows == 0) return HS_OK;
+    return HS_OK;
+}
+
+// The front half both entries share, nrows > 0: the pointer checks, ONE sort, ONE heads pass and ONE (p, q, d) tile carry.
+struct WinFront {
+    const uint8_t* heads;  // by sorted position, whole tiles
+    const int64_t* perm;   // the sorted rows (null: position = row)
+    const int4* carry;     // per tile
+    int64_t tiles;
+    uint8_t* rest;         // the workspace behind what hs_window_ws_bytes counts
+};
+static int win_front(hipStream_t stream, const char* name, const hs_col* keys, const int32_t* descending, int32_t n_part,
+                     int32_t n_keys, int64_t nrows, void* const* out, int32_t n_funcs, void* ws_, WinFront& F) {
     if (!ws_ || (n_keys > 0 && !keys) || (n_keys > n_part && !descending)) {
-        hs_set_error("hs_window: bad arguments");
+        hs_set_error("%s: bad arguments", name);
         return HS_E_ARG;
     }
     for (int f = 0; f < n_funcs; ++f)
         if (!out[f]) {
-            hs_set_error("hs_window: output %d is null", f);
+            hs_set_error("%s: output %d is null", name, f);
             return HS_E_ARG;
         }
     for (int k = 0; k < n_keys; ++k)
         if (!ob_kind_ok(keys[k])) {
-            hs_set_error("hs_window: key %d is not a column that can be ordered", k);
+            hs_set_error("%s: key %d is not a column that can be ordered", name, k);
             return HS_E_ARG;
         }
-    hipStream_t stream = (hipStream_t)stream_;
     int32_t desc[HS_MAX_COLS] = {0};
     for (int k = n_part; k < n_keys; ++k) desc[k] = descending[k] ? 1 : 0;
     WinHeads H;
@@ -2709,7 +2724,7 @@ extern "C" int hs_window(void* stream_, const hs_col* keys, const int32_t* desce
     {
         ObSorted S;
         int64_t sorted_rows = 0;
-        const int rc = ob_sort(stream, keys, desc, n_keys, nrows, nullptr, -1, &sorted_rows, ws_, "hs_window", S);
+        const int rc = ob_sort(stream, keys, desc, n_keys, nrows, nullptr, -1, &sorted_rows, ws_, name, S);
         if (rc != HS_OK) return rc;
         H.K = S.keys;
         H.n_keys = n_keys;
@@ -2723,23 +2738,380 @@ extern "C" int hs_window(void* stream_, const hs_col* keys, const int32_t* desce
     H.heads = (uint8_t*)ws_ + sort_bytes;
     int4* sums = (int4*)(H.heads + win_heads_bytes(nrows));
     const int64_t tiles = (nrows + OB_TILE - 1) / OB_TILE;
-    WinEmit E;
-    std::memset(&E, 0, sizeof(E));
-    E.heads = H.heads;
-    E.perm = H.perm;
-    E.carry = sums;
-    E.n = nrows;
     hipLaunchKernelGGL(k_win_heads, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, H);
-    RX_CHECK_LAUNCH("hs_window (heads)");
+    if (hipGetLastError() != hipSuccess) {
+        hs_set_error("%s (heads): kernel launch failed", name);
+        return HS_E_LAUNCH;
+    }
     hipLaunchKernelGGL(k_win_reduce, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, (const uint8_t*)H.heads, nrows, sums);
     hipLaunchKernelGGL(k_win_tiles, dim3(1), dim3(OB_THREADS), 0, stream, sums, tiles);
-    RX_CHECK_LAUNCH("hs_window (scan)");
+    if (hipGetLastError() != hipSuccess) {
+        hs_set_error("%s (scan): kernel launch failed", name);
+        return HS_E_LAUNCH;
+    }
+    F = WinFront{H.heads, H.perm, sums, tiles, (uint8_t*)sums + rx_align((size_t)(tiles + 1) * sizeof(int4))};
+    return HS_OK;
+}
+
+extern "C" int hs_window(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
+                         int64_t nrows, const int32_t* funcs, int32_t n_funcs, int32_t* const* out, void* ws_, uint32_t* flags) {
+    (void)flags;
+    int rc = win_refuse("hs_window", keys, n_part, n_keys, nrows, funcs, n_funcs, out, HS_WIN_DENSE_RANK);
+    if (rc != HS_OK || nrows == 0) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    WinFront F;
+    rc = win_front(stream, "hs_window", keys, descending, n_part, n_keys, nrows, (void* const*)out, n_funcs, ws_, F);
+    if (rc != HS_OK) return rc;
+    WinEmit E;
+    std::memset(&E, 0, sizeof(E));
+    E.heads = F.heads;
+    E.perm = F.perm;
+    E.carry = F.carry;
+    E.n = nrows;
     for (int f = 0; f < n_funcs; ++f) {
         E.out = out[f];
         E.func = funcs[f];
-        hipLaunchKernelGGL(k_win_emit, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, E);
+        hipLaunchKernelGGL(k_win_emit, dim3((unsigned)F.tiles), dim3(OB_THREADS), 0, stream, E);
     }
     RX_CHECK_LAUNCH("hs_window (emit)");
+    return HS_OK;
+}
+
+// =====================================================================================================
+// Window aggregates over result rows (include/hipspark.h hs_window_agg).
+//
+// COUNT / SUM / AVG / MIN / MAX ride on win_front: the same sort, head bytes and (p, q, d) tile carry.  Per sorted
+// position j the value is the fold of the argument over [P(j), E(j)], P the partition head at or before j and E the
+// frame's end: j itself (ROWS), the last peer of j (RANGE), the partition's last row (PARTITION).  The fold is one more
+// segmented scan that restarts at every partition head, beside p and q:
+//     (p, q, a) (+) (p', q', a') = (max(p, p'), max(q, q'), p' >= 0 ? a' : a op a')
+// - the restart is a select, so a NaN or an infinity never leaves its partition - with a 64-bit accumulator: an i64 sum,
+// an f64 sum, or for MIN / MAX the sort's order-preserving word of the cell (ob_f32_word: -0.0 = 0.0, NaN after +inf).
+// Earlier positions stay on the LEFT at every level, so the association of an f64 sum is fixed by (rows, tile geometry):
+// the same bits from run to run, not those of the left-to-right fold.  Per item:
+//   k_wagg_reduce  gathers the argument through the row list (coalesced over positions, across to the lanes' 8
+//                  consecutive positions through LDS), leaves the cells in SORTED order for the next pass and folds the
+//                  tile into one summary;
+//   k_wagg_tiles   one workgroup, rounds of 2048 summaries: every tile's carry;
+//   k_wagg_scan    scans the tile again behind both carries and, at every frame end, stores the running value and the
+//                  frame's row count into two tables indexed by the frame's START position (j, Q or P): one vector
+//                  store per frame, no atomics;
+//   k_wagg_emit    every position reads the tables at its own j / Q / P - all rows of a frame the same cell - finishes
+//                  the value (AVG divides, SUM / AVG round to the cell type and raise the overflow flags) and scatters
+//                  out[perm[j]], one launch per item like k_win_emit.
+// COUNT has no argument: it skips the first two kernels; COUNT under ROWS is ROW_NUMBER and takes k_win_emit.
+// =====================================================================================================
+enum { WA_NONE = 0, WA_ADD_I = 1, WA_ADD_F = 2, WA_MIN = 3, WA_MAX = 4 };
+
+struct WinA {
+    int32_t p, q;  // as in WinS
+    uint64_t a;    // the fold since the last partition head
+};
+static_assert(sizeof(WinA) == 16, "WinA");
+
+__device__ __forceinline__ uint64_t wa_identity(int op) { return op == WA_MIN ? ~0ull : 0ull; }
+__device__ __forceinline__ uint64_t wa_op(int op, uint64_t a, uint64_t b) {  // a: the EARLIER positions
+    switch (op) {
+        case WA_ADD_I: return a + b;
+        case WA_ADD_F: return hs_d2u(hs_u2d(a) + hs_u2d(b));
+        case WA_MIN: return a < b ? a : b;
+        case WA_MAX: return a > b ? a : b;
+        default: return 0;
+    }
+}
+// a stored cell as an accumulator
+__device__ __forceinline__ uint64_t wa_lift(int op, int is_float, uint32_t v) {
+    switch (op) {
+        case WA_ADD_I: return (uint64_t)(int64_t)(int32_t)v;
+        case WA_ADD_F: return hs_d2u((double)__uint_as_float(v));
+        case WA_MIN:
+        case WA_MAX: return is_float ? ob_f32_word(v) : v ^ 0x80000000u;
+        default: return 0;
+    }
+}
+__device__ __forceinline__ WinA wa_join(int op, const WinA a, const WinA b) {  // a: the EARLIER positions
+    return WinA{a.p > b.p ? a.p : b.p, a.q > b.q ? a.q : b.q, b.p >= 0 ? b.a : wa_op(op, a.a, b.a)};
+}
+__device__ __forceinline__ WinA wa_of(uint32_t head, int32_t j, uint64_t x) {
+    return WinA{(head & 2u) ? j : -1, (head & 1u) ? j : -1, x};
+}
+__device__ __forceinline__ WinA wa_shfl_up(const WinA v, int d) {
+    return WinA{__shfl_up(v.p, d, HS_WAVE), __shfl_up(v.q, d, HS_WAVE),
+                (uint64_t)__shfl_up((unsigned long long)v.a, d, HS_WAVE)};  // two 32-bit shuffles
+}
+// win_block_excl for WinA
+__device__ __forceinline__ WinA wa_block_excl(int op, const WinA v, WinA* s_wave, WinA& total) {
+    const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE;
+    const WinA none{-1, -1, wa_identity(op)};
+    WinA incl = v;
+#pragma unroll
+    for (int d = 1; d < HS_WAVE; d <<= 1) {
+        const WinA t = wa_shfl_up(incl, d);
+        if (lane >= d) incl = wa_join(op, t, incl);
+    }
+    if (lane == HS_WAVE - 1) s_wave[w] = incl;
+    WinA excl = wa_shfl_up(incl, 1);
+    if (lane == 0) excl = none;
+    __syncthreads();
+    WinA base = none;
+    total = none;
+#pragma unroll
+    for (int k = 0; k < OB_WAVES; ++k) {
+        if (k == w) base = total;
+        total = wa_join(op, total, s_wave[k]);
+    }
+    return wa_join(op, base, excl);
+}
+
+struct WaggArgs {
+    const uint8_t* heads;
+    const int64_t* perm;     // null: position = row
+    const int4* carry;       // per tile: (p, q, d) of the tiles before (k_win_tiles)
+    int64_t n;
+    const uint32_t* values;  // the argument's cells, input order (not read when op == WA_NONE)
+    uint32_t* sorted;        // the cells by sorted position, whole tiles
+    WinA* tiles;             // per tile: k_wagg_reduce's summary, then k_wagg_tiles' carry
+    uint64_t* tab_a;         // by the START position of a frame: its fold ...
+    int32_t* tab_c;          // ... and its rows
+    uint32_t* out;           // one item per launch: input order
+    uint32_t* flags;         // may be null
+    int32_t op, is_float, frame, func;
+};
+static_assert(sizeof(WaggArgs) % 8 == 0, "WaggArgs");
+
+__global__ void __launch_bounds__(OB_THREADS) k_wagg_reduce(const WaggArgs A_kernarg) {
+    HS_KERNARG(WaggArgs, A);
+    __shared__ WinA s_wave[OB_WAVES];
+    __shared__ uint32_t s_v[OB_TILE + OB_THREADS];  // one pad word per lane segment (k_win_emit's layout)
+    const int tid = threadIdx.x, op = A.op;
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t j = tile0 + e;
+        uint32_t v = 0;
+        if (j < A.n) {
+            v = A.values[A.perm ? A.perm[j] : j];
+            A.sorted[j] = v;
+        }
+        s_v[e + e / WIN_PER] = v;
+    }
+    __syncthreads();
+    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);  // the buffer holds whole tiles
+    WinA acc{-1, -1, wa_identity(op)};
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const uint64_t x = j0 + k < A.n ? wa_lift(op, A.is_float, s_v[tid * (WIN_PER + 1) + k]) : wa_identity(op);
+        acc = wa_join(op, acc, wa_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k), x));
+    }
+    WinA total;
+    wa_block_excl(op, acc, s_wave, total);
+    if (tid == 0) A.tiles[blockIdx.x] = total;
+}
+
+// one workgroup: tiles[t] = the join of the summaries of tiles 0 .. t - 1, in place (k_win_tiles for WinA)
+__global__ void __launch_bounds__(OB_THREADS) k_wagg_tiles(WinA* tiles, int64_t ntiles, int32_t op) {
+    __shared__ WinA s_wave[OB_WAVES];
+    const WinA none{-1, -1, wa_identity(op)};
+    WinA carry = none;  // the rounds before this one: the same in every thread
+    for (int64_t t0 = 0; t0 < ntiles; t0 += OB_TILE) {
+        const int64_t mine = t0 + (int64_t)threadIdx.x * WIN_PER;
+        WinA v[WIN_PER], acc = none;
+#pragma unroll
+        for (int k = 0; k < WIN_PER; ++k) {
+            v[k] = none;
+            if (mine + k < ntiles) v[k] = tiles[mine + k];
+            acc = wa_join(op, acc, v[k]);
+        }
+        WinA total;
+        WinA run = wa_join(op, carry, wa_block_excl(op, acc, s_wave, total));
+#pragma unroll
+        for (int k = 0; k < WIN_PER; ++k) {
+            if (mine + k < ntiles) tiles[mine + k] = run;
+            run = wa_join(op, run, v[k]);
+        }
+        carry = wa_join(op, carry, total);
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_wagg_scan(const WaggArgs A_kernarg) {
+    HS_KERNARG(WaggArgs, A);
+    __shared__ WinA s_wave[OB_WAVES];
+    const int tid = threadIdx.x, op = A.op, frame = A.frame;
+    const int64_t j0 = (int64_t)blockIdx.x * OB_TILE + (int64_t)tid * WIN_PER;
+    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);
+    // the head byte behind the lane's eight: written where it is a row (the byte after the last tile is never read)
+    const uint32_t next = j0 + WIN_PER < A.n ? A.heads[j0 + WIN_PER] : 0u;
+    uint32_t cell[WIN_PER] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (op != WA_NONE) {  // `sorted` holds whole tiles: cells past the rows are read and not used
+        const uint4 lo = *(const uint4*)(A.sorted + j0), hi = *(const uint4*)(A.sorted + j0 + 4);
+        cell[0] = lo.x, cell[1] = lo.y, cell[2] = lo.z, cell[3] = lo.w;
+        cell[4] = hi.x, cell[5] = hi.y, cell[6] = hi.z, cell[7] = hi.w;
+    }
+    uint64_t x[WIN_PER];
+    WinA acc{-1, -1, wa_identity(op)};
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        x[k] = j0 + k < A.n ? wa_lift(op, A.is_float, cell[k]) : wa_identity(op);
+        acc = wa_join(op, acc, wa_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k), x[k]));
+    }
+    const int4 c = A.carry[blockIdx.x];
+    const uint64_t ca = op != WA_NONE ? A.tiles[blockIdx.x].a : 0ull;
+    WinA total;
+    WinA run = wa_join(op, WinA{c.x, c.y, ca}, wa_block_excl(op, acc, s_wave, total));
+    const uint32_t end_bit = frame == HS_WIN_FRAME_RANGE ? 1u : 2u;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int64_t j = j0 + k;
+        if (j < A.n) {
+            run = wa_join(op, run, wa_of(win_head(bytes, k, j0, A.n), (int32_t)j, x[k]));
+            const uint32_t after = k + 1 < WIN_PER ? (uint32_t)(bytes >> (8 * (k + 1))) : next;
+            // a frame ends where the next position starts another run of peers / another partition, and at the last row
+            if (frame == HS_WIN_FRAME_ROWS || j + 1 >= A.n || (after & end_bit)) {
+                const int32_t start = frame == HS_WIN_FRAME_ROWS ? (int32_t)j : frame == HS_WIN_FRAME_RANGE ? run.q : run.p;
+                A.tab_a[start] = run.a;
+                A.tab_c[start] = (int32_t)j - run.p + 1;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t wa_f32(double d, uint32_t& err) {
+    const float f = (float)d;  // RNE
+    if (isinf(f) && !isinf(d)) err |= HS_FLAG_FLT_OVERFLOW;
+    return __float_as_uint(f);
+}
+// the cell an item stores for a frame's fold `a` over `count` rows
+__device__ __forceinline__ uint32_t wa_finish(int func, int is_float, uint64_t a, int32_t count, uint32_t& err) {
+    switch (func) {
+        case HS_WIN_COUNT: return (uint32_t)count;
+        case HS_WIN_SUM:
+            if (is_float) return wa_f32(hs_u2d(a), err);
+            if ((int64_t)a != (int64_t)(int32_t)a) err |= HS_FLAG_INT_OVERFLOW;
+            return (uint32_t)a;
+        case HS_WIN_AVG: return wa_f32((is_float ? hs_u2d(a) : (double)(int64_t)a) / (double)count, err);
+        default: {  // MIN / MAX: the word back to the cell
+            const uint32_t w = (uint32_t)a;
+            if (!is_float) return w ^ 0x80000000u;
+            return (w & 0x80000000u) ? (w & 0x7fffffffu) : ~w;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_wagg_emit(const WaggArgs A_kernarg) {
+    HS_KERNARG(WaggArgs, A);
+    __shared__ WinS s_wave[OB_WAVES];
+    __shared__ int32_t s_at[OB_TILE + OB_THREADS];  // the table cell of every position, handed over as in k_win_emit
+    const int tid = threadIdx.x, frame = A.frame;
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
+    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);
+    WinS acc{-1, -1, 0};
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) acc = win_join(acc, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
+    const int4 c = A.carry[blockIdx.x];
+    WinS total;
+    WinS run = win_join(WinS{c.x, c.y, c.z}, win_block_excl(acc, s_wave, total));
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        run = win_join(run, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
+        s_at[tid * (WIN_PER + 1) + k] = frame == HS_WIN_FRAME_ROWS ? (int32_t)(j0 + k) : frame == HS_WIN_FRAME_RANGE ? run.q : run.p;
+    }
+    __syncthreads();
+    uint32_t err = 0;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t j = tile0 + e;
+        if (j < A.n) {
+            const int64_t row = A.perm ? A.perm[j] : j;
+            const int32_t at = s_at[e + e / WIN_PER];
+            A.out[row] = wa_finish(A.func, A.is_float, A.tab_a[at], A.tab_c[at], err);
+        }
+    }
+    if (err && A.flags) atomicOr(A.flags, err);
+}
+
+static size_t wagg_extra_bytes(int64_t nrows) {
+    const size_t tiles = (size_t)((nrows + OB_TILE - 1) / OB_TILE);
+    return 4 * win_heads_bytes(nrows) + rx_align((size_t)nrows * 8) + rx_align((size_t)nrows * 4) + rx_align((tiles + 1) * sizeof(WinA));
+}
+
+extern "C" size_t hs_window_agg_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t n_items) {
+    (void)n_items;  // the items run one after the other over the same cells, tables and tile summaries
+    if (nrows < 0) return 0;
+    return hs_window_ws_bytes(nrows, n_keys, max_key_words) + wagg_extra_bytes(nrows);
+}
+
+extern "C" int hs_window_agg(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
+                             int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values, int32_t n_items,
+                             void* const* out, void* ws_, uint32_t* flags) {
+    int rc = win_refuse("hs_window_agg", keys, n_part, n_keys, nrows, funcs, n_items, out, HS_WIN_MAX);
+    if (rc != HS_OK) return rc;
+    for (int i = 0; i < n_items; ++i) {
+        if (funcs[i] < HS_WIN_COUNT) continue;  // ranking: neither a frame nor an argument
+        if (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > HS_WIN_FRAME_ROWS) {
+            hs_set_error("hs_window_agg: item %d: frame %d is not one of HS_WIN_FRAME_*", i, frames ? frames[i] : -1);
+            return HS_E_ARG;
+        }
+        if (funcs[i] == HS_WIN_COUNT) continue;
+        if (!values || (values[i].kind != HS_I32 && values[i].kind != HS_F32)) {
+            hs_set_error("hs_window_agg: item %d: the argument is a column of kind %d (a narrow or virtual column, or another "
+                         "type); it takes HS_I32 or HS_F32 cells", i, values ? values[i].kind : -1);
+            return HS_E_ARG;
+        }
+    }
+    if (nrows == 0) return HS_OK;
+    for (int i = 0; i < n_items; ++i)
+        if (funcs[i] > HS_WIN_COUNT && !values[i].data) {
+            hs_set_error("hs_window_agg: item %d: the argument column is null", i);
+            return HS_E_ARG;
+        }
+    hipStream_t stream = (hipStream_t)stream_;
+    WinFront F;
+    rc = win_front(stream, "hs_window_agg", keys, descending, n_part, n_keys, nrows, out, n_items, ws_, F);
+    if (rc != HS_OK) return rc;
+    WinEmit E;
+    std::memset(&E, 0, sizeof(E));
+    E.heads = F.heads;
+    E.perm = F.perm;
+    E.carry = F.carry;
+    E.n = nrows;
+    WaggArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.heads = F.heads;
+    A.perm = F.perm;
+    A.carry = F.carry;
+    A.n = nrows;
+    A.sorted = (uint32_t*)F.rest;
+    A.tab_a = (uint64_t*)(F.rest + 4 * win_heads_bytes(nrows));
+    A.tab_c = (int32_t*)((uint8_t*)A.tab_a + rx_align((size_t)nrows * 8));
+    A.tiles = (WinA*)((uint8_t*)A.tab_c + rx_align((size_t)nrows * 4));
+    A.flags = flags;
+    const dim3 grid((unsigned)F.tiles), block(OB_THREADS);
+    for (int i = 0; i < n_items; ++i) {
+        const int32_t func = funcs[i];
+        if (func < HS_WIN_COUNT || (func == HS_WIN_COUNT && frames[i] == HS_WIN_FRAME_ROWS)) {
+            E.out = (int32_t*)out[i];
+            E.func = func < HS_WIN_COUNT ? func : HS_WIN_ROW_NUMBER;  // the rows from the partition's first through this one
+            hipLaunchKernelGGL(k_win_emit, grid, block, 0, stream, E);
+            continue;
+        }
+        A.func = func;
+        A.frame = frames[i];
+        A.out = (uint32_t*)out[i];
+        A.op = WA_NONE;
+        if (func != HS_WIN_COUNT) {
+            A.is_float = values[i].kind == HS_F32;
+            A.values = (const uint32_t*)values[i].data;
+            A.op = func == HS_WIN_MIN ? WA_MIN : func == HS_WIN_MAX ? WA_MAX : A.is_float ? WA_ADD_F : WA_ADD_I;
+            hipLaunchKernelGGL(k_wagg_reduce, grid, block, 0, stream, A);
+            hipLaunchKernelGGL(k_wagg_tiles, dim3(1), block, 0, stream, A.tiles, F.tiles, A.op);
+        }
+        hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, A);
+        hipLaunchKernelGGL(k_wagg_emit, grid, block, 0, stream, A);
+    }
+    RX_CHECK_LAUNCH("hs_window_agg (items)");
     return HS_OK;
 }
 

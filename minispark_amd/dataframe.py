@@ -96,9 +96,11 @@ class DataFrame:
         return self._append(_t.SortTask, keys=pairs)
 
     def window(self, *items: Any, select_order: list[str] | None = None) -> "DataFrame":
-        """Window ranking over the result rows: every item - ``F.row_number()``, ``F.rank()`` or
-        ``F.dense_rank()`` with ``.over(partition_by=[...], order_by=[...])`` and an optional ``.alias(name)`` - adds one
-        INTEGER column behind the existing ones, in the order given; no row moves.  ``select_order`` (the SQL front end)
+        """Window items over the result rows: every item - ``F.row_number()``, ``F.rank()`` or
+        ``F.dense_rank()`` with ``.over(partition_by=[...], order_by=[...])``, or an aggregate ``F.sum(c)``, ``F.avg(c)``,
+        ``F.min(c)``, ``F.max(c)``, ``F.count()`` with ``.over(partition_by=[...], order_by=[...], rows=False)``, and an
+        optional ``.alias(name)`` - adds one column behind the existing ones (INTEGER for ranks and counts, the argument's
+        type for SUM / MIN / MAX, FLOAT for AVG), in the order given; no row moves.  ``select_order`` (the SQL front end)
         names all columns in the order wanted instead.  It comes before ``qualify`` / ``distinct`` / ``order_by`` /
         ``limit``, which may name the new columns."""
         if not items:

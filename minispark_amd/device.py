@@ -1703,16 +1703,23 @@ class Device:
             raise DeviceError(f"hs_distinct returned {out_count.value} rows of {n}")
         return perm[:out_count.value], out_count.value
 
-    WINDOW_KINDS = {"row_number": hs.WIN_ROW_NUMBER, "rank": hs.WIN_RANK, "dense_rank": hs.WIN_DENSE_RANK}
+    WINDOW_KINDS = {"row_number": hs.WIN_ROW_NUMBER, "rank": hs.WIN_RANK, "dense_rank": hs.WIN_DENSE_RANK,
+                    "count": hs.WIN_COUNT, "sum": hs.WIN_SUM, "avg": hs.WIN_AVG, "min": hs.WIN_MIN, "max": hs.WIN_MAX}
+    WINDOW_FRAMES = {None: hs.WIN_FRAME_PARTITION, "partition": hs.WIN_FRAME_PARTITION, "range": hs.WIN_FRAME_RANGE,
+                     "rows": hs.WIN_FRAME_ROWS}
 
-    def window(self, batch: DBatch, part_idx: Sequence[int], order_keys: Sequence[tuple[int, bool]],
-               funcs: Sequence[str]) -> list[DCol]:
-        """ROW_NUMBER / RANK / DENSE_RANK over the rows of ``batch`` (hs_window) -> one INTEGER column per entry of
-        ``funcs``, in INPUT order: no row moves.  ``part_idx`` = the PARTITION BY columns, ``order_keys`` = (column,
-        ascending) pairs of the window's ORDER BY; all functions share the one sort.  Equality and order are
-        ``distinct``'s and ``order_by``'s.  A dictionary-coded column goes as its code byte where it only partitions (one
-        code, one string) or where the dictionary is sorted, decoded otherwise, as in ``order_by``.  The call learns sizes
-        on the host between its steps, so a run that contains it is not replayable."""
+    def window(self, batch: DBatch, part_idx: Sequence[int], order_keys: Sequence[tuple[int, bool]], funcs: Sequence[str],
+               frames: Sequence[str | None] | None = None, value_idx: Sequence[int | None] | None = None) -> list[DCol]:
+        """The window items ``funcs`` over the rows of ``batch`` -> one column per item, in INPUT order: no row moves.
+        ``part_idx`` = the PARTITION BY columns, ``order_keys`` = (column, ascending) pairs of the window's ORDER BY; all
+        items share the one sort.  ROW_NUMBER / RANK / DENSE_RANK give INTEGER columns; when every item is one of them the
+        call is hs_window's, as before aggregates existed.  An aggregate item ("count", "sum", "avg", "min", "max") has its
+        frame in ``frames`` ("partition" | "range" | "rows") and its argument's column index in ``value_idx`` (INTEGER or
+        FLOAT; None for "count"), and the call is hs_window_agg's: FLOAT where the value is (AVG, SUM / MIN / MAX of a
+        FLOAT column).  An overflow it meets is raised in the status word, where the result's write finds it.  Equality
+        and order are ``distinct``'s and ``order_by``'s.  A dictionary-coded column goes as its code byte where it only
+        partitions (one code, one string) or where the dictionary is sorted, decoded otherwise, as in ``order_by``.  The
+        call learns sizes on the host between its steps, so a run that contains it is not replayable."""
         batch = self.resolve(batch)
         n = batch.nrows
         if self.rec is not None:
@@ -1732,16 +1739,35 @@ class Device:
             if k >= len(part_idx) and col.dict is not None and list(col.dict) != sorted(col.dict):
                 col = self.decoded(col)
             cols.append(col)
-        outs = [self.empty(max(n, 1), torch.int32) for _ in funcs]
+        codes = [self.WINDOW_KINDS[f] for f in funcs]
+        frames = list(frames) if frames is not None else [None] * len(funcs)
+        value_idx = list(value_idx) if value_idx is not None else [None] * len(funcs)
+        values: list[DCol | None] = []
+        for code, f, which in zip(codes, funcs, value_idx):
+            col = None
+            if code > hs.WIN_COUNT:
+                col = batch.cols[which] if which is not None else None
+                if col is None or col.virtual or col.kind not in (hs.I32, hs.F32):
+                    raise DeviceError(f"the window aggregate {f} takes a stored INTEGER or FLOAT column")
+            values.append(col)
+        floats = [code == hs.WIN_AVG or (col is not None and col.kind == hs.F32) for code, col in zip(codes, values)]
+        outs = [self.empty(max(n, 1), torch.float32 if is_float else torch.int32) for is_float in floats]
         if n:
             arr = (hs.hs_col * max(n_keys, 1))(*[c.as_hs() for c in cols])
             desc = (C.c_int32 * max(n_keys, 1))(*([0] * len(part_idx) + [0 if ascending else 1 for _, ascending in order_keys]))
-            kinds = (C.c_int32 * len(funcs))(*[self.WINDOW_KINDS[f] for f in funcs])
+            kinds = (C.c_int32 * len(funcs))(*codes)
             ptrs = (C.c_void_p * len(funcs))(*[o.data_ptr() for o in outs])
-            ws = self.workspace(self._raw_lib.hs_window_ws_bytes(n, n_keys, 32 * max(n_keys, 1)))
-            hs.check(self._raw_lib.hs_window(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, len(funcs), ptrs,
-                                             ws.data_ptr(), self.flags.data_ptr()), "hs_window")
-        return [DCol(hs.I32, out[:n], n) for out in outs]
+            if all(code <= hs.WIN_DENSE_RANK for code in codes):
+                ws = self.workspace(self._raw_lib.hs_window_ws_bytes(n, n_keys, 32 * max(n_keys, 1)))
+                hs.check(self._raw_lib.hs_window(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, len(funcs), ptrs,
+                                                 ws.data_ptr(), self.flags.data_ptr()), "hs_window")
+            else:
+                frame_codes = (C.c_int32 * len(funcs))(*[self.WINDOW_FRAMES[f] for f in frames])
+                vals = (hs.hs_col * len(funcs))(*[c.as_hs() if c is not None else hs.hs_col() for c in values])
+                ws = self.workspace(self._raw_lib.hs_window_agg_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(funcs)))
+                hs.check(self._raw_lib.hs_window_agg(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, frame_codes, vals,
+                                                     len(funcs), ptrs, ws.data_ptr(), self.flags.data_ptr()), "hs_window_agg")
+        return [DCol(hs.F32 if is_float else hs.I32, out[:n], n) for is_float, out in zip(floats, outs)]
 
     def mark_first(self, batch: DBatch, key_indices: Sequence[int], sel: torch.Tensor | None = None, n_sel: int = 0,
                    mode: int = 0) -> DCol:

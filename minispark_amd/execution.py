@@ -771,8 +771,8 @@ class HipExecutionEngine(ExecutionEngine):
         return self.dev.gather_batch(batch, perm, count)
 
     def _window_rows(self, batch: Any, sort: Any) -> Any:
-        """Window ranking, the first step of a windowed SortTask: the rounded result rows gain one
-        INTEGER column per item - items with one (partition, order) spec share one sort and one launch sequence
+        """Window items, the first step of a windowed SortTask: the rounded result rows gain one
+        column per item - items with one (partition, order) spec share one sort and one launch sequence
         (Device.window) - the column handles are placed in the task's output order (no row is copied), and QUALIFY
         filters the rows through the WHERE machinery.  Keys are found by POSITION in the task's input schema."""
         from .device import DBatch  # noqa: PLC0415
@@ -789,7 +789,11 @@ class HipExecutionEngine(ExecutionEngine):
         for items in specs.values():
             part = [in_names.index(col.name) for col in items[0].partition_by]
             order = [(in_names.index(col.name), ascending) for col, ascending in items[0].order_by]
-            for item, col in zip(items, self.dev.window(batch, part, order, [item.kind for item in items])):
+            extra = ()
+            if any(item.kind in item.AGGREGATES for item in items):  # the frames, and the arguments by position too
+                extra = ([item.frame for item in items],
+                         [None if item.arg is None else in_names.index(item.arg.name) for item in items])
+            for item, col in zip(items, self.dev.window(batch, part, order, [item.kind for item in items], *extra)):
                 by_name[item.name] = col
         out_schema = list(sort.inferred_schema)
         batch = DBatch(out_schema, [by_name[name] for name, _ in out_schema], batch.nrows)

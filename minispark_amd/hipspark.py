@@ -50,6 +50,8 @@ FLAG_KNOWN = 0xFFF  # every HS_FLAG_* bit include/hipspark.h defines
 
 AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2
 WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK = 0, 1, 2  # hs_window's functions
+WIN_COUNT, WIN_SUM, WIN_AVG, WIN_MIN, WIN_MAX = 3, 4, 5, 6, 7  # hs_window_agg's further functions ...
+WIN_FRAME_PARTITION, WIN_FRAME_RANGE, WIN_FRAME_ROWS = 0, 1, 2  # ... and their frames
 WIN_MAX_FUNCS = 8
 
 # opcodes
@@ -376,6 +378,8 @@ SIGNATURES: dict[str, tuple] = {
     "hs_mark_first": (C.c_int, [_P, _COLP, _I32, _I64, _P, _I64, _I32, _P, _P, _P]),
     "hs_window_ws_bytes": (C.c_size_t, [_I64, _I32, _I32]),
     "hs_window": (C.c_int, [_P, _COLP, _P, _I32, _I32, _I64, _P, _I32, _P, _P, _P]),
+    "hs_window_agg_ws_bytes": (C.c_size_t, [_I64, _I32, _I32, _I32]),
+    "hs_window_agg": (C.c_int, [_P, _COLP, _P, _I32, _I32, _I64, _P, _P, _COLP, _I32, _P, _P, _P]),
     "hs_expand_by_bounds": (C.c_int, [_P, _P, _P, _I64, _I64, _P]),
     "hs_group_mask": (C.c_int, [_P, _P, _I64, _P]),
     "hs_group_fold": (C.c_int, [_P, _COLP, _SPECP, _P, _I64, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),

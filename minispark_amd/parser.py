@@ -27,9 +27,11 @@ A hand-written backtracking recursive-descent parser for the same language:
   ``SELECT DISTINCT`` (the keyword, then whitespace) becomes ``distinct()`` between the final select and ``order_by``:
   rows equal in every result column are removed, the first of them stays, and ORDER BY / LIMIT apply to what is left.
   The form without the keyword is tried first, so a text that was accepted before builds the tree it built then.
-* window ranking, tried only after every older form failed, so accepted texts keep their trees:
+* window ranking and window aggregates, tried only after every older form failed, so accepted texts keep their trees:
       select item:  ROW_NUMBER() | RANK() | DENSE_RANK()  OVER ( [PARTITION BY name {, name}]
                                                                  [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] )  [AS alias]
+                    SUM(name) | AVG(name) | MIN(name) | MAX(name) | COUNT()  OVER ( [PARTITION BY ...] [ORDER BY ...] [frame] )
+                    frame:  ROWS | RANGE  [BETWEEN]  UNBOUNDED PRECEDING  [AND CURRENT ROW]         [AS alias]
       clause:       ... [GROUP BY ... [HAVING ...]] [QUALIFY cond] [ORDER BY ...] [LIMIT n] ;
   The items are set aside from the select list (before GROUP BY's stray-column check), the rest of the query is built as
   ever, and ``window(...)`` / ``qualify(cond)`` follow the final select; names inside OVER are names of the RESULT, as for
@@ -303,13 +305,27 @@ class _Parser:
         return self.first_of(self.star, self.window_item, self.aggregate_call, self.expr_aliased)
 
     def window_item(self) -> WindowItem:
-        """ROW_NUMBER() | RANK() | DENSE_RANK(), whitespace, OVER ( [PARTITION BY names] [ORDER BY keys] ) [AS alias].
-        Anything else - no OVER, an argument - is no window item and goes on to the function call it was before."""
-        name = self.first_of(*[(lambda n=n: self.lit(n)) for n in ("ROW_NUMBER", "RANK", "DENSE_RANK")])
+        """ROW_NUMBER() | RANK() | DENSE_RANK() | SUM(name) | AVG(name) | MIN(name) | MAX(name) | COUNT(), whitespace,
+        OVER ( [PARTITION BY names] [ORDER BY keys] [frame] ) [AS alias].  Anything else - no OVER, an argument to a
+        ranking function - is no window item and goes on to the function call it was before."""
+        name = self.first_of(*[(lambda n=n: self.lit(n)) for n in ("ROW_NUMBER", "RANK", "DENSE_RANK", *_AGGREGATES)])
+        ranking = name not in _AGGREGATES
         self.ows()
         self.lit("(")
         self.ows()
-        self.lit(")")
+        arg = None
+        if not ranking and name != "COUNT":
+            has_name, arg = self.attempt(lambda: (self.column_name(), self.ows(), self.lit(")"))[0])
+            if not has_name:  # an expression: a window item only if OVER follows, and then one that says what to do
+                self.expr()
+                self.ows()
+                self.lit(")")
+                self.ws()
+                self.lit("OVER")
+                raise SemanticError(f"{name}(...) OVER takes a plain column of the result, not an expression: alias the "
+                                    f"expression in the select list (SELECT a + 1 AS x, {name}(x) OVER (...))")
+        else:
+            self.lit(")")
         self.ws()
         self.lit("OVER")
         self.ows()
@@ -325,14 +341,38 @@ class _Parser:
             cols += self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), self.column_name())[3])
             return cols
 
+        def frame() -> str:
+            """ROWS | RANGE  [BETWEEN]  UNBOUNDED PRECEDING  [AND CURRENT ROW]: the only frame there is"""
+            unit = self.first_of(lambda: self.lit("ROWS"), lambda: self.lit("RANGE"))
+            self.ws()
+            self.attempt(lambda: (self.lit("BETWEEN"), self.ws()))
+            self.lit("UNBOUNDED")
+            self.ws()
+            self.lit("PRECEDING")
+            self.attempt(lambda: (self.ws(), self.lit("AND"), self.ws(), self.lit("CURRENT"), self.ws(), self.lit("ROW")))
+            return unit
+
         has_partition, part = self.attempt(partition)
         if has_partition:
             has_order, order = self.attempt(lambda: (self.ws(), self.order_by_clause())[1])
         else:
             has_order, order = self.attempt(self.order_by_clause)
+        if has_partition or has_order:
+            has_frame, unit = self.attempt(lambda: (self.ws(), frame())[1])
+        else:
+            has_frame, unit = self.attempt(frame)
         self.ows()
         self.lit(")")
-        item = WindowItem(name.lower()).over(partition_by=part if has_partition else [], order_by=order if has_order else [])
+        keys = dict(partition_by=part if has_partition else [], order_by=order if has_order else [])
+        if ranking:
+            if has_frame:
+                raise ValueError(f"{name}() takes no frame clause ({unit} ...): a rank is a property of the row's place in its "
+                                 "partition, not of a frame")
+            item = WindowItem(name.lower()).over(**keys)
+        else:
+            agg = F.count() if name == "COUNT" else {"SUM": F.sum, "AVG": F.avg, "MIN": F.min, "MAX": F.max}[name](arg)
+            # RANGE is the default frame: through the last peer, which without ORDER BY is the whole partition
+            item = agg.over(**keys, rows=has_frame and unit == "ROWS")
         has_alias, alias = self.attempt(self.alias)
         self.saw_window_item = True
         return item.alias(alias) if has_alias else item

@@ -157,31 +157,50 @@ class SortKey:
 
 
 class WindowItem:
-    """``F.row_number() | F.rank() | F.dense_rank()`` ``.over(partition_by=[...], order_by=[...])`` ``[.alias(name)]``: one
-    window column of ``DataFrame.window`` (no reference counterpart - DESIGN.md 4.4f).  The keys are plain columns of the
-    RESULT the window reads (``Col``, ``Col.asc()``, ``Col.desc()``); the item adds one INTEGER column, named after its
-    function unless ``alias`` says otherwise.  Not an expression: it cannot be selected, compared or nested."""
+    """``F.row_number() | F.rank() | F.dense_rank()`` ``.over(partition_by=[...], order_by=[...])`` ``[.alias(name)]``, or an
+    aggregate ``F.sum(col) | F.avg(col) | F.min(col) | F.max(col) | F.count()`` ``.over(..., rows=False)``: one window column
+    of ``DataFrame.window`` (no reference counterpart - DESIGN.md 4.4f, 4.4g).  The keys and an aggregate's argument are
+    plain columns of the RESULT the window reads (``Col``, ``Col.asc()``, ``Col.desc()``).  A ranking item adds an INTEGER
+    column named after its function; an aggregate item a column of ``out_type`` named as the aggregate is (``sum_v``,
+    ``count``) - unless ``alias`` says otherwise.  ``frame`` (aggregates): "partition" - every row of the partition, no
+    ORDER BY; "range" - through the row's last peer, the default with ORDER BY; "rows" - through the row itself
+    (``rows=True``).  Not an expression: it cannot be selected, compared or nested."""
 
-    KINDS = ("row_number", "rank", "dense_rank")
+    RANKING = ("row_number", "rank", "dense_rank")
+    AGGREGATES = ("sum", "avg", "min", "max", "count")
+    KINDS = RANKING + AGGREGATES
 
-    def __init__(self, kind: str) -> None:
+    def __init__(self, kind: str, arg: Col | None = None) -> None:
         if kind not in self.KINDS:
             raise ValueError(f"window function {kind!r}: one of {self.KINDS}")
-        self.kind, self.name = kind, kind
+        if (arg is not None) != (kind in self.AGGREGATES and kind != "count"):
+            raise ValueError(f"window function {kind!r}: SUM / AVG / MIN / MAX take one column, every other function none")
+        if arg is not None and type(arg).__name__ not in {"Col", "SchemaCol"}:
+            raise ValueError(f"a window aggregate takes plain columns of the result, not the expression {arg}: "
+                             "select(... .alias()) first")
+        self.kind, self.arg = kind, arg
+        self.name = kind if arg is None else f"{kind}_{arg.name}"
+        self.frame: str | None = None
         self.partition_by: list[Col] = []
         self.order_by: list[tuple[Col, bool]] = []
         self.is_over = False
 
-    def over(self, partition_by: Any = (), order_by: Any = ()) -> "WindowItem":
+    def over(self, partition_by: Any = (), order_by: Any = (), rows: bool = False) -> "WindowItem":
         single = lambda v: [v] if isinstance(v, (Col, SortKey)) else list(v)  # noqa: E731
         self.partition_by = single(partition_by)
         self.order_by = [(k.column, k.ascending) if isinstance(k, SortKey) else (k, True) for k in single(order_by)]
         for col in [*self.partition_by, *[c for c, _ in self.order_by]]:
             if type(col).__name__ not in {"Col", "SchemaCol"}:
                 raise ValueError(f"OVER takes plain columns of the result, not the expression {col}: select(... .alias()) first")
-        if self.kind != "row_number" and not self.order_by:
-            raise ValueError(f"{self.kind.upper()}() needs an ORDER BY inside OVER: without one every row of a partition is a "
-                             "peer of every other (ROW_NUMBER() may omit it)")
+        if self.kind in self.RANKING:
+            if rows:
+                raise ValueError(f"{self.kind.upper()}() takes no frame clause: a rank is a property of the row's place in its "
+                                 "partition, not of a frame")
+            if self.kind != "row_number" and not self.order_by:
+                raise ValueError(f"{self.kind.upper()}() needs an ORDER BY inside OVER: without one every row of a partition is "
+                                 "a peer of every other (ROW_NUMBER() may omit it)")
+        else:
+            self.frame = "rows" if rows else "range" if self.order_by else "partition"
         self.is_over = True
         return self
 
@@ -193,13 +212,27 @@ class WindowItem:
         """What the sort depends on: items with one spec share one sort."""
         return (tuple(c.name for c in self.partition_by), tuple((c.name, asc) for c, asc in self.order_by))
 
+    def out_type(self, schema: Schema) -> ColumnType:
+        """The type of the column the item adds, given the schema of the rows it reads.  An aggregate's argument is an
+        INTEGER or FLOAT column of them: ``TypeError`` that names it otherwise (a name the rows do not have: the ``ValueError``
+        a key raises)."""
+        if self.arg is None:
+            return ColumnType.INTEGER
+        arg_type = self.arg.infer_type(schema)  # ValueError('Column "x" not found in schema ...')
+        if arg_type not in (ColumnType.INTEGER, ColumnType.FLOAT):
+            raise TypeError(f'{self.kind.upper()}({self.arg.name}) OVER: column "{self.arg.name}" is {arg_type}; a window '
+                            "aggregate takes an INTEGER or FLOAT column")
+        return ColumnType.FLOAT if self.kind == "avg" else arg_type
+
     def __str__(self) -> str:
         parts = []
         if self.partition_by:
             parts.append("PARTITION BY " + ", ".join(str(c) for c in self.partition_by))
         if self.order_by:
             parts.append("ORDER BY " + ", ".join(f"{c} {'ASC' if asc else 'DESC'}" for c, asc in self.order_by))
-        return f"{self.kind.upper()}() OVER ({' '.join(parts)}) AS {self.name}"
+        if self.frame in ("rows", "range"):
+            parts.append(f"{self.frame.upper()} UNBOUNDED PRECEDING")
+        return f"{self.kind.upper()}({'' if self.arg is None else self.arg}) OVER ({' '.join(parts)}) AS {self.name}"
 
     __repr__ = __str__
 
@@ -591,6 +624,18 @@ class AggCol(Col):
 
     def normalize_agg_columns(self) -> Col:
         return Col(self.name)
+
+    def over(self, partition_by: Any = (), order_by: Any = (), rows: bool = False) -> WindowItem:
+        """The aggregate as a window item: ``F.sum(Col("v")).over(partition_by=[Col("k")])``; it keeps the
+        aggregate's name.  ``F.count().over(...)`` counts the frame's rows."""
+        if self.type == "count_distinct":
+            raise ValueError(f"{self}: COUNT(DISTINCT) has no window form")
+        arg = self.original_col
+        if self.type == "sum" and type(arg) is Lit and arg.value == 1:
+            item = WindowItem("count")
+        else:
+            item = WindowItem(self.type, arg)
+        return item.alias(self.name).over(partition_by=partition_by, order_by=order_by, rows=rows)
 
     def expand_avg(self) -> Iterable["AggCol"]:
         """AVG(x) is carried through the shuffle as SUM(x) and SUM(1) (sql.py:436-441)."""

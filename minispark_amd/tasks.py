@@ -312,7 +312,7 @@ class SortTask(ConsumerTask):
     keys: list[tuple[Col, bool]] = field(default_factory=list)
     limit: int | None = None
     distinct: bool = False
-    # window ranking: ``windows`` = sql.WindowItem list, each one INTEGER column added to the input's
+    # window items: ``windows`` = sql.WindowItem list, each one column added to the input's
     # columns; ``qualify`` = a condition over all of them (QUALIFY), applied right after; ``select_order`` = the names of
     # all output columns in the order wanted (None: the input's columns, then the windows).  They run BEFORE distinct,
     # keys and limit, which may name the window columns.
@@ -336,7 +336,8 @@ class SortTask(ConsumerTask):
             for item in self.windows:
                 for col in [*item.partition_by, *[c for c, _ in item.order_by]]:
                     col.infer_type(schema)  # a key is a column of the INPUT, never another window item
-            schema = [*schema, *[(item.name, ColumnType.INTEGER) for item in self.windows]]
+            # ... and so is an aggregate's argument; every item adds a column of its own type (INTEGER: ranking and COUNT)
+            schema = [*schema, *[(item.name, item.out_type(self.input_schema)) for item in self.windows]]
             names = [name for name, _ in schema]
             repeated = sorted({name for name in names if names.count(name) > 1})
             if repeated:
@@ -375,7 +376,8 @@ def check_windows(windows: list) -> None:
         raise ValueError(f"a query takes at most {SortTask.MAX_WINDOWS} window items, not {len(windows)}")
     for item in windows:
         if type(item).__name__ != "WindowItem" or not item.is_over:
-            raise ValueError(f"window() takes F.row_number() / F.rank() / F.dense_rank() with .over(...), not {item}")
+            raise ValueError("window() takes F.row_number() / F.rank() / F.dense_rank() or F.sum(c) / F.avg(c) / F.min(c) / "
+                             f"F.max(c) / F.count() with .over(...), not {item}")
         if len(item.partition_by) + len(item.order_by) > MAX_WINDOW_KEYS:
             raise ValueError(f"{item}: partition and order columns together are at most {MAX_WINDOW_KEYS} (HS_MAX_COLS)")
 

@@ -6,9 +6,17 @@ per function:
   (b) the same, ROW_NUMBER + RANK + DENSE_RANK
   (c) PARTITION BY a TIMESTAMP ORDER BY an INTEGER, all three (two key words: the words are formed again)
   (d) no PARTITION BY, ORDER BY an INTEGER, all three
+Window aggregates (hs_window_agg), over case (a)'s keys, each timed next to hs_window ROW_NUMBER on the same keys (the cheapest
+windowed call there is: the aggregate adds a 4-byte gather of its argument, its scan passes and, like ROW_NUMBER, one scatter):
+  (e) SUM(INTEGER), default frame (RANGE: through the last peer)
+  (f) SUM(FLOAT) over the whole partition
+  (g) SUM(FLOAT), ROWS frame
+  (h) ROW_NUMBER + RANK + DENSE_RANK + SUM(INTEGER) + COUNT in one call, default frame
 Both calls read a few words back between their steps, so their times include those host round trips.  --case x --reps 3
-under a kernel trace gives the per-kernel split.
-Usage: python tools/bench_window.py [--rows 64M] [--partitions 1M] [--reps 20] [--case abcd] [--out profiles/r15_window.txt]"""
+under a kernel trace gives the per-kernel split.  --lib PATH times another build of the library (the parent commit's, for
+"ranking did not move"); a library without hs_window_agg runs (a) - (d) only.
+Usage: python tools/bench_window.py [--rows 64M] [--partitions 1M] [--reps 20] [--case abcdefgh] [--lib libhipspark.so]
+                                    [--out profiles/r20_window_agg.txt]"""
 from __future__ import annotations
 
 import argparse
@@ -46,11 +54,20 @@ def main() -> None:
     ap.add_argument("--rows", type=float, default=64 * 2**20)
     ap.add_argument("--partitions", type=float, default=2**20)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--case", default="abcd")
+    ap.add_argument("--case", default="abcdefgh")
+    ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     n, d = int(a.rows), int(a.partitions)
-    lib = hs.load_library()
+    if a.lib:  # another build: bind what it exports
+        lib = C.CDLL(str(Path(a.lib).resolve()))
+        for name, (restype, argtypes) in hs.SIGNATURES.items():
+            if hasattr(lib, name):
+                getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
+    else:
+        lib = hs.load_library()
+    has_agg = hasattr(lib, "hs_window_agg")
+    a.case = "".join(tag for tag in a.case if tag in "abcd" or has_agg)
     g = torch.Generator(device="cuda")
     g.manual_seed(15)
     part = torch.randint(0, d, (n,), device="cuda", generator=g, dtype=torch.int64)
@@ -59,8 +76,9 @@ def main() -> None:
     stamps = part * 1_000_003 + 1_700_000_000
     stream = torch.cuda.current_stream().cuda_stream
     perm = torch.empty(n, dtype=torch.int64, device="cuda")
-    outs = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(3)]
-    ws = torch.empty(int(lib.hs_window_ws_bytes(n, 2, 3)) + 256, dtype=torch.uint8, device="cuda")
+    outs = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(5 if has_agg else 3)]
+    ws_bytes = lib.hs_window_agg_ws_bytes(n, 2, 3, 5) if has_agg else lib.hs_window_ws_bytes(n, 2, 3)
+    ws = torch.empty(int(ws_bytes) + 256, dtype=torch.uint8, device="cuda")
     count = C.c_int64(0)
     col = lambda kind, t: hs.hs_col(kind, -1, t.data_ptr(), None, None)  # noqa: E731
     every = [hs.WIN_ROW_NUMBER, hs.WIN_RANK, hs.WIN_DENSE_RANK]
@@ -88,10 +106,45 @@ def main() -> None:
                                      None), "hs_order_by")
         return run
 
+    def window_agg(cols, n_part, items):
+        """items = [(function, frame, argument column or None)]"""
+        arr = (hs.hs_col * len(cols))(*cols)
+        asc = (C.c_int32 * len(cols))(*[0] * len(cols))
+        kinds = (C.c_int32 * len(items))(*[f for f, _, _ in items])
+        frames = (C.c_int32 * len(items))(*[fr for _, fr, _ in items])
+        values = (hs.hs_col * len(items))(*[v if v is not None else hs.hs_col() for _, _, v in items])
+        ptrs = (C.c_void_p * len(items))(*[o.data_ptr() for o in outs[:len(items)]])
+
+        def run():
+            hs.check(lib.hs_window_agg(stream, arr, asc, n_part, len(cols), n, kinds, frames, values, len(items), ptrs,
+                                       ws.data_ptr(), flags.data_ptr()), "hs_window_agg")
+        return run
+
+    agg_cases = {}
+    if has_agg:
+        flags = torch.zeros(2, dtype=torch.int32, device="cuda")
+        ints = torch.randint(-1000, 1001, (n,), device="cuda", generator=g, dtype=torch.int64).to(torch.int32)
+        floats = torch.rand(n, device="cuda", generator=g, dtype=torch.float32) * 2000.0 - 1000.0
+        vi, vf = col(hs.I32, ints), col(hs.F32, floats)
+        agg_cases = {"e": ("SUM(INTEGER), default frame", [(hs.WIN_SUM, hs.WIN_FRAME_RANGE, vi)]),
+                     "f": ("SUM(FLOAT), whole partition", [(hs.WIN_SUM, hs.WIN_FRAME_PARTITION, vf)]),
+                     "g": ("SUM(FLOAT), ROWS", [(hs.WIN_SUM, hs.WIN_FRAME_ROWS, vf)]),
+                     "h": ("three ranks + SUM(INTEGER) + COUNT", [(hs.WIN_ROW_NUMBER, 0, None), (hs.WIN_RANK, 0, None),
+                                                                  (hs.WIN_DENSE_RANK, 0, None), (hs.WIN_SUM, hs.WIN_FRAME_RANGE, vi),
+                                                                  (hs.WIN_COUNT, hs.WIN_FRAME_RANGE, None)])}
+
     lines = [f"tools/bench_window.py --rows {n} --partitions {d} --reps {a.reps}   [{torch.cuda.get_device_name(0)}, host "
              f"{socket.gethostname()}, torch {torch.__version__}]",
              "events on the launch stream, the two calls alternating; median (min - max) ms; ratio = hs_window / hs_order_by"]
     for tag in a.case:
+        if tag in agg_cases:
+            what, items = agg_cases[tag]
+            _, cols, n_part, _ = cases["a"]
+            (mw, lw, hw), (ms, lo, hi) = timed_pair(window_agg(cols, n_part, items), window(cols, n_part, every[:1]), a.reps)
+            lines.append(f"({tag}) hs_window_agg {what:33s} {mw:9.3f} ms ({lw:.3f} - {hw:.3f})   {n / mw / 1e6:8.2f} G rows/s")
+            lines.append(f"({tag}) hs_window    {'the same keys, ROW_NUMBER':34s} {ms:9.3f} ms ({lo:.3f} - {hi:.3f})   "
+                         f"{n / ms / 1e6:8.2f} G rows/s   ratio {mw / ms:.2f}   + {mw - ms:.3f} ms")
+            continue
         what, cols, n_part, funcs = cases[tag]
         (mw, lw, hw), (ms, lo, hi) = timed_pair(window(cols, n_part, funcs), order_by(cols), a.reps)
         lines.append(f"({tag}) hs_window    {what:34s} {mw:9.3f} ms ({lw:.3f} - {hw:.3f})   {n / mw / 1e6:8.2f} G rows/s")
@@ -102,7 +155,7 @@ def main() -> None:
         window(cols, n_part, funcs)()
         order_by(cols)()
         torch.cuda.synchronize()
-        rn, rk, dr = (o[perm].to(torch.int64) for o in outs)
+        rn, rk, dr = (o[perm].to(torch.int64) for o in outs[:3])
         p, o = part32[perm], order32[perm]
         new_part = torch.ones(n, dtype=torch.bool, device="cuda")
         new_part[1:] = p[1:] != p[:-1]
@@ -114,6 +167,24 @@ def main() -> None:
               and bool((dr[1:][~new_part[1:]] == dr[:-1][~new_part[1:]] + new_peer[1:][~new_part[1:]].to(torch.int64)).all()))
         lines.append(f"check (b): along the sorted rows row_number counts up inside a partition, rank is the row_number of the "
                      f"first peer, dense_rank steps by one per group of peers: {ok}")
+    if "e" in a.case:  # checked with torch over the sort's own row list: the running sum through the last peer
+        what, items = agg_cases["e"]
+        _, cols, n_part, _ = cases["a"]
+        window_agg(cols, n_part, items)()
+        order_by(cols)()
+        torch.cuda.synchronize()
+        p, o, v = part32[perm].to(torch.int64), order32[perm].to(torch.int64), ints[perm].to(torch.int64)
+        prefix = torch.cumsum(v, 0)
+        position = torch.arange(n, device="cuda")
+        new_part = torch.ones(n, dtype=torch.bool, device="cuda")
+        new_part[1:] = p[1:] != p[:-1]
+        last_peer = torch.ones(n, dtype=torch.bool, device="cuda")
+        last_peer[:-1] = (p[1:] != p[:-1]) | (o[1:] != o[:-1])
+        start = torch.cummax(torch.where(new_part, position, torch.zeros_like(position)), 0).values
+        end = torch.flip(torch.cummin(torch.flip(torch.where(last_peer, position, torch.full_like(position, n)), [0]), 0).values, [0])
+        want = prefix[end] - prefix[start] + v[start]
+        ok = bool((outs[0][perm].to(torch.int64) == want).all()) and int(flags[0].item()) == 0
+        lines.append(f"check (e): along the sorted rows the sum is the partition's prefix sum at the row's last peer: {ok}")
     text = "\n".join(lines)
     print(text)
     if a.out:
