@@ -702,6 +702,49 @@ size_t hs_window_agg_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_wor
 int hs_window_agg(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows,
                   const int32_t* funcs, const int32_t* frames, const hs_col* values, int32_t n_items,
                   void* const* out, void* ws, uint32_t* flags);
+/* Window navigation over result rows, next to the ranking functions and the aggregates (no reference counterpart).  keys,
+ * descending, n_part, n_keys, nrows, partitions, peers and the order inside a partition are hs_window's.  Item i of n_items
+ * is funcs[i] - any function of hs_window / hs_window_agg, written exactly as those entries write it (one sort for a mixed
+ * select list), or
+ *   HS_WIN_LAG / HS_WIN_LEAD  the cell of values[i] in the row params[i] = k places before / after the row in its
+ *                 partition's order (ties in input order; without an order key: input order); where the partition has no
+ *                 such row, the cell defaults[i] (its bits, in the low 4 bytes for a 4-byte kind).  0 <= k < 2^31; k = 0
+ *                 is the row's own cell
+ *   HS_WIN_FIRST_VALUE  the cell of the partition's first row (all three frames start there)
+ *   HS_WIN_LAST_VALUE   the cell of the last row of the frame frames[i]: the row itself (HS_WIN_FRAME_ROWS), the LAST of the
+ *                 row's peers in input order (HS_WIN_FRAME_RANGE), the partition's last row (HS_WIN_FRAME_PARTITION)
+ *   HS_WIN_NTILE  the row's bucket of params[i] = n buckets, 1 <= n < 2^31 (HS_I32): with r the row's ROW_NUMBER, N the rows
+ *                 of its partition, s = N div n and m = N mod n, (r-1) div (s+1) + 1 for r <= m(s+1), else
+ *                 m + (r-1-m(s+1)) div s + 1 - the first m buckets hold one row more; n > N: buckets 1 .. N of one row each
+ * values[i] (HOST array of n_items columns; read for the four value functions and for SUM / AVG / MIN / MAX): HS_I32, HS_F32
+ * or HS_I64 for the value functions, nrows cells.  frames[i] is read for FIRST_VALUE / LAST_VALUE and the aggregates,
+ * params[i] for LAG / LEAD / NTILE, defaults[i] for LAG / LEAD (HOST arrays of n_items entries; each may be null when no item
+ * reads it).  out[i]: nrows cells in INPUT order, of the argument's width for the value functions (8 bytes for HS_I64), 4 bytes
+ * for NTILE and every older function.  The value functions COPY cells: NaN payloads, -0.0, denormals and infinities come back
+ * bit for bit, and no navigation function raises a flag.
+ * Steps: hs_window's sort, heads pass and tile carry, once; one pass per frame that some item needs (PARTITION for LEAD,
+ * NTILE and LAST_VALUE over the partition, RANGE for LAST_VALUE through the last peer; LAG, FIRST_VALUE and LAST_VALUE under
+ * ROWS need none) stores the frame's rows at the frame's first position, one vector store per frame; one gather per
+ * distinct argument leaves its cells in sorted order (none when n_keys has no byte: position = row); per item one pass scans
+ * the heads again, reads the cell at the source position - computed in 64 bits, never outside the row's partition - and
+ * scatters it through the row list.  No atomics.  Refused before anything is launched or any device pointer is read: what
+ * hs_window refuses (HS_E_LIMIT: n_keys > HS_MAX_COLS, n_items > HS_WIN_MAX_FUNCS, nrows >= 2^31; HS_E_ARG: a function
+ * above HS_WIN_NTILE), and with HS_E_ARG and an error text that names the item: what hs_window_agg refuses for its items,
+ * an unknown frame on FIRST_VALUE / LAST_VALUE, k outside [0, 2^31) or n outside [1, 2^31), params / defaults null where
+ * the item reads them, an argument column of any other kind (narrow and virtual columns and HS_STR among them) or a null
+ * one.  nrows == 0: HS_OK, nothing launched.  Synchronises the stream like hs_window; must not be captured.
+ * ws: hs_window_nav_ws_bytes(...) bytes (hs_window_agg's + 16 bytes per row: the cells in sorted order at 8 bytes and two
+ * tables of frame ends; n_items does not enter).  flags: the device status word, raised by aggregate items only (may be
+ * null). */
+#define HS_WIN_LAG 8
+#define HS_WIN_LEAD 9
+#define HS_WIN_FIRST_VALUE 10
+#define HS_WIN_LAST_VALUE 11
+#define HS_WIN_NTILE 12
+size_t hs_window_nav_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t n_items);
+int hs_window_nav(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows,
+                  const int32_t* funcs, const int32_t* frames, const hs_col* values, const int64_t* params,
+                  const uint64_t* defaults, int32_t n_items, void* const* out, void* ws, uint32_t* flags);
 /* out[i] = values[s] for bounds[s] <= i < bounds[s+1], i in [0, n) (device arrays; bounds has n_seg + 1 entries,
  * bounds[0] = 0): the global block id of every partial row of a multi-rank partial aggregate. */
 int hs_expand_by_bounds(void* stream, const int64_t* bounds, const int64_t* values, int64_t n_seg, int64_t n, int64_t* out);

@@ -3043,24 +3043,79 @@ extern "C" size_t hs_window_agg_ws_bytes(int64_t nrows, int32_t n_keys, int32_t 
     return hs_window_ws_bytes(nrows, n_keys, max_key_words) + wagg_extra_bytes(nrows);
 }
 
+// What an item of funcs[i] <= HS_WIN_MAX needs beside win_refuse, under the caller's name: a frame for the aggregates, an
+// HS_I32 / HS_F32 argument for SUM / AVG / MIN / MAX.  Nothing is launched, no device pointer read.
+static int wagg_refuse_item(const char* name, int i, const int32_t* funcs, const int32_t* frames, const hs_col* values) {
+    if (funcs[i] < HS_WIN_COUNT) return HS_OK;  // ranking: neither a frame nor an argument
+    if (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > HS_WIN_FRAME_ROWS) {
+        hs_set_error("%s: item %d: frame %d is not one of HS_WIN_FRAME_*", name, i, frames ? frames[i] : -1);
+        return HS_E_ARG;
+    }
+    if (funcs[i] == HS_WIN_COUNT) return HS_OK;
+    if (!values || (values[i].kind != HS_I32 && values[i].kind != HS_F32)) {
+        hs_set_error("%s: item %d: the argument is a column of kind %d (a narrow or virtual column, or another "
+                     "type); it takes HS_I32 or HS_F32 cells", name, i, values ? values[i].kind : -1);
+        return HS_E_ARG;
+    }
+    return HS_OK;
+}
+
+// The launches of ranking and aggregate items behind win_front (hs_window_agg, and hs_window_nav for its older codes)
+struct WaggItems {
+    WinEmit E;
+    WaggArgs A;
+    int64_t tiles;
+};
+static WaggItems wagg_items(const WinFront& F, int64_t nrows, uint32_t* flags) {
+    WaggItems W;
+    std::memset(&W, 0, sizeof(W));
+    W.tiles = F.tiles;
+    W.E.heads = F.heads;
+    W.E.perm = F.perm;
+    W.E.carry = F.carry;
+    W.E.n = nrows;
+    W.A.heads = F.heads;
+    W.A.perm = F.perm;
+    W.A.carry = F.carry;
+    W.A.n = nrows;
+    W.A.sorted = (uint32_t*)F.rest;
+    W.A.tab_a = (uint64_t*)(F.rest + 4 * win_heads_bytes(nrows));
+    W.A.tab_c = (int32_t*)((uint8_t*)W.A.tab_a + rx_align((size_t)nrows * 8));
+    W.A.tiles = (WinA*)((uint8_t*)W.A.tab_c + rx_align((size_t)nrows * 4));
+    W.A.flags = flags;
+    return W;
+}
+static void wagg_item(hipStream_t stream, WaggItems& W, int32_t func, int32_t frame, const hs_col* value, void* out) {
+    const dim3 grid((unsigned)W.tiles), block(OB_THREADS);
+    if (func < HS_WIN_COUNT || (func == HS_WIN_COUNT && frame == HS_WIN_FRAME_ROWS)) {
+        W.E.out = (int32_t*)out;
+        W.E.func = func < HS_WIN_COUNT ? func : HS_WIN_ROW_NUMBER;  // the rows from the partition's first through this one
+        hipLaunchKernelGGL(k_win_emit, grid, block, 0, stream, W.E);
+        return;
+    }
+    WaggArgs& A = W.A;
+    A.func = func;
+    A.frame = frame;
+    A.out = (uint32_t*)out;
+    A.op = WA_NONE;
+    if (func != HS_WIN_COUNT) {
+        A.is_float = value->kind == HS_F32;
+        A.values = (const uint32_t*)value->data;
+        A.op = func == HS_WIN_MIN ? WA_MIN : func == HS_WIN_MAX ? WA_MAX : A.is_float ? WA_ADD_F : WA_ADD_I;
+        hipLaunchKernelGGL(k_wagg_reduce, grid, block, 0, stream, A);
+        hipLaunchKernelGGL(k_wagg_tiles, dim3(1), block, 0, stream, A.tiles, W.tiles, A.op);
+    }
+    hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, A);
+    hipLaunchKernelGGL(k_wagg_emit, grid, block, 0, stream, A);
+}
+
 extern "C" int hs_window_agg(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
                              int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values, int32_t n_items,
                              void* const* out, void* ws_, uint32_t* flags) {
     int rc = win_refuse("hs_window_agg", keys, n_part, n_keys, nrows, funcs, n_items, out, HS_WIN_MAX);
     if (rc != HS_OK) return rc;
-    for (int i = 0; i < n_items; ++i) {
-        if (funcs[i] < HS_WIN_COUNT) continue;  // ranking: neither a frame nor an argument
-        if (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > HS_WIN_FRAME_ROWS) {
-            hs_set_error("hs_window_agg: item %d: frame %d is not one of HS_WIN_FRAME_*", i, frames ? frames[i] : -1);
-            return HS_E_ARG;
-        }
-        if (funcs[i] == HS_WIN_COUNT) continue;
-        if (!values || (values[i].kind != HS_I32 && values[i].kind != HS_F32)) {
-            hs_set_error("hs_window_agg: item %d: the argument is a column of kind %d (a narrow or virtual column, or another "
-                         "type); it takes HS_I32 or HS_F32 cells", i, values ? values[i].kind : -1);
-            return HS_E_ARG;
-        }
-    }
+    for (int i = 0; i < n_items; ++i)
+        if ((rc = wagg_refuse_item("hs_window_agg", i, funcs, frames, values)) != HS_OK) return rc;
     if (nrows == 0) return HS_OK;
     for (int i = 0; i < n_items; ++i)
         if (funcs[i] > HS_WIN_COUNT && !values[i].data) {
@@ -3071,47 +3126,238 @@ extern "C" int hs_window_agg(void* stream_, const hs_col* keys, const int32_t* d
     WinFront F;
     rc = win_front(stream, "hs_window_agg", keys, descending, n_part, n_keys, nrows, out, n_items, ws_, F);
     if (rc != HS_OK) return rc;
-    WinEmit E;
-    std::memset(&E, 0, sizeof(E));
-    E.heads = F.heads;
-    E.perm = F.perm;
-    E.carry = F.carry;
-    E.n = nrows;
-    WaggArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.heads = F.heads;
-    A.perm = F.perm;
-    A.carry = F.carry;
-    A.n = nrows;
-    A.sorted = (uint32_t*)F.rest;
-    A.tab_a = (uint64_t*)(F.rest + 4 * win_heads_bytes(nrows));
-    A.tab_c = (int32_t*)((uint8_t*)A.tab_a + rx_align((size_t)nrows * 8));
-    A.tiles = (WinA*)((uint8_t*)A.tab_c + rx_align((size_t)nrows * 4));
-    A.flags = flags;
-    const dim3 grid((unsigned)F.tiles), block(OB_THREADS);
-    for (int i = 0; i < n_items; ++i) {
-        const int32_t func = funcs[i];
-        if (func < HS_WIN_COUNT || (func == HS_WIN_COUNT && frames[i] == HS_WIN_FRAME_ROWS)) {
-            E.out = (int32_t*)out[i];
-            E.func = func < HS_WIN_COUNT ? func : HS_WIN_ROW_NUMBER;  // the rows from the partition's first through this one
-            hipLaunchKernelGGL(k_win_emit, grid, block, 0, stream, E);
+    WaggItems W = wagg_items(F, nrows, flags);
+    for (int i = 0; i < n_items; ++i) wagg_item(stream, W, funcs[i], frames ? frames[i] : 0, values ? &values[i] : nullptr, out[i]);
+    RX_CHECK_LAUNCH("hs_window_agg (items)");
+    return HS_OK;
+}
+
+// =====================================================================================================
+// Window navigation over result rows (include/hipspark.h hs_window_nav).
+//
+// LAG / LEAD / FIRST_VALUE / LAST_VALUE copy the argument's cell of ANOTHER sorted position s of the row's partition,
+// NTILE numbers buckets from (row number, partition rows).  Everything rides on win_front; per sorted position j, P / Q the
+// partition / peer head at or before j (k_win_emit's rescan) and E the frame's end:
+//     LAG(k)       s = j - k, the default when s < P         LEAD(k)  s = j + k, the default when s > E(partition)
+//     FIRST_VALUE  s = P                                     LAST_VALUE  s = j (ROWS) | E(range) | E(partition)
+//     NTILE(n)     r = j - P + 1 of N = E(partition) - P + 1 rows
+// E comes from k_wagg_scan run without an argument (WA_NONE): it leaves tab_c[start] = E - P + 1 at start = P (PARTITION) or
+// Q (RANGE) - one pass per frame the call needs, not per item.  Per distinct argument k_wnav_gather leaves the cells in
+// sorted order (4 or 8 bytes; without keys position = row and the argument is read as it stands), per item k_wnav_emit
+// rescans (p, q), hands them over through LDS, reads cell s and scatters out[perm[j]].  Cells are copied as bits.
+// =====================================================================================================
+template <typename T>
+__global__ void __launch_bounds__(OB_THREADS) k_wnav_gather(const int64_t* perm, const T* values, T* sorted, int64_t n) {
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE;
+    int64_t row[WIN_PER];
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {  // consecutive lanes on consecutive positions; nothing past the rows
+        const int64_t j = tile0 + k * OB_THREADS + threadIdx.x;
+        row[k] = j < n ? perm[j] : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k)
+        if (row[k] >= 0) sorted[tile0 + k * OB_THREADS + threadIdx.x] = values[row[k]];
+}
+
+struct WnavArgs {
+    const uint8_t* heads;
+    const int64_t* perm;   // null: position = row
+    const int4* carry;     // per tile (k_win_tiles)
+    int64_t n;
+    const void* cells;     // the argument by sorted position (not read by NTILE)
+    const int32_t* tab_c;  // E - P + 1 by the frame's start (LEAD, NTILE: PARTITION; LAST_VALUE: its frame's; else not read)
+    void* out;             // one item per launch: input order
+    uint64_t dflt;         // LAG / LEAD: the default's bits
+    int64_t k;             // LAG / LEAD: the offset; NTILE: the buckets
+    int32_t func, frame;
+};
+static_assert(sizeof(WnavArgs) % 8 == 0, "WnavArgs");
+
+// NTILE: the bucket of row r (1-based) of N rows in n buckets, the first N mod n of them one row larger
+__device__ __forceinline__ uint32_t wnav_ntile(uint32_t r, uint32_t N, uint32_t n) {
+    const uint32_t s = N / n, m = N - s * n, big = m * (s + 1);  // big <= N: no overflow
+    if (r <= big) return (r - 1) / (s + 1) + 1;
+    return m + (r - 1 - big) / (s ? s : 1u) + 1;                 // s == 0: big == N, never here
+}
+
+template <typename T>
+__global__ void __launch_bounds__(OB_THREADS) k_wnav_emit(const WnavArgs A_kernarg) {
+    HS_KERNARG(WnavArgs, A);
+    __shared__ WinS s_wave[OB_WAVES];
+    __shared__ int32_t s_p[OB_TILE + OB_THREADS], s_q[OB_TILE + OB_THREADS];  // k_win_emit's hand-over
+    const int tid = threadIdx.x, func = A.func, frame = A.frame;
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
+    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);  // the buffer holds whole tiles
+    WinS acc{-1, -1, 0};
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) acc = win_join(acc, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
+    const int4 c = A.carry[blockIdx.x];
+    WinS total;
+    WinS run = win_join(WinS{c.x, c.y, c.z}, win_block_excl(acc, s_wave, total));
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        run = win_join(run, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
+        s_p[tid * (WIN_PER + 1) + k] = run.p;
+        s_q[tid * (WIN_PER + 1) + k] = run.q;
+    }
+    __syncthreads();
+    const T* cells = (const T*)A.cells;
+    T* out = (T*)A.out;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t j = tile0 + e;
+        if (j >= A.n) break;
+        const int64_t row = A.perm ? A.perm[j] : j;
+        const int64_t p = s_p[e + e / WIN_PER], q = s_q[e + e / WIN_PER];  // 0 <= p <= q <= j: position 0 is a head
+        if (func == HS_WIN_NTILE) {
+            out[row] = (T)wnav_ntile((uint32_t)(j - p + 1), (uint32_t)A.tab_c[p], (uint32_t)A.k);
             continue;
         }
-        A.func = func;
-        A.frame = frames[i];
-        A.out = (uint32_t*)out[i];
-        A.op = WA_NONE;
-        if (func != HS_WIN_COUNT) {
-            A.is_float = values[i].kind == HS_F32;
-            A.values = (const uint32_t*)values[i].data;
-            A.op = func == HS_WIN_MIN ? WA_MIN : func == HS_WIN_MAX ? WA_MAX : A.is_float ? WA_ADD_F : WA_ADD_I;
-            hipLaunchKernelGGL(k_wagg_reduce, grid, block, 0, stream, A);
-            hipLaunchKernelGGL(k_wagg_tiles, dim3(1), block, 0, stream, A.tiles, F.tiles, A.op);
+        int64_t s = j;  // 64 bits: k may be 2^31 - 1
+        bool valid = true;
+        if (func == HS_WIN_LAG) {
+            s = j - A.k;
+            valid = s >= p;
+        } else if (func == HS_WIN_LEAD) {
+            s = j + A.k;
+            valid = s <= p + A.tab_c[p] - 1;
+        } else if (func == HS_WIN_FIRST_VALUE) {
+            s = p;
+        } else if (frame != HS_WIN_FRAME_ROWS) {  // LAST_VALUE: the frame's last row
+            s = p + A.tab_c[frame == HS_WIN_FRAME_RANGE ? q : p] - 1;
         }
-        hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, A);
-        hipLaunchKernelGGL(k_wagg_emit, grid, block, 0, stream, A);
+        out[row] = valid ? cells[s] : (T)A.dflt;  // a valid s lies in the row's partition: inside [0, n)
     }
-    RX_CHECK_LAUNCH("hs_window_agg (items)");
+}
+
+static size_t wnav_extra_bytes(int64_t nrows) {  // the cells in sorted order at 8 bytes, two end tables
+    return 8 * win_heads_bytes(nrows) + 2 * rx_align((size_t)nrows * 4);
+}
+
+extern "C" size_t hs_window_nav_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t n_items) {
+    if (nrows < 0) return 0;
+    return hs_window_agg_ws_bytes(nrows, n_keys, max_key_words, n_items) + wnav_extra_bytes(nrows);
+}
+
+static bool wnav_takes_value(int32_t func) { return func >= HS_WIN_LAG && func <= HS_WIN_LAST_VALUE; }
+
+extern "C" int hs_window_nav(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
+                             int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values,
+                             const int64_t* params, const uint64_t* defaults, int32_t n_items, void* const* out, void* ws_,
+                             uint32_t* flags) {
+    int rc = win_refuse("hs_window_nav", keys, n_part, n_keys, nrows, funcs, n_items, out, HS_WIN_NTILE);
+    if (rc != HS_OK) return rc;
+    for (int i = 0; i < n_items; ++i) {
+        const int32_t func = funcs[i];
+        if (func <= HS_WIN_MAX) {
+            if ((rc = wagg_refuse_item("hs_window_nav", i, funcs, frames, values)) != HS_OK) return rc;
+            continue;
+        }
+        if ((func == HS_WIN_FIRST_VALUE || func == HS_WIN_LAST_VALUE) &&
+            (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > HS_WIN_FRAME_ROWS)) {
+            hs_set_error("hs_window_nav: item %d: frame %d is not one of HS_WIN_FRAME_*", i, frames ? frames[i] : -1);
+            return HS_E_ARG;
+        }
+        if (func == HS_WIN_LAG || func == HS_WIN_LEAD || func == HS_WIN_NTILE) {
+            const int64_t least = func == HS_WIN_NTILE ? 1 : 0;
+            const char* what = func == HS_WIN_NTILE ? "the bucket count n" : "the offset k";
+            if (!params) {
+                hs_set_error("hs_window_nav: item %d: %s is missing (params is null)", i, what);
+                return HS_E_ARG;
+            }
+            if (params[i] < least || params[i] >= (1ll << 31)) {
+                hs_set_error("hs_window_nav: item %d: %s is %lld; it lies in [%lld, 2^31)", i, what, (long long)params[i],
+                             (long long)least);
+                return HS_E_ARG;
+            }
+            if (func != HS_WIN_NTILE && !defaults) {
+                hs_set_error("hs_window_nav: item %d: LAG / LEAD need a default cell (defaults is null)", i);
+                return HS_E_ARG;
+            }
+        }
+        if (wnav_takes_value(func) &&
+            (!values || (values[i].kind != HS_I32 && values[i].kind != HS_F32 && values[i].kind != HS_I64))) {
+            hs_set_error("hs_window_nav: item %d: the argument is a column of kind %d (a narrow or virtual column, a STRING, or "
+                         "another type); it takes HS_I32, HS_F32 or HS_I64 cells", i, values ? values[i].kind : -1);
+            return HS_E_ARG;
+        }
+    }
+    if (nrows == 0) return HS_OK;
+    for (int i = 0; i < n_items; ++i)
+        if (((funcs[i] > HS_WIN_COUNT && funcs[i] <= HS_WIN_MAX) || wnav_takes_value(funcs[i])) && !values[i].data) {
+            hs_set_error("hs_window_nav: item %d: the argument column is null", i);
+            return HS_E_ARG;
+        }
+    hipStream_t stream = (hipStream_t)stream_;
+    WinFront F;
+    rc = win_front(stream, "hs_window_nav", keys, descending, n_part, n_keys, nrows, out, n_items, ws_, F);
+    if (rc != HS_OK) return rc;
+    WaggItems W = wagg_items(F, nrows, flags);
+    const dim3 grid((unsigned)F.tiles), block(OB_THREADS);
+    uint8_t* nav = F.rest + wagg_extra_bytes(nrows);
+    void* sorted = nav;
+    int32_t* ends[2] = {(int32_t*)(nav + 8 * win_heads_bytes(nrows)),                                    // PARTITION
+                        (int32_t*)(nav + 8 * win_heads_bytes(nrows) + rx_align((size_t)nrows * 4))};     // RANGE
+    // the end tables, once per frame some item needs: k_wagg_scan without an argument (its tab_a cells are not used)
+    static_assert(HS_WIN_FRAME_PARTITION == 0 && HS_WIN_FRAME_RANGE == 1, "the end tables are indexed by frame");
+    bool needed[2] = {false, false};
+    for (int i = 0; i < n_items; ++i) {
+        if (funcs[i] == HS_WIN_LEAD || funcs[i] == HS_WIN_NTILE) needed[HS_WIN_FRAME_PARTITION] = true;
+        if (funcs[i] == HS_WIN_LAST_VALUE && frames[i] != HS_WIN_FRAME_ROWS) needed[frames[i]] = true;
+    }
+    for (int fr = HS_WIN_FRAME_PARTITION; fr <= HS_WIN_FRAME_RANGE; ++fr) {
+        if (!needed[fr]) continue;
+        WaggArgs S = W.A;
+        S.op = WA_NONE;
+        S.frame = fr;
+        S.tab_c = ends[fr];
+        hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, S);
+    }
+    WnavArgs N;
+    std::memset(&N, 0, sizeof(N));
+    N.heads = F.heads;
+    N.perm = F.perm;
+    N.carry = F.carry;
+    N.n = nrows;
+    uint32_t done = 0;
+    for (int i = 0; i < n_items; ++i) {
+        if (done & (1u << i)) continue;
+        const int32_t func = funcs[i];
+        if (func <= HS_WIN_MAX) {
+            wagg_item(stream, W, func, frames ? frames[i] : 0, values ? &values[i] : nullptr, out[i]);
+            continue;
+        }
+        const bool wide = wnav_takes_value(func) && values[i].kind == HS_I64;
+        if (wnav_takes_value(func)) {  // the argument in sorted order, once for every item that reads the same cells
+            N.cells = values[i].data;
+            if (F.perm) {
+                N.cells = sorted;
+                if (wide)
+                    hipLaunchKernelGGL(k_wnav_gather<uint64_t>, grid, block, 0, stream, F.perm, (const uint64_t*)values[i].data,
+                                       (uint64_t*)sorted, nrows);
+                else
+                    hipLaunchKernelGGL(k_wnav_gather<uint32_t>, grid, block, 0, stream, F.perm, (const uint32_t*)values[i].data,
+                                       (uint32_t*)sorted, nrows);
+            }
+        }
+        for (int t = i; t < n_items; ++t) {  // this item, then the later ones over the same argument
+            if (t > i && (!wnav_takes_value(func) || !wnav_takes_value(funcs[t]) || (done & (1u << t)) ||
+                          values[t].data != values[i].data || (values[t].kind == HS_I64) != wide))
+                continue;
+            done |= 1u << t;
+            N.func = funcs[t];
+            N.frame = frames ? frames[t] : 0;
+            N.k = params ? params[t] : 0;
+            N.dflt = defaults ? defaults[t] : 0;
+            N.tab_c = ends[N.func == HS_WIN_LAST_VALUE && N.frame == HS_WIN_FRAME_RANGE ? 1 : 0];
+            N.out = out[t];
+            if (wide) hipLaunchKernelGGL(k_wnav_emit<uint64_t>, grid, block, 0, stream, N);
+            else hipLaunchKernelGGL(k_wnav_emit<uint32_t>, grid, block, 0, stream, N);
+        }
+    }
+    RX_CHECK_LAUNCH("hs_window_nav (items)");
     return HS_OK;
 }
 

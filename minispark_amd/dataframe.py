@@ -96,11 +96,13 @@ class DataFrame:
         return self._append(_t.SortTask, keys=pairs)
 
     def window(self, *items: Any, select_order: list[str] | None = None) -> "DataFrame":
-        """Window items over the result rows (DESIGN.md 4.4f, 4.4g): every item - ``F.row_number()``, ``F.rank()`` or
+        """Window items over the result rows (DESIGN.md 4.4f - 4.4h): every item - ``F.row_number()``, ``F.rank()`` or
         ``F.dense_rank()`` with ``.over(partition_by=[...], order_by=[...])``, or an aggregate ``F.sum(c)``, ``F.avg(c)``,
-        ``F.min(c)``, ``F.max(c)``, ``F.count()`` with ``.over(partition_by=[...], order_by=[...], rows=False)``, and an
-        optional ``.alias(name)`` - adds one column behind the existing ones (INTEGER for ranks and counts, the argument's
-        type for SUM / MIN / MAX, FLOAT for AVG), in the order given; no row moves.  ``select_order`` (the SQL front end)
+        ``F.min(c)``, ``F.max(c)``, ``F.count()`` with ``.over(partition_by=[...], order_by=[...], rows=False)``, or a
+        navigation item ``F.lag(c, k, default)``, ``F.lead(c, k, default)``, ``F.first_value(c)``, ``F.last_value(c)``,
+        ``F.ntile(n)`` with ``.over(...)``, and an optional ``.alias(name)`` - adds one column behind the existing ones
+        (INTEGER for ranks, counts and NTILE, the argument's type for SUM / MIN / MAX and the value functions, FLOAT for
+        AVG), in the order given; no row moves.  ``select_order`` (the SQL front end)
         names all columns in the order wanted instead.  It comes before ``qualify`` / ``distinct`` / ``order_by`` /
         ``limit``, which may name the new columns."""
         if not items:

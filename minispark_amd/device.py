@@ -1704,19 +1704,26 @@ class Device:
         return perm[:out_count.value], out_count.value
 
     WINDOW_KINDS = {"row_number": hs.WIN_ROW_NUMBER, "rank": hs.WIN_RANK, "dense_rank": hs.WIN_DENSE_RANK,
-                    "count": hs.WIN_COUNT, "sum": hs.WIN_SUM, "avg": hs.WIN_AVG, "min": hs.WIN_MIN, "max": hs.WIN_MAX}
+                    "count": hs.WIN_COUNT, "sum": hs.WIN_SUM, "avg": hs.WIN_AVG, "min": hs.WIN_MIN, "max": hs.WIN_MAX,
+                    "lag": hs.WIN_LAG, "lead": hs.WIN_LEAD, "first_value": hs.WIN_FIRST_VALUE,
+                    "last_value": hs.WIN_LAST_VALUE, "ntile": hs.WIN_NTILE}
     WINDOW_FRAMES = {None: hs.WIN_FRAME_PARTITION, "partition": hs.WIN_FRAME_PARTITION, "range": hs.WIN_FRAME_RANGE,
                      "rows": hs.WIN_FRAME_ROWS}
 
     def window(self, batch: DBatch, part_idx: Sequence[int], order_keys: Sequence[tuple[int, bool]], funcs: Sequence[str],
-               frames: Sequence[str | None] | None = None, value_idx: Sequence[int | None] | None = None) -> list[DCol]:
+               frames: Sequence[str | None] | None = None, value_idx: Sequence[int | None] | None = None,
+               params: Sequence[tuple[int, int] | None] | None = None) -> list[DCol]:
         """The window items ``funcs`` over the rows of ``batch`` -> one column per item, in INPUT order: no row moves.
         ``part_idx`` = the PARTITION BY columns, ``order_keys`` = (column, ascending) pairs of the window's ORDER BY; all
         items share the one sort.  ROW_NUMBER / RANK / DENSE_RANK give INTEGER columns; when every item is one of them the
         call is hs_window's, as before aggregates existed.  An aggregate item ("count", "sum", "avg", "min", "max") has its
         frame in ``frames`` ("partition" | "range" | "rows") and its argument's column index in ``value_idx`` (INTEGER or
         FLOAT; None for "count"), and the call is hs_window_agg's: FLOAT where the value is (AVG, SUM / MIN / MAX of a
-        FLOAT column).  An overflow it meets is raised in the status word, where the result's write finds it.  Equality
+        FLOAT column).  An overflow it meets is raised in the status word, where the result's write finds it.  A navigation
+        item ("lag", "lead", "first_value", "last_value", "ntile") makes the call hs_window_nav's, which takes every item:
+        its argument (INTEGER, FLOAT or TIMESTAMP; None for "ntile") is in ``value_idx``, the frame of "first_value" /
+        "last_value" in ``frames``, and ``params`` holds (k, the default cell's bits) for "lag" / "lead" and (n, 0) for
+        "ntile"; the column has the argument's kind, INTEGER for "ntile".  Equality
         and order are ``distinct``'s and ``order_by``'s.  A dictionary-coded column goes as its code byte where it only
         partitions (one code, one string) or where the dictionary is sorted, decoded otherwise, as in ``order_by``.  The
         call learns sizes on the host between its steps, so a run that contains it is not replayable."""
@@ -1742,16 +1749,26 @@ class Device:
         codes = [self.WINDOW_KINDS[f] for f in funcs]
         frames = list(frames) if frames is not None else [None] * len(funcs)
         value_idx = list(value_idx) if value_idx is not None else [None] * len(funcs)
+        params = list(params) if params is not None else [None] * len(funcs)
         values: list[DCol | None] = []
         for code, f, which in zip(codes, funcs, value_idx):
             col = None
-            if code > hs.WIN_COUNT:
+            if hs.WIN_COUNT < code <= hs.WIN_MAX:
                 col = batch.cols[which] if which is not None else None
                 if col is None or col.virtual or col.kind not in (hs.I32, hs.F32):
                     raise DeviceError(f"the window aggregate {f} takes a stored INTEGER or FLOAT column")
+            elif hs.WIN_LAG <= code <= hs.WIN_LAST_VALUE:
+                col = batch.cols[which] if which is not None else None
+                if col is None or col.virtual or col.dict is not None or col.kind not in (hs.I32, hs.F32, hs.I64):
+                    raise DeviceError(f"the window function {f} takes a stored INTEGER, FLOAT or TIMESTAMP column")
             values.append(col)
-        floats = [code == hs.WIN_AVG or (col is not None and col.kind == hs.F32) for code, col in zip(codes, values)]
-        outs = [self.empty(max(n, 1), torch.float32 if is_float else torch.int32) for is_float in floats]
+        navigates = any(code >= hs.WIN_LAG for code in codes)
+        for code, f, param in zip(codes, funcs, params):
+            if code in (hs.WIN_LAG, hs.WIN_LEAD, hs.WIN_NTILE) and param is None:
+                raise DeviceError(f"the window function {f} needs its (k or n, default bits) in params")
+        out_kinds = [hs.F32 if code == hs.WIN_AVG else col.kind if col is not None else hs.I32 for code, col in zip(codes, values)]
+        dtypes = {hs.I32: torch.int32, hs.F32: torch.float32, hs.I64: torch.int64}
+        outs = [self.empty(max(n, 1), dtypes[kind]) for kind in out_kinds]
         if n:
             arr = (hs.hs_col * max(n_keys, 1))(*[c.as_hs() for c in cols])
             desc = (C.c_int32 * max(n_keys, 1))(*([0] * len(part_idx) + [0 if ascending else 1 for _, ascending in order_keys]))
@@ -1764,10 +1781,19 @@ class Device:
             else:
                 frame_codes = (C.c_int32 * len(funcs))(*[self.WINDOW_FRAMES[f] for f in frames])
                 vals = (hs.hs_col * len(funcs))(*[c.as_hs() if c is not None else hs.hs_col() for c in values])
-                ws = self.workspace(self._raw_lib.hs_window_agg_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(funcs)))
-                hs.check(self._raw_lib.hs_window_agg(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, frame_codes, vals,
-                                                     len(funcs), ptrs, ws.data_ptr(), self.flags.data_ptr()), "hs_window_agg")
-        return [DCol(hs.F32 if is_float else hs.I32, out[:n], n) for is_float, out in zip(floats, outs)]
+                if not navigates:
+                    ws = self.workspace(self._raw_lib.hs_window_agg_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(funcs)))
+                    hs.check(self._raw_lib.hs_window_agg(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, frame_codes,
+                                                         vals, len(funcs), ptrs, ws.data_ptr(), self.flags.data_ptr()),
+                             "hs_window_agg")
+                else:
+                    steps = (C.c_int64 * len(funcs))(*[int(p[0]) if p is not None else 0 for p in params])
+                    cells = (C.c_uint64 * len(funcs))(*[int(p[1]) if p is not None else 0 for p in params])
+                    ws = self.workspace(self._raw_lib.hs_window_nav_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(funcs)))
+                    hs.check(self._raw_lib.hs_window_nav(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, frame_codes,
+                                                         vals, steps, cells, len(funcs), ptrs, ws.data_ptr(),
+                                                         self.flags.data_ptr()), "hs_window_nav")
+        return [DCol(kind, out[:n], n) for kind, out in zip(out_kinds, outs)]
 
     def mark_first(self, batch: DBatch, key_indices: Sequence[int], sel: torch.Tensor | None = None, n_sel: int = 0,
                    mode: int = 0) -> DCol:

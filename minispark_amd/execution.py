@@ -771,7 +771,7 @@ class HipExecutionEngine(ExecutionEngine):
         return self.dev.gather_batch(batch, perm, count)
 
     def _window_rows(self, batch: Any, sort: Any) -> Any:
-        """Window items, the first step of a windowed SortTask (DESIGN.md 4.4f, 4.4g): the rounded result rows gain one
+        """Window items, the first step of a windowed SortTask (DESIGN.md 4.4f - 4.4h): the rounded result rows gain one
         column per item - items with one (partition, order) spec share one sort and one launch sequence
         (Device.window) - the column handles are placed in the task's output order (no row is copied), and QUALIFY
         filters the rows through the WHERE machinery.  Keys are found by POSITION in the task's input schema."""
@@ -790,9 +790,11 @@ class HipExecutionEngine(ExecutionEngine):
             part = [in_names.index(col.name) for col in items[0].partition_by]
             order = [(in_names.index(col.name), ascending) for col, ascending in items[0].order_by]
             extra = ()
-            if any(item.kind in item.AGGREGATES for item in items):  # the frames, and the arguments by position too
+            if any(item.kind not in item.RANKING for item in items):  # the frames, and the arguments by position too
                 extra = ([item.frame for item in items],
                          [None if item.arg is None else in_names.index(item.arg.name) for item in items])
+            if any(item.kind in item.NAVIGATION for item in items):  # (k, the default as a cell's bits) or (n, 0)
+                extra = (*extra, [self._window_param(item, in_schema) for item in items])
             for item, col in zip(items, self.dev.window(batch, part, order, [item.kind for item in items], *extra)):
                 by_name[item.name] = col
         out_schema = list(sort.inferred_schema)
@@ -800,6 +802,12 @@ class HipExecutionEngine(ExecutionEngine):
         if sort.qualify is not None:
             batch = self.dev.resolve(self._materialise(batch, [sort.qualify]))
         return batch
+
+    @staticmethod
+    def _window_param(item: Any, in_schema: Schema) -> tuple[int, int] | None:
+        if item.kind in ("lag", "lead"):
+            return item.offset, item.default_bits(item.arg.infer_type(in_schema))
+        return (item.buckets, 0) if item.kind == "ntile" else None
 
     def _consume(self, batch: Any, consumers: Sequence[Any]) -> Any:
         """Run a stage's consumer tasks (filters, projections, aggregates) over one batch."""

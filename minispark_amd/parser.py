@@ -27,15 +27,19 @@ A hand-written backtracking recursive-descent parser for the same language:
   ``SELECT DISTINCT`` (the keyword, then whitespace) becomes ``distinct()`` between the final select and ``order_by``:
   rows equal in every result column are removed, the first of them stays, and ORDER BY / LIMIT apply to what is left.
   The form without the keyword is tried first, so a text that was accepted before builds the tree it built then.
-* window ranking and window aggregates, tried only after every older form failed, so accepted texts keep their trees:
+* window ranking, aggregates and navigation, tried only after every older form failed, so accepted texts keep their trees:
       select item:  ROW_NUMBER() | RANK() | DENSE_RANK()  OVER ( [PARTITION BY name {, name}]
                                                                  [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] )  [AS alias]
                     SUM(name) | AVG(name) | MIN(name) | MAX(name) | COUNT()  OVER ( [PARTITION BY ...] [ORDER BY ...] [frame] )
                     frame:  ROWS | RANGE  [BETWEEN]  UNBOUNDED PRECEDING  [AND CURRENT ROW]         [AS alias]
+                    LAG(name, k, default) | LEAD(name, k, default) | NTILE(n)  OVER ( [PARTITION BY ...] [ORDER BY ...] )
+                    FIRST_VALUE(name) | LAST_VALUE(name)  OVER ( [PARTITION BY ...] [ORDER BY ...] [frame] )   [AS alias]
+                    (k, n: integer literals; default: an integer, a decimal - either may be negative -
+                    or a quoted ISO timestamp, of the column's type; k and default are mandatory: there is no NULL)
       clause:       ... [GROUP BY ... [HAVING ...]] [QUALIFY cond] [ORDER BY ...] [LIMIT n] ;
   The items are set aside from the select list (before GROUP BY's stray-column check), the rest of the query is built as
   ever, and ``window(...)`` / ``qualify(cond)`` follow the final select; names inside OVER are names of the RESULT, as for
-  ORDER BY.  ``ROW_NUMBER()`` without OVER and ``RANK(x)`` stay the unsupported functions they were.
+  ORDER BY.  ``ROW_NUMBER()`` without OVER, ``RANK(x)`` and ``LAG(x)`` without OVER stay the unsupported functions they were.
   ``CASE`` (searched form only, ELSE mandatory, INTEGER / FLOAT branches, several WHEN arms nest to the right) stands
   wherever an expression may: a select item, an aggregate's argument, either side of a comparison, inside arithmetic or
   another CASE.  A column called ``CASE`` still parses as a column (no old text holds ``CASE`` whitespace ``WHEN``).
@@ -97,6 +101,7 @@ _COMPARATORS: list[tuple[str, Callable[[Any, Any], Any]]] = [
 ]
 _JOIN_KINDS = [("JOIN",), ("LEFT", "JOIN"), ("RIGHT", "JOIN"), ("INNER", "JOIN"), ("FULL", "JOIN")]
 _AGGREGATES = ("COUNT", "SUM", "AVG", "MIN", "MAX")
+_NAVIGATION = ("LAG", "LEAD", "FIRST_VALUE", "LAST_VALUE", "NTILE")
 
 
 class _Parser:
@@ -305,16 +310,50 @@ class _Parser:
         return self.first_of(self.star, self.window_item, self.aggregate_call, self.expr_aliased)
 
     def window_item(self) -> WindowItem:
-        """ROW_NUMBER() | RANK() | DENSE_RANK() | SUM(name) | AVG(name) | MIN(name) | MAX(name) | COUNT(), whitespace,
+        """ROW_NUMBER() | RANK() | DENSE_RANK() | SUM(name) | AVG(name) | MIN(name) | MAX(name) | COUNT() |
+        LAG(name, k, default) | LEAD(name, k, default) | FIRST_VALUE(name) | LAST_VALUE(name) | NTILE(n), whitespace,
         OVER ( [PARTITION BY names] [ORDER BY keys] [frame] ) [AS alias].  Anything else - no OVER, an argument to a
         ranking function - is no window item and goes on to the function call it was before."""
-        name = self.first_of(*[(lambda n=n: self.lit(n)) for n in ("ROW_NUMBER", "RANK", "DENSE_RANK", *_AGGREGATES)])
-        ranking = name not in _AGGREGATES
+        name = self.first_of(*[(lambda n=n: self.lit(n)) for n in ("ROW_NUMBER", "RANK", "DENSE_RANK", *_AGGREGATES,
+                                                                  *_NAVIGATION)])
+        ranking = name not in _AGGREGATES and name not in _NAVIGATION
         self.ows()
         self.lit("(")
         self.ows()
         arg = None
-        if not ranking and name != "COUNT":
+        extra: list[Any] = []  # LAG / LEAD: the literals behind the column; NTILE: its literal
+
+        def literal() -> Any:
+            """an integer, a decimal (either may be negative) or a quoted string"""
+            has_number, text = self.attempt(lambda: self.rx(_NUMBER))
+            if has_number:
+                return float(text) if "." in text else int(text)
+            return self.string_literal()
+
+        if name == "NTILE":
+            extra = [literal()]
+            self.ows()
+            self.lit(")")
+        elif name in ("LAG", "LEAD"):
+            def plain() -> Col:
+                col = self.column_name()
+                self.ows()
+                if not self.text.startswith((",", ")"), self.pos):
+                    self.fail()
+                return col
+
+            has_name, arg = self.attempt(plain)
+            if not has_name:
+                self.expr()
+            extra = self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), literal())[3])
+            self.ows()
+            self.lit(")")
+            if not has_name:  # as for an aggregate: a window item only if OVER follows
+                self.ws()
+                self.lit("OVER")
+                raise SemanticError(f"{name}(...) OVER takes a plain column of the result, not an expression: alias the "
+                                    f"expression in the select list (SELECT a + 1 AS x, {name}(x, 1, 0) OVER (...))")
+        elif not ranking and name != "COUNT":
             has_name, arg = self.attempt(lambda: (self.column_name(), self.ows(), self.lit(")"))[0])
             if not has_name:  # an expression: a window item only if OVER follows, and then one that says what to do
                 self.expr()
@@ -369,6 +408,19 @@ class _Parser:
                 raise ValueError(f"{name}() takes no frame clause ({unit} ...): a rank is a property of the row's place in its "
                                  "partition, not of a frame")
             item = WindowItem(name.lower()).over(**keys)
+        elif name in _NAVIGATION:
+            if name in ("LAG", "LEAD"):
+                if len(extra) > 2:
+                    raise ValueError(f"{name}({arg}, k, default) takes a column and two literals, not {len(extra)} behind it")
+                item = WindowItem(name.lower(), arg, *extra)  # fewer than two: "k and the default are mandatory"
+            elif name == "NTILE":
+                item = F.ntile(extra[0])
+            else:
+                item = WindowItem(name.lower(), arg)
+            if has_frame and name in ("LAG", "LEAD", "NTILE"):
+                raise ValueError(f"{name}() takes no frame clause ({unit} ...): it is a property of the row's place in its "
+                                 "partition, not of a frame")
+            item = item.over(**keys, rows=has_frame and unit == "ROWS")
         else:
             agg = F.count() if name == "COUNT" else {"SUM": F.sum, "AVG": F.avg, "MIN": F.min, "MAX": F.max}[name](arg)
             # RANGE is the default frame: through the last peer, which without ORDER BY is the whole partition

@@ -164,26 +164,64 @@ class WindowItem:
     column named after its function; an aggregate item a column of ``out_type`` named as the aggregate is (``sum_v``,
     ``count``) - unless ``alias`` says otherwise.  ``frame`` (aggregates): "partition" - every row of the partition, no
     ORDER BY; "range" - through the row's last peer, the default with ORDER BY; "rows" - through the row itself
-    (``rows=True``).  Not an expression: it cannot be selected, compared or nested."""
+    (``rows=True``).  Not an expression: it cannot be selected, compared or nested.
+
+    Navigation items: ``F.lag(col, offset, default) | F.lead(col, offset, default)`` - the value ``offset``
+    rows before / after the row in its partition's order, ``default`` where the partition has no such row (both mandatory:
+    there is no NULL); ``F.first_value(col) | F.last_value(col)`` - the value of the first / last row of the frame, the
+    aggregates' frames; ``F.ntile(n)`` - the row's bucket of ``n``.  The value items copy cells of an INTEGER, FLOAT or
+    TIMESTAMP column and have its type; NTILE is INTEGER.  Named ``lag_v``, ``lead_v``, ``first_value_v``, ``last_value_v``,
+    ``ntile``."""
 
     RANKING = ("row_number", "rank", "dense_rank")
     AGGREGATES = ("sum", "avg", "min", "max", "count")
-    KINDS = RANKING + AGGREGATES
+    NAVIGATION = ("lag", "lead", "first_value", "last_value", "ntile")
+    KINDS = RANKING + AGGREGATES + NAVIGATION
 
-    def __init__(self, kind: str, arg: Col | None = None) -> None:
+    def __init__(self, kind: str, arg: Col | None = None, offset: Any = None, default: Any = None,
+                 buckets: Any = None) -> None:
         if kind not in self.KINDS:
             raise ValueError(f"window function {kind!r}: one of {self.KINDS}")
-        if (arg is not None) != (kind in self.AGGREGATES and kind != "count"):
+        if kind in self.NAVIGATION:
+            self._check_navigation(kind, arg, offset, default, buckets)
+        elif (arg is not None) != (kind in self.AGGREGATES and kind != "count"):
             raise ValueError(f"window function {kind!r}: SUM / AVG / MIN / MAX take one column, every other function none")
         if arg is not None and type(arg).__name__ not in {"Col", "SchemaCol"}:
             raise ValueError(f"a window aggregate takes plain columns of the result, not the expression {arg}: "
                              "select(... .alias()) first")
         self.kind, self.arg = kind, arg
+        self.offset, self.default, self.buckets = offset, default, buckets
         self.name = kind if arg is None else f"{kind}_{arg.name}"
         self.frame: str | None = None
         self.partition_by: list[Col] = []
         self.order_by: list[tuple[Col, bool]] = []
         self.is_over = False
+
+    @staticmethod
+    def _check_navigation(kind: str, arg: Any, offset: Any, default: Any, buckets: Any) -> None:
+        whole = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+        head = kind.upper()
+        if kind == "ntile":
+            if arg is not None or offset is not None or default is not None:
+                raise ValueError("NTILE(n) takes the number of buckets and nothing else")
+            if not whole(buckets) or not 1 <= buckets < 1 << 31:
+                raise ValueError(f"NTILE(n): n is an integer literal with 1 <= n < 2^31, not {buckets!r}")
+            return
+        if arg is None or buckets is not None:
+            raise ValueError(f"window function {kind!r} takes one column of the result")
+        if kind in ("first_value", "last_value"):
+            if offset is not None or default is not None:
+                raise ValueError(f"{head}(column) takes one column and nothing else")
+            return
+        shown = getattr(arg, "name", arg)
+        if offset is None or default is None:
+            raise ValueError(f"{head}: the offset k and the default are mandatory - there is no NULL to stand in for the row "
+                             f"that does not exist, as CASE's ELSE is mandatory: write {head}({shown}, 1, 0)")
+        if not whole(offset) or not 0 <= offset < 1 << 31:
+            raise ValueError(f"{head}({shown}, k, default): k is an integer literal with 0 <= k < 2^31, not {offset!r}")
+        if isinstance(default, bool) or not isinstance(default, (int, float, str)):
+            raise ValueError(f"{head}({shown}, k, default): the default is a literal of the column's type (an integer, a "
+                             f"number or a quoted ISO timestamp), not {default!r}")
 
     def over(self, partition_by: Any = (), order_by: Any = (), rows: bool = False) -> "WindowItem":
         single = lambda v: [v] if isinstance(v, (Col, SortKey)) else list(v)  # noqa: E731
@@ -199,6 +237,10 @@ class WindowItem:
             if self.kind != "row_number" and not self.order_by:
                 raise ValueError(f"{self.kind.upper()}() needs an ORDER BY inside OVER: without one every row of a partition is "
                                  "a peer of every other (ROW_NUMBER() may omit it)")
+        elif self.kind in ("lag", "lead", "ntile"):
+            if rows:
+                raise ValueError(f"{self.kind.upper()}() takes no frame clause: it is a property of the row's place in its "
+                                 "partition, not of a frame")
         else:
             self.frame = "rows" if rows else "range" if self.order_by else "partition"
         self.is_over = True
@@ -215,14 +257,59 @@ class WindowItem:
     def out_type(self, schema: Schema) -> ColumnType:
         """The type of the column the item adds, given the schema of the rows it reads.  An aggregate's argument is an
         INTEGER or FLOAT column of them: ``TypeError`` that names it otherwise (a name the rows do not have: the ``ValueError``
-        a key raises)."""
+        a key raises).  A navigation item's argument may be a TIMESTAMP column too, and the default of LAG / LEAD is a
+        literal of the argument's type (``default_bits``)."""
         if self.arg is None:
             return ColumnType.INTEGER
         arg_type = self.arg.infer_type(schema)  # ValueError('Column "x" not found in schema ...')
+        if self.kind in self.NAVIGATION:
+            if arg_type not in (ColumnType.INTEGER, ColumnType.FLOAT, ColumnType.TIMESTAMP):
+                raise TypeError(f'{self.kind.upper()}({self.arg.name}) OVER: column "{self.arg.name}" is {arg_type}; a window '
+                                "navigation function takes an INTEGER, FLOAT or TIMESTAMP column")
+            if self.kind in ("lag", "lead"):
+                self.default_bits(arg_type)
+            return arg_type
         if arg_type not in (ColumnType.INTEGER, ColumnType.FLOAT):
             raise TypeError(f'{self.kind.upper()}({self.arg.name}) OVER: column "{self.arg.name}" is {arg_type}; a window '
                             "aggregate takes an INTEGER or FLOAT column")
         return ColumnType.FLOAT if self.kind == "avg" else arg_type
+
+    def default_bits(self, arg_type: ColumnType) -> int:
+        """LAG / LEAD's default as the bits of a cell of ``arg_type``: an integer within i32 for INTEGER, a number rounded to
+        a finite f32 for FLOAT, a quoted ISO timestamp for TIMESTAMP (microseconds, 8 bytes).  ``TypeError`` for a default
+        of another type, ``OverflowError`` / ``ValueError`` for one the cell does not hold."""
+        import struct  # noqa: PLC0415
+
+        d, what = self.default, f'{self.kind.upper()}({self.arg.name}, {self.offset}, {self._shown_default()})'
+        whole = isinstance(d, int) and not isinstance(d, bool)
+        if arg_type == ColumnType.INTEGER:
+            if not whole:
+                raise TypeError(f'{what}: column "{self.arg.name}" is INTEGER, its default is an integer literal')
+            if not -(1 << 31) <= d < 1 << 31:
+                raise OverflowError(f"{what}: the default does not fit the 32 bits of an INTEGER cell")
+            return d & 0xFFFFFFFF
+        if arg_type == ColumnType.FLOAT:
+            if not whole and not isinstance(d, float):
+                raise TypeError(f'{what}: column "{self.arg.name}" is FLOAT, its default is a number literal')
+            try:
+                bits = struct.unpack("<I", struct.pack("<f", float(d)))[0]  # OverflowError beyond f32 (RNE inside)
+            except OverflowError:
+                raise OverflowError(f"{what}: the default does not fit a FLOAT cell (f32)") from None
+            if bits & 0x7F800000 == 0x7F800000:
+                raise ValueError(f"{what}: the default of a FLOAT column is a finite number")
+            return bits
+        if not isinstance(d, str):
+            raise TypeError(f'{what}: column "{self.arg.name}" is TIMESTAMP, its default is a quoted ISO timestamp')
+        from .utils import _timestamp_us  # noqa: PLC0415
+
+        try:
+            us = _timestamp_us(d)
+        except ValueError:
+            raise TypeError(f"{what}: the default of a TIMESTAMP column is a quoted ISO timestamp ('1970-01-01')") from None
+        return us & 0xFFFFFFFFFFFFFFFF
+
+    def _shown_default(self) -> str:
+        return f"'{self.default}'" if isinstance(self.default, str) else str(self.default)
 
     def __str__(self) -> str:
         parts = []
@@ -232,7 +319,12 @@ class WindowItem:
             parts.append("ORDER BY " + ", ".join(f"{c} {'ASC' if asc else 'DESC'}" for c, asc in self.order_by))
         if self.frame in ("rows", "range"):
             parts.append(f"{self.frame.upper()} UNBOUNDED PRECEDING")
-        return f"{self.kind.upper()}({'' if self.arg is None else self.arg}) OVER ({' '.join(parts)}) AS {self.name}"
+        inner = "" if self.arg is None else str(self.arg)
+        if self.kind in ("lag", "lead"):
+            inner = f"{self.arg}, {self.offset}, {self._shown_default()}"
+        elif self.kind == "ntile":
+            inner = str(self.buckets)
+        return f"{self.kind.upper()}({inner}) OVER ({' '.join(parts)}) AS {self.name}"
 
     __repr__ = __str__
 
@@ -696,6 +788,27 @@ class Functions:
     @staticmethod
     def dense_rank() -> WindowItem:
         return WindowItem("dense_rank")
+
+    # window navigation: DESIGN.md 4.4h
+    @staticmethod
+    def lag(col: Col, offset: Any = None, default: Any = None) -> WindowItem:
+        return WindowItem("lag", col, offset=offset, default=default)
+
+    @staticmethod
+    def lead(col: Col, offset: Any = None, default: Any = None) -> WindowItem:
+        return WindowItem("lead", col, offset=offset, default=default)
+
+    @staticmethod
+    def first_value(col: Col) -> WindowItem:
+        return WindowItem("first_value", col)
+
+    @staticmethod
+    def last_value(col: Col) -> WindowItem:
+        return WindowItem("last_value", col)
+
+    @staticmethod
+    def ntile(n: int) -> WindowItem:
+        return WindowItem("ntile", buckets=n)
 
     @staticmethod
     def when(condition: Any, value: Any) -> CaseBuilder:

@@ -312,7 +312,7 @@ class SortTask(ConsumerTask):
     keys: list[tuple[Col, bool]] = field(default_factory=list)
     limit: int | None = None
     distinct: bool = False
-    # window items (DESIGN.md 4.4f, 4.4g): ``windows`` = sql.WindowItem list, each one column added to the input's
+    # window items (DESIGN.md 4.4f - 4.4h): ``windows`` = sql.WindowItem list, each one column added to the input's
     # columns; ``qualify`` = a condition over all of them (QUALIFY), applied right after; ``select_order`` = the names of
     # all output columns in the order wanted (None: the input's columns, then the windows).  They run BEFORE distinct,
     # keys and limit, which may name the window columns.

@@ -12,11 +12,17 @@ windowed call there is: the aggregate adds a 4-byte gather of its argument, its 
   (f) SUM(FLOAT) over the whole partition
   (g) SUM(FLOAT), ROWS frame
   (h) ROW_NUMBER + RANK + DENSE_RANK + SUM(INTEGER) + COUNT in one call, default frame
+Window navigation (hs_window_nav), over case (a)'s keys, each timed next to hs_window ROW_NUMBER on the same keys like (e) - (h)
+(a value item adds one gather of its argument into sorted order and one scatter; LEAD / NTILE / LAST_VALUE one end-table pass):
+  (i) LAG(INTEGER, 1)
+  (j) LEAD(TIMESTAMP, 1): 8-byte cells
+  (k) LAST_VALUE(FLOAT), default frame (RANGE: the last peer)
+  (l) ROW_NUMBER + SUM(INTEGER) + LAG(INTEGER, 1) + NTILE(4) in one call, default frame
 Both calls read a few words back between their steps, so their times include those host round trips.  --case x --reps 3
 under a kernel trace gives the per-kernel split.  --lib PATH times another build of the library (the parent commit's, for
-"ranking did not move"); a library without hs_window_agg runs (a) - (d) only.
-Usage: python tools/bench_window.py [--rows 64M] [--partitions 1M] [--reps 20] [--case abcdefgh] [--lib libhipspark.so]
-                                    [--out profiles/r20_window_agg.txt]"""
+"ranking did not move"); a library without hs_window_agg runs (a) - (d) only, one without hs_window_nav (a) - (h).
+Usage: python tools/bench_window.py [--rows 64M] [--partitions 1M] [--reps 20] [--case abcdefghijkl] [--lib libhipspark.so]
+                                    [--out profiles/r21_window_nav.txt]"""
 from __future__ import annotations
 
 import argparse
@@ -54,7 +60,7 @@ def main() -> None:
     ap.add_argument("--rows", type=float, default=64 * 2**20)
     ap.add_argument("--partitions", type=float, default=2**20)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--case", default="abcdefgh")
+    ap.add_argument("--case", default="abcdefghijkl")
     ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -67,7 +73,8 @@ def main() -> None:
     else:
         lib = hs.load_library()
     has_agg = hasattr(lib, "hs_window_agg")
-    a.case = "".join(tag for tag in a.case if tag in "abcd" or has_agg)
+    has_nav = hasattr(lib, "hs_window_nav")
+    a.case = "".join(tag for tag in a.case if tag in "abcd" or (has_agg and tag in "efgh") or has_nav)
     g = torch.Generator(device="cuda")
     g.manual_seed(15)
     part = torch.randint(0, d, (n,), device="cuda", generator=g, dtype=torch.int64)
@@ -77,7 +84,8 @@ def main() -> None:
     stream = torch.cuda.current_stream().cuda_stream
     perm = torch.empty(n, dtype=torch.int64, device="cuda")
     outs = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(5 if has_agg else 3)]
-    ws_bytes = lib.hs_window_agg_ws_bytes(n, 2, 3, 5) if has_agg else lib.hs_window_ws_bytes(n, 2, 3)
+    ws_bytes = (lib.hs_window_nav_ws_bytes(n, 2, 3, 5) if has_nav else lib.hs_window_agg_ws_bytes(n, 2, 3, 5) if has_agg
+                else lib.hs_window_ws_bytes(n, 2, 3))
     ws = torch.empty(int(ws_bytes) + 256, dtype=torch.uint8, device="cuda")
     count = C.c_int64(0)
     col = lambda kind, t: hs.hs_col(kind, -1, t.data_ptr(), None, None)  # noqa: E731
@@ -133,15 +141,44 @@ def main() -> None:
                                                                   (hs.WIN_DENSE_RANK, 0, None), (hs.WIN_SUM, hs.WIN_FRAME_RANGE, vi),
                                                                   (hs.WIN_COUNT, hs.WIN_FRAME_RANGE, None)])}
 
+    def window_nav(cols, n_part, items):
+        """items = [(function, frame, argument column or None, k or n)]; the default cell is 0"""
+        arr = (hs.hs_col * len(cols))(*cols)
+        asc = (C.c_int32 * len(cols))(*[0] * len(cols))
+        kinds = (C.c_int32 * len(items))(*[it[0] for it in items])
+        frames = (C.c_int32 * len(items))(*[it[1] for it in items])
+        values = (hs.hs_col * len(items))(*[it[2] if it[2] is not None else hs.hs_col() for it in items])
+        params = (C.c_int64 * len(items))(*[it[3] for it in items])
+        defaults = (C.c_uint64 * len(items))()
+        ptrs = (C.c_void_p * len(items))(*[(wide_out if it[2] is not None and it[2].kind == hs.I64 else o).data_ptr()
+                                           for it, o in zip(items, outs)])
+
+        def run():
+            hs.check(lib.hs_window_nav(stream, arr, asc, n_part, len(cols), n, kinds, frames, values, params, defaults, len(items),
+                                       ptrs, ws.data_ptr(), flags.data_ptr()), "hs_window_nav")
+        return run
+
+    nav_cases = {}
+    if has_nav:
+        wide_out = torch.empty(n, dtype=torch.int64, device="cuda")
+        vt = col(hs.I64, stamps)
+        nav_cases = {"i": ("LAG(INTEGER, 1)", [(hs.WIN_LAG, 0, vi, 1)]),
+                     "j": ("LEAD(TIMESTAMP, 1)", [(hs.WIN_LEAD, 0, vt, 1)]),
+                     "k": ("LAST_VALUE(FLOAT), default frame", [(hs.WIN_LAST_VALUE, hs.WIN_FRAME_RANGE, vf, 0)]),
+                     "l": ("ROW_NUMBER + SUM(INTEGER) + LAG + NTILE(4)", [(hs.WIN_ROW_NUMBER, 0, None, 0),
+                                                                          (hs.WIN_SUM, hs.WIN_FRAME_RANGE, vi, 0),
+                                                                          (hs.WIN_LAG, 0, vi, 1), (hs.WIN_NTILE, 0, None, 4)])}
+
     lines = [f"tools/bench_window.py --rows {n} --partitions {d} --reps {a.reps}   [{torch.cuda.get_device_name(0)}, host "
              f"{socket.gethostname()}, torch {torch.__version__}]",
              "events on the launch stream, the two calls alternating; median (min - max) ms; ratio = hs_window / hs_order_by"]
     for tag in a.case:
-        if tag in agg_cases:
-            what, items = agg_cases[tag]
+        if tag in agg_cases or tag in nav_cases:
+            what, items = agg_cases[tag] if tag in agg_cases else nav_cases[tag]
+            entry, call = ("hs_window_agg", window_agg) if tag in agg_cases else ("hs_window_nav", window_nav)
             _, cols, n_part, _ = cases["a"]
-            (mw, lw, hw), (ms, lo, hi) = timed_pair(window_agg(cols, n_part, items), window(cols, n_part, every[:1]), a.reps)
-            lines.append(f"({tag}) hs_window_agg {what:33s} {mw:9.3f} ms ({lw:.3f} - {hw:.3f})   {n / mw / 1e6:8.2f} G rows/s")
+            (mw, lw, hw), (ms, lo, hi) = timed_pair(call(cols, n_part, items), window(cols, n_part, every[:1]), a.reps)
+            lines.append(f"({tag}) {entry} {what:33s} {mw:9.3f} ms ({lw:.3f} - {hw:.3f})   {n / mw / 1e6:8.2f} G rows/s")
             lines.append(f"({tag}) hs_window    {'the same keys, ROW_NUMBER':34s} {ms:9.3f} ms ({lo:.3f} - {hi:.3f})   "
                          f"{n / ms / 1e6:8.2f} G rows/s   ratio {mw / ms:.2f}   + {mw - ms:.3f} ms")
             continue
@@ -185,6 +222,17 @@ def main() -> None:
         want = prefix[end] - prefix[start] + v[start]
         ok = bool((outs[0][perm].to(torch.int64) == want).all()) and int(flags[0].item()) == 0
         lines.append(f"check (e): along the sorted rows the sum is the partition's prefix sum at the row's last peer: {ok}")
+    if "i" in a.case:  # checked with torch over the sort's own row list: the left neighbour's cell inside a partition
+        what, items = nav_cases["i"]
+        _, cols, n_part, _ = cases["a"]
+        window_nav(cols, n_part, items)()
+        order_by(cols)()
+        torch.cuda.synchronize()
+        p, v = part32[perm], ints[perm]
+        want = torch.zeros_like(v)
+        want[1:] = torch.where(p[1:] == p[:-1], v[:-1], torch.zeros_like(v[1:]))
+        lines.append(f"check (i): along the sorted rows LAG is the left neighbour's cell, 0 at a partition's first row: "
+                     f"{bool((outs[0][perm] == want).all())}")
     text = "\n".join(lines)
     print(text)
     if a.out:
