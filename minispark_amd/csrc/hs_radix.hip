@@ -2450,24 +2450,32 @@ extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, 
 }
 
 // =====================================================================================================
-// Window ranking over result rows (include/hipspark.h hs_window; the reference has no window functions).
+// Window functions over result rows (include/hipspark.h hs_window, hs_window_agg, hs_window_nav; the reference has no
+// window functions).  What the three entries share stands here; ranking, aggregates and navigation follow.
 //
 // ob_sort orders the rows by (partition columns, order keys): a partition is a run of sorted positions, peers are
 // neighbours, and the sort being stable the rows of a group of peers stand in input order.  k_win_heads writes two bits
 // per SORTED position - the row differs from its left neighbour in any key byte (peer head) / in the first `part_bytes`
-// bytes of the key (partition head) - with k_distinct_heads' neighbour shuffle.  Per position j the answers are
-//     row_number = j - P + 1      P: the last partition head at or before j
-//     rank       = Q - P + 1      Q: the last peer head at or before j
-//     dense_rank = D              D: the peer heads in [P, j]
-// P and Q are max-scans of head positions, D a segmented sum that restarts at every partition head:
-//     (p, q, d) (+) (p', q', d') = (max(p, p'), max(q, q'), p' >= 0 ? d' : d + d')      identity (-1, -1, 0)
-// associative, NOT commutative: every level below joins with the earlier positions on the LEFT.  Three passes over
-// OB_TILE-row tiles, a lane holding 8 consecutive positions (one 8-byte load of head bytes): k_win_reduce folds a tile
-// into one summary, k_win_tiles (one workgroup, rounds of 2048 summaries, the carry of the rounds before on the left)
-// turns the summaries into each tile's carry, k_win_emit scans the tile again behind its carry, hands the results over
-// through LDS so that the row list is read coalesced, and scatters ONE function's values to the rows: out[perm[j]] - a
-// launch per requested function, the scan being cheap next to the scatter.
-// A tile without a head has the summary (-1, -1, 0) and passes its carry on as it is.  Positions are int32: rows < 2^31.
+// bytes of the key (partition head) - with k_distinct_heads' neighbour shuffle.  Everything else is a SEGMENTED SCAN over the positions: a
+// summary (p, q, x) of a range of positions - p / q the last partition / peer head in it (-1: none), x a third field
+// that restarts at every partition head - joins with the summary of the positions behind it as
+//     (p, q, x) (+) (p', q', x') = (max(p, p'), max(q, q'), p' >= 0 ? x' : x op x')
+// associative, NOT commutative: every level joins with the earlier positions on the LEFT.  Two summaries: WinS, x = d,
+// the peer heads since the partition head (op: +, identity 0), and WinA, x = a, a 64-bit fold of an argument (op chosen
+// at run time).  Each has an "ops" type with none() (the identity), join(earlier, later) and shfl_up(v, d); the rest is
+// written once over it, on OB_TILE-row tiles, a lane holding WIN_PER = 8 consecutive positions (one 8-byte load of head
+// bytes, WinLane):
+//   win_fold_lane    a lane's 8 positions joined left to right;
+//   win_block_excl   the exclusive scan of one summary per thread over the workgroup: the __shfl_up ladder inside a wave,
+//                    one LDS hop across the four waves, joined in order;
+//   k_win_tiles      one workgroup, rounds of OB_TILE tile summaries, the carry of the rounds before on the left: every
+//                    tile's summary becomes the tile's carry - the join of all tiles before it - in place;
+//   win_rescan_lane  a tile scanned again behind its carry: put(k, run) gets the inclusive summary at each of the lane's
+//                    positions that is a row.  The kernels that scatter to rows hand what they need over through LDS
+//                    - a lane writes its 8 positions at win_put_at, consecutive lanes read consecutive positions at
+//                    win_get_at, one pad word per lane segment (k_scan_down's layout) - so that the row list is read
+//                    coalesced.
+// A tile without a head has the summary none() and passes its carry on as it is.  Positions are int32: rows < 2^31.
 // =====================================================================================================
 constexpr int WIN_PER = OB_TILE / OB_THREADS;  // consecutive sorted positions of a lane in the scan passes
 static_assert(WIN_PER == 8, "a lane's head bytes are one 8-byte load");
@@ -2528,115 +2536,210 @@ __global__ void __launch_bounds__(OB_THREADS) k_win_heads(const WinHeads A_kerna
 struct WinS {
     int32_t p, q, d;  // last partition head, last peer head (-1: none in the range), peer heads since the partition head
 };
-__device__ __forceinline__ WinS win_join(const WinS a, const WinS b) {  // a: the EARLIER positions
-    return WinS{a.p > b.p ? a.p : b.p, a.q > b.q ? a.q : b.q, b.p >= 0 ? b.d : a.d + b.d};
+// a WinS as the tile records hold it: 16 bytes, one vector load or store (in LDS a WinS stays 12 bytes)
+struct alignas(16) WinRec {
+    int32_t p, q, d, zero;
+    WinRec() = default;
+    __device__ WinRec(const WinS s) : p(s.p), q(s.q), d(s.d), zero(0) {}
+    __device__ operator WinS() const { return WinS{p, q, d}; }
+};
+static_assert(sizeof(WinRec) == 16, "WinRec");
+struct WinSOps {
+    using S = WinS;
+    using Rec = WinRec;
+    __device__ __forceinline__ WinS none() const { return WinS{-1, -1, 0}; }
+    __device__ __forceinline__ WinS join(const WinS a, const WinS b) const {  // a: the EARLIER positions
+        return WinS{a.p > b.p ? a.p : b.p, a.q > b.q ? a.q : b.q, b.p >= 0 ? b.d : a.d + b.d};
+    }
+    __device__ __forceinline__ WinS shfl_up(const WinS v, int d) const {
+        return WinS{__shfl_up(v.p, d, HS_WAVE), __shfl_up(v.q, d, HS_WAVE), __shfl_up(v.d, d, HS_WAVE)};
+    }
+    // the third field of ONE position: it counts itself where it is a peer head (the cell is not looked at)
+    __device__ __forceinline__ int32_t third(uint32_t head, uint64_t) const { return (int32_t)(head & 1u); }
+};
+
+enum { WA_NONE = 0, WA_ADD_I = 1, WA_ADD_F = 2, WA_MIN = 3, WA_MAX = 4 };
+
+struct WinA {
+    int32_t p, q;  // as in WinS
+    uint64_t a;    // the fold since the last partition head
+};
+static_assert(sizeof(WinA) == 16, "WinA");
+
+__device__ __forceinline__ uint64_t wa_identity(int op) { return op == WA_MIN ? ~0ull : 0ull; }
+__device__ __forceinline__ uint64_t wa_op(int op, uint64_t a, uint64_t b) {  // a: the EARLIER positions
+    switch (op) {
+        case WA_ADD_I: return a + b;
+        case WA_ADD_F: return hs_d2u(hs_u2d(a) + hs_u2d(b));
+        case WA_MIN: return a < b ? a : b;
+        case WA_MAX: return a > b ? a : b;
+        default: return 0;
+    }
 }
-__device__ __forceinline__ WinS win_of(uint32_t head, int32_t j) {
-    return WinS{(head & 2u) ? j : -1, (head & 1u) ? j : -1, (int32_t)(head & 1u)};
+struct WinAOps {
+    using S = WinA;
+    using Rec = WinA;
+    int32_t op;
+    __device__ __forceinline__ WinA none() const { return WinA{-1, -1, wa_identity(op)}; }
+    __device__ __forceinline__ WinA join(const WinA a, const WinA b) const {  // a: the EARLIER positions
+        return WinA{a.p > b.p ? a.p : b.p, a.q > b.q ? a.q : b.q, b.p >= 0 ? b.a : wa_op(op, a.a, b.a)};
+    }
+    __device__ __forceinline__ WinA shfl_up(const WinA v, int d) const {
+        return WinA{__shfl_up(v.p, d, HS_WAVE), __shfl_up(v.q, d, HS_WAVE),
+                    (uint64_t)__shfl_up((unsigned long long)v.a, d, HS_WAVE)};  // two 32-bit shuffles
+    }
+    __device__ __forceinline__ uint64_t third(uint32_t, uint64_t x) const { return x; }  // the position's lifted cell
+};
+
+// the summary of ONE position j with head bits `head`
+template <typename S, typename T>
+__device__ __forceinline__ S win_of(uint32_t head, int32_t j, T third) {
+    return S{(head & 2u) ? j : -1, (head & 1u) ? j : -1, third};
 }
-// head bits of position j0 + k, k-th byte of the lane's load; nothing past the rows
-__device__ __forceinline__ uint32_t win_head(uint64_t bytes, int k, int64_t j0, int64_t n) {
-    return j0 + k < n ? (uint32_t)(bytes >> (8 * k)) & 3u : 0u;
+
+// A lane's WIN_PER consecutive positions of its workgroup's tile and their head bytes
+struct WinLane {
+    int64_t j0, n;
+    uint64_t bytes;
+    // head bits of position j0 + k, k-th byte of the lane's load; nothing past the rows
+    __device__ __forceinline__ uint32_t head(int k) const { return j0 + k < n ? (uint32_t)(bytes >> (8 * k)) & 3u : 0u; }
+};
+__device__ __forceinline__ WinLane win_lane(const uint8_t* heads, int64_t n) {
+    const int64_t j0 = (int64_t)blockIdx.x * OB_TILE + (int64_t)threadIdx.x * WIN_PER;
+    return WinLane{j0, n, *(const uint64_t*)(heads + j0)};  // the buffer holds whole tiles
 }
-__device__ __forceinline__ WinS win_shfl_up(const WinS v, int d) {
-    return WinS{__shfl_up(v.p, d, HS_WAVE), __shfl_up(v.q, d, HS_WAVE), __shfl_up(v.d, d, HS_WAVE)};
+struct WinNoCells {  // WinS looks at no cell
+    __device__ __forceinline__ uint64_t operator()(int) const { return 0; }
+};
+// the lane's positions joined left to right; x(k): the lifted cell of position j0 + k
+template <typename O, typename X>
+__device__ __forceinline__ typename O::S win_fold_lane(const O o, const WinLane& L, X x) {
+    typename O::S acc = o.none();
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k)
+        acc = o.join(acc, win_of<typename O::S>(L.head(k), (int32_t)(L.j0 + k), o.third(L.head(k), x(k))));
+    return acc;
 }
-// exclusive scan of one WinS per thread over the workgroup, in thread order; `total` = the join of all (every thread).
+
+// exclusive scan of one summary per thread over the workgroup, in thread order; `total` = the join of all (every thread).
 // Wave shuffles, then one LDS hop across the four waves.  The caller puts a barrier before s_wave is used again.
-__device__ __forceinline__ WinS win_block_excl(const WinS v, WinS* s_wave, WinS& total) {
+template <typename O>
+__device__ __forceinline__ typename O::S win_block_excl(const O o, const typename O::S v, typename O::S* s_wave,
+                                                        typename O::S& total) {
+    typedef typename O::S S;
     const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE;
-    WinS incl = v;
+    S incl = v;
 #pragma unroll
     for (int d = 1; d < HS_WAVE; d <<= 1) {
-        const WinS t = win_shfl_up(incl, d);
-        if (lane >= d) incl = win_join(t, incl);
+        const S t = o.shfl_up(incl, d);
+        if (lane >= d) incl = o.join(t, incl);
     }
     if (lane == HS_WAVE - 1) s_wave[w] = incl;
-    WinS excl = win_shfl_up(incl, 1);
-    if (lane == 0) excl = WinS{-1, -1, 0};
+    S excl = o.shfl_up(incl, 1);
+    if (lane == 0) excl = o.none();
     __syncthreads();
-    WinS base{-1, -1, 0};
+    S base = o.none();
     total = base;
 #pragma unroll
     for (int k = 0; k < OB_WAVES; ++k) {
         if (k == w) base = total;
-        total = win_join(total, s_wave[k]);
+        total = o.join(total, s_wave[k]);
     }
-    return win_join(base, excl);
-}
-
-__global__ void __launch_bounds__(OB_THREADS) k_win_reduce(const uint8_t* heads, int64_t n, int4* sums) {
-    __shared__ WinS s_wave[OB_WAVES];
-    const int64_t j0 = (int64_t)blockIdx.x * OB_TILE + (int64_t)threadIdx.x * WIN_PER;
-    const uint64_t bytes = *(const uint64_t*)(heads + j0);  // the buffer holds whole tiles
-    WinS acc{-1, -1, 0};
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) acc = win_join(acc, win_of(win_head(bytes, k, j0, n), (int32_t)(j0 + k)));
-    WinS total;
-    win_block_excl(acc, s_wave, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = make_int4(total.p, total.q, total.d, 0);
+    return o.join(base, excl);
 }
 
 // one workgroup: sums[t] = the join of the summaries of tiles 0 .. t - 1 (tile t's carry), in place
-__global__ void __launch_bounds__(OB_THREADS) k_win_tiles(int4* sums, int64_t ntiles) {
-    __shared__ WinS s_wave[OB_WAVES];
-    WinS carry{-1, -1, 0};  // the rounds before this one: the same in every thread
+template <typename O>
+__global__ void __launch_bounds__(OB_THREADS) k_win_tiles(typename O::Rec* sums, int64_t ntiles, const O o) {
+    typedef typename O::S S;
+    __shared__ S s_wave[OB_WAVES];
+    S carry = o.none();  // the rounds before this one: the same in every thread
     for (int64_t t0 = 0; t0 < ntiles; t0 += OB_TILE) {
         const int64_t mine = t0 + (int64_t)threadIdx.x * WIN_PER;
-        WinS v[WIN_PER], acc{-1, -1, 0};
+        S v[WIN_PER], acc = o.none();
 #pragma unroll
         for (int k = 0; k < WIN_PER; ++k) {
-            v[k] = WinS{-1, -1, 0};
-            if (mine + k < ntiles) {
-                const int4 s = sums[mine + k];
-                v[k] = WinS{s.x, s.y, s.z};
-            }
-            acc = win_join(acc, v[k]);
+            v[k] = o.none();
+            if (mine + k < ntiles) v[k] = sums[mine + k];
+            acc = o.join(acc, v[k]);
         }
-        WinS total;
-        WinS run = win_join(carry, win_block_excl(acc, s_wave, total));
+        S total;
+        S run = o.join(carry, win_block_excl(o, acc, s_wave, total));
 #pragma unroll
         for (int k = 0; k < WIN_PER; ++k) {
-            if (mine + k < ntiles) sums[mine + k] = make_int4(run.p, run.q, run.d, 0);
-            run = win_join(run, v[k]);
+            if (mine + k < ntiles) sums[mine + k] = run;
+            run = o.join(run, v[k]);
         }
-        carry = win_join(carry, total);
+        carry = o.join(carry, total);
         __syncthreads();
     }
 }
 
-struct WinEmit {
-    const uint8_t* heads;
-    const int64_t* perm;  // null: position = row
-    const int4* carry;    // per tile (k_win_tiles)
+// a tile scanned again behind its carry: put(k, run), run the join of everything through position j0 + k, for the lane's
+// positions that are rows (the step's join stays inside the test: joined ahead of it, eight summaries are live at once)
+template <typename O, typename X, typename Put>
+__device__ __forceinline__ void win_rescan_lane(const O o, const WinLane& L, X x, const typename O::S carry,
+                                                typename O::S* s_wave, Put put) {
+    typename O::S total;
+    typename O::S run = o.join(carry, win_block_excl(o, win_fold_lane(o, L, x), s_wave, total));
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k)
+        if (L.j0 + k < L.n) {
+            run = o.join(run, win_of<typename O::S>(L.head(k), (int32_t)(L.j0 + k), o.third(L.head(k), x(k))));
+            put(k, run);
+        }
+}
+// ... of (p, q, d), what the kernels that scatter to rows start with
+template <typename Put>
+__device__ __forceinline__ void win_rescan(const uint8_t* heads, const WinS carry, int64_t n, WinS* s_wave, Put put) {
+    win_rescan_lane(WinSOps{}, win_lane(heads, n), WinNoCells{}, carry, s_wave, put);
+}
+// the LDS hand-over: where lane `tid` puts its k-th position, where element e = k * OB_THREADS + tid of the tile is read
+__device__ __forceinline__ int win_put_at(int tid, int k) { return tid * (WIN_PER + 1) + k; }
+__device__ __forceinline__ int win_get_at(int e) { return e + e / WIN_PER; }
+
+// what every kernel behind the front half starts from
+struct WinTile {
+    const uint8_t* heads;  // by sorted position, whole tiles
+    const int64_t* perm;   // the sorted rows (null: position = row)
+    const WinRec* carry;   // per tile: (p, q, d) of the tiles before (k_win_tiles)
     int64_t n;
-    int32_t* out;         // one function per launch: three scattered columns at once fall out of the last-level cache
-    int32_t func, pad;    // that one column's partial lines still merge in (profiles/r15_window.txt)
+};
+
+// -----------------------------------------------------------------------------------------------------
+// Ranking (hs_window).  Per position j the answers are
+//     row_number = j - P + 1      P: the last partition head at or before j
+//     rank       = Q - P + 1      Q: the last peer head at or before j
+//     dense_rank = D              D: the peer heads in [P, j]
+// P and Q are max-scans of head positions, D the segmented sum: WinS.  k_win_reduce folds a tile into one summary,
+// k_win_tiles turns the summaries into carries, k_win_emit scans the tile again and scatters ONE function's values to the
+// rows: out[perm[j]] - a launch per requested function, the scan being cheap next to the scatter.
+// -----------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(OB_THREADS) k_win_reduce(const uint8_t* heads, int64_t n, WinRec* sums) {
+    __shared__ WinS s_wave[OB_WAVES];
+    const WinSOps o{};
+    WinS total;
+    win_block_excl(o, win_fold_lane(o, win_lane(heads, n), WinNoCells{}), s_wave, total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+struct WinEmit : WinTile {
+    int32_t* out;       // one function per launch: three scattered columns at once fall out of the last-level cache
+    int32_t func, pad;  // that one column's partial lines still merge in (profiles/r15_window.txt)
 };
 static_assert(sizeof(WinEmit) % 8 == 0, "WinEmit");
 
 __global__ void __launch_bounds__(OB_THREADS) k_win_emit(const WinEmit A_kernarg) {
     HS_KERNARG(WinEmit, A);
     __shared__ WinS s_wave[OB_WAVES];
-    // a lane scans 8 consecutive positions, the row list is read with consecutive lanes on consecutive positions: the
-    // results cross over in LDS, one pad word per lane segment (k_scan_down's layout)
     __shared__ int32_t s_p[OB_TILE + OB_THREADS], s_q[OB_TILE + OB_THREADS], s_d[OB_TILE + OB_THREADS];
     const int tid = threadIdx.x;
-    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
-    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);
-    WinS acc{-1, -1, 0};
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) acc = win_join(acc, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
-    const int4 c = A.carry[blockIdx.x];
-    WinS total;
-    WinS run = win_join(WinS{c.x, c.y, c.z}, win_block_excl(acc, s_wave, total));
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        run = win_join(run, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
-        s_p[tid * (WIN_PER + 1) + k] = run.p;
-        s_q[tid * (WIN_PER + 1) + k] = run.q;
-        s_d[tid * (WIN_PER + 1) + k] = run.d;
-    }
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE;
+    win_rescan(A.heads, A.carry[blockIdx.x], A.n, s_wave, [&](int k, const WinS run) {
+        s_p[win_put_at(tid, k)] = run.p;
+        s_q[win_put_at(tid, k)] = run.q;
+        s_d[win_put_at(tid, k)] = run.d;
+    });
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < WIN_PER; ++k) {
@@ -2644,22 +2747,338 @@ __global__ void __launch_bounds__(OB_THREADS) k_win_emit(const WinEmit A_kernarg
         const int64_t j = tile0 + e;
         if (j >= A.n) break;
         const int64_t row = A.perm ? A.perm[j] : j;
-        const int32_t p = s_p[e + e / WIN_PER], q = s_q[e + e / WIN_PER], d = s_d[e + e / WIN_PER];
+        const int32_t p = s_p[win_get_at(e)], q = s_q[win_get_at(e)], d = s_d[win_get_at(e)];
         A.out[row] = A.func == HS_WIN_ROW_NUMBER ? (int32_t)j - p + 1 : A.func == HS_WIN_RANK ? q - p + 1 : d;
     }
 }
 
-static size_t win_heads_bytes(int64_t nrows) { return rx_align((size_t)((nrows + OB_TILE - 1) / OB_TILE) * OB_TILE); }
-
-extern "C" size_t hs_window_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words) {
-    if (nrows < 0) return 0;
-    // the sort's workspace, then the head bytes of whole tiles and a summary per tile
-    return hs_order_by_ws_bytes(nrows, n_keys, max_key_words) + win_heads_bytes(nrows) +
-           rx_align((size_t)((nrows + OB_TILE - 1) / OB_TILE + 1) * sizeof(int4));
+// -----------------------------------------------------------------------------------------------------
+// Aggregates (hs_window_agg).  COUNT / SUM / AVG / MIN / MAX: per sorted position j the value is the fold
+// of the argument over [P(j), E(j)], E the frame's end: j itself (ROWS), the last peer of j (RANGE), the partition's last
+// row (PARTITION).  The fold is WinA's third field - the restart is a select, so a NaN or an infinity never leaves its
+// partition - with a 64-bit accumulator: an i64 sum, an f64 sum, or for MIN / MAX the sort's order-preserving word of the
+// cell (ob_f32_word: -0.0 = 0.0, NaN after +inf).  Earlier positions stay on the LEFT at every level, so the association
+// of an f64 sum is fixed by (rows, tile geometry): the same bits from run to run, not those of the left-to-right fold.
+// Per item:
+//   k_wagg_reduce  gathers the argument through the row list (coalesced over positions, across to the lanes' 8
+//                  consecutive positions through LDS), leaves the cells in SORTED order for the next pass and folds the
+//                  tile into one summary;
+//   k_win_tiles    over WinA: every tile's carry;
+//   k_wagg_scan    scans the tile again behind both carries and, at every frame end, stores the running value and the
+//                  frame's row count into two tables indexed by the frame's START position (j, Q or P): one vector
+//                  store per frame, no atomics;
+//   k_wagg_emit    every position reads the tables at its own j / Q / P - all rows of a frame the same cell - finishes
+//                  the value (AVG divides, SUM / AVG round to the cell type and raise the overflow flags) and scatters
+//                  out[perm[j]], one launch per item like k_win_emit.
+// COUNT has no argument: it skips the first two kernels; COUNT under ROWS is ROW_NUMBER and takes k_win_emit.
+// -----------------------------------------------------------------------------------------------------
+// a stored cell as an accumulator
+__device__ __forceinline__ uint64_t wa_lift(int op, int is_float, uint32_t v) {
+    switch (op) {
+        case WA_ADD_I: return (uint64_t)(int64_t)(int32_t)v;
+        case WA_ADD_F: return hs_d2u((double)__uint_as_float(v));
+        case WA_MIN:
+        case WA_MAX: return is_float ? ob_f32_word(v) : v ^ 0x80000000u;
+        default: return 0;
+    }
+}
+// x[k] = the lifted cell(k) of the lane's k-th position; the identity past the rows, where no cell is looked at
+template <typename Cell>
+__device__ __forceinline__ void wa_lift_lane(int op, int is_float, const WinLane& L, Cell cell, uint64_t (&x)[WIN_PER]) {
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) x[k] = L.j0 + k < L.n ? wa_lift(op, is_float, cell(k)) : wa_identity(op);
 }
 
-// What both entries (hs_window, hs_window_agg) refuse before anything is launched or any device pointer is read, under
-// the caller's name.  HS_OK: go on (nrows == 0 included - the caller returns then).
+struct WaggArgs : WinTile {
+    const uint32_t* values;  // the argument's cells, input order (not read when op == WA_NONE)
+    uint32_t* sorted;        // the cells by sorted position, whole tiles
+    WinA* tiles;             // per tile: k_wagg_reduce's summary, then k_win_tiles' carry
+    uint64_t* tab_a;         // by the START position of a frame: its fold ...
+    int32_t* tab_c;          // ... and its rows
+    uint32_t* out;           // one item per launch: input order
+    uint32_t* flags;         // may be null
+    int32_t op, is_float, frame, func;
+};
+static_assert(sizeof(WaggArgs) % 8 == 0, "WaggArgs");
+
+__global__ void __launch_bounds__(OB_THREADS) k_wagg_reduce(const WaggArgs A_kernarg) {
+    HS_KERNARG(WaggArgs, A);
+    __shared__ WinA s_wave[OB_WAVES];
+    __shared__ uint32_t s_v[OB_TILE + OB_THREADS];
+    const int tid = threadIdx.x;
+    const WinAOps o{A.op};
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t j = tile0 + e;
+        uint32_t v = 0;
+        if (j < A.n) {
+            v = A.values[A.perm ? A.perm[j] : j];
+            A.sorted[j] = v;
+        }
+        s_v[win_get_at(e)] = v;
+    }
+    __syncthreads();
+    const WinLane L = win_lane(A.heads, A.n);
+    uint64_t x[WIN_PER];
+    wa_lift_lane(o.op, A.is_float, L, [&](int k) { return s_v[win_put_at(tid, k)]; }, x);
+    WinA total;
+    win_block_excl(o, win_fold_lane(o, L, [&](int k) { return x[k]; }), s_wave, total);
+    if (tid == 0) A.tiles[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_wagg_scan(const WaggArgs A_kernarg) {
+    HS_KERNARG(WaggArgs, A);
+    __shared__ WinA s_wave[OB_WAVES];
+    const WinAOps o{A.op};
+    const int frame = A.frame;
+    const WinLane L = win_lane(A.heads, A.n);
+    // the head byte behind the lane's eight: written where it is a row (the byte after the last tile is never read)
+    const uint32_t next = L.j0 + WIN_PER < A.n ? A.heads[L.j0 + WIN_PER] : 0u;
+    uint32_t cell[WIN_PER] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (o.op != WA_NONE) {  // `sorted` holds whole tiles: cells past the rows are read and not used
+        const uint4 lo = *(const uint4*)(A.sorted + L.j0), hi = *(const uint4*)(A.sorted + L.j0 + 4);
+        cell[0] = lo.x, cell[1] = lo.y, cell[2] = lo.z, cell[3] = lo.w;
+        cell[4] = hi.x, cell[5] = hi.y, cell[6] = hi.z, cell[7] = hi.w;
+    }
+    uint64_t x[WIN_PER];
+    wa_lift_lane(o.op, A.is_float, L, [&](int k) { return cell[k]; }, x);
+    const WinS c = A.carry[blockIdx.x];
+    const uint64_t ca = o.op != WA_NONE ? A.tiles[blockIdx.x].a : 0ull;
+    const uint32_t end_bit = frame == HS_WIN_FRAME_RANGE ? 1u : 2u;
+    win_rescan_lane(o, L, [&](int k) { return x[k]; }, WinA{c.p, c.q, ca}, s_wave, [&](int k, const WinA run) {
+        const int64_t j = L.j0 + k;
+        const uint32_t after = k + 1 < WIN_PER ? (uint32_t)(L.bytes >> (8 * (k + 1))) : next;
+        // a frame ends where the next position starts another run of peers / another partition, and at the last row
+        if (frame == HS_WIN_FRAME_ROWS || j + 1 >= A.n || (after & end_bit)) {
+            const int32_t start = frame == HS_WIN_FRAME_ROWS ? (int32_t)j : frame == HS_WIN_FRAME_RANGE ? run.q : run.p;
+            A.tab_a[start] = run.a;
+            A.tab_c[start] = (int32_t)j - run.p + 1;
+        }
+    });
+}
+
+__device__ __forceinline__ uint32_t wa_f32(double d, uint32_t& err) {
+    const float f = (float)d;  // RNE
+    if (isinf(f) && !isinf(d)) err |= HS_FLAG_FLT_OVERFLOW;
+    return __float_as_uint(f);
+}
+// the cell an item stores for a frame's fold `a` over `count` rows
+__device__ __forceinline__ uint32_t wa_finish(int func, int is_float, uint64_t a, int32_t count, uint32_t& err) {
+    switch (func) {
+        case HS_WIN_COUNT: return (uint32_t)count;
+        case HS_WIN_SUM:
+            if (is_float) return wa_f32(hs_u2d(a), err);
+            if ((int64_t)a != (int64_t)(int32_t)a) err |= HS_FLAG_INT_OVERFLOW;
+            return (uint32_t)a;
+        case HS_WIN_AVG: return wa_f32((is_float ? hs_u2d(a) : (double)(int64_t)a) / (double)count, err);
+        default: {  // MIN / MAX: the word back to the cell
+            const uint32_t w = (uint32_t)a;
+            if (!is_float) return w ^ 0x80000000u;
+            return (w & 0x80000000u) ? (w & 0x7fffffffu) : ~w;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_wagg_emit(const WaggArgs A_kernarg) {
+    HS_KERNARG(WaggArgs, A);
+    __shared__ WinS s_wave[OB_WAVES];
+    __shared__ int32_t s_at[OB_TILE + OB_THREADS];  // the table cell of every position
+    const int tid = threadIdx.x, frame = A.frame;
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
+    win_rescan(A.heads, A.carry[blockIdx.x], A.n, s_wave, [&](int k, const WinS run) {
+        s_at[win_put_at(tid, k)] = frame == HS_WIN_FRAME_ROWS ? (int32_t)(j0 + k) : frame == HS_WIN_FRAME_RANGE ? run.q : run.p;
+    });
+    __syncthreads();
+    uint32_t err = 0;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t j = tile0 + e;
+        if (j < A.n) {
+            const int64_t row = A.perm ? A.perm[j] : j;
+            const int32_t at = s_at[win_get_at(e)];
+            A.out[row] = wa_finish(A.func, A.is_float, A.tab_a[at], A.tab_c[at], err);
+        }
+    }
+    if (err && A.flags) atomicOr(A.flags, err);
+}
+
+// -----------------------------------------------------------------------------------------------------
+// Navigation (hs_window_nav).  LAG / LEAD / FIRST_VALUE / LAST_VALUE copy the argument's cell of ANOTHER
+// sorted position s of the row's partition, NTILE numbers buckets from (row number, partition rows).  Per sorted position
+// j, P / Q the partition / peer head at or before j and E the frame's end:
+//     LAG(k)       s = j - k, the default when s < P         LEAD(k)  s = j + k, the default when s > E(partition)
+//     FIRST_VALUE  s = P                                     LAST_VALUE  s = j (ROWS) | E(range) | E(partition)
+//     NTILE(n)     r = j - P + 1 of N = E(partition) - P + 1 rows
+// E comes from k_wagg_scan run without an argument (WA_NONE): it leaves tab_c[start] = E - P + 1 at start = P (PARTITION) or
+// Q (RANGE) - one pass per frame the call needs, not per item.  Per distinct argument k_wnav_gather leaves the cells in
+// sorted order (4 or 8 bytes; without keys position = row and the argument is read as it stands), per item k_wnav_emit
+// rescans (p, q), reads cell s and scatters out[perm[j]].  Cells are copied as bits.
+// -----------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(OB_THREADS) k_wnav_gather(const int64_t* perm, const T* values, T* sorted, int64_t n) {
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE;
+    int64_t row[WIN_PER];
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {  // consecutive lanes on consecutive positions; nothing past the rows
+        const int64_t j = tile0 + k * OB_THREADS + threadIdx.x;
+        row[k] = j < n ? perm[j] : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k)
+        if (row[k] >= 0) sorted[tile0 + k * OB_THREADS + threadIdx.x] = values[row[k]];
+}
+
+struct WnavArgs : WinTile {
+    const void* cells;     // the argument by sorted position (not read by NTILE)
+    const int32_t* tab_c;  // E - P + 1 by the frame's start (LEAD, NTILE: PARTITION; LAST_VALUE: its frame's; else not read)
+    void* out;             // one item per launch: input order
+    uint64_t dflt;         // LAG / LEAD: the default's bits
+    int64_t k;             // LAG / LEAD: the offset; NTILE: the buckets
+    int32_t func, frame;
+};
+static_assert(sizeof(WnavArgs) % 8 == 0, "WnavArgs");
+
+// NTILE: the bucket of row r (1-based) of N rows in n buckets, the first N mod n of them one row larger
+__device__ __forceinline__ uint32_t wnav_ntile(uint32_t r, uint32_t N, uint32_t n) {
+    const uint32_t s = N / n, m = N - s * n, big = m * (s + 1);  // big <= N: no overflow
+    if (r <= big) return (r - 1) / (s + 1) + 1;
+    return m + (r - 1 - big) / (s ? s : 1u) + 1;                 // s == 0: big == N, never here
+}
+
+template <typename T>
+__global__ void __launch_bounds__(OB_THREADS) k_wnav_emit(const WnavArgs A_kernarg) {
+    HS_KERNARG(WnavArgs, A);
+    __shared__ WinS s_wave[OB_WAVES];
+    __shared__ int32_t s_p[OB_TILE + OB_THREADS], s_q[OB_TILE + OB_THREADS];
+    const int tid = threadIdx.x, func = A.func, frame = A.frame;
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE;
+    win_rescan(A.heads, A.carry[blockIdx.x], A.n, s_wave, [&](int k, const WinS run) {
+        s_p[win_put_at(tid, k)] = run.p;
+        s_q[win_put_at(tid, k)] = run.q;
+    });
+    __syncthreads();
+    const T* cells = (const T*)A.cells;
+    T* out = (T*)A.out;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t j = tile0 + e;
+        if (j >= A.n) break;
+        const int64_t row = A.perm ? A.perm[j] : j;
+        const int64_t p = s_p[win_get_at(e)], q = s_q[win_get_at(e)];  // 0 <= p <= q <= j: position 0 is a head
+        if (func == HS_WIN_NTILE) {
+            out[row] = (T)wnav_ntile((uint32_t)(j - p + 1), (uint32_t)A.tab_c[p], (uint32_t)A.k);
+            continue;
+        }
+        int64_t s = j;  // 64 bits: k may be 2^31 - 1
+        bool valid = true;
+        if (func == HS_WIN_LAG) {
+            s = j - A.k;
+            valid = s >= p;
+        } else if (func == HS_WIN_LEAD) {
+            s = j + A.k;
+            valid = s <= p + A.tab_c[p] - 1;
+        } else if (func == HS_WIN_FIRST_VALUE) {
+            s = p;
+        } else if (frame != HS_WIN_FRAME_ROWS) {  // LAST_VALUE: the frame's last row
+            s = p + A.tab_c[frame == HS_WIN_FRAME_RANGE ? q : p] - 1;
+        }
+        out[row] = valid ? cells[s] : (T)A.dflt;  // a valid s lies in the row's partition: inside [0, n)
+    }
+}
+
+// -----------------------------------------------------------------------------------------------------
+// The host side of the three entries: one workspace layout, one item table, one run routine.
+// -----------------------------------------------------------------------------------------------------
+// Where everything lies behind the sort's workspace, and where each entry's share of it ends: hs_window's, then what
+// hs_window_agg adds, then what hs_window_nav adds.  The items of a call run one after the other over the same regions.
+struct WinLayout {
+    size_t heads;    // a head byte per sorted position, whole tiles
+    size_t recs;     // a (p, q, d) record per tile, and one more
+    size_t rank_end;
+    size_t cells4;   // an argument's 4-byte cells by sorted position, whole tiles
+    size_t tab_a;    // a frame's fold ...
+    size_t tab_c;    // ... and its rows, by the frame's start position
+    size_t recs_a;   // a WinA record per tile, and one more
+    size_t agg_end;
+    size_t cells8;   // an argument's cells by sorted position at 8 bytes, whole tiles
+    size_t ends[2];  // the frames' rows by their start position: PARTITION, RANGE
+    size_t nav_end;
+};
+static_assert(HS_WIN_FRAME_PARTITION == 0 && HS_WIN_FRAME_RANGE == 1, "the end tables are indexed by frame");
+static WinLayout win_layout(int64_t nrows) {
+    const size_t tiles = (size_t)((nrows + OB_TILE - 1) / OB_TILE), whole = rx_align(tiles * OB_TILE);
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) {
+        const size_t here = at;
+        at += bytes;
+        return here;
+    };
+    WinLayout L;
+    L.heads = take(whole);
+    L.recs = take(rx_align((tiles + 1) * sizeof(WinRec)));
+    L.rank_end = at;
+    L.cells4 = take(4 * whole);
+    L.tab_a = take(rx_align((size_t)nrows * 8));
+    L.tab_c = take(rx_align((size_t)nrows * 4));
+    L.recs_a = take(rx_align((tiles + 1) * sizeof(WinA)));
+    L.agg_end = at;
+    L.cells8 = take(8 * whole);
+    L.ends[HS_WIN_FRAME_PARTITION] = take(rx_align((size_t)nrows * 4));
+    L.ends[HS_WIN_FRAME_RANGE] = take(rx_align((size_t)nrows * 4));
+    L.nav_end = at;
+    return L;
+}
+
+// the sort's workspace, then the layout up to an entry's end
+static size_t win_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, size_t WinLayout::*end) {
+    return nrows < 0 ? 0 : hs_order_by_ws_bytes(nrows, n_keys, max_key_words) + win_layout(nrows).*end;
+}
+extern "C" size_t hs_window_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words) {
+    return win_ws_bytes(nrows, n_keys, max_key_words, &WinLayout::rank_end);
+}
+extern "C" size_t hs_window_agg_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t) {
+    return win_ws_bytes(nrows, n_keys, max_key_words, &WinLayout::agg_end);
+}
+extern "C" size_t hs_window_nav_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t) {
+    return win_ws_bytes(nrows, n_keys, max_key_words, &WinLayout::nav_end);
+}
+
+// What an item of each HS_WIN_* code takes beside the keys
+enum { WI_ARG_NONE = 0, WI_ARG_32 = 1, WI_ARG_32_64 = 2 };        // the argument column's cells
+enum { WI_PARAM_NONE = 0, WI_PARAM_OFFSET = 1, WI_PARAM_BUCKETS = 2 };  // params[i] (an offset comes with a default cell)
+struct WinItem {
+    uint8_t frame, arg, param;
+};
+static const WinItem WIN_ITEMS[] = {
+    {0, WI_ARG_NONE, WI_PARAM_NONE},     // HS_WIN_ROW_NUMBER
+    {0, WI_ARG_NONE, WI_PARAM_NONE},     // HS_WIN_RANK
+    {0, WI_ARG_NONE, WI_PARAM_NONE},     // HS_WIN_DENSE_RANK
+    {1, WI_ARG_NONE, WI_PARAM_NONE},     // HS_WIN_COUNT
+    {1, WI_ARG_32, WI_PARAM_NONE},       // HS_WIN_SUM
+    {1, WI_ARG_32, WI_PARAM_NONE},       // HS_WIN_AVG
+    {1, WI_ARG_32, WI_PARAM_NONE},       // HS_WIN_MIN
+    {1, WI_ARG_32, WI_PARAM_NONE},       // HS_WIN_MAX
+    {0, WI_ARG_32_64, WI_PARAM_OFFSET},  // HS_WIN_LAG
+    {0, WI_ARG_32_64, WI_PARAM_OFFSET},  // HS_WIN_LEAD
+    {1, WI_ARG_32_64, WI_PARAM_NONE},    // HS_WIN_FIRST_VALUE
+    {1, WI_ARG_32_64, WI_PARAM_NONE},    // HS_WIN_LAST_VALUE
+    {0, WI_ARG_NONE, WI_PARAM_BUCKETS},  // HS_WIN_NTILE
+};
+static_assert(sizeof(WIN_ITEMS) / sizeof(WIN_ITEMS[0]) == HS_WIN_NTILE + 1 && HS_WIN_COUNT == 3 && HS_WIN_MAX == 7 &&
+                  HS_WIN_LAG == 8 && HS_WIN_LAST_VALUE == 11, "WIN_ITEMS is indexed by HS_WIN_*");
+static const struct {
+    bool i64;                    // HS_I32 and HS_F32 cells, and these?
+    const char *others, *takes;  // the refusal's words
+} WIN_ARGS[] = {{false, "", ""},
+                {false, "a narrow or virtual column, or another type", "HS_I32 or HS_F32"},
+                {true, "a narrow or virtual column, a STRING, or another type", "HS_I32, HS_F32 or HS_I64"}};
+
+// What all entries refuse before anything is launched or any device pointer is read, under the caller's name.  HS_OK: go
+// on (nrows == 0 included - the caller returns then).
 static int win_refuse(const char* name, const hs_col* keys, int32_t n_part, int32_t n_keys, int64_t nrows, const int32_t* funcs,
                       int32_t n_funcs, const void* out, int32_t max_func) {
     if (n_keys < 0 || n_part < 0 || n_part > n_keys || nrows < 0 || n_funcs <= 0 || !funcs || !out) {
@@ -2692,23 +3111,69 @@ static int win_refuse(const char* name, const hs_col* keys, int32_t n_part, int3
     return HS_OK;
 }
 
-// The front half both entries share, nrows > 0: the pointer checks, ONE sort, ONE heads pass and ONE (p, q, d) tile carry.
-struct WinFront {
-    const uint8_t* heads;  // by sorted position, whole tiles
-    const int64_t* perm;   // the sorted rows (null: position = row)
-    const int4* carry;     // per tile
-    int64_t tiles;
-    uint8_t* rest;         // the workspace behind what hs_window_ws_bytes counts
-};
-static int win_front(hipStream_t stream, const char* name, const hs_col* keys, const int32_t* descending, int32_t n_part,
-                     int32_t n_keys, int64_t nrows, void* const* out, int32_t n_funcs, void* ws_, WinFront& F) {
+// What item i needs by WIN_ITEMS, behind win_refuse: its frame, its parameter, its argument's kind, in this order.
+// Nothing is launched, no device pointer read.
+static int win_refuse_item(const char* name, int i, const int32_t* funcs, const int32_t* frames, const hs_col* values,
+                           const int64_t* params, const uint64_t* defaults) {
+    const WinItem& item = WIN_ITEMS[funcs[i]];
+    if (item.frame && (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > HS_WIN_FRAME_ROWS)) {
+        hs_set_error("%s: item %d: frame %d is not one of HS_WIN_FRAME_*", name, i, frames ? frames[i] : -1);
+        return HS_E_ARG;
+    }
+    if (item.param != WI_PARAM_NONE) {
+        const int64_t least = item.param == WI_PARAM_BUCKETS ? 1 : 0;
+        const char* what = item.param == WI_PARAM_BUCKETS ? "the bucket count n" : "the offset k";
+        if (!params) {
+            hs_set_error("%s: item %d: %s is missing (params is null)", name, i, what);
+            return HS_E_ARG;
+        }
+        if (params[i] < least || params[i] >= (1ll << 31)) {
+            hs_set_error("%s: item %d: %s is %lld; it lies in [%lld, 2^31)", name, i, what, (long long)params[i], (long long)least);
+            return HS_E_ARG;
+        }
+        if (item.param == WI_PARAM_OFFSET && !defaults) {
+            hs_set_error("%s: item %d: LAG / LEAD need a default cell (defaults is null)", name, i);
+            return HS_E_ARG;
+        }
+    }
+    if (item.arg != WI_ARG_NONE) {
+        const auto& arg = WIN_ARGS[item.arg];
+        const int32_t kind = values ? values[i].kind : -1;
+        if (kind != HS_I32 && kind != HS_F32 && !(arg.i64 && kind == HS_I64)) {
+            hs_set_error("%s: item %d: the argument is a column of kind %d (%s); it takes %s cells", name, i, kind, arg.others,
+                         arg.takes);
+            return HS_E_ARG;
+        }
+    }
+    return HS_OK;
+}
+
+// The three entries: `max_func` the highest HS_WIN_* code the entry takes, `last` what it calls its launches behind the front
+// half; an entry passes null for the arrays it does not have.  ONE sort, ONE heads pass and ONE (p, q, d) tile carry for
+// all items of a call, then the items one after the other.  An entry's workspace ends with its share of WinLayout:
+// pointers into the regions behind it are formed here and not used, no item of the entry reaching them.
+static int win_run(const char* name, const char* last, int32_t max_func, void* stream_, const hs_col* keys,
+                   const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows, const int32_t* funcs,
+                   const int32_t* frames, const hs_col* values, const int64_t* params, const uint64_t* defaults, int32_t n_items,
+                   void* const* out, void* ws_, uint32_t* flags) {
+    int rc = win_refuse(name, keys, n_part, n_keys, nrows, funcs, n_items, out, max_func);
+    if (rc != HS_OK) return rc;
+    for (int i = 0; i < n_items; ++i)
+        if ((rc = win_refuse_item(name, i, funcs, frames, values, params, defaults)) != HS_OK) return rc;
+    if (nrows == 0) return HS_OK;
+    const auto takes_value = [&](int i) { return WIN_ITEMS[funcs[i]].arg != WI_ARG_NONE; };
+    for (int i = 0; i < n_items; ++i)
+        if (takes_value(i) && !values[i].data) {
+            hs_set_error("%s: item %d: the argument column is null", name, i);
+            return HS_E_ARG;
+        }
     if (!ws_ || (n_keys > 0 && !keys) || (n_keys > n_part && !descending)) {
         hs_set_error("%s: bad arguments", name);
         return HS_E_ARG;
     }
-    for (int f = 0; f < n_funcs; ++f)
-        if (!out[f]) {
-            hs_set_error("%s: output %d is null", name, f);
+    for (int i = 0; i < n_items; ++i)
+        if (!out[i]) {
+            hs_set_error("%s: output %d is null", name, i);
             return HS_E_ARG;
         }
     for (int k = 0; k < n_keys; ++k)
@@ -2716,15 +3181,16 @@ static int win_front(hipStream_t stream, const char* name, const hs_col* keys, c
             hs_set_error("%s: key %d is not a column that can be ordered", name, k);
             return HS_E_ARG;
         }
+    hipStream_t stream = (hipStream_t)stream_;
     int32_t desc[HS_MAX_COLS] = {0};
     for (int k = n_part; k < n_keys; ++k) desc[k] = descending[k] ? 1 : 0;
     WinHeads H;
     std::memset(&H, 0, sizeof(H));
-    size_t sort_bytes = 0;
+    uint8_t* base = nullptr;  // behind what the sort laid out
     {
         ObSorted S;
         int64_t sorted_rows = 0;
-        const int rc = ob_sort(stream, keys, desc, n_keys, nrows, nullptr, -1, &sorted_rows, ws_, name, S);
+        rc = ob_sort(stream, keys, desc, n_keys, nrows, nullptr, -1, &sorted_rows, ws_, name, S);
         if (rc != HS_OK) return rc;
         H.K = S.keys;
         H.n_keys = n_keys;
@@ -2733,575 +3199,35 @@ static int win_front(hipStream_t stream, const char* name, const hs_col* keys, c
         H.n = nrows;
         if (S.n_words == 1 && S.rows) H.words = S.words;  // one word per row: the sorted words ARE the rows' keys
         for (int k = 0; k < n_part; ++k) H.part_bytes += S.keys.width[k];
-        sort_bytes = S.ws_bytes;
+        base = (uint8_t*)ws_ + S.ws_bytes;
     }
-    H.heads = (uint8_t*)ws_ + sort_bytes;
-    int4* sums = (int4*)(H.heads + win_heads_bytes(nrows));
+    const WinLayout L = win_layout(nrows);
+    H.heads = base + L.heads;
+    const WinTile T{H.heads, H.perm, (WinRec*)(base + L.recs), nrows};
     const int64_t tiles = (nrows + OB_TILE - 1) / OB_TILE;
-    hipLaunchKernelGGL(k_win_heads, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, H);
+    const dim3 grid((unsigned)tiles), block(OB_THREADS);
+    hipLaunchKernelGGL(k_win_heads, grid, block, 0, stream, H);
     if (hipGetLastError() != hipSuccess) {
         hs_set_error("%s (heads): kernel launch failed", name);
         return HS_E_LAUNCH;
     }
-    hipLaunchKernelGGL(k_win_reduce, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, (const uint8_t*)H.heads, nrows, sums);
-    hipLaunchKernelGGL(k_win_tiles, dim3(1), dim3(OB_THREADS), 0, stream, sums, tiles);
+    hipLaunchKernelGGL(k_win_reduce, grid, block, 0, stream, T.heads, nrows, (WinRec*)T.carry);
+    hipLaunchKernelGGL(k_win_tiles<WinSOps>, dim3(1), block, 0, stream, (WinRec*)T.carry, tiles, WinSOps{});
     if (hipGetLastError() != hipSuccess) {
         hs_set_error("%s (scan): kernel launch failed", name);
         return HS_E_LAUNCH;
     }
-    F = WinFront{H.heads, H.perm, sums, tiles, (uint8_t*)sums + rx_align((size_t)(tiles + 1) * sizeof(int4))};
-    return HS_OK;
-}
-
-extern "C" int hs_window(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
-                         int64_t nrows, const int32_t* funcs, int32_t n_funcs, int32_t* const* out, void* ws_, uint32_t* flags) {
-    (void)flags;
-    int rc = win_refuse("hs_window", keys, n_part, n_keys, nrows, funcs, n_funcs, out, HS_WIN_DENSE_RANK);
-    if (rc != HS_OK || nrows == 0) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    WinFront F;
-    rc = win_front(stream, "hs_window", keys, descending, n_part, n_keys, nrows, (void* const*)out, n_funcs, ws_, F);
-    if (rc != HS_OK) return rc;
-    WinEmit E;
-    std::memset(&E, 0, sizeof(E));
-    E.heads = F.heads;
-    E.perm = F.perm;
-    E.carry = F.carry;
-    E.n = nrows;
-    for (int f = 0; f < n_funcs; ++f) {
-        E.out = out[f];
-        E.func = funcs[f];
-        hipLaunchKernelGGL(k_win_emit, dim3((unsigned)F.tiles), dim3(OB_THREADS), 0, stream, E);
-    }
-    RX_CHECK_LAUNCH("hs_window (emit)");
-    return HS_OK;
-}
-
-// =====================================================================================================
-// Window aggregates over result rows (include/hipspark.h hs_window_agg).
-//
-// COUNT / SUM / AVG / MIN / MAX ride on win_front: the same sort, head bytes and (p, q, d) tile carry.  Per sorted
-// position j the value is the fold of the argument over [P(j), E(j)], P the partition head at or before j and E the
-// frame's end: j itself (ROWS), the last peer of j (RANGE), the partition's last row (PARTITION).  The fold is one more
-// segmented scan that restarts at every partition head, beside p and q:
-//     (p, q, a) (+) (p', q', a') = (max(p, p'), max(q, q'), p' >= 0 ? a' : a op a')
-// - the restart is a select, so a NaN or an infinity never leaves its partition - with a 64-bit accumulator: an i64 sum,
-// an f64 sum, or for MIN / MAX the sort's order-preserving word of the cell (ob_f32_word: -0.0 = 0.0, NaN after +inf).
-// Earlier positions stay on the LEFT at every level, so the association of an f64 sum is fixed by (rows, tile geometry):
-// the same bits from run to run, not those of the left-to-right fold.  Per item:
-//   k_wagg_reduce  gathers the argument through the row list (coalesced over positions, across to the lanes' 8
-//                  consecutive positions through LDS), leaves the cells in SORTED order for the next pass and folds the
-//                  tile into one summary;
-//   k_wagg_tiles   one workgroup, rounds of 2048 summaries: every tile's carry;
-//   k_wagg_scan    scans the tile again behind both carries and, at every frame end, stores the running value and the
-//                  frame's row count into two tables indexed by the frame's START position (j, Q or P): one vector
-//                  store per frame, no atomics;
-//   k_wagg_emit    every position reads the tables at its own j / Q / P - all rows of a frame the same cell - finishes
-//                  the value (AVG divides, SUM / AVG round to the cell type and raise the overflow flags) and scatters
-//                  out[perm[j]], one launch per item like k_win_emit.
-// COUNT has no argument: it skips the first two kernels; COUNT under ROWS is ROW_NUMBER and takes k_win_emit.
-// =====================================================================================================
-enum { WA_NONE = 0, WA_ADD_I = 1, WA_ADD_F = 2, WA_MIN = 3, WA_MAX = 4 };
-
-struct WinA {
-    int32_t p, q;  // as in WinS
-    uint64_t a;    // the fold since the last partition head
-};
-static_assert(sizeof(WinA) == 16, "WinA");
-
-__device__ __forceinline__ uint64_t wa_identity(int op) { return op == WA_MIN ? ~0ull : 0ull; }
-__device__ __forceinline__ uint64_t wa_op(int op, uint64_t a, uint64_t b) {  // a: the EARLIER positions
-    switch (op) {
-        case WA_ADD_I: return a + b;
-        case WA_ADD_F: return hs_d2u(hs_u2d(a) + hs_u2d(b));
-        case WA_MIN: return a < b ? a : b;
-        case WA_MAX: return a > b ? a : b;
-        default: return 0;
-    }
-}
-// a stored cell as an accumulator
-__device__ __forceinline__ uint64_t wa_lift(int op, int is_float, uint32_t v) {
-    switch (op) {
-        case WA_ADD_I: return (uint64_t)(int64_t)(int32_t)v;
-        case WA_ADD_F: return hs_d2u((double)__uint_as_float(v));
-        case WA_MIN:
-        case WA_MAX: return is_float ? ob_f32_word(v) : v ^ 0x80000000u;
-        default: return 0;
-    }
-}
-__device__ __forceinline__ WinA wa_join(int op, const WinA a, const WinA b) {  // a: the EARLIER positions
-    return WinA{a.p > b.p ? a.p : b.p, a.q > b.q ? a.q : b.q, b.p >= 0 ? b.a : wa_op(op, a.a, b.a)};
-}
-__device__ __forceinline__ WinA wa_of(uint32_t head, int32_t j, uint64_t x) {
-    return WinA{(head & 2u) ? j : -1, (head & 1u) ? j : -1, x};
-}
-__device__ __forceinline__ WinA wa_shfl_up(const WinA v, int d) {
-    return WinA{__shfl_up(v.p, d, HS_WAVE), __shfl_up(v.q, d, HS_WAVE),
-                (uint64_t)__shfl_up((unsigned long long)v.a, d, HS_WAVE)};  // two 32-bit shuffles
-}
-// win_block_excl for WinA
-__device__ __forceinline__ WinA wa_block_excl(int op, const WinA v, WinA* s_wave, WinA& total) {
-    const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE;
-    const WinA none{-1, -1, wa_identity(op)};
-    WinA incl = v;
-#pragma unroll
-    for (int d = 1; d < HS_WAVE; d <<= 1) {
-        const WinA t = wa_shfl_up(incl, d);
-        if (lane >= d) incl = wa_join(op, t, incl);
-    }
-    if (lane == HS_WAVE - 1) s_wave[w] = incl;
-    WinA excl = wa_shfl_up(incl, 1);
-    if (lane == 0) excl = none;
-    __syncthreads();
-    WinA base = none;
-    total = none;
-#pragma unroll
-    for (int k = 0; k < OB_WAVES; ++k) {
-        if (k == w) base = total;
-        total = wa_join(op, total, s_wave[k]);
-    }
-    return wa_join(op, base, excl);
-}
-
-struct WaggArgs {
-    const uint8_t* heads;
-    const int64_t* perm;     // null: position = row
-    const int4* carry;       // per tile: (p, q, d) of the tiles before (k_win_tiles)
-    int64_t n;
-    const uint32_t* values;  // the argument's cells, input order (not read when op == WA_NONE)
-    uint32_t* sorted;        // the cells by sorted position, whole tiles
-    WinA* tiles;             // per tile: k_wagg_reduce's summary, then k_wagg_tiles' carry
-    uint64_t* tab_a;         // by the START position of a frame: its fold ...
-    int32_t* tab_c;          // ... and its rows
-    uint32_t* out;           // one item per launch: input order
-    uint32_t* flags;         // may be null
-    int32_t op, is_float, frame, func;
-};
-static_assert(sizeof(WaggArgs) % 8 == 0, "WaggArgs");
-
-__global__ void __launch_bounds__(OB_THREADS) k_wagg_reduce(const WaggArgs A_kernarg) {
-    HS_KERNARG(WaggArgs, A);
-    __shared__ WinA s_wave[OB_WAVES];
-    __shared__ uint32_t s_v[OB_TILE + OB_THREADS];  // one pad word per lane segment (k_win_emit's layout)
-    const int tid = threadIdx.x, op = A.op;
-    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        const int e = k * OB_THREADS + tid;
-        const int64_t j = tile0 + e;
-        uint32_t v = 0;
-        if (j < A.n) {
-            v = A.values[A.perm ? A.perm[j] : j];
-            A.sorted[j] = v;
-        }
-        s_v[e + e / WIN_PER] = v;
-    }
-    __syncthreads();
-    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);  // the buffer holds whole tiles
-    WinA acc{-1, -1, wa_identity(op)};
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        const uint64_t x = j0 + k < A.n ? wa_lift(op, A.is_float, s_v[tid * (WIN_PER + 1) + k]) : wa_identity(op);
-        acc = wa_join(op, acc, wa_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k), x));
-    }
-    WinA total;
-    wa_block_excl(op, acc, s_wave, total);
-    if (tid == 0) A.tiles[blockIdx.x] = total;
-}
-
-// one workgroup: tiles[t] = the join of the summaries of tiles 0 .. t - 1, in place (k_win_tiles for WinA)
-__global__ void __launch_bounds__(OB_THREADS) k_wagg_tiles(WinA* tiles, int64_t ntiles, int32_t op) {
-    __shared__ WinA s_wave[OB_WAVES];
-    const WinA none{-1, -1, wa_identity(op)};
-    WinA carry = none;  // the rounds before this one: the same in every thread
-    for (int64_t t0 = 0; t0 < ntiles; t0 += OB_TILE) {
-        const int64_t mine = t0 + (int64_t)threadIdx.x * WIN_PER;
-        WinA v[WIN_PER], acc = none;
-#pragma unroll
-        for (int k = 0; k < WIN_PER; ++k) {
-            v[k] = none;
-            if (mine + k < ntiles) v[k] = tiles[mine + k];
-            acc = wa_join(op, acc, v[k]);
-        }
-        WinA total;
-        WinA run = wa_join(op, carry, wa_block_excl(op, acc, s_wave, total));
-#pragma unroll
-        for (int k = 0; k < WIN_PER; ++k) {
-            if (mine + k < ntiles) tiles[mine + k] = run;
-            run = wa_join(op, run, v[k]);
-        }
-        carry = wa_join(op, carry, total);
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(OB_THREADS) k_wagg_scan(const WaggArgs A_kernarg) {
-    HS_KERNARG(WaggArgs, A);
-    __shared__ WinA s_wave[OB_WAVES];
-    const int tid = threadIdx.x, op = A.op, frame = A.frame;
-    const int64_t j0 = (int64_t)blockIdx.x * OB_TILE + (int64_t)tid * WIN_PER;
-    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);
-    // the head byte behind the lane's eight: written where it is a row (the byte after the last tile is never read)
-    const uint32_t next = j0 + WIN_PER < A.n ? A.heads[j0 + WIN_PER] : 0u;
-    uint32_t cell[WIN_PER] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (op != WA_NONE) {  // `sorted` holds whole tiles: cells past the rows are read and not used
-        const uint4 lo = *(const uint4*)(A.sorted + j0), hi = *(const uint4*)(A.sorted + j0 + 4);
-        cell[0] = lo.x, cell[1] = lo.y, cell[2] = lo.z, cell[3] = lo.w;
-        cell[4] = hi.x, cell[5] = hi.y, cell[6] = hi.z, cell[7] = hi.w;
-    }
-    uint64_t x[WIN_PER];
-    WinA acc{-1, -1, wa_identity(op)};
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        x[k] = j0 + k < A.n ? wa_lift(op, A.is_float, cell[k]) : wa_identity(op);
-        acc = wa_join(op, acc, wa_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k), x[k]));
-    }
-    const int4 c = A.carry[blockIdx.x];
-    const uint64_t ca = op != WA_NONE ? A.tiles[blockIdx.x].a : 0ull;
-    WinA total;
-    WinA run = wa_join(op, WinA{c.x, c.y, ca}, wa_block_excl(op, acc, s_wave, total));
-    const uint32_t end_bit = frame == HS_WIN_FRAME_RANGE ? 1u : 2u;
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        const int64_t j = j0 + k;
-        if (j < A.n) {
-            run = wa_join(op, run, wa_of(win_head(bytes, k, j0, A.n), (int32_t)j, x[k]));
-            const uint32_t after = k + 1 < WIN_PER ? (uint32_t)(bytes >> (8 * (k + 1))) : next;
-            // a frame ends where the next position starts another run of peers / another partition, and at the last row
-            if (frame == HS_WIN_FRAME_ROWS || j + 1 >= A.n || (after & end_bit)) {
-                const int32_t start = frame == HS_WIN_FRAME_ROWS ? (int32_t)j : frame == HS_WIN_FRAME_RANGE ? run.q : run.p;
-                A.tab_a[start] = run.a;
-                A.tab_c[start] = (int32_t)j - run.p + 1;
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ uint32_t wa_f32(double d, uint32_t& err) {
-    const float f = (float)d;  // RNE
-    if (isinf(f) && !isinf(d)) err |= HS_FLAG_FLT_OVERFLOW;
-    return __float_as_uint(f);
-}
-// the cell an item stores for a frame's fold `a` over `count` rows
-__device__ __forceinline__ uint32_t wa_finish(int func, int is_float, uint64_t a, int32_t count, uint32_t& err) {
-    switch (func) {
-        case HS_WIN_COUNT: return (uint32_t)count;
-        case HS_WIN_SUM:
-            if (is_float) return wa_f32(hs_u2d(a), err);
-            if ((int64_t)a != (int64_t)(int32_t)a) err |= HS_FLAG_INT_OVERFLOW;
-            return (uint32_t)a;
-        case HS_WIN_AVG: return wa_f32((is_float ? hs_u2d(a) : (double)(int64_t)a) / (double)count, err);
-        default: {  // MIN / MAX: the word back to the cell
-            const uint32_t w = (uint32_t)a;
-            if (!is_float) return w ^ 0x80000000u;
-            return (w & 0x80000000u) ? (w & 0x7fffffffu) : ~w;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(OB_THREADS) k_wagg_emit(const WaggArgs A_kernarg) {
-    HS_KERNARG(WaggArgs, A);
-    __shared__ WinS s_wave[OB_WAVES];
-    __shared__ int32_t s_at[OB_TILE + OB_THREADS];  // the table cell of every position, handed over as in k_win_emit
-    const int tid = threadIdx.x, frame = A.frame;
-    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
-    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);
-    WinS acc{-1, -1, 0};
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) acc = win_join(acc, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
-    const int4 c = A.carry[blockIdx.x];
-    WinS total;
-    WinS run = win_join(WinS{c.x, c.y, c.z}, win_block_excl(acc, s_wave, total));
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        run = win_join(run, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
-        s_at[tid * (WIN_PER + 1) + k] = frame == HS_WIN_FRAME_ROWS ? (int32_t)(j0 + k) : frame == HS_WIN_FRAME_RANGE ? run.q : run.p;
-    }
-    __syncthreads();
-    uint32_t err = 0;
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        const int e = k * OB_THREADS + tid;
-        const int64_t j = tile0 + e;
-        if (j < A.n) {
-            const int64_t row = A.perm ? A.perm[j] : j;
-            const int32_t at = s_at[e + e / WIN_PER];
-            A.out[row] = wa_finish(A.func, A.is_float, A.tab_a[at], A.tab_c[at], err);
-        }
-    }
-    if (err && A.flags) atomicOr(A.flags, err);
-}
-
-static size_t wagg_extra_bytes(int64_t nrows) {
-    const size_t tiles = (size_t)((nrows + OB_TILE - 1) / OB_TILE);
-    return 4 * win_heads_bytes(nrows) + rx_align((size_t)nrows * 8) + rx_align((size_t)nrows * 4) + rx_align((tiles + 1) * sizeof(WinA));
-}
-
-extern "C" size_t hs_window_agg_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t n_items) {
-    (void)n_items;  // the items run one after the other over the same cells, tables and tile summaries
-    if (nrows < 0) return 0;
-    return hs_window_ws_bytes(nrows, n_keys, max_key_words) + wagg_extra_bytes(nrows);
-}
-
-// What an item of funcs[i] <= HS_WIN_MAX needs beside win_refuse, under the caller's name: a frame for the aggregates, an
-// HS_I32 / HS_F32 argument for SUM / AVG / MIN / MAX.  Nothing is launched, no device pointer read.
-static int wagg_refuse_item(const char* name, int i, const int32_t* funcs, const int32_t* frames, const hs_col* values) {
-    if (funcs[i] < HS_WIN_COUNT) return HS_OK;  // ranking: neither a frame nor an argument
-    if (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > HS_WIN_FRAME_ROWS) {
-        hs_set_error("%s: item %d: frame %d is not one of HS_WIN_FRAME_*", name, i, frames ? frames[i] : -1);
-        return HS_E_ARG;
-    }
-    if (funcs[i] == HS_WIN_COUNT) return HS_OK;
-    if (!values || (values[i].kind != HS_I32 && values[i].kind != HS_F32)) {
-        hs_set_error("%s: item %d: the argument is a column of kind %d (a narrow or virtual column, or another "
-                     "type); it takes HS_I32 or HS_F32 cells", name, i, values ? values[i].kind : -1);
-        return HS_E_ARG;
-    }
-    return HS_OK;
-}
-
-// The launches of ranking and aggregate items behind win_front (hs_window_agg, and hs_window_nav for its older codes)
-struct WaggItems {
-    WinEmit E;
-    WaggArgs A;
-    int64_t tiles;
-};
-static WaggItems wagg_items(const WinFront& F, int64_t nrows, uint32_t* flags) {
-    WaggItems W;
-    std::memset(&W, 0, sizeof(W));
-    W.tiles = F.tiles;
-    W.E.heads = F.heads;
-    W.E.perm = F.perm;
-    W.E.carry = F.carry;
-    W.E.n = nrows;
-    W.A.heads = F.heads;
-    W.A.perm = F.perm;
-    W.A.carry = F.carry;
-    W.A.n = nrows;
-    W.A.sorted = (uint32_t*)F.rest;
-    W.A.tab_a = (uint64_t*)(F.rest + 4 * win_heads_bytes(nrows));
-    W.A.tab_c = (int32_t*)((uint8_t*)W.A.tab_a + rx_align((size_t)nrows * 8));
-    W.A.tiles = (WinA*)((uint8_t*)W.A.tab_c + rx_align((size_t)nrows * 4));
-    W.A.flags = flags;
-    return W;
-}
-static void wagg_item(hipStream_t stream, WaggItems& W, int32_t func, int32_t frame, const hs_col* value, void* out) {
-    const dim3 grid((unsigned)W.tiles), block(OB_THREADS);
-    if (func < HS_WIN_COUNT || (func == HS_WIN_COUNT && frame == HS_WIN_FRAME_ROWS)) {
-        W.E.out = (int32_t*)out;
-        W.E.func = func < HS_WIN_COUNT ? func : HS_WIN_ROW_NUMBER;  // the rows from the partition's first through this one
-        hipLaunchKernelGGL(k_win_emit, grid, block, 0, stream, W.E);
-        return;
-    }
-    WaggArgs& A = W.A;
-    A.func = func;
-    A.frame = frame;
-    A.out = (uint32_t*)out;
-    A.op = WA_NONE;
-    if (func != HS_WIN_COUNT) {
-        A.is_float = value->kind == HS_F32;
-        A.values = (const uint32_t*)value->data;
-        A.op = func == HS_WIN_MIN ? WA_MIN : func == HS_WIN_MAX ? WA_MAX : A.is_float ? WA_ADD_F : WA_ADD_I;
-        hipLaunchKernelGGL(k_wagg_reduce, grid, block, 0, stream, A);
-        hipLaunchKernelGGL(k_wagg_tiles, dim3(1), block, 0, stream, A.tiles, W.tiles, A.op);
-    }
-    hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, A);
-    hipLaunchKernelGGL(k_wagg_emit, grid, block, 0, stream, A);
-}
-
-extern "C" int hs_window_agg(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
-                             int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values, int32_t n_items,
-                             void* const* out, void* ws_, uint32_t* flags) {
-    int rc = win_refuse("hs_window_agg", keys, n_part, n_keys, nrows, funcs, n_items, out, HS_WIN_MAX);
-    if (rc != HS_OK) return rc;
-    for (int i = 0; i < n_items; ++i)
-        if ((rc = wagg_refuse_item("hs_window_agg", i, funcs, frames, values)) != HS_OK) return rc;
-    if (nrows == 0) return HS_OK;
-    for (int i = 0; i < n_items; ++i)
-        if (funcs[i] > HS_WIN_COUNT && !values[i].data) {
-            hs_set_error("hs_window_agg: item %d: the argument column is null", i);
-            return HS_E_ARG;
-        }
-    hipStream_t stream = (hipStream_t)stream_;
-    WinFront F;
-    rc = win_front(stream, "hs_window_agg", keys, descending, n_part, n_keys, nrows, out, n_items, ws_, F);
-    if (rc != HS_OK) return rc;
-    WaggItems W = wagg_items(F, nrows, flags);
-    for (int i = 0; i < n_items; ++i) wagg_item(stream, W, funcs[i], frames ? frames[i] : 0, values ? &values[i] : nullptr, out[i]);
-    RX_CHECK_LAUNCH("hs_window_agg (items)");
-    return HS_OK;
-}
-
-// =====================================================================================================
-// Window navigation over result rows (include/hipspark.h hs_window_nav).
-//
-// LAG / LEAD / FIRST_VALUE / LAST_VALUE copy the argument's cell of ANOTHER sorted position s of the row's partition,
-// NTILE numbers buckets from (row number, partition rows).  Everything rides on win_front; per sorted position j, P / Q the
-// partition / peer head at or before j (k_win_emit's rescan) and E the frame's end:
-//     LAG(k)       s = j - k, the default when s < P         LEAD(k)  s = j + k, the default when s > E(partition)
-//     FIRST_VALUE  s = P                                     LAST_VALUE  s = j (ROWS) | E(range) | E(partition)
-//     NTILE(n)     r = j - P + 1 of N = E(partition) - P + 1 rows
-// E comes from k_wagg_scan run without an argument (WA_NONE): it leaves tab_c[start] = E - P + 1 at start = P (PARTITION) or
-// Q (RANGE) - one pass per frame the call needs, not per item.  Per distinct argument k_wnav_gather leaves the cells in
-// sorted order (4 or 8 bytes; without keys position = row and the argument is read as it stands), per item k_wnav_emit
-// rescans (p, q), hands them over through LDS, reads cell s and scatters out[perm[j]].  Cells are copied as bits.
-// =====================================================================================================
-template <typename T>
-__global__ void __launch_bounds__(OB_THREADS) k_wnav_gather(const int64_t* perm, const T* values, T* sorted, int64_t n) {
-    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE;
-    int64_t row[WIN_PER];
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {  // consecutive lanes on consecutive positions; nothing past the rows
-        const int64_t j = tile0 + k * OB_THREADS + threadIdx.x;
-        row[k] = j < n ? perm[j] : -1;
-    }
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k)
-        if (row[k] >= 0) sorted[tile0 + k * OB_THREADS + threadIdx.x] = values[row[k]];
-}
-
-struct WnavArgs {
-    const uint8_t* heads;
-    const int64_t* perm;   // null: position = row
-    const int4* carry;     // per tile (k_win_tiles)
-    int64_t n;
-    const void* cells;     // the argument by sorted position (not read by NTILE)
-    const int32_t* tab_c;  // E - P + 1 by the frame's start (LEAD, NTILE: PARTITION; LAST_VALUE: its frame's; else not read)
-    void* out;             // one item per launch: input order
-    uint64_t dflt;         // LAG / LEAD: the default's bits
-    int64_t k;             // LAG / LEAD: the offset; NTILE: the buckets
-    int32_t func, frame;
-};
-static_assert(sizeof(WnavArgs) % 8 == 0, "WnavArgs");
-
-// NTILE: the bucket of row r (1-based) of N rows in n buckets, the first N mod n of them one row larger
-__device__ __forceinline__ uint32_t wnav_ntile(uint32_t r, uint32_t N, uint32_t n) {
-    const uint32_t s = N / n, m = N - s * n, big = m * (s + 1);  // big <= N: no overflow
-    if (r <= big) return (r - 1) / (s + 1) + 1;
-    return m + (r - 1 - big) / (s ? s : 1u) + 1;                 // s == 0: big == N, never here
-}
-
-template <typename T>
-__global__ void __launch_bounds__(OB_THREADS) k_wnav_emit(const WnavArgs A_kernarg) {
-    HS_KERNARG(WnavArgs, A);
-    __shared__ WinS s_wave[OB_WAVES];
-    __shared__ int32_t s_p[OB_TILE + OB_THREADS], s_q[OB_TILE + OB_THREADS];  // k_win_emit's hand-over
-    const int tid = threadIdx.x, func = A.func, frame = A.frame;
-    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE, j0 = tile0 + (int64_t)tid * WIN_PER;
-    const uint64_t bytes = *(const uint64_t*)(A.heads + j0);  // the buffer holds whole tiles
-    WinS acc{-1, -1, 0};
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) acc = win_join(acc, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
-    const int4 c = A.carry[blockIdx.x];
-    WinS total;
-    WinS run = win_join(WinS{c.x, c.y, c.z}, win_block_excl(acc, s_wave, total));
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        run = win_join(run, win_of(win_head(bytes, k, j0, A.n), (int32_t)(j0 + k)));
-        s_p[tid * (WIN_PER + 1) + k] = run.p;
-        s_q[tid * (WIN_PER + 1) + k] = run.q;
-    }
-    __syncthreads();
-    const T* cells = (const T*)A.cells;
-    T* out = (T*)A.out;
-#pragma unroll
-    for (int k = 0; k < WIN_PER; ++k) {
-        const int e = k * OB_THREADS + tid;
-        const int64_t j = tile0 + e;
-        if (j >= A.n) break;
-        const int64_t row = A.perm ? A.perm[j] : j;
-        const int64_t p = s_p[e + e / WIN_PER], q = s_q[e + e / WIN_PER];  // 0 <= p <= q <= j: position 0 is a head
-        if (func == HS_WIN_NTILE) {
-            out[row] = (T)wnav_ntile((uint32_t)(j - p + 1), (uint32_t)A.tab_c[p], (uint32_t)A.k);
-            continue;
-        }
-        int64_t s = j;  // 64 bits: k may be 2^31 - 1
-        bool valid = true;
-        if (func == HS_WIN_LAG) {
-            s = j - A.k;
-            valid = s >= p;
-        } else if (func == HS_WIN_LEAD) {
-            s = j + A.k;
-            valid = s <= p + A.tab_c[p] - 1;
-        } else if (func == HS_WIN_FIRST_VALUE) {
-            s = p;
-        } else if (frame != HS_WIN_FRAME_ROWS) {  // LAST_VALUE: the frame's last row
-            s = p + A.tab_c[frame == HS_WIN_FRAME_RANGE ? q : p] - 1;
-        }
-        out[row] = valid ? cells[s] : (T)A.dflt;  // a valid s lies in the row's partition: inside [0, n)
-    }
-}
-
-static size_t wnav_extra_bytes(int64_t nrows) {  // the cells in sorted order at 8 bytes, two end tables
-    return 8 * win_heads_bytes(nrows) + 2 * rx_align((size_t)nrows * 4);
-}
-
-extern "C" size_t hs_window_nav_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t n_items) {
-    if (nrows < 0) return 0;
-    return hs_window_agg_ws_bytes(nrows, n_keys, max_key_words, n_items) + wnav_extra_bytes(nrows);
-}
-
-static bool wnav_takes_value(int32_t func) { return func >= HS_WIN_LAG && func <= HS_WIN_LAST_VALUE; }
-
-extern "C" int hs_window_nav(void* stream_, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
-                             int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values,
-                             const int64_t* params, const uint64_t* defaults, int32_t n_items, void* const* out, void* ws_,
-                             uint32_t* flags) {
-    int rc = win_refuse("hs_window_nav", keys, n_part, n_keys, nrows, funcs, n_items, out, HS_WIN_NTILE);
-    if (rc != HS_OK) return rc;
-    for (int i = 0; i < n_items; ++i) {
-        const int32_t func = funcs[i];
-        if (func <= HS_WIN_MAX) {
-            if ((rc = wagg_refuse_item("hs_window_nav", i, funcs, frames, values)) != HS_OK) return rc;
-            continue;
-        }
-        if ((func == HS_WIN_FIRST_VALUE || func == HS_WIN_LAST_VALUE) &&
-            (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > HS_WIN_FRAME_ROWS)) {
-            hs_set_error("hs_window_nav: item %d: frame %d is not one of HS_WIN_FRAME_*", i, frames ? frames[i] : -1);
-            return HS_E_ARG;
-        }
-        if (func == HS_WIN_LAG || func == HS_WIN_LEAD || func == HS_WIN_NTILE) {
-            const int64_t least = func == HS_WIN_NTILE ? 1 : 0;
-            const char* what = func == HS_WIN_NTILE ? "the bucket count n" : "the offset k";
-            if (!params) {
-                hs_set_error("hs_window_nav: item %d: %s is missing (params is null)", i, what);
-                return HS_E_ARG;
-            }
-            if (params[i] < least || params[i] >= (1ll << 31)) {
-                hs_set_error("hs_window_nav: item %d: %s is %lld; it lies in [%lld, 2^31)", i, what, (long long)params[i],
-                             (long long)least);
-                return HS_E_ARG;
-            }
-            if (func != HS_WIN_NTILE && !defaults) {
-                hs_set_error("hs_window_nav: item %d: LAG / LEAD need a default cell (defaults is null)", i);
-                return HS_E_ARG;
-            }
-        }
-        if (wnav_takes_value(func) &&
-            (!values || (values[i].kind != HS_I32 && values[i].kind != HS_F32 && values[i].kind != HS_I64))) {
-            hs_set_error("hs_window_nav: item %d: the argument is a column of kind %d (a narrow or virtual column, a STRING, or "
-                         "another type); it takes HS_I32, HS_F32 or HS_I64 cells", i, values ? values[i].kind : -1);
-            return HS_E_ARG;
-        }
-    }
-    if (nrows == 0) return HS_OK;
-    for (int i = 0; i < n_items; ++i)
-        if (((funcs[i] > HS_WIN_COUNT && funcs[i] <= HS_WIN_MAX) || wnav_takes_value(funcs[i])) && !values[i].data) {
-            hs_set_error("hs_window_nav: item %d: the argument column is null", i);
-            return HS_E_ARG;
-        }
-    hipStream_t stream = (hipStream_t)stream_;
-    WinFront F;
-    rc = win_front(stream, "hs_window_nav", keys, descending, n_part, n_keys, nrows, out, n_items, ws_, F);
-    if (rc != HS_OK) return rc;
-    WaggItems W = wagg_items(F, nrows, flags);
-    const dim3 grid((unsigned)F.tiles), block(OB_THREADS);
-    uint8_t* nav = F.rest + wagg_extra_bytes(nrows);
-    void* sorted = nav;
-    int32_t* ends[2] = {(int32_t*)(nav + 8 * win_heads_bytes(nrows)),                                    // PARTITION
-                        (int32_t*)(nav + 8 * win_heads_bytes(nrows) + rx_align((size_t)nrows * 4))};     // RANGE
+    WinEmit E{T};  // the other fields: zero
+    WaggArgs A{T};
+    WnavArgs N{T};
+    A.sorted = (uint32_t*)(base + L.cells4);
+    A.tab_a = (uint64_t*)(base + L.tab_a);
+    A.tab_c = (int32_t*)(base + L.tab_c);
+    A.tiles = (WinA*)(base + L.recs_a);
+    A.flags = flags;
+    void* sorted = base + L.cells8;
+    int32_t* ends[2] = {(int32_t*)(base + L.ends[HS_WIN_FRAME_PARTITION]), (int32_t*)(base + L.ends[HS_WIN_FRAME_RANGE])};
     // the end tables, once per frame some item needs: k_wagg_scan without an argument (its tab_a cells are not used)
-    static_assert(HS_WIN_FRAME_PARTITION == 0 && HS_WIN_FRAME_RANGE == 1, "the end tables are indexed by frame");
     bool needed[2] = {false, false};
     for (int i = 0; i < n_items; ++i) {
         if (funcs[i] == HS_WIN_LEAD || funcs[i] == HS_WIN_NTILE) needed[HS_WIN_FRAME_PARTITION] = true;
@@ -3309,41 +3235,53 @@ extern "C" int hs_window_nav(void* stream_, const hs_col* keys, const int32_t* d
     }
     for (int fr = HS_WIN_FRAME_PARTITION; fr <= HS_WIN_FRAME_RANGE; ++fr) {
         if (!needed[fr]) continue;
-        WaggArgs S = W.A;
+        WaggArgs S = A;
         S.op = WA_NONE;
         S.frame = fr;
         S.tab_c = ends[fr];
         hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, S);
     }
-    WnavArgs N;
-    std::memset(&N, 0, sizeof(N));
-    N.heads = F.heads;
-    N.perm = F.perm;
-    N.carry = F.carry;
-    N.n = nrows;
     uint32_t done = 0;
     for (int i = 0; i < n_items; ++i) {
         if (done & (1u << i)) continue;
-        const int32_t func = funcs[i];
-        if (func <= HS_WIN_MAX) {
-            wagg_item(stream, W, func, frames ? frames[i] : 0, values ? &values[i] : nullptr, out[i]);
+        const int32_t func = funcs[i], frame = frames ? frames[i] : 0;
+        if (func < HS_WIN_COUNT || (func == HS_WIN_COUNT && frame == HS_WIN_FRAME_ROWS)) {
+            E.out = (int32_t*)out[i];
+            E.func = func < HS_WIN_COUNT ? func : HS_WIN_ROW_NUMBER;  // the rows from the partition's first through this one
+            hipLaunchKernelGGL(k_win_emit, grid, block, 0, stream, E);
             continue;
         }
-        const bool wide = wnav_takes_value(func) && values[i].kind == HS_I64;
-        if (wnav_takes_value(func)) {  // the argument in sorted order, once for every item that reads the same cells
+        if (func <= HS_WIN_MAX) {
+            A.func = func;
+            A.frame = frame;
+            A.out = (uint32_t*)out[i];
+            A.op = WA_NONE;
+            if (func != HS_WIN_COUNT) {
+                A.is_float = values[i].kind == HS_F32;
+                A.values = (const uint32_t*)values[i].data;
+                A.op = func == HS_WIN_MIN ? WA_MIN : func == HS_WIN_MAX ? WA_MAX : A.is_float ? WA_ADD_F : WA_ADD_I;
+                hipLaunchKernelGGL(k_wagg_reduce, grid, block, 0, stream, A);
+                hipLaunchKernelGGL(k_win_tiles<WinAOps>, dim3(1), block, 0, stream, A.tiles, tiles, WinAOps{A.op});
+            }
+            hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, A);
+            hipLaunchKernelGGL(k_wagg_emit, grid, block, 0, stream, A);
+            continue;
+        }
+        const bool wide = takes_value(i) && values[i].kind == HS_I64;
+        if (takes_value(i)) {  // the argument in sorted order, once for every item that reads the same cells
             N.cells = values[i].data;
-            if (F.perm) {
+            if (T.perm) {
                 N.cells = sorted;
                 if (wide)
-                    hipLaunchKernelGGL(k_wnav_gather<uint64_t>, grid, block, 0, stream, F.perm, (const uint64_t*)values[i].data,
+                    hipLaunchKernelGGL(k_wnav_gather<uint64_t>, grid, block, 0, stream, T.perm, (const uint64_t*)values[i].data,
                                        (uint64_t*)sorted, nrows);
                 else
-                    hipLaunchKernelGGL(k_wnav_gather<uint32_t>, grid, block, 0, stream, F.perm, (const uint32_t*)values[i].data,
+                    hipLaunchKernelGGL(k_wnav_gather<uint32_t>, grid, block, 0, stream, T.perm, (const uint32_t*)values[i].data,
                                        (uint32_t*)sorted, nrows);
             }
         }
-        for (int t = i; t < n_items; ++t) {  // this item, then the later ones over the same argument
-            if (t > i && (!wnav_takes_value(func) || !wnav_takes_value(funcs[t]) || (done & (1u << t)) ||
+        for (int t = i; t < n_items; ++t) {  // this item, then the later navigation items over the same argument
+            if (t > i && (!takes_value(i) || funcs[t] < HS_WIN_LAG || !takes_value(t) || (done & (1u << t)) ||
                           values[t].data != values[i].data || (values[t].kind == HS_I64) != wide))
                 continue;
             done |= 1u << t;
@@ -3357,8 +3295,30 @@ extern "C" int hs_window_nav(void* stream_, const hs_col* keys, const int32_t* d
             else hipLaunchKernelGGL(k_wnav_emit<uint32_t>, grid, block, 0, stream, N);
         }
     }
-    RX_CHECK_LAUNCH("hs_window_nav (items)");
+    if (hipGetLastError() != hipSuccess) {
+        hs_set_error("%s (%s): kernel launch failed", name, last);
+        return HS_E_LAUNCH;
+    }
     return HS_OK;
+}
+
+extern "C" int hs_window(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
+                         int64_t nrows, const int32_t* funcs, int32_t n_funcs, int32_t* const* out, void* ws, uint32_t* flags) {
+    return win_run("hs_window", "emit", HS_WIN_DENSE_RANK, stream, keys, descending, n_part, n_keys, nrows, funcs, nullptr, nullptr,
+                   nullptr, nullptr, n_funcs, (void* const*)out, ws, flags);
+}
+extern "C" int hs_window_agg(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
+                             int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values, int32_t n_items,
+                             void* const* out, void* ws, uint32_t* flags) {
+    return win_run("hs_window_agg", "items", HS_WIN_MAX, stream, keys, descending, n_part, n_keys, nrows, funcs, frames, values,
+                   nullptr, nullptr, n_items, out, ws, flags);
+}
+extern "C" int hs_window_nav(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
+                             int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values,
+                             const int64_t* params, const uint64_t* defaults, int32_t n_items, void* const* out, void* ws,
+                             uint32_t* flags) {
+    return win_run("hs_window_nav", "items", HS_WIN_NTILE, stream, keys, descending, n_part, n_keys, nrows, funcs, frames, values,
+                   params, defaults, n_items, out, ws, flags);
 }
 
 // out[i] = values[s] for bounds[s] <= i < bounds[s + 1]: a value per segment spread over the segment's rows (the global

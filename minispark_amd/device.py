@@ -1762,7 +1762,6 @@ class Device:
                 if col is None or col.virtual or col.dict is not None or col.kind not in (hs.I32, hs.F32, hs.I64):
                     raise DeviceError(f"the window function {f} takes a stored INTEGER, FLOAT or TIMESTAMP column")
             values.append(col)
-        navigates = any(code >= hs.WIN_LAG for code in codes)
         for code, f, param in zip(codes, funcs, params):
             if code in (hs.WIN_LAG, hs.WIN_LEAD, hs.WIN_NTILE) and param is None:
                 raise DeviceError(f"the window function {f} needs its (k or n, default bits) in params")
@@ -1774,25 +1773,23 @@ class Device:
             desc = (C.c_int32 * max(n_keys, 1))(*([0] * len(part_idx) + [0 if ascending else 1 for _, ascending in order_keys]))
             kinds = (C.c_int32 * len(funcs))(*codes)
             ptrs = (C.c_void_p * len(funcs))(*[o.data_ptr() for o in outs])
-            if all(code <= hs.WIN_DENSE_RANK for code in codes):
-                ws = self.workspace(self._raw_lib.hs_window_ws_bytes(n, n_keys, 32 * max(n_keys, 1)))
-                hs.check(self._raw_lib.hs_window(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, len(funcs), ptrs,
-                                                 ws.data_ptr(), self.flags.data_ptr()), "hs_window")
+            frame_codes = (C.c_int32 * len(funcs))(*[self.WINDOW_FRAMES[f] for f in frames])
+            vals = (hs.hs_col * len(funcs))(*[c.as_hs() if c is not None else hs.hs_col() for c in values])
+            steps = (C.c_int64 * len(funcs))(*[int(p[0]) if p is not None else 0 for p in params])
+            cells = (C.c_uint64 * len(funcs))(*[int(p[1]) if p is not None else 0 for p in params])
+            # the entry by the highest code present: each takes the arrays of the one before and asks for a larger workspace
+            lib, sized = self._raw_lib, (n, n_keys, 32 * max(n_keys, 1))
+            if max(codes) <= hs.WIN_DENSE_RANK:
+                name, ws_bytes, items = "hs_window", lib.hs_window_ws_bytes(*sized), (kinds, len(funcs))
+            elif max(codes) <= hs.WIN_MAX:
+                name, ws_bytes, items = ("hs_window_agg", lib.hs_window_agg_ws_bytes(*sized, len(funcs)),
+                                         (kinds, frame_codes, vals, len(funcs)))
             else:
-                frame_codes = (C.c_int32 * len(funcs))(*[self.WINDOW_FRAMES[f] for f in frames])
-                vals = (hs.hs_col * len(funcs))(*[c.as_hs() if c is not None else hs.hs_col() for c in values])
-                if not navigates:
-                    ws = self.workspace(self._raw_lib.hs_window_agg_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(funcs)))
-                    hs.check(self._raw_lib.hs_window_agg(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, frame_codes,
-                                                         vals, len(funcs), ptrs, ws.data_ptr(), self.flags.data_ptr()),
-                             "hs_window_agg")
-                else:
-                    steps = (C.c_int64 * len(funcs))(*[int(p[0]) if p is not None else 0 for p in params])
-                    cells = (C.c_uint64 * len(funcs))(*[int(p[1]) if p is not None else 0 for p in params])
-                    ws = self.workspace(self._raw_lib.hs_window_nav_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(funcs)))
-                    hs.check(self._raw_lib.hs_window_nav(self.stream, arr, desc, len(part_idx), n_keys, n, kinds, frame_codes,
-                                                         vals, steps, cells, len(funcs), ptrs, ws.data_ptr(),
-                                                         self.flags.data_ptr()), "hs_window_nav")
+                name, ws_bytes, items = ("hs_window_nav", lib.hs_window_nav_ws_bytes(*sized, len(funcs)),
+                                         (kinds, frame_codes, vals, steps, cells, len(funcs)))
+            ws = self.workspace(ws_bytes)
+            hs.check(getattr(lib, name)(self.stream, arr, desc, len(part_idx), n_keys, n, *items, ptrs, ws.data_ptr(),
+                                        self.flags.data_ptr()), name)
         return [DCol(kind, out[:n], n) for kind, out in zip(out_kinds, outs)]
 
     def mark_first(self, batch: DBatch, key_indices: Sequence[int], sel: torch.Tensor | None = None, n_sel: int = 0,

@@ -196,6 +196,41 @@ def test_a_two_word_key_with_a_coded_partition_column_and_a_descending_order_key
             assert np.array_equal(column, np.asarray(want[k])), (frame, k)
 
 
+def test_aggregates_across_a_round_of_the_tile_scan(dev):
+    """The tile-carry kernel takes OB_TILE summaries per round: rows beyond OB_TILE tiles lie in its second round, and the
+    64-bit fold's carry crosses it.  Three partitions in order, the middle one starting in the first round and ending in
+    the second; the order key is the position, so every row is its own peer group and RANGE is ROWS.  Cells in [-3, 3]:
+    no sum leaves i32, and the FLOAT sums (|sum| < 2^24) are exact under any association.  Expected values are numpy's
+    segmented cumsum / accumulate per partition, compared exactly."""
+    n = OB_TILE * OB_TILE + 3 * OB_TILE + 5
+    rng = np.random.default_rng(22)
+    position = np.arange(n)
+    ids = np.where(position < 1000, 0, np.where(position < n - 700, 1, 2))
+    cells = rng.integers(-3, 4, n)
+    cols = [upload(dev, ids, T.INTEGER), upload(dev, position, T.INTEGER)]
+    value, value_f = upload(dev, cells, T.INTEGER), upload(dev, cells.astype(np.float32), T.FLOAT)
+    running = {f: np.empty(n, dtype=np.int64) for f in (COUNT, SUM, MIN, MAX)}
+    whole = {f: np.empty(n, dtype=np.int64) for f in (COUNT, SUM, MIN, MAX)}
+    for lo, hi in ((0, 1000), (1000, n - 700), (n - 700, n)):
+        part = cells[lo:hi]
+        running[COUNT][lo:hi] = np.arange(1, hi - lo + 1)
+        running[SUM][lo:hi] = np.cumsum(part)
+        running[MIN][lo:hi] = np.minimum.accumulate(part)
+        running[MAX][lo:hi] = np.maximum.accumulate(part)
+        for f in running:
+            whole[f][lo:hi] = running[f][hi - 1]
+    for frame in FRAMES:
+        want = whole if frame == "partition" else running
+        items = [(COUNT, frame, None), (SUM, frame, value), (MIN, frame, value), (MAX, frame, value), (SUM, frame, value_f)]
+        rc, got, flags = hs_window_agg(dev, cols, [0, 0], 1, items, n)
+        assert rc == 0 and flags == 0, (dev._raw_lib.hs_last_error(), flags)
+        expected = [want[COUNT], want[SUM], want[MIN], want[MAX], want[SUM].astype(np.float32)]
+        for (f, _, v), column, exp in zip(items, got, expected):
+            bad = np.nonzero(column != exp)[0]
+            assert bad.size == 0, (f"{frame}: function {f} of kind {v.kind if v is not None else None} differs at {bad.size} of "
+                                   f"{n} rows, first row {bad[0]}: got {column[bad[0]]!r}, want {exp[bad[0]]!r}")
+
+
 def test_without_keys_the_rows_frame_is_a_running_sum_in_input_order(dev):
     n = 2 * OB_TILE + 13
     cells = np.random.default_rng(4).integers(-50000, 50001, n)
