@@ -745,6 +745,34 @@ size_t hs_window_nav_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_wor
 int hs_window_nav(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows,
                   const int32_t* funcs, const int32_t* frames, const hs_col* values, const int64_t* params,
                   const uint64_t* defaults, int32_t n_items, void* const* out, void* ws, uint32_t* flags);
+/* Sliding frames next to everything hs_window_nav takes (no reference counterpart): the same arguments, items and frames,
+ * and one frame more,
+ *   HS_WIN_FRAME_BETWEEN  ROWS BETWEEN preceding[i] PRECEDING AND following[i] FOLLOWING: with j the row's place in its
+ *                 partition's order (ties in input order; without an order key: input order), P / L the partition's first /
+ *                 last place, the places [max(P, j - preceding[i]), min(L, j + following[i])].  It holds the row itself:
+ *                 never empty.  0 <= preceding[i], following[i] < 2^31 (0: CURRENT ROW)
+ * for COUNT / SUM / AVG / MIN / MAX - hs_window_agg's value rules word for word: i64 / f64 sums rounded once, the overflow
+ * flags raised on the value emitted, AVG an f64 division by the frame's rows, MIN / MAX in hs_order_by's order, a NaN or an
+ * infinity only in the rows whose frame holds it - and for FIRST_VALUE / LAST_VALUE, which copy the cell at the frame's
+ * first / last place bit for bit.  preceding / following: HOST arrays of n_items entries, read for items of this frame only
+ * (FIRST_VALUE reads preceding alone, LAST_VALUE following alone); each may be null when no item reads it.  The other
+ * entries go on refusing the frame.
+ * Steps: hs_window_nav's; per sliding aggregate item the partitions are cut into blocks of W = preceding + following + 1
+ * places, a forward and a backward segmented scan leave the fold from the block's head through every place and from every
+ * place through the block's end, and a frame - at most W long - is one of the two or one op of both: the cost per row does
+ * not depend on W, and no running fold is ever subtracted from another.  A FLOAT sum's association is fixed by (nrows,
+ * preceding, following, tile geometry): the same bits from run to run, not those of the left-to-right fold.  No atomics on
+ * values.  Refused before anything is launched or any device pointer is read: what hs_window_nav refuses, and with HS_E_ARG
+ * and a text that names the item: an offset outside [0, 2^31), preceding / following null where an item of the frame reads
+ * it, the frame on a function that takes none (ranking, LAG, LEAD, NTILE).  nrows == 0: HS_OK, nothing launched.
+ * Synchronises the stream like hs_window; must not be captured.  ws: hs_window_frames_ws_bytes(...) bytes (hs_window_nav's
+ * + 10 bytes per row + 16 per tile: two rows of head bytes and the backward table; n_items does not enter). */
+#define HS_WIN_FRAME_BETWEEN 3
+size_t hs_window_frames_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t n_items);
+int hs_window_frames(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows,
+                     const int32_t* funcs, const int32_t* frames, const hs_col* values, const int64_t* params,
+                     const uint64_t* defaults, const int64_t* preceding, const int64_t* following, int32_t n_items,
+                     void* const* out, void* ws, uint32_t* flags);
 /* out[i] = values[s] for bounds[s] <= i < bounds[s+1], i in [0, n) (device arrays; bounds has n_seg + 1 entries,
  * bounds[0] = 0): the global block id of every partial row of a multi-rank partial aggregate. */
 int hs_expand_by_bounds(void* stream, const int64_t* bounds, const int64_t* values, int64_t n_seg, int64_t n, int64_t* out);

@@ -2450,8 +2450,9 @@ extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, 
 }
 
 // =====================================================================================================
-// Window functions over result rows (include/hipspark.h hs_window, hs_window_agg, hs_window_nav; the reference has no
-// window functions).  What the three entries share stands here; ranking, aggregates and navigation follow.
+// Window functions over result rows (include/hipspark.h hs_window, hs_window_agg, hs_window_nav, hs_window_frames; the
+// reference has no window functions).  What the four entries share stands here; ranking, aggregates, navigation and the
+// sliding frames follow.
 //
 // ob_sort orders the rows by (partition columns, order keys): a partition is a run of sorted positions, peers are
 // neighbours, and the sort being stable the rows of a group of peers stand in input order.  k_win_heads writes two bits
@@ -2936,8 +2937,8 @@ struct WnavArgs : WinTile {
     const int32_t* tab_c;  // E - P + 1 by the frame's start (LEAD, NTILE: PARTITION; LAST_VALUE: its frame's; else not read)
     void* out;             // one item per launch: input order
     uint64_t dflt;         // LAG / LEAD: the default's bits
-    int64_t k;             // LAG / LEAD: the offset; NTILE: the buckets
-    int32_t func, frame;
+    int64_t k;             // LAG / LEAD: the offset; NTILE: the buckets; FIRST_VALUE / LAST_VALUE under HS_WIN_FRAME_BETWEEN:
+    int32_t func, frame;   // the frame's n PRECEDING / m FOLLOWING (4.4i)
 };
 static_assert(sizeof(WnavArgs) % 8 == 0, "WnavArgs");
 
@@ -2982,7 +2983,10 @@ __global__ void __launch_bounds__(OB_THREADS) k_wnav_emit(const WnavArgs A_kerna
             s = j + A.k;
             valid = s <= p + A.tab_c[p] - 1;
         } else if (func == HS_WIN_FIRST_VALUE) {
-            s = p;
+            s = frame == HS_WIN_FRAME_BETWEEN && j - A.k > p ? j - A.k : p;  // k PRECEDING, clamped to the partition's first row
+        } else if (frame == HS_WIN_FRAME_BETWEEN) {  // LAST_VALUE, k FOLLOWING, clamped to the partition's last row
+            const int64_t last = p + A.tab_c[p] - 1;
+            s = j + A.k < last ? j + A.k : last;
         } else if (frame != HS_WIN_FRAME_ROWS) {  // LAST_VALUE: the frame's last row
             s = p + A.tab_c[frame == HS_WIN_FRAME_RANGE ? q : p] - 1;
         }
@@ -2991,10 +2995,145 @@ __global__ void __launch_bounds__(OB_THREADS) k_wnav_emit(const WnavArgs A_kerna
 }
 
 // -----------------------------------------------------------------------------------------------------
-// The host side of the three entries: one workspace layout, one item table, one run routine.
+// Sliding frames (hs_window_frames).  ROWS BETWEEN n PRECEDING AND m FOLLOWING: per sorted position j the
+// frame is [lo, hi] = [max(P, j - n), min(L, j + m)], P / L the first / last position of j's partition.  Both ends move,
+// so no fold from the partition head answers it, and the difference of two running folds is not taken: it would carry a
+// NaN or an infinity out of its frame (inf - inf) and cancel.  Instead every partition is cut into BLOCKS of
+// W = n + m + 1 positions counted from P - block heads where (j - P) mod W == 0 - and two folds restart at them:
+//     pre[j] = the fold from j's block head through j          (WinA over the block-head bytes, left to right)
+//     suf[j] = the fold from j through the end of j's block    (the same scan over the MIRRORED positions n - 1 - j,
+//                                                               whose heads are the block ends)
+// A frame is at most W long, so it starts at a block head, ends at a block end, or crosses exactly one block boundary:
+//     lo, hi in different blocks: suf[lo] op pre[hi]     same block, lo its head: pre[hi]     else (hi its end): suf[lo]
+// two table reads and one op per row whatever W is, and nothing outside the frame is ever folded in.  COUNT is
+// hi - lo + 1.  L = P + rows - 1 from navigation's PARTITION end table.  W and the positions are 64-bit on the host; on
+// the device W is capped at 2^31 (no partition is longer), which keeps the division at 32 bits.
+// FLOAT sums: pre is joined with the earlier positions on the left at every level, suf with the LATER positions on the
+// left (f64 addition commutes, so only the association differs); the association is fixed by (rows, n, m, tile
+// geometry): the same bits from run to run, not those of the left-to-right fold of the frame.
+// Per item with an argument:
+//   k_wfr_heads    rescans (p, q, d) and writes both head byte rows (kept while the next item has the same W);
+//   k_wnav_gather  the cells in sorted order (32-bit);
+//   k_wfr_reduce   grid.y = direction: a tile's cells, coalesced and across to the lanes through LDS, folded to a summary;
+//   k_win_tiles    over WinA, once per direction;
+//   k_wfr_scan     grid.y = direction: the tile scanned again behind its carry, pre / suf stored per position;
+//   k_wfr_emit     per position: P by rescan, L, lo, hi, the case above, wa_finish, out[perm[j]] - one launch per item.
+// FIRST_VALUE / LAST_VALUE read the sorted cell at lo / hi in k_wnav_emit.  No atomics on values, no scratch.
+// -----------------------------------------------------------------------------------------------------
+struct WfrArgs : WinTile {
+    const int32_t* part_rows;  // the partition's rows by its head position (navigation's PARTITION end table)
+    const uint32_t* sorted;    // the argument's cells by sorted position: exactly n of them
+    uint8_t* bheads[2];        // block heads by position / block ends by mirrored position, bit 1, whole tiles
+    WinA* tiles[2];            // per tile and direction: k_wfr_reduce's summary, then k_win_tiles' carry
+    uint64_t* tab[2];          // pre / suf by sorted position
+    uint32_t* out;             // one item per launch: input order
+    uint32_t* flags;           // may be null
+    int64_t preceding, following;
+    uint32_t width;            // min(W, 2^31)
+    int32_t op, is_float, func;
+};
+static_assert(sizeof(WfrArgs) % 8 == 0, "WfrArgs");
+
+__global__ void __launch_bounds__(OB_THREADS) k_wfr_heads(const WfrArgs A_kernarg) {
+    HS_KERNARG(WfrArgs, A);
+    __shared__ WinS s_wave[OB_WAVES];
+    const int64_t j0 = (int64_t)blockIdx.x * OB_TILE + (int64_t)threadIdx.x * WIN_PER;
+    uint64_t fwd = 0;
+    win_rescan(A.heads, A.carry[blockIdx.x], A.n, s_wave, [&](int k, const WinS run) {
+        const int64_t j = j0 + k;
+        const uint8_t head = (uint32_t)(j - run.p) % A.width == 0 ? 2 : 0;
+        fwd |= (uint64_t)head << (8 * k);
+        // position j - 1 ends a block where j starts one, and so does the last row: mirrored, those are the heads
+        if (j > 0) A.bheads[1][A.n - j] = head;
+        else A.bheads[1][0] = 2;
+    });
+    if (j0 < A.n) *(uint64_t*)(A.bheads[0] + j0) = fwd;  // whole tiles: the bytes past the rows are not looked at
+}
+
+// the cells of the lane's WIN_PER scan positions in direction `dir` (1: mirrored), zero past the rows
+__device__ __forceinline__ void wfr_cells(const WfrArgs& A, int dir, uint32_t* s_v, uint32_t (&cell)[WIN_PER]) {
+    const int tid = threadIdx.x;
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t t = tile0 + e;
+        s_v[win_get_at(e)] = t < A.n ? A.sorted[dir ? A.n - 1 - t : t] : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) cell[k] = s_v[win_put_at(tid, k)];
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_wfr_reduce(const WfrArgs A_kernarg) {
+    HS_KERNARG(WfrArgs, A);
+    __shared__ WinA s_wave[OB_WAVES];
+    __shared__ uint32_t s_v[OB_TILE + OB_THREADS];
+    const int dir = blockIdx.y;
+    const WinAOps o{A.op};
+    uint32_t cell[WIN_PER];
+    wfr_cells(A, dir, s_v, cell);
+    const WinLane L = win_lane(A.bheads[dir], A.n);
+    uint64_t x[WIN_PER];
+    wa_lift_lane(o.op, A.is_float, L, [&](int k) { return cell[k]; }, x);
+    WinA total;
+    win_block_excl(o, win_fold_lane(o, L, [&](int k) { return x[k]; }), s_wave, total);
+    if (threadIdx.x == 0) A.tiles[dir][blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_wfr_scan(const WfrArgs A_kernarg) {
+    HS_KERNARG(WfrArgs, A);
+    __shared__ WinA s_wave[OB_WAVES];
+    __shared__ uint32_t s_v[OB_TILE + OB_THREADS];
+    const int dir = blockIdx.y;
+    const WinAOps o{A.op};
+    uint32_t cell[WIN_PER];
+    wfr_cells(A, dir, s_v, cell);
+    const WinLane L = win_lane(A.bheads[dir], A.n);
+    uint64_t x[WIN_PER];
+    wa_lift_lane(o.op, A.is_float, L, [&](int k) { return cell[k]; }, x);
+    uint64_t* tab = A.tab[dir];
+    win_rescan_lane(o, L, [&](int k) { return x[k]; }, A.tiles[dir][blockIdx.x], s_wave, [&](int k, const WinA run) {
+        const int64_t t = L.j0 + k;  // a row: t < n
+        tab[dir ? A.n - 1 - t : t] = run.a;
+    });
+}
+
+__global__ void __launch_bounds__(OB_THREADS) k_wfr_emit(const WfrArgs A_kernarg) {
+    HS_KERNARG(WfrArgs, A);
+    __shared__ WinS s_wave[OB_WAVES];
+    __shared__ int32_t s_p[OB_TILE + OB_THREADS];
+    const int tid = threadIdx.x;
+    const int64_t tile0 = (int64_t)blockIdx.x * OB_TILE;
+    win_rescan(A.heads, A.carry[blockIdx.x], A.n, s_wave, [&](int k, const WinS run) { s_p[win_put_at(tid, k)] = run.p; });
+    __syncthreads();
+    uint32_t err = 0;
+#pragma unroll
+    for (int k = 0; k < WIN_PER; ++k) {
+        const int e = k * OB_THREADS + tid;
+        const int64_t j = tile0 + e;
+        if (j < A.n) {
+            const int64_t row = A.perm ? A.perm[j] : j;
+            const int64_t p = s_p[win_get_at(e)], last = p + A.part_rows[p] - 1;  // p <= j <= last < n
+            const int64_t lo = j - A.preceding > p ? j - A.preceding : p, hi = j + A.following < last ? j + A.following : last;
+            uint64_t a = 0;
+            if (A.op != WA_NONE) {
+                const uint32_t at = (uint32_t)(lo - p), block = at / A.width;
+                if ((uint64_t)(hi - p) >= ((uint64_t)block + 1) * A.width) a = wa_op(A.op, A.tab[1][lo], A.tab[0][hi]);
+                else a = at == block * A.width ? A.tab[0][hi] : A.tab[1][lo];
+            }
+            A.out[row] = wa_finish(A.func, A.is_float, a, (int32_t)(hi - lo + 1), err);
+        }
+    }
+    if (err && A.flags) atomicOr(A.flags, err);
+}
+
+// -----------------------------------------------------------------------------------------------------
+// The host side of the four entries: one workspace layout, one item table, one run routine.
 // -----------------------------------------------------------------------------------------------------
 // Where everything lies behind the sort's workspace, and where each entry's share of it ends: hs_window's, then what
-// hs_window_agg adds, then what hs_window_nav adds.  The items of a call run one after the other over the same regions.
+// hs_window_agg adds, then what hs_window_nav adds, then what hs_window_frames adds.  The items of a call run one after
+// the other over the same regions.
 struct WinLayout {
     size_t heads;    // a head byte per sorted position, whole tiles
     size_t recs;     // a (p, q, d) record per tile, and one more
@@ -3007,6 +3146,10 @@ struct WinLayout {
     size_t cells8;   // an argument's cells by sorted position at 8 bytes, whole tiles
     size_t ends[2];  // the frames' rows by their start position: PARTITION, RANGE
     size_t nav_end;
+    size_t bheads[2];  // sliding frames: block heads by position, block ends by mirrored position, whole tiles
+    size_t suf;        // ... the backward fold by position (the forward one lies in tab_a)
+    size_t recs_b;     // ... a WinA record per tile of the backward scan, and one more (the forward ones in recs_a)
+    size_t frames_end;
 };
 static_assert(HS_WIN_FRAME_PARTITION == 0 && HS_WIN_FRAME_RANGE == 1, "the end tables are indexed by frame");
 static WinLayout win_layout(int64_t nrows) {
@@ -3030,6 +3173,11 @@ static WinLayout win_layout(int64_t nrows) {
     L.ends[HS_WIN_FRAME_PARTITION] = take(rx_align((size_t)nrows * 4));
     L.ends[HS_WIN_FRAME_RANGE] = take(rx_align((size_t)nrows * 4));
     L.nav_end = at;
+    L.bheads[0] = take(whole);
+    L.bheads[1] = take(whole);
+    L.suf = take(rx_align((size_t)nrows * 8));
+    L.recs_b = take(rx_align((tiles + 1) * sizeof(WinA)));
+    L.frames_end = at;
     return L;
 }
 
@@ -3045,6 +3193,9 @@ extern "C" size_t hs_window_agg_ws_bytes(int64_t nrows, int32_t n_keys, int32_t 
 }
 extern "C" size_t hs_window_nav_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t) {
     return win_ws_bytes(nrows, n_keys, max_key_words, &WinLayout::nav_end);
+}
+extern "C" size_t hs_window_frames_ws_bytes(int64_t nrows, int32_t n_keys, int32_t max_key_words, int32_t) {
+    return win_ws_bytes(nrows, n_keys, max_key_words, &WinLayout::frames_end);
 }
 
 // What an item of each HS_WIN_* code takes beside the keys
@@ -3111,14 +3262,46 @@ static int win_refuse(const char* name, const hs_col* keys, int32_t n_part, int3
     return HS_OK;
 }
 
-// What item i needs by WIN_ITEMS, behind win_refuse: its frame, its parameter, its argument's kind, in this order.
-// Nothing is launched, no device pointer read.
-static int win_refuse_item(const char* name, int i, const int32_t* funcs, const int32_t* frames, const hs_col* values,
-                           const int64_t* params, const uint64_t* defaults) {
+// Does item i slide (HS_WIN_FRAME_BETWEEN, in the entry that takes it: the others do not look at the frame of a function
+// without one), and which of the frame's two offsets does it read?  FIRST_VALUE looks at the frame's first row only,
+// LAST_VALUE at its last.
+static bool win_slides(int32_t max_frame, const int32_t* frames, int i) {
+    return max_frame == HS_WIN_FRAME_BETWEEN && frames && frames[i] == HS_WIN_FRAME_BETWEEN;
+}
+static bool win_reads_preceding(int32_t func) { return func != HS_WIN_LAST_VALUE; }
+static bool win_reads_following(int32_t func) { return func != HS_WIN_FIRST_VALUE; }
+
+// What item i needs by WIN_ITEMS, behind win_refuse: its frame (up to the entry's `max_frame`) and a sliding frame's
+// offsets, its parameter, its argument's kind, in this order.  Nothing is launched, no device pointer read.
+static int win_refuse_item(const char* name, int i, const int32_t* funcs, const int32_t* frames, int32_t max_frame,
+                           const hs_col* values, const int64_t* params, const uint64_t* defaults, const int64_t* preceding,
+                           const int64_t* following) {
     const WinItem& item = WIN_ITEMS[funcs[i]];
-    if (item.frame && (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > HS_WIN_FRAME_ROWS)) {
+    if (item.frame && (!frames || frames[i] < HS_WIN_FRAME_PARTITION || frames[i] > max_frame)) {
         hs_set_error("%s: item %d: frame %d is not one of HS_WIN_FRAME_*", name, i, frames ? frames[i] : -1);
         return HS_E_ARG;
+    }
+    if (win_slides(max_frame, frames, i)) {
+        if (!item.frame) {
+            hs_set_error("%s: item %d: frame %d on function %d, which takes no frame", name, i, frames[i], funcs[i]);
+            return HS_E_ARG;
+        }
+        const struct {
+            bool read;
+            const int64_t* at;
+            const char* what;
+        } ends[2] = {{win_reads_preceding(funcs[i]), preceding, "preceding"}, {win_reads_following(funcs[i]), following, "following"}};
+        for (const auto& end : ends) {
+            if (!end.read) continue;
+            if (!end.at) {
+                hs_set_error("%s: item %d: frame %d needs its offset (%s is null)", name, i, frames[i], end.what);
+                return HS_E_ARG;
+            }
+            if (end.at[i] < 0 || end.at[i] >= (1ll << 31)) {
+                hs_set_error("%s: item %d: %s is %lld; it lies in [0, 2^31)", name, i, end.what, (long long)end.at[i]);
+                return HS_E_ARG;
+            }
+        }
     }
     if (item.param != WI_PARAM_NONE) {
         const int64_t least = item.param == WI_PARAM_BUCKETS ? 1 : 0;
@@ -3148,18 +3331,20 @@ static int win_refuse_item(const char* name, int i, const int32_t* funcs, const 
     return HS_OK;
 }
 
-// The three entries: `max_func` the highest HS_WIN_* code the entry takes, `last` what it calls its launches behind the front
-// half; an entry passes null for the arrays it does not have.  ONE sort, ONE heads pass and ONE (p, q, d) tile carry for
+// The four entries: `max_func` / `max_frame` the highest HS_WIN_* / HS_WIN_FRAME_* code the entry takes, `last` what it calls
+// its launches behind the front half; an entry passes null for the arrays it does not have.  ONE sort, ONE heads pass and ONE (p, q, d) tile carry for
 // all items of a call, then the items one after the other.  An entry's workspace ends with its share of WinLayout:
 // pointers into the regions behind it are formed here and not used, no item of the entry reaching them.
-static int win_run(const char* name, const char* last, int32_t max_func, void* stream_, const hs_col* keys,
+static int win_run(const char* name, const char* last, int32_t max_func, int32_t max_frame, void* stream_, const hs_col* keys,
                    const int32_t* descending, int32_t n_part, int32_t n_keys, int64_t nrows, const int32_t* funcs,
-                   const int32_t* frames, const hs_col* values, const int64_t* params, const uint64_t* defaults, int32_t n_items,
-                   void* const* out, void* ws_, uint32_t* flags) {
+                   const int32_t* frames, const hs_col* values, const int64_t* params, const uint64_t* defaults,
+                   const int64_t* preceding, const int64_t* following, int32_t n_items, void* const* out, void* ws_,
+                   uint32_t* flags) {
     int rc = win_refuse(name, keys, n_part, n_keys, nrows, funcs, n_items, out, max_func);
     if (rc != HS_OK) return rc;
     for (int i = 0; i < n_items; ++i)
-        if ((rc = win_refuse_item(name, i, funcs, frames, values, params, defaults)) != HS_OK) return rc;
+        if ((rc = win_refuse_item(name, i, funcs, frames, max_frame, values, params, defaults, preceding, following)) != HS_OK)
+            return rc;
     if (nrows == 0) return HS_OK;
     const auto takes_value = [&](int i) { return WIN_ITEMS[funcs[i]].arg != WI_ARG_NONE; };
     for (int i = 0; i < n_items; ++i)
@@ -3231,8 +3416,16 @@ static int win_run(const char* name, const char* last, int32_t max_func, void* s
     bool needed[2] = {false, false};
     for (int i = 0; i < n_items; ++i) {
         if (funcs[i] == HS_WIN_LEAD || funcs[i] == HS_WIN_NTILE) needed[HS_WIN_FRAME_PARTITION] = true;
-        if (funcs[i] == HS_WIN_LAST_VALUE && frames[i] != HS_WIN_FRAME_ROWS) needed[frames[i]] = true;
+        if (win_slides(max_frame, frames, i)) needed[HS_WIN_FRAME_PARTITION] |= funcs[i] != HS_WIN_FIRST_VALUE;  // the frame's clamp
+        else if (funcs[i] == HS_WIN_LAST_VALUE && frames[i] != HS_WIN_FRAME_ROWS) needed[frames[i]] = true;
     }
+    WfrArgs F{T};
+    F.part_rows = ends[HS_WIN_FRAME_PARTITION];
+    F.bheads[0] = base + L.bheads[0], F.bheads[1] = base + L.bheads[1];
+    F.tiles[0] = A.tiles, F.tiles[1] = (WinA*)(base + L.recs_b);
+    F.tab[0] = A.tab_a, F.tab[1] = (uint64_t*)(base + L.suf);
+    F.flags = flags;
+    const dim3 both((unsigned)tiles, 2);  // the forward and the backward scan of a sliding item
     for (int fr = HS_WIN_FRAME_PARTITION; fr <= HS_WIN_FRAME_RANGE; ++fr) {
         if (!needed[fr]) continue;
         WaggArgs S = A;
@@ -3249,6 +3442,34 @@ static int win_run(const char* name, const char* last, int32_t max_func, void* s
             E.out = (int32_t*)out[i];
             E.func = func < HS_WIN_COUNT ? func : HS_WIN_ROW_NUMBER;  // the rows from the partition's first through this one
             hipLaunchKernelGGL(k_win_emit, grid, block, 0, stream, E);
+            continue;
+        }
+        if (func <= HS_WIN_MAX && win_slides(max_frame, frames, i)) {
+            F.func = func;
+            F.out = (uint32_t*)out[i];
+            F.preceding = preceding[i], F.following = following[i];
+            F.op = WA_NONE;
+            if (func != HS_WIN_COUNT) {
+                const int64_t w = preceding[i] + following[i] + 1;  // up to 2^32 - 1
+                const uint32_t width = (uint32_t)(w < (1ll << 31) ? w : (1ll << 31));
+                if (width != F.width) {  // the head bytes of the item before hold for the same W
+                    F.width = width;
+                    hipLaunchKernelGGL(k_wfr_heads, grid, block, 0, stream, F);
+                }
+                F.is_float = values[i].kind == HS_F32;
+                F.op = func == HS_WIN_MIN ? WA_MIN : func == HS_WIN_MAX ? WA_MAX : F.is_float ? WA_ADD_F : WA_ADD_I;
+                F.sorted = (const uint32_t*)values[i].data;
+                if (T.perm) {
+                    F.sorted = A.sorted;
+                    hipLaunchKernelGGL(k_wnav_gather<uint32_t>, grid, block, 0, stream, T.perm, (const uint32_t*)values[i].data,
+                                       A.sorted, nrows);
+                }
+                hipLaunchKernelGGL(k_wfr_reduce, both, block, 0, stream, F);
+                hipLaunchKernelGGL(k_win_tiles<WinAOps>, dim3(1), block, 0, stream, F.tiles[0], tiles, WinAOps{F.op});
+                hipLaunchKernelGGL(k_win_tiles<WinAOps>, dim3(1), block, 0, stream, F.tiles[1], tiles, WinAOps{F.op});
+                hipLaunchKernelGGL(k_wfr_scan, both, block, 0, stream, F);
+            }
+            hipLaunchKernelGGL(k_wfr_emit, grid, block, 0, stream, F);
             continue;
         }
         if (func <= HS_WIN_MAX) {
@@ -3288,6 +3509,7 @@ static int win_run(const char* name, const char* last, int32_t max_func, void* s
             N.func = funcs[t];
             N.frame = frames ? frames[t] : 0;
             N.k = params ? params[t] : 0;
+            if (win_slides(max_frame, frames, t)) N.k = N.func == HS_WIN_FIRST_VALUE ? preceding[t] : following[t];
             N.dflt = defaults ? defaults[t] : 0;
             N.tab_c = ends[N.func == HS_WIN_LAST_VALUE && N.frame == HS_WIN_FRAME_RANGE ? 1 : 0];
             N.out = out[t];
@@ -3304,21 +3526,28 @@ static int win_run(const char* name, const char* last, int32_t max_func, void* s
 
 extern "C" int hs_window(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
                          int64_t nrows, const int32_t* funcs, int32_t n_funcs, int32_t* const* out, void* ws, uint32_t* flags) {
-    return win_run("hs_window", "emit", HS_WIN_DENSE_RANK, stream, keys, descending, n_part, n_keys, nrows, funcs, nullptr, nullptr,
-                   nullptr, nullptr, n_funcs, (void* const*)out, ws, flags);
+    return win_run("hs_window", "emit", HS_WIN_DENSE_RANK, HS_WIN_FRAME_ROWS, stream, keys, descending, n_part, n_keys, nrows, funcs,
+                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_funcs, (void* const*)out, ws, flags);
 }
 extern "C" int hs_window_agg(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
                              int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values, int32_t n_items,
                              void* const* out, void* ws, uint32_t* flags) {
-    return win_run("hs_window_agg", "items", HS_WIN_MAX, stream, keys, descending, n_part, n_keys, nrows, funcs, frames, values,
-                   nullptr, nullptr, n_items, out, ws, flags);
+    return win_run("hs_window_agg", "items", HS_WIN_MAX, HS_WIN_FRAME_ROWS, stream, keys, descending, n_part, n_keys, nrows, funcs,
+                   frames, values, nullptr, nullptr, nullptr, nullptr, n_items, out, ws, flags);
 }
 extern "C" int hs_window_nav(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
                              int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values,
                              const int64_t* params, const uint64_t* defaults, int32_t n_items, void* const* out, void* ws,
                              uint32_t* flags) {
-    return win_run("hs_window_nav", "items", HS_WIN_NTILE, stream, keys, descending, n_part, n_keys, nrows, funcs, frames, values,
-                   params, defaults, n_items, out, ws, flags);
+    return win_run("hs_window_nav", "items", HS_WIN_NTILE, HS_WIN_FRAME_ROWS, stream, keys, descending, n_part, n_keys, nrows, funcs,
+                   frames, values, params, defaults, nullptr, nullptr, n_items, out, ws, flags);
+}
+extern "C" int hs_window_frames(void* stream, const hs_col* keys, const int32_t* descending, int32_t n_part, int32_t n_keys,
+                                int64_t nrows, const int32_t* funcs, const int32_t* frames, const hs_col* values,
+                                const int64_t* params, const uint64_t* defaults, const int64_t* preceding,
+                                const int64_t* following, int32_t n_items, void* const* out, void* ws, uint32_t* flags) {
+    return win_run("hs_window_frames", "items", HS_WIN_NTILE, HS_WIN_FRAME_BETWEEN, stream, keys, descending, n_part, n_keys, nrows,
+                   funcs, frames, values, params, defaults, preceding, following, n_items, out, ws, flags);
 }
 
 // out[i] = values[s] for bounds[s] <= i < bounds[s + 1]: a value per segment spread over the segment's rows (the global

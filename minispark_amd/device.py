@@ -1708,11 +1708,12 @@ class Device:
                     "lag": hs.WIN_LAG, "lead": hs.WIN_LEAD, "first_value": hs.WIN_FIRST_VALUE,
                     "last_value": hs.WIN_LAST_VALUE, "ntile": hs.WIN_NTILE}
     WINDOW_FRAMES = {None: hs.WIN_FRAME_PARTITION, "partition": hs.WIN_FRAME_PARTITION, "range": hs.WIN_FRAME_RANGE,
-                     "rows": hs.WIN_FRAME_ROWS}
+                     "rows": hs.WIN_FRAME_ROWS, "between": hs.WIN_FRAME_BETWEEN}
 
     def window(self, batch: DBatch, part_idx: Sequence[int], order_keys: Sequence[tuple[int, bool]], funcs: Sequence[str],
                frames: Sequence[str | None] | None = None, value_idx: Sequence[int | None] | None = None,
-               params: Sequence[tuple[int, int] | None] | None = None) -> list[DCol]:
+               params: Sequence[tuple[int, int] | None] | None = None,
+               offsets: Sequence[tuple[int, int] | None] | None = None) -> list[DCol]:
         """The window items ``funcs`` over the rows of ``batch`` -> one column per item, in INPUT order: no row moves.
         ``part_idx`` = the PARTITION BY columns, ``order_keys`` = (column, ascending) pairs of the window's ORDER BY; all
         items share the one sort.  ROW_NUMBER / RANK / DENSE_RANK give INTEGER columns; when every item is one of them the
@@ -1723,7 +1724,9 @@ class Device:
         item ("lag", "lead", "first_value", "last_value", "ntile") makes the call hs_window_nav's, which takes every item:
         its argument (INTEGER, FLOAT or TIMESTAMP; None for "ntile") is in ``value_idx``, the frame of "first_value" /
         "last_value" in ``frames``, and ``params`` holds (k, the default cell's bits) for "lag" / "lead" and (n, 0) for
-        "ntile"; the column has the argument's kind, INTEGER for "ntile".  Equality
+        "ntile"; the column has the argument's kind, INTEGER for "ntile".  An aggregate, "first_value" or "last_value" whose
+        frame is "between" (ROWS BETWEEN n PRECEDING AND m FOLLOWING) has its (n, m) in ``offsets``, and the
+        call is hs_window_frames', which takes every item; without such an item the call is the one it was.  Equality
         and order are ``distinct``'s and ``order_by``'s.  A dictionary-coded column goes as its code byte where it only
         partitions (one code, one string) or where the dictionary is sorted, decoded otherwise, as in ``order_by``.  The
         call learns sizes on the host between its steps, so a run that contains it is not replayable."""
@@ -1762,6 +1765,10 @@ class Device:
                 if col is None or col.virtual or col.dict is not None or col.kind not in (hs.I32, hs.F32, hs.I64):
                     raise DeviceError(f"the window function {f} takes a stored INTEGER, FLOAT or TIMESTAMP column")
             values.append(col)
+        offsets = list(offsets) if offsets is not None else [None] * len(funcs)
+        for f, frame, offset in zip(funcs, frames, offsets):
+            if (frame == "between") != (offset is not None):
+                raise DeviceError(f'the window function {f}: the frame "between" and its (n, m) in offsets come together')
         for code, f, param in zip(codes, funcs, params):
             if code in (hs.WIN_LAG, hs.WIN_LEAD, hs.WIN_NTILE) and param is None:
                 raise DeviceError(f"the window function {f} needs its (k or n, default bits) in params")
@@ -1779,7 +1786,12 @@ class Device:
             cells = (C.c_uint64 * len(funcs))(*[int(p[1]) if p is not None else 0 for p in params])
             # the entry by the highest code present: each takes the arrays of the one before and asks for a larger workspace
             lib, sized = self._raw_lib, (n, n_keys, 32 * max(n_keys, 1))
-            if max(codes) <= hs.WIN_DENSE_RANK:
+            if "between" in frames:
+                before = (C.c_int64 * len(funcs))(*[int(o[0]) if o is not None else 0 for o in offsets])
+                after = (C.c_int64 * len(funcs))(*[int(o[1]) if o is not None else 0 for o in offsets])
+                name, ws_bytes, items = ("hs_window_frames", lib.hs_window_frames_ws_bytes(*sized, len(funcs)),
+                                         (kinds, frame_codes, vals, steps, cells, before, after, len(funcs)))
+            elif max(codes) <= hs.WIN_DENSE_RANK:
                 name, ws_bytes, items = "hs_window", lib.hs_window_ws_bytes(*sized), (kinds, len(funcs))
             elif max(codes) <= hs.WIN_MAX:
                 name, ws_bytes, items = ("hs_window_agg", lib.hs_window_agg_ws_bytes(*sized, len(funcs)),

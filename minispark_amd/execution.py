@@ -771,7 +771,7 @@ class HipExecutionEngine(ExecutionEngine):
         return self.dev.gather_batch(batch, perm, count)
 
     def _window_rows(self, batch: Any, sort: Any) -> Any:
-        """Window items, the first step of a windowed SortTask (DESIGN.md 4.4f - 4.4h): the rounded result rows gain one
+        """Window items, the first step of a windowed SortTask (DESIGN.md 4.4f - 4.4i): the rounded result rows gain one
         column per item - items with one (partition, order) spec share one sort and one launch sequence
         (Device.window) - the column handles are placed in the task's output order (no row is copied), and QUALIFY
         filters the rows through the WHERE machinery.  Keys are found by POSITION in the task's input schema."""
@@ -795,6 +795,9 @@ class HipExecutionEngine(ExecutionEngine):
                          [None if item.arg is None else in_names.index(item.arg.name) for item in items])
             if any(item.kind in item.NAVIGATION for item in items):  # (k, the default as a cell's bits) or (n, 0)
                 extra = (*extra, [self._window_param(item, in_schema) for item in items])
+            if any(item.frame == "between" for item in items):  # (n PRECEDING, m FOLLOWING) of the sliding items
+                extra = (*extra, *[None] * (3 - len(extra)),
+                         [(item.preceding, item.following) if item.frame == "between" else None for item in items])
             for item, col in zip(items, self.dev.window(batch, part, order, [item.kind for item in items], *extra)):
                 by_name[item.name] = col
         out_schema = list(sort.inferred_schema)

@@ -53,6 +53,7 @@ WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK = 0, 1, 2  # hs_window's functions
 WIN_COUNT, WIN_SUM, WIN_AVG, WIN_MIN, WIN_MAX = 3, 4, 5, 6, 7  # hs_window_agg's further functions ...
 WIN_FRAME_PARTITION, WIN_FRAME_RANGE, WIN_FRAME_ROWS = 0, 1, 2  # ... and their frames
 WIN_LAG, WIN_LEAD, WIN_FIRST_VALUE, WIN_LAST_VALUE, WIN_NTILE = 8, 9, 10, 11, 12  # hs_window_nav's further functions
+WIN_FRAME_BETWEEN = 3  # hs_window_frames' further frame: ROWS BETWEEN n PRECEDING AND m FOLLOWING
 WIN_MAX_FUNCS = 8
 
 # opcodes
@@ -383,6 +384,8 @@ SIGNATURES: dict[str, tuple] = {
     "hs_window_agg": (C.c_int, [_P, _COLP, _P, _I32, _I32, _I64, _P, _P, _COLP, _I32, _P, _P, _P]),
     "hs_window_nav_ws_bytes": (C.c_size_t, [_I64, _I32, _I32, _I32]),
     "hs_window_nav": (C.c_int, [_P, _COLP, _P, _I32, _I32, _I64, _P, _P, _COLP, _P, _P, _I32, _P, _P, _P]),
+    "hs_window_frames_ws_bytes": (C.c_size_t, [_I64, _I32, _I32, _I32]),
+    "hs_window_frames": (C.c_int, [_P, _COLP, _P, _I32, _I32, _I64, _P, _P, _COLP, _P, _P, _P, _P, _I32, _P, _P, _P]),
     "hs_expand_by_bounds": (C.c_int, [_P, _P, _P, _I64, _I64, _P]),
     "hs_group_mask": (C.c_int, [_P, _P, _I64, _P]),
     "hs_group_fold": (C.c_int, [_P, _COLP, _SPECP, _P, _I64, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),

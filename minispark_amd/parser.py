@@ -32,6 +32,10 @@ A hand-written backtracking recursive-descent parser for the same language:
                                                                  [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] )  [AS alias]
                     SUM(name) | AVG(name) | MIN(name) | MAX(name) | COUNT()  OVER ( [PARTITION BY ...] [ORDER BY ...] [frame] )
                     frame:  ROWS | RANGE  [BETWEEN]  UNBOUNDED PRECEDING  [AND CURRENT ROW]         [AS alias]
+                         |  ROWS BETWEEN (n PRECEDING | CURRENT ROW) AND (m FOLLOWING | CURRENT ROW)
+                            (n, m: integer literals below 2^31; BETWEEN mandatory, both ends finite:
+                            ROWS 3 PRECEDING, an UNBOUNDED end next to a finite one, GROUPS and a RANGE of values stay
+                            syntax errors)
                     LAG(name, k, default) | LEAD(name, k, default) | NTILE(n)  OVER ( [PARTITION BY ...] [ORDER BY ...] )
                     FIRST_VALUE(name) | LAST_VALUE(name)  OVER ( [PARTITION BY ...] [ORDER BY ...] [frame] )   [AS alias]
                     (k, n: integer literals; default: an integer, a decimal - either may be negative -
@@ -380,8 +384,34 @@ class _Parser:
             cols += self.repeat(lambda: (self.ows(), self.lit(","), self.ows(), self.column_name())[3])
             return cols
 
-        def frame() -> str:
-            """ROWS | RANGE  [BETWEEN]  UNBOUNDED PRECEDING  [AND CURRENT ROW]: the only frame there is"""
+        def sliding() -> tuple[int, int]:
+            """ROWS BETWEEN (n PRECEDING | CURRENT ROW) AND (m FOLLOWING | CURRENT ROW) -> (n, m): both ends finite, BETWEEN
+            mandatory"""
+            def end(side: str) -> int:
+                has_current, _ = self.attempt(lambda: (self.lit("CURRENT"), self.ws(), self.lit("ROW")))
+                if has_current:
+                    return 0
+                digits = self.rx(_DIGITS)
+                self.ws()
+                self.lit(side)
+                return int(digits)
+
+            self.lit("ROWS")
+            self.ws()
+            self.lit("BETWEEN")
+            self.ws()
+            n = end("PRECEDING")
+            self.ws()
+            self.lit("AND")
+            self.ws()
+            return n, end("FOLLOWING")
+
+        def frame() -> Any:
+            """ROWS | RANGE  [BETWEEN]  UNBOUNDED PRECEDING  [AND CURRENT ROW] -> the unit, or the sliding frame -> what
+            ``over(rows=)`` takes for it, (n, m): the only frames there are"""
+            has_sliding, between = self.attempt(sliding)
+            if has_sliding:
+                return between
             unit = self.first_of(lambda: self.lit("ROWS"), lambda: self.lit("RANGE"))
             self.ws()
             self.attempt(lambda: (self.lit("BETWEEN"), self.ws()))
@@ -403,6 +433,9 @@ class _Parser:
         self.ows()
         self.lit(")")
         keys = dict(partition_by=part if has_partition else [], order_by=order if has_order else [])
+        rows: Any = has_frame and unit == "ROWS"  # what over(rows=) takes: True, False or the sliding frame's (n, m)
+        if has_frame and type(unit) is tuple:
+            rows, unit = unit, "ROWS BETWEEN"
         if ranking:
             if has_frame:
                 raise ValueError(f"{name}() takes no frame clause ({unit} ...): a rank is a property of the row's place in its "
@@ -420,11 +453,11 @@ class _Parser:
             if has_frame and name in ("LAG", "LEAD", "NTILE"):
                 raise ValueError(f"{name}() takes no frame clause ({unit} ...): it is a property of the row's place in its "
                                  "partition, not of a frame")
-            item = item.over(**keys, rows=has_frame and unit == "ROWS")
+            item = item.over(**keys, rows=rows)
         else:
             agg = F.count() if name == "COUNT" else {"SUM": F.sum, "AVG": F.avg, "MIN": F.min, "MAX": F.max}[name](arg)
             # RANGE is the default frame: through the last peer, which without ORDER BY is the whole partition
-            item = agg.over(**keys, rows=has_frame and unit == "ROWS")
+            item = agg.over(**keys, rows=rows)
         has_alias, alias = self.attempt(self.alias)
         self.saw_window_item = True
         return item.alias(alias) if has_alias else item

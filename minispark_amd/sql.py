@@ -164,7 +164,9 @@ class WindowItem:
     column named after its function; an aggregate item a column of ``out_type`` named as the aggregate is (``sum_v``,
     ``count``) - unless ``alias`` says otherwise.  ``frame`` (aggregates): "partition" - every row of the partition, no
     ORDER BY; "range" - through the row's last peer, the default with ORDER BY; "rows" - through the row itself
-    (``rows=True``).  Not an expression: it cannot be selected, compared or nested.
+    (``rows=True``); "between" - ``rows=(n, m)``, ROWS BETWEEN n PRECEDING AND m FOLLOWING: the row's place
+    j in its partition's order, the places ``[max(first, j - n), min(last, j + m)]``; ``preceding`` / ``following`` hold n and
+    m (None for every other frame).  Not an expression: it cannot be selected, compared or nested.
 
     Navigation items: ``F.lag(col, offset, default) | F.lead(col, offset, default)`` - the value ``offset``
     rows before / after the row in its partition's order, ``default`` where the partition has no such row (both mandatory:
@@ -193,6 +195,8 @@ class WindowItem:
         self.offset, self.default, self.buckets = offset, default, buckets
         self.name = kind if arg is None else f"{kind}_{arg.name}"
         self.frame: str | None = None
+        self.preceding: int | None = None
+        self.following: int | None = None
         self.partition_by: list[Col] = []
         self.order_by: list[tuple[Col, bool]] = []
         self.is_over = False
@@ -223,7 +227,19 @@ class WindowItem:
             raise ValueError(f"{head}({shown}, k, default): the default is a literal of the column's type (an integer, a "
                              f"number or a quoted ISO timestamp), not {default!r}")
 
-    def over(self, partition_by: Any = (), order_by: Any = (), rows: bool = False) -> "WindowItem":
+    @staticmethod
+    def _check_rows(rows: Any) -> tuple[int, int] | None:
+        """``rows`` of ``over``: True / False -> None; (n, m) -> the pair, two integers in [0, 2^31); else ``ValueError``"""
+        if isinstance(rows, bool):
+            return None
+        whole = lambda v: isinstance(v, int) and not isinstance(v, bool) and 0 <= v < 1 << 31  # noqa: E731
+        if not isinstance(rows, (tuple, list)) or len(rows) != 2 or not all(whole(v) for v in rows):
+            raise ValueError(f"rows= is True, False or a pair (n, m) of integers with 0 <= n, m < 2^31 - ROWS BETWEEN n PRECEDING "
+                             f"AND m FOLLOWING - not {rows!r}")
+        return int(rows[0]), int(rows[1])
+
+    def over(self, partition_by: Any = (), order_by: Any = (), rows: Any = False) -> "WindowItem":
+        between = self._check_rows(rows)
         single = lambda v: [v] if isinstance(v, (Col, SortKey)) else list(v)  # noqa: E731
         self.partition_by = single(partition_by)
         self.order_by = [(k.column, k.ascending) if isinstance(k, SortKey) else (k, True) for k in single(order_by)]
@@ -241,8 +257,11 @@ class WindowItem:
             if rows:
                 raise ValueError(f"{self.kind.upper()}() takes no frame clause: it is a property of the row's place in its "
                                  "partition, not of a frame")
+        elif between is not None:
+            self.frame, (self.preceding, self.following) = "between", between
         else:
             self.frame = "rows" if rows else "range" if self.order_by else "partition"
+            self.preceding = self.following = None
         self.is_over = True
         return self
 
@@ -319,6 +338,9 @@ class WindowItem:
             parts.append("ORDER BY " + ", ".join(f"{c} {'ASC' if asc else 'DESC'}" for c, asc in self.order_by))
         if self.frame in ("rows", "range"):
             parts.append(f"{self.frame.upper()} UNBOUNDED PRECEDING")
+        elif self.frame == "between":
+            end = lambda k, side: f"{k} {side}" if k else "CURRENT ROW"  # noqa: E731
+            parts.append(f"ROWS BETWEEN {end(self.preceding, 'PRECEDING')} AND {end(self.following, 'FOLLOWING')}")
         inner = "" if self.arg is None else str(self.arg)
         if self.kind in ("lag", "lead"):
             inner = f"{self.arg}, {self.offset}, {self._shown_default()}"
@@ -717,9 +739,10 @@ class AggCol(Col):
     def normalize_agg_columns(self) -> Col:
         return Col(self.name)
 
-    def over(self, partition_by: Any = (), order_by: Any = (), rows: bool = False) -> WindowItem:
+    def over(self, partition_by: Any = (), order_by: Any = (), rows: Any = False) -> WindowItem:
         """The aggregate as a window item: ``F.sum(Col("v")).over(partition_by=[Col("k")])``; it keeps the
-        aggregate's name.  ``F.count().over(...)`` counts the frame's rows."""
+        aggregate's name.  ``F.count().over(...)`` counts the frame's rows.  ``rows=True``: ROWS UNBOUNDED PRECEDING;
+        ``rows=(n, m)``: ROWS BETWEEN n PRECEDING AND m FOLLOWING (4.4i)."""
         if self.type == "count_distinct":
             raise ValueError(f"{self}: COUNT(DISTINCT) has no window form")
         arg = self.original_col

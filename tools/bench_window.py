@@ -18,10 +18,16 @@ Window navigation (hs_window_nav), over case (a)'s keys, each timed next to hs_w
   (j) LEAD(TIMESTAMP, 1): 8-byte cells
   (k) LAST_VALUE(FLOAT), default frame (RANGE: the last peer)
   (l) ROW_NUMBER + SUM(INTEGER) + LAG(INTEGER, 1) + NTILE(4) in one call, default frame
+Sliding frames (hs_window_frames), SUM(FLOAT) ROWS BETWEEN n PRECEDING AND n FOLLOWING, each timed next to
+hs_window ROW_NUMBER on the same keys (a sliding item adds the block heads, one gather, a forward and a backward scan with
+their tile carries, and one scatter that reads two tables); the cost must not depend on n:
+  (m) n = 1   (n) n = 500   (o) n = 50 000       over case (a)'s keys: partitions of about 64 rows clamp the wider frames
+  (p) n = 1   (q) n = 500   (r) n = 50 000       over case (d)'s key: ONE partition, every frame as wide as it says
 Both calls read a few words back between their steps, so their times include those host round trips.  --case x --reps 3
 under a kernel trace gives the per-kernel split.  --lib PATH times another build of the library (the parent commit's, for
-"ranking did not move"); a library without hs_window_agg runs (a) - (d) only, one without hs_window_nav (a) - (h).
-Usage: python tools/bench_window.py [--rows 64M] [--partitions 1M] [--reps 20] [--case abcdefghijkl] [--lib libhipspark.so]
+"ranking did not move"); a library without hs_window_agg runs (a) - (d) only, one without hs_window_nav (a) - (h), one
+without hs_window_frames (a) - (l).
+Usage: python tools/bench_window.py [--rows 64M] [--partitions 1M] [--reps 20] [--case abcdefghijklmnopqr] [--lib libhipspark.so]
                                     [--out profiles/r21_window_nav.txt]"""
 from __future__ import annotations
 
@@ -60,7 +66,7 @@ def main() -> None:
     ap.add_argument("--rows", type=float, default=64 * 2**20)
     ap.add_argument("--partitions", type=float, default=2**20)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--case", default="abcdefghijkl")
+    ap.add_argument("--case", default="abcdefghijklmnopqr")
     ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -74,7 +80,8 @@ def main() -> None:
         lib = hs.load_library()
     has_agg = hasattr(lib, "hs_window_agg")
     has_nav = hasattr(lib, "hs_window_nav")
-    a.case = "".join(tag for tag in a.case if tag in "abcd" or (has_agg and tag in "efgh") or has_nav)
+    has_frames = hasattr(lib, "hs_window_frames")
+    a.case = "".join(tag for tag in a.case if tag in "abcd" or (has_agg and tag in "efgh") or (has_nav and tag in "ijkl") or has_frames)
     g = torch.Generator(device="cuda")
     g.manual_seed(15)
     part = torch.randint(0, d, (n,), device="cuda", generator=g, dtype=torch.int64)
@@ -84,7 +91,7 @@ def main() -> None:
     stream = torch.cuda.current_stream().cuda_stream
     perm = torch.empty(n, dtype=torch.int64, device="cuda")
     outs = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(5 if has_agg else 3)]
-    ws_bytes = (lib.hs_window_nav_ws_bytes(n, 2, 3, 5) if has_nav else lib.hs_window_agg_ws_bytes(n, 2, 3, 5) if has_agg
+    ws_bytes = (lib.hs_window_frames_ws_bytes(n, 2, 3, 5) if has_frames else lib.hs_window_nav_ws_bytes(n, 2, 3, 5) if has_nav else lib.hs_window_agg_ws_bytes(n, 2, 3, 5) if has_agg
                 else lib.hs_window_ws_bytes(n, 2, 3))
     ws = torch.empty(int(ws_bytes) + 256, dtype=torch.uint8, device="cuda")
     count = C.c_int64(0)
@@ -169,10 +176,39 @@ def main() -> None:
                                                                           (hs.WIN_SUM, hs.WIN_FRAME_RANGE, vi, 0),
                                                                           (hs.WIN_LAG, 0, vi, 1), (hs.WIN_NTILE, 0, None, 4)])}
 
+    def window_frames(cols, n_part, items):
+        """items = [(function, argument column, n PRECEDING, m FOLLOWING)], all of HS_WIN_FRAME_BETWEEN"""
+        arr = (hs.hs_col * len(cols))(*cols)
+        asc = (C.c_int32 * len(cols))(*[0] * len(cols))
+        kinds = (C.c_int32 * len(items))(*[it[0] for it in items])
+        frames = (C.c_int32 * len(items))(*[hs.WIN_FRAME_BETWEEN] * len(items))
+        values = (hs.hs_col * len(items))(*[it[1] for it in items])
+        before, after = (C.c_int64 * len(items))(*[it[2] for it in items]), (C.c_int64 * len(items))(*[it[3] for it in items])
+        ptrs = (C.c_void_p * len(items))(*[o.data_ptr() for o in outs[:len(items)]])
+
+        def run():
+            hs.check(lib.hs_window_frames(stream, arr, asc, n_part, len(cols), n, kinds, frames, values, None, None, before, after,
+                                          len(items), ptrs, ws.data_ptr(), flags.data_ptr()), "hs_window_frames")
+        return run
+
+    frame_cases = {}
+    if has_frames:
+        frame_cases = {tag: (f"SUM(FLOAT), ({k}, {k}), keys of ({keys})", keys, [(hs.WIN_SUM, vf, k, k)])
+                       for tag, keys, k in (("m", "a", 1), ("n", "a", 500), ("o", "a", 50000), ("p", "d", 1), ("q", "d", 500),
+                                            ("r", "d", 50000))}
+
     lines = [f"tools/bench_window.py --rows {n} --partitions {d} --reps {a.reps}   [{torch.cuda.get_device_name(0)}, host "
              f"{socket.gethostname()}, torch {torch.__version__}]",
              "events on the launch stream, the two calls alternating; median (min - max) ms; ratio = hs_window / hs_order_by"]
     for tag in a.case:
+        if tag in frame_cases:
+            what, keys, items = frame_cases[tag]
+            _, cols, n_part, _ = cases[keys]
+            (mw, lw, hw), (ms, lo, hi) = timed_pair(window_frames(cols, n_part, items), window(cols, n_part, every[:1]), a.reps)
+            lines.append(f"({tag}) hs_window_frames {what:30s} {mw:9.3f} ms ({lw:.3f} - {hw:.3f})   {n / mw / 1e6:8.2f} G rows/s")
+            lines.append(f"({tag}) hs_window    {'the same keys, ROW_NUMBER':34s} {ms:9.3f} ms ({lo:.3f} - {hi:.3f})   "
+                         f"{n / ms / 1e6:8.2f} G rows/s   ratio {mw / ms:.2f}   + {mw - ms:.3f} ms")
+            continue
         if tag in agg_cases or tag in nav_cases:
             what, items = agg_cases[tag] if tag in agg_cases else nav_cases[tag]
             entry, call = ("hs_window_agg", window_agg) if tag in agg_cases else ("hs_window_nav", window_nav)
@@ -233,6 +269,17 @@ def main() -> None:
         want[1:] = torch.where(p[1:] == p[:-1], v[:-1], torch.zeros_like(v[1:]))
         lines.append(f"check (i): along the sorted rows LAG is the left neighbour's cell, 0 at a partition's first row: "
                      f"{bool((outs[0][perm] == want).all())}")
+    if "q" in a.case:  # checked with torch over the sort's own row list: one partition, so a difference of i64 prefix sums
+        what, keys, _ = frame_cases["q"]
+        _, cols, n_part, _ = cases[keys]
+        window_frames(cols, n_part, [(hs.WIN_SUM, vi, 500, 500)])()
+        order_by(cols)()
+        torch.cuda.synchronize()
+        prefix = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(ints[perm].to(torch.int64), 0)])
+        position = torch.arange(n, device="cuda")
+        want = prefix[torch.clamp(position + 501, max=n)] - prefix[torch.clamp(position - 500, min=0)]
+        ok = bool((outs[0][perm].to(torch.int64) == want).all()) and int(flags[0].item()) == 0
+        lines.append(f"check (q): along the sorted rows SUM(INTEGER) over (500, 500) is the sum of the 1001 cells around the row: {ok}")
     text = "\n".join(lines)
     print(text)
     if a.out:
