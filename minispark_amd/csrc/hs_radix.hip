@@ -1892,6 +1892,25 @@ static bool ob_kind_ok(const hs_col& c) {
     }
 }
 
+// What every entry over ob_sort refuses of its key columns, under its own name and in its own nouns: before its
+// `nrows == 0` return the limit (`many`: "keys" / "columns" / "partition and order columns") and a narrow column, behind
+// it a column ob_kind_ok does not take (`one` / `done`: "key" ... "ordered" / "column" ... "compared").
+static int ob_refuse_keys(const char* name, const hs_col* keys, int32_t n_keys, const char* many) {
+    if (n_keys > HS_MAX_COLS) {
+        hs_set_error("%s: more than %d %s", name, HS_MAX_COLS, many);
+        return HS_E_LIMIT;
+    }
+    return hs_refuse_narrow(name, keys, n_keys) ? HS_E_ARG : HS_OK;
+}
+static int ob_refuse_kinds(const char* name, const hs_col* keys, int32_t n_keys, const char* one, const char* done) {
+    for (int k = 0; k < n_keys; ++k)
+        if (!ob_kind_ok(keys[k])) {
+            hs_set_error("%s: %s %d is not a column that can be %s", name, one, k, done);
+            return HS_E_ARG;
+        }
+    return HS_OK;
+}
+
 // a launch inside ob_sort: the error names the entry point that called
 #define OB_CHECK_LAUNCH(what)                                        \
     if (hipGetLastError() != hipSuccess) {                           \
@@ -1910,6 +1929,21 @@ struct ObSorted {
     uint64_t varying;     // `unsorted`: the bits of the first word formed that differ between rows
     int32_t unsorted;     // `dense` ended the sort before any pass moved a row: `rows` / `words` stand in input order
 };
+
+// The sorted rows as the kernels that look for the runs of equal keys take them: the first members of DhArgs
+// (k_distinct_heads) and of WinHeads (k_win_heads)
+struct ObRun {
+    ObKeys K;               // col / width / str_cap / desc of the sort
+    int32_t n_keys, n_words;
+    const int64_t* perm;    // the rows, sorted by all keys (null: position = row, the keys have no byte)
+    const uint64_t* words;  // a key of ONE word: that word of the sorted rows, as the sort left it - compared instead of
+                            // formed again (null: the words are formed from the columns)
+    int64_t n;
+};
+static ObRun ob_run(const ObSorted& S, int32_t n_keys) {
+    // one word per row: the sorted words ARE the rows' keys
+    return ObRun{S.keys, n_keys, S.n_words, S.rows, S.n_words == 1 && S.rows ? S.words : nullptr, S.n};
+}
 
 // hs_mark_first's dense path holds a key of ONE word whose varying bits are few (defined with its kernels, below)
 static bool mf_dense_fits(int32_t n_words, uint64_t varying);
@@ -2126,21 +2160,14 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
         hs_set_error("hs_order_by: bad arguments");
         return HS_E_ARG;
     }
-    if (n_keys > HS_MAX_COLS) {
-        hs_set_error("hs_order_by: more than %d keys", HS_MAX_COLS);
-        return HS_E_LIMIT;
-    }
-    if (hs_refuse_narrow("hs_order_by", keys, n_keys)) return HS_E_ARG;
+    int rc = ob_refuse_keys("hs_order_by", keys, n_keys, "keys");
+    if (rc != HS_OK) return rc;
     *out_count = 0;
     if (nrows == 0 || limit == 0) return HS_OK;
-    for (int k = 0; k < n_keys; ++k)
-        if (!ob_kind_ok(keys[k])) {
-            hs_set_error("hs_order_by: key %d is not a column that can be ordered", k);
-            return HS_E_ARG;
-        }
+    if ((rc = ob_refuse_kinds("hs_order_by", keys, n_keys, "key", "ordered")) != HS_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     ObSorted S;
-    const int rc = ob_sort(stream, keys, descending, n_keys, nrows, nrows_dev, limit, out_count, ws_, "hs_order_by", S);
+    rc = ob_sort(stream, keys, descending, n_keys, nrows, nrows_dev, limit, out_count, ws_, "hs_order_by", S);
     if (rc != HS_OK || S.count == 0) return rc;
     if (!S.rows) {
         hipLaunchKernelGGL(k_ob_iota, dim3(ob_grid(S.count)), dim3(OB_THREADS), 0, stream, out_perm, S.count);
@@ -2168,17 +2195,11 @@ extern "C" int hs_order_by(void* stream_, const hs_col* keys, const int32_t* des
 // INTEGER) needs none of that: the sorted words the sort leaves behind are the rows' keys, read coalesced.  No LDS, no
 // atomics; the pass is bound by the gathers of the key cells (one per row and word) and the byte scattered into keep.
 // =====================================================================================================
-struct DhArgs {
-    ObKeys K;             // col / width / str_cap / desc of the sort
-    int32_t n_keys, n_words;
-    const int64_t* perm;  // the rows, sorted by all keys (null: position = row)
-    const uint64_t* words;  // a key of ONE word: that word of the sorted rows, as the sort left it - compared instead of
-                          // formed again (null: the words are formed from the columns)
-    int64_t n;
+struct DhArgs : ObRun {
     uint8_t* keep;        // [n], input order
     int32_t* mark;        // hs_mark_first: INTEGER cells, input order, instead of `keep` (rows outside perm are not written)
 };
-static_assert(sizeof(DhArgs) % 8 == 0, "DhArgs");
+static_assert(sizeof(DhArgs) == sizeof(ObRun) + 16, "DhArgs");  // `keep` directly behind the base: see WinHeads
 
 // word w of a row's key, formed again from the columns (k_distinct_heads, k_win_heads)
 __device__ __forceinline__ uint64_t ob_word(const ObKeys& K, int32_t n_keys, int32_t w, int64_t row) {
@@ -2241,48 +2262,28 @@ extern "C" int hs_distinct(void* stream_, const hs_col* keys, int32_t n_keys, in
         hs_set_error("hs_distinct: bad arguments");
         return HS_E_ARG;
     }
-    if (n_keys > HS_MAX_COLS) {
-        hs_set_error("hs_distinct: more than %d columns", HS_MAX_COLS);
-        return HS_E_LIMIT;
-    }
-    if (hs_refuse_narrow("hs_distinct", keys, n_keys)) return HS_E_ARG;
+    int rc = ob_refuse_keys("hs_distinct", keys, n_keys, "columns");
+    if (rc != HS_OK) return rc;
     *out_count = 0;
     if (nrows == 0) return HS_OK;
-    for (int k = 0; k < n_keys; ++k)
-        if (!ob_kind_ok(keys[k])) {
-            hs_set_error("hs_distinct: column %d is not a column that can be compared", k);
-            return HS_E_ARG;
-        }
+    if ((rc = ob_refuse_kinds("hs_distinct", keys, n_keys, "column", "compared")) != HS_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const int32_t ascending[HS_MAX_COLS] = {0};
-    DhArgs D;
-    std::memset(&D, 0, sizeof(D));
+    ObSorted S;
     int64_t sorted_rows = 0;
-    size_t sort_bytes = 0;
-    {
-        ObSorted S;
-        const int rc = ob_sort(stream, keys, ascending, n_keys, nrows, nrows_dev, -1, &sorted_rows, ws_, "hs_distinct", S);
-        if (rc != HS_OK || S.count == 0) return rc;
-        D.K = S.keys;
-        D.n_keys = n_keys;
-        D.n_words = S.n_words;
-        D.perm = S.rows;
-        D.n = S.n;
-        // one word per row: the sorted words ARE the rows' keys.  HIPSPARK_DISTINCT_GATHER=1 keeps the general path,
-        // so that tools/bench_distinct.py can time one against the other
-        const char* gather = std::getenv("HIPSPARK_DISTINCT_GATHER");
-        if (S.n_words == 1 && S.rows && !(gather && gather[0] == '1')) D.words = S.words;
-        sort_bytes = S.ws_bytes;
-    }
-    uint8_t* extra = (uint8_t*)ws_ + sort_bytes;  // behind what the sort laid out (hs_distinct_ws_bytes: at most hs_order_by_ws_bytes)
+    rc = ob_sort(stream, keys, ascending, n_keys, nrows, nrows_dev, -1, &sorted_rows, ws_, "hs_distinct", S);
+    if (rc != HS_OK || S.count == 0) return rc;
+    DhArgs D{ob_run(S, n_keys)};  // keep, mark: null
+    // HIPSPARK_DISTINCT_GATHER=1 keeps the general path, so that tools/bench_distinct.py can time one against the other
+    if (const char* gather = std::getenv("HIPSPARK_DISTINCT_GATHER"); gather && gather[0] == '1') D.words = nullptr;
+    uint8_t* extra = (uint8_t*)ws_ + S.ws_bytes;  // behind what the sort laid out (hs_distinct_ws_bytes: at most hs_order_by_ws_bytes)
     D.keep = extra;
     int64_t* count_dev = (int64_t*)(extra + rx_align((size_t)nrows));
     void* scan_ws = (uint8_t*)count_dev + 256;
     const int64_t tiles = (D.n + OB_TILE - 1) / OB_TILE;
     hipLaunchKernelGGL(k_distinct_heads, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, D);
     RX_CHECK_LAUNCH("hs_distinct (heads)");
-    const int rc = hs_compact(stream, D.keep, D.n, out_perm, count_dev, scan_ws);
-    if (rc != HS_OK) return rc;
+    if ((rc = hs_compact(stream, D.keep, D.n, out_perm, count_dev, scan_ws)) != HS_OK) return rc;
     int64_t kept = 0;
     if (hipMemcpyAsync(&kept, count_dev, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess || kept < 1 || kept > D.n) {
@@ -2380,17 +2381,10 @@ extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, 
         hs_set_error("hs_mark_first: bad arguments");
         return HS_E_ARG;
     }
-    if (n_keys > HS_MAX_COLS) {
-        hs_set_error("hs_mark_first: more than %d columns", HS_MAX_COLS);
-        return HS_E_LIMIT;
-    }
-    if (hs_refuse_narrow("hs_mark_first", keys, n_keys)) return HS_E_ARG;
+    int rc = ob_refuse_keys("hs_mark_first", keys, n_keys, "columns");
+    if (rc != HS_OK) return rc;
     if (nrows == 0) return HS_OK;
-    for (int k = 0; k < n_keys; ++k)
-        if (!ob_kind_ok(keys[k])) {
-            hs_set_error("hs_mark_first: column %d is not a column that can be compared", k);
-            return HS_E_ARG;
-        }
+    if ((rc = ob_refuse_kinds("hs_mark_first", keys, n_keys, "column", "compared")) != HS_OK) return rc;
     const bool rows_fit = nrows < 0xffffffffll;  // a row number and the table's fill must differ
     if (mode == 2 && !rows_fit) {
         hs_set_error("hs_mark_first: the dense path holds row numbers below 2^32 - 1, not %lld rows", (long long)nrows);
@@ -2406,8 +2400,8 @@ extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, 
     ObSorted S;
     int64_t considered = 0;
     const int dense = mode == 2 ? OB_DENSE_ONLY : (mode == 0 && rows_fit) ? OB_DENSE_IF_FITS : OB_SORT;
-    const int rc = ob_sort(stream, keys, ascending, n_keys, nrows, nullptr, -1, &considered, ws_, "hs_mark_first", S, sel,
-                           sel ? n_sel : 0, dense);
+    rc = ob_sort(stream, keys, ascending, n_keys, nrows, nullptr, -1, &considered, ws_, "hs_mark_first", S, sel, sel ? n_sel : 0,
+                 dense);
     if (rc != HS_OK || S.count == 0) return rc;
     if (S.unsorted) {
         MfArgs M;
@@ -2434,14 +2428,8 @@ extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, 
         RX_CHECK_LAUNCH("hs_mark_first (dense)");
         return HS_OK;
     }
-    DhArgs D;
-    std::memset(&D, 0, sizeof(D));
-    D.K = S.keys;
-    D.n_keys = n_keys;
-    D.n_words = S.n_words;
-    D.perm = S.n_words ? S.rows : sel;  // a key without a byte: every considered row is equal, the first of them the head
-    D.n = S.n;
-    if (S.n_words == 1 && S.rows) D.words = S.words;
+    DhArgs D{ob_run(S, n_keys)};
+    if (!S.n_words) D.perm = sel;  // a key without a byte: every considered row is equal, the first of them the head
     D.mark = marks;
     const int64_t tiles = (D.n + OB_TILE - 1) / OB_TILE;
     hipLaunchKernelGGL(k_distinct_heads, dim3((unsigned)tiles), dim3(OB_THREADS), 0, stream, D);
@@ -2481,16 +2469,16 @@ extern "C" int hs_mark_first(void* stream_, const hs_col* keys, int32_t n_keys, 
 constexpr int WIN_PER = OB_TILE / OB_THREADS;  // consecutive sorted positions of a lane in the scan passes
 static_assert(WIN_PER == 8, "a lane's head bytes are one 8-byte load");
 
-struct WinHeads {
-    ObKeys K;               // col / width / str_cap / desc of the sort
-    int32_t n_keys, n_words;
-    const int64_t* perm;    // the rows, sorted by all keys (null: position = row, the keys have no byte)
-    const uint64_t* words;  // a key of ONE word: the sorted words, compared instead of formed again (else null)
-    int64_t n;
+struct WinHeads : ObRun {
     int64_t part_bytes;     // the partition columns' bytes: the first part_bytes bytes of a row's key
     uint8_t* heads;         // by sorted position: bit 0 peer head, bit 1 partition head
 };
-static_assert(sizeof(WinHeads) % 8 == 0, "WinHeads");
+static_assert(sizeof(WinHeads) == sizeof(ObRun) + 16, "WinHeads");
+// a kernel argument is ObRun's members, then the struct's own directly behind them
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"  // a struct with a base is no standard-layout type; clang lays it out as C would
+static_assert(offsetof(DhArgs, keep) == sizeof(ObRun) && offsetof(WinHeads, part_bytes) == sizeof(ObRun), "behind ObRun");
+#pragma clang diagnostic pop
 
 // the bytes of word w that belong to the partition prefix (byte 0 of the key = most significant byte of word 0)
 __device__ __forceinline__ uint64_t win_part_mask(int64_t part_bytes, int32_t w) {
@@ -3236,11 +3224,7 @@ static int win_refuse(const char* name, const hs_col* keys, int32_t n_part, int3
         hs_set_error("%s: bad arguments", name);
         return HS_E_ARG;
     }
-    if (n_keys > HS_MAX_COLS) {
-        hs_set_error("%s: more than %d partition and order columns", name, HS_MAX_COLS);
-        return HS_E_LIMIT;
-    }
-    if (hs_refuse_narrow(name, keys, n_keys)) return HS_E_ARG;
+    if (const int rc = ob_refuse_keys(name, keys, n_keys, "partition and order columns"); rc != HS_OK) return rc;
     if (n_funcs > HS_WIN_MAX_FUNCS) {
         hs_set_error("%s: more than %d functions in one call", name, HS_WIN_MAX_FUNCS);
         return HS_E_LIMIT;
@@ -3361,31 +3345,16 @@ static int win_run(const char* name, const char* last, int32_t max_func, int32_t
             hs_set_error("%s: output %d is null", name, i);
             return HS_E_ARG;
         }
-    for (int k = 0; k < n_keys; ++k)
-        if (!ob_kind_ok(keys[k])) {
-            hs_set_error("%s: key %d is not a column that can be ordered", name, k);
-            return HS_E_ARG;
-        }
+    if ((rc = ob_refuse_kinds(name, keys, n_keys, "key", "ordered")) != HS_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     int32_t desc[HS_MAX_COLS] = {0};
     for (int k = n_part; k < n_keys; ++k) desc[k] = descending[k] ? 1 : 0;
-    WinHeads H;
-    std::memset(&H, 0, sizeof(H));
-    uint8_t* base = nullptr;  // behind what the sort laid out
-    {
-        ObSorted S;
-        int64_t sorted_rows = 0;
-        rc = ob_sort(stream, keys, desc, n_keys, nrows, nullptr, -1, &sorted_rows, ws_, name, S);
-        if (rc != HS_OK) return rc;
-        H.K = S.keys;
-        H.n_keys = n_keys;
-        H.n_words = S.n_words;
-        H.perm = S.rows;
-        H.n = nrows;
-        if (S.n_words == 1 && S.rows) H.words = S.words;  // one word per row: the sorted words ARE the rows' keys
-        for (int k = 0; k < n_part; ++k) H.part_bytes += S.keys.width[k];
-        base = (uint8_t*)ws_ + S.ws_bytes;
-    }
+    ObSorted S;
+    int64_t sorted_rows = 0;
+    if ((rc = ob_sort(stream, keys, desc, n_keys, nrows, nullptr, -1, &sorted_rows, ws_, name, S)) != HS_OK) return rc;
+    WinHeads H{ob_run(S, n_keys)};  // n: nrows, nothing limits the rows
+    for (int k = 0; k < n_part; ++k) H.part_bytes += S.keys.width[k];
+    uint8_t* base = (uint8_t*)ws_ + S.ws_bytes;  // behind what the sort laid out
     const WinLayout L = win_layout(nrows);
     H.heads = base + L.heads;
     const WinTile T{H.heads, H.perm, (WinRec*)(base + L.recs), nrows};
@@ -3428,11 +3397,11 @@ static int win_run(const char* name, const char* last, int32_t max_func, int32_t
     const dim3 both((unsigned)tiles, 2);  // the forward and the backward scan of a sliding item
     for (int fr = HS_WIN_FRAME_PARTITION; fr <= HS_WIN_FRAME_RANGE; ++fr) {
         if (!needed[fr]) continue;
-        WaggArgs S = A;
-        S.op = WA_NONE;
-        S.frame = fr;
-        S.tab_c = ends[fr];
-        hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, S);
+        WaggArgs Ends = A;
+        Ends.op = WA_NONE;
+        Ends.frame = fr;
+        Ends.tab_c = ends[fr];
+        hipLaunchKernelGGL(k_wagg_scan, grid, block, 0, stream, Ends);
     }
     uint32_t done = 0;
     for (int i = 0; i < n_items; ++i) {

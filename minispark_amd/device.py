@@ -164,6 +164,21 @@ class DBatch:
         raise ValueError(f'Column "{name}" not found in schema {self.schema}')
 
 
+@dataclass(frozen=True)
+class WinItem:
+    """One item of ``Device.window``.  ``func``: a name of ``Device.WINDOW_KINDS``.  ``frame``:
+    "partition" | "range" | "rows" | "between" for an aggregate ("count", "sum", "avg", "min", "max"), "first_value" and
+    "last_value"; the others take none.  ``value``: the argument's column index - INTEGER or FLOAT for an aggregate,
+    TIMESTAMP too for "lag", "lead", "first_value" and "last_value"; none for the ranking functions, "count" and "ntile".
+    ``param``: (k, the default cell's bits) for "lag" / "lead", (n, 0) for "ntile".  ``offsets``: (n PRECEDING, m
+    FOLLOWING) with the frame "between", and only with it."""
+    func: str
+    frame: str | None = None
+    value: int | None = None
+    param: tuple[int, int] | None = None
+    offsets: tuple[int, int] | None = None
+
+
 class TierExceeded(NotImplementedError):
     """The on-chip (LDS) aggregation tier cannot hold this launch: the engine switches to the global tier."""
 
@@ -1640,6 +1655,24 @@ class Device:
         n_pad = self.host_int(self.lower_bound(srt, n, zero))  # rows with order < 0
         return perm[n_pad:n], n - n_pad
 
+    def _key_cols(self, cols: Sequence[DCol], what: str, orders_from: int | None = None) -> tuple[list[DCol], Any, int]:
+        """The key columns of ``order_by``, ``distinct``, ``window`` and ``mark_first`` -> (the columns as they go to the
+        device, their hs_col array, the bound of a key's words their ``*_ws_bytes`` take).  The array holds addresses only:
+        the caller keeps the columns - a decoded one exists nowhere else - until its call has returned.  A virtual column
+        is refused as ``what``; the columns from ``orders_from`` on ORDER the rows (None: the columns are only compared -
+        one code, one string), so a dictionary that is not sorted is decoded there.  All four learn sizes on the host
+        between their steps: the recording is poisoned."""
+        if self.rec is not None:
+            self.rec.poisoned = True
+        cols = list(cols)
+        for k, col in enumerate(cols):
+            if col.virtual:
+                raise DeviceError(f"a virtual column of the fused join cannot be {what}")
+            if orders_from is not None and k >= orders_from and col.dict is not None and list(col.dict) != sorted(col.dict):
+                cols[k] = self.decoded(col)
+        n_keys = max(len(cols), 1)
+        return cols, (hs.hs_col * n_keys)(*[c.as_hs() for c in cols]), 32 * n_keys  # a key column: <= 256 bytes, 32 words
+
     def order_by(self, batch: DBatch, keys: Sequence[tuple[Any, bool]], limit: int | None = None) -> tuple[torch.Tensor, int]:
         """ORDER BY keys [LIMIT limit] over the rows of ``batch`` -> (row list, its length): row ``perm[j]`` of the batch
         is the j-th row of the answer; ``gather_batch`` moves the columns.  ``keys`` = (column index or name, ascending)
@@ -1649,25 +1682,16 @@ class Device:
         so a run that contains it is not replayable."""
         batch = self.resolve(batch)
         n = batch.nrows
-        if self.rec is not None:
-            self.rec.poisoned = True
-        cols = []
-        for which, _ in keys:
-            col = batch.cols[batch.column_index(which) if isinstance(which, str) else which]
-            if col.virtual:
-                raise DeviceError("a virtual column of the fused join cannot be a sort key")
-            if col.dict is not None and list(col.dict) != sorted(col.dict):
-                col = self.decoded(col)
-            cols.append(col)
+        cols, arr, key_words = self._key_cols([batch.cols[batch.column_index(which) if isinstance(which, str) else which]
+                                               for which, _ in keys], "a sort key", orders_from=0)
         count = n if limit is None else min(n, int(limit))
         perm = self.empty(max(count, 1), torch.int64)
         if count == 0 or not cols:
             if count:
                 torch.arange(count, out=perm)
             return perm[:count], count
-        arr = (hs.hs_col * len(cols))(*[c.as_hs() for c in cols])
         desc = (C.c_int32 * len(cols))(*[0 if ascending else 1 for _, ascending in keys])
-        ws = self.workspace(self._raw_lib.hs_order_by_ws_bytes(n, len(cols), 32 * len(cols)))  # a key: <= 256 bytes
+        ws = self.workspace(self._raw_lib.hs_order_by_ws_bytes(n, len(cols), key_words))
         out_count = C.c_int64(0)
         hs.check(self._raw_lib.hs_order_by(self.stream, arr, desc, len(cols), n, None, -1 if limit is None else int(limit),
                                            perm.data_ptr(), C.byref(out_count), ws.data_ptr(), self.flags.data_ptr()),
@@ -1684,19 +1708,15 @@ class Device:
         sized batch passes its device row count along.  Like ``order_by`` the call learns sizes on the host between
         its steps, so a run that contains it is not replayable."""
         n = batch.nrows
-        if self.rec is not None:
-            self.rec.poisoned = True
         if len(batch.cols) > hs.HS_MAX_COLS:
             raise DeviceError(f"DISTINCT over {len(batch.cols)} columns: at most {hs.HS_MAX_COLS}")
-        if any(col.virtual for col in batch.cols):
-            raise DeviceError("a virtual column of the fused join cannot be compared by DISTINCT")
+        cols, arr, key_words = self._key_cols(batch.cols, "compared by DISTINCT")
         perm = self.empty(max(n, 1), torch.int64)
-        if n == 0 or not batch.cols:
+        if n == 0 or not cols:
             return perm[:0], 0
-        arr = (hs.hs_col * len(batch.cols))(*[c.as_hs() for c in batch.cols])
-        ws = self.workspace(self._raw_lib.hs_distinct_ws_bytes(n, len(batch.cols), 32 * len(batch.cols)))
+        ws = self.workspace(self._raw_lib.hs_distinct_ws_bytes(n, len(cols), key_words))
         out_count = C.c_int64(0)
-        hs.check(self._raw_lib.hs_distinct(self.stream, arr, len(batch.cols), n, batch.n_dev_ptr,
+        hs.check(self._raw_lib.hs_distinct(self.stream, arr, len(cols), n, batch.n_dev_ptr,
                                            perm.data_ptr(), C.byref(out_count), ws.data_ptr(), self.flags.data_ptr()),
                  "hs_distinct")
         if not 0 <= out_count.value <= n:
@@ -1710,98 +1730,71 @@ class Device:
     WINDOW_FRAMES = {None: hs.WIN_FRAME_PARTITION, "partition": hs.WIN_FRAME_PARTITION, "range": hs.WIN_FRAME_RANGE,
                      "rows": hs.WIN_FRAME_ROWS, "between": hs.WIN_FRAME_BETWEEN}
 
-    def window(self, batch: DBatch, part_idx: Sequence[int], order_keys: Sequence[tuple[int, bool]], funcs: Sequence[str],
-               frames: Sequence[str | None] | None = None, value_idx: Sequence[int | None] | None = None,
-               params: Sequence[tuple[int, int] | None] | None = None,
-               offsets: Sequence[tuple[int, int] | None] | None = None) -> list[DCol]:
-        """The window items ``funcs`` over the rows of ``batch`` -> one column per item, in INPUT order: no row moves.
-        ``part_idx`` = the PARTITION BY columns, ``order_keys`` = (column, ascending) pairs of the window's ORDER BY; all
-        items share the one sort.  ROW_NUMBER / RANK / DENSE_RANK give INTEGER columns; when every item is one of them the
-        call is hs_window's, as before aggregates existed.  An aggregate item ("count", "sum", "avg", "min", "max") has its
-        frame in ``frames`` ("partition" | "range" | "rows") and its argument's column index in ``value_idx`` (INTEGER or
-        FLOAT; None for "count"), and the call is hs_window_agg's: FLOAT where the value is (AVG, SUM / MIN / MAX of a
-        FLOAT column).  An overflow it meets is raised in the status word, where the result's write finds it.  A navigation
-        item ("lag", "lead", "first_value", "last_value", "ntile") makes the call hs_window_nav's, which takes every item:
-        its argument (INTEGER, FLOAT or TIMESTAMP; None for "ntile") is in ``value_idx``, the frame of "first_value" /
-        "last_value" in ``frames``, and ``params`` holds (k, the default cell's bits) for "lag" / "lead" and (n, 0) for
-        "ntile"; the column has the argument's kind, INTEGER for "ntile".  An aggregate, "first_value" or "last_value" whose
-        frame is "between" (ROWS BETWEEN n PRECEDING AND m FOLLOWING) has its (n, m) in ``offsets``, and the
-        call is hs_window_frames', which takes every item; without such an item the call is the one it was.  Equality
-        and order are ``distinct``'s and ``order_by``'s.  A dictionary-coded column goes as its code byte where it only
-        partitions (one code, one string) or where the dictionary is sorted, decoded otherwise, as in ``order_by``.  The
-        call learns sizes on the host between its steps, so a run that contains it is not replayable."""
+    # The four entries, oldest first: (name, the highest function it takes, takes the frame "between", how many of the
+    # item arrays - functions, frames, values, params, defaults, preceding, following - it takes).  Each takes the arrays
+    # of the one before it and asks for a larger workspace; a call goes to the first that takes all its items.
+    WINDOW_ENTRIES = (("hs_window", hs.WIN_DENSE_RANK, False, 1), ("hs_window_agg", hs.WIN_MAX, False, 3),
+                      ("hs_window_nav", hs.WIN_NTILE, False, 5), ("hs_window_frames", hs.WIN_NTILE, True, 7))
+
+    def window(self, batch: DBatch, part_idx: Sequence[int], order_keys: Sequence[tuple[int, bool]],
+               items: Sequence[WinItem]) -> list[DCol]:
+        """The window ``items`` (``WinItem``: its fields say what each function takes) over the rows of ``batch`` -> one
+        column per item, in INPUT order: no row moves.  ``part_idx`` = the PARTITION BY columns, ``order_keys`` = (column,
+        ascending) pairs of the window's ORDER BY; all items share the one sort and one call, the oldest entry of
+        ``WINDOW_ENTRIES`` that takes them all.  A column has its argument's kind, but INTEGER for the ranking functions,
+        "count" and "ntile" and FLOAT for "avg"; an overflow an aggregate meets is raised in the status word, where the
+        result's write finds it.  Equality and order are ``distinct``'s and ``order_by``'s: a dictionary-coded column goes
+        as its code byte where it only partitions or where the dictionary is sorted, decoded otherwise.  The call learns
+        sizes on the host between its steps, so a run that contains it is not replayable."""
         batch = self.resolve(batch)
         n = batch.nrows
-        if self.rec is not None:
-            self.rec.poisoned = True
         n_keys = len(part_idx) + len(order_keys)
         if n_keys > hs.HS_MAX_COLS:
             raise DeviceError(f"a window over {n_keys} partition and order columns: at most {hs.HS_MAX_COLS}")
-        if not 0 < len(funcs) <= hs.WIN_MAX_FUNCS:
-            raise DeviceError(f"{len(funcs)} window functions in one call: 1 to {hs.WIN_MAX_FUNCS}")
+        if not 0 < len(items) <= hs.WIN_MAX_FUNCS:
+            raise DeviceError(f"{len(items)} window functions in one call: 1 to {hs.WIN_MAX_FUNCS}")
         if n >= 1 << 31:
             raise DeviceError(f"a window over {n} rows: the INTEGER result numbers fewer than 2^31")
-        cols = []
-        for k, which in enumerate([*part_idx, *[i for i, _ in order_keys]]):
-            col = batch.cols[which]
-            if col.virtual:
-                raise DeviceError("a virtual column of the fused join cannot be a window key")
-            if k >= len(part_idx) and col.dict is not None and list(col.dict) != sorted(col.dict):
-                col = self.decoded(col)
-            cols.append(col)
-        codes = [self.WINDOW_KINDS[f] for f in funcs]
-        frames = list(frames) if frames is not None else [None] * len(funcs)
-        value_idx = list(value_idx) if value_idx is not None else [None] * len(funcs)
-        params = list(params) if params is not None else [None] * len(funcs)
+        cols, arr, key_words = self._key_cols([batch.cols[which] for which in [*part_idx, *[i for i, _ in order_keys]]],
+                                              "a window key", orders_from=len(part_idx))  # cols: held until the call is over
+        codes = [self.WINDOW_KINDS[item.func] for item in items]
         values: list[DCol | None] = []
-        for code, f, which in zip(codes, funcs, value_idx):
+        for code, item in zip(codes, items):
             col = None
             if hs.WIN_COUNT < code <= hs.WIN_MAX:
-                col = batch.cols[which] if which is not None else None
+                col = batch.cols[item.value] if item.value is not None else None
                 if col is None or col.virtual or col.kind not in (hs.I32, hs.F32):
-                    raise DeviceError(f"the window aggregate {f} takes a stored INTEGER or FLOAT column")
+                    raise DeviceError(f"the window aggregate {item.func} takes a stored INTEGER or FLOAT column")
             elif hs.WIN_LAG <= code <= hs.WIN_LAST_VALUE:
-                col = batch.cols[which] if which is not None else None
+                col = batch.cols[item.value] if item.value is not None else None
                 if col is None or col.virtual or col.dict is not None or col.kind not in (hs.I32, hs.F32, hs.I64):
-                    raise DeviceError(f"the window function {f} takes a stored INTEGER, FLOAT or TIMESTAMP column")
+                    raise DeviceError(f"the window function {item.func} takes a stored INTEGER, FLOAT or TIMESTAMP column")
             values.append(col)
-        offsets = list(offsets) if offsets is not None else [None] * len(funcs)
-        for f, frame, offset in zip(funcs, frames, offsets):
-            if (frame == "between") != (offset is not None):
-                raise DeviceError(f'the window function {f}: the frame "between" and its (n, m) in offsets come together')
-        for code, f, param in zip(codes, funcs, params):
-            if code in (hs.WIN_LAG, hs.WIN_LEAD, hs.WIN_NTILE) and param is None:
-                raise DeviceError(f"the window function {f} needs its (k or n, default bits) in params")
+        for item in items:
+            if (item.frame == "between") != (item.offsets is not None):
+                raise DeviceError(f'the window function {item.func}: the frame "between" and its (n, m) in offsets come together')
+        for code, item in zip(codes, items):
+            if code in (hs.WIN_LAG, hs.WIN_LEAD, hs.WIN_NTILE) and item.param is None:
+                raise DeviceError(f"the window function {item.func} needs its (k or n, default bits) in params")
         out_kinds = [hs.F32 if code == hs.WIN_AVG else col.kind if col is not None else hs.I32 for code, col in zip(codes, values)]
         dtypes = {hs.I32: torch.int32, hs.F32: torch.float32, hs.I64: torch.int64}
         outs = [self.empty(max(n, 1), dtypes[kind]) for kind in out_kinds]
         if n:
-            arr = (hs.hs_col * max(n_keys, 1))(*[c.as_hs() for c in cols])
             desc = (C.c_int32 * max(n_keys, 1))(*([0] * len(part_idx) + [0 if ascending else 1 for _, ascending in order_keys]))
-            kinds = (C.c_int32 * len(funcs))(*codes)
-            ptrs = (C.c_void_p * len(funcs))(*[o.data_ptr() for o in outs])
-            frame_codes = (C.c_int32 * len(funcs))(*[self.WINDOW_FRAMES[f] for f in frames])
-            vals = (hs.hs_col * len(funcs))(*[c.as_hs() if c is not None else hs.hs_col() for c in values])
-            steps = (C.c_int64 * len(funcs))(*[int(p[0]) if p is not None else 0 for p in params])
-            cells = (C.c_uint64 * len(funcs))(*[int(p[1]) if p is not None else 0 for p in params])
-            # the entry by the highest code present: each takes the arrays of the one before and asks for a larger workspace
-            lib, sized = self._raw_lib, (n, n_keys, 32 * max(n_keys, 1))
-            if "between" in frames:
-                before = (C.c_int64 * len(funcs))(*[int(o[0]) if o is not None else 0 for o in offsets])
-                after = (C.c_int64 * len(funcs))(*[int(o[1]) if o is not None else 0 for o in offsets])
-                name, ws_bytes, items = ("hs_window_frames", lib.hs_window_frames_ws_bytes(*sized, len(funcs)),
-                                         (kinds, frame_codes, vals, steps, cells, before, after, len(funcs)))
-            elif max(codes) <= hs.WIN_DENSE_RANK:
-                name, ws_bytes, items = "hs_window", lib.hs_window_ws_bytes(*sized), (kinds, len(funcs))
-            elif max(codes) <= hs.WIN_MAX:
-                name, ws_bytes, items = ("hs_window_agg", lib.hs_window_agg_ws_bytes(*sized, len(funcs)),
-                                         (kinds, frame_codes, vals, len(funcs)))
-            else:
-                name, ws_bytes, items = ("hs_window_nav", lib.hs_window_nav_ws_bytes(*sized, len(funcs)),
-                                         (kinds, frame_codes, vals, steps, cells, len(funcs)))
-            ws = self.workspace(ws_bytes)
-            hs.check(getattr(lib, name)(self.stream, arr, desc, len(part_idx), n_keys, n, *items, ptrs, ws.data_ptr(),
-                                        self.flags.data_ptr()), name)
+            ptrs = (C.c_void_p * len(items))(*[o.data_ptr() for o in outs])
+            pair = lambda ctype, pairs, at: (ctype * len(items))(*[int(p[at]) if p is not None else 0 for p in pairs])  # noqa: E731
+            params, offsets = [item.param for item in items], [item.offsets for item in items]
+            arrays = ((C.c_int32 * len(items))(*codes),
+                      (C.c_int32 * len(items))(*[self.WINDOW_FRAMES[item.frame] for item in items]),
+                      (hs.hs_col * len(items))(*[c.as_hs() if c is not None else hs.hs_col() for c in values]),
+                      pair(C.c_int64, params, 0), pair(C.c_uint64, params, 1), pair(C.c_int64, offsets, 0), pair(C.c_int64, offsets, 1))
+            slides = any(item.frame == "between" for item in items)
+            name, taken = next((name, taken) for name, top, between, taken in self.WINDOW_ENTRIES
+                               if max(codes) <= top and between >= slides)
+            sized = (n, n_keys, key_words) if name == "hs_window" else (n, n_keys, key_words, len(items))  # the oldest: no item count
+            ws = self.workspace(getattr(self._raw_lib, name + "_ws_bytes")(*sized))
+            hs.check(getattr(self._raw_lib, name)(self.stream, arr, desc, len(part_idx), n_keys, n, *arrays[:taken], len(items),
+                                                  ptrs, ws.data_ptr(), self.flags.data_ptr()), name)
         return [DCol(kind, out[:n], n) for kind, out in zip(out_kinds, outs)]
 
     def mark_first(self, batch: DBatch, key_indices: Sequence[int], sel: torch.Tensor | None = None, n_sel: int = 0,
@@ -1814,18 +1807,14 @@ class Device:
         ``distinct`` the call learns sizes on the host between its steps, so a run that contains it is not replayable."""
         batch = self.resolve(batch)
         n = batch.nrows
-        if self.rec is not None:
-            self.rec.poisoned = True
         cols = [batch.cols[i] for i in key_indices]
         if not 1 <= len(cols) <= hs.HS_MAX_COLS:
             raise DeviceError(f"COUNT(DISTINCT) compares 1 to {hs.HS_MAX_COLS} columns, not {len(cols)}")
-        if any(col.virtual for col in cols):
-            raise DeviceError("a virtual column of the fused join cannot be compared by COUNT(DISTINCT)")
+        cols, arr, key_words = self._key_cols(cols, "compared by COUNT(DISTINCT)")
         marks = self.empty(n, torch.int32)
         if n == 0:
             return DCol(hs.I32, marks, 0)
-        arr = (hs.hs_col * len(cols))(*[c.as_hs() for c in cols])
-        ws = self.workspace(self._raw_lib.hs_mark_first_ws_bytes(n, len(cols), 32 * len(cols)))
+        ws = self.workspace(self._raw_lib.hs_mark_first_ws_bytes(n, len(cols), key_words))
         hs.check(self._raw_lib.hs_mark_first(self.stream, arr, len(cols), n, sel.data_ptr() if sel is not None else None,
                                              int(n_sel) if sel is not None else 0, int(mode), marks.data_ptr(),
                                              ws.data_ptr(), self.flags.data_ptr()), "hs_mark_first")

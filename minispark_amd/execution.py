@@ -775,7 +775,7 @@ class HipExecutionEngine(ExecutionEngine):
         column per item - items with one (partition, order) spec share one sort and one launch sequence
         (Device.window) - the column handles are placed in the task's output order (no row is copied), and QUALIFY
         filters the rows through the WHERE machinery.  Keys are found by POSITION in the task's input schema."""
-        from .device import DBatch  # noqa: PLC0415
+        from .device import DBatch, WinItem  # noqa: PLC0415
 
         in_schema = list(sort.input_schema)
         batch = self.dev.resolve(self._quantise_batch(self.dev.resolve(batch), in_schema))
@@ -786,31 +786,26 @@ class HipExecutionEngine(ExecutionEngine):
         for item in sort.windows:
             specs.setdefault(item.spec(), []).append(item)
         by_name = dict(zip(in_names, batch.cols))
+
+        def record(item: Any) -> Any:  # the argument by position; (k, the default as a cell's bits) or (n, 0); (n, m)
+            param = None
+            if item.kind in ("lag", "lead"):
+                param = (item.offset, item.default_bits(item.arg.infer_type(in_schema)))
+            elif item.kind == "ntile":
+                param = (item.buckets, 0)
+            return WinItem(item.kind, item.frame, None if item.arg is None else in_names.index(item.arg.name), param,
+                           (item.preceding, item.following) if item.frame == "between" else None)
+
         for items in specs.values():
             part = [in_names.index(col.name) for col in items[0].partition_by]
             order = [(in_names.index(col.name), ascending) for col, ascending in items[0].order_by]
-            extra = ()
-            if any(item.kind not in item.RANKING for item in items):  # the frames, and the arguments by position too
-                extra = ([item.frame for item in items],
-                         [None if item.arg is None else in_names.index(item.arg.name) for item in items])
-            if any(item.kind in item.NAVIGATION for item in items):  # (k, the default as a cell's bits) or (n, 0)
-                extra = (*extra, [self._window_param(item, in_schema) for item in items])
-            if any(item.frame == "between" for item in items):  # (n PRECEDING, m FOLLOWING) of the sliding items
-                extra = (*extra, *[None] * (3 - len(extra)),
-                         [(item.preceding, item.following) if item.frame == "between" else None for item in items])
-            for item, col in zip(items, self.dev.window(batch, part, order, [item.kind for item in items], *extra)):
+            for item, col in zip(items, self.dev.window(batch, part, order, [record(item) for item in items])):
                 by_name[item.name] = col
         out_schema = list(sort.inferred_schema)
         batch = DBatch(out_schema, [by_name[name] for name, _ in out_schema], batch.nrows)
         if sort.qualify is not None:
             batch = self.dev.resolve(self._materialise(batch, [sort.qualify]))
         return batch
-
-    @staticmethod
-    def _window_param(item: Any, in_schema: Schema) -> tuple[int, int] | None:
-        if item.kind in ("lag", "lead"):
-            return item.offset, item.default_bits(item.arg.infer_type(in_schema))
-        return (item.buckets, 0) if item.kind == "ntile" else None
 
     def _consume(self, batch: Any, consumers: Sequence[Any]) -> Any:
         """Run a stage's consumer tasks (filters, projections, aggregates) over one batch."""

@@ -7,10 +7,8 @@ from __future__ import annotations
 
 import json
 import os
-import socket
 import subprocess
 import sys
-import time
 
 import numpy as np
 import pytest
@@ -19,6 +17,7 @@ from minispark_amd.constants import ColumnType as T
 from oracle.compare import assert_rows_match
 from tests.conftest import ROOT, load_golden
 from tests.count_distinct_model import counts, marks
+from tests.ranks import run_ranks
 from tests.test_gpu_distinct import _constants, py_values, upload
 
 pytestmark = pytest.mark.gpu
@@ -642,27 +641,8 @@ def test_a_join_whose_inputs_stream_still_hands_the_marks_the_whole_join():
 
 
 def test_two_ranks_refuse_on_every_rank_and_go_on(tmp_path):
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "ranks.json"
-    procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "tests" / "count_distinct_worker.py"), "ranks", str(out)],
-                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    deadline = time.monotonic() + 240
-    while (time.monotonic() < deadline and any(p.poll() is None for p in procs)
-           and all(p.poll() in (None, 0) for p in procs)):
-        try:
-            next(p for p in procs if p.poll() is None).wait(timeout=0.5)
-        except subprocess.TimeoutExpired:
-            pass
-    for p in procs:  # the first failure (or the time limit) ends the other rank too
-        if p.poll() is None:
-            p.kill()
-    logs = [p.communicate()[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(f"--- rank {r} ---\n{log[-2500:]}" for r, log in enumerate(logs))
+    run_ranks([ROOT / "tests" / "count_distinct_worker.py", "ranks", out])
     results = [json.loads((tmp_path / f"ranks.json.rank{rank}").read_text()) for rank in range(2)]
     assert all("COUNT(DISTINCT) runs on one GPU" in r["refused"] for r in results)
     assert len(results[0]["rows"]) == 3 and results[1]["rows"] == []  # rank 0 owns the result of the query that ran

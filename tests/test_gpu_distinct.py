@@ -8,12 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import json
 import math
-import os
 import re
-import socket
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
@@ -21,6 +16,7 @@ import pytest
 from minispark_amd.constants import ColumnType as T
 from tests.conftest import ROOT, load_golden
 from tests.queries import case_by_name
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -402,27 +398,8 @@ def test_two_ranks_deduplicate_the_gathered_result_on_rank_0(tmp_path):
     from minispark_amd.sql import Col, Functions, Lit
     from minispark_amd.workloads import api_namespace
 
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "rows.json"
-    procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "tests" / "distinct_worker.py"), str(out)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    deadline = time.monotonic() + 240
-    while (time.monotonic() < deadline and any(p.poll() is None for p in procs)
-           and all(p.poll() in (None, 0) for p in procs)):
-        try:
-            next(p for p in procs if p.poll() is None).wait(timeout=0.5)
-        except subprocess.TimeoutExpired:
-            pass
-    for p in procs:  # the first failure (or the time limit) ends the other rank too
-        if p.poll() is None:
-            p.kill()
-    logs = [p.communicate()[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(f"--- rank {r} ---\n{log[-2500:]}" for r, log in enumerate(logs))
+    run_ranks([ROOT / "tests" / "result_rows_worker.py", "tests.test_gpu_distinct", "two_rank_frame", "q1_multiblock", out])
     api = api_namespace(lambda: DataFrame(object()), Col, Functions, Lit)
     paths = load_golden("q1_multiblock")["paths"]
     plain = api.DataFrame().table(paths["lineitem"]).select(api.Col("l_shipmode"), api.Col("l_returnflag"))

@@ -11,10 +11,8 @@ from __future__ import annotations
 
 import json
 import os
-import socket
 import subprocess
 import sys
-import time
 from pathlib import Path
 
 import numpy as np
@@ -26,6 +24,7 @@ from minispark_amd.io import BlockFile, StrCol
 from minispark_amd.sql import Col, Functions as F, Lit
 from oracle.py_engine import run_query
 from tests.conftest import assert_rows_match
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -372,27 +371,8 @@ def test_order_by_limit_and_sql_on_top(engine, tables, wanted):
 
 # 11: two ranks over gloo on one GPU
 def test_two_ranks(tables, wanted, tmp_path):
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "rows.json"
-    procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "tests" / "global_agg_worker.py"), "ranks", str(out), tables[0]],
-                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    deadline = time.monotonic() + 240
-    while (time.monotonic() < deadline and any(p.poll() is None for p in procs)
-           and all(p.poll() in (None, 0) for p in procs)):
-        try:
-            next(p for p in procs if p.poll() is None).wait(timeout=0.5)
-        except subprocess.TimeoutExpired:
-            pass
-    for p in procs:  # the first failure (or the time limit) ends the other rank too
-        if p.poll() is None:
-            p.kill()
-    logs = [p.communicate()[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(f"--- rank {r} ---\n{log[-2500:]}" for r, log in enumerate(logs))
+    run_ranks([ROOT / "tests" / "global_agg_worker.py", "ranks", out, tables[0]])
     got = json.loads(out.read_text())
     for name in ("none", "empties_a_middle_unit", "empties_everything"):
         rows = [{k: (float.fromhex(v) if isinstance(v, str) else v) for k, v in r.items()} for r in got[name]]

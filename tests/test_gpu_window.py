@@ -5,20 +5,17 @@ model applied to the rows the same engine returns for the same query without its
 
 from __future__ import annotations
 
-import ctypes as C
 import json
-import os
-import socket
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 from minispark_amd.constants import ColumnType as T
 from tests.conftest import ROOT, load_golden
-from tests.test_gpu_distinct import _constants, py_values, tuples, upload
+from tests.ranks import run_ranks
+from tests.test_gpu_count_distinct import hs_mark_first
+from tests.test_gpu_distinct import _constants, hs_distinct, py_values, tuples, upload
+from tests.window_abi import call_window
 from tests.window_model import window_model
 
 pytestmark = pytest.mark.gpu
@@ -45,22 +42,9 @@ def dev():
 
 # ---- C ABI --------------------------------------------------------------------------------------------------------------
 def hs_window(dev, cols, descending, n_part, funcs, n, n_keys=None):
-    """The entry point itself -> (return code, [one int32 array per function, input order])."""
-    import torch
-
-    from minispark_amd import hipspark as hs
-
-    lib = dev._raw_lib
-    n_keys = len(cols) if n_keys is None else n_keys
-    arr = (hs.hs_col * max(len(cols), 1))(*[c.as_hs() for c in cols])
-    desc = (C.c_int32 * max(n_keys, 1))(*[int(d) for d in descending])
-    kinds = (C.c_int32 * len(funcs))(*funcs)
-    outs = [torch.full((max(n, 1),), -7, dtype=torch.int32, device=dev.device) for _ in funcs]
-    ptrs = (C.c_void_p * len(funcs))(*[o.data_ptr() for o in outs])
-    ws = torch.empty(int(lib.hs_window_ws_bytes(n, n_keys, 32 * max(n_keys, 1))) + 256, dtype=torch.uint8, device=dev.device)
-    rc = lib.hs_window(dev.stream, arr, desc, n_part, n_keys, n, kinds, len(funcs), ptrs, ws.data_ptr(), None)
-    torch.cuda.synchronize()
-    return rc, [o[:n].cpu().numpy() for o in outs]
+    """The entry point itself (tests/window_abi.py) -> (return code, [one int32 array per function, input order])."""
+    rc, got, _ = call_window(dev, "hs_window", cols, descending, n_part, [(f,) for f in funcs], n, n_keys)
+    return rc, [o.view(np.int32) for o in got]
 
 
 def check(dev, partition, order, funcs=(ROW_NUMBER, RANK, DENSE_RANK), coded=()):
@@ -187,6 +171,36 @@ def test_one_partition_across_a_round_of_the_tile_scan(dev):
     check(dev, [(ids[order], T.INTEGER)], [(values[order], T.INTEGER, True)])
 
 
+RUN_KEYS = {  # n -> [(values, type)]: few values per column, so that rows repeat
+    "one_word": lambda rng, n: [(rng.integers(-3, 4, n), T.INTEGER)],
+    "two_words": lambda rng, n: [(rng.integers(0, 3, n), T.INTEGER), ((rng.integers(0, 3, n) << 21) + (1 << 44), T.TIMESTAMP),
+                                 (rng.integers(-1, 2, n), T.INTEGER)],
+    "string_and_integer": lambda rng, n: [([STRINGS[v] for v in rng.integers(0, len(STRINGS), n)], T.STRING),
+                                          (rng.integers(0, 3, n), T.INTEGER)],
+}
+
+
+@pytest.mark.parametrize("keys", RUN_KEYS)
+def test_the_three_readers_of_the_sorted_runs_see_the_same_runs(dev, keys):
+    """hs_mark_first (its sort path), hs_distinct and the window entries take the sorted rows through one routine: over
+    the same key columns, as ORDER BY keys of one partition, the first-occurrence marks are the rows that lead their
+    peers, the surviving rows are the marked ones, and there are as many as DENSE_RANK counts.  Sizes: the wave step, the
+    wave's share and the tile of the two heads kernels, and their neighbours."""
+    for n in (1, 2, 64, 65, 512, 513, OB_TILE, OB_TILE + 1, 2 * OB_TILE + 1):
+        columns = RUN_KEYS[keys](np.random.default_rng(2400 + n), n)
+        cols = [upload(dev, v, t) for v, t in columns]
+        rc, marks = hs_mark_first(dev, cols, n, mode=1)
+        assert rc == 0, dev._raw_lib.hs_last_error()
+        rc, (row_number, rank, dense_rank) = hs_window(dev, cols, [0] * len(cols), 0, [ROW_NUMBER, RANK, DENSE_RANK], n)
+        assert rc == 0, dev._raw_lib.hs_last_error()
+        rc, rows = hs_distinct(dev, cols, n)
+        assert rc == 0, dev._raw_lib.hs_last_error()
+        assert marks == (row_number == rank).astype(np.int32).tolist(), (keys, n)
+        assert rows == np.nonzero(marks)[0].tolist(), (keys, n)
+        assert len(rows) == dense_rank.max(), (keys, n)
+        assert n < 64 or len(rows) < n, "rows repeat"
+
+
 def test_argument_errors_are_codes_and_nothing_is_launched(dev):
     col = upload(dev, [1, 2, 3], T.INTEGER)
     lib = dev._raw_lib
@@ -309,7 +323,7 @@ def test_two_items_share_a_spec_and_one_has_another_in_the_middle_of_the_select_
                                 ("row_number", "row_number", [], [("l_orderkey", False)])])
     calls = []
     window = type(engine.dev).window
-    monkeypatch.setattr(type(engine.dev), "window", lambda self, *a: calls.append(a[3]) or window(self, *a))
+    monkeypatch.setattr(type(engine.dev), "window", lambda self, *a: calls.append([i.func for i in a[3]]) or window(self, *a))
     got = engine.sql("SELECT l_returnflag, RANK() OVER (PARTITION BY l_returnflag ORDER BY l_quantity) AS a, l_orderkey, "
                      "ROW_NUMBER() OVER (ORDER BY l_orderkey DESC), DENSE_RANK() OVER (PARTITION BY l_returnflag ORDER BY "
                      f"l_quantity ASC) AS b, l_quantity FROM '{LINEITEM()}';").collect()
@@ -354,27 +368,8 @@ def two_rank_frame(api, paths):
 
 
 def test_two_ranks_rank_the_gathered_result_on_rank_0(tmp_path, engine, api):
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "rows.json"
-    procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "tests" / "window_worker.py"), str(out)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    deadline = time.monotonic() + 240
-    while (time.monotonic() < deadline and any(p.poll() is None for p in procs)
-           and all(p.poll() in (None, 0) for p in procs)):
-        try:
-            next(p for p in procs if p.poll() is None).wait(timeout=0.5)
-        except subprocess.TimeoutExpired:
-            pass
-    for p in procs:  # the first failure (or the time limit) ends the other rank too
-        if p.poll() is None:
-            p.kill()
-    logs = [p.communicate()[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(f"--- rank {r} ---\n{log[-2500:]}" for r, log in enumerate(logs))
+    run_ranks([ROOT / "tests" / "result_rows_worker.py", "tests.test_gpu_window", "two_rank_frame", "q1_multiblock", out])
     one_rank = two_rank_frame(api, load_golden("q1_multiblock")["paths"]).collect()
     got = [tuple(r) for r in json.loads(out.read_text())]
     assert got == tuples(one_rank) and len(got) == 35

@@ -6,28 +6,23 @@ applied to the rows the same engine returns for the query without its window ite
 
 from __future__ import annotations
 
-import ctypes as C
 import json
 import math
-import os
-import socket
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 from minispark_amd.constants import ColumnType as T
 from tests.conftest import ROOT, load_golden
+from tests.ranks import run_ranks
 from tests.test_gpu_distinct import py_values, tuples, upload
 from tests.test_gpu_window import DENSE_RANK, OB_TILE, RANK, ROW_NUMBER, SIZES, hs_window, layouts
+from tests.window_abi import call_window
 from tests.window_agg_model import FRAMES, window_agg_model
 
 pytestmark = pytest.mark.gpu
 
 COUNT, SUM, AVG, MIN, MAX = 3, 4, 5, 6, 7
-FRAME = {"partition": 0, "range": 1, "rows": 2}
 INT_OVERFLOW, FLT_OVERFLOW = 0x2, 0x4
 
 
@@ -42,30 +37,11 @@ def dev():
 def hs_window_agg(dev, cols, descending, n_part, items, n, n_keys=None):
     """The entry point itself.  items = [(function, frame name or None, value column or None)] -> (return code, [one
     array per item, input order: float32 where the item's value is FLOAT, else int32], the status word)."""
-    import torch
-
     from minispark_amd import hipspark as hs
 
-    lib = dev._raw_lib
-    n_keys = len(cols) if n_keys is None else n_keys
-    arr = (hs.hs_col * max(len(cols), 1))(*[c.as_hs() for c in cols])
-    desc = (C.c_int32 * max(n_keys, 1))(*[int(d) for d in descending])
-    funcs = (C.c_int32 * len(items))(*[f for f, _, _ in items])
-    frames = (C.c_int32 * len(items))(*[FRAME.get(fr, 0) if isinstance(fr, (str, type(None))) else fr for _, fr, _ in items])
-    values = (hs.hs_col * len(items))(*[v.as_hs() if v is not None else hs.hs_col() for _, _, v in items])
-    outs = [torch.full((max(n, 1),), -7, dtype=torch.int32, device=dev.device) for _ in items]
-    ptrs = (C.c_void_p * len(items))(*[o.data_ptr() for o in outs])
-    flags = torch.zeros(2, dtype=torch.int32, device=dev.device)
-    ws = torch.empty(int(lib.hs_window_agg_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(items))) + 256, dtype=torch.uint8,
-                     device=dev.device)
-    rc = lib.hs_window_agg(dev.stream, arr, desc, n_part, n_keys, n, funcs, frames, values, len(items), ptrs, ws.data_ptr(),
-                           flags.data_ptr())
-    torch.cuda.synchronize()
-    got = []
-    for (f, _, v), o in zip(items, outs):
-        is_float = f == AVG or (f in (SUM, MIN, MAX) and v is not None and v.kind == hs.F32)
-        got.append(o[:n].cpu().numpy().view(np.float32 if is_float else np.int32))
-    return rc, got, int(flags[0].item())
+    rc, got, flags = call_window(dev, "hs_window_agg", cols, descending, n_part, items, n, n_keys)
+    is_float = lambda f, v: f == AVG or (f in (SUM, MIN, MAX) and v is not None and v.kind == hs.F32)  # noqa: E731
+    return rc, [o.view(np.float32 if is_float(f, v) else np.int32) for (f, _, v), o in zip(items, got)], flags
 
 
 def keys_of(dev, ids, values):
@@ -411,7 +387,7 @@ def test_an_aggregate_next_to_row_number_with_distinct_order_by_and_limit(engine
     want = sorted(kept, key=lambda r: (-r[3], r[0], r[2]))[:9]
     calls = []
     window = type(engine.dev).window
-    monkeypatch.setattr(type(engine.dev), "window", lambda self, *a: calls.append(a[3]) or window(self, *a))
+    monkeypatch.setattr(type(engine.dev), "window", lambda self, *a: calls.append([i.func for i in a[3]]) or window(self, *a))
     over = "OVER (PARTITION BY l_shipmode ORDER BY l_returnflag)"
     got = engine.sql(f"SELECT DISTINCT l_shipmode, l_returnflag, ROW_NUMBER() {over} AS rn, COUNT() {over} AS c "
                      f"FROM '{LINEITEM()}' QUALIFY rn <= 400 ORDER BY c DESC, l_shipmode, rn LIMIT 9;").collect()
@@ -431,27 +407,8 @@ def two_rank_frame(api, paths):
 
 
 def test_two_ranks_aggregate_the_gathered_result_on_rank_0(tmp_path, engine, api):
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "rows.json"
-    procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "tests" / "window_agg_worker.py"), str(out)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    deadline = time.monotonic() + 240
-    while (time.monotonic() < deadline and any(p.poll() is None for p in procs)
-           and all(p.poll() in (None, 0) for p in procs)):
-        try:
-            next(p for p in procs if p.poll() is None).wait(timeout=0.5)
-        except subprocess.TimeoutExpired:
-            pass
-    for p in procs:  # the first failure (or the time limit) ends the other rank too
-        if p.poll() is None:
-            p.kill()
-    logs = [p.communicate()[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(f"--- rank {r} ---\n{log[-2500:]}" for r, log in enumerate(logs))
+    run_ranks([ROOT / "tests" / "result_rows_worker.py", "tests.test_gpu_window_agg", "two_rank_frame", "q1_multiblock", out])
     one_rank = two_rank_frame(api, load_golden("q1_multiblock")["paths"]).collect()
     got = [tuple(r) for r in json.loads(out.read_text())]
     assert got == tuples(one_rank) and len(got) == 35

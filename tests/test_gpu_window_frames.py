@@ -7,29 +7,24 @@ the query without its window items."""
 
 from __future__ import annotations
 
-import ctypes as C
 import json
 import math
-import os
-import socket
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 from minispark_amd.constants import ColumnType as T
 from tests.conftest import ROOT, load_golden
+from tests.ranks import run_ranks
 from tests.test_gpu_distinct import py_values, tuples, upload
 from tests.test_gpu_window import FLOATS, OB_TILE, ROW_NUMBER, hs_window
 from tests.test_gpu_window_agg import AVG, COUNT, FLT_OVERFLOW, INT_OVERFLOW, MAX, MIN, SUM, avg32, f32, hs_window_agg, ulp32
-from tests.test_gpu_window_nav import FIRST_VALUE, LAG, LAST_VALUE, LEAD, NTILE, SENTINEL, SLACK, cells_of, hs_window_nav, untouched
+from tests.test_gpu_window_nav import FIRST_VALUE, LAG, LAST_VALUE, LEAD, NTILE, cells_of, hs_window_nav, untouched
+from tests.window_abi import call_window
 from tests.window_frame_model import window_frame_exact, window_frame_model
 
 pytestmark = pytest.mark.gpu
 
-FRAME = {"partition": 0, "range": 1, "rows": 2, "between": 3}
 K_MAX = (1 << 31) - 1
 ROWS = [1, 2, OB_TILE - 1, OB_TILE, OB_TILE + 1, 3 * OB_TILE + 5]
 # CURRENT ROW alone; one neighbour on either side; both sides; a block of one tile less a row / one tile more a row; W = 1024,
@@ -49,38 +44,9 @@ def hs_window_frames(dev, cols, descending, n_part, items, n, n_keys=None, no_pr
     """The entry point itself.  items = [(function, frame name or code, value column or None, n PRECEDING, m FOLLOWING[, k,
     default bits])] -> (return code, [one array per item, input order: the cells' bits as uint32, uint64 for an 8-byte
     argument], the status word).  Every output has a sentinel in SLACK cells behind the rows, which must stay untouched."""
-    import torch
-
-    from minispark_amd import hipspark as hs
-
-    lib = dev._raw_lib
-    n_keys = len(cols) if n_keys is None else n_keys
-    field = lambda it, k: int(it[k]) if len(it) > k and it[k] is not None else 0  # noqa: E731
-    arr = (hs.hs_col * max(len(cols), 1))(*[c.as_hs() for c in cols])
-    desc = (C.c_int32 * max(n_keys, 1))(*[int(d) for d in descending])
-    funcs = (C.c_int32 * len(items))(*[it[0] for it in items])
-    frames = (C.c_int32 * len(items))(*[FRAME.get(it[1], 0) if isinstance(it[1], (str, type(None))) else it[1] for it in items])
-    values = (hs.hs_col * len(items))(*[it[2].as_hs() if it[2] is not None else hs.hs_col() for it in items])
-    preceding = (C.c_int64 * len(items))(*[field(it, 3) for it in items])
-    following = (C.c_int64 * len(items))(*[field(it, 4) for it in items])
-    params = (C.c_int64 * len(items))(*[field(it, 5) for it in items])
-    defaults = (C.c_uint64 * len(items))(*[field(it, 6) for it in items])
-    wide = [LAG <= it[0] <= LAST_VALUE and it[2] is not None and it[2].kind == hs.I64 for it in items]
-    outs = [torch.full((n + SLACK,), SENTINEL, dtype=torch.int64 if w else torch.int32, device=dev.device) for w in wide]
-    ptrs = (C.c_void_p * len(items))(*[o.data_ptr() for o in outs])
-    flags = torch.zeros(2, dtype=torch.int32, device=dev.device)
-    ws = torch.empty(int(lib.hs_window_frames_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(items))) + 256, dtype=torch.uint8,
-                     device=dev.device)
-    rc = lib.hs_window_frames(dev.stream, arr, desc, n_part, n_keys, n, funcs, frames, values, params, defaults,
-                              None if no_preceding else preceding, None if no_following else following, len(items), ptrs,
-                              ws.data_ptr(), flags.data_ptr())
-    torch.cuda.synchronize()
-    got = []
-    for w, o in zip(wide, outs):
-        host = o.cpu().numpy()
-        assert np.all(host[n:] == SENTINEL), "cells behind the rows were written"
-        got.append(host[:n].view(np.uint64 if w else np.uint32))
-    return rc, got, int(flags[0].item())
+    omit = [name for name, off in (("preceding", no_preceding), ("following", no_following)) if off]
+    behind = [(*it[:3], *it[5:7], *[None] * (2 - len(it[5:7])), *it[3:5]) for it in items]  # the harness: k, default, then n, m
+    return call_window(dev, "hs_window_frames", cols, descending, n_part, behind, n, n_keys, omit)
 
 
 def said(dev):
@@ -467,14 +433,16 @@ def test_a_three_row_moving_average_per_key_with_qualify_by_sql_and_by_the_api(e
     want = [r for r in ranked if r["l_quantity"] > r["ma"]]
     calls = []
     window = type(engine.dev).window
-    monkeypatch.setattr(type(engine.dev), "window", lambda self, *a: calls.append(a[3:]) or window(self, *a))
+    monkeypatch.setattr(type(engine.dev), "window", lambda self, *a: calls.append(
+        [(i.func, i.frame, i.value, i.param, i.offsets) for i in a[3]]) or window(self, *a))
     over = "PARTITION BY l_shipmode ORDER BY l_orderkey"
     got = engine.sql(f"SELECT l_shipmode, l_orderkey, l_quantity, AVG(l_quantity) OVER ({over} ROWS BETWEEN 2 PRECEDING AND CURRENT ROW) "
                      f"AS ma, SUM(l_orderkey) OVER ({over} ROWS BETWEEN 1 PRECEDING AND 1 FOLLOWING) AS around, "
                      f"FIRST_VALUE(l_quantity) OVER ({over} ROWS BETWEEN 2 PRECEDING AND CURRENT ROW) AS before "
                      f"FROM '{LINEITEM()}' QUALIFY l_quantity > ma;").collect()
     assert got == want and 1500 < len(got) < 4500
-    assert calls == [(["avg", "sum", "first_value"], ["between"] * 3, [2, 1, 2], [None] * 3, [(2, 0), (1, 1), (2, 0)])]  # one sort, one call
+    assert calls == [[("avg", "between", 2, None, (2, 0)), ("sum", "between", 1, None, (1, 1)),
+                      ("first_value", "between", 2, None, (2, 0))]]  # one sort, one call
     keys = dict(partition_by=[C_("l_shipmode")], order_by=[C_("l_orderkey")])
     frame = (api.DataFrame().table(LINEITEM()).select(C_("l_shipmode"), C_("l_orderkey"), C_("l_quantity"))
              .window(F.avg(C_("l_quantity")).over(**keys, rows=(2, 0)).alias("ma"),
@@ -522,27 +490,8 @@ def two_rank_frame(api, paths):
 
 
 def test_two_ranks_slide_over_the_gathered_result_on_rank_0(tmp_path, engine, api):
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "rows.json"
-    procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "tests" / "window_frames_worker.py"), str(out)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    deadline = time.monotonic() + 240
-    while (time.monotonic() < deadline and any(p.poll() is None for p in procs)
-           and all(p.poll() in (None, 0) for p in procs)):
-        try:
-            next(p for p in procs if p.poll() is None).wait(timeout=0.5)
-        except subprocess.TimeoutExpired:
-            pass
-    for p in procs:  # the first failure (or the time limit) ends the other rank too
-        if p.poll() is None:
-            p.kill()
-    logs = [p.communicate()[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(f"--- rank {r} ---\n{log[-2500:]}" for r, log in enumerate(logs))
+    run_ranks([ROOT / "tests" / "result_rows_worker.py", "tests.test_gpu_window_frames", "two_rank_frame", "q1_multiblock", out])
     one_rank = two_rank_frame(api, load_golden("q1_multiblock")["paths"]).collect()
     got = [tuple(r) for r in json.loads(out.read_text())]
     assert got == tuples(one_rank) and len(got) == 35

@@ -6,13 +6,7 @@ returns for the query without its window items."""
 
 from __future__ import annotations
 
-import ctypes as C
 import json
-import os
-import socket
-import subprocess
-import sys
-import time
 from datetime import datetime
 
 import numpy as np
@@ -20,18 +14,18 @@ import pytest
 
 from minispark_amd.constants import ColumnType as T
 from tests.conftest import ROOT, load_golden
+from tests.ranks import run_ranks
 from tests.test_gpu_distinct import py_values, tuples, upload
 from tests.test_gpu_window import (DENSE_RANK, FLOATS, OB_TILE, ROW_NUMBER, SIZES, hs_window, layouts, shape_i32_i32,
                                    shape_no_partition, shape_timestamp_i32)
 from tests.test_gpu_window_agg import AVG, COUNT, SUM, hs_window_agg
+from tests.window_abi import SENTINEL, call_window
 from tests.window_nav_model import FRAMES, window_nav_model, window_nav_plan
 
 pytestmark = pytest.mark.gpu
 
 LAG, LEAD, FIRST_VALUE, LAST_VALUE, NTILE = 8, 9, 10, 11, 12
 NAMES = {LAG: "lag", LEAD: "lead", FIRST_VALUE: "first_value", LAST_VALUE: "last_value", NTILE: "ntile"}
-FRAME = {"partition": 0, "range": 1, "rows": 2}
-SENTINEL, SLACK = -7, 16
 K_MAX = (1 << 31) - 1
 # a default per cell type that no cell of the tests holds: an INTEGER, a NaN with a payload, a TIMESTAMP
 DEFAULTS = {T.INTEGER: 0xDEADBEEF, T.FLOAT: 0x7FC12345, T.TIMESTAMP: 0x8000000000000123}
@@ -49,34 +43,8 @@ def hs_window_nav(dev, cols, descending, n_part, items, n, n_keys=None, no_param
     """The entry point itself.  items = [(function, frame name / code or None, value column or None, k or n, default bits)]
     -> (return code, [one array per item, input order: the cells' bits as uint32, uint64 for an 8-byte argument], the
     status word).  Every output is allocated with a sentinel and SLACK cells behind the rows, which must stay untouched."""
-    import torch
-
-    from minispark_amd import hipspark as hs
-
-    lib = dev._raw_lib
-    n_keys = len(cols) if n_keys is None else n_keys
-    arr = (hs.hs_col * max(len(cols), 1))(*[c.as_hs() for c in cols])
-    desc = (C.c_int32 * max(n_keys, 1))(*[int(d) for d in descending])
-    funcs = (C.c_int32 * len(items))(*[it[0] for it in items])
-    frames = (C.c_int32 * len(items))(*[FRAME.get(it[1], 0) if isinstance(it[1], (str, type(None))) else it[1] for it in items])
-    values = (hs.hs_col * len(items))(*[it[2].as_hs() if it[2] is not None else hs.hs_col() for it in items])
-    params = (C.c_int64 * len(items))(*[int(it[3]) if len(it) > 3 and it[3] is not None else 0 for it in items])
-    defaults = (C.c_uint64 * len(items))(*[int(it[4]) if len(it) > 4 and it[4] is not None else 0 for it in items])
-    wide = [LAG <= it[0] <= LAST_VALUE and it[2] is not None and it[2].kind == hs.I64 for it in items]
-    outs = [torch.full((n + SLACK,), SENTINEL, dtype=torch.int64 if w else torch.int32, device=dev.device) for w in wide]
-    ptrs = (C.c_void_p * len(items))(*[o.data_ptr() for o in outs])
-    flags = torch.zeros(2, dtype=torch.int32, device=dev.device)
-    ws = torch.empty(int(lib.hs_window_nav_ws_bytes(n, n_keys, 32 * max(n_keys, 1), len(items))) + 256, dtype=torch.uint8,
-                     device=dev.device)
-    rc = lib.hs_window_nav(dev.stream, arr, desc, n_part, n_keys, n, funcs, frames, values, None if no_params else params,
-                           None if no_defaults else defaults, len(items), ptrs, ws.data_ptr(), flags.data_ptr())
-    torch.cuda.synchronize()
-    got = []
-    for w, o in zip(wide, outs):
-        host = o.cpu().numpy()
-        assert np.all(host[n:] == SENTINEL), "cells behind the rows were written"
-        got.append(host[:n].view(np.uint64 if w else np.uint32))
-    return rc, got, int(flags[0].item())
+    omit = [name for name, off in (("params", no_params), ("defaults", no_defaults)) if off]
+    return call_window(dev, "hs_window_nav", cols, descending, n_part, items, n, n_keys, omit)
 
 
 def untouched(out):
@@ -395,7 +363,7 @@ def test_one_spec_of_ranking_aggregate_and_navigation_items_is_one_call(engine, 
                                   ("first", "first_value", "l_extendedprice", [], [("l_orderkey", True)], dict(frame="range"))])
     calls = []
     window = type(engine.dev).window
-    monkeypatch.setattr(type(engine.dev), "window", lambda self, *a: calls.append(a[3]) or window(self, *a))
+    monkeypatch.setattr(type(engine.dev), "window", lambda self, *a: calls.append([i.func for i in a[3]]) or window(self, *a))
     inside = "PARTITION BY l_shipmode ORDER BY l_orderkey, l_extendedprice"
     got = engine.sql(f"SELECT l_shipmode, l_orderkey, l_extendedprice, ROW_NUMBER() OVER ({inside}) AS rn, "
                      f"SUM(l_orderkey) OVER ({inside} ROWS UNBOUNDED PRECEDING) AS upto, LAG(l_orderkey, 1, -1) OVER ({inside}) AS prev, "
@@ -443,27 +411,8 @@ def two_rank_frame(api, paths):
 
 
 def test_two_ranks_navigate_the_gathered_result_on_rank_0(tmp_path, engine, api):
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
     out = tmp_path / "rows.json"
-    procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "tests" / "window_nav_worker.py"), str(out)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    deadline = time.monotonic() + 240
-    while (time.monotonic() < deadline and any(p.poll() is None for p in procs)
-           and all(p.poll() in (None, 0) for p in procs)):
-        try:
-            next(p for p in procs if p.poll() is None).wait(timeout=0.5)
-        except subprocess.TimeoutExpired:
-            pass
-    for p in procs:  # the first failure (or the time limit) ends the other rank too
-        if p.poll() is None:
-            p.kill()
-    logs = [p.communicate()[0].decode() for p in procs]
-    assert all(p.returncode == 0 for p in procs), "\n".join(f"--- rank {r} ---\n{log[-2500:]}" for r, log in enumerate(logs))
+    run_ranks([ROOT / "tests" / "result_rows_worker.py", "tests.test_gpu_window_nav", "two_rank_frame", "q1_multiblock", out])
     one_rank = two_rank_frame(api, load_golden("q1_multiblock")["paths"]).collect()
     got = [tuple(r) for r in json.loads(out.read_text())]
     assert got == tuples(one_rank) and len(got) == 35

@@ -304,9 +304,10 @@ def test_window_rows_hands_the_offsets_over_and_older_queries_make_the_call_they
         def resolve(self, batch):
             return batch
 
-        def window(self, batch, *args):
-            self.calls.append(args)
-            return [f"col{i}" for i in range(len(args[2]))]
+        def window(self, batch, part, order, items):
+            self.calls.append((part, order, [i.func for i in items], [i.frame for i in items], [i.value for i in items],
+                               [i.param for i in items], [i.offsets for i in items]))
+            return [f"col{i}" for i in range(len(items))]
 
     class Batch:
         nrows, cols = 5, ["k", "v"]
@@ -329,12 +330,12 @@ def test_window_rows_hands_the_offsets_over_and_older_queries_make_the_call_they
     assert calls == [([0], [(1, True)], ["row_number", "sum", "lag", "last_value"], [None, "between", None, "between"],
                       [None, 1, 1, 1], [None, None, (1, 0), None], [None, (2, 1), None, (0, 3)])]
     calls = run(F.count().over(**keys, rows=(1, 1)))
-    assert calls == [([0], [(1, True)], ["count"], ["between"], [None], None, [(1, 1)])]
-    # without a sliding item: the arguments of before, nothing behind them
-    assert run(F.row_number().over(**keys)) == [([0], [(1, True)], ["row_number"])]
-    assert run(F.sum(Col("v")).over(**keys, rows=True)) == [([0], [(1, True)], ["sum"], ["rows"], [1])]
+    assert calls == [([0], [(1, True)], ["count"], ["between"], [None], [None], [(1, 1)])]
+    # without a sliding item: the fields of before, no offsets
+    assert run(F.row_number().over(**keys)) == [([0], [(1, True)], ["row_number"], [None], [None], [None], [None])]
+    assert run(F.sum(Col("v")).over(**keys, rows=True)) == [([0], [(1, True)], ["sum"], ["rows"], [1], [None], [None])]
     assert run(F.sum(Col("v")).over(**keys), F.lead(Col("v"), 2, 7).over(**keys)) == \
-        [([0], [(1, True)], ["sum", "lead"], ["range", None], [1, 1], [None, (2, 7)])]
+        [([0], [(1, True)], ["sum", "lead"], ["range", None], [1, 1], [None, (2, 7)], [None, None])]
 
 
 # ---- ABI ---------------------------------------------------------------------------------------------------------------
