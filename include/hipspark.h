@@ -527,6 +527,31 @@ int hs_join_dense_count(void* stream, const int32_t* probe_keys, int64_t n_probe
                         const uint32_t* words, const uint32_t* rows, const uint32_t* list_count, int64_t* counts, void* aux);
 int hs_join_dense_fill(void* stream, int64_t n_probe, const uint32_t* rows, const void* aux, const int64_t* out_start,
                        int64_t* out_left, int64_t* out_right);
+/* ---- key sets for LEFT SEMI / LEFT ANTI joins on INTEGER keys (csrc/hs_radix.hip) -----------------------
+ * No reference counterpart (the reference runs every join kind as the inner join).  A semi join asks one bit per key -
+ * "does some build row hold it" - so the build side becomes a BITMAP over the key range instead of the dense join's CSR:
+ *   bitmap              32-bit words; bit (s & 31) of word (s >> 5) is set iff some build key equals key_min + s, 0 <= s < slots
+ *                       (1 <= slots <= 2^32); bits at and past `slots` are zero.  hs_keyset_bitmap_bytes(slots) bytes = the words
+ *                       rounded up to 16 bytes + 64 bytes of slack (0: slots out of range), 16-byte aligned.  The build writes
+ *                       EVERY word of the buffer: a reused buffer needs no memset.
+ * hs_keyset_build: the keys ALONE (no row ids: a set needs none) are moved by up to two stable range partition passes on the
+ * high bits of key - key_min into partitions of 2^L slots (L: KS_L in the source; none when slots <= 2^L); work items =
+ * (partition, chunk of at most KS_CHUNK of its keys) set the chunk's bits in LDS and store the partition's words with coalesced
+ * 16-byte plain stores; only a partition that holds more than one chunk is zeroed first and merged with atomic ORs over
+ * consecutive non-zero words.  A build key outside the declared range raises HS_FLAG_BAD_PROGRAM in *flags (and sets no bit).
+ * n < 2^31; ws: hs_keyset_ws_bytes(n, slots) (0 = refused).
+ * hs_keyset_probe: mask[i] = (probe key i is in the set) != (anti != 0), one byte per row; four keys per lane, an
+ * out-of-range key is a non-member without a read.  probe keys 16-byte aligned, mask 4-byte aligned, n < 2^31; bytes past
+ * n are not written.
+ * hs_mask_from_counts: mask[i] = (counts[i] != 0) != (anti != 0) - the count pass of hs_join_hash_count / hs_join_count turned
+ * into the same byte mask (counts 16-byte aligned, mask 4-byte aligned).  hs_compact of the mask lists the surviving rows. */
+size_t hs_keyset_bitmap_bytes(int64_t slots);
+size_t hs_keyset_ws_bytes(int64_t n_build, int64_t slots);
+int hs_keyset_build(void* stream, const int32_t* keys, int64_t n, int32_t key_min, int64_t slots, uint32_t* bitmap, void* ws,
+                    uint32_t* flags);
+int hs_keyset_probe(void* stream, const int32_t* keys, int64_t n, int32_t key_min, int64_t slots, const uint32_t* bitmap,
+                    int32_t anti, uint8_t* mask);
+int hs_mask_from_counts(void* stream, const int64_t* counts, int64_t n, int32_t anti, uint8_t* mask);
 /* ---- the general inner join on ANY INTEGER keys (round 4; csrc/hs_radix.hip) -------------------------------------------
  * The same reference loop (tasks.py:201-240) for keys the dense form does not hold: a sparse or huge key range, negative
  * keys.  table = hs_join_hash_slots(n_build) 8-byte slots {key, word} (word as in the dense form), cut into windows of 512

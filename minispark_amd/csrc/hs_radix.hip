@@ -3747,7 +3747,7 @@ __global__ void __launch_bounds__(256) k_jd_setup(uint32_t* iota, int64_t n_iota
 }
 
 // ---- the build's host side, shared by the three forms -----------------------------------------------------------------
-enum JxForm { JX_DENSE, JX_HASH, JX_HASH_STR };
+enum JxForm { JX_DENSE, JX_HASH, JX_HASH_STR, JX_KEYSET };
 constexpr int JH_L_SMALL = 9, JH_L_LARGE = 10;  // window sizes of the hashed forms (log2), see their section below
 
 static int64_t jh_windows(int64_t n_build, int L) {   // ~1.75 slots per build row: distinct keys <= rows
@@ -3775,6 +3775,12 @@ static bool jx_layout(JxForm form, int64_t n, int64_t slots, JxLayout& Y) {
         if (Y.L > JD_MAX_L) return false;  // (slots <= 2^29 with 16 partition bits)
         bits = S > Y.L ? S - Y.L : 0;
         Y.windows = 0;
+    } else if (form == JX_KEYSET) {  // keys alone, partitions of 2^L BITS (Y.L is the caller's: ks_partition_bits)
+        if (slots < 1 || slots > ((int64_t)1 << 32) || Y.L < 32 - 2 * RX_MAX_BITS || Y.L > 19) return false;
+        int S = 0;
+        while (S < 32 && ((int64_t)1 << S) < slots) ++S;
+        bits = S > Y.L ? S - Y.L : 0;
+        Y.windows = 0;
     } else {
         Y.L = jh_windows(n, JH_L_SMALL) <= ((int64_t)1 << (2 * RX_MAX_BITS)) ? JH_L_SMALL : JH_L_LARGE;
         Y.windows = jh_windows(n, Y.L);
@@ -3796,13 +3802,13 @@ static bool jx_layout(JxForm form, int64_t n, int64_t slots, JxLayout& Y) {
         return at;
     };
     const size_t col = (size_t)n * 4 + 64;  // one 4-byte column
-    const bool str = form == JX_HASH_STR;
-    Y.keys_a = take(col);
-    Y.rows_a = take(col);
+    const bool str = form == JX_HASH_STR, set = form == JX_KEYSET;  // a key set moves no row ids and keeps no copy without a pass
+    Y.keys_a = take(set && !Y.bits1 ? 0 : col);
+    Y.rows_a = take(set ? 0 : col);
     Y.keys_b = take(Y.bits2 ? col : 0);
-    Y.rows_b = take(Y.bits2 ? col : 0);
-    Y.iota = take(Y.bits1 ? 64 : col);  // row ids travel from the first pass on; needed as an array only without passes
-    Y.slot_of = take(form == JX_DENSE ? 0 : (size_t)n * 2 + 64);
+    Y.rows_b = take(Y.bits2 && !set ? col : 0);
+    Y.iota = take(Y.bits1 || set ? 64 : col);  // row ids travel from the first pass on; needed as an array only without passes
+    Y.slot_of = take(form == JX_DENSE || set ? 0 : (size_t)n * 2 + 64);
     Y.win = take(str ? col : 0);
     Y.fp = take(str ? col : 0);
     Y.fp_a = take(str && Y.bits1 ? col : 0);
@@ -3830,13 +3836,14 @@ struct JxTuples {
 // Row ids, then one or two stable partition passes (RxPass.mode = mode, range_bias = bias) on the bits1 + bits2 bits of
 // the 4-byte partition key `key` above bit `low`; `third` (4 bytes per row, or null) travels along.  Without passes (one
 // partition) the tuples are the columns themselves and the row ids 0 .. n-1; without rows every partition is empty.
+// with_rows = false (a key set): the keys travel ALONE - no row id column is made, moved or written (T.rows is null).
 static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const JxLayout& Y, int64_t n, const void* key, RxBin mode,
-                        int32_t bias, int low, const uint32_t* third, JxTuples& T) {
+                        int32_t bias, int low, const uint32_t* third, JxTuples& T, bool with_rows = true) {
     uint32_t* iota = (uint32_t*)(ws + Y.iota);
     int64_t* seg0 = (int64_t*)(ws + Y.seg0);
     int64_t* seg1 = (int64_t*)(ws + Y.seg1);
     int64_t* seg2 = (int64_t*)(ws + Y.seg2);
-    const int64_t n_iota = Y.bits1 ? 0 : n;
+    const int64_t n_iota = Y.bits1 || !with_rows ? 0 : n;
     int64_t grid = (n_iota + 255) / 256;
     grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
     hipLaunchKernelGGL(k_jd_setup, dim3((unsigned)grid), dim3(256), 0, stream, iota, n_iota, n, seg0);
@@ -3844,7 +3851,7 @@ static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const 
         hs_set_error("%s (row ids): kernel launch failed", who);
         return HS_E_LAUNCH;
     }
-    T = JxTuples{key, iota, third, seg0, 1};
+    T = JxTuples{key, with_rows ? iota : nullptr, third, seg0, 1};
     if (Y.bits1 == 0) return HS_OK;
     T.seg = seg2;
     T.parts = Y.parts;
@@ -3854,7 +3861,7 @@ static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const 
     }
     RxPass P;
     std::memset(&P, 0, sizeof(P));
-    P.n_cols = third ? 3 : 2;
+    P.n_cols = !with_rows ? 1 : third ? 3 : 2;
     P.esize[0] = P.esize[1] = 4;
     if (third) P.esize[2] = 4;
     P.mode = mode;
@@ -3871,12 +3878,12 @@ static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const 
     P.src[1] = nullptr;  // the row id column is the position (k_rx_scatter4)
     P.src[2] = third;
     P.dst[0] = ws + Y.keys_a;
-    P.dst[1] = ws + Y.rows_a;
+    P.dst[1] = with_rows ? ws + Y.rows_a : nullptr;
     P.dst[2] = third ? ws + Y.fp_a : nullptr;
     int rc = rx_pass(stream, P, Y.tiles1, (int64_t*)(ws + Y.cnt), (int64_t*)(ws + Y.scan), ws + Y.scan_ws, n, Y.bits2 ? seg1 : seg2);
     if (rc != HS_OK) return rc;
     T.keys = ws + Y.keys_a;
-    T.rows = (const uint32_t*)(ws + Y.rows_a);
+    T.rows = with_rows ? (const uint32_t*)(ws + Y.rows_a) : nullptr;
     if (third) T.third = (const uint32_t*)(ws + Y.fp_a);
     if (Y.bits2) {  // pass 2: the next bits2 bits inside every segment of pass 1
         P.seg_start = seg1;
@@ -3886,15 +3893,15 @@ static int jx_partition(hipStream_t stream, const char* who, uint8_t* ws, const 
         P.bits = Y.bits2;
         P.first = 0;
         P.src[0] = ws + Y.keys_a;
-        P.src[1] = ws + Y.rows_a;
+        P.src[1] = with_rows ? ws + Y.rows_a : nullptr;
         P.src[2] = third ? ws + Y.fp_a : nullptr;
         P.dst[0] = ws + Y.keys_b;
-        P.dst[1] = ws + Y.rows_b;
+        P.dst[1] = with_rows ? ws + Y.rows_b : nullptr;
         P.dst[2] = third ? ws + Y.fp_b : nullptr;
         rc = rx_pass(stream, P, Y.tiles2, (int64_t*)(ws + Y.cnt), (int64_t*)(ws + Y.scan), ws + Y.scan_ws, n, seg2);
         if (rc != HS_OK) return rc;
         T.keys = ws + Y.keys_b;
-        T.rows = (const uint32_t*)(ws + Y.rows_b);
+        T.rows = with_rows ? (const uint32_t*)(ws + Y.rows_b) : nullptr;
         if (third) T.third = (const uint32_t*)(ws + Y.fp_b);
     }
     return HS_OK;
@@ -4088,6 +4095,277 @@ extern "C" int hs_join_dense_fill(void* stream, int64_t n_probe, const uint32_t*
     if (g > 256 * 64) g = 256 * 64;
     hipLaunchKernelGGL(k_jd_fill, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, A);
     RX_CHECK_LAUNCH("hs_join_dense_fill");
+    return HS_OK;
+}
+
+// =====================================================================================================
+// Key sets for LEFT SEMI / LEFT ANTI joins on INTEGER keys (include/hipspark.h hs_keyset_*)
+// =====================================================================================================
+// No reference counterpart: the reference runs every join kind as the inner join.  A semi join asks ONE BIT per key, so the
+// build side becomes a bitmap over the key range - bit s of the bitmap = "some build key equals key_min + s" - and the probe
+// one scattered 4-byte read per row.  The build follows the dense join's rule (move the rows, do not hammer global memory
+// with scattered atomics) with half its traffic: the keys travel ALONE through the partition passes (jx_partition without
+// rows), on the high bits of key - key_min, into partitions of 2^KS_L slots whose bits fit a workgroup's LDS; a key range of
+// one partition takes no pass at all.  Work items are (partition, chunk of at most KS_CHUNK of its keys): clear the LDS bits,
+// OR the chunk in (LDS atomics: order-free, all waves of the workgroup share the table), store the partition's words with
+// coalesced 16-byte plain stores.  Only a partition too crowded for one chunk is zeroed up front (k_ks_plan) and merged
+// with atomic ORs over its consecutive non-zero words - whole 256-byte lines per wave, never a scattered atomic.
+constexpr int KS_L = 19;          // log2 of a partition's slots: 2^19 bits = 64 KB of LDS (measured: profiles/r25_semi_join.txt)
+constexpr int KS_CHUNK = 65536;   // keys of one work item
+constexpr int KS_THREADS = 1024;
+constexpr int KS_SLACK = 64;      // bytes past the rounded words (zeroed by the build like every other word)
+
+// tuning knobs of the measurement (tools/bench_semi_join.py): HIPSPARK_KEYSET_L = 16 .. 19, HIPSPARK_KEYSET_CHUNK = keys per work item
+static int ks_partition_bits() {
+    static const int L = [] {
+        const char* e = getenv("HIPSPARK_KEYSET_L");
+        const int v = e ? atoi(e) : KS_L;
+        return v >= 32 - 2 * RX_MAX_BITS && v <= 19 ? v : KS_L;
+    }();
+    return L;
+}
+static int64_t ks_chunk_keys() {
+    static const int64_t c = [] {
+        const char* e = getenv("HIPSPARK_KEYSET_CHUNK");
+        const long long v = e ? atoll(e) : (long long)KS_CHUNK;
+        return (int64_t)(v >= 1024 && v <= ((long long)1 << 30) ? v : KS_CHUNK);
+    }();
+    return c;
+}
+
+struct KsBuild {
+    const int64_t* seg;        // [parts + 1] key ranges of the partitions
+    int64_t parts, last;       // last: the partition that holds slot `slots - 1` (partitions past it must be empty)
+    const int32_t* keys;       // partitioned (the build column itself without a pass)
+    int64_t slots, chunk;
+    int32_t key_min, L;
+    uint32_t* bitmap;
+    int64_t words;             // all words of the buffer, slack included (a multiple of 4)
+    int64_t* items;            // [parts] work items of every partition, then (item_start) their exclusive scan [parts + 1]
+    const int64_t* item_start;
+    uint32_t* flags;
+};
+
+// the words of partition p: [lo, hi) - the last live partition also owns the rounding and the slack behind it
+__device__ __forceinline__ void ks_words(const KsBuild& A, int64_t p, int64_t& lo, int64_t& hi) {
+    const int64_t pw = (int64_t)1 << (A.L - 5);
+    lo = p * pw;
+    hi = p == A.last ? A.words : lo + pw;
+}
+
+// work items per partition (a live one has at least one: its words are written even without a key); a partition of
+// several chunks is zeroed here, ahead of the atomic merge
+__global__ void __launch_bounds__(256) k_ks_plan(const KsBuild A) {
+    for (int64_t p = blockIdx.x; p < A.parts; p += gridDim.x) {
+        const int64_t len = A.seg[p + 1] - A.seg[p];
+        const bool live = p <= A.last;
+        if (threadIdx.x == 0) {
+            A.items[p] = live ? (len > A.chunk ? (len + A.chunk - 1) / A.chunk : 1) : 0;
+            if (!live && len > 0) atomicOr(A.flags, HS_FLAG_BAD_PROGRAM);  // a key past the declared range
+        }
+        if (live && len > A.chunk) {
+            int64_t lo, hi;
+            ks_words(A, p, lo, hi);
+            jd_u32x4* out = reinterpret_cast<jd_u32x4*>(A.bitmap);
+            for (int64_t q = lo / 4 + threadIdx.x; q < hi / 4; q += blockDim.x) out[q] = jd_u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+}
+
+__global__ void __launch_bounds__(KS_THREADS) k_ks_build(const KsBuild A) {
+    extern __shared__ __align__(16) uint32_t ks_bits[];  // 2^(L - 5) words
+    const int tid = threadIdx.x;
+    const int64_t pw = (int64_t)1 << (A.L - 5);
+    const uint32_t kmin = (uint32_t)A.key_min, smask = (1u << A.L) - 1u;
+    const int64_t n_items = A.item_start[A.parts];
+    uint32_t err = 0;
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        int64_t lo_p = 0, hi_p = A.parts;  // the last p with item_start[p] <= item owns it (dead partitions share the total)
+        while (hi_p - lo_p > 1) {
+            const int64_t mid = (lo_p + hi_p) >> 1;
+            if (A.item_start[mid] <= item) lo_p = mid;
+            else hi_p = mid;
+        }
+        const int64_t p = lo_p, c = item - A.item_start[p], chunks = A.item_start[p + 1] - A.item_start[p];
+        const int64_t b = A.seg[p] + c * A.chunk;
+        const int64_t e = b + A.chunk < A.seg[p + 1] ? b + A.chunk : A.seg[p + 1];
+        for (int64_t q = tid; q < pw / 4; q += KS_THREADS) reinterpret_cast<jd_u32x4*>(ks_bits)[q] = jd_u32x4{0u, 0u, 0u, 0u};
+        __syncthreads();
+        for (int64_t base = b; base < e; base += (int64_t)KS_THREADS * 4) {
+            uint32_t s[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {  // four coalesced loads in flight; slot = key - key_min as uint32 (k_jd_count's rule)
+                const int64_t i = base + (int64_t)j * KS_THREADS + tid;
+                s[j] = i < e ? (uint32_t)A.keys[i] - kmin : 0u;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (base + (int64_t)j * KS_THREADS + tid >= e) continue;
+                if ((int64_t)s[j] < A.slots && (int64_t)(s[j] >> A.L) == p) atomicOr(&ks_bits[(s[j] & smask) >> 5], 1u << (s[j] & 31u));
+                else err = HS_FLAG_BAD_PROGRAM;  // outside the declared range (or the partition): no bit is set
+            }
+        }
+        __syncthreads();
+        int64_t lo, hi;
+        ks_words(A, p, lo, hi);
+        if (chunks == 1) {
+            for (int64_t q = tid; q < (hi - lo) / 4; q += KS_THREADS) {
+                const jd_u32x4 v = q < pw / 4 ? reinterpret_cast<const jd_u32x4*>(ks_bits)[q] : jd_u32x4{0u, 0u, 0u, 0u};
+                reinterpret_cast<jd_u32x4*>(A.bitmap + lo)[q] = v;
+            }
+        } else {  // (k_ks_plan zeroed [lo, hi)) consecutive lanes, consecutive words: a wave's atomics fall into whole lines
+            for (int64_t w = tid; w < pw; w += KS_THREADS) {
+                const uint32_t v = ks_bits[w];
+                if (v) atomicOr(A.bitmap + lo + w, v);
+            }
+        }
+        __syncthreads();  // the table is cleared again for the next item
+    }
+    if (err) atomicOr(A.flags, err);
+}
+
+static int64_t ks_words_total(int64_t slots) { return (((slots + 31) / 32 + 3) & ~(int64_t)3) + KS_SLACK / 4; }
+
+struct KsLayout {
+    JxLayout Y;
+    size_t items, item_start, scan_ws, total;
+};
+static bool ks_layout(int64_t n, int64_t slots, KsLayout& K) {
+    K.Y.L = ks_partition_bits();
+    if (!jx_layout(JX_KEYSET, n, slots, K.Y)) return false;
+    size_t off = K.Y.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += rx_align(bytes);
+        return at;
+    };
+    K.items = take((size_t)K.Y.parts * 8);
+    K.item_start = take((size_t)(K.Y.parts + 1) * 8);
+    K.scan_ws = take(hs_scan_ws_bytes(K.Y.parts));
+    K.total = off;
+    return true;
+}
+
+extern "C" size_t hs_keyset_bitmap_bytes(int64_t slots) {
+    return slots < 1 || slots > ((int64_t)1 << 32) ? 0 : (size_t)ks_words_total(slots) * 4;
+}
+extern "C" size_t hs_keyset_ws_bytes(int64_t n_build, int64_t slots) {
+    KsLayout K;
+    return ks_layout(n_build, slots, K) ? K.total : 0;
+}
+
+extern "C" int hs_keyset_build(void* stream_, const int32_t* keys, int64_t n, int32_t key_min, int64_t slots, uint32_t* bitmap,
+                               void* ws_, uint32_t* flags) {
+    KsLayout K;
+    if ((!keys && n > 0) || !bitmap || !ws_ || !flags || ((uintptr_t)bitmap & 15) || !ks_layout(n, slots, K) ||
+        (int64_t)key_min + slots - 1 > 0x7fffffffll) {
+        hs_set_error("hs_keyset_build: bad arguments (n < 2^31, 1 <= slots <= 2^32, key_min + slots - 1 an int32, bitmap 16-byte aligned)");
+        return HS_E_ARG;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    uint8_t* ws = (uint8_t*)ws_;
+    const JxLayout& Y = K.Y;
+    JxTuples T;
+    int rc = jx_partition(stream, "hs_keyset_build", ws, Y, n, keys, RX_BIN_RANGE, key_min, Y.L, nullptr, T, false);
+    if (rc != HS_OK) return rc;
+    const KsBuild A{T.seg, T.parts, (slots - 1) >> Y.L, (const int32_t*)T.keys, slots, ks_chunk_keys(), key_min, Y.L, bitmap,
+                    ks_words_total(slots), (int64_t*)(ws + K.items), (const int64_t*)(ws + K.item_start), flags};
+    hipLaunchKernelGGL(k_ks_plan, dim3((unsigned)(T.parts < 4096 ? T.parts : 4096)), dim3(256), 0, stream, A);
+    RX_CHECK_LAUNCH("hs_keyset_build (plan)");
+    rc = hs_exclusive_scan_i64(stream, A.items, T.parts, (int64_t*)(ws + K.item_start), ws + K.scan_ws);
+    if (rc != HS_OK) return rc;
+    const size_t lds = (size_t)4 << (Y.L - 5);
+    static unsigned long long attr_set = 0;
+    if (hs_first_on_device(attr_set))
+        (void)hipFuncSetAttribute((const void*)k_ks_build, hipFuncAttributeMaxDynamicSharedMemorySize, 4 << (19 - 5));
+    int64_t g = A.last + 1 + n / A.chunk;  // >= the work items: one per live partition and one per further whole chunk
+    if (g > 256 * 8) g = 256 * 8;
+    hipLaunchKernelGGL(k_ks_build, dim3((unsigned)g), dim3(KS_THREADS), lds, stream, A);
+    RX_CHECK_LAUNCH("hs_keyset_build");
+    return HS_OK;
+}
+
+struct KsProbe {
+    const int32_t* keys;
+    int64_t n, slots;
+    int32_t key_min, anti;
+    const uint32_t* bitmap;
+    uint8_t* mask;
+};
+// Probe (modelled on k_jd_count): four keys per lane from one 16-byte non-temporal load, their four word reads in flight
+// together, a key outside [key_min, key_min + slots) is a non-member without a read; one byte per row leaves as a packed
+// 4-byte store.  The last, partial quad reads and writes its rows one by one: nothing past n is touched.
+__global__ void __launch_bounds__(256) k_ks_probe(const KsProbe A) {
+    const int64_t nq = (A.n + 3) / 4;
+    const uint32_t flip = A.anti ? 1u : 0u;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+        const bool whole = q * 4 + 3 < A.n;
+        int32_t k[4] = {0, 0, 0, 0};
+        if (whole) {
+            const jd_i32x4 kv = __builtin_nontemporal_load(reinterpret_cast<const jd_i32x4*>(A.keys) + q);
+            k[0] = kv.x; k[1] = kv.y; k[2] = kv.z; k[3] = kv.w;
+        } else {
+            for (int j = 0; j < 4 && q * 4 + j < A.n; ++j) k[j] = A.keys[q * 4 + j];
+        }
+        uint32_t word[4], bit[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t o = (int64_t)k[j] - (int64_t)A.key_min;
+            const bool in = q * 4 + j < A.n && (uint64_t)o < (uint64_t)A.slots;
+            word[j] = in ? A.bitmap[o >> 5] : 0u;
+            bit[j] = (uint32_t)o & 31u;
+        }
+        uint32_t packed = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) packed |= (((word[j] >> bit[j]) & 1u) ^ flip) << (8 * j);
+        if (whole) __builtin_nontemporal_store(packed, reinterpret_cast<uint32_t*>(A.mask) + q);
+        else
+            for (int j = 0; j < 4 && q * 4 + j < A.n; ++j) A.mask[q * 4 + j] = (uint8_t)(packed >> (8 * j));
+    }
+}
+
+extern "C" int hs_keyset_probe(void* stream, const int32_t* keys, int64_t n, int32_t key_min, int64_t slots, const uint32_t* bitmap,
+                               int32_t anti, uint8_t* mask) {
+    if ((!keys && n > 0) || !bitmap || (!mask && n > 0) || n < 0 || n >= 0x7fffffffll || slots < 1 || slots > ((int64_t)1 << 32) ||
+        ((uintptr_t)keys & 15) || ((uintptr_t)mask & 3)) {
+        hs_set_error("hs_keyset_probe: bad arguments (n < 2^31, 1 <= slots <= 2^32, probe keys 16-byte aligned, mask 4-byte aligned)");
+        return HS_E_ARG;
+    }
+    if (n == 0) return HS_OK;
+    const KsProbe A{keys, n, slots, key_min, anti ? 1 : 0, bitmap, mask};
+    int64_t g = ((n + 3) / 4 + 255) / 256;
+    if (g > 256 * 64) g = 256 * 64;
+    hipLaunchKernelGGL(k_ks_probe, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, A);
+    RX_CHECK_LAUNCH("hs_keyset_probe");
+    return HS_OK;
+}
+
+// the count pass of the hashed / global-table joins as the same mask: (counts[i] != 0) != anti
+__global__ void __launch_bounds__(256) k_mask_from_counts(const int64_t* counts, int64_t n, uint32_t flip, uint8_t* mask) {
+    const int64_t nq = (n + 3) / 4;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+        if (q * 4 + 3 < n) {
+            const jd_i64x2 a = __builtin_nontemporal_load(reinterpret_cast<const jd_i64x2*>(counts) + 2 * q);
+            const jd_i64x2 b = __builtin_nontemporal_load(reinterpret_cast<const jd_i64x2*>(counts) + 2 * q + 1);
+            const uint32_t packed = ((a.x != 0 ? 1u : 0u) ^ flip) | (((a.y != 0 ? 1u : 0u) ^ flip) << 8) |
+                                    (((b.x != 0 ? 1u : 0u) ^ flip) << 16) | (((b.y != 0 ? 1u : 0u) ^ flip) << 24);
+            __builtin_nontemporal_store(packed, reinterpret_cast<uint32_t*>(mask) + q);
+        } else {
+            for (int j = 0; j < 4 && q * 4 + j < n; ++j) mask[q * 4 + j] = (uint8_t)((counts[q * 4 + j] != 0 ? 1u : 0u) ^ flip);
+        }
+    }
+}
+
+extern "C" int hs_mask_from_counts(void* stream, const int64_t* counts, int64_t n, int32_t anti, uint8_t* mask) {
+    if (n < 0 || ((!counts || !mask) && n > 0) || ((uintptr_t)counts & 15) || ((uintptr_t)mask & 3)) {
+        hs_set_error("hs_mask_from_counts: bad arguments (counts 16-byte aligned, mask 4-byte aligned)");
+        return HS_E_ARG;
+    }
+    if (n == 0) return HS_OK;
+    int64_t g = ((n + 3) / 4 + 255) / 256;
+    if (g > 256 * 64) g = 256 * 64;
+    hipLaunchKernelGGL(k_mask_from_counts, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, counts, n, anti ? 1u : 0u, mask);
+    RX_CHECK_LAUNCH("hs_mask_from_counts");
     return HS_OK;
 }
 

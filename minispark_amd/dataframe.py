@@ -79,6 +79,11 @@ class DataFrame:
         return self._append(_t.AggregateTask, group_by_column=None, agg_columns=list(agg_columns))
 
     def join(self, other_df: "DataFrame", on: Any, how: _t.JoinType) -> "DataFrame":
+        """``how`` = "left_semi" / "left_anti": the rows of this frame with (without) a partner in ``other_df`` - this
+        frame's columns, rows and order; ``on`` is one equality between a column of each side, optionally
+        AND-ed with conditions over ``other_df``'s columns.  Every other kind runs as the inner join, as in the reference."""
+        if how in ("left_semi", "left_anti"):
+            return self._append(_t.SemiJoinTask, right_side_task=other_df.task, join_condition=on, anti=how == "left_anti")
         return self._append(_t.BroadcastHashJoinTask, right_side_task=other_df.task, join_condition=on, how=how)
 
     def order_by(self, *keys: Any) -> "DataFrame":

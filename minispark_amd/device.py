@@ -2639,3 +2639,108 @@ class Device:
                                        treps.data_ptr(), slot_start.data_ptr(), rows.data_ptr(), out_start.data_ptr(),
                                        out_left.data_ptr(), out_right.data_ptr()), "hs_join_fill")
         return out_left, out_right, out_start, n_out
+
+    # ---- LEFT SEMI / LEFT ANTI join: membership of the left keys in the right side's key set -------------
+    SEMI_BITMAP_SLOTS = 1 << 26  # the bitmap is taken while the right keys' range holds at most this many slots (8 MB of bits) ...
+    SEMI_BITMAP_SPREAD = 64      # ... or at most this many slots per right row (2 bits of bitmap per key byte moved)
+
+    def _semi_mask_bitmap(self, left_key: DCol, right_key: DCol, anti: bool, mask: torch.Tensor) -> dict | None:
+        """INTEGER keys over a range the bitmap holds (hs_keyset_*): the right keys become one bit per key slot, a left row is
+        kept on its bit.  None: the range is too wide or too sparse for a bitmap."""
+        lo, hi, n_right = self.key_range(right_key)
+        slots = hi - lo + 1
+        if slots > 1 << 32 or slots > max(self.SEMI_BITMAP_SLOTS, self.SEMI_BITMAP_SPREAD * n_right):
+            return None
+        ws_bytes = int(self.lib.hs_keyset_ws_bytes(n_right, slots))
+        bitmap_bytes = int(self.lib.hs_keyset_bitmap_bytes(slots))
+        if ws_bytes == 0 or bitmap_bytes == 0:
+            return None
+        bitmap = self.empty(bitmap_bytes // 4, torch.int32)
+        ws = self.workspace(ws_bytes)
+        hs.check(self.lib.hs_keyset_build(self.stream, right_key.data.data_ptr(), n_right, lo, slots, bitmap.data_ptr(),
+                                          ws.data_ptr(), self.flags.data_ptr()), "hs_keyset_build")
+        hs.check(self.lib.hs_keyset_probe(self.stream, left_key.data.data_ptr(), left_key.n, lo, slots, bitmap.data_ptr(),
+                                          1 if anti else 0, mask.data_ptr()), "hs_keyset_probe")
+        return {"mode": "bitmap", "slots": slots, "n_build": n_right}
+
+    def _semi_mask_hashed(self, left_key: DCol, right_key: DCol, anti: bool, mask: torch.Tensor) -> dict | None:
+        """Any INTEGER keys: the hashed-window join's build over the right keys and its count pass over the left keys, whose
+        counts become the mask.  None: more right rows than the windows hold, or a window overflowed."""
+        n_left, n_right = left_key.n, right_key.n
+        slots = int(self.lib.hs_join_hash_slots(n_right))
+        if slots == 0:
+            return None
+        table = self.empty(slots, torch.int64)
+        rows = self.empty(n_right, torch.int32)
+        list_count = self.empty(n_right, torch.int32)
+        ws = self.workspace(int(self.lib.hs_join_hash_ws_bytes(n_right)))
+        overflowed = self.empty(1, torch.int32)
+        overflowed.zero_()
+        hs.check(self.lib.hs_join_hash_build(self.stream, right_key.data.data_ptr(), n_right, table.data_ptr(), rows.data_ptr(),
+                                             list_count.data_ptr(), ws.data_ptr(), overflowed.data_ptr(), self.flags.data_ptr()),
+                 "hs_join_hash_build")
+        counts = self.empty(n_left, torch.int64)
+        aux = self.workspace(self.lib.hs_join_dense_aux_bytes(n_left))
+        hs.check(self.lib.hs_join_hash_count(self.stream, left_key.data.data_ptr(), n_left, n_right, table.data_ptr(), rows.data_ptr(),
+                                             list_count.data_ptr(), counts.data_ptr(), aux.data_ptr()), "hs_join_hash_count")
+        if self.host_int(overflowed) != 0:
+            return None
+        hs.check(self.lib.hs_mask_from_counts(self.stream, counts.data_ptr(), n_left, 1 if anti else 0, mask.data_ptr()),
+                 "hs_mask_from_counts")
+        return {"mode": "hashed windows", "slots": slots, "n_build": n_right}
+
+    def _semi_mask_table(self, left_key: DCol, right_key: DCol, anti: bool, mask: torch.Tensor) -> dict:
+        """STRING / TIMESTAMP keys (and INTEGER keys the windows refused): the global hash table's build over the right keys
+        and its count pass over the left keys."""
+        n_left, n_right = left_key.n, right_key.n
+        cap = 16
+        while cap < 2 * max(n_right, 1):
+            cap *= 2
+        tkeys = self.empty(cap, torch.int64)
+        treps = self.empty(cap, torch.int64)
+        slot_start = self.empty(cap + 1, torch.int64)
+        rows = self.empty(max(n_right, 1), torch.int64)
+        ws = self.workspace(self.lib.hs_join_build_ws_bytes(n_right, cap))
+        bk, pk = right_key.as_hs(), left_key.as_hs()
+        hs.check(self.lib.hs_join_build(self.stream, C.byref(bk), n_right, cap, tkeys.data_ptr(), treps.data_ptr(),
+                                        slot_start.data_ptr(), rows.data_ptr(), ws.data_ptr(), self.flags.data_ptr()),
+                 "hs_join_build")
+        counts = self.empty(n_left, torch.int64)
+        hs.check(self.lib.hs_join_count(self.stream, C.byref(bk), C.byref(pk), n_left, cap, tkeys.data_ptr(),
+                                        treps.data_ptr(), slot_start.data_ptr(), counts.data_ptr()), "hs_join_count")
+        hs.check(self.lib.hs_mask_from_counts(self.stream, counts.data_ptr(), n_left, 1 if anti else 0, mask.data_ptr()),
+                 "hs_mask_from_counts")
+        return {"mode": "global hash table", "n_build": n_right}
+
+    def semi_select(self, left_key: DCol, right_key: DCol, anti: bool) -> tuple[torch.Tensor, int]:
+        """LEFT SEMI (``anti``: LEFT ANTI) join -> the ascending list of the left rows whose key occurs (does not occur) among
+        the right keys, and their number (one D2H).  Keys of one kind, decoded: INTEGER keys over a range a bitmap holds take
+        hs_keyset_*, other INTEGER keys the hashed windows, STRING / TIMESTAMP keys (and what the windows refuse) the global
+        hash table - the latter two stop after their count pass.  ``last_semi_join`` names the path taken."""
+        n_left, n_right = left_key.n, right_key.n
+        if left_key.kind != right_key.kind:
+            raise DeviceError(f"semi join keys of kinds {left_key.kind} / {right_key.kind}")
+        if n_left >= (1 << 31) - 1 or n_right >= (1 << 31) - 1:
+            raise DeviceError("a semi join side holds fewer than 2^31 - 1 rows")
+        if n_left == 0 or (n_right == 0 and not anti):  # nothing to keep
+            self.last_semi_join = {"mode": "empty", "n_build": n_right}
+            return self.empty(0, torch.int64), 0
+        if n_right == 0:  # nothing to drop: every left row, in order
+            self.last_semi_join = {"mode": "empty", "n_build": 0}
+            sel = self.empty(n_left, torch.int64)
+            sel.copy_(torch.arange(n_left, dtype=torch.int64, device=self.device))
+            return sel, n_left
+        mask = self.empty(n_left, torch.uint8)
+        info = None
+        if left_key.kind == hs.I32 and left_key.data.data_ptr() % 16 == 0 and right_key.data.data_ptr() % 16 == 0:
+            info = (self._semi_mask_bitmap(left_key, right_key, anti, mask)
+                    or self._semi_mask_hashed(left_key, right_key, anti, mask))
+        if info is None:
+            info = self._semi_mask_table(left_key, right_key, anti, mask)
+        self.last_semi_join = {**info, "n_probe": n_left, "anti": bool(anti)}
+        sel = self.empty(n_left, torch.int64)
+        count = self.empty(1, torch.int64)
+        ws = self.workspace(self.lib.hs_scan_ws_bytes(n_left))
+        hs.check(self.lib.hs_compact(self.stream, mask.data_ptr(), n_left, sel.data_ptr(), count.data_ptr(), ws.data_ptr()),
+                 "hs_compact")
+        return sel, self.host_int(count)

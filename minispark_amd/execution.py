@@ -307,7 +307,7 @@ class HipExecutionEngine(ExecutionEngine):
                 for task in (stage.producer, *stage.consumers, stage.writer):
                     attrs = [str(getattr(task, name)) for name in ("file_path", "alias", "condition", "columns",
                                                                    "group_by_column", "agg_columns", "join_condition",
-                                                                   "key_column", "before_shuffle") if hasattr(task, name)]
+                                                                   "key_column", "before_shuffle", "anti") if hasattr(task, name)]
                     parts.append((_cls(task), *attrs))
             shape = plan._hs_shape = tuple(parts)
         caps = self._caps_by_shape.get(shape)
@@ -419,6 +419,7 @@ class HipExecutionEngine(ExecutionEngine):
         for _attempt in range(12):
             plan = self._cached_plan(full_task)
             self._refuse_marks_on_ranks(plan)
+            self._refuse_semi_join_on_ranks(plan)
             self._select_caps(plan)
             rec_key = self._recording_key(plan)
             rec = self._recordings.get(rec_key) if self.replay_enabled else None
@@ -567,7 +568,7 @@ class HipExecutionEngine(ExecutionEngine):
                     stamps.append((p, node.alias, st.st_mtime_ns, st.st_size))
                 except OSError:
                     stamps.append((p, node.alias, 0, 0))
-            if _cls(node) == "BroadcastHashJoinTask":
+            if _cls(node) in ("BroadcastHashJoinTask", "SemiJoinTask"):
                 stack.append(node.right_side_task)
             node = node.parent_task
             if (node is None or _cls(node) == "VoidTask") and stack:
@@ -683,6 +684,9 @@ class HipExecutionEngine(ExecutionEngine):
                 return self._run_join_stage_streamed(stage, outputs, feeds_aggregate)
             batch = self._join(producer, outputs[id(stage.dependencies[0])], outputs[id(stage.dependencies[1])],
                                self._needed_names(consumers), feeds_aggregate, consumers)
+        elif kind == "SemiJoinTask":
+            batch = self._semi_join(producer, outputs[id(stage.dependencies[0])], outputs[id(stage.dependencies[1])],
+                                    self._needed_names(consumers))
         else:
             raise NotImplementedError(f"Job creation not implemented for {type(producer)}")
 
@@ -740,6 +744,41 @@ class HipExecutionEngine(ExecutionEngine):
         if self.dist is not None and any(_cls(t) == "MarkFirstTask" for st in plan.stages for t in st.consumers):
             raise NotImplementedError("COUNT(DISTINCT) runs on one GPU: on N ranks the same (key, value) pair may sit on two "
                                       "ranks; run the query on one rank, or SELECT DISTINCT the pairs and count them")
+
+    def _refuse_semi_join_on_ranks(self, plan: Any) -> None:
+        """A LEFT SEMI / LEFT ANTI join asks the WHOLE right side's key set about every left row, and on N ranks every rank
+        holds a share of the right side.  Raised from the plan alone, on every rank alike, before a launch or a collective."""
+        if self.dist is not None and any(_cls(st.producer) == "SemiJoinTask" for st in plan.stages):
+            raise NotImplementedError("a LEFT SEMI / LEFT ANTI join runs on one GPU: on N ranks the right side's key set would "
+                                      "have to be gathered on every rank first; run the query on one rank")
+
+    def _semi_join(self, task: Any, left: Any, right: Any, needed: set[str] | None) -> Any:
+        """LEFT SEMI / LEFT ANTI join: the left batch filtered by the membership of its key in the right
+        batch's key column - ``left WHERE key IN {right keys}`` - so the tail is _materialise's: the surviving rows' list is
+        cut at the left batch's unit boundaries, and units, unit ids and the merge order stay the left input's.  Only the
+        columns a consumer names are gathered.  The row count is read back: the run is not replayable."""
+        import numpy as np  # noqa: PLC0415
+
+        from . import hipspark as hs  # noqa: PLC0415
+        from .device import DBatch, DCol  # noqa: PLC0415
+
+        dev = self.dev
+        left, right = dev.resolve(left), dev.resolve(right)
+        lkey = left.column_index(task.left_key.name)
+        rkey = right.column_index(task.right_key.name)
+        # codes of two dictionaries do not compare: keys are matched on the strings themselves, as the inner join does
+        sel, count = dev.semi_select(dev.decoded(left.cols[lkey]), dev.decoded(right.cols[rkey]), task.anti)
+        if dev.rec is not None:
+            dev.rec.poisoned = True
+        bounds = dev.to_device(np.asarray(left.unit_rows, dtype=np.int64))
+        unit_rows = [int(v) for v in dev.lower_bound(sel, count, bounds).tolist()]
+        keep = [i for i, (name, _) in enumerate(left.schema) if needed is None or name in needed] or [lkey]
+        pruned = DBatch([left.schema[i] for i in keep], [left.cols[i] for i in keep], left.nrows, list(left.unit_rows))
+        out = dev.gather_batch(pruned, sel, count, unit_rows)
+        out.unit_ids, out.total_units, out.partitioned = left.unit_ids, left.total_units, left.partitioned
+        if left.order is not None:
+            out.order = dev.gather_col(DCol(hs.I64, left.order, left.nrows), sel, count).data
+        return out
 
     def _order_rows(self, batch: Any, sort: Any, schema: Schema) -> Any:
         """ORDER BY / LIMIT over the finished result: the rows are first rounded to the types they are stored in, so

@@ -408,6 +408,11 @@ SIGNATURES: dict[str, tuple] = {
     "hs_join_dense_aux_bytes": (C.c_size_t, [_I64]),
     "hs_join_dense_count": (C.c_int, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P, _P]),
     "hs_join_dense_fill": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P]),
+    "hs_keyset_bitmap_bytes": (C.c_size_t, [_I64]),
+    "hs_keyset_ws_bytes": (C.c_size_t, [_I64, _I64]),
+    "hs_keyset_build": (C.c_int, [_P, _P, _I64, _I32, _I64, _P, _P, _P]),
+    "hs_keyset_probe": (C.c_int, [_P, _P, _I64, _I32, _I64, _P, _I32, _P]),
+    "hs_mask_from_counts": (C.c_int, [_P, _P, _I64, _I32, _P]),
     "hs_join_hash_ws_bytes": (C.c_size_t, [_I64]),
     "hs_join_hash_slots": (C.c_int64, [_I64]),
     "hs_join_hash_build": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P]),

@@ -4,7 +4,8 @@ requirements, so `.sql()` would not work next to the HIP engine without this mod
 
 A hand-written backtracking recursive-descent parser for the same language:
 
-    SELECT [DISTINCT] select_list FROM 'path' [AS t] { [LEFT|RIGHT|INNER|FULL] JOIN 'path' [AS t] ON cond }
+    SELECT [DISTINCT] select_list FROM 'path' [AS t] { [LEFT|RIGHT|INNER|FULL] JOIN 'path' [AS t] ON cond
+                                                       | [LEFT] SEMI JOIN 'path' [AS t] ON cond | [LEFT] ANTI JOIN 'path' [AS t] ON cond }
            [WHERE cond] [GROUP BY col | (col {, col}) [HAVING cond]] [ORDER BY name [ASC|DESC] {, name [ASC|DESC]}] [LIMIT n] ;
 
 * select items: ``*``, ``COUNT()/SUM(e)/AVG(e)/MIN(e)/MAX(e)/COUNT(DISTINCT e) [AS name]``, ``expr [AS name]``;
@@ -59,6 +60,13 @@ A hand-written backtracking recursive-descent parser for the same language:
   forms above, so ``COUNT(DISTINCT)`` still reads a column called DISTINCT and raises what it raised, and every text
   accepted before builds the tree it built.  ``COUNT(DISTINCT a, b)`` and ``SUM(DISTINCT a)`` are not part of the language.
 
+* ``[LEFT] SEMI JOIN 'path' [AS t] ON cond`` / ``[LEFT] ANTI JOIN ...`` keep the rows of the query so far
+  that have / lack a partner in the table: ``join(other, on, how="left_semi" | "left_anti")``.  ``cond`` is one equality
+  between a column of each side, optionally AND-ed with conditions over the joined table's columns (``ON o_orderkey =
+  l_orderkey AND l_quantity > 45``).  The result keeps the left side's columns only, so the joined table's columns are
+  unknown names to everything after it.  Joins apply left to right: ``A JOIN B ON ... LEFT ANTI JOIN C ON ...`` filters the
+  join's rows.  The four spellings are tried after the five join kinds above, which keep running as the inner join.
+
 Alternatives are tried in the grammar's order and the first that fits wins (ordered choice), so texts the
 reference accepts build the same task tree here (tests/test_parser.py compares both renderings).
 """
@@ -104,6 +112,8 @@ _COMPARATORS: list[tuple[str, Callable[[Any, Any], Any]]] = [
     (">", operator.gt),
 ]
 _JOIN_KINDS = [("JOIN",), ("LEFT", "JOIN"), ("RIGHT", "JOIN"), ("INNER", "JOIN"), ("FULL", "JOIN")]
+_SEMI_JOIN_KINDS = [(("SEMI", "JOIN"), "left_semi"), (("LEFT", "SEMI", "JOIN"), "left_semi"),
+                    (("ANTI", "JOIN"), "left_anti"), (("LEFT", "ANTI", "JOIN"), "left_anti")]
 _AGGREGATES = ("COUNT", "SUM", "AVG", "MIN", "MAX")
 _NAVIGATION = ("LAG", "LEAD", "FIRST_VALUE", "LAST_VALUE", "NTILE")
 
@@ -226,8 +236,8 @@ class _Parser:
             if not select_list:
                 raise SemanticError("a select list needs at least one column next to its window items")
 
-        for other, cond in joins:
-            df = df.join(other, on=cond, how="inner")
+        for other, cond, how in joins:  # left to right: a semi / anti join filters the rows of the joins before it
+            df = df.join(other, on=cond, how=how)
         if has_where:
             df = df.filter(where)
         if has_group:
@@ -523,22 +533,26 @@ class _Parser:
         has_alias, alias = self.attempt(self.alias)
         return df.alias(alias) if has_alias else df
 
-    def join_clause(self) -> tuple[DataFrame, Col]:
-        def kind(words: tuple[str, ...]) -> Callable[[], None]:
-            def rule() -> None:
+    def join_clause(self) -> tuple[DataFrame, Col, str]:
+        """-> (right table, condition, kind): "inner" for the reference's five spellings (it runs them all as the inner
+        join), "left_semi" / "left_anti" for [LEFT] SEMI JOIN / [LEFT] ANTI JOIN, which are tried after those five."""
+        def kind(words: tuple[str, ...], how: str) -> Callable[[], str]:
+            def rule() -> str:
                 self.lit(words[0])
                 for w in words[1:]:
                     self.ws()
                     self.lit(w)
+                return how
             return rule
 
-        self.first_of(*[kind(words) for words in _JOIN_KINDS])
+        how = self.first_of(*[kind(words, "inner") for words in _JOIN_KINDS],
+                            *[kind(words, how) for words, how in _SEMI_JOIN_KINDS])
         self.ws()
         table = self.table_reference()
         self.ws()
         self.lit("ON")
         self.ws()
-        return table, self.condition()
+        return table, self.condition(), how
 
     def where_clause(self) -> Col:
         self.lit("WHERE")

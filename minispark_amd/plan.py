@@ -17,6 +17,9 @@ Rewrites applied, in the reference's order (plan.py:224-235):
    2a. a GROUP BY over several columns (``KeyTupleCol``, this build's own): both aggregates and the shuffle write see the
    tuple as ONE packed STRING column under the tuple's reserved name, and an ``UnpackKeyTask`` directly above the merging
    aggregate - below the AVG projection, HAVING, the final select and any ``SortTask`` - restores the key columns;
+   2c. a ``SemiJoinTask`` (LEFT SEMI / LEFT ANTI join, this build's own): the right input becomes
+   right -> Filter(each right-side conjunct of the condition) -> Project(right key), so only the key column is
+   materialised; both inputs get a WriteToShufflePartitions on their key as a join's do, and the stage is cut there;
    2b. ``COUNT(DISTINCT e)`` (this build's own): one ``MarkFirstTask`` directly under the partial aggregate
    appends a first-occurrence mark column per distinct argument, and the aggregate carries ``SUM(mark)`` under the
    requested name in its place (the ``expand_avg`` pattern) - the merge and everything above it see an integer SUM;
@@ -36,10 +39,12 @@ from .tasks import (
     AggregateTask,
     BroadcastHashJoinTask,
     ConsumerTask,
+    FilterTask,
     LoadShuffleFilesTask,
     MarkFirstTask,
     ProducerTask,
     ProjectTask,
+    SemiJoinTask,
     SortTask,
     Task,
     UnpackKeyTask,
@@ -94,7 +99,7 @@ def _cut(top: Task) -> Stage:
     next stage down)."""
     node = top
     while True:
-        if type(node) is BroadcastHashJoinTask:
+        if type(node) in (BroadcastHashJoinTask, SemiJoinTask):
             left_top, right_top = node.parent_task, node.right_side_task
             node.parent_task, node.right_side_task = VoidTask(), VoidTask()
             return Stage(top, [_cut(left_top), _cut(right_top)])
@@ -122,7 +127,7 @@ class PhysicalPlan:
         node: Task | None = task
         while node is not None and type(node) is not VoidTask:
             node.inferred_schema = node.validate_schema()
-            if type(node) is BroadcastHashJoinTask:
+            if type(node) in (BroadcastHashJoinTask, SemiJoinTask):
                 PhysicalPlan.infer_schema(node.right_side_task)
             node = node.parent_task
 
@@ -135,6 +140,17 @@ class PhysicalPlan:
             task.right_side_task = PhysicalPlan.expand_tasks(task.right_side_task)
             task.parent_task = WriteToShufflePartitions(task.parent_task, key_column=task.left_key)
             task.right_side_task = WriteToShufflePartitions(task.right_side_task, key_column=task.right_key)
+            return task
+        if type(task) is SemiJoinTask:
+            # the right input is a key SET: its conditions, then the key column alone (rewrite 2c); both inputs end in a
+            # shuffle write as a join's do - no row moves here, the write quantises them to their stored types
+            right = PhysicalPlan.expand_tasks(task.right_side_task)
+            for cond in task.right_filters:
+                right = FilterTask(right, condition=cond)
+            right = ProjectTask(right, columns=[Col(task.right_key.name)])
+            task.parent_task = WriteToShufflePartitions(task.parent_task, key_column=task.left_key)
+            task.right_side_task = WriteToShufflePartitions(right, key_column=task.right_key)
+            task.expanded = True
             return task
         if type(task) is AggregateTask and task.before_shuffle:
             requested = task.agg_columns
@@ -197,7 +213,7 @@ class PhysicalPlan:
                                  "operation, not below a join, an aggregate or another operation")
             if type(node) is SortTask and not top:
                 raise ValueError("DISTINCT / ORDER BY / LIMIT must be the last operation")
-            if type(node) is BroadcastHashJoinTask:
+            if type(node) in (BroadcastHashJoinTask, SemiJoinTask):
                 PhysicalPlan.check_sort_is_last(node.right_side_task, top=False)
             top = False
             node = node.parent_task

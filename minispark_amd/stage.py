@@ -143,6 +143,9 @@ def _plan_of(full_task: Any, plan: Any) -> list:
     """The stages of ``plan``, or of the physical plan of ``full_task`` when none is given."""
     stages = list((plan if plan is not None else PhysicalPlan.generate_physical_plan(full_task)).stages)
     for stage in stages:
+        if _cls(stage.producer) == "SemiJoinTask":
+            # (no stage blob describes a key set; the engine runs it through Device.semi_select: DESIGN.md 4.4j)
+            raise StageUnsupported("a LEFT SEMI / LEFT ANTI join")
         for task in stage.consumers:
             if _cls(task) == "MarkFirstTask":
                 # (the marks are a pass over the whole batch in front of the scan: DESIGN.md 4.4e)

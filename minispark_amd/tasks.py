@@ -21,7 +21,7 @@ from .constants import ColumnType, Schema
 from .io import BlockFile
 from .sql import BINOP_SYMBOLS, AggCol, BinaryOperatorColumn, Col, KeyTupleCol, LikeColumn
 
-JoinType = Literal["inner", "left", "right", "outer"]
+JoinType = Literal["inner", "left", "right", "outer", "left_semi", "left_anti"]
 
 
 def nice_schema(schema: Schema | None) -> str:
@@ -184,6 +184,94 @@ class BroadcastHashJoinTask(ProducerTask):
 
     def describe(self) -> str:
         return f'Join({self.join_condition}, "{self.how}")'
+
+    def explain(self, lvl: int = 0) -> None:
+        indent = "  " * lvl + ("+- " if lvl > 0 else "")
+        print(f"{indent} {self.describe()}:{nice_schema(self.inferred_schema)}")  # noqa: T201
+        self.parent_task.explain(lvl + 1)
+        self.right_side_task.explain(lvl + 1)
+
+
+def _conjuncts(cond: Col) -> list[Col]:
+    """The operands of the AND chain on top of a condition, left to right."""
+    if type(cond).__name__ == "BinaryOperatorColumn" and BINOP_SYMBOLS[cond.operator] == "and":
+        return [*_conjuncts(cond.left_side), *_conjuncts(cond.right_side)]
+    return [cond]
+
+
+SEMI_KEY_TYPES = (ColumnType.INTEGER, ColumnType.STRING, ColumnType.TIMESTAMP)
+
+
+@dataclass(kw_only=True)
+class SemiJoinTask(ProducerTask):
+    """LEFT SEMI / LEFT ANTI join (no reference counterpart: DESIGN.md 4.4j): the rows of the LEFT input (``parent_task``)
+    whose key occurs (``anti``: does not occur) in the right input's key column - the left input's columns, rows and order,
+    i.e. ``left WHERE key IN {right keys}``.  ``join_condition`` is one equality between a plain column of each side,
+    optionally AND-ed with conditions over right-side columns only (``... ON o_orderkey = l_orderkey AND l_commitdate <
+    l_receiptdate``); ``validate_schema`` resolves it into ``left_key``, ``right_key`` and ``right_filters``, which the planner
+    places on the right input.  A class of its own, not a ``how`` of the inner join: nothing that matches the inner join by
+    name - fused probes, native stages - can take it for one."""
+
+    right_side_task: Task
+    join_condition: Col
+    anti: bool = False
+    left_key: Col | None = None
+    right_key: Col | None = None
+    right_filters: list[Col] = field(default_factory=list)
+    left_schema: Schema | None = None
+    right_schema: Schema | None = None
+    expanded: bool = False  # the planner has moved right_filters below the right input's key projection
+
+    @property
+    def how(self) -> str:
+        return "left_anti" if self.anti else "left_semi"
+
+    def validate_schema(self) -> Schema:
+        self.left_schema = self.parent_task.validate_schema()
+        self.right_schema = self.right_side_task.validate_schema()
+        if not self.expanded:
+            self._resolve_condition()
+        left_type = self.left_key.infer_type(self.left_schema)
+        right_type = self.right_key.infer_type(self.right_schema)
+        if left_type != right_type or left_type not in SEMI_KEY_TYPES:
+            raise TypeError(f"{self.how} join on {self.left_key.name}:{left_type} = {self.right_key.name}:{right_type}: the keys "
+                            "are two INTEGER, two STRING or two TIMESTAMP columns (a FLOAT key has no exact equality)")
+        return list(self.left_schema)
+
+    def _resolve_condition(self) -> None:
+        left_names = {n for n, _ in self.left_schema}
+        right_names = {n for n, _ in self.right_schema}
+        _check_known([self.join_condition], self.left_schema + self.right_schema, "Join")
+        key, filters = None, []
+        for part in _conjuncts(self.join_condition):
+            names = set(_plain_column_names(part))
+            on_left, on_right = names & left_names, names & right_names
+            if on_left & on_right:
+                raise ValueError(f"{self.how} join: {part} names {sorted(on_left & on_right)}, which both inputs hold: alias() "
+                                 "the tables")
+            if on_left and on_right:
+                is_key = (type(part).__name__ == "BinaryOperatorColumn" and BINOP_SYMBOLS[part.operator] == "=="
+                          and type(part.left_side).__name__ == "Col" and type(part.right_side).__name__ == "Col")
+                if not is_key or key is not None:
+                    raise ValueError(f"{self.how} join: the condition {part} reads both inputs; beside ONE equality between a "
+                                     "plain column of each side, a condition may read the right input only")
+                key = part
+            elif on_left:
+                raise ValueError(f"{self.how} join: the condition {part} reads the left input only: it belongs in WHERE "
+                                 "(filter() the left input)")
+            else:
+                if type(part).__name__ not in {"BinaryOperatorColumn", "LikeColumn"}:
+                    raise ValueError(f"{self.how} join: {part} is no condition")
+                part.infer_type(self.right_schema)
+                filters.append(part)
+        if key is None:
+            raise ValueError(f"{self.how} join: the condition {self.join_condition} holds no equality between a plain column of "
+                             "each side")
+        self.left_key, self.right_key = key.extract_left_right_key(self.left_schema, self.right_schema)
+        self.right_filters = filters
+
+    def describe(self) -> str:
+        return f'SemiJoin({self.join_condition}, "{self.how}")'
 
     def explain(self, lvl: int = 0) -> None:
         indent = "  " * lvl + ("+- " if lvl > 0 else "")
@@ -440,6 +528,7 @@ __all__ = [
     "MarkFirstTask",
     "ProducerTask",
     "ProjectTask",
+    "SemiJoinTask",
     "SortTask",
     "Task",
     "UnpackKeyTask",
