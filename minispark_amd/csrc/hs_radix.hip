@@ -1,4 +1,18 @@
-// hs_radix.hip - the HBM tier of GROUP BY as a radix partition + on-chip ordered fold (round 2).
+// hs_radix.hip - everything built on the stable radix partition pass.  In file order:
+//
+//   partition pass      k_rx_tiles / rx_pass: RxPass, the tile routines (rx_tile, rx_peers, rx_rank, rx_bin_starts, ...) behind
+//                       the generic, 4-byte and wide-STRING histogram / scatter kernels
+//   fold                GROUP BY's HBM tier: rx_fold_walk (one partition walk) under k_rx_fold (any aggregate) and
+//                       k_rx_fold_sum (SUM / COUNT classes), dense output, hs_group_radix_plan / run / emit
+//   hs_sort_by_order    the merge order of a multi-rank final aggregate: a stable sort of small integers
+//   ORDER BY            hs_order_by: ob_sort and top-k over result rows
+//   DISTINCT            hs_distinct: duplicate-row removal over result rows
+//   mark-first          hs_mark_first: first-occurrence marks, what COUNT(DISTINCT e) sums
+//   windows             hs_window, hs_window_agg, hs_window_nav, hs_window_frames over ob_sort's (partition, order) runs
+//   join builds         dense (hs_join_dense_*), keyset (hs_keyset_*: LEFT SEMI / ANTI), hashed (hs_join_hash_*) and STRING
+//                       (hs_join_hash_str_*): one partition or window per wave in LDS, jx_count / jx_scan / jx_place / jx_emit
+//
+// The HBM tier of GROUP BY as a radix partition + on-chip ordered fold (round 2):
 //
 // Reference loop replaced: AggregateTask over a block, tasks.py:284-310 - a Python dict per block, every row folded
 // into its group's accumulators in row order (fp64 / int), written to the shuffle file at the block's end.
@@ -20,6 +34,7 @@
 // hs_group_radix_run.  A partition that meets more distinct keys than its dictionary holds raises HS_FLAG_DICT_FULL
 // (the caller takes the round-1 path).  Keys: INTEGER / TIMESTAMP (the key word is the value).
 #include <type_traits>
+#include <utility>
 #include "hs_device.h"
 
 #include <cstdlib>
@@ -217,16 +232,33 @@ __device__ __forceinline__ void rx_hist_tile(const RxPass& A, uint32_t (*hist)[1
     }
     rx_hist_store<WAVES>(A, T, hist);
 }
-// One step of a wave's ranking (64 rows in order): a row's rank among the rows of its bin that this wave has ranked so
-// far = the wave's running count of the bin + its rank among this step's equal-bin lanes (the AND of one ballot per bin
-// bit).  The bin's first lane of the step is the only writer of whist_w[bin].
-__device__ __forceinline__ uint32_t rx_rank(uint32_t* whist_w, uint32_t bin, bool valid, int bits, uint64_t below) {
+// The valid lanes of a 64-row step that hold the same id (a bin, a dictionary slot) as this lane: the AND of one ballot
+// per id bit.  Lane order is row order, so a lane's rank among its peers is popc(peers & below).  The partition pass, both
+// folds and the join builds' jx_place rank with it; a compile-time `bits` unrolls.
+__device__ __forceinline__ uint64_t rx_peers(uint32_t id, bool valid, int bits) {
     uint64_t peers = __ballot(valid);
     for (int bit = 0; bit < bits; ++bit) {
-        const bool on = (bin >> bit) & 1u;
+        const bool on = (id >> bit) & 1u;
         const uint64_t bal = __ballot(valid && on);
         peers &= on ? bal : ~bal;
     }
+    return peers;
+}
+// Cross-lane read-after-write through LDS inside ONE wave (the SUM fold's rank rounds and second key word, the join
+// builds' cursors and tags): the hardware runs a wave's LDS instructions in order, but the COMPILER must be told not to
+// move the plain loads / stores across the hand-over - __builtin_amdgcn_wave_barrier alone is a scheduling barrier, not a
+// memory fence.  Wavefront-scope fences cost no instruction (no s_waitcnt at this scope); they pin the order in the source
+// instead of in today's codegen.
+__device__ __forceinline__ void rx_wave_handover() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// One step of a wave's ranking (64 rows in order): a row's rank among the rows of its bin that this wave has ranked so
+// far = the wave's running count of the bin + its rank among this step's equal-bin lanes (rx_peers).  The bin's first
+// lane of the step is the only writer of whist_w[bin].
+__device__ __forceinline__ uint32_t rx_rank(uint32_t* whist_w, uint32_t bin, bool valid, int bits, uint64_t below) {
+    const uint64_t peers = rx_peers(bin, valid, bits);
     const uint32_t prior = valid ? whist_w[bin] : 0u;
     const uint32_t rank = (uint32_t)__popcll(peers & below);
     if (valid && rank == 0) whist_w[bin] = prior + (uint32_t)__popcll(peers);
@@ -624,15 +656,6 @@ struct RxAgg {
     int64_t* overflow_count;
 };
 
-__device__ __forceinline__ uint64_t rx_cell(const void* src, int kind, int64_t i) {
-    switch (kind) {
-        case HS_I32: return (uint64_t)(int64_t)((const int32_t*)src)[i];
-        case HS_F32: return hs_d2u((double)((const float*)src)[i]);
-        case HS_U8: return (uint64_t)((const uint8_t*)src)[i];
-        default: return ((const uint64_t*)src)[i];  // HS_I64 / HS_F64: the cell itself
-    }
-}
-
 __device__ __forceinline__ uint64_t rx_widen(uint64_t raw, int kind) {
     switch (kind) {
         case HS_I32: return (uint64_t)(int64_t)(int32_t)(uint32_t)raw;
@@ -644,45 +667,86 @@ __device__ __forceinline__ uint64_t rx_raw(const void* src, int esize, int64_t i
     return esize == 4 ? (uint64_t)((const uint32_t*)src)[i] : esize == 8 ? ((const uint64_t*)src)[i] : (uint64_t)((const uint8_t*)src)[i];
 }
 
-// HIPSPARK_RADIX_STAMPS=1: cycles (s_memtime) a wave spends per phase of k_rx_fold, summed over all waves
+// HIPSPARK_RADIX_STAMPS=1: cycles (s_memtime) a wave spends per phase of k_rx_fold, summed over all waves.  The walk
+// marks its phases through its policy: the general fold answers with RxStamps, the SUM fold with RxNoStamps - nothing.
 __device__ unsigned long long rx_stamp_acc[8];
-#define RX_T(var) const long long var = A.debug ? (long long)clock64() : 0
+enum { RX_T_INIT, RX_T_WAIT, RX_T_SLOT, RX_T_RANK, RX_T_FOLD, RX_T_EMIT, RX_T_PHASES };
+struct RxStamps {
+    const bool on;
+    long long from = 0, t[RX_T_PHASES] = {};
+    __device__ __forceinline__ void mark() { from = on ? (long long)clock64() : 0; }  // a phase starts
+    __device__ __forceinline__ void lap(int phase) {                                   // ... ends, and the next one starts
+        const long long now = on ? (long long)clock64() : 0;
+        t[phase] += now - from;
+        from = now;
+    }
+    __device__ __forceinline__ void flush(int lane) const {
+        if (!on || lane) return;
+        for (int k = 0; k < RX_T_PHASES; ++k) atomicAdd(&rx_stamp_acc[k], (unsigned long long)t[k]);
+        atomicAdd(&rx_stamp_acc[RX_T_PHASES], 1ull);
+    }
+};
+struct RxNoStamps {
+    __device__ __forceinline__ void mark() {}
+    __device__ __forceinline__ void lap(int) {}
+    __device__ __forceinline__ void flush(int) const {}
+};
 
 constexpr int RX_CHUNK = 4;  // 64-row steps loaded together; the next chunk is in flight while this one is folded
 
-// NC = value columns that travel with the rows (0 .. 4 specialised: the tuples of a chunk sit in registers;
-// -1: any number, one global round trip per step and column).
+// 8-byte words of LDS one fold wave takes: keys[cap] (a wide key: and keys1[cap], its second word), acc[n_acc][cap] and
+// order[cap] (u16).  The plan sizes cap by it, the launch the workgroup's LDS, the kernel carves by it.
+__host__ __device__ constexpr size_t rx_fold_words(int cap, int n_acc, bool wide) {
+    return (size_t)cap * (1 + (wide ? 1 : 0) + n_acc) + (size_t)cap / 4;
+}
+struct RxWave {  // a fold wave's tables, and what every step of it needs
+    uint64_t* keys;   // [cap]
+    uint64_t* keys1;  // [cap] wide keys only
+    uint64_t* acc;    // [n_acc][cap]
+    uint16_t* order;  // [cap] the slots in the order their keys first appeared = the order the groups are written in
+    int cap;
+    uint32_t mask;
+    uint64_t below;   // the lanes before this one
+};
+
+// ONE WAVE per partition, both folds.  The tables are cleared once per wave; after a partition only the slots on its
+// order list are reset, so a partition costs its rows and its groups, not the table size.  Rows are taken 64 at a time in
+// order, RX_CHUNK steps loaded together; the rows of a step that share a slot (rx_peers) reach the accumulators in lane =
+// row order.  The partition's groups go to its own start in first-appearance order.
 //
-// A wave's tables: keys[cap], acc[NA][cap] and order[cap] - the slots in the order their keys first appeared, which is
-// also the order the partition's groups are written in.  The tables are cleared once per wave; after a partition only
-// the slots on its list are reset, so a partition costs its rows and its groups, not the table size.
+// Up to three launches share a kernel, smallest table first (hs_group_radix_run): a partition that meets more keys than
+// 3/4 of a table that is not the last is put on the overflow list instead of being finished; the next launch (A.list set)
+// takes the listed partitions; the last table is the one the plan sized for the worst case (every row its own group), and
+// outgrowing it raises HS_FLAG_DICT_FULL.
 //
-// Two launches share the kernel: the first with a SMALL table (512 slots: many waves per CU), where a partition that
-// meets more keys than 3/4 of it is put on the overflow list instead of being finished; the second (A.list set) takes
-// the listed partitions with the big table the plan sized for the worst case (every row its own group).
-template <int NC, int SLOT_BITS>
-__global__ void __launch_bounds__(256) k_rx_fold(const RxAgg A_kernarg) {
-    HS_KERNARG(RxAgg, A);
-    extern __shared__ __align__(16) uint64_t rx_lds[];
+// A policy P says what the walk does not know - nothing here depends on the kind of an aggregate:
+//   Chunk, load(chunk, base, e, lane)          RX_CHUNK steps of the partition's tuples as registers (0 past the end e)
+//   find(T, chunk, j, slot, inserted)          the dictionary slot of step j's row (valid lanes; slot stays -1: no room)
+//   fold(T, chunk, j, i, valid, slot, peers)   step j's rows into acc[][slot], every f64 cell in row order
+//   n_acc(), is_int(a), identity(a), check(a, cell, err)   the cells: their number, empty value and emit-time check
+//   slot_bits(cap), WIDE, stamps
+template <typename P>
+__device__ __forceinline__ void rx_fold_walk(const RxAgg& A, uint64_t* lds, P pol) {
     const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE, wpb = blockDim.x / HS_WAVE;
-    const int NA = A.spec.n_acc, cap = A.cap;
-    const size_t per_wave = (size_t)cap * (1 + NA) + (size_t)cap / 4;  // in 8-byte words; order[] is u16
-    uint64_t* keys = rx_lds + (size_t)w * per_wave;  // [cap]
-    uint64_t* acc = keys + cap;                       // [NA][cap]
-    uint16_t* order = (uint16_t*)(acc + (size_t)NA * cap);
-    const uint32_t mask = (uint32_t)cap - 1u;
-    const int limit = A.last ? cap : cap - cap / 4;   // groups a partition may hold in this launch
-    const uint64_t below = (1ull << lane) - 1ull;
-    constexpr int NCR = NC > 0 ? NC : 1;
+    const int NA = pol.n_acc(), cap = A.cap;
+    RxWave T;
+    T.keys = lds + (size_t)w * rx_fold_words(cap, NA, P::WIDE);
+    T.keys1 = T.keys + cap;
+    T.acc = T.keys + (P::WIDE ? 2 : 1) * cap;
+    T.order = (uint16_t*)(T.acc + (size_t)NA * cap);
+    T.cap = cap;
+    T.mask = (uint32_t)cap - 1u;
+    T.below = (1ull << lane) - 1ull;
+    const int limit = A.last ? cap : cap - cap / 4;  // groups a partition may hold in this launch
+    const int slot_bits = pol.slot_bits(cap);
     uint32_t err = 0;
-    long long t_init = 0, t_slot = 0, t_rank = 0, t_fold = 0, t_emit = 0, t_wait = 0;
-    if ((int64_t)blockIdx.x * wpb + w >= (A.list ? *A.list_count : A.n_parts)) return;  // nothing for this wave: no table to clear
-    for (int s = lane; s < cap; s += HS_WAVE) keys[s] = HS_EMPTY_KEY;
-    for (int a = 0; a < NA; ++a) {
-        const uint64_t id = hs_acc_identity(A.spec.op[a], A.spec.is_int[a] != 0);
-        for (int s = lane; s < cap; s += HS_WAVE) acc[a * cap + s] = id;
-    }
     const int64_t n_todo = A.list ? *A.list_count : A.n_parts;
+    if ((int64_t)blockIdx.x * wpb + w >= n_todo) return;  // nothing listed for this wave: no table to clear either
+    for (int s = lane; s < cap; s += HS_WAVE) T.keys[s] = HS_EMPTY_KEY;
+    for (int a = 0; a < NA; ++a) {
+        const uint64_t id = pol.identity(a);
+        for (int s = lane; s < cap; s += HS_WAVE) T.acc[a * cap + s] = id;
+    }
     for (int64_t q = (int64_t)blockIdx.x * wpb + w; q < n_todo; q += (int64_t)gridDim.x * wpb) {
         const int64_t p = A.list ? A.list[q] : q;
         const int64_t b = A.seg_start[p], e = A.seg_start[p + 1];
@@ -690,143 +754,62 @@ __global__ void __launch_bounds__(256) k_rx_fold(const RxAgg A_kernarg) {
             if (lane == 0) A.pcount[p] = 0;
             continue;
         }
-        RX_T(c0);
-        uint64_t nk[RX_CHUNK], nx[RX_CHUNK][NCR];
-        auto load_chunk = [&](int64_t base) {
-#pragma unroll
-            for (int j = 0; j < RX_CHUNK; ++j) {
-                const int64_t i = base + j * HS_WAVE + lane;
-                const bool valid = i < e;
-                nk[j] = !valid ? 0 : (A.esize[0] == 4 ? (uint64_t)(int64_t)((const int32_t*)A.src[0])[i] : ((const uint64_t*)A.src[0])[i]);
-                if constexpr (NC > 0) {
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) nx[j][c] = valid ? rx_raw(A.src[1 + c], A.esize[1 + c], i) : 0;
-                }
-            }
-        };
-        load_chunk(b);
+        pol.stamps.mark();
+        typename P::Chunk next;
+        pol.load(next, b, e, lane);
         int ngroups = 0;
         bool full = false;
-        RX_T(c1);
-        t_init += c1 - c0;
+        pol.stamps.lap(RX_T_INIT);
         for (int64_t base = b; base < e && !full; base += RX_CHUNK * HS_WAVE) {
-            RX_T(w0);
-            uint64_t ck[RX_CHUNK], cx[RX_CHUNK][NCR];
+            pol.stamps.mark();
+            const typename P::Chunk cur = next;
+            pol.stamps.lap(RX_T_WAIT);  // only the register copy: nothing here waits for the loads, the first use (SLOT) does
+            if (base + RX_CHUNK * HS_WAVE < e) pol.load(next, base + RX_CHUNK * HS_WAVE, e, lane);
 #pragma unroll
             for (int j = 0; j < RX_CHUNK; ++j) {
-                ck[j] = nk[j];
-#pragma unroll
-                for (int c = 0; c < NCR; ++c) cx[j][c] = NC > 0 ? nx[j][c] : 0;
-            }
-            if (A.debug) t_wait += (long long)(ck[0] & 1) * 0 + (long long)clock64() - w0;  // the chunk's loads have landed
-            if (base + RX_CHUNK * HS_WAVE < e) load_chunk(base + RX_CHUNK * HS_WAVE);
-#pragma unroll
-            for (int j = 0; j < RX_CHUNK; ++j) {
-                const int64_t i = base + j * HS_WAVE + lane;
                 if (base + j * HS_WAVE >= e || full) break;
+                const int64_t i = base + j * HS_WAVE + lane;
                 const bool valid = i < e;
-                RX_T(s0);
-                int slot = 0;
+                pol.stamps.mark();
+                int slot = valid ? -1 : 0;
                 bool inserted = false;
-                if (valid) {
-                    const uint64_t k = ck[j];
-                    uint32_t h = (uint32_t)(hs_mix64(k) >> 36) & mask;
-                    slot = -1;
-                    for (uint32_t probe = 0; probe <= mask; ++probe) {
-                        uint64_t cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (cur == HS_EMPTY_KEY) {
-                            cur = atomicCAS((unsigned long long*)&keys[h], (unsigned long long)HS_EMPTY_KEY, (unsigned long long)k);
-                            if (cur == HS_EMPTY_KEY) {
-                                cur = k;
-                                inserted = true;
-                            }
-                        }
-                        if (cur == k) {
-                            slot = (int)h;
-                            break;
-                        }
-                        h = (h + 1) & mask;
-                    }
-                }
+                if (valid) pol.find(T, cur, j, slot, inserted);
                 const uint64_t fresh = __ballot(inserted);
-                if (inserted) order[ngroups + __popcll(fresh & below)] = (uint16_t)slot;
+                if (inserted) T.order[ngroups + __popcll(fresh & T.below)] = (uint16_t)slot;
                 ngroups += __popcll(fresh);
                 if (ngroups > limit || __ballot(valid && slot < 0) != 0ull) {  // too many keys for this table
                     full = true;
                     break;
                 }
-                // lanes of this step in the same group (one ballot per slot bit, SLOT_BITS >= log2(cap)), my rank among
-                // them: row order = lane order
-                RX_T(s1);
-                t_slot += s1 - s0;
-                uint64_t peers = __ballot(valid);
-#pragma unroll
-                for (int bit = 0; bit < SLOT_BITS; ++bit) {
-                    const bool on = (slot >> bit) & 1;
-                    peers &= ~(__ballot(valid && on) ^ (on ? ~0ull : 0ull));
-                }
-                const int rank = __popcll(peers & below);
-                const int most = __popcll(peers);
-                uint64_t crowded = __ballot(valid && most > 1);
-                RX_T(s2);
-                t_rank += s2 - s1;
-                for (int a = 0; a < NA; ++a) {
-                    const uint32_t op = A.spec.op[a];
-                    const bool is_int = A.spec.is_int[a] != 0;
-                    const int c = A.carried[a];
-                    uint64_t x = A.const_cell[a];
-                    if (c) {
-                        uint64_t raw = 0;
-                        if constexpr (NC > 0) {
-#pragma unroll
-                            for (int cc = 0; cc < NC; ++cc)
-                                if (c - 1 == cc) raw = cx[j][cc];
-                        } else {
-                            raw = valid ? rx_raw(A.src[c], A.esize[c], i) : 0;
-                        }
-                        x = rx_widen(raw, A.val_kind[a]);
-                    }
-                    // a group's first lane of the step folds the values of all its lanes, in lane order, from registers
-                    uint64_t v = 0;
-                    const bool leader = valid && rank == 0;
-                    if (leader) v = hs_acc_fold(op, is_int, acc[a * cap + slot], x);
-                    if (crowded) {
-                        uint64_t rest = leader ? peers & ~(1ull << lane) : 0ull;
-                        while (__ballot(rest != 0ull) != 0ull) {
-                            const int from = rest ? __ffsll((long long)rest) - 1 : lane;
-                            const uint64_t xv = __shfl(x, from, HS_WAVE);
-                            if (rest) {
-                                v = hs_acc_fold(op, is_int, v, xv);
-                                rest &= rest - 1;
-                            }
-                        }
-                    }
-                    if (leader) acc[a * cap + slot] = v;
-                }
-                if (A.debug) t_fold += (long long)clock64() - s2;
+                pol.stamps.lap(RX_T_SLOT);
+                const uint64_t peers = rx_peers((uint32_t)slot, valid, slot_bits);
+                pol.stamps.lap(RX_T_RANK);
+                pol.fold(T, cur, j, i, valid, slot, peers);
+                pol.stamps.lap(RX_T_FOLD);
             }
         }
-        RX_T(e0);
+        pol.stamps.mark();
         if (full) {
-            // leave the partition to the launch with the big table (or, from that one, to the caller's other path)
+            // leave the partition to the launch with the next table (or, from the last one, to the caller's other path)
             if (A.last) err |= HS_FLAG_DICT_FULL;
             else if (lane == 0) A.overflow[atomicAdd((unsigned long long*)A.overflow_count, 1ull)] = p;
             if (lane == 0) A.pcount[p] = 0;
         }
-        // the partition's groups, in the order their keys first appeared, from the partition's own start
+        // the partition's groups, in the order their keys first appeared, from the partition's own start; their slots reset
         for (int g0 = 0; g0 < ngroups; g0 += HS_WAVE) {
             const int g = g0 + lane;
             if (g >= ngroups) continue;
-            const int s = order[g];
+            const int s = T.order[g];
             const int64_t at = b + g;
-            if (!full) A.prov_key[at] = keys[s];
-            keys[s] = HS_EMPTY_KEY;
+            if (!full) A.prov_key[at] = T.keys[s];
+            if (P::WIDE && !full) A.prov_key1[at] = T.keys1[s];
+            T.keys[s] = HS_EMPTY_KEY;
             for (int a = 0; a < NA; ++a) {
-                const bool is_int = A.spec.is_int[a] != 0;
-                uint64_t v = acc[a * cap + s];
-                acc[a * cap + s] = hs_acc_identity(A.spec.op[a], is_int);
+                const bool is_int = pol.is_int(a);
+                uint64_t v = T.acc[a * cap + s];
+                T.acc[a * cap + s] = pol.identity(a);
                 if (full) continue;
-                if (hs_float_identity_left(A.spec.op[a], is_int, v)) err |= HS_FLAG_TYPE_ASSERT;
+                pol.check(a, v, err);
                 if (A.quantise) {
                     v = hs_quantise_cell(is_int, v, err);
                     if (is_int) ((int32_t*)A.prov_acc[a])[at] = (int32_t)(int64_t)v;
@@ -837,225 +820,228 @@ __global__ void __launch_bounds__(256) k_rx_fold(const RxAgg A_kernarg) {
             }
         }
         if (!full && lane == 0) A.pcount[p] = ngroups;
-        if (A.debug) t_emit += (long long)clock64() - e0;
+        pol.stamps.lap(RX_T_EMIT);
     }
     if (err) atomicOr(A.flags, err);
-    if (A.debug && lane == 0) {
-        atomicAdd(&rx_stamp_acc[0], (unsigned long long)t_init);
-        atomicAdd(&rx_stamp_acc[1], (unsigned long long)t_wait);
-        atomicAdd(&rx_stamp_acc[2], (unsigned long long)t_slot);
-        atomicAdd(&rx_stamp_acc[3], (unsigned long long)t_rank);
-        atomicAdd(&rx_stamp_acc[4], (unsigned long long)t_fold);
-        atomicAdd(&rx_stamp_acc[5], (unsigned long long)t_emit);
-        atomicAdd(&rx_stamp_acc[6], 1ull);
-    }
+    pol.stamps.flush(lane);
 }
 
-// Cross-lane read-after-write through LDS inside ONE wave (the rank rounds and the wide key's second word below): the
-// hardware runs a wave's LDS instructions in order, but the COMPILER must be told not to move the plain loads / stores
-// across the hand-over - __builtin_amdgcn_wave_barrier alone is a scheduling barrier, not a memory fence.  Wavefront-scope
-// fences cost no instruction (no s_waitcnt at this scope); they pin the order in the source instead of in today's codegen.
-__device__ __forceinline__ void rx_wave_handover() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+// ---- the general fold: any operator over any cell kind ------------------------------------------------------------------
+// NC = value columns that travel with the rows (0 .. 4 specialised: the tuples of a chunk sit in registers; -1: any
+// number, one global round trip per step and column).  SLOT_BITS >= log2(cap): 9 for the small tables, 12 for the large.
+// A group's first lane of a step folds the values of all its lanes, in lane order, collecting them by shuffle.
+template <int NC, int SLOT_BITS>
+struct RxFoldAny {
+    static constexpr bool WIDE = false;
+    struct Chunk {
+        uint64_t k[RX_CHUNK], x[RX_CHUNK][NC > 0 ? NC : 1];
+    };
+    const RxAgg& A;
+    RxStamps stamps;
+    __device__ __forceinline__ int n_acc() const { return A.spec.n_acc; }
+    __device__ __forceinline__ int slot_bits(int) const { return SLOT_BITS; }
+    __device__ __forceinline__ bool is_int(int a) const { return A.spec.is_int[a] != 0; }
+    __device__ __forceinline__ uint64_t identity(int a) const { return hs_acc_identity(A.spec.op[a], is_int(a)); }
+    __device__ __forceinline__ void check(int a, uint64_t cell, uint32_t& err) const {
+        if (hs_float_identity_left(A.spec.op[a], is_int(a), cell)) err |= HS_FLAG_TYPE_ASSERT;
+    }
+    __device__ __forceinline__ void load(Chunk& n, int64_t base, int64_t e, int lane) const {
+#pragma unroll
+        for (int j = 0; j < RX_CHUNK; ++j) {
+            const int64_t i = base + j * HS_WAVE + lane;
+            const bool valid = i < e;
+            n.k[j] = !valid ? 0 : (A.esize[0] == 4 ? (uint64_t)(int64_t)((const int32_t*)A.src[0])[i] : ((const uint64_t*)A.src[0])[i]);
+            n.x[j][0] = 0;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) n.x[j][c] = valid ? rx_raw(A.src[1 + c], A.esize[1 + c], i) : 0;
+        }
+    }
+    __device__ __forceinline__ void find(const RxWave& T, const Chunk& ch, int j, int& slot, bool& inserted) const {
+        const uint64_t k = ch.k[j];
+        uint32_t h = (uint32_t)(hs_mix64(k) >> 36) & T.mask;
+        for (uint32_t probe = 0; probe <= T.mask; ++probe) {
+            uint64_t cur = __hip_atomic_load(&T.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (cur == HS_EMPTY_KEY) {
+                cur = atomicCAS((unsigned long long*)&T.keys[h], (unsigned long long)HS_EMPTY_KEY, (unsigned long long)k);
+                if (cur == HS_EMPTY_KEY) {
+                    cur = k;
+                    inserted = true;
+                }
+            }
+            if (cur == k) {
+                slot = (int)h;
+                break;
+            }
+            h = (h + 1) & T.mask;
+        }
+    }
+    __device__ __forceinline__ void fold(const RxWave& T, const Chunk& ch, int j, int64_t i, bool valid, int slot, uint64_t peers) const {
+        const int lane = threadIdx.x & (HS_WAVE - 1), NA = A.spec.n_acc;
+        const bool leader = valid && (peers & T.below) == 0ull;
+        const uint64_t crowded = __ballot(valid && __popcll(peers) > 1);
+        for (int a = 0; a < NA; ++a) {
+            const uint32_t op = A.spec.op[a];
+            const bool is_int = A.spec.is_int[a] != 0;
+            const int c = A.carried[a];
+            uint64_t x = A.const_cell[a];
+            if (c) {
+                uint64_t raw = 0;
+                if constexpr (NC > 0) {
+#pragma unroll
+                    for (int cc = 0; cc < NC; ++cc)
+                        if (c - 1 == cc) raw = ch.x[j][cc];
+                } else {
+                    raw = valid ? rx_raw(A.src[c], A.esize[c], i) : 0;
+                }
+                x = rx_widen(raw, A.val_kind[a]);
+            }
+            uint64_t v = 0;
+            if (leader) v = hs_acc_fold(op, is_int, T.acc[a * T.cap + slot], x);
+            if (crowded) {
+                uint64_t rest = leader ? peers & ~(1ull << lane) : 0ull;
+                while (__ballot(rest != 0ull) != 0ull) {
+                    const int from = rest ? __ffsll((long long)rest) - 1 : lane;
+                    const uint64_t xv = __shfl(x, from, HS_WAVE);
+                    if (rest) {
+                        v = hs_acc_fold(op, is_int, v, xv);
+                        rest &= rest - 1;
+                    }
+                }
+            }
+            if (leader) T.acc[a * T.cap + slot] = v;
+        }
+    }
+};
+template <int NC, int SLOT_BITS>
+__global__ void __launch_bounds__(256) k_rx_fold(const RxAgg A_kernarg) {
+    HS_KERNARG(RxAgg, A);
+    extern __shared__ __align__(16) uint64_t rx_lds[];
+    rx_fold_walk(A, rx_lds, RxFoldAny<NC, SLOT_BITS>{A, {A.debug != 0}});
 }
 
 // ---- the fold, specialised for SUMs (round 3) ---------------------------------------------------------------------
 // What SUM / AVG / COUNT lower to: every aggregate is a SUM whose argument is an f32 column (class 0: f64 cell), an i32
-// column (class 1: i64 cell) or an integer constant (class 2: COUNT).  Same tables, same launches (small table first,
-// overflow list, big table) and the same order of additions as k_rx_fold - a group's f64 cell takes its rows' values in
-// row order - at about a quarter of the instructions: the classes are compile-time (no per-value switches on kind and
-// operator), the dictionary probe is the compare-and-swap itself, values travel as the 32 bits they are, and the rows of
-// a step that share a group are folded in RANK ROUNDS - round r: the lanes whose rank among their group's lanes is r add
-// their value to the group's cell in LDS (distinct cells within a round; LDS executes a wave's instructions in order, so
-// round r + 1 reads what round r wrote) - instead of a leader lane collecting its peers' values with shuffles.  Integer
-// cells are order-free: one LDS atomic per lane (COUNT: one per group and step, with the group's lane count).
-// KM: 0 = 4-byte key column, 1 = 8-byte key words, 2 .. 4 = a wide STRING key in that many 4-byte word columns (compared as
-// two 64-bit words; the value columns follow the key's)
+// column (class 1: i64 cell) or an integer constant (class 2: COUNT).  The same walk and the same order of additions as
+// the general fold - a group's f64 cell takes its rows' values in row order - at about a quarter of the instructions: the
+// classes are compile-time (no per-value switches on kind and operator), the dictionary probe is the compare-and-swap
+// itself, values travel as the 32 bits they are, and the rows of a step that share a group are folded in RANK ROUNDS -
+// round r: the lanes whose rank among their group's lanes is r add their value to the group's cell in LDS (distinct cells
+// within a round; LDS executes a wave's instructions in order, so round r + 1 reads what round r wrote) - instead of a
+// leader lane collecting its peers' values with shuffles.  Integer cells are order-free: one LDS atomic per lane (COUNT:
+// one per group and step, with the group's lane count).
+// CLS: two bits of class per aggregate.  KM: 0 = 4-byte key column, 1 = 8-byte key words, 2 .. 4 = a wide STRING key in
+// that many 4-byte word columns (compared as two 64-bit words; the value columns follow the key's)
+constexpr int rx_sum_class(int cls, int a) { return (cls >> (2 * a)) & 3; }
+constexpr int rx_sum_col(int cls, int a) {  // carried columns are numbered in aggregate order (hs_group_radix_run)
+    int c = 0;
+    for (int k = 0; k < a; ++k) c += rx_sum_class(cls, k) < 2 ? 1 : 0;
+    return c;
+}
+template <int NA, int CLS, int KM>
+struct RxFoldSum {
+    static constexpr bool WIDE = KM >= 2, KEY4 = KM == 0 || WIDE;
+    static constexpr int KW = WIDE ? KM : 1, NC = rx_sum_col(CLS, NA);
+    using KeyReg = std::conditional_t<KEY4, uint32_t, uint64_t>;  // as loaded: widening a key right after its load would wait for it
+    struct Chunk {
+        KeyReg k[RX_CHUNK];
+        uint32_t w[RX_CHUNK][KW];  // WIDE: key words 1 .. KW - 1 ([0] unused)
+        uint32_t x[RX_CHUNK][NC > 0 ? NC : 1];
+    };
+    const RxAgg& A;
+    RxNoStamps stamps;
+    __device__ __forceinline__ int n_acc() const { return NA; }
+    __device__ __forceinline__ int slot_bits(int cap) const {
+        int bits = 0;
+        while ((1 << bits) < cap) ++bits;
+        return bits;
+    }
+    __device__ __forceinline__ bool is_int(int a) const { return rx_sum_class(CLS, a) != 0; }
+    __device__ __forceinline__ uint64_t identity(int) const { return 0; }  // of SUM, f64 and i64 alike
+    __device__ __forceinline__ void check(int, uint64_t, uint32_t&) const {}
+    __device__ __forceinline__ void load(Chunk& n, int64_t base, int64_t e, int lane) const {
+#pragma unroll
+        for (int j = 0; j < RX_CHUNK; ++j) {
+            const int64_t i = base + j * HS_WAVE + lane;
+            const bool valid = i < e;
+            n.k[j] = valid ? ((const KeyReg*)A.src[0])[i] : 0;
+            n.w[j][0] = n.x[j][0] = 0u;
+#pragma unroll
+            for (int q = 1; q < KW; ++q) n.w[j][q] = valid ? ((const uint32_t*)A.src[q])[i] : 0u;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) n.x[j][c] = valid ? ((const uint32_t*)A.src[KW + c])[i] : 0u;
+        }
+    }
+    __device__ __forceinline__ void find(const RxWave& T, const Chunk& ch, int j, int& slot, bool& inserted) const {
+        uint64_t k, k1 = 0;
+        if constexpr (WIDE) {
+            k = (uint64_t)ch.k[j] | ((uint64_t)ch.w[j][1] << 32);
+            if constexpr (KW > 2) k1 = (uint64_t)ch.w[j][2];
+            if constexpr (KW > 3) k1 |= (uint64_t)ch.w[j][3] << 32;
+        } else {
+            k = KEY4 ? (uint64_t)(int64_t)(int32_t)ch.k[j] : (uint64_t)ch.k[j];
+        }
+        uint32_t h;
+        if constexpr (KEY4 && !WIDE) {  // two 32-bit multiplies; bits independent of the ones the partitions were cut on
+            uint32_t m = (uint32_t)k * 0xCC9E2D51u;
+            m ^= m >> 17;
+            h = ((m * 0x1B873593u) >> 12) & T.mask;
+        } else if constexpr (WIDE) {
+            h = (uint32_t)(hs_mix64(k ^ hs_mix64(k1)) >> 36) & T.mask;
+        } else {
+            h = (uint32_t)(hs_mix64(k) >> 36) & T.mask;
+        }
+        // no break: the loop ends on slot >= 0, so its body stays one block of selects (with a break in it the compiler
+        // keeps a branch per probe round, which costs the many-keys shapes 3-4 % of the tier)
+        for (uint32_t probe = 0; probe <= T.mask && slot < 0; ++probe) {
+            const uint64_t cur = atomicCAS((unsigned long long*)&T.keys[h], (unsigned long long)HS_EMPTY_KEY, (unsigned long long)k);
+            bool mine = cur == HS_EMPTY_KEY || cur == k;
+            if constexpr (WIDE) {
+                // the lane that claimed the slot completes it before any lane of the wave - this probe round or a
+                // later one - compares the second word (LDS executes the wave's instructions in order)
+                if (cur == HS_EMPTY_KEY) T.keys1[h] = k1;
+                rx_wave_handover();
+                mine = cur == HS_EMPTY_KEY || (cur == k && T.keys1[h] == k1);
+            }
+            inserted = mine && cur == HS_EMPTY_KEY;
+            slot = mine ? (int)h : -1;
+            h = (h + 1) & T.mask;
+        }
+    }
+    __device__ __forceinline__ void fold(const RxWave& T, const Chunk& ch, int j, int64_t, bool valid, int slot, uint64_t peers) const {
+        constexpr bool any_float = (NA > 0 && rx_sum_class(CLS, 0) == 0) || (NA > 1 && rx_sum_class(CLS, 1) == 0) ||
+                                   (NA > 2 && rx_sum_class(CLS, 2) == 0);
+        const int rank = valid ? __popcll(peers & T.below) : -1;
+        // the group's cell of aggregate a is mine[a * cap]: ONE per-lane address and uniform offsets (written as
+        // acc[a * cap + slot] the compiler keeps a per-lane base per aggregate alive through the whole walk: +4 VGPRs)
+        uint64_t* mine = T.acc + slot;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {  // integer cells: any order
+            if (rx_sum_class(CLS, a) == 1) {
+                if (valid) atomicAdd((unsigned long long*)&mine[a * T.cap], (unsigned long long)(int64_t)(int32_t)ch.x[j][rx_sum_col(CLS, a)]);
+            } else if (rx_sum_class(CLS, a) == 2) {
+                if (rank == 0) atomicAdd((unsigned long long*)&mine[a * T.cap], A.const_cell[a] * (uint64_t)__popcll(peers));
+            }
+        }
+        if constexpr (any_float) {
+            for (int r = 0; __ballot(rank == r) != 0ull; ++r) {
+                if (rank == r) {
+#pragma unroll
+                    for (int a = 0; a < NA; ++a) {
+                        if (rx_sum_class(CLS, a) != 0) continue;
+                        uint64_t* cell = &mine[a * T.cap];
+                        *cell = hs_d2u(hs_u2d(*cell) + (double)__uint_as_float(ch.x[j][rx_sum_col(CLS, a)]));
+                    }
+                }
+                rx_wave_handover();
+            }
+        }
+    }
+};
 template <int NA, int CLS, int KM>
 __global__ void __launch_bounds__(256) k_rx_fold_sum(const RxAgg A_kernarg) {
-    constexpr bool WIDE = KM >= 2, KEY4 = KM == 0 || WIDE;
-    constexpr int KW = WIDE ? KM : 1;
     HS_KERNARG(RxAgg, A);
     extern __shared__ __align__(16) uint64_t rx_lds[];
-    const int lane = threadIdx.x & (HS_WAVE - 1), w = threadIdx.x / HS_WAVE, wpb = blockDim.x / HS_WAVE;
-    const int cap = A.cap;
-    const size_t per_wave = (size_t)cap * (1 + (WIDE ? 1 : 0) + NA) + (size_t)cap / 4;  // the host sizes LDS by the same rule
-    uint64_t* keys = rx_lds + (size_t)w * per_wave;
-    uint64_t* keys1 = keys + cap;  // WIDE: the second key word of every slot
-    uint64_t* acc = keys + (WIDE ? 2 : 1) * cap;
-    uint16_t* order = (uint16_t*)(acc + (size_t)NA * cap);
-    const uint32_t mask = (uint32_t)cap - 1u;
-    const int limit = A.last ? cap : cap - cap / 4;
-    const uint64_t below = (1ull << lane) - 1ull;
-    constexpr auto cls = [](int a) { return (CLS >> (2 * a)) & 3; };
-    constexpr int NC = (NA > 0 && cls(0) < 2 ? 1 : 0) + (NA > 1 && cls(1) < 2 ? 1 : 0) + (NA > 2 && cls(2) < 2 ? 1 : 0);
-    constexpr int NCR = NC > 0 ? NC : 1;
-    constexpr auto col_of = [](int a) {  // carried columns are numbered in aggregate order (hs_group_radix_run)
-        int c = 0;
-        for (int k = 0; k < a; ++k) c += ((CLS >> (2 * k)) & 3) < 2 ? 1 : 0;
-        return c;
-    };
-    constexpr bool any_float = (NA > 0 && cls(0) == 0) || (NA > 1 && cls(1) == 0) || (NA > 2 && cls(2) == 0);
-    int slot_bits = 0;
-    while ((1 << slot_bits) < cap) ++slot_bits;
-    uint32_t err = 0;
-    const int64_t n_todo = A.list ? *A.list_count : A.n_parts;
-    if ((int64_t)blockIdx.x * wpb + w >= n_todo) return;  // nothing listed for this wave: no table to clear either
-    for (int s = lane; s < cap; s += HS_WAVE) keys[s] = HS_EMPTY_KEY;
-    for (int s = lane; s < NA * cap; s += HS_WAVE) acc[s] = 0;  // the identity of SUM, f64 and i64 alike
-    for (int64_t q = (int64_t)blockIdx.x * wpb + w; q < n_todo; q += (int64_t)gridDim.x * wpb) {
-        const int64_t p = A.list ? A.list[q] : q;
-        const int64_t b = A.seg_start[p], e = A.seg_start[p + 1];
-        if (b >= e) {
-            if (lane == 0) A.pcount[p] = 0;
-            continue;
-        }
-        using KeyReg = std::conditional_t<KEY4, uint32_t, uint64_t>;  // as loaded: widening a key right after its load would wait for it
-        KeyReg nk[RX_CHUNK];
-        uint32_t nw[RX_CHUNK][KW];  // WIDE: key words 1 .. KW - 1 ([0] unused)
-        uint32_t nx[RX_CHUNK][NCR];
-        auto load_chunk = [&](int64_t base) {
-#pragma unroll
-            for (int j = 0; j < RX_CHUNK; ++j) {
-                const int64_t i = base + j * HS_WAVE + lane;
-                const bool valid = i < e;
-                nk[j] = valid ? ((const KeyReg*)A.src[0])[i] : 0;
-#pragma unroll
-                for (int q = 1; q < KW; ++q) nw[j][q] = valid ? ((const uint32_t*)A.src[q])[i] : 0u;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) nx[j][c] = valid ? ((const uint32_t*)A.src[KW + c])[i] : 0u;
-            }
-        };
-        load_chunk(b);
-        int ngroups = 0;
-        bool full = false;
-        for (int64_t base = b; base < e && !full; base += RX_CHUNK * HS_WAVE) {
-            KeyReg ck[RX_CHUNK];
-            uint32_t cw[RX_CHUNK][KW];
-            uint32_t cx[RX_CHUNK][NCR];
-#pragma unroll
-            for (int j = 0; j < RX_CHUNK; ++j) {
-                ck[j] = nk[j];
-#pragma unroll
-                for (int q = 1; q < KW; ++q) cw[j][q] = nw[j][q];
-#pragma unroll
-                for (int c = 0; c < NCR; ++c) cx[j][c] = NC > 0 ? nx[j][c] : 0u;
-            }
-            if (base + RX_CHUNK * HS_WAVE < e) load_chunk(base + RX_CHUNK * HS_WAVE);
-#pragma unroll
-            for (int j = 0; j < RX_CHUNK; ++j) {
-                if (base + j * HS_WAVE >= e || full) break;
-                const bool valid = base + j * HS_WAVE + lane < e;
-                int slot = valid ? -1 : 0;
-                bool inserted = false;
-                if (valid) {
-                    uint64_t k, k1 = 0;
-                    if constexpr (WIDE) {
-                        k = (uint64_t)ck[j] | ((uint64_t)cw[j][1] << 32);
-                        if constexpr (KW > 2) k1 = (uint64_t)cw[j][2];
-                        if constexpr (KW > 3) k1 |= (uint64_t)cw[j][3] << 32;
-                    } else {
-                        k = KEY4 ? (uint64_t)(int64_t)(int32_t)ck[j] : (uint64_t)ck[j];
-                    }
-                    uint32_t h;
-                    if constexpr (KEY4 && !WIDE) {  // two 32-bit multiplies; bits independent of the ones the partitions were cut on
-                        uint32_t m = (uint32_t)k * 0xCC9E2D51u;
-                        m ^= m >> 17;
-                        h = ((m * 0x1B873593u) >> 12) & mask;
-                    } else if constexpr (WIDE) {
-                        h = (uint32_t)(hs_mix64(k ^ hs_mix64(k1)) >> 36) & mask;
-                    } else {
-                        h = (uint32_t)(hs_mix64(k) >> 36) & mask;
-                    }
-                    for (uint32_t probe = 0; probe <= mask; ++probe) {
-                        const uint64_t cur = atomicCAS((unsigned long long*)&keys[h], (unsigned long long)HS_EMPTY_KEY, (unsigned long long)k);
-                        if constexpr (WIDE) {
-                            // the lane that claimed the slot completes it before any lane of the wave - this probe round or a
-                            // later one - compares the second word (LDS executes the wave's instructions in order)
-                            if (cur == HS_EMPTY_KEY) keys1[h] = k1;
-                            rx_wave_handover();
-                            if (cur == HS_EMPTY_KEY || (cur == k && keys1[h] == k1)) {
-                                inserted = cur == HS_EMPTY_KEY;
-                                slot = (int)h;
-                                break;
-                            }
-                        } else if (cur == HS_EMPTY_KEY || cur == k) {
-                            inserted = cur == HS_EMPTY_KEY;
-                            slot = (int)h;
-                            break;
-                        }
-                        h = (h + 1) & mask;
-                    }
-                }
-                const uint64_t fresh = __ballot(inserted);
-                if (inserted) order[ngroups + __popcll(fresh & below)] = (uint16_t)slot;
-                ngroups += __popcll(fresh);
-                if (ngroups > limit || __ballot(valid && slot < 0) != 0ull) {
-                    full = true;
-                    break;
-                }
-                uint64_t peers = __ballot(valid);
-                for (int bit = 0; bit < slot_bits; ++bit) {
-                    const bool on = (slot >> bit) & 1;
-                    peers &= ~(__ballot(valid && on) ^ (on ? ~0ull : 0ull));
-                }
-                const int rank = valid ? __popcll(peers & below) : -1;
-#pragma unroll
-                for (int a = 0; a < NA; ++a) {  // integer cells: any order
-                    if (cls(a) == 1) {
-                        if (valid) atomicAdd((unsigned long long*)&acc[a * cap + slot], (unsigned long long)(int64_t)(int32_t)cx[j][col_of(a)]);
-                    } else if (cls(a) == 2) {
-                        if (rank == 0) atomicAdd((unsigned long long*)&acc[a * cap + slot], A.const_cell[a] * (uint64_t)__popcll(peers));
-                    }
-                }
-                if constexpr (any_float) {
-                    for (int r = 0; __ballot(rank == r) != 0ull; ++r) {
-                        if (rank == r) {
-#pragma unroll
-                            for (int a = 0; a < NA; ++a) {
-                                if (cls(a) != 0) continue;
-                                uint64_t* cell = &acc[a * cap + slot];
-                                *cell = hs_d2u(hs_u2d(*cell) + (double)__uint_as_float(cx[j][col_of(a)]));
-                            }
-                        }
-                        rx_wave_handover();
-                    }
-                }
-            }
-        }
-        if (full) {
-            if (A.last) err |= HS_FLAG_DICT_FULL;
-            else if (lane == 0) A.overflow[atomicAdd((unsigned long long*)A.overflow_count, 1ull)] = p;
-            if (lane == 0) A.pcount[p] = 0;
-        }
-        for (int g0 = 0; g0 < ngroups; g0 += HS_WAVE) {
-            const int g = g0 + lane;
-            if (g >= ngroups) continue;
-            const int s = order[g];
-            const int64_t at = b + g;
-            if (!full) A.prov_key[at] = keys[s];
-            if (WIDE && !full) A.prov_key1[at] = keys1[s];
-            keys[s] = HS_EMPTY_KEY;
-#pragma unroll
-            for (int a = 0; a < NA; ++a) {
-                const bool is_int = cls(a) != 0;
-                uint64_t v = acc[a * cap + s];
-                acc[a * cap + s] = 0;
-                if (full) continue;
-                if (A.quantise) {
-                    v = hs_quantise_cell(is_int, v, err);
-                    if (is_int) ((int32_t*)A.prov_acc[a])[at] = (int32_t)(int64_t)v;
-                    else ((float*)A.prov_acc[a])[at] = (float)hs_u2d(v);
-                } else {
-                    ((uint64_t*)A.prov_acc[a])[at] = v;
-                }
-            }
-        }
-        if (!full && lane == 0) A.pcount[p] = ngroups;
-    }
-    if (err) atomicOr(A.flags, err);
+    rx_fold_walk(A, rx_lds, RxFoldSum<NA, CLS, KM>{A, {}});
 }
 
 // ---- dense output -----------------------------------------------------------------------------------------------
@@ -1135,6 +1121,36 @@ static constexpr RxKernel RX_SCATTER4[4][2] = {{k_rx_scatter4<0, false>, k_rx_sc
                                                {k_rx_scatter4<1, false>, k_rx_scatter4<1, true>},
                                                {k_rx_scatter4<2, false>, k_rx_scatter4<2, true>},
                                                {k_rx_scatter4<3, false>, k_rx_scatter4<3, true>}};
+// ... and of the folds.  The general one by [carried columns 0 .. 4, 5: any number][cap <= 512 ? 0 : 1]:
+using RxFoldKernel = void (*)(const RxAgg);
+static constexpr RxFoldKernel RX_FOLD[6][2] = {{k_rx_fold<0, 9>, k_rx_fold<0, 12>}, {k_rx_fold<1, 9>, k_rx_fold<1, 12>},
+                                               {k_rx_fold<2, 9>, k_rx_fold<2, 12>}, {k_rx_fold<3, 9>, k_rx_fold<3, 12>},
+                                               {k_rx_fold<4, 9>, k_rx_fold<4, 12>}, {k_rx_fold<-1, 9>, k_rx_fold<-1, 12>}};
+// the SUM fold by [n_acc - 1][class code: two bits per aggregate, 0 .. 2 each][key mode 0 .. 4]: 3 + 9 + 27 class codes
+// x 5 key modes are kernels, every other cell (a class 3, a class beyond n_acc) is null
+constexpr int RX_SUM_CODES = 64, RX_SUM_KM = 5;
+constexpr bool rx_sum_code_ok(int n_acc, int code) {
+    for (int a = 0; a < 3; ++a)
+        if (a < n_acc ? rx_sum_class(code, a) > 2 : rx_sum_class(code, a) != 0) return false;
+    return true;
+}
+template <int NA, int CLS, int KM>
+constexpr RxFoldKernel rx_sum_kernel() {
+    if constexpr (rx_sum_code_ok(NA, CLS)) return k_rx_fold_sum<NA, CLS, KM>;
+    else return nullptr;
+}
+struct RxSumTable {
+    RxFoldKernel k[3][RX_SUM_CODES][RX_SUM_KM];
+};
+template <size_t... I>
+constexpr RxSumTable rx_sum_table(std::index_sequence<I...>) {
+    RxSumTable t{};
+    ((t.k[I / (RX_SUM_CODES * RX_SUM_KM)][I / RX_SUM_KM % RX_SUM_CODES][I % RX_SUM_KM] =
+          rx_sum_kernel<(int)(I / (RX_SUM_CODES * RX_SUM_KM)) + 1, (int)(I / RX_SUM_KM % RX_SUM_CODES), (int)(I % RX_SUM_KM)>()),
+     ...);
+    return t;
+}
+static constexpr RxSumTable RX_FOLD_SUM = rx_sum_table(std::make_index_sequence<3 * RX_SUM_CODES * RX_SUM_KM>{});
 
 // one partition pass over the segments of `pass`: tiles, histogram, scan, scatter, the next level's segments
 static int rx_pass(hipStream_t stream, const RxPass& pass, int64_t max_tiles, int64_t* counters, int64_t* scanned, void* scan_ws,
@@ -1215,7 +1231,7 @@ extern "C" int hs_group_radix_plan(int32_t key_kind, int64_t n, int32_t n_units,
     for (int i = 0; i < 48; ++i) f[i] = 0;
     const int NA = spec->n_acc;
     int cap = 2048;
-    while (cap > 64 && ((size_t)cap * (1 + (wide ? 1 : 0) + NA) + (size_t)cap / 4) * 8 > 65536) cap >>= 1;
+    while (cap > 64 && rx_fold_words(cap, NA, wide != 0) * 8 > 65536) cap >>= 1;
     // rows per partition: half the slots of the LARGE table.  Partitions that turn out to hold few distinct keys - the
     // usual case - are folded by the 512-slot launch anyway.  (Cutting down to half the slots of the SMALL table where two
     // passes can was measured at 600 M rows / 287 units: all-distinct keys 2.2x faster - no partition needs the large-table
@@ -1414,80 +1430,26 @@ extern "C" int hs_group_radix_run(void* stream_, const hs_radix_plan* plan, cons
         hs_set_error("hs_group_radix_run: a wide STRING key needs the SUM-specialised fold");
         return HS_E_LIMIT;
     }
+    const int km = wide ? kcols : (G.esize[0] == 4 ? 0 : 1), nc = (int)f[PL_NCARRIED];
     // todo: the partitions this launch works on (NULL: all), left: where it notes the ones that outgrow its tables
-    auto fold = [&](int cap, int64_t* todo, int64_t* left) {
+    auto fold = [&](int cap, int64_t* todo, int64_t* left) -> int {
         G.cap = cap;
         G.last = cap == (int)f[PL_CAP] ? 1 : 0;
         G.list = todo ? todo + 1 : nullptr;
         G.list_count = todo;
         G.overflow = left + 1;
         G.overflow_count = left;
-        const size_t per_wave = ((size_t)cap * ((wide ? 2 : 1) + NA) + (size_t)cap / 4) * 8;
+        const size_t per_wave = rx_fold_words(cap, NA, wide != 0) * 8;
         int wpb = (int)(65536 / per_wave);
         wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
         int64_t grid = (parts + wpb - 1) / wpb;
         if (grid > 256 * 32) grid = 256 * 32;
-        const dim3 g((unsigned)grid), t(HS_WAVE * wpb);
-#define RX_FOLD(NC)                                                                                    \
-    if (cap <= 512) hipLaunchKernelGGL((k_rx_fold<NC, 9>), g, t, per_wave * wpb, stream, G);           \
-    else hipLaunchKernelGGL((k_rx_fold<NC, 12>), g, t, per_wave * wpb, stream, G)
-#define RX_SUM1(C0) \
-    case (C0):                                                                                              \
-        switch (km) { \
-            case 0: hipLaunchKernelGGL((k_rx_fold_sum<1, (C0), 0>), g, t, per_wave * wpb, stream, G); break; \
-            case 1: hipLaunchKernelGGL((k_rx_fold_sum<1, (C0), 1>), g, t, per_wave * wpb, stream, G); break; \
-            case 2: hipLaunchKernelGGL((k_rx_fold_sum<1, (C0), 2>), g, t, per_wave * wpb, stream, G); break; \
-            case 3: hipLaunchKernelGGL((k_rx_fold_sum<1, (C0), 3>), g, t, per_wave * wpb, stream, G); break; \
-            case 4: hipLaunchKernelGGL((k_rx_fold_sum<1, (C0), 4>), g, t, per_wave * wpb, stream, G); break; \
-        } \
-        return;
-#define RX_SUM2(C0, C1) \
-    case ((C0) | ((C1) << 2)):                                                                                             \
-        switch (km) { \
-            case 0: hipLaunchKernelGGL((k_rx_fold_sum<2, ((C0) | ((C1) << 2)), 0>), g, t, per_wave * wpb, stream, G); break; \
-            case 1: hipLaunchKernelGGL((k_rx_fold_sum<2, ((C0) | ((C1) << 2)), 1>), g, t, per_wave * wpb, stream, G); break; \
-            case 2: hipLaunchKernelGGL((k_rx_fold_sum<2, ((C0) | ((C1) << 2)), 2>), g, t, per_wave * wpb, stream, G); break; \
-            case 3: hipLaunchKernelGGL((k_rx_fold_sum<2, ((C0) | ((C1) << 2)), 3>), g, t, per_wave * wpb, stream, G); break; \
-            case 4: hipLaunchKernelGGL((k_rx_fold_sum<2, ((C0) | ((C1) << 2)), 4>), g, t, per_wave * wpb, stream, G); break; \
-        } \
-        return;
-#define RX_SUM3(C0, C1, C2) \
-    case ((C0) | ((C1) << 2) | ((C2) << 4)): \
-        switch (km) { \
-            case 0: hipLaunchKernelGGL((k_rx_fold_sum<3, ((C0) | ((C1) << 2) | ((C2) << 4)), 0>), g, t, per_wave * wpb, stream, G); break; \
-            case 1: hipLaunchKernelGGL((k_rx_fold_sum<3, ((C0) | ((C1) << 2) | ((C2) << 4)), 1>), g, t, per_wave * wpb, stream, G); break; \
-            case 2: hipLaunchKernelGGL((k_rx_fold_sum<3, ((C0) | ((C1) << 2) | ((C2) << 4)), 2>), g, t, per_wave * wpb, stream, G); break; \
-            case 3: hipLaunchKernelGGL((k_rx_fold_sum<3, ((C0) | ((C1) << 2) | ((C2) << 4)), 3>), g, t, per_wave * wpb, stream, G); break; \
-            case 4: hipLaunchKernelGGL((k_rx_fold_sum<3, ((C0) | ((C1) << 2) | ((C2) << 4)), 4>), g, t, per_wave * wpb, stream, G); break; \
-        } \
-        return;
-#define RX_SUM3_LAST(C0, C1) RX_SUM3(C0, C1, 0) RX_SUM3(C0, C1, 1) RX_SUM3(C0, C1, 2)
-#define RX_SUM3_MID(C0) RX_SUM3_LAST(C0, 0) RX_SUM3_LAST(C0, 1) RX_SUM3_LAST(C0, 2)
-        const int km = wide ? kcols : (G.esize[0] == 4 ? 0 : 1);
-        if (sum_cls >= 0 && NA == 1) {
-            switch (sum_cls) { RX_SUM1(0) RX_SUM1(1) RX_SUM1(2) default: break; }
-        } else if (sum_cls >= 0 && NA == 2) {
-            switch (sum_cls) {
-                RX_SUM2(0, 0) RX_SUM2(1, 0) RX_SUM2(2, 0) RX_SUM2(0, 1) RX_SUM2(1, 1) RX_SUM2(2, 1) RX_SUM2(0, 2) RX_SUM2(1, 2) RX_SUM2(2, 2)
-                default: break;
-            }
-        } else if (sum_cls >= 0 && NA == 3) {
-            switch (sum_cls) { RX_SUM3_MID(0) RX_SUM3_MID(1) RX_SUM3_MID(2) default: break; }
-        }
-#undef RX_SUM1
-#undef RX_SUM2
-#undef RX_SUM3
-#undef RX_SUM3_LAST
-#undef RX_SUM3_MID
-        switch ((int)f[PL_NCARRIED]) {
-            case 0: RX_FOLD(0); break;
-            case 1: RX_FOLD(1); break;
-            case 2: RX_FOLD(2); break;
-            case 3: RX_FOLD(3); break;
-            case 4: RX_FOLD(4); break;
-            default: RX_FOLD(-1); break;
-        }
-#undef RX_FOLD
+        RxFoldKernel kernel = nullptr;
+        if (sum_cls >= 0 && sum_cls < RX_SUM_CODES && NA >= 1 && NA <= 3 && km >= 0 && km < RX_SUM_KM) kernel = RX_FOLD_SUM.k[NA - 1][sum_cls][km];
+        if (!kernel) kernel = RX_FOLD[nc >= 0 && nc <= 4 ? nc : 5][cap <= 512 ? 0 : 1];
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(HS_WAVE * wpb), per_wave * wpb, stream, G);
+        RX_CHECK_LAUNCH("hs_group_radix_run (fold)");
+        return HS_OK;
     };
     // Three table sizes, smallest first: a partition is cut to hold ~half the LARGE table's slots in ROWS, and usually holds far
     // fewer distinct keys.  The fold is a chain of LDS round trips per 64-row step, one wave per partition - what it needs is
@@ -1495,21 +1457,16 @@ extern "C" int hs_group_radix_run(void* stream_, const hs_radix_plan* plan, cons
     // size's list (round 4; 64 Mi rows / 4 Mi groups: fold 0.52 -> see profiles/r04_radix_tier_64M.txt).
     const int big = (int)f[PL_CAP], small = big > 512 ? 512 : big, tiny = small > 256 ? 256 : small;
     if (tiny < small) {
-        fold(tiny, nullptr, overflow);
-        RX_CHECK_LAUNCH("hs_group_radix_run (fold)");
-        fold(small, overflow, overflow2);
-        if (small < big) {
-            RX_CHECK_LAUNCH("hs_group_radix_run (fold)");
-            fold(big, overflow2, overflow2);
-        }
+        rc = fold(tiny, nullptr, overflow);
+        if (rc == HS_OK) rc = fold(small, overflow, overflow2);
+        if (rc == HS_OK && small < big) rc = fold(big, overflow2, overflow2);
     } else if (small < big) {
-        fold(small, nullptr, overflow);
-        RX_CHECK_LAUNCH("hs_group_radix_run (fold)");
-        fold(big, overflow, overflow);
+        rc = fold(small, nullptr, overflow);
+        if (rc == HS_OK) rc = fold(big, overflow, overflow);
     } else {
-        fold(big, nullptr, overflow);  // nothing can overflow into a list: a full table raises HS_FLAG_DICT_FULL ...
+        rc = fold(big, nullptr, overflow);  // nothing can overflow into a list: a full table raises HS_FLAG_DICT_FULL ...
     }
-    RX_CHECK_LAUNCH("hs_group_radix_run (fold)");
+    if (rc != HS_OK) return rc;
     int64_t* pscan = (int64_t*)(ws + f[PL_OFF_PSCAN]);
     rc = hs_exclusive_scan_i64(stream, G.pcount, parts, pscan, scan_ws);
     if (rc != HS_OK) return rc;
@@ -3656,12 +3613,7 @@ __device__ __forceinline__ void jx_place(uint32_t* cur, uint32_t* head, uint8_t*
             rx_wave_handover();
             continue;
         }
-        uint64_t peers = __ballot(valid);
-        for (int bit = 0; bit < L; ++bit) {
-            const bool on = (s >> bit) & 1u;
-            const uint64_t bal = __ballot(valid && on);
-            peers &= on ? bal : ~bal;
-        }
+        const uint64_t peers = rx_peers(s, valid, L);
         const uint32_t rank = (uint32_t)__popcll(peers & below);
         rx_wave_handover();  // every lane has read its slot's cursor before a leader moves it
         if (valid) {

@@ -45,14 +45,20 @@ def _expected(keys, vals, ops, is_int, bounds, quantise):
     return out
 
 
-def _run(dev, keys, key_kind, sel, bounds, values, ops, quantise):
+def _run(dev, keys, key_kind, sel, bounds, values, ops, quantise, digits=0):
+    """digits: GROUP BY the (non-negative) keys' zero-padded decimal digits, a STRING column of that fixed length"""
     import torch
 
     from minispark_amd import hipspark as hs
     from minispark_amd.device import DCol
 
-    tk = torch.from_numpy(keys).cuda()
-    key = DCol(key_kind, tk, len(keys))
+    place = 10 ** np.arange(digits - 1, -1, -1, dtype=np.int64)
+    if digits:
+        text = (keys.astype(np.int64)[:, None] // place % 10 + 48).astype(np.uint8)
+        key = DCol(hs.STR, torch.from_numpy(text.reshape(-1)).cuda(), len(keys),
+                   lens=torch.full((len(keys),), digits, dtype=torch.uint8, device="cuda"), offs=None, fixed_len=digits)
+    else:
+        key = DCol(key_kind, torch.from_numpy(keys).cuda(), len(keys))
     tsel = torch.from_numpy(sel).cuda() if sel is not None else None
     n = len(sel) if sel is not None else len(keys)
     vals = []
@@ -70,7 +76,10 @@ def _run(dev, keys, key_kind, sel, bounds, values, ops, quantise):
     key_col, accs, unit_rows = done
     torch.cuda.synchronize()
     assert dev.read_flags() == 0
-    k = key_col.data[: key_col.n].cpu().numpy().astype(np.int64)
+    if digits:
+        k = ((key_col.data[: key_col.n * digits].cpu().numpy().reshape(-1, digits).astype(np.int64) - 48) * place).sum(axis=1)
+    else:
+        k = key_col.data[: key_col.n].cpu().numpy().astype(np.int64)
     a = [c.data[: c.n].cpu().numpy() for c in accs]
     got = []
     for lo, hi in zip(unit_rows, unit_rows[1:]):
@@ -146,6 +155,58 @@ def test_radix_sum_fold_in_every_class_combination(dev, classes, n, units, group
     for quantise in (True, False):
         got = _run(dev, keys, hs.I32, None, bounds, values, ops, quantise)
         _same(got, _expected(keys, values, ops, is_int, bounds, quantise))
+
+
+_LADDER = {  # fold, key and aggregates -> (classes: f32 / f64 / i32 column or constant, operators or None = all SUM, STRING digits)
+    "sum-f": ("f", None, 0), "sum-ic": ("ic", None, 0), "sum-fif": ("fif", None, 0), "sum-f-str12": ("f", None, 12),
+    "general-3": ("ffi", ("SUM", "MIN", "MAX"), 0),
+    "general-6-any-columns": ("fdifci", ("SUM", "SUM", "SUM", "MIN", "SUM", "MAX"), 0),  # five carried columns: no register tuple
+}
+
+
+@pytest.mark.parametrize("quantise", [True, False])
+@pytest.mark.parametrize("passes", [0, 1])
+@pytest.mark.parametrize("combo", list(_LADDER))
+def test_radix_fold_walks_every_table_size_in_both_kernels(dev, combo, passes, quantise):
+    """The fold takes a partition with the 256-slot table, moves it to the 512-slot table past 192 groups and to the plan's
+    large table (cap) past 384: three units whose partitions end on the first, the second and the third rung, in the SUM
+    fold (classes f, ic, fif; a 12-byte STRING key) and the general fold (three aggregates; six over five carried columns),
+    at the smallest shapes that have the rungs.  A partition holds at most cap / 2 rows: without a pass (passes = 0) a unit
+    of exactly cap / 2 rows is one partition - 100 distinct keys, 300, every row its own; with one pass a unit of
+    4 x cap / 2 rows is cut into four on hash bits - 400, 1200 distinct keys, every row its own.  Which table finished a
+    partition cannot be seen from here: the answers are pinned, bit for bit, on the shapes that reach each rung."""
+    import ctypes as C
+
+    from minispark_amd import hipspark as hs
+
+    classes, op_names, digits = _LADDER[combo]
+    ops = [getattr(hs, "AGG_" + o) for o in (op_names or ["SUM"] * len(classes))]
+    cap = 2048 if len(classes) <= 2 else 1024  # what the plan makes of 64 KB of LDS per wave
+    rows = cap // 2 << (2 * passes)
+    n, bounds = 3 * rows, [0, rows, 2 * rows, 3 * rows]
+    plan, spec = hs.hs_radix_plan(), hs.hs_agg_spec()
+    spec.n_acc = len(classes)
+    kinds = (C.c_int32 * len(classes))(*[{"f": hs.F32, "d": hs.F64, "i": hs.I32, "c": -1}[c] for c in classes])
+    for a, c in enumerate(classes):
+        spec.op[a], spec.is_int[a] = ops[a], int(c in "ic")
+    key_code = hs.STR + 256 * digits if digits else hs.I32
+    assert dev.lib.hs_group_radix_plan(key_code, n, 3, rows, kinds, C.byref(spec), int(quantise), C.byref(plan)) == 0
+    assert plan.f[4] == cap, f"the plan's large table has {plan.f[4]} slots, not {cap}: resize this test's units"
+    assert (plan.f[2], plan.f[3]) == (2 * passes, 0), "the units are no longer cut into 1 / 4 partitions"
+    assert dev.lib.hs_group_radix_plan(key_code, n + 1, 3, rows + 1, kinds, C.byref(spec), int(quantise), C.byref(plan)) == 0
+    assert plan.f[2] + plan.f[3] == 2 * passes + 1, "a larger unit is cut no finer: this one is not the largest of its cut"
+
+    rng = np.random.default_rng(rows + len(combo))
+    keys = np.empty(n, np.int32)
+    for u, distinct in enumerate((100 << (2 * passes), 300 << (2 * passes), rows)):
+        pool = rng.choice(1 << 30, distinct, replace=False).astype(np.int32) - (0 if digits else 1 << 29)
+        keys[u * rows: (u + 1) * rows] = rng.permutation(np.concatenate([pool, pool[rng.integers(0, distinct, rows - distinct)]]))
+        assert len(np.unique(keys[u * rows: (u + 1) * rows])) == distinct
+    make = {"f": lambda: (rng.normal(0, 1, n) * np.exp2(rng.integers(-8, 8, n))).astype(np.float32), "d": lambda: rng.normal(0, 1e3, n),
+            "i": lambda: rng.integers(-100_000, 100_000, n).astype(np.int32), "c": lambda: 3}
+    values = [make[c]() for c in classes]
+    got = _run(dev, keys, hs.I32, None, bounds, values, ops, quantise, digits=digits)
+    _same(got, _expected(keys, values, ops, [c in "ic" for c in classes], bounds, quantise))
 
 
 def test_radix_tier_takes_float_and_short_string_keys(dev):

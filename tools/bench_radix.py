@@ -1,5 +1,7 @@
 """Radix tier of GROUP BY alone (hs_group_radix_*): python tools/bench_radix.py [rows] [groups] [units] [reps]
-One SUM(f32) over `groups` random int32 keys - the A5 line of tools/bench_ops.py without the rest, for rocprofv3."""
+One SUM(f32) over `groups` random int32 keys - the A5 line of tools/bench_ops.py without the rest, for rocprofv3.
+RADIX_BENCH_COUNT=1 adds COUNT, RADIX_BENCH_STR=<length> groups by a STRING key (both stay in the SUM fold),
+RADIX_BENCH_GENERAL=1 adds MAX(f32), which takes the general fold."""
 import os, sys, time
 from pathlib import Path
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", str(Path(__file__).resolve().parent.parent)))
@@ -29,8 +31,9 @@ vals = DCol(hs.F32, torch.rand(N, dtype=torch.float32, device="cuda", generator=
 bounds = torch.tensor([N * u // U for u in range(U + 1)], dtype=torch.int64, device="cuda")
 biggest = max(N * (u + 1) // U - N * u // U for u in range(U))
 COUNT = os.environ.get("RADIX_BENCH_COUNT") == "1"  # a second aggregate: COUNT (a constant 1 that does not travel)
-VALUES = [(vals, 0, False)] + ([(None, 1, True)] if COUNT else [])
-OPS = [hs.AGG_SUM] * len(VALUES)
+GENERAL = os.environ.get("RADIX_BENCH_GENERAL") == "1"  # a last aggregate MAX(f32): no SUM, so the general fold (k_rx_fold) runs
+VALUES = [(vals, 0, False)] + ([(None, 1, True)] if COUNT else []) + ([(vals, 0, False)] if GENERAL else [])
+OPS = [hs.AGG_SUM] * (len(VALUES) - GENERAL) + [hs.AGG_MAX] * GENERAL
 for r in range(reps):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize(); t0 = time.perf_counter()
