@@ -126,13 +126,12 @@ def test_jit_translates_and_compiles_q1_for_gfx950():
     assert "cell[1280] = a5;" in text and "const unsigned long long k" in text  # 256-lane workgroup; hoisted literals
 
 
-def test_expression_programs_translate_and_compile_for_gfx950_without_a_gpu():
-    """hs_eval's compiled form: bytecode -> four-rows-per-lane kernel source -> hiprtc for gfx950."""
+def eval_program():
+    """-> (program, kinds of the schema's columns, out kinds): four expressions of hs_eval (also in tools/jit_source.py's corpus)."""
     from minispark_amd.constants import ColumnType as T
     from minispark_amd.lowering import ProgramBuilder
     from minispark_amd.sql import Col, Lit
 
-    lib = hs.load_library()
     schema = [("a", T.FLOAT), ("b", T.FLOAT), ("i", T.INTEGER), ("t", T.TIMESTAMP), ("s", T.STRING)]
     kinds = [hs.F32, hs.F32, hs.I32, hs.I64, hs.STR]
     b = ProgramBuilder(schema, kinds)
@@ -140,11 +139,16 @@ def test_expression_programs_translate_and_compile_for_gfx950_without_a_gpu():
              Col("s").like("%AIR%") | (Col("s") == "MAIL")]
     tags = [b.emit_out(o, e) for o, e in enumerate(exprs)]
     assert tags == ["F", "I", "B", "B"]
-    prog = b.finish()
+    return b.finish(), kinds, (C.c_int32 * 4)(hs.F64, hs.I64, hs.U8, hs.U8)
+
+
+def test_expression_programs_translate_and_compile_for_gfx950_without_a_gpu():
+    """hs_eval's compiled form: bytecode -> four-rows-per-lane kernel source -> hiprtc for gfx950."""
+    lib = hs.load_library()
+    prog, kinds, out_kinds = eval_program()
     cols = (hs.hs_col * len(prog.columns))()
     for slot, idx in enumerate(prog.columns):
         cols[slot].kind, cols[slot].fixed_len = kinds[idx], -1
-    out_kinds = (C.c_int32 * 4)(hs.F64, hs.I64, hs.U8, hs.U8)
     pstruct = prog.to_struct()
     size = C.c_int64(0)
     src = C.create_string_buffer(1 << 16)
