@@ -179,7 +179,8 @@ const char* hs_last_error(void);
 int hs_version(void);
 /* sizeof() of ABI structure `which` as compiled: 0 hs_col, 1 hs_program, 2 hs_agg_spec, 3 hs_agg_geom, 4 hs_chunk,
  * 5 hs_slab_desc, 6 hs_finish_out, 7 hs_finish_spec, 8 hs_stage_plan, 9 hs_result_col, 10 hs_join8, 11 hs_join_stage_plan, 12 hs_select_stage_plan,
- * 14 hs_join_select_stage_plan, 15 hs_join_group_stage_plan (13 stays unassigned: it returns 0, the end of the round-4 list)
+ * 14 hs_join_select_stage_plan, 15 hs_join_group_stage_plan, 16 hs_join_table (13 stays unassigned: it returns 0, the end of the
+ * round-4 list)
  * (0 for anything else) - lets a
  * binding verify its mirror. */
 size_t hs_sizeof(int32_t which);
@@ -593,6 +594,55 @@ int hs_join_hash_str_build(void* stream, const hs_col* build_key, int64_t n_buil
                            void* ws, uint32_t* status, uint32_t* flags);
 int hs_join_hash_str_count(void* stream, const hs_col* build_key, const hs_col* probe_key, int64_t n_probe, int64_t n_build,
                            const void* table, const uint32_t* rows, const uint32_t* list_count, int64_t* counts, void* aux);
+/* ---- the general inner join: one route planner and one table handle over the four forms (csrc/hs_radix.hip) ---------------
+ * The four forms of the reference's loop (tasks.py:201-240) - dense CSR, hashed windows, hashed STRING windows, the
+ * global-memory table - behind one handle, so that every caller (the join stages, Device.join_indices, Device.semi_select)
+ * runs the same "plan, allocate, build, count, did a window overflow, plan again, scan, fill" and the routing rule is written
+ * once.  hs_join_table_plan is host only: it touches no GPU and dereferences no pointer; it reads the two key columns for
+ * their kinds and the alignment of their data pointers.  `routes` is a mask of HS_JOIN_ROUTE_BIT(route) for every route the
+ * caller accepts; out->route is the FIRST of DENSE, HASH, HASH_STR, GLOBAL that is in the mask and holds the shape (0: none):
+ *   DENSE     both keys HS_I32, n_build > 0, n_probe > 0, n_build < 2^31, both data pointers 16-byte aligned, key_lo <=
+ *             key_hi (the build keys' range, e.g. from hs_minmax_i32), slots = key_hi - key_lo + 1 <= min(2^29, 32 n_build +
+ *             65 536) - at most 32 slots per build row: TPC-H order keys use 8 of every 32 values - and slots * 4 >= n_build
+ *             - at most 4 build rows per slot on average: a few hot keys would leave the assembly to single waves - and
+ *             hs_join_dense_ws_bytes(n_build, slots) != 0;
+ *   HASH      both keys HS_I32, both counts > 0, both data pointers 16-byte aligned, hs_join_hash_slots(n_build) > 0;
+ *   HASH_STR  both keys HS_STR, both counts > 0, hs_join_hash_str_slots(n_build) > 0;
+ *   GLOBAL    everything else, empty sides included; slots = table_cap, the smallest power of two >= 16 and >= 2 max(n_build, 1).
+ * The form's arrays are parts of ONE allocation of table_bytes bytes (16-byte aligned), part i at byte part[i]; every part
+ * starts 256-byte aligned and is followed by at least 64 bytes of slack:
+ *   DENSE             part 0 words[slots] (4 B), 1 rows[n_build] (4 B), 2 list_count[n_build] (4 B)
+ *   HASH / HASH_STR   part 0 table[slots] (8 B), 1 rows[n_build] (4 B), 2 list_count[n_build] (4 B)
+ *   GLOBAL            part 0 table_keys[slots] (8 B), 1 table_reps[slots] (8 B), 2 slot_start[slots + 1] (8 B),
+ *                     3 rows[max(n_build, 1)] (8 B)
+ * hs_join_table_build / count / fill dispatch to the form's own entry points above (same arguments, same launches) and do
+ * nothing else.  ws: ws_bytes bytes.  counts: n_probe int64, 16-byte aligned.  aux: hs_join_dense_aux_bytes(n_probe) bytes
+ * for every route (GLOBAL ignores it).  *status (device, zeroed by the caller) receives HS_FLAG_DICT_FULL when a window of
+ * HASH / HASH_STR overflowed: the caller plans again with routes & ~HS_JOIN_ROUTE_BIT(t->route) - that is the whole fallback
+ * ladder.  The caller scans counts (hs_exclusive_scan_i64) into out_start and sizes the pair lists before the fill. */
+#define HS_JOIN_ROUTE_DENSE 1       /* hs_join_dense_* */
+#define HS_JOIN_ROUTE_HASH 2        /* hs_join_hash_* */
+#define HS_JOIN_ROUTE_HASH_STR 3    /* hs_join_hash_str_* */
+#define HS_JOIN_ROUTE_GLOBAL 4      /* hs_join_build / count / fill */
+#define HS_JOIN_ROUTE_BIT(route) (1u << (route))
+#define HS_JOIN_ROUTES_ALL 0x1eu
+typedef struct hs_join_table {
+    int32_t route;       /* HS_JOIN_ROUTE_*; 0: no route of the mask holds this shape */
+    int32_t key_min;     /* DENSE: the key of slot 0 */
+    int64_t n_build;
+    int64_t slots;       /* DENSE: key slots; HASH / HASH_STR: table slots; GLOBAL: table_cap */
+    int64_t table_bytes; /* the one table allocation */
+    int64_t part[4];     /* byte offsets of the form's parts inside it */
+    int64_t ws_bytes;    /* the build's workspace */
+} hs_join_table;
+int hs_join_table_plan(const hs_col* build_key, const hs_col* probe_key, int64_t n_build, int64_t n_probe, int64_t key_lo,
+                       int64_t key_hi, uint32_t routes, hs_join_table* out);
+int hs_join_table_build(void* stream, const hs_join_table* t, const hs_col* build_key, void* table, void* ws, uint32_t* status,
+                        uint32_t* flags);
+int hs_join_table_count(void* stream, const hs_join_table* t, const hs_col* build_key, const hs_col* probe_key, int64_t n_probe,
+                        const void* table, int64_t* counts, void* aux);
+int hs_join_table_fill(void* stream, const hs_join_table* t, const hs_col* build_key, const hs_col* probe_key, int64_t n_probe,
+                       const void* table, const void* aux, const int64_t* out_start, int64_t* out_left, int64_t* out_right);
 /* Merge order of a multi-rank final aggregate (the reference reads a partition's shuffle files in block order,
  * tasks.py:117-133): STABLE sort of positions 0 .. n-1 by order[i] in [-1, n_order) (global block id; -1 = padding,
  * sorted first) with the radix tier's partition passes, least significant byte first.  out_perm[j] = position of the
@@ -1305,9 +1355,9 @@ void hs_select_stage_destroy(hs_select_stage* stage);
  * A JoinJob whose rows go to the result file (jobs.py:45-79; BroadcastHashJoinTask tasks.py:201-240, WriteToLocalFileTask
  * tasks.py:391-410): both tables through the native reader (only the named columns), a WHERE per side (hs_eval + hs_compact;
  * the lowering pushes every one-side conjunct to its side, which keeps the row order), the probe rows ordered by JoinJob -
- * hs_partition_ids / hs_partition_perm by hash(key) % n_parts, the fixed FNV-1a for strings - then the join: INTEGER keys
- * through hs_join_dense_* (key range <= 4 x build rows), else hs_join_hash_*, STRING keys through hs_join_hash_str_*, and
- * hs_join_build / count / fill when a window overflows or the size is not held; pairs ordered by partition, probe row, build
+ * hs_partition_ids / hs_partition_perm by hash(key) % n_parts, the fixed FNV-1a for strings - then the join in the form
+ * hs_join_table_plan picks among all four routes (dense or hashed INTEGER keys, hashed STRING keys, the global table when a
+ * window overflows or the size is not held: planned again without that route); pairs ordered by partition, probe row, build
  * row - the engine's order.  Every output column (either side, strings included) is gathered through the pair lists and held
  * on the host; hs_join_select_result_write_blockfile writes it as blocks of rows_per_block rows (no file for no rows).  The
  * output size depends on the data, so runs are not replayed: a second run recomputes the same rows.  HS_E_LIMIT: key columns
@@ -1330,10 +1380,6 @@ typedef struct hs_join_select_stage_plan {
     int32_t out_types[HS_FINISH_MAX_OUT];     /* BlockFile type code of every result column */
     char out_names[HS_FINISH_MAX_OUT][64];
 } hs_join_select_stage_plan;
-#define HS_JOIN_ROUTE_DENSE 1       /* hs_join_dense_* */
-#define HS_JOIN_ROUTE_HASH 2        /* hs_join_hash_* */
-#define HS_JOIN_ROUTE_HASH_STR 3    /* hs_join_hash_str_* */
-#define HS_JOIN_ROUTE_GLOBAL 4      /* hs_join_build / count / fill */
 int hs_join_select_stage_prepare(hs_engine* engine, hs_table* build, hs_table* probe, const hs_join_select_stage_plan* plan,
                                  size_t plan_bytes, hs_join_select_stage** out);
 int hs_join_select_stage_run(hs_join_select_stage* stage, void* stream, uint32_t* flags_out, int64_t* n_rows_out);

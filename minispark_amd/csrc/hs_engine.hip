@@ -2442,86 +2442,47 @@ struct JoinPairs {
 };
 
 int join_pairs(hipStream_t stream, const hs_col& bk, int64_t nb, const hs_col& pk, int64_t np, uint32_t* flags, JoinPairs& J) {
-    DevBuf counts, aux, scan_ws, rows32, lcount, table, ws, status;
+    DevBuf counts, aux, scan_ws, table, ws, status;
     if (!counts.alloc((size_t)np * 8) || !J.out_start.alloc((size_t)(np + 1) * 8) || !scan_ws.alloc(hs_scan_ws_bytes(np)) ||
-        !aux.alloc(hs_join_dense_aux_bytes(np)) || !rows32.alloc((size_t)nb * 4) || !lcount.alloc((size_t)nb * 4) || !status.alloc(4, true))
+        !aux.alloc(hs_join_dense_aux_bytes(np)) || !status.alloc(4, true))
         return HS_E_LAUNCH;
-    int rc = HS_OK;
-    int route = 0;
+    int32_t lohi[2] = {0, -1};  // the build keys' range, what the dense form is planned from
     if (bk.kind == HS_I32) {
         DevBuf mm;
-        int32_t lohi[2] = {0, 0};
         if (!mm.alloc(8)) return HS_E_LAUNCH;
-        rc = hs_minmax_i32(stream, (const int32_t*)bk.data, nb, (int32_t*)mm.p);
+        const int rc = hs_minmax_i32(stream, (const int32_t*)bk.data, nb, (int32_t*)mm.p);
         if (rc) return rc;
         if (hipMemcpyAsync(lohi, mm.p, 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
             return HS_E_LAUNCH;
-        // Device._join_indices_dense's rule: at most 32 slots per build row (+ 65 536) and 4 build rows per slot
-        const int64_t slots = (int64_t)lohi[1] - (int64_t)lohi[0] + 1;
-        const int64_t spread = 32 * nb + 65536;
-        const size_t dws = slots <= ((int64_t)1 << 29) && slots <= spread && slots * 4 >= nb ? hs_join_dense_ws_bytes(nb, slots) : 0;
-        if (dws) {
-            if (!table.alloc((size_t)slots * 4) || !ws.alloc(dws)) return HS_E_LAUNCH;
-            rc = hs_join_dense_build(stream, (const int32_t*)bk.data, nb, lohi[0], slots, (uint32_t*)table.p, (uint32_t*)rows32.p,
-                                     (uint32_t*)lcount.p, ws.p, flags);
-            if (!rc) rc = hs_join_dense_count(stream, (const int32_t*)pk.data, np, lohi[0], slots, (const uint32_t*)table.p,
-                                              (const uint32_t*)rows32.p, (const uint32_t*)lcount.p, (int64_t*)counts.p, aux.p);
-            if (rc) return rc;
-            route = HS_JOIN_ROUTE_DENSE;
-        } else if (hs_join_hash_slots(nb) > 0) {
-            if (!table.alloc((size_t)hs_join_hash_slots(nb) * 8) || !ws.alloc(hs_join_hash_ws_bytes(nb))) return HS_E_LAUNCH;
-            rc = hs_join_hash_build(stream, (const int32_t*)bk.data, nb, table.p, (uint32_t*)rows32.p, (uint32_t*)lcount.p, ws.p,
-                                    (uint32_t*)status.p, flags);
-            if (!rc) rc = hs_join_hash_count(stream, (const int32_t*)pk.data, np, nb, table.p, (const uint32_t*)rows32.p,
-                                             (const uint32_t*)lcount.p, (int64_t*)counts.p, aux.p);
-            if (rc) return rc;
-            route = HS_JOIN_ROUTE_HASH;
-        }
-    } else if (hs_join_hash_str_slots(nb) > 0) {
-        if (!table.alloc((size_t)hs_join_hash_str_slots(nb) * 8) || !ws.alloc(hs_join_hash_str_ws_bytes(nb))) return HS_E_LAUNCH;
-        rc = hs_join_hash_str_build(stream, &bk, nb, table.p, (uint32_t*)rows32.p, (uint32_t*)lcount.p, ws.p, (uint32_t*)status.p, flags);
-        if (!rc) rc = hs_join_hash_str_count(stream, &bk, &pk, np, nb, table.p, (const uint32_t*)rows32.p, (const uint32_t*)lcount.p,
-                                             (int64_t*)counts.p, aux.p);
-        if (rc) return rc;
-        route = HS_JOIN_ROUTE_HASH_STR;
     }
-    if (route) {
+    // plan, allocate, build, count - and once more without a route whose window overflowed (hs_join_table_plan owns the rule)
+    hs_join_table t{};
+    for (uint32_t routes = HS_JOIN_ROUTES_ALL;; routes &= ~HS_JOIN_ROUTE_BIT(t.route)) {
+        int rc = hs_join_table_plan(&bk, &pk, nb, np, lohi[0], lohi[1], routes, &t);
+        if (rc) return rc;
+        if (!t.route) {
+            hs_set_error("join_pairs: no join route left for %lld build rows", (long long)nb);
+            return HS_E_LIMIT;
+        }
+        if (!table.alloc((size_t)t.table_bytes) || !ws.alloc((size_t)t.ws_bytes)) return HS_E_LAUNCH;
+        rc = hs_join_table_build(stream, &t, &bk, table.p, ws.p, (uint32_t*)status.p, flags);
+        if (!rc) rc = hs_join_table_count(stream, &t, &bk, &pk, np, table.p, (int64_t*)counts.p, aux.p);
+        if (rc) return rc;
+        if (t.route == HS_JOIN_ROUTE_GLOBAL) break;
         uint32_t st = 0;
         if (hipMemcpyAsync(&st, status.p, 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
             return HS_E_LAUNCH;
-        if (st & HS_FLAG_DICT_FULL) route = 0;  // a window overflowed: the global table takes this build side
+        if (!(st & HS_FLAG_DICT_FULL)) break;
     }
-    if (route) {
-        rc = hs_exclusive_scan_i64(stream, (const int64_t*)counts.p, np, (int64_t*)J.out_start.p, scan_ws.p);
-        if (rc) return rc;
-        if (!read_i64(stream, (const int64_t*)J.out_start.p + np, J.n_out)) return HS_E_LAUNCH;
-        if (!J.out_left.alloc((size_t)(J.n_out > 0 ? J.n_out : 1) * 8) || !J.out_right.alloc((size_t)(J.n_out > 0 ? J.n_out : 1) * 8))
-            return HS_E_LAUNCH;
-        if (J.n_out > 0)
-            rc = hs_join_dense_fill(stream, np, (const uint32_t*)rows32.p, aux.p, (const int64_t*)J.out_start.p, (int64_t*)J.out_left.p,
-                                    (int64_t*)J.out_right.p);
-        J.route = route;
-        return rc;
-    }
-    // the global-memory table (tasks.py:201-240 as round 1 built it): any key kind and size
-    int64_t cap = 16;
-    while (cap < 2 * nb) cap *= 2;
-    DevBuf tkeys, treps, slot_start, rows64;
-    if (!tkeys.alloc((size_t)cap * 8) || !treps.alloc((size_t)cap * 8) || !slot_start.alloc((size_t)(cap + 1) * 8) ||
-        !rows64.alloc((size_t)nb * 8) || !ws.alloc(hs_join_build_ws_bytes(nb, cap)))
-        return HS_E_LAUNCH;
-    rc = hs_join_build(stream, &bk, nb, cap, (uint64_t*)tkeys.p, (int64_t*)treps.p, (int64_t*)slot_start.p, (int64_t*)rows64.p, ws.p, flags);
-    if (!rc) rc = hs_join_count(stream, &bk, &pk, np, cap, (const uint64_t*)tkeys.p, (const int64_t*)treps.p, (const int64_t*)slot_start.p,
-                                (int64_t*)counts.p);
-    if (!rc) rc = hs_exclusive_scan_i64(stream, (const int64_t*)counts.p, np, (int64_t*)J.out_start.p, scan_ws.p);
+    int rc = hs_exclusive_scan_i64(stream, (const int64_t*)counts.p, np, (int64_t*)J.out_start.p, scan_ws.p);
     if (rc) return rc;
     if (!read_i64(stream, (const int64_t*)J.out_start.p + np, J.n_out)) return HS_E_LAUNCH;
     if (!J.out_left.alloc((size_t)(J.n_out > 0 ? J.n_out : 1) * 8) || !J.out_right.alloc((size_t)(J.n_out > 0 ? J.n_out : 1) * 8))
         return HS_E_LAUNCH;
     if (J.n_out > 0)
-        rc = hs_join_fill(stream, &bk, &pk, np, cap, (const uint64_t*)tkeys.p, (const int64_t*)treps.p, (const int64_t*)slot_start.p,
-                          (const int64_t*)rows64.p, (const int64_t*)J.out_start.p, (int64_t*)J.out_left.p, (int64_t*)J.out_right.p);
-    J.route = HS_JOIN_ROUTE_GLOBAL;
+        rc = hs_join_table_fill(stream, &t, &bk, &pk, np, table.p, aux.p, (const int64_t*)J.out_start.p, (int64_t*)J.out_left.p,
+                                (int64_t*)J.out_right.p);
+    J.route = t.route;
     return rc;
 }
 

@@ -42,6 +42,7 @@ extern "C" size_t hs_sizeof(int32_t which) {
         case 12: return sizeof(hs_select_stage_plan);
         case 14: return sizeof(hs_join_select_stage_plan);
         case 15: return sizeof(hs_join_group_stage_plan);
+        case 16: return sizeof(hs_join_table);
         default: return 0;
     }
 }

@@ -11,6 +11,7 @@
 //   windows             hs_window, hs_window_agg, hs_window_nav, hs_window_frames over ob_sort's (partition, order) runs
 //   join builds         dense (hs_join_dense_*), keyset (hs_keyset_*: LEFT SEMI / ANTI), hashed (hs_join_hash_*) and STRING
 //                       (hs_join_hash_str_*): one partition or window per wave in LDS, jx_count / jx_scan / jx_place / jx_emit
+//   join table          hs_join_table_plan / build / count / fill: the routing rule and the table layout of the four join forms
 //
 // The HBM tier of GROUP BY as a radix partition + on-chip ordered fold (round 2):
 //
@@ -33,6 +34,7 @@
 // Everything is sized on the host from the row count and the largest unit; no host round trip inside
 // hs_group_radix_run.  A partition that meets more distinct keys than its dictionary holds raises HS_FLAG_DICT_FULL
 // (the caller takes the round-1 path).  Keys: INTEGER / TIMESTAMP (the key word is the value).
+#include <algorithm>
 #include <type_traits>
 #include <utility>
 #include "hs_device.h"
@@ -4688,4 +4690,122 @@ extern "C" int hs_join_hash_str_count(void* stream, const hs_col* build_key, con
     else hipLaunchKernelGGL(k_js_count<JH_L_LARGE>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, A);
     RX_CHECK_LAUNCH("hs_join_hash_str_count");
     return HS_OK;
+}
+
+// =====================================================================================================
+// The general inner join: one route planner and one table handle (include/hipspark.h hs_join_table_*)
+// =====================================================================================================
+// Host code only.  hs_join_table_plan owns the routing rule of the four forms and the layout of the form's arrays inside one
+// allocation; build / count / fill hand the planned parts to the form's own entry points.  A caller's fallback ladder is
+// "plan again without the route whose window overflowed".
+namespace {
+struct JtParts {
+    uint8_t* p[4];
+    JtParts(const hs_join_table& t, const void* table) {
+        for (int i = 0; i < 4; ++i) p[i] = (uint8_t*)const_cast<void*>(table) + t.part[i];
+    }
+    template <class T>
+    T* at(int i) const { return (T*)p[i]; }
+};
+
+bool jt_args(const char* who, const hs_join_table* t, const hs_col* build_key, const hs_col* probe_key, const void* table) {
+    if (t && build_key && probe_key && table && t->route >= HS_JOIN_ROUTE_DENSE && t->route <= HS_JOIN_ROUTE_GLOBAL) return true;
+    hs_set_error("%s: bad arguments (a planned table with a route)", who);
+    return false;
+}
+}  // namespace
+
+extern "C" int hs_join_table_plan(const hs_col* build_key, const hs_col* probe_key, int64_t n_build, int64_t n_probe, int64_t key_lo,
+                                  int64_t key_hi, uint32_t routes, hs_join_table* out) {
+    if (!build_key || !probe_key || !out || n_build < 0 || n_probe < 0) {
+        hs_set_error("hs_join_table_plan: bad arguments");
+        return HS_E_ARG;
+    }
+    const auto wants = [&](int route) { return (routes & HS_JOIN_ROUTE_BIT(route)) != 0; };
+    const bool rows = n_build > 0 && n_probe > 0;
+    const bool i32 = rows && build_key->kind == HS_I32 && probe_key->kind == HS_I32 &&
+                     !(((uintptr_t)build_key->data | (uintptr_t)probe_key->data) & 15);
+    hs_join_table t{};
+    t.n_build = n_build;
+    int64_t size[4] = {0, (int64_t)n_build * 4, (int64_t)n_build * 4, -1};  // bytes of every part (-1: no such part)
+    const int64_t range = key_hi - key_lo + 1;
+    if (wants(HS_JOIN_ROUTE_DENSE) && i32 && n_build < ((int64_t)1 << 31) && key_lo <= key_hi &&
+        range <= std::min<int64_t>((int64_t)1 << 29, 32 * n_build + 65536) && range * 4 >= n_build && hs_join_dense_ws_bytes(n_build, range)) {
+        t.route = HS_JOIN_ROUTE_DENSE;
+        t.key_min = (int32_t)key_lo;
+        t.slots = range;
+        t.ws_bytes = (int64_t)hs_join_dense_ws_bytes(n_build, range);
+        size[0] = range * 4;
+    } else if (wants(HS_JOIN_ROUTE_HASH) && i32 && hs_join_hash_slots(n_build) > 0) {
+        t.route = HS_JOIN_ROUTE_HASH;
+        t.slots = hs_join_hash_slots(n_build);
+        t.ws_bytes = (int64_t)hs_join_hash_ws_bytes(n_build);
+        size[0] = t.slots * 8;
+    } else if (wants(HS_JOIN_ROUTE_HASH_STR) && rows && build_key->kind == HS_STR && probe_key->kind == HS_STR &&
+               hs_join_hash_str_slots(n_build) > 0) {
+        t.route = HS_JOIN_ROUTE_HASH_STR;
+        t.slots = hs_join_hash_str_slots(n_build);
+        t.ws_bytes = (int64_t)hs_join_hash_str_ws_bytes(n_build);
+        size[0] = t.slots * 8;
+    } else if (wants(HS_JOIN_ROUTE_GLOBAL)) {
+        t.route = HS_JOIN_ROUTE_GLOBAL;
+        for (t.slots = 16; t.slots < 2 * n_build; t.slots *= 2) {}
+        t.ws_bytes = (int64_t)hs_join_build_ws_bytes(n_build, t.slots);
+        size[0] = size[1] = t.slots * 8;
+        size[2] = (t.slots + 1) * 8;
+        size[3] = (n_build > 0 ? n_build : 1) * 8;
+    }
+    for (int i = 0; i < 4 && t.route && size[i] >= 0; ++i) {
+        t.part[i] = t.table_bytes;
+        t.table_bytes = (t.table_bytes + size[i] + 64 + 255) & ~(int64_t)255;
+    }
+    *out = t;
+    return HS_OK;
+}
+
+extern "C" int hs_join_table_build(void* stream, const hs_join_table* t, const hs_col* build_key, void* table, void* ws, uint32_t* status,
+                                   uint32_t* flags) {
+    if (!jt_args("hs_join_table_build", t, build_key, build_key, table)) return HS_E_ARG;
+    const JtParts P(*t, table);
+    uint32_t *const rows = P.at<uint32_t>(1), *const list_count = P.at<uint32_t>(2);
+    switch (t->route) {
+        case HS_JOIN_ROUTE_DENSE:
+            return hs_join_dense_build(stream, (const int32_t*)build_key->data, t->n_build, t->key_min, t->slots, P.at<uint32_t>(0), rows,
+                                       list_count, ws, flags);
+        case HS_JOIN_ROUTE_HASH:
+            return hs_join_hash_build(stream, (const int32_t*)build_key->data, t->n_build, P.p[0], rows, list_count, ws, status, flags);
+        case HS_JOIN_ROUTE_HASH_STR:
+            return hs_join_hash_str_build(stream, build_key, t->n_build, P.p[0], rows, list_count, ws, status, flags);
+        default:
+            return hs_join_build(stream, build_key, t->n_build, t->slots, P.at<uint64_t>(0), P.at<int64_t>(1), P.at<int64_t>(2),
+                                 P.at<int64_t>(3), ws, flags);
+    }
+}
+
+extern "C" int hs_join_table_count(void* stream, const hs_join_table* t, const hs_col* build_key, const hs_col* probe_key, int64_t n_probe,
+                                   const void* table, int64_t* counts, void* aux) {
+    if (!jt_args("hs_join_table_count", t, build_key, probe_key, table)) return HS_E_ARG;
+    const JtParts P(*t, table);
+    const uint32_t *const rows = P.at<uint32_t>(1), *const list_count = P.at<uint32_t>(2);
+    switch (t->route) {
+        case HS_JOIN_ROUTE_DENSE:
+            return hs_join_dense_count(stream, (const int32_t*)probe_key->data, n_probe, t->key_min, t->slots, P.at<uint32_t>(0), rows,
+                                       list_count, counts, aux);
+        case HS_JOIN_ROUTE_HASH:
+            return hs_join_hash_count(stream, (const int32_t*)probe_key->data, n_probe, t->n_build, P.p[0], rows, list_count, counts, aux);
+        case HS_JOIN_ROUTE_HASH_STR:
+            return hs_join_hash_str_count(stream, build_key, probe_key, n_probe, t->n_build, P.p[0], rows, list_count, counts, aux);
+        default:
+            return hs_join_count(stream, build_key, probe_key, n_probe, t->slots, P.at<uint64_t>(0), P.at<int64_t>(1), P.at<int64_t>(2),
+                                 counts);
+    }
+}
+
+extern "C" int hs_join_table_fill(void* stream, const hs_join_table* t, const hs_col* build_key, const hs_col* probe_key, int64_t n_probe,
+                                  const void* table, const void* aux, const int64_t* out_start, int64_t* out_left, int64_t* out_right) {
+    if (!jt_args("hs_join_table_fill", t, build_key, probe_key, table)) return HS_E_ARG;
+    const JtParts P(*t, table);
+    if (t->route != HS_JOIN_ROUTE_GLOBAL) return hs_join_dense_fill(stream, n_probe, P.at<uint32_t>(1), aux, out_start, out_left, out_right);
+    return hs_join_fill(stream, build_key, probe_key, n_probe, t->slots, P.at<uint64_t>(0), P.at<int64_t>(1), P.at<int64_t>(2),
+                        P.at<int64_t>(3), out_start, out_left, out_right);
 }

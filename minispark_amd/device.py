@@ -303,6 +303,7 @@ class Device:
         torch.cuda.set_device(self.device)
         self.flags = torch.zeros(4, dtype=torch.int32, device=self.device)
         self.last_global_tier = ""  # "radix" / "hash": what the last HBM-tier partial aggregate ran on
+        self.dense_joins = self.hashed_joins = 0  # join_indices calls that took the dense CSR / the hashed windows
         self._partial_prepared: dict[Any, dict] = {}
         self._finish_prepared: dict[Any, dict] = {}
         self._join8_prepared: dict[Any, dict] = {}
@@ -2524,120 +2525,57 @@ class Device:
         return batch
 
     # ---- hash join (A8) --------------------------------------------------------------------------------
-    JOIN_DENSE_SPREAD = 32  # slots per build row at most (TPC-H order keys use 8 of every 32 values) ...
-    JOIN_DENSE_CROWD = 4    # ... and build rows per slot at most on average: a few hot keys would leave the assembly to single waves
+    def _join_table(self, build_key: DCol, probe_key: DCol, routes: int) -> tuple:
+        """The general join's table over ``build_key`` and its count pass over ``probe_key`` in the first form among ``routes``
+        (hs.join_route_mask) that hs_join_table_plan - the owner of the routing rule - gives this shape, planned again
+        without a route whose window overflowed (a degenerate key set) -> (table handle, counts, aux, what the fill reads:
+        the table's buffer and the two key descriptors)."""
+        n_build, n_probe = build_key.n, probe_key.n
+        bk, pk = build_key.as_hs(), probe_key.as_hs()
+        lo, hi = 0, -1  # the build keys' range: learnt where the dense form is asked for and hs_minmax_i32 reads the column
+        if routes & 1 << hs.JOIN_ROUTE_DENSE and build_key.kind == hs.I32 and n_build and n_probe and build_key.data.data_ptr() % 16 == 0:
+            lo, hi, _ = self.key_range(build_key)
+        t, status, counts = hs.hs_join_table(), None, None
+        while True:
+            hs.check(self._raw_lib.hs_join_table_plan(C.byref(bk), C.byref(pk), n_build, n_probe, lo, hi, routes, C.byref(t)),
+                     "hs_join_table_plan")
+            if not t.route:
+                raise DeviceError(f"no join route among {routes:#x} holds {n_build} build rows")
+            table, ws = self.workspace(t.table_bytes), self.workspace(t.ws_bytes)
+            windows = t.route in (hs.JOIN_ROUTE_HASH, hs.JOIN_ROUTE_HASH_STR)
+            if windows:
+                status = self.empty(1, torch.int32)  # a status word of this build's own: "a window overflowed" is not an error
+                status.zero_()
+            hs.check(self.lib.hs_join_table_build(self.stream, C.byref(t), C.byref(bk), table.data_ptr(), ws.data_ptr(),
+                                                  status.data_ptr() if windows else None, self.flags.data_ptr()),
+                     "hs_join_table_build")
+            if counts is None:  # (allocated behind the build's launch: the host's share runs while the GPU builds)
+                counts = self.empty(max(n_probe, 1), torch.int64)
+                aux = self.workspace(self.lib.hs_join_dense_aux_bytes(n_probe))
+            hs.check(self.lib.hs_join_table_count(self.stream, C.byref(t), C.byref(bk), C.byref(pk), n_probe, table.data_ptr(),
+                                                  counts.data_ptr(), aux.data_ptr()), "hs_join_table_count")
+            if not windows or not self.host_int(status) & hs.FLAG_DICT_FULL:
+                return t, counts, aux, (table, bk, pk)
+            routes &= ~(1 << t.route)
 
-    def _join_indices_dense(self, left_key: DCol, right_key: DCol) -> tuple | None:
-        """INTEGER keys over a dense range (round 4, hs_join_dense_*): the build rows are range-partitioned and assembled
-        into a CSR over key slots - no hash table, no global atomics; the probe reads two adjacent offsets per row.  None:
-        this shape keeps the hash-table join (other key kinds, a sparse or a crowded key range)."""
-        n_left, n_right = left_key.n, right_key.n
-        if (left_key.kind != hs.I32 or right_key.kind != hs.I32 or n_left == 0 or n_right == 0 or n_left >= 0xFFFFFFFF
-                or left_key.data.data_ptr() % 16 or right_key.data.data_ptr() % 16):
-            return None
-        lo, hi, _ = self.key_range(left_key)
-        slots = hi - lo + 1
-        if slots > min(1 << 29, self.JOIN_DENSE_SPREAD * n_left + 65536) or slots * self.JOIN_DENSE_CROWD < n_left or n_left >= 1 << 31:
-            return None
-        ws_bytes = int(self.lib.hs_join_dense_ws_bytes(n_left, slots))
-        if ws_bytes == 0:
-            return None
-        words = self.empty(slots, torch.int32)
-        rows = self.empty(n_left, torch.int32)
-        list_count = self.empty(n_left, torch.int32)
-        ws = self.workspace(ws_bytes)
-        hs.check(self.lib.hs_join_dense_build(self.stream, left_key.data.data_ptr(), n_left, lo, slots, words.data_ptr(),
-                                              rows.data_ptr(), list_count.data_ptr(), ws.data_ptr(), self.flags.data_ptr()),
-                 "hs_join_dense_build")
-        pairs = self._join_probe_pairs(n_right, rows, "hs_join_dense_count", lambda counts, aux: self.lib.hs_join_dense_count(
-            self.stream, right_key.data.data_ptr(), n_right, lo, slots, words.data_ptr(), rows.data_ptr(), list_count.data_ptr(), counts, aux))
-        self.last_join = {"mode": "dense csr", "slots": slots, "n_build": n_left}
-        self.dense_joins = getattr(self, "dense_joins", 0) + 1
-        return pairs
-
-    def _join_indices_hashed(self, left_key: DCol, right_key: DCol) -> tuple | None:
-        """Any INTEGER keys (round 4, hs_join_hash_*): the build rows are moved into the order of their hash windows and every
-        window of the {key, word} table is assembled in LDS - no global atomics; the probe reads one 8-byte slot per row in
-        the usual case and shares the dense form's second pass.  None: other key kinds, more than ~38 M build rows, or a
-        window that overflowed (a degenerate key set) - the hash table in global memory takes those."""
-        n_left, n_right = left_key.n, right_key.n
-        if (left_key.kind != hs.I32 or right_key.kind != hs.I32 or n_left == 0 or n_right == 0
-                or left_key.data.data_ptr() % 16 or right_key.data.data_ptr() % 16):
-            return None
-        slots = int(self.lib.hs_join_hash_slots(n_left))
-        if slots == 0:
-            return None
-        table = self.empty(slots, torch.int64)
-        rows = self.empty(n_left, torch.int32)
-        list_count = self.empty(n_left, torch.int32)
-        ws = self.workspace(int(self.lib.hs_join_hash_ws_bytes(n_left)))
-        overflowed = self.empty(1, torch.int32)  # a status word of this build's own: "a window overflowed" is not an error
-        overflowed.zero_()
-        hs.check(self.lib.hs_join_hash_build(self.stream, left_key.data.data_ptr(), n_left, table.data_ptr(), rows.data_ptr(),
-                                             list_count.data_ptr(), ws.data_ptr(), overflowed.data_ptr(), self.flags.data_ptr()),
-                 "hs_join_hash_build")
-        pairs = self._join_probe_pairs(n_right, rows, "hs_join_hash_count", lambda counts, aux: self.lib.hs_join_hash_count(
-            self.stream, right_key.data.data_ptr(), n_right, n_left, table.data_ptr(), rows.data_ptr(), list_count.data_ptr(), counts, aux),
-            overflowed)
-        if pairs is None:
-            return None
-        self.last_join = {"mode": "hashed windows", "slots": slots, "n_build": n_left}
-        self.hashed_joins = getattr(self, "hashed_joins", 0) + 1
-        return pairs
-
-    def _join_probe_pairs(self, n_right: int, rows: torch.Tensor, name: str, count, overflowed: torch.Tensor | None = None) -> tuple | None:
-        """The probe side of the dense and hashed joins after their build: count(counts_ptr, aux_ptr) launches the form's count
-        pass (`name`), then exclusive scan -> pair count on the host -> hs_join_dense_fill (both forms leave the dense form's
-        counts / aux).  None: the build's `overflowed` status word is set - checked after the host read, before the fill."""
-        counts = self.empty(max(n_right, 1), torch.int64)
-        aux = self.workspace(self.lib.hs_join_dense_aux_bytes(n_right))
-        hs.check(count(counts.data_ptr(), aux.data_ptr()), name)
+    def join_indices(self, left_key: DCol, right_key: DCol) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:
+        """Inner equi-join -> (left_rows, right_rows, out_start, n_out): pairs ordered by right row,
+        then by left row (the reference's emission order, tasks.py:224-240).  ``last_join`` names the form taken."""
+        n_right = right_key.n
+        t, counts, aux, (table, lk, rk) = self._join_table(
+            left_key, right_key, hs.join_route_mask(hs.JOIN_ROUTE_DENSE, hs.JOIN_ROUTE_HASH, hs.JOIN_ROUTE_GLOBAL))
         out_start = self.empty(n_right + 1, torch.int64)
         ws2 = self.workspace(self.lib.hs_scan_ws_bytes(n_right))
         hs.check(self.lib.hs_exclusive_scan_i64(self.stream, counts.data_ptr(), n_right, out_start.data_ptr(), ws2.data_ptr()),
                  "hs_exclusive_scan_i64")
         n_out = self.host_int(out_start[n_right])  # sizes the pair lists: the run is data-dependent (not replayable)
-        if overflowed is not None and int(overflowed.item()) != 0:  # (the stream is idle after the read above: this one costs no second wait)
-            return None
         out_left = self.empty(max(n_out, 1), torch.int64)
         out_right = self.empty(max(n_out, 1), torch.int64)
-        hs.check(self.lib.hs_join_dense_fill(self.stream, n_right, rows.data_ptr(), aux.data_ptr(), out_start.data_ptr(),
-                                             out_left.data_ptr(), out_right.data_ptr()), "hs_join_dense_fill")
-        return out_left, out_right, out_start, n_out
-
-    def join_indices(self, left_key: DCol, right_key: DCol) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:
-        """Inner equi-join -> (left_rows, right_rows, out_start, n_out): pairs ordered by right row,
-        then by left row (the reference's emission order, tasks.py:224-240)."""
-        n_left, n_right = left_key.n, right_key.n
-        dense = self._join_indices_dense(left_key, right_key) or self._join_indices_hashed(left_key, right_key)
-        if dense is not None:
-            return dense
-        self.last_join = {"mode": "global hash table", "n_build": n_left}
-        cap = 16
-        while cap < 2 * max(n_left, 1):
-            cap *= 2
-        tkeys = self.empty(cap, torch.int64)
-        treps = self.empty(cap, torch.int64)
-        slot_start = self.empty(cap + 1, torch.int64)
-        rows = self.empty(max(n_left, 1), torch.int64)
-        ws = self.workspace(self.lib.hs_join_build_ws_bytes(n_left, cap))
-        lk, rk = left_key.as_hs(), right_key.as_hs()
-        hs.check(self.lib.hs_join_build(self.stream, C.byref(lk), n_left, cap, tkeys.data_ptr(), treps.data_ptr(),
-                                        slot_start.data_ptr(), rows.data_ptr(), ws.data_ptr(), self.flags.data_ptr()),
-                 "hs_join_build")
-        counts = self.empty(max(n_right, 1), torch.int64)
-        hs.check(self.lib.hs_join_count(self.stream, C.byref(lk), C.byref(rk), n_right, cap, tkeys.data_ptr(),
-                                        treps.data_ptr(), slot_start.data_ptr(), counts.data_ptr()), "hs_join_count")
-        out_start = self.empty(n_right + 1, torch.int64)
-        ws2 = self.workspace(self.lib.hs_scan_ws_bytes(n_right))
-        hs.check(self.lib.hs_exclusive_scan_i64(self.stream, counts.data_ptr(), n_right, out_start.data_ptr(),
-                                                ws2.data_ptr()), "hs_exclusive_scan_i64")
-        n_out = self.host_int(out_start[n_right])  # sizes the pair lists: the run is data-dependent (not replayable)
-        out_left = self.empty(max(n_out, 1), torch.int64)
-        out_right = self.empty(max(n_out, 1), torch.int64)
-        hs.check(self.lib.hs_join_fill(self.stream, C.byref(lk), C.byref(rk), n_right, cap, tkeys.data_ptr(),
-                                       treps.data_ptr(), slot_start.data_ptr(), rows.data_ptr(), out_start.data_ptr(),
-                                       out_left.data_ptr(), out_right.data_ptr()), "hs_join_fill")
+        hs.check(self.lib.hs_join_table_fill(self.stream, C.byref(t), C.byref(lk), C.byref(rk), n_right, table.data_ptr(), aux.data_ptr(),
+                                             out_start.data_ptr(), out_left.data_ptr(), out_right.data_ptr()), "hs_join_table_fill")
+        self.last_join = {"mode": hs.JOIN_MODES[t.route], "slots": t.slots, "n_build": left_key.n}
+        self.dense_joins += t.route == hs.JOIN_ROUTE_DENSE
+        self.hashed_joins += t.route == hs.JOIN_ROUTE_HASH
         return out_left, out_right, out_start, n_out
 
     # ---- LEFT SEMI / LEFT ANTI join: membership of the left keys in the right side's key set (DESIGN.md 4.4j) -------------
@@ -2663,55 +2601,6 @@ class Device:
                                           1 if anti else 0, mask.data_ptr()), "hs_keyset_probe")
         return {"mode": "bitmap", "slots": slots, "n_build": n_right}
 
-    def _semi_mask_hashed(self, left_key: DCol, right_key: DCol, anti: bool, mask: torch.Tensor) -> dict | None:
-        """Any INTEGER keys: the hashed-window join's build over the right keys and its count pass over the left keys, whose
-        counts become the mask.  None: more right rows than the windows hold, or a window overflowed."""
-        n_left, n_right = left_key.n, right_key.n
-        slots = int(self.lib.hs_join_hash_slots(n_right))
-        if slots == 0:
-            return None
-        table = self.empty(slots, torch.int64)
-        rows = self.empty(n_right, torch.int32)
-        list_count = self.empty(n_right, torch.int32)
-        ws = self.workspace(int(self.lib.hs_join_hash_ws_bytes(n_right)))
-        overflowed = self.empty(1, torch.int32)
-        overflowed.zero_()
-        hs.check(self.lib.hs_join_hash_build(self.stream, right_key.data.data_ptr(), n_right, table.data_ptr(), rows.data_ptr(),
-                                             list_count.data_ptr(), ws.data_ptr(), overflowed.data_ptr(), self.flags.data_ptr()),
-                 "hs_join_hash_build")
-        counts = self.empty(n_left, torch.int64)
-        aux = self.workspace(self.lib.hs_join_dense_aux_bytes(n_left))
-        hs.check(self.lib.hs_join_hash_count(self.stream, left_key.data.data_ptr(), n_left, n_right, table.data_ptr(), rows.data_ptr(),
-                                             list_count.data_ptr(), counts.data_ptr(), aux.data_ptr()), "hs_join_hash_count")
-        if self.host_int(overflowed) != 0:
-            return None
-        hs.check(self.lib.hs_mask_from_counts(self.stream, counts.data_ptr(), n_left, 1 if anti else 0, mask.data_ptr()),
-                 "hs_mask_from_counts")
-        return {"mode": "hashed windows", "slots": slots, "n_build": n_right}
-
-    def _semi_mask_table(self, left_key: DCol, right_key: DCol, anti: bool, mask: torch.Tensor) -> dict:
-        """STRING / TIMESTAMP keys (and INTEGER keys the windows refused): the global hash table's build over the right keys
-        and its count pass over the left keys."""
-        n_left, n_right = left_key.n, right_key.n
-        cap = 16
-        while cap < 2 * max(n_right, 1):
-            cap *= 2
-        tkeys = self.empty(cap, torch.int64)
-        treps = self.empty(cap, torch.int64)
-        slot_start = self.empty(cap + 1, torch.int64)
-        rows = self.empty(max(n_right, 1), torch.int64)
-        ws = self.workspace(self.lib.hs_join_build_ws_bytes(n_right, cap))
-        bk, pk = right_key.as_hs(), left_key.as_hs()
-        hs.check(self.lib.hs_join_build(self.stream, C.byref(bk), n_right, cap, tkeys.data_ptr(), treps.data_ptr(),
-                                        slot_start.data_ptr(), rows.data_ptr(), ws.data_ptr(), self.flags.data_ptr()),
-                 "hs_join_build")
-        counts = self.empty(n_left, torch.int64)
-        hs.check(self.lib.hs_join_count(self.stream, C.byref(bk), C.byref(pk), n_left, cap, tkeys.data_ptr(),
-                                        treps.data_ptr(), slot_start.data_ptr(), counts.data_ptr()), "hs_join_count")
-        hs.check(self.lib.hs_mask_from_counts(self.stream, counts.data_ptr(), n_left, 1 if anti else 0, mask.data_ptr()),
-                 "hs_mask_from_counts")
-        return {"mode": "global hash table", "n_build": n_right}
-
     def semi_select(self, left_key: DCol, right_key: DCol, anti: bool) -> tuple[torch.Tensor, int]:
         """LEFT SEMI (``anti``: LEFT ANTI) join -> the ascending list of the left rows whose key occurs (does not occur) among
         the right keys, and their number (one D2H).  Keys of one kind, decoded: INTEGER keys over a range a bitmap holds take
@@ -2733,10 +2622,12 @@ class Device:
         mask = self.empty(n_left, torch.uint8)
         info = None
         if left_key.kind == hs.I32 and left_key.data.data_ptr() % 16 == 0 and right_key.data.data_ptr() % 16 == 0:
-            info = (self._semi_mask_bitmap(left_key, right_key, anti, mask)
-                    or self._semi_mask_hashed(left_key, right_key, anti, mask))
-        if info is None:
-            info = self._semi_mask_table(left_key, right_key, anti, mask)
+            info = self._semi_mask_bitmap(left_key, right_key, anti, mask)
+        if info is None:  # the general join's table over the right keys, stopped after its count pass over the left keys
+            t, counts, _, _ = self._join_table(right_key, left_key, hs.join_route_mask(hs.JOIN_ROUTE_HASH, hs.JOIN_ROUTE_GLOBAL))
+            hs.check(self.lib.hs_mask_from_counts(self.stream, counts.data_ptr(), n_left, 1 if anti else 0, mask.data_ptr()),
+                     "hs_mask_from_counts")
+            info = {"mode": hs.JOIN_MODES[t.route], "slots": t.slots, "n_build": n_right}
         self.last_semi_join = {**info, "n_probe": n_left, "anti": bool(anti)}
         sel = self.empty(n_left, torch.int64)
         count = self.empty(1, torch.int64)

@@ -218,7 +218,26 @@ class hs_join_stage_plan(C.Structure):
 
 HS_SELECT_STAGE_PLAN_VERSION = 1
 HS_JOIN_SELECT_STAGE_PLAN_VERSION = 1
-JOIN_ROUTES = {1: "dense", 2: "hashed", 3: "hashed-string", 4: "global"}  # HS_JOIN_ROUTE_*
+JOIN_ROUTE_DENSE, JOIN_ROUTE_HASH, JOIN_ROUTE_HASH_STR, JOIN_ROUTE_GLOBAL = 1, 2, 3, 4
+JOIN_ROUTES = {1: "dense", 2: "hashed", 3: "hashed-string", 4: "global"}  # HS_JOIN_ROUTE_*: the stages' stats ...
+JOIN_MODES = {1: "dense csr", 2: "hashed windows", 3: "hashed string windows", 4: "global hash table"}  # ... and Device.last_join["mode"]
+
+
+def join_route_mask(*routes: int) -> int:
+    """HS_JOIN_ROUTE_BIT of every route: what hs_join_table_plan takes."""
+    return sum(1 << r for r in routes)
+
+
+class hs_join_table(C.Structure):
+    _fields_ = [
+        ("route", C.c_int32),
+        ("key_min", C.c_int32),
+        ("n_build", C.c_int64),
+        ("slots", C.c_int64),
+        ("table_bytes", C.c_int64),
+        ("part", C.c_int64 * 4),
+        ("ws_bytes", C.c_int64),
+    ]
 
 
 class hs_select_stage_plan(C.Structure):
@@ -421,6 +440,10 @@ SIGNATURES: dict[str, tuple] = {
     "hs_join_hash_str_slots": (C.c_int64, [_I64]),
     "hs_join_hash_str_build": (C.c_int, [_P, _COLP, _I64, _P, _P, _P, _P, _P, _P]),
     "hs_join_hash_str_count": (C.c_int, [_P, _COLP, _COLP, _I64, _I64, _P, _P, _P, _P, _P]),
+    "hs_join_table_plan": (C.c_int, [_COLP, _COLP, _I64, _I64, _I64, _I64, C.c_uint32, C.POINTER(hs_join_table)]),
+    "hs_join_table_build": (C.c_int, [_P, C.POINTER(hs_join_table), _COLP, _P, _P, _P, _P]),
+    "hs_join_table_count": (C.c_int, [_P, C.POINTER(hs_join_table), _COLP, _COLP, _I64, _P, _P, _P]),
+    "hs_join_table_fill": (C.c_int, [_P, C.POINTER(hs_join_table), _COLP, _COLP, _I64, _P, _P, _P, _P, _P]),
     "hs_remap_u8": (C.c_int, [_P, _P, _I64, _P, _P]),
     "hs_dict_build": (C.c_int, [_P, _COLP, _I64, _I32, _P, _P, _P, _P]),
     "hs_dict_assign": (C.c_int, [_P, _COLP, _I64, _I32, _P, _P, _P, _P, _P]),

@@ -42,6 +42,7 @@ def test_struct_layouts_match_the_header():
     for which, mirror in enumerate(mirrors):
         assert lib.hs_sizeof(which) == C.sizeof(mirror), mirror.__name__
     assert lib.hs_sizeof(len(mirrors)) == 0
+    assert lib.hs_sizeof(16) == C.sizeof(hs.hs_join_table) == 72
 
 
 def test_bad_arguments_are_refused_without_a_gpu():
@@ -90,6 +91,70 @@ def test_join_table_geometries_without_a_gpu():
     assert lib.hs_join_dense_ws_bytes(1000, 1 << 29) > 0
     assert lib.hs_join_dense_ws_bytes(1000, (1 << 29) + 1) == 0
     assert lib.hs_join_dense_aux_bytes(5) == 8 * 2 * 4 + 64
+
+
+def _join_route_rule(lib, bkind, pkind, n_build, n_probe, lo, hi, aligned, routes):
+    """The general join's routing rule as include/hipspark.h states it: the first of DENSE, HASH, HASH_STR, GLOBAL that is in
+    the mask and holds the shape (0: none)."""
+    rows = n_build > 0 and n_probe > 0
+    i32 = rows and bkind == pkind == hs.I32 and aligned
+    slots = hi - lo + 1
+    if (routes & 1 << hs.JOIN_ROUTE_DENSE and i32 and n_build < 1 << 31 and lo <= hi and slots <= min(1 << 29, 32 * n_build + 65536)
+            and slots * 4 >= n_build and lib.hs_join_dense_ws_bytes(n_build, slots) != 0):
+        return hs.JOIN_ROUTE_DENSE
+    if routes & 1 << hs.JOIN_ROUTE_HASH and i32 and lib.hs_join_hash_slots(n_build) > 0:
+        return hs.JOIN_ROUTE_HASH
+    if routes & 1 << hs.JOIN_ROUTE_HASH_STR and rows and bkind == pkind == hs.STR and lib.hs_join_hash_str_slots(n_build) > 0:
+        return hs.JOIN_ROUTE_HASH_STR
+    return hs.JOIN_ROUTE_GLOBAL if routes & 1 << hs.JOIN_ROUTE_GLOBAL else 0
+
+
+def test_join_table_plan_follows_the_routing_rule_without_a_gpu():
+    """hs_join_table_plan against the rule above over key kinds, build / probe sizes on both sides of what the windows hold,
+    key ranges on both sides of every boundary of the dense form, an unaligned key column and every subset of the route mask
+    (fake addresses: the planner dereferences nothing); and the planned table: parts that do not overlap, lie inside
+    table_bytes, start 256-byte aligned with 64 bytes of slack behind them and are as large as their form documents."""
+    lib = hs.load_library()
+    seen = set()
+    for bkind, pkind in [(hs.I32, hs.I32), (hs.I64, hs.I64), (hs.STR, hs.STR), (hs.I32, hs.I64)]:
+        for n_build in (0, 1, 1000, 38_000_000, 40_000_000):
+            spread, crowd = 32 * n_build + 65536, -(-n_build // 4)
+            ranges = [(0, spread - 1), (0, spread), (-7, crowd - 8), (-7, crowd - 9), (-(1 << 31), -(1 << 31) + (1 << 29) - 1),
+                      (0, 1 << 29), (5, 4), (3, 3)]
+            for n_probe in (0, 5):
+                for baddr, paddr in [(0x10000, 0x20000), (0x10004, 0x20000), (0x10000, 0x20008)]:
+                    bcol, pcol = hs.hs_col(bkind, -1, baddr, None, None), hs.hs_col(pkind, -1, paddr, None, None)
+                    for lo, hi in ranges:
+                        for routes in range(0, 32, 2):
+                            t = hs.hs_join_table()
+                            assert lib.hs_join_table_plan(C.byref(bcol), C.byref(pcol), n_build, n_probe, lo, hi, routes, C.byref(t)) == 0
+                            aligned = baddr % 16 == 0 and paddr % 16 == 0
+                            case = (bkind, pkind, n_build, n_probe, lo, hi, aligned, routes)
+                            assert t.route == _join_route_rule(lib, *case), case
+                            seen.add(t.route)
+                            if t.route == 0:
+                                continue
+                            n = n_build
+                            if t.route == hs.JOIN_ROUTE_DENSE:
+                                assert (t.key_min, t.slots, t.ws_bytes) == (lo, hi - lo + 1, lib.hs_join_dense_ws_bytes(n, hi - lo + 1)), case
+                                sizes = [t.slots * 4, n * 4, n * 4]
+                            elif t.route == hs.JOIN_ROUTE_HASH:
+                                assert (t.slots, t.ws_bytes) == (lib.hs_join_hash_slots(n), lib.hs_join_hash_ws_bytes(n)), case
+                                sizes = [t.slots * 8, n * 4, n * 4]
+                            elif t.route == hs.JOIN_ROUTE_HASH_STR:
+                                assert (t.slots, t.ws_bytes) == (lib.hs_join_hash_str_slots(n), lib.hs_join_hash_str_ws_bytes(n)), case
+                                sizes = [t.slots * 8, n * 4, n * 4]
+                            else:
+                                cap = max(16, 1 << (2 * max(n, 1) - 1).bit_length())
+                                assert (t.slots, t.ws_bytes) == (cap, lib.hs_join_build_ws_bytes(n, cap)), case
+                                sizes = [cap * 8, cap * 8, (cap + 1) * 8, max(n, 1) * 8]
+                            assert t.n_build == n and t.part[0] == 0
+                            ends = [t.part[i] for i in range(1, len(sizes))] + [t.table_bytes]
+                            for i, size in enumerate(sizes):
+                                assert t.part[i] % 256 == 0 and t.part[i] + size + 64 <= ends[i], (case, i)
+    assert seen == {0, 1, 2, 3, 4}
+    t = hs.hs_join_table()
+    assert lib.hs_join_table_plan(None, None, 1, 1, 0, 0, 30, C.byref(t)) == 1 and b"bad arguments" in lib.hs_last_error()
 
 
 def test_jit_translates_and_compiles_q1_for_gfx950():
