@@ -1,6 +1,7 @@
 """The shared-dictionary aggregation tier (tens to thousands of groups per unit; LDS atomics) against the oracle.
-Additions of a group happen in hardware order there, so FLOAT results may differ from the reference's sequential
-sums at an f32 rounding boundary: at most one ulp, and rarely (the test bounds the number of such values)."""
+Additions of a group happen in hardware order there, so FLOAT SUM / AVG results may differ from the reference's sequential
+sums at an f32 rounding boundary: at most one ulp, and rarely (the test bounds the number of such values).  MIN, MAX, COUNT
+and every INTEGER column do not depend on the order and are compared exactly."""
 
 from __future__ import annotations
 
@@ -23,6 +24,26 @@ def engine():
 
     with HipExecutionEngine(0) as e:
         yield e
+
+
+def _assert_match(got, want, loose):
+    """assert_rows_match with the one-ulp allowance, then every column outside `loose` (the FLOAT SUM / AVG columns) exactly,
+    row by row under the group key (the first column).  -> the number of values an ulp apart"""
+    flips = assert_rows_match(got, want, max_ulps=1)
+    if not want:  # (a filter that keeps no row: the row counts already agree)
+        return flips
+    key = next(iter(want[0]))
+    by_key = {row[key]: row for row in want}
+    assert len(by_key) == len(want)
+    for row in got:
+        for name, value in row.items():
+            if name not in loose:
+                other = by_key[row[key]][name]
+                assert type(value) is type(other) and value == other, f"{key}={row[key]!r} {name}: {value!r} != {other!r}"
+    return flips
+
+
+LOOSE = {"int key, 1400 groups": {"sf", "av"}, "long string key, 400 groups, filtered": {"x"}, "computed int key": {"sf"}}
 
 
 def _table(path, n, blocks, seed):
@@ -71,7 +92,7 @@ def test_many_group_queries_match_the_oracle(engine, tmp_path):
         want = run_query(oracle[name].task)
         for _run in range(2):
             got = ours[name].collect()
-            flips = assert_rows_match(got, want, max_ulps=1)
+            flips = _assert_match(got, want, LOOSE[name])
             assert flips <= 3, f"{name}: {flips} values moved across an f32 rounding boundary"
         assert engine.dev.last_scan["tier"] == "shared", name
         assert engine.dev.last_scan["wg_threads"] == 1024
@@ -101,7 +122,7 @@ def test_the_interpreter_kernels_of_the_shared_tier_match_the_oracle(tmp_path):
             for name in ours:
                 want = run_query(oracle[name].task)
                 for _run in range(2):
-                    assert assert_rows_match(ours[name].collect(), want, max_ulps=1) <= 3, name
+                    assert _assert_match(ours[name].collect(), want, LOOSE[name]) <= 3, name
                 assert e.dev.last_scan["tier"] == "shared", name
             e.dev.lib.hs_jit_stats(stats)
             assert stats[1] == launches_before, "no compiled program may have run"
@@ -167,6 +188,11 @@ def _wide_table(path, n, blocks, seed):
 
 
 def _wide_query(rng: random.Random, api, path):
+    return _wide_query_and_loose(rng, api, path)[0]
+
+
+def _wide_query_and_loose(rng: random.Random, api, path):
+    """-> (the query, the names of its FLOAT SUM / AVG columns)"""
     C, F, Lit = api.Col, api.F, api.Lit
     df = api.DataFrame().table(path)
     if rng.random() < 0.5:
@@ -178,10 +204,12 @@ def _wide_query(rng: random.Random, api, path):
         df = df.select((C("u") + "/" + C("u")).alias("hu"), C("f"), C("g"), C("i"))
     pool = [lambda: F.sum(C("f")), lambda: F.sum(C("i")), lambda: F.min(C("f")), lambda: F.max(C("i")), lambda: F.avg(C("g")),
             lambda: F.sum(C("f") * (Lit(1) - C("g"))), lambda: F.min(C("i")), lambda: F.max(C("g"))]
-    aggs = [fn().alias(f"a{n}") for n, fn in enumerate(rng.sample(pool, rng.randint(1, 4)))]
+    picked = rng.sample(range(len(pool)), rng.randint(1, 4))  # (the same draws as a sample of the pool itself)
+    aggs = [pool[p]().alias(f"a{n}") for n, p in enumerate(picked)]
     if rng.random() < 0.7:
         aggs.append(F.count())
-    return df.group_by(C(key)).agg(*aggs)
+    loose = {f"a{n}" for n, p in enumerate(picked) if p in (0, 4, 5)}  # FLOAT SUM / AVG: the order of additions shows
+    return df.group_by(C(key)).agg(*aggs), loose
 
 
 _WIDE_FIRST = int(__import__("os").environ.get("HIPSPARK_WIDE_FIRST", "0"))
@@ -201,9 +229,9 @@ def test_random_many_group_queries_match_the_oracle(engine, tmp_path, seed):
     path = tmp_path / "w.bin"
     _wide_table(path, rng.choice([5_000, 20_000, 50_000]), rng.choice([1, 3, 7]), seed)
     want = run_query(_wide_query(random.Random(seed), api_namespace(lambda: DataFrame(object()), Col, Functions, Lit), str(path)).task)
-    frame = _wide_query(random.Random(seed), api_namespace(lambda: DataFrame(engine), Col, Functions, Lit), str(path))
+    frame, loose = _wide_query_and_loose(random.Random(seed), api_namespace(lambda: DataFrame(engine), Col, Functions, Lit), str(path))
     for _ in range(2):
-        flips = assert_rows_match(frame.collect(), want, max_ulps=1)
+        flips = _assert_match(frame.collect(), want, loose)
         assert flips <= 3
 
 
@@ -243,7 +271,7 @@ def test_final_merge_tier_follows_the_real_number_of_partial_rows(tmp_path, grou
     with HipExecutionEngine(0) as engine:
         frame = build(engine)
         for _ in range(5):
-            flips = assert_rows_match(frame.collect(), want, max_ulps=1)
+            flips = _assert_match(frame.collect(), want, {"s"})
             assert flips <= 3
         assert engine.dev.last_scan["tier"] == "shared"
         assert bool(engine._global_merge) != on_chip
